@@ -12,6 +12,10 @@ the same one tests/test_gpu_prove.py feeds to the independent verifier.
 
 Multi-GPU (--gpus N under torch.distributed.run): each rank proves independent statements on its own GPU
 (weak scaling, no data-path collective); value = total proofs / max-over-ranks time.
+
+A plain run sets up, warms up, times --steps steps and prints the headline; --full adds every secondary figure (rooflines,
+one proof at a time, the other size classes, the 2^26 commit, the PCIe-inclusive rate, the CPU baseline, the multi-rank
+probes).  --dump-outputs DIR writes the proofs of the last timed step for output-for-output comparison of two builds.
 """
 import argparse
 import json
@@ -591,7 +595,7 @@ def commit_workload(args, rank, local_rank, world, dist, torch):
 
     for _ in range(max(args.warmup, 1)):
         commit()
-    ctx.profile(True)
+    ctx.profile(args.full)  # hipEvent pairs around the launches: the roofline / per-stage figures of --full
     ctx.profile_reset()
     barrier()
     t0 = time.perf_counter()
@@ -601,6 +605,8 @@ def commit_workload(args, rank, local_rank, world, dist, torch):
     dt = max_over_ranks(time.perf_counter() - t0, dist, None if one_gpu else f"cuda:{local_rank}")
     prof = ctx.profile_read()
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, [("root", bytes(root))])
         emit_commit_line(args, world, m, dt, prof, bytes(root).hex(),
                          ("host-transport (gloo) all-gather of leaf digests, single-GPU development mode" if one_gpu else
                           "RCCL all-gather of leaf digests") + " behind the C ABI (pk_commit_into)")
@@ -611,23 +617,27 @@ def commit_workload(args, rank, local_rank, world, dist, torch):
 def emit_commit_line(args, world, m, dt, prof, root_hex, how):
     n, rows = 1 << m, 1 << (m + 1 - 4)
     alg_bytes = 32 * 2 * n + 32 * 2 * 2 * n + 64 * rows  # coeffs read + leaves written + digests
-    n_l, ms_l = prof.get("leaf_hash", (1, 0.0))
-    avg_ms = ms_l / max(n_l, 1)
-    lh_bytes = (rows // world) * 33 * 32
-    achieved = lh_bytes / (avg_ms * 1e-3) / 1e9 if avg_ms else 0.0
-    emit({
+    line = {
         "metric": "commits/sec (2^m-coefficient batch-2 WHIR commit: RS-encode NTT + Skyscraper Merkle)",
         "value": args.steps / dt, "unit": "commits/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
         "ms_per_step": 1e3 * dt / args.steps, "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
         "dtype": "u32x8 (BN254-Fr, 256-bit Montgomery integers)", "data": "synthetic",
         "config": {"workload": f"synthetic WHIR commit: batch 2, n={m}, rate 1/2, fold 16, sharded by leaf index over {world} GPU(s), {how}",
                    "root": root_hex},
-        "commit_GBps_algorithmic": alg_bytes / (dt / args.steps) / 1e9,
-        "roofline": {"kernel": "leaf_hash_kernel", "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": achieved / HBM_PEAK_GBS, "traffic": None, "avg_launch_ms": avg_ms,
-                     "algorithmic_bytes_per_launch": lh_bytes},
-        "stage_ms_per_step": {k: round(v[1] / args.steps, 4) for k, v in sorted(prof.items(), key=lambda kv: -kv[1][1])},
-    })
+    }
+    if args.full:  # the per-launch figures of the events recorded in the timed region
+        n_l, ms_l = prof.get("leaf_hash", (1, 0.0))
+        avg_ms = ms_l / max(n_l, 1)
+        lh_bytes = (rows // world) * 33 * 32
+        achieved = lh_bytes / (avg_ms * 1e-3) / 1e9 if avg_ms else 0.0
+        line.update({
+            "commit_GBps_algorithmic": alg_bytes / (dt / args.steps) / 1e9,
+            "roofline": {"kernel": "leaf_hash_kernel", "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                         "frac": achieved / HBM_PEAK_GBS, "traffic": None, "avg_launch_ms": avg_ms,
+                         "algorithmic_bytes_per_launch": lh_bytes},
+            "stage_ms_per_step": {k: round(v[1] / args.steps, 4) for k, v in sorted(prof.items(), key=lambda kv: -kv[1][1])},
+        })
+    emit(line)
 
 
 def self_launch(args):
@@ -682,6 +692,22 @@ def emit(line):
     print(json.dumps(line), flush=True)
 
 
+DUMP_LIMIT_BYTES = 64 * 10**6
+
+
+def dump_outputs(out_dir, named_bytes):
+    """--dump-outputs: every (name, bytes) as DIR/<name>.npy, one float32 per byte (exact), in the given order while the files fit
+    DUMP_LIMIT_BYTES -- a fixed prefix of the list, so two runs with the same arguments write the same files"""
+    os.makedirs(out_dir, exist_ok=True)
+    used = 0
+    for name, raw in named_bytes:
+        a = np.frombuffer(bytes(raw), dtype=np.uint8).astype(np.float32)
+        if used + a.nbytes + 128 > DUMP_LIMIT_BYTES:  # 128: the .npy header
+            break
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+        used += a.nbytes + 128
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -718,13 +744,22 @@ def main():
     ap.add_argument("--concurrency", type=int, default=20,
                     help="provers per GPU, each with its own context/stream/arena (host transcript work of one proof overlaps "
                          "the kernels of another); 1 = strictly one proof at a time.  20 with sleeping host threads is the measured optimum on one "
-                         "MI355X (profiles/r05_wait_ab.jsonl: 16 spinning 260.7, 16 blocking 262.6, 20 blocking 266.8 proofs/s on one box; polling = blocking + 1 %)")
+                         "MI355X (profiles/r05_wait_ab.jsonl: 16 spinning 260.7, 16 blocking 262.6, 20 blocking 266.8 proofs/s on one box; polling = blocking + 1 %%)")
     ap.add_argument("--sharded", action="store_true",
                     help="prove workload, latency mode (BASELINE configs[3]): ONE proof at a time sharded over all ranks -- every large "
                          "commit split by leaf index with an RCCL all-gather of leaf digests behind the C ABI; strong scaling")
     ap.add_argument("--h2d", action="store_true",
                     help="upload the witness from (pageable) host memory before every proof: the PCIe-inclusive rate DESIGN.md quotes; "
                          "never the judged line (inputs are resident when the clock starts)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline figure: the one-proof-at-a-time and isolated-kernel passes (roofline, single_stream), "
+                         "the size classes, the 2^26 commit, the PCIe-inclusive rate, the CPU baseline, the library's communicator probe and, "
+                         "under several ranks, the sharded figures.  The --no-* switches above trim a --full run.  Without it a run sets up, "
+                         "warms up, times --steps steps and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32): prove = the proof "
+                         "strings of its proofs (proof_000.npy, ... one value per byte, in seed order, as many as fit 64 MB), commit = "
+                         "the Merkle root (root.npy).  Inputs and keys are seeded: the same arguments give the same files")
     args = ap.parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return self_launch(args)
@@ -851,13 +886,13 @@ def main():
     # just spent seconds at its power limit and this process still holds queues on it.  Under several ranks they stay at the end (rank 0 would keep the
     # others waiting inside the communicator probe's watchdog).
     size_figs = {}
-    if os.environ.get("PK_BENCH_SIZE_CLASSES_LAST") != "1" and rank == 0 and m == 21 and not args.sharded and args.size_classes and world == 1:
+    if args.full and os.environ.get("PK_BENCH_SIZE_CLASSES_LAST") != "1" and rank == 0 and m == 21 and not args.sharded and args.size_classes and world == 1:
         size_figs = run_size_classes()
     # The one-proof-at-a-time figures of a process that will run its provers' threads in blocking-wait mode are taken by a FRESH process in
     # the default spinning mode, and FIRST, before this process creates a prover (a second process on a GPU where another holds two dozen idle
     # hardware queues runs ~3.5 % slower -- measured: 9.9 against 9.6 ms per proof)
     ss = None
-    if block_wait and rank == 0 and not args.sharded:
+    if args.full and block_wait and rank == 0 and not args.sharded:
         try:
             import subprocess
 
@@ -898,17 +933,23 @@ def main():
             transports.append(join_device_set(c, rank, world, dist, "host" if one_gpu else "rccl"))
         srank = 0 if args.sharded else rank  # the ranks of a sharded prover hold the SAME statement and witness
         r1cs_w, mats, interner, nc, n_in = synth_r1cs(c, m_0, n_wit, seed=1234 + srank)
-        d_z, z_host = satisfying_witness(c, r1cs_w, n_wit, nc, n_in, 99 + srank + 1000 * w)
+        # one witness per rank, each prover with its own copy: a proof is then a function of its seed alone, whichever prover the
+        # dynamic hand-out gives it to, so what --dump-outputs writes is the same from run to run
+        if w == 0:
+            d_z, z_host = satisfying_witness(c, r1cs_w, n_wit, nc, n_in, 99 + srank)
+        else:
+            d_z = c.upload(z_host)
         if os.environ.get("PK_BENCH_LATENCY_ALL") == "1":  # experiment: every prover in latency mode while they share the chip
             c.set_latency_mode(True)
         workers.append((c, WhirR1CSScheme(c, r1cs_w, m, m_0, cfg_w, cfg_b), d_z, r1cs_w, z_host))
     ctx = workers[0][0]
-    mats0, interner0 = mats, interner  # every prover of a rank proves the same statement (one seed), each with its own witness
+    mats0, interner0 = mats, interner  # every prover of a rank proves the same statement (one seed) and witness
 
-    def run_proofs(first_seed, count):
+    def run_proofs(first_seed, count, keep=None):
         """`count` proofs through the `conc` provers of this GPU.  Work is handed out dynamically (each prover thread takes the
         next proof when it finishes one), so the chip stays full until the last wave whatever the count; ctypes releases the
-        GIL inside pk_prove.  Seeds are injected (test hook) only to make runs comparable; production passes none."""
+        GIL inside pk_prove.  Seeds are injected (test hook) only to make runs comparable; production passes none.
+        keep: a dict that receives the proof strings of the last `conc` proofs (the last step), by position in the step."""
         import itertools
 
         nxt = itertools.count()
@@ -923,7 +964,10 @@ def main():
                     return
                 if args.h2d:
                     c.upload_into(d_z.ptr, z_host)
-                prover.prove_nocopy(d_z, seed=first_seed + i)
+                if keep is not None and i >= count - conc:
+                    keep[i - (count - conc)] = prover.prove(d_z, seed=first_seed + i)
+                else:
+                    prover.prove_nocopy(d_z, seed=first_seed + i)
 
         ths = [threading.Thread(target=work, args=(w,)) for w in range(conc)]
         for t in ths:
@@ -941,7 +985,7 @@ def main():
     # collective figures and nothing else)
     groups, hung = {}, False
     rccl_fig = None
-    if not args.sharded:
+    if args.full and not args.sharded:
         box = {}
 
         def probe():
@@ -971,25 +1015,28 @@ def main():
     # hipEvent pairs around the launches of ONE of the `conc` provers (worker 0) during the timed region: the source of the
     # *_under_load figures.  PK_BENCH_NO_TIMED_PROFILE=1 turns it off for an A/B (profiles/r05_timed_profile_ab.json: no
     # measurable difference)
-    timed_profile = os.environ.get("PK_BENCH_NO_TIMED_PROFILE") != "1"
+    timed_profile = args.full and os.environ.get("PK_BENCH_NO_TIMED_PROFILE") != "1"
     ctx.profile(timed_profile)
     ctx.profile_reset()
+    last_step = {} if args.dump_outputs else None
     barrier()
     cpu0 = time.process_time()  # CPU seconds of every thread of this process: what the provers' host side costs (transcript, launches, waiting)
     t0 = time.perf_counter()
-    run_proofs(1, args.steps * conc)
+    run_proofs(1, args.steps * conc, last_step)
     barrier()
     own_dt = time.perf_counter() - t0
     host_cpu_ms_per_proof = 1e3 * (time.process_time() - cpu0) / (args.steps * conc)
     host_cores_busy = (time.process_time() - cpu0) / own_dt
     dt = max_over_ranks(own_dt, dist, None if one_gpu else f"cuda:{local_rank}")
     prof = ctx.profile_read()
+    if last_step is not None and rank == 0:
+        dump_outputs(args.dump_outputs, [(f"proof_{k:03d}", last_step[k]) for k in sorted(last_step)])
     throughput_wait(False)
     # One proof at a time on an otherwise idle chip: isolated kernel durations for the roofline, the single-stream figures, the multiplier peak.
     # Spinning waits here: the polling mode of the many-prover phases is the library's own loop and was switched off above.  (With
     # --host-wait block -- a mode of the runtime, fixed for the life of the process -- these figures were taken at the start by a FRESH process in
     # spinning mode, `ss` above: a blocked thread wakes ~20 us after its kernel, 65 times per proof, no part of a single prover's latency.)
-    if ss is None and (rank == 0 or not block_wait):
+    if args.full and ss is None and (rank == 0 or not block_wait):
         ss = single_stream_figures(torch, ctx, workers[0][1], workers[0][2], not args.no_latency_pass, args.sharded)
         ss["how"] = "this process, after the timed region, spinning waits" + (" -- NO: blocking-wait mode, a single prover pays ~20 us per synchronisation for it" if block_wait else "")
     if ss is None:
@@ -1000,7 +1047,7 @@ def main():
     # (b) BASELINE configs[4]: the 2^26 commit -- on one GPU, and under several ranks SHARDED over the first G = 1, 2, 4, 8 <= N of them
     # in the same invocation, so that one `--gpus N` run yields north_star's whole strong-scaling curve
     def run_commit_probe():
-        if not (m == 21 and not args.sharded and not args.no_commit_probe):
+        if not (args.full and m == 21 and not args.sharded and not args.no_commit_probe):
             return None
         try:
             if world == 1:
@@ -1037,7 +1084,7 @@ def main():
     # (a) PCIe-inclusive rate: the same waves with the witness uploaded before every proof.  On one GPU it runs LAST, so that it cannot disturb
     # the figures above (see --size-class-probe: probes run back to back in one process were measured to depress whichever comes later)
     def run_h2d_probe():
-        if args.h2d or args.sharded or args.no_h2d_probe:
+        if not args.full or args.h2d or args.sharded or args.no_h2d_probe:
             return None
         try:
             args.h2d = True
@@ -1063,7 +1110,7 @@ def main():
     if world > 1 and not comm_ok:
         h2d_rate = run_h2d_probe()  # torch's collectives only
         commit_fig = {"error": "skipped: the library's communicator did not pass its probe on every rank (see `rccl`)"}
-    elif world > 1:
+    elif world > 1 and args.full:
         h2d_rate = run_h2d_probe()
         time.sleep(2.0)  # idle seconds after 16 provers at the power limit (see --size-class-probe)
         box = {}
@@ -1086,16 +1133,16 @@ def main():
         commit_fig = {"error": "the sharded commit / proof did not return within its limit on some rank; skipped"} if hung_any else box.get("fig")
         sharded_fig = None if hung_any else box.get("sharded")
     else:
-        commit_fig = run_commit_probe()
+        commit_fig = run_commit_probe()  # None without --full
     if world == 1:
         h2d_rate = run_h2d_probe()
     # Everything that needs this process's provers is done.  The CPU leg will want a GPU proof to compare bytes with: take it now, then release
     # the provers -- a fresh process on a GPU where another holds two dozen idle hardware queues measures ~3.5 % low (9.9 against 9.6 ms per proof)
     cpu_seed, gpu_proof, ds0, z0 = (4242).to_bytes(32, "little"), None, workers[0][1].domain_separator, workers[0][4]
-    if rank == 0 and not args.no_cpu_baseline and world == 1:
+    if args.full and rank == 0 and not args.no_cpu_baseline and world == 1:
         gpu_proof = workers[0][1].prove(workers[0][2], seed=cpu_seed)
     # (c) the other BASELINE size classes (configs[2] m = 23, configs[3] m = 25), rank 0's GPU only
-    if rank == 0 and m == 21 and not args.sharded and args.size_classes and not size_figs:
+    if args.full and rank == 0 and m == 21 and not args.sharded and args.size_classes and not size_figs:
         for c_, prover_, d_z_, r1cs_, _ in workers:
             prover_.close()
             d_z_.free()
@@ -1108,36 +1155,6 @@ def main():
         dist.barrier()
 
     if rank == 0:
-        # roofline of the dominant kernel (leaf_hash): algorithmic bytes per launch / measured avg duration
-        bytes_step, launches_step, compresses_step = leaf_hash_bytes([(m, 2, cfg_w.n_rounds), (cfg_b.n_vars, 2, cfg_b.n_rounds)])
-        n_l, ms_l = prof.get("leaf_hash", (0, 0.0))
-        avg_ms = ms_l / max(n_l, 1)  # in the timed region: a launch shares the chip with the other provers' kernels
-        achieved_load = (bytes_step / launches_step) / (avg_ms * 1e-3) / 1e9 if n_l else 0.0
-        n_i, ms_i = prof_iso.get("leaf_hash", (0, 0.0))
-        iso_avg_ms = ms_i / max(n_i, 1)  # the kernel by itself (one proof at a time, same process, same hipEvent timing)
-        achieved = (bytes_step / launches_step) / (iso_avg_ms * 1e-3) / 1e9 if n_i else 0.0
-        step_bytes = proof_algorithmic_bytes(m, m_0, n_wit, cfg_w, cfg_b) * conc
-        # HBM bytes per launch come from rocprofv3 PMC passes (tools/pmc.sh: separate FETCH_SIZE / WRITE_SIZE runs, FETCH doubled
-        # for gfx950 as the microarch guide prescribes); counters cannot be read from inside this process.  A committed summary is
-        # used ONLY if it was taken with this very binary (sha256 of libprovekit_hip.so recorded by the tool) on this workload
-        # size; otherwise the field is null rather than a stale number.
-        traffic, valu_busy = None, None
-        try:
-            import glob
-            import hashlib
-
-            lib_sha = hashlib.sha256(open(provekit_amd.LIB_PATH, "rb").read()).hexdigest()[:16]
-            for fn in sorted(glob.glob(os.path.join(ROOT, "profiles", "*pmc_leaf_hash.json"))):
-                pmc = json.load(open(fn))
-                if pmc.get("lib_sha16") == lib_sha and pmc.get("m") == m:
-                    traffic = pmc["traffic_bytes_per_launch"]
-                    valu_busy = pmc.get("valu_busy_pct_largest_launch")
-        except Exception:
-            pass
-        iso_leaf_ms = prof_iso.get("leaf_hash", (1, 0.0))[1] / max(prof_iso.get("leaf_hash", (1, 0.0))[0], 1)
-        # per-proof kernel time by stage, from the one-proof-at-a-time pass (in the timed region a prover's kernels share the
-        # chip with the other provers', so their elapsed times there say little about the work)
-        stage_ms = {k: round(v[1] / iso_steps, 4) for k, v in sorted(prof_iso.items(), key=lambda kv: -kv[1][1])}
         line = {
             "metric": "proofs/sec (noir-r1cs prove hot path, WHIR commit + sumcheck + folding rounds)",
             "value": (1 if args.sharded else world) * args.steps * conc / dt,
@@ -1171,50 +1188,83 @@ def main():
                                f"GPU_MAX_HW_QUEUES={os.environ.get('GPU_MAX_HW_QUEUES')})"
                                + (", witness uploaded over PCIe before every proof (--h2d)" if args.h2d else ""),
             },
-            "roofline": {
-                "kernel": "leaf_hash_kernel (Skyscraper leaf digests)",
-                "bound": "hbm",
-                "achieved": achieved,
-                "peak": HBM_PEAK_GBS,
-                "unit": "GB/s",
-                "frac": achieved / HBM_PEAK_GBS,
-                "traffic": traffic,
-                "traffic_note": ("replayed from the rocprofv3 PMC summary under profiles/ taken with this exact binary (sha256 match), not "
-                                 "measured by this run") if traffic is not None else "no PMC summary of this binary under profiles/",
-                "algorithmic_bytes_per_launch": bytes_step / launches_step,
-                "launches_per_proof": launches_step,
-                "launches_per_step": launches_step * conc,
-                "avg_launch_ms": iso_avg_ms,
-                "achieved_under_load": achieved_load,
-                "frac_under_load": achieved_load / HBM_PEAK_GBS,
-                "avg_launch_ms_under_load": avg_ms,
-                "note": "integer-ALU bound (14 Montgomery squarings per compression, DESIGN.md 4).  achieved / frac / avg_launch_ms: the "
-                        "kernel by itself, hipEvent pairs around every launch on the work stream with one proof in flight (the figure rocprofv3 "
-                        f"--kernel-trace reports at concurrency 1); *_under_load: the same launches inside the timed region, where {conc} provers' "
-                        "kernels share the chip, so it falls as throughput rises",
-                "alu": {
-                    "achieved": 14.0 * (compresses_step / launches_step) / max(iso_leaf_ms * 1e-3, 1e-12) / 1e12,
-                    "peak": peak_modmul / 1e12 if peak_modmul else None,
-                    "unit": "T modmul/s",
-                    "frac": 14.0 * (compresses_step / launches_step) / max(iso_leaf_ms * 1e-3, 1e-12) / peak_modmul if peak_modmul else None,
-                    "valu_busy_pct_largest_launch": valu_busy,
-                    "note": "isolated launches; achieved counts only the 14 Montgomery squarings of each compression (the 4 bars, "
-                            "18 round-constant additions/reductions and the layout conversion are extra work on the same VALUs); peak = "
-                            "pk_probe_modmul_rate, register-resident squaring chains, best of 2/4/8 waves per SIMD x ILP 1/2",
-                },
-            },
-            # every kernel's algorithmic bytes (SURVEY 8d per-unit figures, proof_algorithmic_bytes) over the step's wall time
-            "step_algorithmic_GBps": step_bytes / (dt / args.steps) / 1e9,
-            "step_algorithmic_bytes": step_bytes,
-            # BASELINE.json's metric also asks for achieved HBM GB/s on the WHIR NTT: algorithmic bytes = 64 B per codeword
-            # element (one logical read + write) over the measured time of all encode kernels of a proof
-            "roofline_ntt": ntt_roofline(prof_iso, iso_steps, m, cfg_w, cfg_b, ss.get("peak_constmul") or None),
-            "single_stream": {"ms_per_proof": 1e3 * iso_dt, "proofs_per_s": 1.0 / iso_dt,
-                              "latency_mode_ms_per_proof": None if lat_dt is None else 1e3 * lat_dt,
-                              "note": "one proof at a time; latency_mode = pk_ctx_set_latency_mode (sumcheck rounds enqueued one ahead "
-                                      "behind a host-published gate; same transcript); measured in " + ss["how"]},
-            "stage_ms_per_proof_isolated": stage_ms,
         }
+        if args.full:
+            # roofline of the dominant kernel (leaf_hash): algorithmic bytes per launch / measured avg duration
+            bytes_step, launches_step, compresses_step = leaf_hash_bytes([(m, 2, cfg_w.n_rounds), (cfg_b.n_vars, 2, cfg_b.n_rounds)])
+            n_l, ms_l = prof.get("leaf_hash", (0, 0.0))
+            avg_ms = ms_l / max(n_l, 1)  # in the timed region: a launch shares the chip with the other provers' kernels
+            achieved_load = (bytes_step / launches_step) / (avg_ms * 1e-3) / 1e9 if n_l else 0.0
+            n_i, ms_i = prof_iso.get("leaf_hash", (0, 0.0))
+            iso_avg_ms = ms_i / max(n_i, 1)  # the kernel by itself (one proof at a time, same process, same hipEvent timing)
+            achieved = (bytes_step / launches_step) / (iso_avg_ms * 1e-3) / 1e9 if n_i else 0.0
+            step_bytes = proof_algorithmic_bytes(m, m_0, n_wit, cfg_w, cfg_b) * conc
+            # HBM bytes per launch come from rocprofv3 PMC passes (tools/pmc.sh: separate FETCH_SIZE / WRITE_SIZE runs, FETCH doubled
+            # for gfx950 as the microarch guide prescribes); counters cannot be read from inside this process.  A committed summary is
+            # used ONLY if it was taken with this very binary (sha256 of libprovekit_hip.so recorded by the tool) on this workload
+            # size; otherwise the field is null rather than a stale number.
+            traffic, valu_busy = None, None
+            try:
+                import glob
+                import hashlib
+
+                lib_sha = hashlib.sha256(open(provekit_amd.LIB_PATH, "rb").read()).hexdigest()[:16]
+                for fn in sorted(glob.glob(os.path.join(ROOT, "profiles", "*pmc_leaf_hash.json"))):
+                    pmc = json.load(open(fn))
+                    if pmc.get("lib_sha16") == lib_sha and pmc.get("m") == m:
+                        traffic = pmc["traffic_bytes_per_launch"]
+                        valu_busy = pmc.get("valu_busy_pct_largest_launch")
+            except Exception:
+                pass
+            iso_leaf_ms = prof_iso.get("leaf_hash", (1, 0.0))[1] / max(prof_iso.get("leaf_hash", (1, 0.0))[0], 1)
+            # per-proof kernel time by stage, from the one-proof-at-a-time pass (in the timed region a prover's kernels share the
+            # chip with the other provers', so their elapsed times there say little about the work)
+            stage_ms = {k: round(v[1] / iso_steps, 4) for k, v in sorted(prof_iso.items(), key=lambda kv: -kv[1][1])}
+            line.update({
+                "roofline": {
+                    "kernel": "leaf_hash_kernel (Skyscraper leaf digests)",
+                    "bound": "hbm",
+                    "achieved": achieved,
+                    "peak": HBM_PEAK_GBS,
+                    "unit": "GB/s",
+                    "frac": achieved / HBM_PEAK_GBS,
+                    "traffic": traffic,
+                    "traffic_note": ("replayed from the rocprofv3 PMC summary under profiles/ taken with this exact binary (sha256 match), not "
+                                     "measured by this run") if traffic is not None else "no PMC summary of this binary under profiles/",
+                    "algorithmic_bytes_per_launch": bytes_step / launches_step,
+                    "launches_per_proof": launches_step,
+                    "launches_per_step": launches_step * conc,
+                    "avg_launch_ms": iso_avg_ms,
+                    "achieved_under_load": achieved_load,
+                    "frac_under_load": achieved_load / HBM_PEAK_GBS,
+                    "avg_launch_ms_under_load": avg_ms,
+                    "note": "integer-ALU bound (14 Montgomery squarings per compression, DESIGN.md 4).  achieved / frac / avg_launch_ms: the "
+                            "kernel by itself, hipEvent pairs around every launch on the work stream with one proof in flight (the figure rocprofv3 "
+                            f"--kernel-trace reports at concurrency 1); *_under_load: the same launches inside the timed region, where {conc} provers' "
+                            "kernels share the chip, so it falls as throughput rises",
+                    "alu": {
+                        "achieved": 14.0 * (compresses_step / launches_step) / max(iso_leaf_ms * 1e-3, 1e-12) / 1e12,
+                        "peak": peak_modmul / 1e12 if peak_modmul else None,
+                        "unit": "T modmul/s",
+                        "frac": 14.0 * (compresses_step / launches_step) / max(iso_leaf_ms * 1e-3, 1e-12) / peak_modmul if peak_modmul else None,
+                        "valu_busy_pct_largest_launch": valu_busy,
+                        "note": "isolated launches; achieved counts only the 14 Montgomery squarings of each compression (the 4 bars, "
+                                "18 round-constant additions/reductions and the layout conversion are extra work on the same VALUs); peak = "
+                                "pk_probe_modmul_rate, register-resident squaring chains, best of 2/4/8 waves per SIMD x ILP 1/2",
+                    },
+                },
+                # every kernel's algorithmic bytes (SURVEY 8d per-unit figures, proof_algorithmic_bytes) over the step's wall time
+                "step_algorithmic_GBps": step_bytes / (dt / args.steps) / 1e9,
+                "step_algorithmic_bytes": step_bytes,
+                # BASELINE.json's metric also asks for achieved HBM GB/s on the WHIR NTT: algorithmic bytes = 64 B per codeword
+                # element (one logical read + write) over the measured time of all encode kernels of a proof
+                "roofline_ntt": ntt_roofline(prof_iso, iso_steps, m, cfg_w, cfg_b, ss.get("peak_constmul") or None),
+                "single_stream": {"ms_per_proof": 1e3 * iso_dt, "proofs_per_s": 1.0 / iso_dt,
+                                  "latency_mode_ms_per_proof": None if lat_dt is None else 1e3 * lat_dt,
+                                  "note": "one proof at a time; latency_mode = pk_ctx_set_latency_mode (sumcheck rounds enqueued one ahead "
+                                          "behind a host-published gate; same transcript); measured in " + ss["how"]},
+                "stage_ms_per_proof_isolated": stage_ms,
+            })
         if h2d_rate is not None:
             line["h2d_inclusive_proofs_per_s"] = h2d_rate
             line["h2d_note"] = (f"same workload, {conc} provers, the 32 x {n_wit} B witness uploaded from pageable host memory before every proof; "
@@ -1227,7 +1277,7 @@ def main():
             line[f"sharded_proof_m{args.sharded_proof_log2_size}"] = sharded_fig
         if size_figs:
             line["size_classes"] = size_figs
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             cb = cpu_baseline(m, m_0, mats0, interner0, nc, n_wit, cfg_w, cfg_b, ds0, z0, cpu_seed, gpu_proof, budget_s=args.cpu_baseline_budget)
             line["cpu_baseline"] = {
                 "value": 1.0 / cb["seconds"],

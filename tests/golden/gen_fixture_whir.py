@@ -3,7 +3,7 @@
 W1 fold, W3 sumcheck convention, E1 OOD evaluation, S6 blinding algebra) DERIVED FROM THE REFERENCE'S OWN PROOF
 tooling/provekit-bench/benches/poseidon-1000.np -- a data file of the reference's benches -- by plain algebra.
 
-Run in the BUILD container only (reads /root/reference).  Output is data; the tests read only the JSON.
+Reads the copy of that proof under tests/golden/ (gen_golden.FIXTURE).  Output is data; the tests read only the JSON.
 
 What the real proof gives (SURVEY Appendix A offsets) and what is derived here:
   * the blinding commitment T_b0 (root @96) is opened at ALL 32 leaves: an inverse DFT of each of its 32 columns yields

@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
 """Mint the golden fixtures under tests/golden/.
 
-Run in the BUILD container only (needs /root/reference for the proof fixture);
-the outputs are committed and are what the tests read -- nothing under tests/
-touches /root/reference at run time.
+Reads the proof fixture kept next to this script (poseidon-1000.np, a copy of
+the reference's tooling/provekit-bench/benches/poseidon-1000.np); the outputs
+are committed and are what the tests read.
 
 Sources of truth:
   * skyscraper_kats.json  -- the known-answer values typed in the reference's own
@@ -36,7 +36,7 @@ ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
 import pyref as pr  # noqa: E402
 
-FIXTURE = "/root/reference/tooling/provekit-bench/benches/poseidon-1000.np"
+FIXTURE = os.path.join(HERE, "poseidon-1000.np")
 
 
 def hx(x):

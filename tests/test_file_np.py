@@ -1,12 +1,13 @@
 """CPU: the `.np` proof container (provekit/common/src/file/{mod,bin}.rs): header bytes as in the reference's fixture,
-round trip, the error conditions of read_bin, and -- when the reference tree is mounted -- decoding the real fixture."""
+round trip, the error conditions of read_bin, and decoding the real fixture (a copy under tests/golden/)."""
 import hashlib
 import os
 
 import pytest
 
-FIXTURE = "/root/reference/tooling/provekit-bench/benches/poseidon-1000.np"
-# first 20 bytes of tooling/provekit-bench/benches/poseidon-1000.np
+# the reference's tooling/provekit-bench/benches/poseidon-1000.np, kept as a golden fixture
+FIXTURE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "poseidon-1000.np")
+# first 20 bytes of that file
 FIXTURE_HEADER = bytes([0xDC, 0xDF, 0x4F, 0x5A, 0x6B, 0x70, 0x01, 0x00]) + b"NPSProof" + b"\x00\x00\x00\x00"
 FIXTURE_TRANSCRIPT_LEN = 268756
 
@@ -42,7 +43,6 @@ def test_read_errors(tmp_path):
         write_np(str(tmp_path / "proof.bin"), b"abc")
 
 
-@pytest.mark.skipif(not os.path.exists(FIXTURE), reason="reference tree not mounted (GPU box)")
 def test_decodes_the_reference_fixture():
     from provekit_amd.file import decode_np, encode_np
 

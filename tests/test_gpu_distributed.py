@@ -83,11 +83,11 @@ def _check_multirank_bench(ctx, one_gpu):
     # whole-job aggregate: one step = one wave of `concurrency` proofs per GPU -> ranks x concurrency x steps proofs / time
     assert p["config"]["proofs_per_step"] == 2 * 2
     assert abs(p["value"] - 2 * 2 * 2 / (p["ms_per_step"] * 2 * 1e-3)) / p["value"] < 1e-6
-    # the DEFAULT line's secondary figures under world > 1 (what the driver's `--gpus N` run yields besides the weak-scaling
+    # the --full line's secondary figures under world > 1 (what a `--gpus N --full` run yields besides the weak-scaling
     # proofs/s): the commit probe runs SHARDED over the ranks (north_star's strong-scaling curve; here 2^17 instead of 2^26 to
     # keep the test short) and gives the unsharded root; the PCIe-inclusive rate is a second timed pass
     m2 = 17
-    q = launch(["--workload", "prove", "--concurrency", "2", "--no-cpu-baseline", "--commit-log2-size", str(m2), "--size-classes", "", "--sharded-proof-log2-size", "16"])
+    q = launch(["--full", "--workload", "prove", "--concurrency", "2", "--no-cpu-baseline", "--commit-log2-size", str(m2), "--size-classes", "", "--sharded-proof-log2-size", "16"])
     assert q["n_gpus"] == 2 and q["scaling"] == "weak" and q["h2d_inclusive_proofs_per_s"] > 0
     cp = q[f"commit_2p{m2}"]
     assert cp["n_gpus"] == 2 and cp["scaling"] == "strong" and cp["ms_per_commit"] > 0 and "sharded by leaf index over 2 ranks" in cp["workload"]
@@ -120,7 +120,7 @@ def test_bench_multirank_on_one_gpu_host_transport(ctx, oracle):
 
 
 def test_bench_gpus_2_without_a_launcher():
-    """plain `python bench.py --gpus 2 --steps 2` -- no torchrun around it, WORLD_SIZE unset -- starts its own
+    """`python bench.py --gpus 2 --steps 2 --full` -- no torchrun around it, WORLD_SIZE unset -- starts its own
     two ranks (here both on GPU 0: PK_BENCH_ONE_GPU=1, host transport), reads --gpus, and the one line says so: n_gpus 2, the
     library's communicator saw 2 ranks, and the 2^26 commit ran sharded over them next to the one-rank figure"""
     import json
@@ -131,7 +131,7 @@ def test_bench_gpus_2_without_a_launcher():
     root_dir = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "TORCHELASTIC_RUN_ID")}
     env["PK_BENCH_ONE_GPU"] = "1"
-    out = subprocess.run([sys.executable, os.path.join(root_dir, "bench.py"), "--gpus", "2", "--steps", "2", "--size-classes", "", "--no-cpu-baseline", "--sharded-proof-log2-size", "19"],
+    out = subprocess.run([sys.executable, os.path.join(root_dir, "bench.py"), "--gpus", "2", "--steps", "2", "--full", "--size-classes", "", "--no-cpu-baseline", "--sharded-proof-log2-size", "19"],
                          env=env, capture_output=True, text=True, timeout=1500)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
@@ -160,7 +160,7 @@ def test_a_stuck_library_collective_costs_the_line_only_its_own_keys(where, limi
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "TORCHELASTIC_RUN_ID")}
     env.update(PK_BENCH_ONE_GPU="1", PK_BENCH_TEST_HANG=where)
     env[limit_env] = "3"
-    out = subprocess.run([sys.executable, os.path.join(root_dir, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--concurrency", "2", "--size-classes", "",
+    out = subprocess.run([sys.executable, os.path.join(root_dir, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--concurrency", "2", "--full", "--size-classes", "",
                           "--no-cpu-baseline", "--commit-log2-size", "17", "--sharded-proof-log2-size", "15"], env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
@@ -190,7 +190,7 @@ def test_bench_gpus_more_than_present_is_clamped():
     root_dir = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "TORCHELASTIC_RUN_ID", "PK_BENCH_ONE_GPU")}
     out = subprocess.run([sys.executable, os.path.join(root_dir, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1", "--log2-size", "13", "--concurrency", "2",
-                          "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
+                          "--full", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.strip()][-1])
     assert d["n_gpus"] == 1 and d["rccl"]["world"] == 1
@@ -210,7 +210,7 @@ def test_bench_multirank_over_rccl_needs_two_gpus(ctx, oracle):
 
 
 def test_bench_line_contract(ctx):
-    """the ONE JSON line `python bench.py` prints at N = 1 carries every field the driver and the judge read (here at a small
+    """the ONE JSON line `python bench.py --full` prints at N = 1 carries every field the driver and the judge read (here at a small
     size, CPU baseline included): metric / value / unit / n_gpus / steps / warmup / ms_per_step / scaling / dtype / config.workload,
     `roofline` {bound, achieved, peak, unit, frac, traffic} with frac = achieved / peak, and `cpu_baseline` {value, unit, cores,
     kind, sample}"""
@@ -220,7 +220,7 @@ def test_bench_line_contract(ctx):
     import sys
 
     root_dir = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = subprocess.run([sys.executable, os.path.join(root_dir, "bench.py"), "--log2-size", "13", "--steps", "2", "--warmup", "1", "--concurrency", "4"],
+    out = subprocess.run([sys.executable, os.path.join(root_dir, "bench.py"), "--log2-size", "13", "--steps", "2", "--warmup", "1", "--concurrency", "4", "--full"],
                          capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
@@ -238,3 +238,54 @@ def test_bench_line_contract(ctx):
     assert r["launches_per_step"] == r["launches_per_proof"] * d["config"]["proofs_per_step"]
     c = d["cpu_baseline"]
     assert c["kind"] in ("port", "reference") and c["cores"] >= 1 and c["value"] > 0 and c["unit"] == "proofs/s" and "proof" in c["sample"]
+
+
+def test_bench_plain_line_and_dump_outputs(ctx, tmp_path):
+    """a plain run (no --full) prints the headline keys only, and --dump-outputs writes what its last timed step computed: the proofs
+    of that step, one float32 per byte, the same files from run to run and the same bytes as a prover of the bench's statement gives
+    for those seeds; the commit workload writes its root"""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    import numpy as np
+
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import bench
+
+    from provekit_amd.scheme import WhirConfig, WhirR1CSScheme, blinding_config_for
+
+    root_dir = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    m, steps, conc = 13, 3, 4
+
+    def run(extra, out_dir):
+        out = subprocess.run([sys.executable, os.path.join(root_dir, "bench.py"), "--steps", str(steps), "--warmup", "1", "--dump-outputs", str(out_dir)] + extra,
+                             capture_output=True, text=True, timeout=900)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [l for l in out.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, lines
+        return json.loads(lines[0])
+
+    d = run(["--log2-size", str(m), "--concurrency", str(conc)], tmp_path / "a")
+    assert d["unit"] == "proofs/s" and d["higher_is_better"] is True and d["steps"] == steps and "u32x8" in d["dtype"]
+    assert abs(d["value"] - conc * steps / (d["ms_per_step"] * steps * 1e-3)) / d["value"] < 1e-6
+    assert not {"roofline", "cpu_baseline", "single_stream", "size_classes", "commit_2p26", "h2d_inclusive_proofs_per_s", "rccl"} & set(d)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == [f"proof_{k:03d}.npy" for k in range(conc)]
+    run(["--log2-size", str(m), "--concurrency", str(conc)], tmp_path / "b")
+    assert sorted(os.listdir(tmp_path / "b")) == names
+    m_0, n_wit = m - 1, (1 << (m - 1)) - 5
+    r1cs, _, _, nc, n_in = bench.synth_r1cs(ctx, m_0, n_wit, seed=1234)
+    d_z, _ = bench.satisfying_witness(ctx, r1cs, n_wit, nc, n_in, 99)
+    scheme = WhirR1CSScheme(ctx, r1cs, m, m_0, WhirConfig.derive(m), blinding_config_for(m_0))
+    for k, name in enumerate(names):
+        a, b = np.load(tmp_path / "a" / name), np.load(tmp_path / "b" / name)
+        assert a.dtype == np.float32 and np.array_equal(a, b)
+        assert a.astype(np.uint8).tobytes() == scheme.prove(d_z, seed=1 + (steps - 1) * conc + k)  # the timed proofs' seeds start at 1
+    scheme.close()
+    d_z.free()
+    r1cs.close()
+    c = run(["--workload", "commit", "--log2-size", "15"], tmp_path / "c")
+    assert os.listdir(tmp_path / "c") == ["root.npy"]
+    assert np.load(tmp_path / "c" / "root.npy").astype(np.uint8).tobytes().hex() == c["config"]["root"]

@@ -13,10 +13,9 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
-FIXTURE = "/root/reference/tooling/provekit-bench/benches/poseidon-1000.np"
+FIXTURE = os.path.join(ROOT, "tests", "golden", "poseidon-1000.np")  # the reference's own proof, kept as a golden fixture
 
 
-@pytest.mark.skipif(not os.path.exists(FIXTURE), reason="reference tree not mounted (GPU box)")
 def test_reference_proof_walks_in_our_read_order():
     import verifier as V
     from provekit_amd.file import read_np

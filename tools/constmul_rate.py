@@ -1,5 +1,5 @@
-import ctypes as C, sys, json
-sys.path.insert(0, "/root/repo")
+import ctypes as C, os, sys, json
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import provekit_amd
 from provekit_amd._lib import lib
 from tools.pk_probes import lib as probes

@@ -8,7 +8,7 @@ predates the Skyscraper v2 switch -- the permutation the sponge ran at the time.
 right iff replaying the proof's first absorbs gives the blinding commitment's OOD point that gen_fixture_whir.py
 recovered from the proof by algebra (tests/golden/fixture_whir.json: blinding.ood_point).
 
-BUILD CONTAINER ONLY (reads /root/reference).  Writes the list of patterns tried to profiles/r04_iopattern_search.json.
+Reads the reference's proof from tests/golden/poseidon-1000.np.  Writes the list of patterns tried to profiles/r04_iopattern_search.json.
 """
 import hashlib
 import itertools
@@ -24,7 +24,7 @@ import pyref as pr  # noqa: E402
 import verifier as V  # noqa: E402
 
 P = pr.P
-FIXTURE = "/root/reference/tooling/provekit-bench/benches/poseidon-1000.np"
+FIXTURE = os.path.join(ROOT, "tests", "golden", "poseidon-1000.np")
 
 
 # ------------------------------------------------------------------ permutation candidates

@@ -4,6 +4,7 @@
 # usage: tools/pmc_valu.sh <tag> [bench args...]
 set -u
 TAG=${1:-pmcv}; shift || true
+set -- --full "$@"  # bench.py --full: the traces these recipes are read with include its one-proof-at-a-time pass
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 export TMPDIR=/tmp
 mkdir -p "$R/gpurun_out/$TAG"
