@@ -4,12 +4,12 @@
 // O(m_0^2) blinding algebra run here on the CPU; every data-parallel step is a call into this library's kernels on
 // buffers that never leave HBM.  One proof allocates nothing: all device memory comes from a per-scheme arena.
 //
-//   pk_prove
-//    +- batch_commit (whir_r1cs.rs:182-209): mask / random polynomial on device, to_coeffs x2, commit_batch
-//    +- run_zk_sumcheck (whir_r1cs.rs:228-369): witness bounds, eq table, blinding commitment, m_0 cubic rounds,
-//    |                                          small WHIR proof of the blinding polynomial
-//    +- external rows, weighted sums, claimed_evaluations hint (whir_r1cs.rs:81-91)
-//    +- whir_prove (whir::Prover::prove; structure pinned by recursive-verifier/app/circuit/whir.go:51-220)
+//   pk_prove -> prove, one stage per step of the reference (struct Proof)
+//    +- commit_witness (whir_r1cs.rs:57-69, 182-209): mask / random polynomial on device, to_coeffs x2, commit_batch
+//    +- zk_sumcheck (whir_r1cs.rs:228-369): witness bounds, eq table, blinding commitment, m_0 cubic rounds
+//    +- prove_blinding: small WHIR proof of the blinding polynomial
+//    +- witness_statement: external rows, weighted sums, claimed_evaluations hint (whir_r1cs.rs:81-91)
+//    +- prove_witness: whir_prove (whir::Prover::prove; structure pinned by recursive-verifier/app/circuit/whir.go:51-220)
 #include <sys/random.h>
 #include <unistd.h>
 
@@ -60,6 +60,7 @@ struct pk_scheme {
     const pk_r1cs* r1cs = nullptr;
     size_t num_constraints = 0, num_witnesses = 0;
     unsigned m = 0, m_0 = 0;
+    unsigned nb = 0;  // the blinding polynomial's table: 2^nb = next_power_of_two(4 m_0) coefficients
     pk_whir_config whir_witness{}, whir_hiding{};
     char* arena = nullptr;
     size_t arena_bytes = 0;
@@ -342,44 +343,29 @@ std::vector<uint64_t> stir_queries(Transcript& T, size_t domain_size, unsigned f
     return idx;
 }
 
-void pow_round(pk_ctx* ctx, Transcript& T, double bits, int* rc) {
-    if (bits <= 0.0) return;
+int pow_round(pk_ctx* ctx, Transcript& T, double bits) {
+    if (bits <= 0.0) return PK_OK;
     uint8_t challenge[32];
     T.challenge_bytes(challenge, 32);
     uint64_t nonce = 0;
-    *rc = pow_solve_x(ctx, challenge, bits, &nonce, comm_world(ctx) > 1);  // nonce ranges striped over the ranks of a device set
+    const int rc = pow_solve_x(ctx, challenge, bits, &nonce, comm_world(ctx) > 1);  // nonce ranges striped over the ranks of a device set
     uint8_t be[8];
     for (int i = 0; i < 8; i++) be[i] = (uint8_t)(nonce >> (56 - 8 * i));  // utilities.go:89-95
     T.add_bytes(be, 8);
+    return rc;
 }
 
-// hints: stir_answers = Vec<Vec<F>> and merkle_proof = ark MultiPath, ark-serialize uncompressed (common.go:36-61)
-int emit_opening_hints(pk_ctx* ctx, Transcript& T, const fe* d_leaves, const fe* d_nodes, size_t n_leaves, size_t width,
-                       const pk_commit_layout& lay, const std::vector<uint64_t>& idx) {
-    const size_t k = idx.size();
-    const unsigned logn = ilog2(n_leaves);
-    const size_t plen = logn ? logn - 1 : 0;
-    std::vector<uint64_t> leaves(4 * k * width), sib(4 * (k ? k : 1)), paths(4 * (k * plen ? k * plen : 1));
-    CK(open_raw(ctx, U(d_leaves), U(d_nodes), n_leaves, width, lay, idx.data(), k, /*canonical=*/1, leaves.data(), sib.data(), paths.data()));
-    const auto ser0 = std::chrono::steady_clock::now();
-    std::vector<uint8_t> buf;
-    auto put_u64 = [&](uint64_t v) {
-        for (int i = 0; i < 8; i++) buf.push_back((uint8_t)(v >> (8 * i)));
-    };
-    put_u64(k);
-    for (size_t q = 0; q < k; q++) {
-        put_u64(width);
-        const uint8_t* b = (const uint8_t*)(leaves.data() + 4 * q * width);
-        buf.insert(buf.end(), b, b + 32 * width);
+// hint payloads, ark-serialize uncompressed (common.go:36-73): a u64 little-endian, and a Vec<F> = its u64 length, then every
+// element's canonical 32 bytes (`montgomery`: the elements are still in Montgomery form)
+void put_u64(std::vector<uint8_t>& buf, uint64_t v) {
+    for (int i = 0; i < 8; i++) buf.push_back((uint8_t)(v >> (8 * i)));
+}
+void put_vec(std::vector<uint8_t>& buf, const fe* v, size_t n, bool montgomery = true) {
+    put_u64(buf, n);
+    for (size_t j = 0; j < n; j++) {
+        const fe c = montgomery ? h_to_canon(v[j]) : v[j];
+        buf.insert(buf.end(), (const uint8_t*)c.v, (const uint8_t*)c.v + 32);
     }
-    T.hint(buf.data(), buf.size());
-    size_t len = 0;
-    pk_multipath_serialize(idx.data(), k, plen, sib.data(), paths.data(), nullptr, 0, &len);
-    std::vector<uint8_t> mp(len ? len : 1);
-    CK(pk_multipath_serialize(idx.data(), k, plen, sib.data(), paths.data(), mp.data(), len, &len));
-    T.hint(mp.data(), len);
-    T.hint_seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - ser0).count();
-    return PK_OK;
 }
 
 // ------------------------------------------------------------------ WHIR
@@ -396,15 +382,37 @@ struct Commitment {  // whir::committer::Witness
     fe beta;                      // batching randomness
 };
 
+// hints: stir_answers = Vec<Vec<F>> and merkle_proof = ark MultiPath of the commitment's tree at the queried rows (common.go:36-61)
+int emit_opening_hints(pk_ctx* ctx, Transcript& T, const Commitment& C, const std::vector<uint64_t>& idx) {
+    const size_t k = idx.size(), width = C.width;
+    const unsigned logn = ilog2(C.rows);
+    const size_t plen = logn ? logn - 1 : 0;
+    std::vector<uint64_t> leaves(4 * k * width), sib(4 * (k ? k : 1)), paths(4 * (k * plen ? k * plen : 1));
+    CK(open_raw(ctx, U(C.leaves), U(C.nodes), C.rows, width, C.layout, idx.data(), k, /*canonical=*/1, leaves.data(), sib.data(), paths.data()));
+    const auto ser0 = std::chrono::steady_clock::now();
+    std::vector<uint8_t> buf;
+    put_u64(buf, k);
+    for (size_t q = 0; q < k; q++) put_vec(buf, (const fe*)(leaves.data() + 4 * q * width), width, /*montgomery=*/false);
+    T.hint(buf.data(), buf.size());
+    size_t len = 0;
+    pk_multipath_serialize(idx.data(), k, plen, sib.data(), paths.data(), nullptr, 0, &len);
+    std::vector<uint8_t> mp(len ? len : 1);
+    CK(pk_multipath_serialize(idx.data(), k, plen, sib.data(), paths.data(), mp.data(), len, &len));
+    T.hint(mp.data(), len);
+    T.hint_seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - ser0).count();
+    return PK_OK;
+}
+
 // CommitmentWriter::commit_batch (call site provekit/prover/src/whir_r1cs.rs:200-206; transcript order mtUtilities.go:51-76)
-// the commitment's device work (RS-encode, leaf hashes, tree) on `ctx`'s stream, nothing read back: the half of whir_commit that needs no
-// transcript -- in latency mode the blinding commitment's runs on a second stream while the witness commitment fills the chip
-int whir_commit_compute(pk_ctx* ctx, Arena& A, const pk_whir_config& cfg, fe* const* polys, unsigned batch, Commitment& C) {
-    C.n_vars = cfg.n_vars;
+// the commitment's device work (RS-encode, leaf hashes, tree) on `ctx`'s stream, nothing read back: the half that needs no transcript
+// -- in latency mode the blinding commitment's runs on a second stream while the witness commitment fills the chip.  Also the
+// re-commit of every WHIR round (batch 1).
+int whir_commit_compute(pk_ctx* ctx, Arena& A, unsigned n_vars, unsigned log_inv_rate, unsigned fold, fe* const* polys, unsigned batch,
+                        Commitment& C) {
+    C.n_vars = n_vars;
     C.batch = batch;
-    const unsigned k = cfg.folding_factor;
-    C.rows = (size_t)1 << (cfg.n_vars + cfg.starting_log_inv_rate - k);
-    C.width = (size_t)batch << k;
+    C.rows = (size_t)1 << (n_vars + log_inv_rate - fold);
+    C.width = (size_t)batch << fold;
     for (unsigned b = 0; b < batch; b++) C.polys[b] = polys[b];
     ALLOC(leaves, C.rows * C.width / shard_factor(ctx, C.rows));  // a rank of a device set keeps only its rows (tree.hip)
     ALLOC(nodes, 2 * C.rows);
@@ -413,14 +421,7 @@ int whir_commit_compute(pk_ctx* ctx, Arena& A, const pk_whir_config& cfg, fe* co
     CK(ensure_ws(ctx, commit_scratch_fes(ctx, C.rows, C.width) * 32));
     const uint64_t* ptrs[4];
     for (unsigned b = 0; b < batch; b++) ptrs[b] = U(polys[b]);
-    return commit_into(ctx, ptrs, batch, cfg.n_vars, cfg.starting_log_inv_rate, k, U(leaves), U(nodes), (uint64_t*)ctx->d_ws, &C.layout);
-}
-int whir_commit_transcript(pk_ctx* ctx, const pk_whir_config& cfg, const fe& root, Transcript& T, Commitment& C);
-int whir_commit(pk_ctx* ctx, Arena& A, const pk_whir_config& cfg, fe* const* polys, unsigned batch, Transcript& T, Commitment& C) {
-    CK(whir_commit_compute(ctx, A, cfg, polys, batch, C));
-    fe root;
-    CK(read_root(ctx, U(C.nodes), C.rows, (uint64_t*)root.v));
-    return whir_commit_transcript(ctx, cfg, root, T, C);
+    return commit_into(ctx, ptrs, batch, n_vars, log_inv_rate, fold, U(leaves), U(nodes), (uint64_t*)ctx->d_ws, &C.layout);
 }
 // ... and the half that talks: root, OOD points and answers, batching randomness (mtUtilities.go:51-76)
 int whir_commit_transcript(pk_ctx* ctx, const pk_whir_config& cfg, const fe& root, Transcript& T, Commitment& C) {
@@ -453,285 +454,265 @@ bool whir_sharded(const pk_ctx* ctx, unsigned n_vars) {
     const size_t G = (size_t)comm_world(ctx);
     return G > 1 && (((size_t)1 << n_vars) / G) >= 2 * SHARD_MIN_LOCAL;
 }
-int whir_prove(pk_ctx* ctx, Arena& A, const pk_whir_config& cfg, const Commitment& C, fe* const* d_weights, const size_t* weight_len,
-               unsigned n_weights, Transcript& T) {
-    const unsigned n = cfg.n_vars, k = cfg.folding_factor;
-    const size_t N = (size_t)1 << n;
-    const unsigned G = (unsigned)comm_world(ctx), lgG = ilog2(G), rank = (unsigned)comm_rank(ctx);
-    bool sharded = whir_sharded(ctx, n);              // the sumcheck tables are this rank's block [off, off + len)
-    const size_t B0 = sharded ? N / G : N, off0 = sharded ? (size_t)rank * B0 : 0;
-    // working polynomial c = sum_b beta^b poly_b (mtUtilities.go:98-114), whole on every rank: it is folded and re-committed
-    ALLOC(d_c, N);
+// how many of a weight's `stored` leading entries lie inside the block [off, off + len)
+size_t in_block(size_t stored, size_t off, size_t len) {
+    const size_t hi = stored < off + len ? stored : off + len;
+    return hi > off ? hi - off : 0;
+}
+// generator of the domain of 2^log_size points, raised to the 2^fold-th power (whir.go:99)
+fe folded_domain_generator(unsigned log_size, unsigned fold) {
+    fe root28;
+    const uint64_t l[4] = {0x9bd61b6e725b19f0ULL, 0x402d111e41112ed4ULL, 0x00e0a7eb8ef62abcULL, 0x2a3c09f0a58a7e85ULL};
+    memcpy(root28.v, l, 32);
+    fe gen = h_from_canon(root28);
+    for (unsigned i = log_size; i < 28 + fold; i++) gen = h_mul(gen, gen);
+    return gen;
+}
+
+struct WhirProver {
+    pk_ctx* ctx;
+    Arena& A;
+    const pk_whir_config& cfg;
+    const Commitment& C;
+    Transcript& T;
+    const unsigned n, k, G, lgG, rank;
+    bool sharded;          // the sumcheck tables are this rank's block [off0, off0 + B0) of the hypercube
+    const size_t B0, off0;
+    fe* d_c = nullptr;     // working polynomial c = sum_b beta^b poly_b (mtUtilities.go:98-114), whole on every rank: folded, re-committed
+    fe* bp[2] = {};        // sumcheck operands: p = evaluations of c over the hypercube, w = combined weights; ping-pong halves
+    fe* bw[2] = {};
+    fe* gathered[4] = {};  // sharded: where p, w go once the blocks are short (p0, p1, w0, w1)
+    int cur = 0;
+    size_t len;             // local length of p and w
+    std::vector<fe> rs;     // the challenges of the last sumcheck_rounds call
+    std::vector<fe> all_r;  // every folding challenge, in squeeze order
+
+    WhirProver(pk_ctx* c, Arena& a, const pk_whir_config& cf, const Commitment& com, Transcript& t)
+        : ctx(c), A(a), cfg(cf), C(com), T(t), n(cf.n_vars), k(cf.folding_factor), G((unsigned)comm_world(c)), lgG(ilog2(G)),
+          rank((unsigned)comm_rank(c)), sharded(whir_sharded(c, n)), B0(sharded ? ((size_t)1 << n) / G : (size_t)1 << n),
+          off0(sharded ? (size_t)rank * B0 : 0), len(B0) {}
+
     // sum_b beta^b x_b over `cnt` entries from `from` of coefficient tables or evaluation tables: the first two in one pass
-    auto batch_combine = [&](fe* dst, fe* const* x, size_t from, size_t cnt) -> int {
+    int batch_combine(fe* dst, fe* const* x, size_t from, size_t cnt) {
         if (C.batch == 1) return pk_memcpy_d2d(ctx, dst, x[0] + from, 32 * cnt);
         uint64_t s[4];
         h_store(s, C.beta);
         int rc = lincomb2(ctx, U(dst), U(x[0] + from), s, U(x[1] + from), cnt);
-        fe bp = h_mul(C.beta, C.beta);
+        fe bp_ = h_mul(C.beta, C.beta);
         for (unsigned b = 2; b < C.batch && !rc; b++) {
-            h_store(s, bp);
+            h_store(s, bp_);
             rc = pk_fe_axpy(ctx, U(dst), s, U(x[b] + from), cnt);
-            bp = h_mul(bp, C.beta);
+            bp_ = h_mul(bp_, C.beta);
         }
         return rc;
-    };
-    CK(batch_combine(d_c, C.polys, 0, N));
-    // sumcheck operands: p = evaluations of c over the hypercube, w = combined weights; ping-pong halves
-    fe* bp_[2];
-    fe* bw_[2];
-    ALLOC(p0, B0);
-    ALLOC(p1, B0 / 2 ? B0 / 2 : 1);
-    ALLOC(w0, B0);
-    ALLOC(w1, B0 / 2 ? B0 / 2 : 1);
-    bp_[0] = p0; bp_[1] = p1; bw_[0] = w0; bw_[1] = w1;
-    bool have_evals = true;
-    for (unsigned b = 0; b < C.batch; b++) have_evals = have_evals && C.evals[b] != nullptr;
-    if (have_evals) {
-        CK(batch_combine(p0, C.evals, off0, B0));  // to_evals is linear: combine the tables the committer kept instead of transforming d_c
-    } else if (!sharded) {
-        CK(pk_to_evals_into(ctx, U(d_c), U(p0), n));
-    } else {
-        ALLOC(d_ev, N);
-        CK(pk_to_evals_into(ctx, U(d_c), U(d_ev), n));
-        CK(pk_memcpy_d2d(ctx, p0, d_ev + off0, 32 * B0));
     }
-    // equality weights of `q` points (each nv coordinates, variable 0 <-> the top index bit) scaled by scales[j], accumulated
-    // into a weight table: the whole table, or -- sharded -- this rank's block, whose top lgG index bits are the rank: that
-    // factor of eq goes into the scale and the table is built over the remaining variables
-    auto eq_weights = [&](fe* dst, unsigned nv, std::vector<fe>& pts, std::vector<fe>& scales, size_t q, int overwrite) -> int {
-        if (!sharded) return pk_eq_accumulate(ctx, U(dst), nv, (const uint64_t*)pts.data(), (const uint64_t*)scales.data(), (unsigned)q, overwrite);
-        const unsigned nl = nv - lgG;
-        std::vector<fe> lp(q * (nl ? nl : 1)), ls(q ? q : 1);
+
+    // equality weights of the univariate points zs (expand_from_univariate; variable 0 <-> the top index bit), scaled by 1, gamma,
+    // gamma^2, ... and accumulated into a weight table; *next = the following power of gamma.  The whole table, or -- sharded -- this
+    // rank's block, whose top lgG index bits are the rank: that factor of eq goes into the scale and the table is built over the rest.
+    int eq_weights(fe* dst, unsigned nv, const std::vector<fe>& zs, const fe& gamma, int overwrite, fe* next) {
+        const size_t q = zs.size();
+        const unsigned lg = sharded ? lgG : 0, nl = nv - lg;
+        std::vector<fe> x(nv ? nv : 1), pts(q * (nl ? nl : 1)), scales(q ? q : 1);
+        fe g = fe_one();
         for (size_t j = 0; j < q; j++) {
-            ls[j] = h_mul(scales[j], eq_bits(&pts[j * nv], lgG, rank));
-            for (unsigned t = 0; t < nl; t++) lp[j * nl + t] = pts[j * nv + lgG + t];
-        }
-        return pk_eq_accumulate(ctx, U(dst), nl, (const uint64_t*)lp.data(), (const uint64_t*)ls.data(), (unsigned)q, overwrite);
-    };
-    // initial combination randomness; weights = sum gamma^i w_i over [OOD constraints..., statement weights...]
-    fe gamma = T.challenge_scalar();
-    fe g = fe_one();
-    {
-        const size_t q = C.ood_points.size();
-        std::vector<fe> pts(q * (n ? n : 1)), scales(q ? q : 1);
-        for (size_t j = 0; j < q; j++) {
-            expand_from_univariate(C.ood_points[j], n, &pts[j * n]);
-            scales[j] = g;
+            expand_from_univariate(zs[j], nv, x.data());
+            scales[j] = lg ? h_mul(g, eq_bits(x.data(), lg, rank)) : g;
+            std::copy(x.begin() + lg, x.begin() + nv, pts.begin() + j * nl);
             g = h_mul(g, gamma);
         }
-        CK(eq_weights(w0, n, pts, scales, q, /*overwrite=*/1));
-        for (unsigned i = 0; i < n_weights; i++) {
-            uint64_t s[4];
-            h_store(s, g);
-            const size_t hi = weight_len[i] < off0 + B0 ? weight_len[i] : off0 + B0;  // the part of the weight inside this block
-            if (hi > off0) CK(pk_fe_axpy(ctx, U(w0), s, U(d_weights[i] + off0), hi - off0));
-            g = h_mul(g, gamma);
-        }
+        *next = g;
+        return pk_eq_accumulate(ctx, U(dst), nl, (const uint64_t*)pts.data(), (const uint64_t*)scales.data(), (unsigned)q, overwrite);
     }
-    int cur = 0;
-    size_t len = B0;         // local length of p and w
-    std::vector<fe> all_r;  // every folding challenge, in squeeze order
-    // latency mode (one GPU): round t+1's kernel -- and after the last round the fold -- is enqueued BEFORE round t's result is read,
-    // gated on the challenge the host publishes once it has squeezed it; the round trip then costs the link, not a launch + sync
-    auto sumcheck_rounds_pipelined = [&](unsigned rounds, std::vector<fe>& rs) -> int {
+
+    void flip() {
+        cur = 1 - cur;
+        len /= 2;
+    }
+
+    // `rounds` quadratic sumcheck rounds on p, w, each: the round's h(0), h(1), h(2), absorb, squeeze the folding challenge, record
+    // it; afterwards p, w describe the folded polynomial.  Latency mode (one GPU): round t+1's kernel -- after the last round the
+    // fold -- is enqueued BEFORE round t's result is read, gated on the challenge the host publishes once it has squeezed it; the
+    // round trip then costs the link, not a launch + sync.  Otherwise every round is a synchronous call that first folds by the
+    // previous challenge (sharded: its h(0), h(1), h(2) are sums over the ranks' blocks).
+    int sumcheck_rounds(unsigned rounds) {
         rs.clear();
-        if (!rounds) return PK_OK;
+        const bool pipelined = ctx->latency_mode && G == 1 && rounds && len >= ((size_t)1 << rounds);
+        Across ac(ctx, sharded);
+        CK(ac.rc);
         unsigned red_cur = 0, red_next = 0;
-        CK(sumcheck_quadratic_launch(ctx, U(bp_[cur]), U(bw_[cur]), len, nullptr, 0, nullptr, nullptr, &red_cur));
+        if (pipelined) CK(sumcheck_quadratic_launch(ctx, U(bp[cur]), U(bw[cur]), len, nullptr, 0, nullptr, nullptr, &red_cur));
         for (unsigned t = 0; t < rounds; t++) {
             PendingGate gate(ctx);
-            // what consumes this round's challenge: the next round (folding first), or the closing fold
-            const bool more = t + 1 < rounds;
-            if (more || len >= 2) {
-                gate.arm(sumcheck_gate_next(ctx));
-                if (more) CK(sumcheck_quadratic_launch(ctx, U(bp_[cur]), U(bw_[cur]), len, nullptr, gate.seq, U(bp_[1 - cur]), U(bw_[1 - cur]), &red_next));
-                else CK(fold_pairs2_gated(ctx, U(bp_[cur]), U(bp_[1 - cur]), U(bw_[cur]), U(bw_[1 - cur]), len, nullptr, gate.seq));
-                cur = 1 - cur;
-                len /= 2;
+            uint64_t out[12], f[4];
+            if (pipelined) {
+                // what consumes this round's challenge: the next round (folding first), or the closing fold
+                const bool more = t + 1 < rounds;
+                if (more || len >= 2) {
+                    gate.arm(sumcheck_gate_next(ctx));
+                    if (more) CK(sumcheck_quadratic_launch(ctx, U(bp[cur]), U(bw[cur]), len, nullptr, gate.seq, U(bp[1 - cur]), U(bw[1 - cur]), &red_next));
+                    else CK(fold_pairs2_gated(ctx, U(bp[cur]), U(bp[1 - cur]), U(bw[cur]), U(bw[1 - cur]), len, nullptr, gate.seq));
+                    flip();
+                }
+                CK(sumcheck_collect_spin(ctx, red_cur, out));
+                red_cur = red_next;
+            } else if (t == 0) {
+                CK(pk_sumcheck_quadratic_round(ctx, U(bp[cur]), U(bw[cur]), len, nullptr, nullptr, nullptr, out));
+            } else {
+                h_store(f, rs.back());
+                CK(pk_sumcheck_quadratic_round(ctx, U(bp[cur]), U(bw[cur]), len, f, U(bp[1 - cur]), U(bw[1 - cur]), out));
+                flip();
             }
-            uint64_t out[12];
-            CK(sumcheck_collect_spin(ctx, red_cur, out));
-            fe h[3] = {h_load(out), h_load(out + 4), h_load(out + 8)};
+            const fe h[3] = {h_load(out), h_load(out + 4), h_load(out + 8)};
             T.add_scalars(h, 3);
             const fe fold = T.challenge_scalar();
             gate.publish(fold);
             rs.push_back(fold);
             all_r.push_back(fold);
-            red_cur = red_next;
         }
-        return PK_OK;
-    };
-    auto sumcheck_rounds = [&](unsigned rounds, std::vector<fe>& rs) -> int {
-        if (ctx->latency_mode && G == 1 && rounds && len >= ((size_t)1 << rounds)) return sumcheck_rounds_pipelined(rounds, rs);
-        rs.clear();
-        bool have_fold = false;
-        fe fold = fe_zero();
-        Across ac(ctx, sharded);  // sharded: h(0), h(1), h(2) are sums over the ranks' blocks
-        CK(ac.rc);
-        for (unsigned t = 0; t < rounds; t++) {
-            uint64_t out[12], f[4];
-            if (!have_fold) {
-                CK(pk_sumcheck_quadratic_round(ctx, U(bp_[cur]), U(bw_[cur]), len, nullptr, nullptr, nullptr, out));
-            } else {
-                h_store(f, fold);
-                CK(pk_sumcheck_quadratic_round(ctx, U(bp_[cur]), U(bw_[cur]), len, f, U(bp_[1 - cur]), U(bw_[1 - cur]), out));
-                cur = 1 - cur;
-                len /= 2;
-            }
-            fe h[3] = {h_load(out), h_load(out + 4), h_load(out + 8)};
-            T.add_scalars(h, 3);
-            fold = T.challenge_scalar();
-            have_fold = true;
-            rs.push_back(fold);
-            all_r.push_back(fold);
-        }
-        if (have_fold && len >= 2) {  // apply the last challenge: p, w now describe the folded polynomial
+        if (!pipelined && rounds && len >= 2) {  // apply the last challenge: p, w now describe the folded polynomial
             uint64_t f[4];
-            h_store(f, fold);
-            CK(fold_pairs2(ctx, U(bp_[cur]), U(bp_[1 - cur]), U(bw_[cur]), U(bw_[1 - cur]), len, f));
-            cur = 1 - cur;
-            len /= 2;
+            h_store(f, rs.back());
+            CK(fold_pairs2(ctx, U(bp[cur]), U(bp[1 - cur]), U(bw[cur]), U(bw[1 - cur]), len, f));
+            flip();
         }
         return PK_OK;
-    };
-    // once a rank's block is short the blocks are all-gathered (block r of the gather IS index range r) and the rest of the
-    // sumcheck runs replicated; a sumcheck_rounds call shrinks the block 2^k-fold, so blocks never run out inside one
-    fe *gp[2] = {nullptr, nullptr}, *gw[2] = {nullptr, nullptr};
-    if (sharded) {
-        const size_t cap = G * SHARD_MIN_LOCAL;
-        ALLOC(gp0, cap);
-        ALLOC(gp1, cap / 2);
-        ALLOC(gw0, cap);
-        ALLOC(gw1, cap / 2);
-        gp[0] = gp0; gp[1] = gp1; gw[0] = gw0; gw[1] = gw1;
     }
-    auto maybe_gather = [&]() -> int {
-        if (!sharded || len > SHARD_MIN_LOCAL) return PK_OK;
-        CK(gather_blocks(ctx, bp_[cur], len, gp[0]));
-        CK(gather_blocks(ctx, bw_[cur], len, gw[0]));
-        bp_[0] = gp[0]; bp_[1] = gp[1]; bw_[0] = gw[0]; bw_[1] = gw[1];
+
+    // all-gather of the ranks' blocks of p and w into (p0, w0) -- block r of the gather IS index range r -- after which the rest of
+    // the sumcheck runs replicated
+    int gather(fe* p0, fe* p1, fe* w0, fe* w1) {
+        CK(gather_blocks(ctx, bp[cur], len, p0));
+        CK(gather_blocks(ctx, bw[cur], len, w0));
+        bp[0] = p0; bp[1] = p1; bw[0] = w0; bw[1] = w1;
         cur = 0;
         len *= G;
         sharded = false;
         return PK_OK;
-    };
-    std::vector<fe> rs;
-    CK(sumcheck_rounds(k, rs));
-    CK(maybe_gather());
+    }
+    // once a rank's block is short; a sumcheck_rounds call shrinks the block 2^k-fold, so blocks never run out inside one
+    int maybe_gather() { return sharded && len <= SHARD_MIN_LOCAL ? gather(gathered[0], gathered[1], gathered[2], gathered[3]) : PK_OK; }
 
-    const fe* prev_leaves = C.leaves;
-    const fe* prev_nodes = C.nodes;
-    size_t prev_rows = C.rows, prev_width = C.width;
-    pk_commit_layout prev_layout = C.layout;
-    unsigned nv = n, log_inv_rate = cfg.starting_log_inv_rate;
-    size_t domain_size = (size_t)1 << (n + log_inv_rate);
-    // generator of the starting domain and its 2^k-th power (whir.go:99)
-    fe exp_gen;
-    {
-        fe root28;
-        const uint64_t l[4] = {0x9bd61b6e725b19f0ULL, 0x402d111e41112ed4ULL, 0x00e0a7eb8ef62abcULL, 0x2a3c09f0a58a7e85ULL};
-        memcpy(root28.v, l, 32);
-        fe gen = h_from_canon(root28);
-        for (unsigned i = n + log_inv_rate; i < 28; i++) gen = h_mul(gen, gen);
-        exp_gen = gen;
-        for (unsigned i = 0; i < k; i++) exp_gen = h_mul(exp_gen, exp_gen);
-    }
-    for (unsigned r = 0; r < cfg.n_rounds; r++) {
-        // W1: fold the coefficient form by this round's randomness
-        const unsigned nv2 = nv - k;
-        ALLOC(d_c2, (size_t)1 << nv2);
-        CK(pk_fold_coeffs(ctx, U(d_c), nv, (const uint64_t*)rs.data(), k, U(d_c2)));
-        d_c = d_c2;
-        nv = nv2;
-        log_inv_rate += k - 1;  // the domain halves while the polynomial shrinks 2^k-fold
-        // N1+N2+M1+M2: re-commit
-        const size_t rows = (size_t)1 << (nv + log_inv_rate - k), width = (size_t)1 << k;
-        ALLOC(leaves, rows * width / shard_factor(ctx, rows));
-        ALLOC(nodes, 2 * rows);
-        CK(ensure_ws(ctx, commit_scratch_fes(ctx, rows, width) * 32));
-        const uint64_t* ptr = U(d_c);
-        pk_commit_layout layout;
-        CK(commit_into(ctx, &ptr, 1, nv, log_inv_rate, k, U(leaves), U(nodes), (uint64_t*)ctx->d_ws, &layout));
-        fe root;
-        CK(read_root(ctx, U(nodes), rows, (uint64_t*)root.v));
-        T.add_canon(root);
-        // E1: OOD
-        std::vector<fe> ood(cfg.ood_samples[r]);
-        T.challenge_scalars(ood.data(), ood.size());
-        std::vector<fe> ood_ans(ood.size());
-        for (size_t j = 0; j < ood.size(); j++) CK(eval_univariate_x(ctx, d_c, (size_t)1 << nv, ood[j], ood_ans[j]));
-        T.add_scalars(ood_ans.data(), ood_ans.size());
-        // P1
-        int prc = PK_OK;
-        pow_round(ctx, T, cfg.pow_bits[r], &prc);
-        CK(prc);
-        // Q1: STIR queries into the previous tree
-        std::vector<uint64_t> idx = stir_queries(T, domain_size, k, cfg.num_queries[r]);
-        CK(emit_opening_hints(ctx, T, prev_leaves, prev_nodes, prev_rows, prev_width, prev_layout, idx));
-        // W2: equality weights of the OOD and STIR points, scaled by powers of the combination randomness
-        gamma = T.challenge_scalar();
-        g = fe_one();
-        const size_t q = ood.size() + idx.size();
-        std::vector<fe> pts(q * (nv ? nv : 1)), scales(q ? q : 1);
-        size_t j = 0;
-        for (size_t t = 0; t < ood.size(); t++, j++) {
-            expand_from_univariate(ood[t], nv, &pts[j * nv]);
-            scales[j] = g;
+    // the working polynomial, the sumcheck tables, the initial weights and the first k sumcheck rounds
+    int start(fe* const* d_weights, const size_t* weight_len, unsigned n_weights) {
+        const size_t N = (size_t)1 << n;
+        ALLOC(dc, N);
+        d_c = dc;
+        CK(batch_combine(d_c, C.polys, 0, N));
+        ALLOC(p0, B0);
+        ALLOC(p1, B0 / 2 ? B0 / 2 : 1);
+        ALLOC(w0, B0);
+        ALLOC(w1, B0 / 2 ? B0 / 2 : 1);
+        bp[0] = p0; bp[1] = p1; bw[0] = w0; bw[1] = w1;
+        bool have_evals = true;
+        for (unsigned b = 0; b < C.batch; b++) have_evals = have_evals && C.evals[b] != nullptr;
+        if (have_evals) {
+            CK(batch_combine(p0, C.evals, off0, B0));  // to_evals is linear: combine the tables the committer kept instead of transforming d_c
+        } else if (!sharded) {
+            CK(pk_to_evals_into(ctx, U(d_c), U(p0), n));
+        } else {
+            ALLOC(d_ev, N);
+            CK(pk_to_evals_into(ctx, U(d_c), U(d_ev), n));
+            CK(pk_memcpy_d2d(ctx, p0, d_ev + off0, 32 * B0));
+        }
+        // initial combination randomness; weights = sum gamma^i w_i over [OOD constraints..., statement weights...]
+        const fe gamma = T.challenge_scalar();
+        fe g;
+        CK(eq_weights(w0, n, C.ood_points, gamma, /*overwrite=*/1, &g));
+        for (unsigned i = 0; i < n_weights; i++) {
+            uint64_t s[4];
+            h_store(s, g);
+            const size_t cnt = in_block(weight_len[i], off0, B0);
+            if (cnt) CK(pk_fe_axpy(ctx, U(w0), s, U(d_weights[i] + off0), cnt));
             g = h_mul(g, gamma);
         }
-        for (size_t t = 0; t < idx.size(); t++, j++) {
-            expand_from_univariate(h_pow(exp_gen, idx[t]), nv, &pts[j * nv]);
-            scales[j] = g;
-            g = h_mul(g, gamma);
+        if (sharded) {
+            const size_t cap = G * SHARD_MIN_LOCAL;
+            const size_t sizes[4] = {cap, cap / 2, cap, cap / 2};
+            for (int q = 0; q < 4; q++) {
+                ALLOC(buf, sizes[q]);
+                gathered[q] = buf;
+            }
         }
-        CK(eq_weights(bw_[cur], nv, pts, scales, q, 0));
-        // W3
-        CK(sumcheck_rounds(k, rs));
-        CK(maybe_gather());
-        prev_leaves = leaves;
-        prev_nodes = nodes;
-        prev_rows = rows;
-        prev_width = width;
-        prev_layout = layout;
-        domain_size /= 2;
-        exp_gen = h_mul(exp_gen, exp_gen);
+        CK(sumcheck_rounds(k));
+        return maybe_gather();
     }
+
+    // the folding rounds: fold, re-commit, OOD, PoW, STIR openings of the previous tree, new weights, k sumcheck rounds (whir.go:51-220)
+    int rounds() {
+        const Commitment* prev = &C;  // the tree this round's STIR queries open
+        Commitment com;
+        unsigned nv = n, log_inv_rate = cfg.starting_log_inv_rate;
+        size_t domain_size = (size_t)1 << (n + log_inv_rate);
+        fe exp_gen = folded_domain_generator(n + log_inv_rate, k);
+        for (unsigned r = 0; r < cfg.n_rounds; r++) {
+            // W1: fold the coefficient form by this round's randomness
+            const unsigned nv2 = nv - k;
+            ALLOC(d_c2, (size_t)1 << nv2);
+            CK(pk_fold_coeffs(ctx, U(d_c), nv, (const uint64_t*)rs.data(), k, U(d_c2)));
+            d_c = d_c2;
+            nv = nv2;
+            log_inv_rate += k - 1;  // the domain halves while the polynomial shrinks 2^k-fold
+            // N1+N2+M1+M2: re-commit
+            Commitment next;
+            CK(whir_commit_compute(ctx, A, nv, log_inv_rate, k, &d_c, 1, next));
+            fe root;
+            CK(read_root(ctx, U(next.nodes), next.rows, (uint64_t*)root.v));
+            T.add_canon(root);
+            // E1: OOD
+            std::vector<fe> zs(cfg.ood_samples[r]);
+            T.challenge_scalars(zs.data(), zs.size());
+            std::vector<fe> ood_ans(zs.size());
+            for (size_t j = 0; j < zs.size(); j++) CK(eval_univariate_x(ctx, d_c, (size_t)1 << nv, zs[j], ood_ans[j]));
+            T.add_scalars(ood_ans.data(), ood_ans.size());
+            // P1
+            CK(pow_round(ctx, T, cfg.pow_bits[r]));
+            // Q1: STIR queries into the previous tree
+            const std::vector<uint64_t> idx = stir_queries(T, domain_size, k, cfg.num_queries[r]);
+            CK(emit_opening_hints(ctx, T, *prev, idx));
+            // W2: equality weights of the OOD and STIR points, scaled by powers of the combination randomness
+            const fe gamma = T.challenge_scalar();
+            for (uint64_t i : idx) zs.push_back(h_pow(exp_gen, i));
+            fe g;
+            CK(eq_weights(bw[cur], nv, zs, gamma, 0, &g));
+            // W3
+            CK(sumcheck_rounds(k));
+            CK(maybe_gather());
+            com = next;
+            prev = &com;
+            domain_size /= 2;
+            exp_gen = h_mul(exp_gen, exp_gen);
+        }
+        return final_round(*prev, nv, domain_size);
+    }
+
     // final round: the folded polynomial in the clear, PoW, final STIR openings, final sumcheck
-    {
+    int final_round(const Commitment& prev, unsigned nv, size_t domain_size) {
         if (sharded) {  // a schedule that ends before the blocks got short: finish replicated
             const size_t cap = len * G;
             ALLOC(fp0, cap);
             ALLOC(fp1, cap / 2 ? cap / 2 : 1);
             ALLOC(fw0, cap);
             ALLOC(fw1, cap / 2 ? cap / 2 : 1);
-            CK(gather_blocks(ctx, bp_[cur], len, fp0));
-            CK(gather_blocks(ctx, bw_[cur], len, fw0));
-            bp_[0] = fp0; bp_[1] = fp1; bw_[0] = fw0; bw_[1] = fw1;
-            cur = 0;
-            len = cap;
-            sharded = false;
+            CK(gather(fp0, fp1, fw0, fw1));
         }
         const unsigned nv2 = nv - k;
         ALLOC(d_final, (size_t)1 << nv2);
         CK(pk_fold_coeffs(ctx, U(d_c), nv, (const uint64_t*)rs.data(), k, U(d_final)));
-        nv = nv2;
-        std::vector<fe> fin((size_t)1 << nv);
+        std::vector<fe> fin((size_t)1 << nv2);
         CK(pk_memcpy_d2h(ctx, fin.data(), d_final, 32 * fin.size()));
         T.add_scalars(fin.data(), fin.size());
-        int prc = PK_OK;
-        pow_round(ctx, T, cfg.final_pow_bits, &prc);
-        CK(prc);
-        std::vector<uint64_t> idx = stir_queries(T, domain_size, k, cfg.final_queries);
-        CK(emit_opening_hints(ctx, T, prev_leaves, prev_nodes, prev_rows, prev_width, prev_layout, idx));
-        CK(sumcheck_rounds(nv, rs));
-        prc = PK_OK;
-        pow_round(ctx, T, cfg.final_folding_pow_bits, &prc);  // whir.go:196-201
-        CK(prc);
+        CK(pow_round(ctx, T, cfg.final_pow_bits));
+        const std::vector<uint64_t> idx = stir_queries(T, domain_size, k, cfg.final_queries);
+        CK(emit_opening_hints(ctx, T, prev, idx));
+        CK(sumcheck_rounds(nv2));
+        return pow_round(ctx, T, cfg.final_folding_pow_bits);  // whir.go:196-201
     }
+
     // deferred_weight_evaluations hint (common.go:63-73): each linear weight's MLE at the full folding point.
     // Round t folds index bit t (LSB first), so the point in eval_eq's MSB-first order is reverse(all_r).
-    if (n_weights) {
+    int deferred_hint(fe* const* d_weights, const size_t* weight_len, unsigned n_weights) {
+        if (!n_weights) return PK_OK;
         std::vector<fe> point(all_r.rbegin(), all_r.rend());
         const bool sh = whir_sharded(ctx, n);  // the eq table and the dot products by blocks, like the weights themselves
         ALLOC(d_eq, B0);
@@ -741,33 +722,35 @@ int whir_prove(pk_ctx* ctx, Arena& A, const pk_whir_config& cfg, const Commitmen
         } else {
             CK(pk_eq_table(ctx, (const uint64_t*)point.data(), n, U(d_eq)));
         }
-        std::vector<uint8_t> buf;
-        uint64_t cnt = n_weights;
-        for (int i = 0; i < 8; i++) buf.push_back((uint8_t)(cnt >> (8 * i)));
         Across ac(ctx, sh);
         CK(ac.rc);
-        uint64_t outs[4 * 8] = {};
+        std::vector<fe> evals(n_weights);
         const bool rows3 = n_weights == 3 && weight_len[0] == weight_len[1] && weight_len[1] == weight_len[2] && d_weights[1] > d_weights[0] &&
                            d_weights[1] - d_weights[0] == d_weights[2] - d_weights[1];
         if (rows3) {  // the three external rows against the eq table in one pass
-            const size_t hi = weight_len[0] < off0 + B0 ? weight_len[0] : off0 + B0;
+            uint64_t o[12] = {};
             if (sh || weight_len[0])
-                CK(dot_rows(ctx, U(d_weights[0] + off0), (size_t)(d_weights[1] - d_weights[0]), 3, U(d_eq), nullptr, hi > off0 ? hi - off0 : 0, outs));
-        }
-        for (unsigned i = 0; i < n_weights; i++) {
-            uint64_t* out = outs + 4 * (i < 8 ? i : 7);
-            const size_t hi = weight_len[i] < off0 + B0 ? weight_len[i] : off0 + B0;
-            if (!rows3) {
-                if (sh || weight_len[i]) CK(pk_dot(ctx, U(d_weights[i] + off0), U(d_eq), hi > off0 ? hi - off0 : 0, out));
-                else memset(out, 0, 32);
+                CK(dot_rows(ctx, U(d_weights[0] + off0), (size_t)(d_weights[1] - d_weights[0]), 3, U(d_eq), nullptr, in_block(weight_len[0], off0, B0), o));
+            for (int i = 0; i < 3; i++) evals[i] = h_load(o + 4 * i);
+        } else {
+            for (unsigned i = 0; i < n_weights; i++) {
+                uint64_t o[4] = {};
+                if (sh || weight_len[i]) CK(pk_dot(ctx, U(d_weights[i] + off0), U(d_eq), in_block(weight_len[i], off0, B0), o));
+                evals[i] = h_load(o);
             }
-            fe c = h_to_canon(h_load(out));
-            const uint8_t* b = (const uint8_t*)c.v;
-            buf.insert(buf.end(), b, b + 32);
         }
+        std::vector<uint8_t> buf;
+        put_vec(buf, evals.data(), n_weights);
         T.hint(buf.data(), buf.size());
+        return PK_OK;
     }
-    return PK_OK;
+};
+int whir_prove(pk_ctx* ctx, Arena& A, const pk_whir_config& cfg, const Commitment& C, fe* const* d_weights, const size_t* weight_len,
+               unsigned n_weights, Transcript& T) {
+    WhirProver P(ctx, A, cfg, C, T);
+    CK(P.start(d_weights, weight_len, n_weights));
+    CK(P.rounds());
+    return P.deferred_hint(d_weights, weight_len, n_weights);
 }
 
 // batch_commit_to_polynomial (provekit/prover/src/whir_r1cs.rs:182-209)
@@ -799,17 +782,10 @@ int batch_commit_compute(pk_ctx* ctx, Arena& A, unsigned m, const pk_whir_config
     out.f_evals = f;
     out.g_evals = g;
     fe* polys[2] = {fe_, ge_};
-    int rc = whir_commit_compute(ctx, A, cfg, polys, 2, out.com);
+    int rc = whir_commit_compute(ctx, A, cfg.n_vars, cfg.starting_log_inv_rate, cfg.folding_factor, polys, 2, out.com);
     out.com.evals[0] = f;
     out.com.evals[1] = g;
     return rc;
-}
-int batch_commit(pk_ctx* ctx, Arena& A, unsigned m, const pk_whir_config& cfg, const fe* d_evals, size_t n_evals, const RngKey& key,
-                 u32 stream_mask, u32 stream_g, Transcript& T, BatchCommit& out) {
-    CK(batch_commit_compute(ctx, A, m, cfg, d_evals, n_evals, key, stream_mask, stream_g, out));
-    fe root;
-    CK(read_root(ctx, U(out.com.nodes), out.com.rows, (uint64_t*)root.v));
-    return whir_commit_transcript(ctx, cfg, root, T, out.com);
 }
 
 // 256-bit key of one proof's random draws: fresh from the OS CSPRNG (the reference's thread_rng) unless injected.  One proof
@@ -1002,11 +978,12 @@ std::string io_pattern_mismatch(const std::string& theirs, unsigned m_0, const p
 // communicator stays usable for the next call.
 struct AbortOnFailure {
     pk_ctx* c;
-    bool ok = false;
     unsigned long long issued0;
+    int rc = PK_ERR_HIP;  // until done(): a path that leaves without reporting its status fails, and not the same on every rank
     explicit AbortOnFailure(pk_ctx* ctx) : c(ctx), issued0(comm_collectives_issued(ctx)) {}
+    int done(int status) { return rc = status; }
     ~AbortOnFailure() {
-        if (ok) return;
+        if (rc == PK_OK) return;
         struct Drain {  // whatever happens to the communicator, an abandoned proof leaves nothing behind on the stream: a gated kernel
             pk_ctx* c;  // released with a zero challenge must have finished -- and its give-up word be cleared -- before the next proof starts
             ~Drain() {
@@ -1015,11 +992,372 @@ struct AbortOnFailure {
             }
         } drain{c};
         if (comm_world(c) <= 1) return;
-        const bool same_everywhere = c->err_code == PK_ERR_BAD_ARG || c->err_code == PK_ERR_UNSATISFIED || c->err_code == PK_ERR_IO_PATTERN;
+        const bool same_everywhere = rc == PK_ERR_BAD_ARG || rc == PK_ERR_UNSATISFIED || rc == PK_ERR_IO_PATTERN;
         if (comm_rccl(c) && same_everywhere && comm_collectives_issued(c) == issued0) return;
         comm_abort(c);
     }
 };
+
+// the WHIR configs this prover runs: nullptr if `c` is one, else why not.  pk_scheme_create refuses the rest, and so does every
+// host-only entry point that takes a config.
+const char* whir_config_error(const pk_whir_config* c) {
+    if (!c) return "null pointer";
+    if (c->folding_factor < 1 || c->folding_factor > 8 || c->n_rounds > PK_MAX_WHIR_ROUNDS) return "bad WHIR config";
+    if (c->n_vars < c->folding_factor * (c->n_rounds + 1)) return "WHIR rounds exceed the number of variables";
+    if (c->commitment_ood_samples > 4) return "too many OOD samples";
+    if (c->batch_size < 1 || c->batch_size > 4) return "batch size out of range";
+    // the evaluation domain must exist in BN254-Fr (two-adicity 28) and the codeword must fit pk_rs_encode's bound
+    if (c->starting_log_inv_rate < 1 || c->starting_log_inv_rate > 28 || c->n_vars > 28 - c->starting_log_inv_rate)
+        return "n_vars + starting_log_inv_rate exceeds 28";
+    if (c->n_vars + c->starting_log_inv_rate - c->folding_factor > 27) return "codeword has more than 2^27 rows";
+    for (unsigned r = 0; r < c->n_rounds; r++)
+        if (c->ood_samples[r] > 4) return "too many OOD samples";
+    return nullptr;
+}
+
+// latency mode, one GPU: the scheme's second context (a stream and workspace of its own on the same device, created on first use)
+// runs the work that can overlap -- the blinding commitment underneath the witness commitment, the external rows underneath the
+// blinding WHIR proof.  Whatever path leaves pk_prove, its stream must not still be working in this proof's arena: drained on every
+// exit, its mailbox rewound.
+struct SideContext {
+    pk_ctx* c = nullptr;
+    int open(pk_ctx* ctx, pk_scheme* s) {
+        if (!s->side) {
+            int dev = 0;
+            PK_HIP(ctx, hipGetDevice(&dev));
+            CK(pk_ctx_create(dev, &s->side));
+        }
+        c = s->side;
+        c->hash_version = ctx->hash_version;
+        return PK_OK;
+    }
+    ~SideContext() {
+        if (!c) return;
+        (void)wait_stream(c->device, c->stream);
+        c->mail_off = 0;
+    }
+};
+
+// one pk_prove call: the state its stages share
+struct Proof {
+    pk_ctx* ctx;
+    pk_scheme* s;
+    const fe* d_witness;
+    size_t n_witness;
+    const RngKey& key;
+    Arena A;
+    Transcript T;
+    const unsigned G, lgG, rank;
+    // sharded witness WHIR: a rank needs (and computes) only the columns of the external rows inside its block of the hypercube
+    const bool st_sharded;
+    const size_t blk, blk_lo;
+    SideContext side;
+    pk_ctx* aux;             // where the work that can overlap runs: the side context in latency mode on one GPU, else ctx
+    BatchCommit W, B;        // the witness commitment, the blinding commitment
+    std::vector<fe> g_univ;  // blinding univariates: 4 coefficients per variable
+    fe* h_univ = nullptr;    // ... as the side stream copied them into its mailbox
+    std::vector<fe> alpha;   // the zk sumcheck's challenges
+    fe* rows = nullptr;      // the three external rows, n_witness each
+    const bool timing = getenv("PK_PROVE_TIMING") != nullptr;
+    std::chrono::steady_clock::time_point t_lap = std::chrono::steady_clock::now();
+
+    Proof(pk_ctx* c, pk_scheme* sc, const fe* w, size_t nw, const RngKey& k)
+        : ctx(c), s(sc), d_witness(w), n_witness(nw), key(k), A{sc->arena, sc->arena_bytes}, T(sc->domain_separator), G((unsigned)comm_world(c)),
+          lgG(ilog2(G)), rank((unsigned)comm_rank(c)), st_sharded(whir_sharded(c, sc->m)), blk(((size_t)1 << sc->m) / (st_sharded ? G : 1)),
+          blk_lo(st_sharded ? (size_t)rank * blk : 0), aux(c), g_univ(4 * (size_t)sc->m_0) {}
+
+    int init() {
+        if (!ctx->latency_mode || G != 1) return PK_OK;
+        CK(side.open(ctx, s));
+        aux = side.c;
+        return PK_OK;
+    }
+    // the external rows go to the side context too, unless there are none
+    pk_ctx* rows_ctx() const { return n_witness ? aux : ctx; }
+    // a failure on the side context is reported where the caller looks
+    int relay(pk_ctx* c, int rc, const char* what) {
+        if (!rc || c == ctx) return rc;
+        return set_err(ctx, rc, "%s on the side stream: %s", what, pk_last_error(c));
+    }
+    void lap(const char* what) {  // PK_PROVE_TIMING: one stderr line per stage
+        if (!timing) return;
+        (void)wait_ctx(ctx);
+        const auto t = std::chrono::steady_clock::now();
+        fprintf(stderr, "[pk_prove] %-28s %8.3f ms (sponge: %u permutes, %.3f ms; hint serialisation so far %.3f ms)\n", what,
+                1e3 * std::chrono::duration<double>(t - t_lap).count(), T.permutes, 1e3 * T.permute_seconds, 1e3 * T.hint_seconds);
+        t_lap = t;
+    }
+
+    int commit_witness();
+    int blinding_transcript();
+    int zk_sumcheck();
+    int zk_rounds(fe* z[4], size_t length, bool sharded);
+    int prove_blinding();
+    int witness_statement();
+    int prove_witness();
+};
+
+// blinding univariates: 4 random coefficients per variable [RNG], committed with the small WHIR (whir_r1cs.rs:212-226): the device
+// work, on `ctx`'s stream.  On the side context the coefficients come back through its mailbox, else at once.
+int blinding_compute(pk_ctx* ctx, Proof& P) {
+    Arena& A = P.A;
+    const size_t NB = (size_t)1 << P.s->nb, n = P.g_univ.size();
+    ALLOC(d_blind, NB);
+    CK(pk_memset_zero(ctx, d_blind, 32 * NB));
+    random_fe_kernel<<<1, 256, 0, ctx->stream>>>(d_blind, n, P.key, RNG_BLIND);
+    PK_LAUNCH_CHECK(ctx);
+    if (ctx == P.ctx) {
+        CK(pk_memcpy_d2h(ctx, P.g_univ.data(), d_blind, 32 * n));
+    } else {
+        CK(mail_alloc(ctx, 32 * n, (void**)&P.h_univ));
+        PK_HIP(ctx, hipMemcpyAsync(P.h_univ, d_blind, 32 * n, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    return batch_commit_compute(ctx, A, P.s->nb + 1, P.s->whir_hiding, d_blind, NB, P.key, RNG_MASK_B, RNG_G_B, P.B);
+}
+
+// external rows (whir_r1cs.rs:81-91, 382-412): eq(alpha) and the three rows [S4] on `ctx`'s stream.  On the side context the six
+// weighted sums follow at once, deferred: their results are read after its next synchronisation.
+int external_rows(pk_ctx* ctx, Proof& P) {
+    Arena& A = P.A;
+    const size_t nw = P.n_witness;
+    ALLOC(d_eq_alpha, (size_t)1 << P.s->m_0);
+    ALLOC(rows, 3 * (nw ? nw : 1));
+    P.rows = rows;
+    CK(pk_eq_table(ctx, (const uint64_t*)P.alpha.data(), P.s->m_0, U(d_eq_alpha)));
+    if (P.st_sharded) CK(external_row_range(ctx, P.s->r1cs, U(d_eq_alpha), P.blk_lo, std::min(nw, P.blk_lo + P.blk), U(rows)));  // this rank's columns
+    else CK(pk_r1cs_external_row(ctx, P.s->r1cs, U(d_eq_alpha), U(rows)));
+    if (ctx == P.ctx) return PK_OK;
+    return dot_rows_x(ctx, U(rows), nw, 3, U(P.W.f_evals), U(P.W.g_evals), nw, nullptr, /*defer=*/true);
+}
+
+// --- commit to the masked witness polynomial (whir_r1cs.rs:57-69).  Latency mode: the blinding commitment depends on nothing but the
+// proof's key -- 0.6 ms of launches that keep 32 lanes busy (its two leaf hashes are chains of 31 compressions).  Its device work goes
+// to the side stream right after the witness commitment's launches and runs underneath them, which fill the chip for 2.6 ms; only its
+// transcript half (root, OOD, batching) waits for its turn.
+int Proof::commit_witness() {
+    CK(batch_commit_compute(ctx, A, s->m, s->whir_witness, d_witness, n_witness, key, RNG_MASK, RNG_G, W));
+    if (aux != ctx) CK(relay(aux, blinding_compute(aux, *this), "blinding commitment"));
+    fe root;
+    CK(read_root(ctx, U(W.com.nodes), W.com.rows, (uint64_t*)root.v));
+    return whir_commit_transcript(ctx, s->whir_witness, root, T, W.com);
+}
+
+// the blinding commitment's transcript half.  Its root is read on the context that built the tree (on the side context that waits
+// for its stream and rewinds its mailbox), then the coefficients are taken out of the mailbox before anything is allocated there.
+int Proof::blinding_transcript() {
+    fe root;
+    CK(relay(aux, read_root(aux, U(B.com.nodes), B.com.rows, (uint64_t*)root.v), "blinding commitment"));
+    if (h_univ) memcpy(g_univ.data(), h_univ, 32 * g_univ.size());
+    return whir_commit_transcript(ctx, s->whir_hiding, root, T, B.com);
+}
+
+// zk sumcheck message (whir_r1cs.rs:280-345): the round polynomial c[0..3] of the blinded sum from the sumcheck's h(0), h(-1), h(inf)
+// (`out`), the blinding polynomial's round coefficients gp, rho and the running claim `saved`
+void zk_round_message(const uint64_t out[12], const fe gp[4], const fe& rho, const fe& saved, fe c[4]) {
+    const fe half = h_half();
+    c[0] = h_add(h_load(out), h_mul(rho, gp[0]));
+    const fe g_m1 = h_sub(h_add(h_sub(gp[0], gp[1]), gp[2]), gp[3]);
+    const fe at_m1 = h_add(h_load(out + 4), h_mul(rho, g_m1));
+    c[2] = h_mul(half, h_sub(h_sub(h_sub(h_add(saved, at_m1), c[0]), c[0]), c[0]));
+    c[3] = h_add(h_load(out + 8), h_mul(rho, gp[3]));
+    c[1] = h_sub(h_sub(h_sub(h_sub(saved, c[0]), c[0]), c[3]), c[2]);
+}
+
+// --- run_zk_sumcheck_prover (whir_r1cs.rs:228-369): witness bounds, eq table, blinding commitment, m_0 cubic rounds
+int Proof::zk_sumcheck() {
+    const unsigned m_0 = s->m_0;
+    std::vector<fe> r(m_0);
+    T.challenge_scalars(r.data(), m_0);
+    const size_t M0 = (size_t)1 << m_0;
+    // On a device set the four sumcheck arrays are split by the LOW index bits: rank g holds the entries i = g (mod G) at local
+    // index i / G (see "one proof over a device set" above).  eq(r, i) factors into eq over the high variables (the local
+    // table) times eq(last lgG variables, bits of g), a scalar that goes in as the table's scale.
+    const bool sharded = G > 1 && M0 / G >= 2 * SHARD_MIN_LOCAL;
+    const size_t length = sharded ? M0 / G : M0;
+    ALLOC(d_a, length);
+    ALLOC(d_b, length);
+    ALLOC(d_cc, length);
+    ALLOC(d_eq, length);
+    if (sharded) {
+        CK(witness_bounds_strided(ctx, s->r1cs, U(d_witness), m_0, G, rank, U(d_a), U(d_b), U(d_cc)));  // S1, this rank's rows
+        const fe sc = eq_bits(&r[m_0 - lgG], lgG, rank);
+        CK(pk_eq_accumulate(ctx, U(d_eq), m_0 - lgG, (const uint64_t*)r.data(), (const uint64_t*)&sc, 1, 1));  // S2
+    } else {
+        CK(pk_r1cs_witness_bounds(ctx, s->r1cs, U(d_witness), m_0, U(d_a), U(d_b), U(d_cc)));  // S1
+        CK(pk_eq_table(ctx, (const uint64_t*)r.data(), m_0, U(d_eq)));                       // S2
+    }
+    if (aux == ctx) CK(blinding_compute(ctx, *this));  // else the side stream finished it long ago
+    CK(blinding_transcript());
+    lap("bounds+eq+blinding commit");
+    fe* z[4] = {d_a, d_b, d_cc, d_eq};
+    return zk_rounds(z, length, sharded);
+}
+
+// the m_0 cubic rounds, each: the round's evaluations, the message, absorb, squeeze, record.  Latency mode (one GPU): round idx+1 is
+// in the queue, gated on a_idx, while round idx is absorbed.  Otherwise every round is a synchronous call that first folds by the
+// previous challenge (sharded: its evaluations are sums over the ranks' shares; short shares are gathered and finish replicated).
+int Proof::zk_rounds(fe* z[4], size_t length, bool sharded) {
+    const unsigned m_0 = s->m_0;
+    // sum_over_hypercube (whir_r1cs.rs:172-180)
+    fe gp[4];
+    blinding_coefficients_for_round(g_univ, 0, nullptr, gp);
+    const fe sum_g = h_add(eval_cubic(gp, fe_zero()), eval_cubic(gp, fe_one()));
+    T.add_scalar(sum_g);
+    const fe rho = T.challenge_scalar();
+    fe saved = h_mul(rho, sum_g);
+    fe* zfull[4] = {nullptr, nullptr, nullptr, nullptr};
+    fe* ztmp = nullptr;
+    if (sharded) {
+        const size_t cap = G * SHARD_MIN_LOCAL;
+        for (int q = 0; q < 4; q++) {
+            ALLOC(zf, cap);
+            zfull[q] = zf;
+        }
+        ALLOC(zt, cap);
+        ztmp = zt;
+    }
+    const bool pipelined = ctx->latency_mode && G == 1 && m_0 >= 2;
+    unsigned red_cur = 0, red_next = 0;
+    if (pipelined) CK(sumcheck_cubic_launch(ctx, U(z[0]), U(z[1]), U(z[2]), U(z[3]), length, nullptr, 0, &red_cur));
+    alpha.reserve(m_0);
+    for (unsigned idx = 0; idx < m_0; idx++) {  // the hot loop, whir_r1cs.rs:280-345
+        PendingGate gate(ctx);
+        if (pipelined && idx + 1 < m_0) {
+            gate.arm(sumcheck_gate_next(ctx));
+            CK(sumcheck_cubic_launch(ctx, U(z[0]), U(z[1]), U(z[2]), U(z[3]), length, nullptr, gate.seq, &red_next));
+            length /= 2;
+        }
+        // the round's blinding coefficients depend only on the earlier challenges: in latency mode computed while the kernel runs
+        blinding_coefficients_for_round(g_univ, idx, alpha.data(), gp);
+        uint64_t out[12], f[4];
+        if (pipelined) {
+            CK(sumcheck_collect_spin(ctx, red_cur, out));
+            red_cur = red_next;
+        } else {
+            if (sharded && length <= SHARD_MIN_LOCAL) {  // short shares: gather, re-interleave, finish replicated
+                for (int q = 0; q < 4; q++) {
+                    CK(gather_strided(ctx, z[q], length, ztmp, zfull[q]));
+                    z[q] = zfull[q];
+                }
+                length *= G;
+                sharded = false;
+            }
+            Across ac(ctx, sharded);  // sharded: the three evaluations are sums over the ranks' shares
+            CK(ac.rc);
+            if (idx) h_store(f, alpha.back());
+            CK(pk_sumcheck_cubic_round(ctx, U(z[0]), U(z[1]), U(z[2]), U(z[3]), length, idx ? f : nullptr, out));
+            if (idx) length /= 2;
+        }
+        fe c[4];
+        zk_round_message(out, gp, rho, saved, c);
+        T.add_scalars(c, 4);
+        const fe a_i = T.challenge_scalar();
+        gate.publish(a_i);
+        alpha.push_back(a_i);
+        saved = eval_cubic(c, a_i);
+    }
+    return PK_OK;
+}
+
+// --- statement over the blinding commitment: weight = expand_powers(alpha) zero-extended (whir_r1cs.rs:347-366,371-380), and its
+// WHIR proof.  Latency mode: the witness statement's external rows and its six weighted sums depend on alpha and nothing else, and
+// the transcript wants them only AFTER this proof -- 0.4 ms of kernels that go to the side stream first and run underneath it.
+int Proof::prove_blinding() {
+    if (rows_ctx() != ctx) CK(relay(aux, external_rows(aux, *this), "external rows"));
+    const size_t nbw = 4 * (size_t)s->m_0;  // the weight is zero beyond the 4 m_0 blinding coefficients
+    std::vector<fe> wv(nbw);
+    for (size_t i = 0; i < s->m_0; i++) {
+        wv[4 * i] = fe_one();
+        wv[4 * i + 1] = alpha[i];
+        wv[4 * i + 2] = h_mul(alpha[i], alpha[i]);
+        wv[4 * i + 3] = h_mul(wv[4 * i + 2], alpha[i]);
+    }
+    ALLOC(d_bw, nbw);
+    CK(pk_memcpy_h2d(ctx, d_bw, wv.data(), 32 * nbw));
+    uint64_t fg[8];
+    CK(pk_dot2(ctx, U(d_bw), U(B.f_evals), U(B.g_evals), nbw, fg));
+    const fe sums[2] = {h_load(fg), h_load(fg + 4)};
+    T.add_scalars(sums, 2);
+    fe* wts[1] = {d_bw};
+    return whir_prove(ctx, A, s->whir_hiding, B.com, wts, &nbw, 1, T);
+}
+
+// --- the statement over the witness commitment (whir_r1cs.rs:81-91): external rows, their six sums, the claimed_evaluations hint
+int Proof::witness_statement() {
+    pk_ctx* rc = rows_ctx();
+    if (rc == ctx) CK(external_rows(ctx, *this));
+    Across ac(ctx, st_sharded);
+    CK(ac.rc);
+    // the statement weights are the rows zero-extended to 2^m (whir_r1cs.rs:391-400): only their support is stored and summed;
+    // the three rows share f and g, so all six sums come from one pass (S5)
+    uint64_t o[24] = {};
+    if (rc != ctx) {  // launched before the blinding WHIR proof: finished long ago
+        CK(relay(rc, sync_stream(rc), "external rows"));
+        memcpy(o, rc->h_pinned, 32 * 6);
+    } else if (st_sharded || n_witness) {
+        CK(dot_rows(ctx, U(rows + blk_lo), n_witness, 3, U(W.f_evals + blk_lo), U(W.g_evals + blk_lo), in_block(n_witness, blk_lo, blk), o));
+    }
+    // hint::<(Vec<F>, Vec<F>)>: the three sums against f, then the three against g
+    fe fsum[3], gsum[3];
+    for (int k = 0; k < 3; k++) {
+        fsum[k] = h_load(o + 8 * k);
+        gsum[k] = h_load(o + 8 * k + 4);
+    }
+    std::vector<uint8_t> claimed;
+    put_vec(claimed, fsum, 3);
+    put_vec(claimed, gsum, 3);
+    T.hint(claimed.data(), claimed.size());
+    return PK_OK;
+}
+
+// --- WHIR weighted batch opening (whir_r1cs.rs:94-95)
+int Proof::prove_witness() {
+    fe* wts[3] = {rows, rows + n_witness, rows + 2 * n_witness};
+    const size_t wlen[3] = {n_witness, n_witness, n_witness};
+    CK(whir_prove(ctx, A, s->whir_witness, W.com, wts, wlen, 3, T));
+    return pk_ctx_sync(ctx);
+}
+
+// WhirR1CSProver::prove (provekit/prover/src/whir_r1cs.rs:42-100): the proof string into `narg`
+int prove(pk_ctx* ctx, pk_scheme* s, const uint64_t* d_witness, size_t n_witness, const uint8_t* rng_seed32, const size_t* len,
+          std::vector<uint8_t>& narg) {
+    PK_REQUIRE(ctx, s && d_witness && len, "null pointer");
+    PK_REQUIRE(ctx, n_witness == s->num_witnesses, "Unexpected witness length for R1CS instance");  // whir_r1cs.rs:43-46
+    RngKey key;
+    CK(proof_key(ctx, rng_seed32, key));
+    struct Turn {  // see comm.hip: a no-op outside the test-suite's one-GPU timing mode
+        pk_ctx* c;
+        explicit Turn(pk_ctx* ctx) : c(ctx) { comm_turn_begin(c); }
+        ~Turn() { comm_turn_end(c); }
+    } turn(ctx);
+    Proof P(ctx, s, (const fe*)d_witness, n_witness, key);
+    CK(P.init());
+    (void)sumcheck_gate_check(ctx);  // a word left by an earlier, abandoned proof is not this proof's
+    CK(P.commit_witness());
+    P.lap("witness commit");
+    CK(P.zk_sumcheck());
+    P.lap("zk sumcheck rounds");
+    CK(P.prove_blinding());
+    P.lap("blinding WHIR proof");
+    CK(P.witness_statement());
+    P.lap("external rows + sums");
+    CK(P.prove_witness());
+    P.lap("witness WHIR proof");
+    // latency mode: every gated kernel of this proof has completed by now; one that gave up on its challenge computed with zero
+    CK(sumcheck_gate_check(ctx));
+    // the proof performed exactly the operations its IO pattern declares (what spongefish enforces on the reference's side)
+    if (!P.T.finished())
+        return set_err(ctx, PK_ERR_IO_PATTERN, "%s", P.T.violation().empty() ? "the proof ended before its IO pattern did" : P.T.violation().c_str());
+    narg = std::move(P.T.narg);
+    return PK_OK;
+}
+
+// the blinding polynomial's variables less one: 2^nb = next_power_of_two(4 m_0)
+unsigned blinding_log_len(unsigned m_0) {
+    unsigned nb = 0;
+    while (((size_t)1 << nb) < 4 * (size_t)m_0) nb++;
+    return nb;
+}
 
 }  // namespace
 
@@ -1048,7 +1386,7 @@ static size_t scheme_arena_bytes(unsigned m, unsigned m_0, size_t num_witnesses,
     return (size_t)(1.05 * 32.0 * fes) + ((size_t)64 << 20);
 }
 int pk_scheme_arena_bytes(unsigned m, unsigned m_0, size_t num_witnesses, const pk_whir_config* whir_witness, size_t* bytes) {
-    if (!whir_witness || !bytes || m > 28 || m_0 > m) return PK_ERR_BAD_ARG;
+    if (!bytes || m > 28 || m_0 > m || whir_config_error(whir_witness)) return PK_ERR_BAD_ARG;
     *bytes = scheme_arena_bytes(m, m_0, num_witnesses, *whir_witness);
     return PK_OK;
 }
@@ -1067,17 +1405,10 @@ int pk_scheme_create(pk_ctx* ctx, const pk_r1cs* r1cs, size_t num_constraints, s
     // pk_prove commits the blinding polynomial next to its mask exactly as the witness (whir_r1cs.rs:212-226): batch 2, nothing else
     PK_REQUIRE(ctx, whir_for_hiding_spartan->batch_size == 2, "whir_for_hiding_spartan must have batch_size 2");
     for (const pk_whir_config* c : {whir_witness, whir_for_hiding_spartan}) {
-        PK_REQUIRE(ctx, c->folding_factor >= 1 && c->folding_factor <= 8 && c->n_rounds <= PK_MAX_WHIR_ROUNDS, "bad WHIR config");
-        PK_REQUIRE(ctx, c->n_vars >= c->folding_factor * (c->n_rounds + 1), "WHIR rounds exceed the number of variables");
-        PK_REQUIRE(ctx, c->commitment_ood_samples <= 4, "too many OOD samples");
-        PK_REQUIRE(ctx, c->batch_size >= 1 && c->batch_size <= 4, "batch size out of range");
-        // the evaluation domain must exist in BN254-Fr (two-adicity 28) and the codeword must fit pk_rs_encode's bound
-        PK_REQUIRE(ctx, c->starting_log_inv_rate >= 1 && c->n_vars + c->starting_log_inv_rate <= 28, "n_vars + starting_log_inv_rate exceeds 28");
-        PK_REQUIRE(ctx, c->n_vars + c->starting_log_inv_rate - c->folding_factor <= 27, "codeword has more than 2^27 rows");
-        for (unsigned r = 0; r < c->n_rounds; r++) PK_REQUIRE(ctx, c->ood_samples[r] <= 4, "too many OOD samples");
+        const char* why = whir_config_error(c);
+        PK_REQUIRE(ctx, !why, why);
     }
-    unsigned nb = 0;
-    while (((size_t)1 << nb) < 4 * (size_t)m_0) nb++;
+    const unsigned nb = blinding_log_len(m_0);
     PK_REQUIRE(ctx, whir_for_hiding_spartan->n_vars == nb + 1, "whir_for_hiding_spartan must have next_power_of_two(4*m_0)+1 variables");
     pk_scheme* s = new (std::nothrow) pk_scheme();
     if (!s) return PK_ERR_OOM;
@@ -1086,6 +1417,7 @@ int pk_scheme_create(pk_ctx* ctx, const pk_r1cs* r1cs, size_t num_constraints, s
     s->num_witnesses = num_witnesses;
     s->m = m;
     s->m_0 = m_0;
+    s->nb = nb;
     s->whir_witness = *whir_witness;
     s->whir_hiding = *whir_for_hiding_spartan;
     s->domain_separator = whir_r1cs_io_pattern(s->m_0, s->whir_witness, s->whir_hiding);
@@ -1102,329 +1434,12 @@ int pk_prove(pk_ctx* ctx, pk_scheme* s, const uint64_t* d_witness, size_t n_witn
              size_t cap, size_t* len) {
     PK_ENTER(ctx);
     AbortOnFailure guard(ctx);  // before the argument checks: a rank refused here never joins its peers' collectives either
-    PK_REQUIRE(ctx, s && d_witness && len, "null pointer");
-    PK_REQUIRE(ctx, n_witness == s->num_witnesses, "Unexpected witness length for R1CS instance");  // whir_r1cs.rs:43-46
-    RngKey key;
-    {
-        int rc = proof_key(ctx, rng_seed32, key);
-        if (rc) return rc;
-    }
-    struct Turn {  // see comm.hip: a no-op outside the test-suite's one-GPU timing mode
-        pk_ctx* c;
-        explicit Turn(pk_ctx* ctx) : c(ctx) { comm_turn_begin(c); }
-        ~Turn() { comm_turn_end(c); }
-    } turn(ctx);
-    Arena A{s->arena, s->arena_bytes};
-    Transcript T(s->domain_separator);
-    (void)sumcheck_gate_check(ctx);  // a word left by an earlier, abandoned proof is not this proof's
-    const bool timing = getenv("PK_PROVE_TIMING") != nullptr;
-    auto now = [] { return std::chrono::steady_clock::now(); };
-    auto t_start = now();
-    auto lap = [&](const char* what) {
-        if (!timing) return;
-        (void)wait_ctx(ctx);
-        auto t = now();
-        fprintf(stderr, "[pk_prove] %-28s %8.3f ms (sponge: %u permutes, %.3f ms; hint serialisation so far %.3f ms)\n", what,
-                1e3 * std::chrono::duration<double>(t - t_start).count(), T.permutes, 1e3 * T.permute_seconds, 1e3 * T.hint_seconds);
-        t_start = t;
-    };
-    const unsigned m = s->m, m_0 = s->m_0;
-
-    // blinding univariates: 4 random coefficients per variable [RNG], committed with the small WHIR (whir_r1cs.rs:212-226)
-    unsigned nb = 0;
-    while (((size_t)1 << nb) < 4 * (size_t)m_0) nb++;
-    const size_t NB = (size_t)1 << nb;
-    BatchCommit B;
-    fe* d_blind = nullptr;
-    fe* side_univ = nullptr;  // pinned: the 4 m_0 blinding coefficients as the side stream copied them out
-    // Latency mode, one GPU: the blinding commitment depends on nothing but the proof's key -- 0.6 ms of launches that keep 32 lanes
-    // busy (its two leaf hashes are chains of 31 compressions).  Its device work goes to a second stream NOW and runs underneath the
-    // witness commitment, which fills the chip for 2.6 ms; only the transcript half (root, OOD, batching) waits for its turn.
-    const bool overlap_blinding = ctx->latency_mode && comm_world(ctx) == 1 && !getenv("PK_NO_BLINDING_OVERLAP");  // (the env switch: A/B only)
-    struct SideDrain {  // whatever path leaves pk_prove, the side stream must not still be working in this proof's arena
-        pk_scheme* s;
-        bool used = false;
-        ~SideDrain() {
-            if (used && s->side) {
-                (void)wait_stream(s->side->device, s->side->stream);
-                s->side->mail_off = 0;
-            }
-        }
-    } side_drain{s};
-    // --- commit to the masked witness polynomial (whir_r1cs.rs:57-69)
-    BatchCommit W;
-    if (overlap_blinding) {
-        side_drain.used = true;
-        // the witness commitment's launches first (the chip starts on them at once), then the side stream's, then the witness root
-        CK(batch_commit_compute(ctx, A, m, s->whir_witness, (const fe*)d_witness, n_witness, key, RNG_MASK, RNG_G, W));
-        if (!s->side) {
-            int dev = 0;
-            PK_HIP(ctx, hipGetDevice(&dev));
-            CK(pk_ctx_create(dev, &s->side));
-        }
-        pk_ctx* sc = s->side;
-        sc->hash_version = ctx->hash_version;
-        d_blind = A.alloc(NB);
-        if (!d_blind) return set_err(ctx, PK_ERR_OOM, "prover arena exhausted (d_blind)");
-        int rc = pk_memset_zero(sc, d_blind, 32 * NB);
-        if (!rc) {
-            random_fe_kernel<<<1, 256, 0, sc->stream>>>(d_blind, 4 * (size_t)m_0, key, RNG_BLIND);
-            rc = mail_alloc(sc, 32 * 4 * (size_t)m_0, (void**)&side_univ);
-        }
-        if (!rc && hipMemcpyAsync(side_univ, d_blind, 32 * 4 * (size_t)m_0, hipMemcpyDeviceToHost, sc->stream) != hipSuccess) rc = PK_ERR_HIP;
-        if (!rc) rc = batch_commit_compute(sc, A, nb + 1, s->whir_hiding, d_blind, NB, key, RNG_MASK_B, RNG_G_B, B);
-        if (rc) return set_err(ctx, rc, "blinding commitment on the side stream: %s", pk_last_error(sc));
-        fe root_w;
-        CK(read_root(ctx, U(W.com.nodes), W.com.rows, (uint64_t*)root_w.v));
-        CK(whir_commit_transcript(ctx, s->whir_witness, root_w, T, W.com));
-    } else {
-        CK(batch_commit(ctx, A, m, s->whir_witness, (const fe*)d_witness, n_witness, key, RNG_MASK, RNG_G, T, W));
-    }
-
-    lap("witness commit");
-    // --- run_zk_sumcheck_prover (whir_r1cs.rs:228-369)
-    std::vector<fe> r(m_0);
-    T.challenge_scalars(r.data(), m_0);
-    const size_t M0 = (size_t)1 << m_0;
-    // On a device set the four sumcheck arrays are split by the LOW index bits: rank g holds the entries i = g (mod G) at local
-    // index i / G (see "one proof over a device set" above).  eq(r, i) factors into eq over the high variables (the local
-    // table) times eq(last lgG variables, bits of g), a scalar that goes in as the table's scale.
-    const unsigned G = (unsigned)comm_world(ctx), lgG = ilog2(G), rank = (unsigned)comm_rank(ctx);
-    bool zk_sharded = G > 1 && M0 / G >= 2 * SHARD_MIN_LOCAL;
-    const size_t Lz = zk_sharded ? M0 / G : M0;
-    ALLOC(d_a, Lz);
-    ALLOC(d_b, Lz);
-    ALLOC(d_cc, Lz);
-    ALLOC(d_eq, Lz);
-    if (zk_sharded) {
-        CK(witness_bounds_strided(ctx, s->r1cs, d_witness, m_0, G, rank, U(d_a), U(d_b), U(d_cc)));  // S1, this rank's rows
-        const fe sc = eq_bits(&r[m_0 - lgG], lgG, rank);
-        CK(pk_eq_accumulate(ctx, U(d_eq), m_0 - lgG, (const uint64_t*)r.data(), (const uint64_t*)&sc, 1, 1));  // S2
-    } else {
-        CK(pk_r1cs_witness_bounds(ctx, s->r1cs, d_witness, m_0, U(d_a), U(d_b), U(d_cc)));  // S1
-        CK(pk_eq_table(ctx, (const uint64_t*)r.data(), m_0, U(d_eq)));                       // S2
-    }
-    std::vector<fe> g_univ(4 * (size_t)m_0);
-    if (overlap_blinding) {  // the side stream finished long ago: take its root and the coefficients, then the transcript half here
-        pk_ctx* sc = s->side;
-        if (wait_stream(sc->device, sc->stream) != hipSuccess) return set_err(ctx, PK_ERR_HIP, "side stream synchronisation failed");
-        memcpy(g_univ.data(), side_univ, 32 * g_univ.size());
-        sc->mail_off = 0;
-        fe root_b;
-        if (B.com.rows < 2) CK(pk_memcpy_d2h(ctx, root_b.v, B.com.nodes + 1, 32));
-        else memcpy(root_b.v, (char*)sc->h_pinned + PK_PIN_ROOT, 32);
-        CK(whir_commit_transcript(ctx, s->whir_hiding, root_b, T, B.com));
-    } else {
-        ALLOC(d_blind_, NB);
-        d_blind = d_blind_;
-        CK(pk_memset_zero(ctx, d_blind, 32 * NB));
-        random_fe_kernel<<<1, 256, 0, ctx->stream>>>(d_blind, 4 * (size_t)m_0, key, RNG_BLIND);
-        PK_LAUNCH_CHECK(ctx);
-        CK(pk_memcpy_d2h(ctx, g_univ.data(), d_blind, 32 * g_univ.size()));
-        CK(batch_commit(ctx, A, nb + 1, s->whir_hiding, d_blind, NB, key, RNG_MASK_B, RNG_G_B, T, B));
-    }
-    lap("bounds+eq+blinding commit");
-    // sum_over_hypercube (whir_r1cs.rs:172-180)
-    fe sum_g;
-    {
-        fe c[4];
-        blinding_coefficients_for_round(g_univ, 0, nullptr, c);
-        sum_g = h_add(eval_cubic(c, fe_zero()), eval_cubic(c, fe_one()));
-    }
-    T.add_scalar(sum_g);
-    const fe rho = T.challenge_scalar();
-    fe saved = h_mul(rho, sum_g);
-    std::vector<fe> alpha;
-    alpha.reserve(m_0);
-    {
-        size_t length = Lz;  // local length while sharded
-        const fe half = h_half();
-        fe *za = d_a, *zb = d_b, *zc = d_cc, *ze = d_eq;
-        fe* zfull[4] = {nullptr, nullptr, nullptr, nullptr};
-        fe* ztmp = nullptr;
-        if (zk_sharded) {
-            const size_t cap = G * SHARD_MIN_LOCAL;
-            for (int q = 0; q < 4; q++) {
-                ALLOC(zf, cap);
-                zfull[q] = zf;
-            }
-            ALLOC(zt, cap);
-            ztmp = zt;
-        }
-        const bool pipelined = ctx->latency_mode && G == 1 && m_0 >= 2;
-        unsigned red_cur = 0, red_next = 0;
-        if (pipelined) CK(sumcheck_cubic_launch(ctx, U(za), U(zb), U(zc), U(ze), length, nullptr, 0, &red_cur));
-        double t_launch = 0, t_wait = 0, t_host = 0;  // PK_PROVE_TIMING: where a pipelined round's wall time goes
-        for (unsigned idx = 0; pipelined && idx < m_0; idx++) {  // latency mode: round idx+1 is in the queue, gated, while round idx is absorbed
-            PendingGate gate(ctx);
-            auto q0 = now();
-            if (idx + 1 < m_0) {
-                gate.arm(sumcheck_gate_next(ctx));
-                CK(sumcheck_cubic_launch(ctx, U(za), U(zb), U(zc), U(ze), length, nullptr, gate.seq, &red_next));
-                length /= 2;
-            }
-            // the round's blinding coefficients depend only on the earlier challenges: computed while the kernel runs
-            fe gp[4];
-            blinding_coefficients_for_round(g_univ, idx, alpha.data(), gp);
-            const fe g_m1 = h_sub(h_add(h_sub(gp[0], gp[1]), gp[2]), gp[3]);
-            const fe rg0 = h_mul(rho, gp[0]), rgm1 = h_mul(rho, g_m1), rg3 = h_mul(rho, gp[3]);
-            auto q1 = now();
-            uint64_t out[12];
-            CK(sumcheck_collect_spin(ctx, red_cur, out));
-            auto q2 = now();
-            t_launch += std::chrono::duration<double>(q1 - q0).count();
-            t_wait += std::chrono::duration<double>(q2 - q1).count();
-            const fe h0 = h_load(out), hm1 = h_load(out + 4), hinf = h_load(out + 8);
-            fe c[4];
-            c[0] = h_add(h0, rg0);
-            const fe at_m1 = h_add(hm1, rgm1);
-            c[2] = h_mul(half, h_sub(h_sub(h_sub(h_add(saved, at_m1), c[0]), c[0]), c[0]));
-            c[3] = h_add(hinf, rg3);
-            c[1] = h_sub(h_sub(h_sub(h_sub(saved, c[0]), c[0]), c[3]), c[2]);
-            T.add_scalars(c, 4);
-            const fe a_i = T.challenge_scalar();
-            gate.publish(a_i);
-            alpha.push_back(a_i);
-            saved = eval_cubic(c, a_i);
-            red_cur = red_next;
-            t_host += std::chrono::duration<double>(now() - q2).count();
-        }
-        if (timing && pipelined)
-            fprintf(stderr, "[pk_prove]   pipelined cubic rounds: launch %.3f ms, wait %.3f ms, host %.3f ms\n", 1e3 * t_launch, 1e3 * t_wait, 1e3 * t_host);
-        for (unsigned idx = 0; !pipelined && idx < m_0; idx++) {  // the hot loop, whir_r1cs.rs:280-345
-            uint64_t out[12], f[4];
-            if (zk_sharded && length <= SHARD_MIN_LOCAL) {  // short shares: gather, re-interleave, finish replicated
-                fe* loc[4] = {za, zb, zc, ze};
-                for (int q = 0; q < 4; q++) CK(gather_strided(ctx, loc[q], length, ztmp, zfull[q]));
-                za = zfull[0]; zb = zfull[1]; zc = zfull[2]; ze = zfull[3];
-                length *= G;
-                zk_sharded = false;
-            }
-            Across ac(ctx, zk_sharded);  // sharded: the three evaluations are sums over the ranks' shares
-            CK(ac.rc);
-            if (idx == 0) {
-                CK(pk_sumcheck_cubic_round(ctx, U(za), U(zb), U(zc), U(ze), length, nullptr, out));
-            } else {
-                h_store(f, alpha.back());
-                CK(pk_sumcheck_cubic_round(ctx, U(za), U(zb), U(zc), U(ze), length, f, out));
-                length /= 2;
-            }
-            const fe h0 = h_load(out), hm1 = h_load(out + 4), hinf = h_load(out + 8);
-            fe gp[4];
-            blinding_coefficients_for_round(g_univ, idx, alpha.data(), gp);
-            fe c[4];
-            c[0] = h_add(h0, h_mul(rho, gp[0]));
-            const fe g_m1 = h_sub(h_add(h_sub(gp[0], gp[1]), gp[2]), gp[3]);
-            const fe at_m1 = h_add(hm1, h_mul(rho, g_m1));
-            c[2] = h_mul(half, h_sub(h_sub(h_sub(h_add(saved, at_m1), c[0]), c[0]), c[0]));
-            c[3] = h_add(hinf, h_mul(rho, gp[3]));
-            c[1] = h_sub(h_sub(h_sub(h_sub(saved, c[0]), c[0]), c[3]), c[2]);
-            T.add_scalars(c, 4);
-            const fe a_i = T.challenge_scalar();
-            alpha.push_back(a_i);
-            saved = eval_cubic(c, a_i);
-        }
-    }
-    lap("zk sumcheck rounds");
-    // latency mode: the witness statement's external rows and its six weighted sums depend on alpha and nothing else, and the transcript
-    // wants them only AFTER the blinding WHIR proof -- 0.4 ms of kernels that go to the side stream now and run underneath that proof
-    fe* d_eq_alpha_side = nullptr;
-    fe* d_rows_side = nullptr;
-    const bool overlap_rows = overlap_blinding && n_witness > 0;
-    if (overlap_rows) {
-        pk_ctx* sc = s->side;
-        d_eq_alpha_side = A.alloc((size_t)1 << m_0);
-        d_rows_side = A.alloc(3 * n_witness);
-        if (!d_eq_alpha_side || !d_rows_side) return set_err(ctx, PK_ERR_OOM, "prover arena exhausted (external rows)");
-        int rc = pk_eq_table(sc, (const uint64_t*)alpha.data(), m_0, U(d_eq_alpha_side));
-        if (!rc) rc = pk_r1cs_external_row(sc, s->r1cs, U(d_eq_alpha_side), U(d_rows_side));
-        if (!rc) rc = dot_rows_x(sc, U(d_rows_side), n_witness, 3, U(W.f_evals), U(W.g_evals), n_witness, nullptr, /*defer=*/true);
-        if (rc) return set_err(ctx, rc, "external rows on the side stream: %s", pk_last_error(sc));
-    }
-    // statement over the blinding commitment: weight = expand_powers(alpha) zero-extended (whir_r1cs.rs:347-366,371-380)
-    {
-        const size_t NB2 = 2 * NB;
-        std::vector<fe> wv(NB2, fe_zero());
-        for (unsigned i = 0; i < m_0; i++) {
-            wv[4 * i] = fe_one();
-            wv[4 * i + 1] = alpha[i];
-            wv[4 * i + 2] = h_mul(alpha[i], alpha[i]);
-            wv[4 * i + 3] = h_mul(wv[4 * i + 2], alpha[i]);
-        }
-        const size_t nbw = 4 * (size_t)m_0;  // the weight is zero beyond the 4 m_0 blinding coefficients
-        ALLOC(d_bw, nbw);
-        CK(pk_memcpy_h2d(ctx, d_bw, wv.data(), 32 * nbw));
-        uint64_t fg[8];
-        CK(pk_dot2(ctx, U(d_bw), U(B.f_evals), U(B.g_evals), nbw, fg));
-        fe sums[2] = {h_load(fg), h_load(fg + 4)};
-        T.add_scalars(sums, 2);
-        fe* wts[1] = {d_bw};
-        CK(whir_prove(ctx, A, s->whir_hiding, B.com, wts, &nbw, 1, T));
-    }
-    lap("blinding WHIR proof");
-    // --- external rows and the statement over the witness commitment (whir_r1cs.rs:81-91, 382-412)
-    // sharded witness WHIR: a rank needs (and computes) only the columns of the rows inside its block of the hypercube
-    const bool st_sharded = whir_sharded(ctx, m);
-    const size_t blk = st_sharded ? ((size_t)1 << m) / G : (size_t)1 << m, blk_lo = st_sharded ? (size_t)rank * blk : 0;
-    const size_t col_hi = n_witness < blk_lo + blk ? n_witness : blk_lo + blk, col_n = col_hi > blk_lo ? col_hi - blk_lo : 0;
-    fe* d_rows = d_rows_side;
-    if (!overlap_rows) {
-        ALLOC(d_eq_alpha, M0);
-        CK(pk_eq_table(ctx, (const uint64_t*)alpha.data(), m_0, U(d_eq_alpha)));
-        ALLOC(d_rows_, 3 * (n_witness ? n_witness : 1));
-        d_rows = d_rows_;
-        if (st_sharded) CK(external_row_range(ctx, s->r1cs, U(d_eq_alpha), blk_lo, col_hi, U(d_rows)));  // S4, this rank's columns
-        else CK(pk_r1cs_external_row(ctx, s->r1cs, U(d_eq_alpha), U(d_rows)));                            // S4
-    }
-    fe* wts[3];
-    const size_t wlen[3] = {n_witness, n_witness, n_witness};
-    std::vector<uint8_t> claimed;
-    {
-        std::vector<fe> fsum(3), gsum(3);
-        Across ac(ctx, st_sharded);
-        CK(ac.rc);
-        // the statement weights are the rows zero-extended to 2^m (whir_r1cs.rs:391-400): only their support is stored and summed;
-        // the three rows share f and g, so all six sums come from one pass (S5)
-        for (int k = 0; k < 3; k++) wts[k] = d_rows + (size_t)k * n_witness;
-        uint64_t o[24] = {};
-        if (overlap_rows) {  // launched before the blinding WHIR proof: finished long ago
-            CK(sync_stream(s->side));
-            memcpy(o, s->side->h_pinned, 32 * 6);
-        } else if (st_sharded || n_witness) {
-            CK(dot_rows(ctx, U(d_rows + blk_lo), n_witness, 3, U(W.f_evals + blk_lo), U(W.g_evals + blk_lo), col_n, o));
-        }
-        for (int k = 0; k < 3; k++) {
-            fsum[k] = h_load(o + 8 * k);
-            gsum[k] = h_load(o + 8 * k + 4);
-        }
-        // hint::<(Vec<F>, Vec<F>)>: two ark-serialize vectors (u64 length + canonical elements)
-        for (const std::vector<fe>* v : {&fsum, &gsum}) {
-            uint64_t cnt = 3;
-            for (int i = 0; i < 8; i++) claimed.push_back((uint8_t)(cnt >> (8 * i)));
-            for (const fe& x : *v) {
-                fe c = h_to_canon(x);
-                const uint8_t* b = (const uint8_t*)c.v;
-                claimed.insert(claimed.end(), b, b + 32);
-            }
-        }
-    }
-    T.hint(claimed.data(), claimed.size());
-    lap("external rows + sums");
-    // --- WHIR weighted batch opening (whir_r1cs.rs:94-95)
-    CK(whir_prove(ctx, A, s->whir_witness, W.com, wts, wlen, 3, T));
-    CK(pk_ctx_sync(ctx));
-    lap("witness WHIR proof");
-    // latency mode: every gated kernel of this proof has completed by now; one that gave up on its challenge computed with zero
-    CK(sumcheck_gate_check(ctx));
-    // the proof performed exactly the operations its IO pattern declares (what spongefish enforces on the reference's side)
-    if (!T.finished())
-        return set_err(ctx, PK_ERR_IO_PATTERN, "%s", T.violation().empty() ? "the proof ended before its IO pattern did" : T.violation().c_str());
-
-    guard.ok = true;  // every collective of this proof has been passed
-    *len = T.narg.size();
+    std::vector<uint8_t> narg;
+    if (int rc = guard.done(prove(ctx, s, d_witness, n_witness, rng_seed32, len, narg))) return rc;
+    *len = narg.size();
     if (!transcript_out) return PK_OK;  // size query
-    PK_REQUIRE(ctx, cap >= T.narg.size(), "transcript buffer too small");
-    memcpy(transcript_out, T.narg.data(), T.narg.size());
+    PK_REQUIRE(ctx, cap >= narg.size(), "transcript buffer too small");
+    memcpy(transcript_out, narg.data(), narg.size());
     return PK_OK;
 }
 
@@ -1570,17 +1585,16 @@ int pk_noir_prove(pk_ctx* ctx, pk_scheme* s, pk_witness_program* builders, const
         if (rc) return rc;
     }
     AbortOnFailure guard(ctx);  // a witness that fails to solve on this rank only must not leave the others inside pk_prove's collectives
-    int rc = pk_witness_challenges(s->num_constraints, nw, pub.data(), n_public, chal.data(), n_chal);
-    if (rc) return set_err(ctx, rc, "witness transcript");
-    rc = pk_witness_solve(ctx, builders, d_acir, n_acir, chal.data(), n_chal, d_w, nw, d_set);
-    if (rc) return rc;
-    RngKey key;  // one key for the fill and the proof's masks (distinct streams)
-    rc = proof_key(ctx, rng_seed32, key);
-    if (rc) return rc;
-    rc = pk_witness_fill(ctx, d_w, d_set, nw, (const uint8_t*)key.k, nullptr);
-    if (rc) return rc;
-    guard.ok = true;  // pk_prove carries its own guard
-    return pk_prove(ctx, s, d_w, nw, (const uint8_t*)key.k, transcript_out, cap, len);
+    RngKey key;                 // one key for the fill and the proof's masks (distinct streams)
+    auto witness = [&]() -> int {
+        int rc = pk_witness_challenges(s->num_constraints, nw, pub.data(), n_public, chal.data(), n_chal);
+        if (rc) return set_err(ctx, rc, "witness transcript");
+        CK(pk_witness_solve(ctx, builders, d_acir, n_acir, chal.data(), n_chal, d_w, nw, d_set));
+        CK(proof_key(ctx, rng_seed32, key));
+        return pk_witness_fill(ctx, d_w, d_set, nw, (const uint8_t*)key.k, nullptr);
+    };
+    if (int rc = guard.done(witness())) return rc;
+    return pk_prove(ctx, s, d_w, nw, (const uint8_t*)key.k, transcript_out, cap, len);  // pk_prove carries its own guard
 }
 
 int pk_scheme_domain_separator(const pk_scheme* s, char* buf, size_t cap, size_t* len) {
@@ -1590,14 +1604,9 @@ int pk_scheme_domain_separator(const pk_scheme* s, char* buf, size_t cap, size_t
     return PK_OK;
 }
 
-static bool whir_config_sane(const pk_whir_config* c) {
-    return c && c->folding_factor >= 1 && c->folding_factor <= 8 && c->n_rounds <= PK_MAX_WHIR_ROUNDS && c->batch_size >= 1 && c->batch_size <= 4 &&
-           c->n_vars >= c->folding_factor * (c->n_rounds + 1) && c->n_vars + c->starting_log_inv_rate <= 28 && c->commitment_ood_samples <= 4;
-}
-
 int pk_whir_r1cs_io_pattern(unsigned m_0, const pk_whir_config* whir_witness, const pk_whir_config* whir_for_hiding_spartan, uint8_t* buf,
                             size_t cap, size_t* len) {
-    if (!len || m_0 < 1 || m_0 > 27 || !whir_config_sane(whir_witness) || !whir_config_sane(whir_for_hiding_spartan)) return PK_ERR_BAD_ARG;
+    if (!len || m_0 < 1 || m_0 > 27 || whir_config_error(whir_witness) || whir_config_error(whir_for_hiding_spartan)) return PK_ERR_BAD_ARG;
     const std::string p = whir_r1cs_io_pattern(m_0, *whir_witness, *whir_for_hiding_spartan);
     *len = p.size();
     if (buf && cap >= p.size()) memcpy(buf, p.data(), p.size());
@@ -1607,7 +1616,7 @@ int pk_whir_r1cs_io_pattern(unsigned m_0, const pk_whir_config* whir_witness, co
 int pk_io_pattern_check(const uint8_t* pattern, size_t n, unsigned m_0, const pk_whir_config* whir_witness,
                         const pk_whir_config* whir_for_hiding_spartan, char* why, size_t why_cap) {
     if (why && why_cap) why[0] = 0;
-    if (!pattern || m_0 < 1 || m_0 > 27 || !whir_config_sane(whir_witness) || !whir_config_sane(whir_for_hiding_spartan)) return PK_ERR_BAD_ARG;
+    if (!pattern || m_0 < 1 || m_0 > 27 || whir_config_error(whir_witness) || whir_config_error(whir_for_hiding_spartan)) return PK_ERR_BAD_ARG;
     const std::string bad = io_pattern_mismatch(std::string((const char*)pattern, n), m_0, *whir_witness, *whir_for_hiding_spartan);
     if (bad.empty()) return PK_OK;
     if (why && why_cap) snprintf(why, why_cap, "%s", bad.c_str());

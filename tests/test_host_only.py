@@ -197,6 +197,15 @@ def test_scheme_arena_bytes_is_the_sum_of_a_proofs_buffers():
     assert lib.pk_scheme_arena_bytes(21, 22, 1 << 20, C.byref(cw), C.byref(n)) == -1  # m_0 > m
     assert lib.pk_scheme_arena_bytes(21, 20, 1 << 20, None, C.byref(n)) == -1
     assert lib.pk_scheme_arena_bytes(21, 20, 1 << 20, C.byref(cw), None) == -1
+    # the configs pk_scheme_create refuses are refused by the host-only entry points too
+    from provekit_amd.scheme import WhirConfigStruct, blinding_config_for
+
+    assert lib.pk_scheme_arena_bytes(21, 20, 1 << 20, C.byref(WhirConfigStruct()), C.byref(n)) == -1  # all zero
+    cb = _cfg_struct(blinding_config_for(20))
+    cw.starting_log_inv_rate = 0
+    assert lib.pk_whir_r1cs_io_pattern(20, C.byref(cw), C.byref(cb), None, 0, C.byref(n)) == -1
+    why = C.create_string_buffer(256)
+    assert lib.pk_io_pattern_check(b"x", 1, 20, C.byref(cw), C.byref(cb), why, len(why)) == -1
 
 
 def test_test_hooks_are_an_entry_point_not_the_environment():
