@@ -258,7 +258,9 @@ PK_HD fe29 mont261_29(const fe29& a, const fe29& b) {
 // of that product change it by less than 2^-22.  53 + 45 + 45 = 143 multiply-adds and no per-step quotient digit, against the
 // 162 + 9 of a Montgomery product (mont261_29) -- and the value stays in whatever domain `a` is in (a Montgomery image times a plain
 // w is the Montgomery image of the product).  q*p is subtracted as q*(2^261 - p) added, the 2^261 multiple falling off limb 8.
-// a: limbs < 2^30.7 (lazy), value < 8p.  w, wq: normalised (limbs < 2^29).  Result normalised, < 2.2p.
+// a: limbs < 2^30.7 (lazy), value < 8p.  w, wq: normalised (limbs < 2^29).  Result normalised, < 2.2p.  With wq the exact quotient
+// (the NTT's constants and twiddle tables) the NTT relies on more, for its lazy a (limbs < 2^31.4, value < 10.5p): result
+// normalised, < 1.2p (ntt_regs.hpp; driven at its extremes by test_fe29_host.py and test_ntt_pre_load_host.py).
 PK_HD constexpr u32 pcomp29(int k) {  // limb k of 2^261 - p
     long long borrow = 0;
     u32 out = 0;

@@ -126,11 +126,24 @@ struct PassParams {
     size_t tiles;       // register-radix kernel: tiles per column, columns, and whether the XCD-aware block order applies
     unsigned ncols;
     int xcd_tiles;
-    int lazy_store;     // outputs may be stored almost reduced (< 1.6p) instead of canonical: intermediate passes, and the
-                        // hash-ready final pass (its consumers reduce anyway)
+    int lazy_store;     // outputs may be stored almost reduced instead of canonical: intermediate passes, and the hash-ready final
+                        // pass (its consumers reduce anyway).  pack29 of a value the pass leaves normalised and < 1.2p (ntt_regs.hpp):
+                        // the next pass loads it as it is, below the 1.2p its butterfly network takes.
     size_t n_mask;      // N - 1
     size_t tw_mul;      // twiddle exponent = tw_mul * k * v  (0 = no twiddle)
     size_t wr_step;     // w_R^j = W[j * wr_step]
+    // register-radix kernel only.  Fused de-interleave: when in_poly[0] is set, column col is the stride-2^in_fold sub-sequence
+    // in_poly[col >> in_fold][(col & (2^in_fold - 1)) + 2^in_fold t] of the caller's polynomials (in_stride_* are then in units of
+    // the polynomial's elements); otherwise column col starts at in + col * in_col_stride.
+    const fe* in_poly[16];
+    unsigned in_fold;
+    // Pass 1 folded into this pass's load (pre_terms = L1 > 0, see ntt_columns): the element at natural index m of this pass's
+    // input (m < pre_stride, m = nat0 + r in_nat_r + b in_nat_v) is  sum_{n1 < L1} x[n1 pre_stride + m] * w_N^(k1 (n1 pre_stride + m))
+    // with k1 = u pre_ku + (v0 + b) pre_kv and x[t] at column base + t * pre_elem: pass 1's DFT and inter-pass twiddle when only its
+    // first L1 rows are nonzero.  Inputs at t >= nonzero are zero and are neither loaded nor multiplied.
+    int pre_terms;
+    size_t pre_stride, pre_elem, pre_ku, pre_kv;
+    const u32* Wpre29;  // the table of pass 1's inter-pass twiddle (carries the output scaling when pass 1 would have)
 };
 
 template <int LOG_R, bool IN_R_CONTIG>
@@ -254,14 +267,15 @@ __host__ __device__ __forceinline__ constexpr int bitrev_c(int v, int bits) {
 
 struct Ntt8Ctx {
     const fe* in;
+    const fe* cin;  // the input column's base (pre_terms path)
     fe* out;
-    size_t nat0, v0;
+    size_t nat0, v0, k10;
     unsigned tid;
 };
 
 // LE = log2 of the elements a lane holds (NTT_LE = 2: four registers, radix-4 rounds, 512 lanes per tile).
 // one round (digit J) of the register NTT; everything about the digit layout is a compile-time constant
-template <int LE, int LOG_R, int J>
+template <int LE, int LOG_R, int J, bool PRE>
 __device__ __forceinline__ void ntt8_round(fe29 (&x)[1 << LE], const PassParams& p, const Ntt8Ctx& c, u32* planes) {
     constexpr int NX = 1 << LE;
     constexpr int LOGB = 11 - LOG_R, BTT = 1 << LOGB;
@@ -282,10 +296,20 @@ __device__ __forceinline__ void ntt8_round(fe29 (&x)[1 << LE], const PassParams&
         for (int reg = 0; reg < NX; reg++) {
             const int I = PK_TILE_INDEX(reg);
             const int r = I >> LOGB, b = I & (BTT - 1);
-            size_t nat = c.nat0 + (size_t)r * p.in_nat_r + (size_t)b * p.in_nat_v;
-            fe t = fe_zero();
-            if (nat < p.nonzero) t = fe_load(c.in + (size_t)r * p.in_stride_r + (size_t)b * p.in_stride_v);
-            x[reg] = unpack29<0>(t);
+            const size_t nat = c.nat0 + (size_t)r * p.in_nat_r + (size_t)b * p.in_nat_v;
+            if constexpr (PRE) {
+                const size_t k1 = c.k10 + (size_t)b * p.pre_kv;
+                x[reg] = pre_load_sum(p.pre_terms, [&](int n1, fe29& y) {
+                    const size_t t = nat + (size_t)n1 * p.pre_stride;
+                    if (t >= p.nonzero) return false;
+                    y = mul_tw(unpack29<0>(fe_load(c.cin + t * p.pre_elem)), tw29s_load(p.Wpre29, (k1 * t) & p.n_mask));
+                    return true;
+                });
+            } else {
+                fe t = fe_zero();
+                if (nat < p.nonzero) t = fe_load(c.in + (size_t)r * p.in_stride_r + (size_t)b * p.in_stride_v);
+                x[reg] = unpack29<0>(t);
+            }
         }
     } else {
         __syncthreads();
@@ -340,16 +364,17 @@ __device__ __forceinline__ void ntt8_round(fe29 (&x)[1 << LE], const PassParams&
 #undef PK_TILE_INDEX
 }
 
-template <int LE, int LOG_R, int J>
+template <int LE, int LOG_R, int J, bool PRE>
 __device__ __forceinline__ void ntt8_rounds_from(fe29 (&x)[1 << LE], const PassParams& p, const Ntt8Ctx& c, u32* planes) {
     constexpr int NR = (LOG_R + LE - 1) / LE;
     if constexpr (J < NR) {
-        ntt8_round<LE, LOG_R, J>(x, p, c, planes);
-        ntt8_rounds_from<LE, LOG_R, J + 1>(x, p, c, planes);
+        ntt8_round<LE, LOG_R, J, PRE>(x, p, c, planes);
+        ntt8_rounds_from<LE, LOG_R, J + 1, PRE>(x, p, c, planes);
     }
 }
 
-template <int LE, int LOG_R, bool IN_R_CONTIG>
+// PRE: pass 1 is carried in the load (PassParams::pre_terms); a template flag, so the passes that do not need it keep their code
+template <int LE, int LOG_R, bool IN_R_CONTIG, bool PRE>
 __global__ __launch_bounds__(2048 >> LE) __attribute__((amdgpu_waves_per_eu(4, 4))) void ntt8_pass_kernel(PassParams p) {
     PK_LATENCY_PRIO();
     constexpr int LOGB = 11 - LOG_R;
@@ -370,12 +395,14 @@ __global__ __launch_bounds__(2048 >> LE) __attribute__((amdgpu_waves_per_eu(4, 4
     const size_t u = tile / vblocks, vb = tile % vblocks;
     Ntt8Ctx c;
     c.v0 = vb << LOGB;
-    c.in = p.in + col * p.in_col_stride + u * p.in_stride_u + c.v0 * p.in_stride_v;
+    c.cin = p.in_poly[0] ? p.in_poly[col >> p.in_fold] + (col & (((size_t)1 << p.in_fold) - 1)) : p.in + col * p.in_col_stride;
+    c.in = c.cin + u * p.in_stride_u + c.v0 * p.in_stride_v;
+    c.k10 = u * p.pre_ku + c.v0 * p.pre_kv;
     c.out = p.out + col * p.out_col_stride + u * p.out_stride_u + c.v0 * p.out_stride_v;
     c.nat0 = u * p.in_nat_u + c.v0 * p.in_nat_v;
     c.tid = threadIdx.x;
     fe29 x[1 << LE];
-    ntt8_rounds_from<LE, LOG_R, 0>(x, p, c, planes);
+    ntt8_rounds_from<LE, LOG_R, 0, PRE>(x, p, c, planes);
 }
 
 // c[2^k t + j] -> S[j][t]  (t < L): stride-2^k gather done through LDS so both sides coalesce
@@ -586,17 +613,17 @@ inline bool pass_is_fast(unsigned log_r, unsigned log_v, size_t N) { return log_
 // VALUBusy against 89 % and 6-9 % slower from 2^19 rows up: profiles/r06_ntt_le_ab.jsonl.)
 constexpr int NTT_LE = 2;
 
-template <int LE, int LOG_R, bool CONTIG>
+template <int LE, int LOG_R, bool CONTIG, bool PRE>
 int launch_fast(pk_ctx* ctx, const PassParams& pp, unsigned grid) {
     const size_t lds_bytes = 9 * 2048 * 4;
     // the 72 KiB dynamic-LDS opt-in is a per-function, per-device attribute: set it once per device, not per launch
     static std::atomic<unsigned long long> lds_set{0};
     const unsigned long long dev_bit = 1ull << (ctx->device & 63);
     if (!(lds_set.load(std::memory_order_acquire) & dev_bit)) {
-        PK_HIP(ctx, hipFuncSetAttribute((const void*)ntt8_pass_kernel<LE, LOG_R, CONTIG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+        PK_HIP(ctx, hipFuncSetAttribute((const void*)ntt8_pass_kernel<LE, LOG_R, CONTIG, PRE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
         lds_set.fetch_or(dev_bit, std::memory_order_release);
     }
-    ntt8_pass_kernel<LE, LOG_R, CONTIG><<<dim3(grid, 1), 2048 >> LE, lds_bytes, ctx->stream>>>(pp);
+    ntt8_pass_kernel<LE, LOG_R, CONTIG, PRE><<<dim3(grid, 1), 2048 >> LE, lds_bytes, ctx->stream>>>(pp);
     PK_LAUNCH_CHECK(ctx);
     return PK_OK;
 }
@@ -611,12 +638,17 @@ int launch_pass_r(pk_ctx* ctx, const PassParams& p, bool in_r_contig, size_t til
         PassParams pp = p;
         pp.tiles = tiles8;
         pp.ncols = ncols;
-        pp.xcd_tiles = (p.Tpass29 != nullptr && tiles8 % 8 == 0) ? 1 : 0;  // the XCD order exists to share the pass table's rows
+        // the XCD order exists to share what the columns of a tile read in common: the pass table's rows, and with the fused
+        // de-interleave the input lines (one 128 B line holds the same t of four adjacent columns, 2^fold columns one row)
+        pp.xcd_tiles = ((p.Tpass29 != nullptr || p.in_poly[0] != nullptr) && tiles8 % 8 == 0) ? 1 : 0;
         PK_REQUIRE(ctx, tiles8 * ncols < ((size_t)1 << 31), "NTT launch too large");
         const unsigned grid = (unsigned)(tiles8 * ncols);
         constexpr int LR = LOG_R >= 3 ? LOG_R : 3;
-        return in_r_contig ? launch_fast<NTT_LE, LR, true>(ctx, pp, grid) : launch_fast<NTT_LE, LR, false>(ctx, pp, grid);
+        if (p.pre_terms)
+            return in_r_contig ? launch_fast<NTT_LE, LR, true, true>(ctx, pp, grid) : launch_fast<NTT_LE, LR, false, true>(ctx, pp, grid);
+        return in_r_contig ? launch_fast<NTT_LE, LR, true, false>(ctx, pp, grid) : launch_fast<NTT_LE, LR, false, false>(ctx, pp, grid);
     }
+    PK_REQUIRE(ctx, p.in_poly[0] == nullptr && p.pre_terms == 0, "fused NTT input needs the register-radix pass");
     ProfScope prof(ctx, in_r_contig ? "ntt_pass_last" : "ntt_pass");
     size_t lds_bytes = (size_t)(2 * R * BT + 2 * (R / 2 > 0 ? R / 2 : 1)) * 16;
     dim3 grid((unsigned)tiles, ncols);
@@ -683,13 +715,60 @@ bool ntt_scaled_available(unsigned log_n) {
     return pass_is_fast(l2, l3, (size_t)1 << log_n);
 }
 
+// Pass 1 evaluated inside the next pass's load (PassParams::pre_terms) when at most this many of its rows are nonzero.  Counted per
+// element of pass 2's input: the direct sum costs L1 Shoup products (+ L1 - 1 lazy additions and one red29).  Pass 1 itself costs
+// 1/4 product per radix-4 digit (w_4), 3/4 per inter-round twiddle of its register network (1/2 after a radix-2 first round) and one
+// inter-pass twiddle: 3.75 products at R1 = 2^7, 4.25 at 2^8, 4.75 at 2^9, plus the launch and a scratch write and read of every
+// element.  So the direct sum wins for L1 <= 3 at every radix the register-radix pass takes; red29 would take up to four terms.
+constexpr size_t PRE_MAX_TERMS = 3;
+static_assert(PRE_MAX_TERMS <= 4, "pre_load_sum: red29 takes a sum of at most four products");
+
+// the pass split of a transform of 2^log_n (log_n > 9) and how its first pass is run for a given number of nonzero inputs
+struct NttPlan {
+    unsigned npass, l1, l2, l3;
+    size_t stride1;   // natural-index distance between the rows of pass 1's DFT
+    size_t L1;        // rows of pass 1 that hold a nonzero input
+    bool pre;         // pass 1 is folded into pass 2's load
+    bool fast1;       // pass 1 runs in the register-radix kernel
+};
+NttPlan ntt_plan(unsigned log_n, size_t nonzero) {
+    NttPlan q{};
+    const size_t N = (size_t)1 << log_n;
+    if (log_n <= 18) {
+        q.npass = 2;
+        q.l1 = (log_n + 1) / 2;
+        q.l2 = log_n - q.l1;
+        q.stride1 = (size_t)1 << q.l2;
+        q.fast1 = pass_is_fast(q.l1, q.l2, N);
+    } else {
+        q.npass = 3;
+        q.l1 = (log_n + 2) / 3;
+        q.l2 = (log_n - q.l1 + 1) / 2;
+        q.l3 = log_n - q.l1 - q.l2;
+        q.stride1 = (size_t)1 << (q.l2 + q.l3);
+        q.fast1 = pass_is_fast(q.l1, q.l2 + q.l3, N);
+    }
+    q.L1 = std::max<size_t>(1, (std::min(nonzero, N) + q.stride1 - 1) / q.stride1);
+    const bool fast2 = q.npass == 2 ? pass_is_fast(q.l2, q.l1, N) : pass_is_fast(q.l2, q.l3, N);
+    q.pre = q.L1 <= PRE_MAX_TERMS && fast2;
+    return q;
+}
+
+// where the transform's input columns are: in + col * col_stride, or (polys != null) the de-interleaved polynomials
+// polys[col >> fold][(col & (2^fold - 1)) + 2^fold t], read in place by the first pass that loads them
+struct NttInput {
+    const fe* in;
+    size_t col_stride;
+    const fe* const* polys;
+    unsigned fold, npolys;
+};
+
 // Column-batched NTT, natural -> natural.  `ncols` vectors of length N = 2^log_n:
-// input column c at in + c*in_col_stride holds `nonzero` leading coefficients (rest is zero
-// and is never read); output column c at out + c*out_col_stride.  `scratch` must hold
-// ncols columns of N elements (column stride N) when log_n > 9, and may alias nothing.
+// input column c (NttInput) holds `nonzero` leading coefficients (rest is zero and is never read); output column c at
+// out + c*out_col_stride.  `scratch` must hold ncols columns of N elements (column stride N) when log_n > 9, and may alias nothing.
 // scaled_out: deliver the hash-ready encoding (only legal when ntt_scaled_available(log_n)).
-int ntt_columns(pk_ctx* ctx, const fe* in, size_t in_col_stride, size_t nonzero, fe* out, size_t out_col_stride, fe* scratch,
-                unsigned log_n, unsigned ncols, bool scaled_out) {
+int ntt_columns_in(pk_ctx* ctx, const NttInput& src, size_t nonzero, fe* out, size_t out_col_stride, fe* scratch, unsigned log_n,
+                   unsigned ncols, bool scaled_out) {
     PK_REQUIRE(ctx, log_n <= 27, "NTT size above 2^27");
     PK_REQUIRE(ctx, !scaled_out || ntt_scaled_available(log_n), "hash-ready NTT output is not available at this size");
     const size_t N = (size_t)1 << log_n;
@@ -704,6 +783,8 @@ int ntt_columns(pk_ctx* ctx, const fe* in, size_t in_col_stride, size_t nonzero,
         Ws29 = W29;
         if (scaled_out && (rc = get_twiddles29(ctx, log_n, 1, Ws, &Ws29))) return rc;
     }
+    const fe* in = src.in;
+    const size_t in_col_stride = src.col_stride;
     PassParams p{};
     p.W = W;
     p.Wtw = W;
@@ -712,6 +793,7 @@ int ntt_columns(pk_ctx* ctx, const fe* in, size_t in_col_stride, size_t nonzero,
     p.lazy_store = 0;
     p.n_mask = N - 1;
     if (log_n <= 9) {
+        PK_REQUIRE(ctx, src.polys == nullptr, "fused NTT input needs more than 512 rows");
         // single pass: R = N and the tile's batch axis v runs over BT adjacent *columns*
         p.in = in;
         p.out = out;
@@ -751,77 +833,118 @@ int ntt_columns(pk_ctx* ctx, const fe* in, size_t in_col_stride, size_t nonzero,
         return PK_OK;
     }
     PK_REQUIRE(ctx, scratch != nullptr, "scratch required for N > 512");
-    if (log_n <= 18) {
-        unsigned l1 = (log_n + 1) / 2, l2 = log_n - l1;
+    const NttPlan plan = ntt_plan(log_n, nonzero);
+    // the input side of whichever pass reads the columns: strides below are in units of `e` elements of the column
+    size_t e = 1;
+    if (src.polys) {
+        PK_REQUIRE(ctx, plan.pre || plan.fast1, "fused NTT input needs the register-radix pass");
+        PK_REQUIRE(ctx, src.npolys >= 1 && src.npolys <= 16 && ((size_t)src.npolys << src.fold) == ncols, "bad fused NTT input");
+        for (unsigned b = 0; b < src.npolys; b++) p.in_poly[b] = src.polys[b];
+        p.in_fold = src.fold;
+        e = (size_t)1 << src.fold;
+    }
+    // PassParams of a pass that reads the transform's input (pass 1, or pass 2 with pass 1 folded into its load)
+    auto reads_input = [&](PassParams q) {
+        q.in = in;
+        q.in_col_stride = in_col_stride;
+        q.nonzero = nonzero;
+        return q;
+    };
+    auto reads_scratch = [&](PassParams q) {
+        for (auto& ptr : q.in_poly) ptr = nullptr;
+        q.pre_terms = 0;
+        q.in = scratch;
+        q.in_col_stride = N;
+        q.nonzero = 1;  // nat is always 0 < 1: everything is read
+        return q;
+    };
+    if (plan.npass == 2) {
+        const unsigned l1 = plan.l1, l2 = plan.l2;
         size_t R1 = (size_t)1 << l1, R2 = (size_t)1 << l2;
-        // pass 1: DFT over n1 (stride R2); v = n2; in -> scratch (same layout); twiddle w_N^(k1*n2)
-        p.in = in;
-        p.out = scratch;
-        p.in_col_stride = in_col_stride;
-        p.out_col_stride = N;
-        p.in_stride_r = R2; p.in_stride_v = 1; p.in_stride_u = 0;
-        p.out_stride_r = R2; p.out_stride_v = 1; p.out_stride_u = 0;
-        p.log_v = l2;
-        p.in_nat_r = R2; p.in_nat_v = 1; p.in_nat_u = 0;
-        p.nonzero = nonzero;
-        p.tw_mul = 1;
-        p.Wtw = Ws;  // the only inter-pass twiddle of a two-pass transform carries the output scaling
-        p.Wtw29 = Ws29;
-        p.lazy_store = pass_is_fast(l2, l1, N);  // the register-radix kernel takes almost reduced inputs
-        p.wr_step = N >> l1;
-        if (log_n >= PASS_TABLE_MIN_LOG_N && pass_is_fast(l1, l2, N) && (rc = get_pass_table(ctx, log_n, 1, scaled_out, Ws29, R1, R2, 1, &p.Tpass29))) return rc;
-        p.tp_row = R2;
-        rc = launch_pass(ctx, l1, p, false, R2 / BT, ncols);
-        if (rc) return rc;
-        p.Tpass29 = nullptr;
+        if (!plan.pre) {
+            // pass 1: DFT over n1 (stride R2); v = n2; in -> scratch (same layout); twiddle w_N^(k1*n2)
+            p = reads_input(p);
+            p.out = scratch;
+            p.out_col_stride = N;
+            p.in_stride_r = R2 * e; p.in_stride_v = e; p.in_stride_u = 0;
+            p.out_stride_r = R2; p.out_stride_v = 1; p.out_stride_u = 0;
+            p.log_v = l2;
+            p.in_nat_r = R2; p.in_nat_v = 1; p.in_nat_u = 0;
+            p.tw_mul = 1;
+            p.Wtw = Ws;  // the only inter-pass twiddle of a two-pass transform carries the output scaling
+            p.Wtw29 = Ws29;
+            p.lazy_store = pass_is_fast(l2, l1, N);  // the register-radix kernel takes almost reduced inputs
+            p.wr_step = N >> l1;
+            p.tp_row = R2;
+            rc = launch_pass(ctx, l1, p, false, R2 / BT, ncols);
+            if (rc) return rc;
+            p = reads_scratch(p);
+            p.in_stride_r = 1; p.in_stride_v = R2; p.in_stride_u = 0;
+            p.in_nat_r = 0; p.in_nat_v = 0; p.in_nat_u = 0;
+        } else {
+            // pass 1 folded into pass 2's load: input m = n2 = r, k1 = v
+            p = reads_input(p);
+            p.in_stride_r = 0; p.in_stride_v = 0; p.in_stride_u = 0;
+            p.in_nat_r = 1; p.in_nat_v = 0; p.in_nat_u = 0;
+            p.pre_terms = (int)plan.L1;
+            p.pre_stride = R2;
+            p.pre_elem = e;
+            p.pre_ku = 0;
+            p.pre_kv = 1;
+            p.Wpre29 = Ws29;  // pass 1's twiddle carries the output scaling
+        }
         p.Wtw = W;
         p.Wtw29 = W29;
         p.lazy_store = scaled_out ? 1 : 0;
         // pass 2: DFT over n2 (contiguous); v = k1 (in stride R2, out stride 1); out k2 stride R1
-        p.in = scratch;
         p.out = out;
-        p.in_col_stride = N;
         p.out_col_stride = out_col_stride;
-        p.in_stride_r = 1; p.in_stride_v = R2; p.in_stride_u = 0;
         p.out_stride_r = R1; p.out_stride_v = 1; p.out_stride_u = 0;
         p.log_v = l1;
-        p.in_nat_r = 0; p.in_nat_v = 0; p.in_nat_u = 0;
-        p.nonzero = 1;  // nat is always 0 < 1: everything is read
         p.tw_mul = 0;
         p.wr_step = N >> l2;
         return launch_pass(ctx, l2, p, true, R1 / BT, ncols);
     }
     // three passes
-    unsigned l1 = (log_n + 2) / 3, l2 = (log_n - l1 + 1) / 2, l3 = log_n - l1 - l2;
+    const unsigned l1 = plan.l1, l2 = plan.l2, l3 = plan.l3;
     size_t R1 = (size_t)1 << l1, R2 = (size_t)1 << l2, R3 = (size_t)1 << l3;
-    // pass 1: DFT over n1 (stride R2*R3); v = m = n2*R3+n3; twiddle w_N^(k1*m); in -> scratch
-    p.in = in;
-    p.out = scratch;
-    p.in_col_stride = in_col_stride;
-    p.out_col_stride = N;
-    p.in_stride_r = R2 * R3; p.in_stride_v = 1; p.in_stride_u = 0;
-    p.out_stride_r = R2 * R3; p.out_stride_v = 1; p.out_stride_u = 0;
-    p.log_v = l2 + l3;
-    p.in_nat_r = R2 * R3; p.in_nat_v = 1; p.in_nat_u = 0;
-    p.nonzero = nonzero;
-    p.tw_mul = 1;
-    p.lazy_store = pass_is_fast(l2, l3, N);
-    p.wr_step = N >> l1;
-    if (log_n >= PASS_TABLE_MIN_LOG_N && pass_is_fast(l1, l2 + l3, N) && (rc = get_pass_table(ctx, log_n, 1, false, W29, R1, R2 * R3, 1, &p.Tpass29))) return rc;
-    p.tp_row = R2 * R3;
-    rc = launch_pass(ctx, l1, p, false, (R2 * R3) / BT, ncols);
-    if (rc) return rc;
-    p.Tpass29 = nullptr;
+    if (!plan.pre) {
+        // pass 1: DFT over n1 (stride R2*R3); v = m = n2*R3+n3; twiddle w_N^(k1*m); in -> scratch
+        p = reads_input(p);
+        p.out = scratch;
+        p.out_col_stride = N;
+        p.in_stride_r = R2 * R3 * e; p.in_stride_v = e; p.in_stride_u = 0;
+        p.out_stride_r = R2 * R3; p.out_stride_v = 1; p.out_stride_u = 0;
+        p.log_v = l2 + l3;
+        p.in_nat_r = R2 * R3; p.in_nat_v = 1; p.in_nat_u = 0;
+        p.tw_mul = 1;
+        p.lazy_store = pass_is_fast(l2, l3, N);
+        p.wr_step = N >> l1;
+        if (log_n >= PASS_TABLE_MIN_LOG_N && pass_is_fast(l1, l2 + l3, N) && (rc = get_pass_table(ctx, log_n, 1, false, W29, R1, R2 * R3, 1, &p.Tpass29))) return rc;
+        p.tp_row = R2 * R3;
+        rc = launch_pass(ctx, l1, p, false, (R2 * R3) / BT, ncols);
+        if (rc) return rc;
+        p.Tpass29 = nullptr;
+        p = reads_scratch(p);
+        p.in_stride_r = R3; p.in_stride_v = 1; p.in_stride_u = R2 * R3;
+        p.in_nat_r = 0; p.in_nat_v = 0; p.in_nat_u = 0;
+    } else {
+        // pass 1 folded into pass 2's load: input m = n2*R3 + n3 = r*R3 + v, k1 = u
+        p = reads_input(p);
+        p.in_stride_r = 0; p.in_stride_v = 0; p.in_stride_u = 0;
+        p.in_nat_r = R3; p.in_nat_v = 1; p.in_nat_u = 0;
+        p.pre_terms = (int)plan.L1;
+        p.pre_stride = R2 * R3;
+        p.pre_elem = e;
+        p.pre_ku = 1;
+        p.pre_kv = 0;
+        p.Wpre29 = W29;
+    }
     // pass 2: DFT over n2 (stride R3); v = n3; u = k1 (stride R2*R3); in place; twiddle w_N^(R1*k2*n3)
-    p.in = scratch;
     p.out = scratch;
-    p.in_col_stride = N;
     p.out_col_stride = N;
-    p.in_stride_r = R3; p.in_stride_v = 1; p.in_stride_u = R2 * R3;
     p.out_stride_r = R3; p.out_stride_v = 1; p.out_stride_u = R2 * R3;
     p.log_v = l3;
-    p.in_nat_r = 0; p.in_nat_v = 0; p.in_nat_u = 0;
-    p.nonzero = 1;
     p.tw_mul = R1;
     p.Wtw = Ws;  // the last inter-pass twiddle carries the output scaling
     p.Wtw29 = Ws29;
@@ -832,20 +955,34 @@ int ntt_columns(pk_ctx* ctx, const fe* in, size_t in_col_stride, size_t nonzero,
     rc = launch_pass(ctx, l2, p, false, R1 * (R3 / BT), ncols);
     if (rc) return rc;
     p.Tpass29 = nullptr;
+    p = reads_scratch(p);
     p.Wtw = W;
     p.Wtw29 = W29;
     p.lazy_store = scaled_out ? 1 : 0;
     // pass 3: DFT over n3 (contiguous); v = k1 (in stride R2*R3, out stride 1); u = k2 (in stride R3, out stride R1)
-    p.in = scratch;
     p.out = out;
-    p.in_col_stride = N;
     p.out_col_stride = out_col_stride;
     p.in_stride_r = 1; p.in_stride_v = R2 * R3; p.in_stride_u = R3;
+    p.in_nat_r = 0; p.in_nat_v = 0; p.in_nat_u = 0;
     p.out_stride_r = R1 * R2; p.out_stride_v = 1; p.out_stride_u = R1;
     p.log_v = l1;
     p.tw_mul = 0;
     p.wr_step = N >> l3;
     return launch_pass(ctx, l3, p, true, R2 * (R1 / BT), ncols);
+}
+
+int ntt_columns(pk_ctx* ctx, const fe* in, size_t in_col_stride, size_t nonzero, fe* out, size_t out_col_stride, fe* scratch,
+                unsigned log_n, unsigned ncols, bool scaled_out) {
+    const NttInput src{in, in_col_stride, nullptr, 0, 0};
+    return ntt_columns_in(ctx, src, nonzero, out, out_col_stride, scratch, log_n, ncols, scaled_out);
+}
+
+// can a transform of 2^log_n with `nonzero` leading inputs read de-interleaved polynomials in place (NttInput::polys)?  The pass
+// that loads them must be the register-radix kernel.
+bool ntt_reads_polys(unsigned log_n, size_t nonzero) {
+    if (log_n <= 9) return false;
+    const NttPlan q = ntt_plan(log_n, nonzero);
+    return q.pre || q.fast1;
 }
 
 int deinterleave(pk_ctx* ctx, const fe* coeffs, size_t n_coeffs, unsigned fold, fe* S, size_t col_stride) {
@@ -894,10 +1031,16 @@ int rs_encode_x(pk_ctx* ctx, const uint64_t* const* d_coeffs, unsigned batch, un
     unsigned log_rows = n_vars + log_inv_rate - fold;
     size_t rows = (size_t)1 << log_rows, fw = (size_t)1 << fold;
     size_t L = ((size_t)1 << n_vars) / fw;
+    for (unsigned b = 0; b < batch; b++) PK_REQUIRE(ctx, d_coeffs[b], "null polynomial pointer");
     fe* S = (fe*)d_scratch;                 // first half: de-interleaved coefficients, [batch*fw][rows]
     fe* S2 = S + (size_t)batch * fw * rows;  // second half: inter-pass buffer
+    if (ntt_reads_polys(log_rows, L)) {
+        // the first pass that loads the input gathers the stride-2^fold sub-sequences itself: no de-interleave, and only the
+        // first half of the scratch is used (inter-pass buffer)
+        const NttInput src{nullptr, 0, (const fe* const*)d_coeffs, fold, batch};
+        return ntt_columns_in(ctx, src, L, (fe*)d_leaves, rows, S, log_rows, (unsigned)(batch * fw), scaled);
+    }
     for (unsigned b = 0; b < batch; b++) {
-        PK_REQUIRE(ctx, d_coeffs[b], "null polynomial pointer");
         int rc = pk::deinterleave(ctx, (const fe*)d_coeffs[b], (size_t)1 << n_vars, fold, S + (size_t)b * fw * rows, rows);
         if (rc) return rc;
     }

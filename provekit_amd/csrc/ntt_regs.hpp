@@ -13,7 +13,11 @@
 //                            quotient above 4 would overflow the signed limb differences: red29w takes up to 8p)
 //   shoup261_29(v)           limbs < 2^31.4, v < 10.5p -> normalised, < 1.07p with an exact quotient (the in-register constants), < 1.2p
 //                            with a table quotient up to two short
-// so every value that re-enters a butterfly or is stored is below 1.2p (the almost-reduced stores promise < 1.6p).
+// so every value that re-enters a butterfly or is stored is below 1.2p, normalised: the almost-reduced stores of a pass
+// (ntt.hip PassParams::lazy_store) hand the next pass exactly what its network takes.
+//   pre_load_sum             a pass that carries pass 1 in its load: up to four products (each < 1.2p) summed (limbs < 2^31,
+//                            value < 4.8p) and one red29 -> normalised, < 1.001p; one product enters as it is
+//                            (test_ntt_pre_load_on_the_host drives it with inputs up to 2^256 - 1 and twiddles 0, 1, p - 1)
 #pragma once
 #include "fe29.hpp"
 
@@ -108,6 +112,22 @@ PK_HD fe29 red29w(fe29 x) {
 //   X0 = s0 + s1   X2 = s0 - s1 + 4p   X1 = d0 + d1   X3 = d0 - d1 + 2p          (register order X0, X2, X1, X3: bit-reversed)
 // with inputs below 1.2p: X0 < 4.8p (limbs < 2^31: red29), the others < 6.4p, limbs < 2^31.4 -- what shoup261_29 (a < 10.5p: quotient
 // at most one short; columns 9 * 2^31.4 * 2^29 + 9 * 2^58 < 2^64) and red29w accept.  (The subtractions themselves hold up to 1.9p.)
+// One input of a pass that carries pass 1 in its load (ntt.hip PassParams::pre_terms): the sum over pass 1's first `terms`
+// rows of input x twiddle.  term(n1, y) sets y to row n1's Shoup product (normalised, < 1.2p) and returns true, or returns false
+// when that row's input lies past the nonzero ones (so do all later rows).  terms <= 4: red29 takes limbs < 2^31 and values < 5p.
+template <class Term>
+PK_HD fe29 pre_load_sum(int terms, Term term) {
+    fe29 acc;
+#pragma unroll
+    for (int l = 0; l < 9; l++) acc.v[l] = 0;
+    for (int n1 = 0; n1 < terms; n1++) {
+        fe29 y;
+        if (!term(n1, y)) break;
+        acc = n1 == 0 ? y : add29(acc, y);
+    }
+    return terms > 1 ? red29(acc) : acc;
+}
+
 template <int LE, int D>
 PK_HD void dft_regs(fe29 (&x)[1 << LE]) {
     static_assert(D >= 1 && D <= 2 && D <= LE && LE <= 3, "radix 2 or 4");

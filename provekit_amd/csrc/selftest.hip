@@ -35,6 +35,25 @@ static int selftest_dft(const uint64_t* in, const uint64_t* tw, uint64_t* out, s
     }
     return PK_OK;
 }
+// ntt_regs.hpp pre_load_sum on the host: n outputs, each from `terms` inputs x (any value below 2^256) and `terms` multipliers
+// below p (Shoup products with the quotient the twiddle tables hold); rows n1 >= live read as past the nonzero inputs.  out: the
+// lazy result as it enters the network (not reduced further); a result with a limb not normalised is an error.
+static int selftest_pre_load(const uint64_t* x, const uint64_t* tw, uint64_t* out, int terms, int live, size_t n) {
+    for (size_t i = 0; i < n; i++) {
+        const fe29 y = pre_load_sum(terms, [&](int n1, fe29& v) {
+            if (n1 >= live) return false;
+            tw29s t;
+            t.w = unpack29<0>(load_host(tw + 4 * (terms * i + n1)));
+            t.wq = shoup_quotient29(t.w);
+            v = mul_tw(unpack29<0>(load_host(x + 4 * (terms * i + n1))), t);
+            return true;
+        });
+        for (int k = 0; k < 9; k++)
+            if (y.v[k] >> 29) return PK_ERR_BAD_ARG;
+        store_host(out + 4 * i, pack29(y));
+    }
+    return PK_OK;
+}
 extern "C" {
 
 // domain-separator tag (Keccak duplex, overwrite mode) and one Skyscraper sponge permutation, host only
@@ -65,6 +84,10 @@ int pk_selftest_arith(int op, const uint64_t* a, const uint64_t* b, uint64_t* ou
     return PK_OK;
 }
 
+int pk_selftest_pre_load(const uint64_t* x, const uint64_t* tw, uint64_t* out, int terms, int live, size_t n) {
+    if (!x || !tw || !out || terms < 1 || terms > 4 || live < 0 || live > terms) return PK_ERR_BAD_ARG;
+    return selftest_pre_load(x, tw, out, terms, live, n);
+}
 int pk_selftest_dft(const uint64_t* in, const uint64_t* tw, uint64_t* out, int le, int d, size_t n_groups) {
     if (!in || !out) return PK_ERR_BAD_ARG;
     if (le == 3 && d == 1) return selftest_dft<3, 1>(in, tw, out, n_groups);

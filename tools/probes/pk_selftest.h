@@ -29,6 +29,9 @@ int pk_selftest_random_fe(pk_ctx *ctx, const uint8_t seed32[32], uint32_t stream
  * frequency digit).  tw (may be NULL): one multiplier below p per value, applied to the UNREDUCED outputs as the pass kernel applies its
  * twiddles. */
 int pk_selftest_dft(const uint64_t *in, const uint64_t *tw, uint64_t *out, int le, int d, size_t n_groups);
+/* ntt_regs.hpp pre_load_sum (an NTT pass carrying pass 1 in its load): n outputs from `terms` inputs and multipliers each, rows
+ * >= live past the nonzero inputs; out = the lazy result (selftest.hip). */
+int pk_selftest_pre_load(const uint64_t *x, const uint64_t *tw, uint64_t *out, int terms, int live, size_t n);
 
 /* hooks of the GPU suite (process-wide, 0 = off; the library reads no test switch from the environment): which = 0 the spin bound of a
  * latency-mode gated kernel (to reach its give-up path in milliseconds), 1 microseconds the host sleeps before publishing each gate's
