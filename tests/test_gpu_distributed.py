@@ -10,12 +10,16 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 
-@pytest.mark.parametrize("batch,n_vars,rho,G", [(2, 10, 1, 2), (2, 10, 1, 4), (2, 13, 1, 8), (1, 12, 4, 2), (2, 17, 1, 8), (1, 9, 7, 4), (2, 8, 1, 16)])
-def test_shards_interleave_to_unsharded_encode(ctx, oracle, batch, n_vars, rho, G):
+# fold 4; then batch 3 at fold 0, 2 and 8, each with a two-pass local NTT (G = 2) and a single-pass one (G = 8)
+@pytest.mark.parametrize("batch,n_vars,rho,G,fold",
+                         [pytest.param(b, n, r, g, 4, id="%d-%d-%d-%d" % (b, n, r, g))
+                          for b, n, r, g in [(2, 10, 1, 2), (2, 10, 1, 4), (2, 13, 1, 8), (1, 12, 4, 2), (2, 17, 1, 8), (1, 9, 7, 4), (2, 8, 1, 16)]]
+                         + [pytest.param(3, n, r, g, f, id="f%d-b3-rows2^%d-G%d" % (f, n + r - f, g))
+                            for f, n, r in [(0, 11, 1), (2, 11, 3), (8, 17, 2)] for g in (2, 8)])
+def test_shards_interleave_to_unsharded_encode(ctx, oracle, batch, n_vars, rho, G, fold):
     from provekit_amd._lib import lib
     from provekit_amd.field import random_field
 
-    fold = 4
     rows, w = 1 << (n_vars + rho - fold), batch << fold
     polys = [ctx.upload(random_field(1 << n_vars, 5 * b + n_vars)) for b in range(batch)]
     ptrs = (C.c_void_p * batch)(*[p.ptr for p in polys])

@@ -5,19 +5,28 @@ import os
 
 import numpy as np
 import pytest
+from test_gpu_ntt_plan import NTT_GRID, ntt_case_id
 
 pytestmark = pytest.mark.gpu
 G = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 VEC = json.load(open(os.path.join(G, "vectors.json")))
 
 
-@pytest.mark.parametrize("log_n", [0, 1, 2, 3, 5, 9, 10, 11, 13, 18, 19, 20])
-def test_ntt_vs_oracle(ctx, oracle, log_n):
+# every size 0..20 (test_gpu_ntt_plan.NTT_GRID): the single pass at every radix with full tiles and leftover columns, then every pass
+# plan.  The sizes this test had before keep their id and operands: 3 columns below 2^16, 1 from there.
+FIRST_SIZES = {0, 1, 2, 3, 5, 9, 10, 11, 13, 18, 19, 20}
+
+
+def first_case(log_n, ncols):
+    return log_n in FIRST_SIZES and ncols == (3 if log_n < 16 else 1)
+
+
+@pytest.mark.parametrize("log_n,ncols", [pytest.param(n, c, id=str(n) if first_case(n, c) else ntt_case_id(n, c)) for n, c in NTT_GRID])
+def test_ntt_vs_oracle(ctx, oracle, log_n, ncols):
     from provekit_amd.field import random_field
     from provekit_amd.rs import ntt
 
-    ncols = 3 if log_n < 16 else 1
-    x = random_field(ncols << log_n, 100 + log_n).reshape(ncols, 1 << log_n, 4)
+    x = random_field(ncols << log_n, 100 + log_n + (0 if first_case(log_n, ncols) else 64 * ncols)).reshape(ncols, 1 << log_n, 4)
     got = ntt(x, ctx=ctx)
     for c in range(ncols):
         assert np.array_equal(got[c], oracle.ntt(x[c], log_n)), (log_n, c)

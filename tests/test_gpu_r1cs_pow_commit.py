@@ -292,11 +292,13 @@ def test_r1cs_from_postcard_matches_direct_upload(ctx, oracle):
     viapc.close()
 
 
-@pytest.mark.parametrize("batch,n_vars", [(2, 13), (2, 14), (1, 14), (1, 15), (2, 17)])
-def test_commit_across_the_hash_ready_boundary(ctx, oracle, batch, n_vars):
+# fold 4 at the shapes of the first WHIR rounds; batch 3 at fold 0, 2 and 8 right below (2^10 rows) and at (2^11) the switch
+@pytest.mark.parametrize("batch,n_vars,fold", [pytest.param(b, n, 4, id="%d-%d" % (b, n)) for b, n in [(2, 13), (2, 14), (1, 14), (1, 15), (2, 17)]]
+                         + [pytest.param(3, lr + f - 1, f, id="f%d-b3-rows2^%d" % (f, lr)) for f in (0, 2, 8) for lr in (10, 11)])
+def test_commit_across_the_hash_ready_boundary(ctx, oracle, batch, n_vars, fold):
     """pk_commit holds its codeword hash-ready (32 * value) from 2^11 rows up and as Montgomery images below (tree.hip
     codeword_scaled): roots and BOTH opening forms must equal the oracle's on either side of the switch, and pk_commit_into
-    (caller-owned buffers) must give the same root as pk_commit."""
+    (caller-owned buffers) must give the same root as pk_commit.  The first, a middle and the last leaf are always opened."""
     import ctypes as C
 
     from provekit_amd._lib import lib
@@ -305,27 +307,27 @@ def test_commit_across_the_hash_ready_boundary(ctx, oracle, batch, n_vars):
 
     polys = [random_field(1 << n_vars, 900 + b + n_vars) for b in range(batch)]
     bufs = [ctx.upload(p) for p in polys]
-    c = commit_batch(ctx, bufs, n_vars, 1, 4)
-    leaves = oracle.rs_encode(np.concatenate(polys), batch, n_vars, 1, 4)
+    c = commit_batch(ctx, bufs, n_vars, 1, fold)
+    leaves = oracle.rs_encode(np.concatenate(polys), batch, n_vars, 1, fold)
     nodes = oracle.merkle_commit(leaves)
     n = leaves.shape[0]
     assert int.from_bytes(c.root, "little") == oracle.limbs_to_ints(nodes[1])[0]
-    idx = np.unique(np.random.default_rng(n_vars).integers(0, n, size=25)).astype(np.uint64)
+    idx = np.unique(np.concatenate([np.random.default_rng(n_vars).integers(0, n, size=25), [0, n // 2, n - 1]])).astype(np.uint64)
     lv_c, sib, paths = c.open(idx, canonical_leaves=True)
     lv_m, _, _ = c.open(idx, canonical_leaves=False)
     assert np.array_equal(lv_m, leaves[idx])
     assert np.array_equal(lv_c, np.stack([oracle.from_mont(leaves[i]) for i in idx]))
     assert np.array_equal(sib, nodes[(n + idx.astype(np.int64)) ^ 1])
     szs = [C.c_size_t() for _ in range(3)]
-    ctx._check(lib.pk_commit_sizes(ctx.handle, batch, n_vars, 1, 4, *[C.byref(x) for x in szs]))
-    assert szs[0].value == n * 16 * batch and szs[1].value == 2 * n
+    ctx._check(lib.pk_commit_sizes(ctx.handle, batch, n_vars, 1, fold, *[C.byref(x) for x in szs]))
+    assert szs[0].value == n * (batch << fold) and szs[1].value == 2 * n
     d_l, d_n, d_s = (ctx.alloc_fe(x.value) for x in szs)
     ptrs = (C.c_void_p * batch)(*[b.ptr for b in bufs])
     root = (C.c_uint8 * 32)()
     from provekit_amd._lib import LEAVES_MONTGOMERY, LEAVES_SCALED32, CommitLayout
 
     lay = CommitLayout()
-    ctx._check(lib.pk_commit_into(ctx.handle, ptrs, batch, n_vars, 1, 4, d_l.ptr, d_n.ptr, d_s.ptr, root, C.byref(lay)))
+    ctx._check(lib.pk_commit_into(ctx.handle, ptrs, batch, n_vars, 1, fold, d_l.ptr, d_n.ptr, d_s.ptr, root, C.byref(lay)))
     assert bytes(root) == c.root
     assert np.array_equal(ctx.download_fe(d_n.view_fe(1), 2 * n - 1), nodes[1:])  # every node of the heap
     # the layout the commit reports: hash-ready from 2^11 rows, Montgomery below; one shard outside a device set
@@ -334,7 +336,7 @@ def test_commit_across_the_hash_ready_boundary(ctx, oracle, batch, n_vars):
     tl = CommitLayout()
     assert lib.pk_tree_layout(c.handle, C.byref(tl)) == 0 and (tl.n_shards, tl.shard, tl.encoding) == (1, 0, lay.encoding)
     # openings of the raw buffers under that layout == the handle's openings == the oracle's
-    k, w, plen = len(idx), 16 * batch, int(np.log2(n)) - 1
+    k, w, plen = len(idx), batch << fold, int(np.log2(n)) - 1
     for canon, want in ((1, lv_c), (0, lv_m)):
         lo = np.zeros((k, w, 4), dtype=np.uint64)
         so = np.zeros((k, 4), dtype=np.uint64)
