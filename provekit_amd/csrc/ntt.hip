@@ -470,7 +470,7 @@ __global__ __launch_bounds__(256) void ntt_shard_prestep_kernel(const fe* __rest
 // Sixteen provers on one GPU used to hold sixteen copies of every table (71 MB each at the poseidon size): 1.1 GB of identical
 // twiddles competing for the 256 MiB Infinity Cache.  The tables are pure functions of their key, so one copy per device serves
 // every context: built once under the store's mutex (the building context drains its stream before the table is published),
-// kept until the last context of the device is destroyed.  A context remembers the pointers it has looked up (its own maps), so
+// kept until the last context of the device is destroyed.  A context remembers the pointers it has looked up (pk_ctx::tables), so
 // the hot path takes no lock.
 struct TableStore {
     std::mutex mu;
@@ -484,125 +484,65 @@ TableStore& store_of(int device) {
     return stores[device];
 }
 enum TableKind : unsigned long long { TK_W = 1, TK_WS = 2, TK_W29 = 3, TK_WS29 = 4, TK_PASS = 5 };
-// looks `key` up in the device's store; on a miss `build` allocates and fills the table on ctx->stream
-template <class Build>
-int shared_table(pk_ctx* ctx, unsigned long long key, void** out, Build build) {
-    TableStore& S = store_of(ctx->device);
-    std::lock_guard<std::mutex> lock(S.mu);
-    auto it = S.tables.find(key);
-    if (it != S.tables.end()) {
-        *out = it->second;
-        return PK_OK;
+// the table (kind, key), `bytes` long: from the context's own map (a pk_ctx is single-caller: no locking on this path), else from the
+// device's store, else built into the store -- `fill` enqueues the kernels that fill a fresh allocation on ctx->stream
+template <class T, class Fill>
+int table(pk_ctx* ctx, TableKind kind, unsigned key, size_t bytes, const T** out, Fill fill) {
+    const unsigned long long id = (kind << 56) | key;
+    auto it = ctx->tables.find(id);
+    if (it == ctx->tables.end()) {
+        TableStore& S = store_of(ctx->device);
+        std::lock_guard<std::mutex> lock(S.mu);
+        auto st = S.tables.find(id);
+        if (st == S.tables.end()) {
+            T* made = nullptr;
+            PK_HIP(ctx, hipMalloc((void**)&made, bytes));
+            fill(made);
+            PK_LAUNCH_CHECK(ctx);
+            PK_WAIT(ctx);  // complete before another context's stream may read it
+            st = S.tables.emplace(id, (void*)made).first;
+        }
+        it = ctx->tables.emplace(id, st->second).first;
     }
-    void* T = nullptr;
-    int rc = build(&T);
-    if (rc) return rc;
-    PK_WAIT(ctx);  // complete before another context's stream may read it
-    S.tables[key] = T;
-    *out = T;
+    *out = (const T*)it->second;
     return PK_OK;
 }
 
+// W[e] = w_N^e, e < N
 int get_twiddles(pk_ctx* ctx, unsigned log_n, const fe** out) {
-    // the context's own map of pointers already looked up (a pk_ctx is single-caller: no locking on this path)
-    auto it = ctx->twiddles.find(log_n);
-    if (it != ctx->twiddles.end()) {
-        *out = (const fe*)it->second;
-        return PK_OK;
-    }
-    void* T = nullptr;
-    int rc = shared_table(ctx, (TK_W << 56) | log_n, &T, [&](void** made) {
-        size_t n = (size_t)1 << log_n;
-        fe* W = nullptr;
-        PK_HIP(ctx, hipMalloc((void**)&W, 32 * (n < 2 ? 2 : n)));
+    const size_t n = (size_t)1 << log_n;
+    return table(ctx, TK_W, log_n, 32 * std::max<size_t>(n, 2), out, [&](fe* W) {
         twiddle_init_kernel<<<1, 64, 0, ctx->stream>>>(W, log_n);
         for (size_t h = 2; h < n; h <<= 1) {
             twiddle_seed_kernel<<<1, 64, 0, ctx->stream>>>(W, h);
             unsigned grid = (unsigned)((h + 255) / 256);
             twiddle_double_kernel<<<grid, 256, 0, ctx->stream>>>(W, h);
         }
-        PK_LAUNCH_CHECK(ctx);
-        *made = W;
-        return (int)PK_OK;
     });
-    if (rc) return rc;
-    ctx->twiddles[log_n] = T;
-    *out = (const fe*)T;
-    return PK_OK;
 }
 
-int get_twiddles_scaled(pk_ctx* ctx, unsigned log_n, const fe* W, const fe** out) {
-    auto it = ctx->twiddles_scaled.find(log_n);
-    if (it != ctx->twiddles_scaled.end()) {
-        *out = (const fe*)it->second;
-        return PK_OK;
-    }
-    void* T = nullptr;
-    int rc = shared_table(ctx, (TK_WS << 56) | log_n, &T, [&](void** made) {
-        const size_t n = (size_t)1 << log_n;
-        fe* Ws = nullptr;
-        PK_HIP(ctx, hipMalloc((void**)&Ws, 32 * (n < 2 ? 2 : n)));
-        twiddle_scale_kernel<<<(unsigned)((n + 255) / 256), 256, 0, ctx->stream>>>(W, Ws, n);
-        PK_LAUNCH_CHECK(ctx);
-        *made = Ws;
-        return (int)PK_OK;
-    });
-    if (rc) return rc;
-    ctx->twiddles_scaled[log_n] = T;
-    *out = (const fe*)T;
-    return PK_OK;
-}
-
-int get_twiddles29(pk_ctx* ctx, unsigned log_n, int which, const fe* W, const u32** out) {
-    auto& cache = ctx->twiddles29[which];
-    auto it = cache.find(log_n);
-    if (it != cache.end()) {
-        *out = (const u32*)it->second;
-        return PK_OK;
-    }
-    void* T = nullptr;
-    int rc = shared_table(ctx, ((which ? TK_WS29 : TK_W29) << 56) | log_n, &T, [&](void** made) {
-        const size_t n = (size_t)1 << log_n;
-        u32* U = nullptr;
-        PK_HIP(ctx, hipMalloc((void**)&U, 4 * TW29S_WORDS * (n < 2 ? 2 : n)));
-        twiddle_shoup_kernel<<<(unsigned)((n + 255) / 256), 256, 0, ctx->stream>>>(W, U, n);
-        PK_LAUNCH_CHECK(ctx);
-        *made = U;
-        return (int)PK_OK;
-    });
-    if (rc) return rc;
-    cache[log_n] = T;
-    *out = (const u32*)T;
-    return PK_OK;
-}
-
-// Pass-ordered tables pay where the size-N multiplier table no longer fits the caches (72 B x 2^19 = 36 MiB > the 32 MiB of L2): there
-// the strided gathers cost 2.6x the data traffic of a pass.  Below that both tables are cache-resident and the gathers are free.
-// Measured on the 2^22 / 2^21-coefficient encodes (rows 2^19 / 2^18), same box, alternating: threshold 20 -> 1.705 / 0.783 ms,
-// 19 -> 1.634 / 0.793, 18 -> 1.641 / 0.814.
-constexpr unsigned PASS_TABLE_MIN_LOG_N = 19;
-// the pass-ordered table of one (size, pass, variant): key = log_n | pass << 8 | scaled << 12
-int get_pass_table(pk_ctx* ctx, unsigned log_n, unsigned pass, bool scaled, const u32* src29, size_t rows_k, size_t row, size_t mul, const u32** out) {
-    const unsigned key = log_n | (pass << 8) | ((scaled ? 1u : 0u) << 12);
-    auto it = ctx->twiddles_pass.find(key);
-    if (it != ctx->twiddles_pass.end()) {
-        *out = (const u32*)it->second;
-        return PK_OK;
-    }
-    void* T = nullptr;
-    int rc = shared_table(ctx, (TK_PASS << 56) | key, &T, [&](void** made) {
-        u32* U = nullptr;
-        const size_t n = rows_k * row;
-        PK_HIP(ctx, hipMalloc((void**)&U, 4 * TW29S_WORDS * n));
-        twiddle_pass_table_kernel<<<(unsigned)((n + 255) / 256), 256, 0, ctx->stream>>>(src29, U, rows_k, row, mul, ((size_t)1 << log_n) - 1);
-        PK_LAUNCH_CHECK(ctx);
-        *made = U;
-        return (int)PK_OK;
-    });
-    if (rc) return rc;
-    ctx->twiddles_pass[key] = T;
-    *out = (const u32*)T;
-    return PK_OK;
+// The tables of a transform of 2^log_n.  Ws: the hash-ready variant 32 * w_N^e when `scaled`, else W itself.  W29 / Ws29: W / Ws as
+// the register-radix kernel's Shoup multipliers (18 x u32 per entry, ntt_regs.hpp tw29s), from log_n >= 3.
+struct Twiddles {
+    const fe *W, *Ws;
+    const u32 *W29, *Ws29;
+};
+int get_tables(pk_ctx* ctx, unsigned log_n, bool scaled, Twiddles* t) {
+    const size_t n = (size_t)1 << log_n, entries = std::max<size_t>(n, 2);
+    const unsigned grid = (unsigned)((n + 255) / 256);
+    *t = Twiddles{};
+    int rc = get_twiddles(ctx, log_n, &t->W);
+    t->Ws = t->W;
+    if (!rc && scaled)
+        rc = table(ctx, TK_WS, log_n, 32 * entries, &t->Ws, [&](fe* Ws) { twiddle_scale_kernel<<<grid, 256, 0, ctx->stream>>>(t->W, Ws, n); });
+    if (rc || log_n < 3) return rc;
+    auto shoup = [&](TableKind kind, const fe* X, const u32** out) {
+        return table(ctx, kind, log_n, 4 * TW29S_WORDS * entries, out, [&](u32* U) { twiddle_shoup_kernel<<<grid, 256, 0, ctx->stream>>>(X, U, n); });
+    };
+    rc = shoup(TK_W29, t->W, &t->W29);
+    t->Ws29 = t->W29;
+    if (!rc && scaled) rc = shoup(TK_WS29, t->Ws, &t->Ws29);
+    return rc;
 }
 
 // does a pass of radix 2^log_r over a v axis of 2^log_v take the register-radix kernel?
@@ -613,24 +553,40 @@ inline bool pass_is_fast(unsigned log_r, unsigned log_v, size_t N) { return log_
 // VALUBusy against 89 % and 6-9 % slower from 2^19 rows up: profiles/r06_ntt_le_ab.jsonl.)
 constexpr int NTT_LE = 2;
 
+// The dynamic-LDS opt-in (up to 72 KiB) is a per-function, per-device attribute: set it once per device (the kernel's `done` bits),
+// not per launch
+int set_lds_once(pk_ctx* ctx, const void* kernel, size_t lds_bytes, std::atomic<unsigned long long>& done) {
+    const unsigned long long dev_bit = 1ull << (ctx->device & 63);
+    if (!(done.load(std::memory_order_acquire) & dev_bit)) {
+        PK_HIP(ctx, hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+        done.fetch_or(dev_bit, std::memory_order_release);
+    }
+    return PK_OK;
+}
+
 template <int LE, int LOG_R, bool CONTIG, bool PRE>
 int launch_fast(pk_ctx* ctx, const PassParams& pp, unsigned grid) {
     const size_t lds_bytes = 9 * 2048 * 4;
-    // the 72 KiB dynamic-LDS opt-in is a per-function, per-device attribute: set it once per device, not per launch
     static std::atomic<unsigned long long> lds_set{0};
-    const unsigned long long dev_bit = 1ull << (ctx->device & 63);
-    if (!(lds_set.load(std::memory_order_acquire) & dev_bit)) {
-        PK_HIP(ctx, hipFuncSetAttribute((const void*)ntt8_pass_kernel<LE, LOG_R, CONTIG, PRE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-        lds_set.fetch_or(dev_bit, std::memory_order_release);
-    }
+    if (int rc = set_lds_once(ctx, (const void*)ntt8_pass_kernel<LE, LOG_R, CONTIG, PRE>, lds_bytes, lds_set)) return rc;
     ntt8_pass_kernel<LE, LOG_R, CONTIG, PRE><<<dim3(grid, 1), 2048 >> LE, lds_bytes, ctx->stream>>>(pp);
+    PK_LAUNCH_CHECK(ctx);
+    return PK_OK;
+}
+
+template <int LOG_R, bool CONTIG>
+int launch_lds(pk_ctx* ctx, const PassParams& p, dim3 grid) {
+    constexpr int R = 1 << LOG_R;
+    const size_t lds_bytes = (size_t)(2 * R * BT + 2 * (R / 2 > 0 ? R / 2 : 1)) * 16;
+    static std::atomic<unsigned long long> lds_set{0};
+    if (int rc = set_lds_once(ctx, (const void*)ntt_pass_kernel<LOG_R, CONTIG>, lds_bytes, lds_set)) return rc;
+    ntt_pass_kernel<LOG_R, CONTIG><<<grid, NTHREADS, lds_bytes, ctx->stream>>>(p);
     PK_LAUNCH_CHECK(ctx);
     return PK_OK;
 }
 
 template <int LOG_R>
 int launch_pass_r(pk_ctx* ctx, const PassParams& p, bool in_r_contig, size_t tiles, unsigned ncols) {
-    constexpr int R = 1 << LOG_R;
     // register-radix fast path: needs at least BT8 = 2048/R elements along v per tile and a real twiddle table
     if (pass_is_fast(LOG_R, p.log_v, p.n_mask + 1)) {
         ProfScope prof(ctx, in_r_contig ? "ntt_pass_last" : "ntt_pass");
@@ -650,17 +606,8 @@ int launch_pass_r(pk_ctx* ctx, const PassParams& p, bool in_r_contig, size_t til
     }
     PK_REQUIRE(ctx, p.in_poly[0] == nullptr && p.pre_terms == 0, "fused NTT input needs the register-radix pass");
     ProfScope prof(ctx, in_r_contig ? "ntt_pass_last" : "ntt_pass");
-    size_t lds_bytes = (size_t)(2 * R * BT + 2 * (R / 2 > 0 ? R / 2 : 1)) * 16;
-    dim3 grid((unsigned)tiles, ncols);
-    if (in_r_contig) {
-        PK_HIP(ctx, hipFuncSetAttribute((const void*)ntt_pass_kernel<LOG_R, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-        ntt_pass_kernel<LOG_R, true><<<grid, NTHREADS, lds_bytes, ctx->stream>>>(p);
-    } else {
-        PK_HIP(ctx, hipFuncSetAttribute((const void*)ntt_pass_kernel<LOG_R, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-        ntt_pass_kernel<LOG_R, false><<<grid, NTHREADS, lds_bytes, ctx->stream>>>(p);
-    }
-    PK_LAUNCH_CHECK(ctx);
-    return PK_OK;
+    const dim3 grid((unsigned)tiles, ncols);
+    return in_r_contig ? launch_lds<LOG_R, true>(ctx, p, grid) : launch_lds<LOG_R, false>(ctx, p, grid);
 }
 
 int launch_pass(pk_ctx* ctx, unsigned log_r, const PassParams& p, bool in_r_contig, size_t tiles, unsigned ncols) {
@@ -690,29 +637,13 @@ void ntt_retain_ctx(pk_ctx* ctx) {
 }
 // the context forgets its pointers; the device's tables go with its last context
 void ntt_release_ctx(pk_ctx* ctx) {
-    ctx->twiddles.clear();
-    ctx->twiddles_scaled.clear();
-    for (auto& c : ctx->twiddles29) c.clear();
-    ctx->twiddles_pass.clear();
+    ctx->tables.clear();
     TableStore& S = store_of(ctx->device);
     std::lock_guard<std::mutex> lock(S.mu);
     if (S.contexts && --S.contexts == 0) {
         for (auto& kv : S.tables) (void)hipFree(kv.second);
         S.tables.clear();
     }
-}
-
-// Can a transform of this size deliver the hash-ready output (every output = 32 * value as a plain integer < p instead of
-// the Montgomery image)?  It rides on the LAST inter-pass twiddle multiplication, so the size needs two or more passes and
-// that pass must be the register-radix kernel.  A pure function of the size: commit and openings agree on the encoding.
-bool ntt_scaled_available(unsigned log_n) {
-    if (log_n <= 9 || log_n > 27) return false;
-    if (log_n <= 18) {
-        unsigned l1 = (log_n + 1) / 2, l2 = log_n - l1;
-        return pass_is_fast(l1, l2, (size_t)1 << log_n);
-    }
-    unsigned l1 = (log_n + 2) / 3, l2 = (log_n - l1 + 1) / 2, l3 = log_n - l1 - l2;
-    return pass_is_fast(l2, l3, (size_t)1 << log_n);
 }
 
 // Pass 1 evaluated inside the next pass's load (PassParams::pre_terms) when at most this many of its rows are nonzero.  Counted per
@@ -723,35 +654,48 @@ bool ntt_scaled_available(unsigned log_n) {
 constexpr size_t PRE_MAX_TERMS = 3;
 static_assert(PRE_MAX_TERMS <= 4, "pre_load_sum: red29 takes a sum of at most four products");
 
-// the pass split of a transform of 2^log_n (log_n > 9) and how its first pass is run for a given number of nonzero inputs
+// The pass split of a transform of 2^log_n (log_n > 9) into P passes of radix R_i = 2^l[i-1], and how its first pass is run for a
+// given number of nonzero inputs.  Arrays are indexed by pass - 1.
 struct NttPlan {
-    unsigned npass, l1, l2, l3;
-    size_t stride1;   // natural-index distance between the rows of pass 1's DFT
-    size_t L1;        // rows of pass 1 that hold a nonzero input
-    bool pre;         // pass 1 is folded into pass 2's load
-    bool fast1;       // pass 1 runs in the register-radix kernel
+    unsigned P;         // 2 up to 2^18, else 3
+    unsigned l[3];      // as even as possible, the larger first
+    unsigned log_v[3];  // the pass's v axis: the index below its digit, k_1 for the last pass
+    bool fast[3];       // the pass runs in the register-radix kernel
+    size_t L1;          // rows of pass 1 that hold a nonzero input
+    bool pre;           // pass 1 is folded into pass 2's load
 };
 NttPlan ntt_plan(unsigned log_n, size_t nonzero) {
     NttPlan q{};
     const size_t N = (size_t)1 << log_n;
-    if (log_n <= 18) {
-        q.npass = 2;
-        q.l1 = (log_n + 1) / 2;
-        q.l2 = log_n - q.l1;
-        q.stride1 = (size_t)1 << q.l2;
-        q.fast1 = pass_is_fast(q.l1, q.l2, N);
-    } else {
-        q.npass = 3;
-        q.l1 = (log_n + 2) / 3;
-        q.l2 = (log_n - q.l1 + 1) / 2;
-        q.l3 = log_n - q.l1 - q.l2;
-        q.stride1 = (size_t)1 << (q.l2 + q.l3);
-        q.fast1 = pass_is_fast(q.l1, q.l2 + q.l3, N);
+    q.P = log_n <= 18 ? 2 : 3;
+    unsigned left = log_n;
+    for (unsigned i = 0; i < q.P; i++) {
+        q.l[i] = (left + q.P - i - 1) / (q.P - i);
+        left -= q.l[i];
+        q.log_v[i] = i + 1 < q.P ? left : q.l[0];
+        q.fast[i] = pass_is_fast(q.l[i], q.log_v[i], N);
     }
-    q.L1 = std::max<size_t>(1, (std::min(nonzero, N) + q.stride1 - 1) / q.stride1);
-    const bool fast2 = q.npass == 2 ? pass_is_fast(q.l2, q.l1, N) : pass_is_fast(q.l2, q.l3, N);
-    q.pre = q.L1 <= PRE_MAX_TERMS && fast2;
+    const size_t stride1 = N >> q.l[0];  // natural-index distance between the rows of pass 1's DFT
+    q.L1 = std::max<size_t>(1, (std::min(nonzero, N) + stride1 - 1) / stride1);
+    q.pre = q.L1 <= PRE_MAX_TERMS && q.fast[1];
     return q;
+}
+
+// Can a transform of this size deliver the hash-ready output (every output = 32 * value as a plain integer < p instead of
+// the Montgomery image)?  It rides on the LAST inter-pass twiddle multiplication (pass P-1's), so the size needs two or more passes
+// and that pass must be the register-radix kernel.  A pure function of the size: commit and openings agree on the encoding.
+bool ntt_scaled_available(unsigned log_n) {
+    if (log_n <= 9 || log_n > 27) return false;
+    const NttPlan q = ntt_plan(log_n, 0);
+    return q.fast[q.P - 2];
+}
+
+// can a transform of 2^log_n with `nonzero` leading inputs read de-interleaved polynomials in place (NttInput::polys)?  The pass
+// that loads them must be the register-radix kernel.
+bool ntt_reads_polys(unsigned log_n, size_t nonzero) {
+    if (log_n <= 9) return false;
+    const NttPlan q = ntt_plan(log_n, nonzero);
+    return q.pre || q.fast[0];
 }
 
 // where the transform's input columns are: in + col * col_stride, or (polys != null) the de-interleaved polynomials
@@ -763,6 +707,108 @@ struct NttInput {
     unsigned fold, npolys;
 };
 
+// what the passes of one transform share
+struct NttRun {
+    NttPlan plan;
+    unsigned log_n;
+    bool scaled_out;
+    Twiddles tw;
+    NttInput src;
+    size_t nonzero;
+    size_t e;  // element stride of the input columns: 2^fold for de-interleaved polynomials, else 1
+    fe* scratch;
+    fe* out;
+    size_t out_col_stride;
+};
+
+// Pass-ordered tables pay where the size-N multiplier table no longer fits the caches (72 B x 2^19 = 36 MiB > the 32 MiB of L2): there
+// the strided gathers cost 2.6x the data traffic of a pass.  Below that both tables are cache-resident and the gathers are free.
+// Measured on the 2^22 / 2^21-coefficient encodes (rows 2^19 / 2^18), same box, alternating: threshold 20 -> 1.705 / 0.783 ms,
+// 19 -> 1.634 / 0.793, 18 -> 1.641 / 0.814.
+constexpr unsigned PASS_TABLE_MIN_LOG_N = 19;
+
+// The PassParams of pass i + 1 of P by the mixed-radix rule at the head of this file (N = R_1 ... R_P), written from a
+// value-initialised struct so that nothing carries over from another pass.  S = R_(i+2) ... R_P is the distance between the rows of
+// the pass's DFT.  A pass before the last transforms digit n_(i+1) for every v < S (the index below that digit) and every u (the
+// digits k_1 .. k_i of the earlier passes), multiplies output k_(i+1) by w_N^(R_1 ... R_i k_(i+1) v) and writes in place into the
+// scratch.  The last pass transforms n_P (contiguous) for v = k_1 and u = k_2 (P = 3) into output k_1 + R_1 k_2 + R_1 R_2 k_3.
+static int pass_params(pk_ctx* ctx, const NttRun& t, unsigned i, PassParams* out) {
+    const NttPlan& q = t.plan;
+    const bool last = i + 1 == q.P;
+    const size_t N = (size_t)1 << t.log_n, R1 = (size_t)1 << q.l[0], S1 = N / R1;
+    unsigned done = 0;
+    for (unsigned j = 0; j < i; j++) done += q.l[j];
+    const size_t K = (size_t)1 << done, R = (size_t)1 << q.l[i], S = N / (K * R);  // K = R_1 ... R_i
+    // the table of pass j + 1's inter-pass twiddle: the last of them (pass P-1's) carries the hash-ready output scaling
+    auto tw29 = [&](unsigned j) { return j + 2 == q.P ? t.tw.Ws29 : t.tw.W29; };
+    PassParams p{};
+    p.W = t.tw.W;
+    p.W29 = t.tw.W29;
+    p.Wtw = i + 2 == q.P ? t.tw.Ws : t.tw.W;
+    p.Wtw29 = tw29(i);
+    p.n_mask = N - 1;
+    p.log_v = q.log_v[i];
+    p.wr_step = N >> q.l[i];
+    if (!last) {
+        p.out = t.scratch;
+        p.out_col_stride = N;
+        p.out_stride_r = S;
+        p.out_stride_v = 1;
+        p.out_stride_u = i ? R * S : 0;
+        p.tw_mul = K;
+        p.tp_row = S;
+        p.lazy_store = q.fast[i + 1];  // the register-radix kernel takes almost reduced inputs
+    } else {
+        p.out = t.out;
+        p.out_col_stride = t.out_col_stride;
+        p.out_stride_r = K;
+        p.out_stride_v = 1;
+        p.out_stride_u = q.P == 3 ? R1 : 0;
+        p.lazy_store = t.scaled_out;
+    }
+    if (i == 0 || (i == 1 && q.pre)) {  // the pass that reads the transform's input: strides in units of e elements
+        p.in = t.src.in;
+        p.in_col_stride = t.src.col_stride;
+        if (t.src.polys) {
+            for (unsigned b = 0; b < t.src.npolys; b++) p.in_poly[b] = t.src.polys[b];
+            p.in_fold = t.src.fold;
+        }
+        p.nonzero = t.nonzero;
+        p.in_nat_r = S;  // natural input index r S + v (the last pass's v is k_1, no input digit)
+        p.in_nat_v = last ? 0 : 1;
+        if (i == 0) {
+            p.in_stride_r = S * t.e;
+            p.in_stride_v = t.e;
+        } else {
+            // pass 1 folded into this pass's load: k_1 lies on v when this is the last pass, on u otherwise
+            p.pre_terms = (int)q.L1;
+            p.pre_stride = S1;
+            p.pre_elem = t.e;
+            p.pre_ku = last ? 0 : 1;
+            p.pre_kv = last ? 1 : 0;
+            p.Wpre29 = tw29(0);
+        }
+    } else {  // the scratch as the previous pass wrote it
+        p.in = t.scratch;
+        p.in_col_stride = N;
+        p.nonzero = 1;  // nat is always 0 < 1: everything is read
+        p.in_stride_r = last ? 1 : S;
+        p.in_stride_v = last ? S1 : 1;
+        p.in_stride_u = last ? (q.P == 3 ? R : 0) : R * S;
+    }
+    if (!last && t.log_n >= PASS_TABLE_MIN_LOG_N && q.fast[i]) {
+        // the pass's inter-pass twiddles in the order it reads them: key = log_n | pass << 8 | scaled << 12
+        const unsigned key = t.log_n | ((i + 1) << 8) | ((t.scaled_out && i + 2 == q.P ? 1u : 0u) << 12);
+        const u32* src = p.Wtw29;
+        int rc = table(ctx, TK_PASS, key, 4 * TW29S_WORDS * R * S, &p.Tpass29, [&](u32* T) {
+            twiddle_pass_table_kernel<<<(unsigned)((R * S + 255) / 256), 256, 0, ctx->stream>>>(src, T, R, S, K, N - 1);
+        });
+        if (rc) return rc;
+    }
+    *out = p;
+    return PK_OK;
+}
+
 // Column-batched NTT, natural -> natural.  `ncols` vectors of length N = 2^log_n:
 // input column c (NttInput) holds `nonzero` leading coefficients (rest is zero and is never read); output column c at
 // out + c*out_col_stride.  `scratch` must hold ncols columns of N elements (column stride N) when log_n > 9, and may alias nothing.
@@ -772,217 +818,59 @@ int ntt_columns_in(pk_ctx* ctx, const NttInput& src, size_t nonzero, fe* out, si
     PK_REQUIRE(ctx, log_n <= 27, "NTT size above 2^27");
     PK_REQUIRE(ctx, !scaled_out || ntt_scaled_available(log_n), "hash-ready NTT output is not available at this size");
     const size_t N = (size_t)1 << log_n;
-    const fe* W = nullptr;
-    int rc = get_twiddles(ctx, log_n, &W);
+    Twiddles tw;
+    int rc = get_tables(ctx, log_n, scaled_out, &tw);
     if (rc) return rc;
-    const fe* Ws = W;
-    if (scaled_out && (rc = get_twiddles_scaled(ctx, log_n, W, &Ws))) return rc;
-    const u32 *W29 = nullptr, *Ws29 = nullptr;
-    if (log_n >= 3) {  // the register-radix kernel's operand tables
-        if ((rc = get_twiddles29(ctx, log_n, 0, W, &W29))) return rc;
-        Ws29 = W29;
-        if (scaled_out && (rc = get_twiddles29(ctx, log_n, 1, Ws, &Ws29))) return rc;
-    }
-    const fe* in = src.in;
-    const size_t in_col_stride = src.col_stride;
-    PassParams p{};
-    p.W = W;
-    p.Wtw = W;
-    p.W29 = W29;
-    p.Wtw29 = W29;
-    p.lazy_store = 0;
-    p.n_mask = N - 1;
     if (log_n <= 9) {
         PK_REQUIRE(ctx, src.polys == nullptr, "fused NTT input needs more than 512 rows");
         // single pass: R = N and the tile's batch axis v runs over BT adjacent *columns*
-        p.in = in;
+        PassParams p{};
+        p.in = src.in;
         p.out = out;
-        p.in_col_stride = 0;
-        p.out_col_stride = 0;
         p.in_stride_r = 1;
-        p.in_stride_v = in_col_stride;
-        p.in_stride_u = 0;
+        p.in_stride_v = src.col_stride;
         p.out_stride_r = 1;
         p.out_stride_v = out_col_stride;
-        p.out_stride_u = 0;
         p.in_nat_r = 1;
-        p.in_nat_v = 0;
-        p.in_nat_u = 0;
         p.nonzero = nonzero;
-        p.tw_mul = 0;
+        p.W = p.Wtw = tw.W;
+        p.W29 = p.Wtw29 = tw.W29;
+        p.n_mask = N - 1;
         p.wr_step = 1;
+        p.log_v = 62;  // vblocks = 2^62/BT: u = 0 and vb = blockIdx.x = group of BT columns
         unsigned full = ncols / BT, rem = ncols % BT;
-        if (full) {
-            PassParams q = p;
-            q.log_v = 62;  // vblocks = 2^62/BT: u = 0 and vb = blockIdx.x = group of BT columns
-            rc = launch_pass(ctx, log_n, q, true, full, 1);
-            if (rc) return rc;
-        }
+        if (full && (rc = launch_pass(ctx, log_n, p, true, full, 1))) return rc;
         for (unsigned c = ncols - rem; c < ncols; c++) {
             // remainder columns: a tile whose 4 lanes-of-batch all read column c; only b == 0 is stored
             // (handled by pointing the v stride at 0 and letting the 4 copies write the same values)
             PassParams q = p;
-            q.in = in + (size_t)c * in_col_stride;
+            q.in = src.in + (size_t)c * src.col_stride;
             q.out = out + (size_t)c * out_col_stride;
             q.in_stride_v = 0;
             q.out_stride_v = 0;
-            q.log_v = 62;
-            rc = launch_pass(ctx, log_n, q, true, 1, 1);
-            if (rc) return rc;
+            if ((rc = launch_pass(ctx, log_n, q, true, 1, 1))) return rc;
         }
         return PK_OK;
     }
     PK_REQUIRE(ctx, scratch != nullptr, "scratch required for N > 512");
-    const NttPlan plan = ntt_plan(log_n, nonzero);
-    // the input side of whichever pass reads the columns: strides below are in units of `e` elements of the column
-    size_t e = 1;
+    NttRun t{ntt_plan(log_n, nonzero), log_n, scaled_out, tw, src, nonzero, 1, scratch, out, out_col_stride};
     if (src.polys) {
-        PK_REQUIRE(ctx, plan.pre || plan.fast1, "fused NTT input needs the register-radix pass");
+        PK_REQUIRE(ctx, t.plan.pre || t.plan.fast[0], "fused NTT input needs the register-radix pass");
         PK_REQUIRE(ctx, src.npolys >= 1 && src.npolys <= 16 && ((size_t)src.npolys << src.fold) == ncols, "bad fused NTT input");
-        for (unsigned b = 0; b < src.npolys; b++) p.in_poly[b] = src.polys[b];
-        p.in_fold = src.fold;
-        e = (size_t)1 << src.fold;
+        t.e = (size_t)1 << src.fold;
     }
-    // PassParams of a pass that reads the transform's input (pass 1, or pass 2 with pass 1 folded into its load)
-    auto reads_input = [&](PassParams q) {
-        q.in = in;
-        q.in_col_stride = in_col_stride;
-        q.nonzero = nonzero;
-        return q;
-    };
-    auto reads_scratch = [&](PassParams q) {
-        for (auto& ptr : q.in_poly) ptr = nullptr;
-        q.pre_terms = 0;
-        q.in = scratch;
-        q.in_col_stride = N;
-        q.nonzero = 1;  // nat is always 0 < 1: everything is read
-        return q;
-    };
-    if (plan.npass == 2) {
-        const unsigned l1 = plan.l1, l2 = plan.l2;
-        size_t R1 = (size_t)1 << l1, R2 = (size_t)1 << l2;
-        if (!plan.pre) {
-            // pass 1: DFT over n1 (stride R2); v = n2; in -> scratch (same layout); twiddle w_N^(k1*n2)
-            p = reads_input(p);
-            p.out = scratch;
-            p.out_col_stride = N;
-            p.in_stride_r = R2 * e; p.in_stride_v = e; p.in_stride_u = 0;
-            p.out_stride_r = R2; p.out_stride_v = 1; p.out_stride_u = 0;
-            p.log_v = l2;
-            p.in_nat_r = R2; p.in_nat_v = 1; p.in_nat_u = 0;
-            p.tw_mul = 1;
-            p.Wtw = Ws;  // the only inter-pass twiddle of a two-pass transform carries the output scaling
-            p.Wtw29 = Ws29;
-            p.lazy_store = pass_is_fast(l2, l1, N);  // the register-radix kernel takes almost reduced inputs
-            p.wr_step = N >> l1;
-            p.tp_row = R2;
-            rc = launch_pass(ctx, l1, p, false, R2 / BT, ncols);
-            if (rc) return rc;
-            p = reads_scratch(p);
-            p.in_stride_r = 1; p.in_stride_v = R2; p.in_stride_u = 0;
-            p.in_nat_r = 0; p.in_nat_v = 0; p.in_nat_u = 0;
-        } else {
-            // pass 1 folded into pass 2's load: input m = n2 = r, k1 = v
-            p = reads_input(p);
-            p.in_stride_r = 0; p.in_stride_v = 0; p.in_stride_u = 0;
-            p.in_nat_r = 1; p.in_nat_v = 0; p.in_nat_u = 0;
-            p.pre_terms = (int)plan.L1;
-            p.pre_stride = R2;
-            p.pre_elem = e;
-            p.pre_ku = 0;
-            p.pre_kv = 1;
-            p.Wpre29 = Ws29;  // pass 1's twiddle carries the output scaling
-        }
-        p.Wtw = W;
-        p.Wtw29 = W29;
-        p.lazy_store = scaled_out ? 1 : 0;
-        // pass 2: DFT over n2 (contiguous); v = k1 (in stride R2, out stride 1); out k2 stride R1
-        p.out = out;
-        p.out_col_stride = out_col_stride;
-        p.out_stride_r = R1; p.out_stride_v = 1; p.out_stride_u = 0;
-        p.log_v = l1;
-        p.tw_mul = 0;
-        p.wr_step = N >> l2;
-        return launch_pass(ctx, l2, p, true, R1 / BT, ncols);
+    for (unsigned i = t.plan.pre ? 1 : 0; i < t.plan.P; i++) {  // a folded pass 1 is not launched
+        PassParams p;
+        if ((rc = pass_params(ctx, t, i, &p)) || (rc = launch_pass(ctx, t.plan.l[i], p, i + 1 == t.plan.P, (N >> t.plan.l[i]) / BT, ncols)))
+            return rc;
     }
-    // three passes
-    const unsigned l1 = plan.l1, l2 = plan.l2, l3 = plan.l3;
-    size_t R1 = (size_t)1 << l1, R2 = (size_t)1 << l2, R3 = (size_t)1 << l3;
-    if (!plan.pre) {
-        // pass 1: DFT over n1 (stride R2*R3); v = m = n2*R3+n3; twiddle w_N^(k1*m); in -> scratch
-        p = reads_input(p);
-        p.out = scratch;
-        p.out_col_stride = N;
-        p.in_stride_r = R2 * R3 * e; p.in_stride_v = e; p.in_stride_u = 0;
-        p.out_stride_r = R2 * R3; p.out_stride_v = 1; p.out_stride_u = 0;
-        p.log_v = l2 + l3;
-        p.in_nat_r = R2 * R3; p.in_nat_v = 1; p.in_nat_u = 0;
-        p.tw_mul = 1;
-        p.lazy_store = pass_is_fast(l2, l3, N);
-        p.wr_step = N >> l1;
-        if (log_n >= PASS_TABLE_MIN_LOG_N && pass_is_fast(l1, l2 + l3, N) && (rc = get_pass_table(ctx, log_n, 1, false, W29, R1, R2 * R3, 1, &p.Tpass29))) return rc;
-        p.tp_row = R2 * R3;
-        rc = launch_pass(ctx, l1, p, false, (R2 * R3) / BT, ncols);
-        if (rc) return rc;
-        p.Tpass29 = nullptr;
-        p = reads_scratch(p);
-        p.in_stride_r = R3; p.in_stride_v = 1; p.in_stride_u = R2 * R3;
-        p.in_nat_r = 0; p.in_nat_v = 0; p.in_nat_u = 0;
-    } else {
-        // pass 1 folded into pass 2's load: input m = n2*R3 + n3 = r*R3 + v, k1 = u
-        p = reads_input(p);
-        p.in_stride_r = 0; p.in_stride_v = 0; p.in_stride_u = 0;
-        p.in_nat_r = R3; p.in_nat_v = 1; p.in_nat_u = 0;
-        p.pre_terms = (int)plan.L1;
-        p.pre_stride = R2 * R3;
-        p.pre_elem = e;
-        p.pre_ku = 1;
-        p.pre_kv = 0;
-        p.Wpre29 = W29;
-    }
-    // pass 2: DFT over n2 (stride R3); v = n3; u = k1 (stride R2*R3); in place; twiddle w_N^(R1*k2*n3)
-    p.out = scratch;
-    p.out_col_stride = N;
-    p.out_stride_r = R3; p.out_stride_v = 1; p.out_stride_u = R2 * R3;
-    p.log_v = l3;
-    p.tw_mul = R1;
-    p.Wtw = Ws;  // the last inter-pass twiddle carries the output scaling
-    p.Wtw29 = Ws29;
-    p.lazy_store = pass_is_fast(l3, l1, N);
-    p.wr_step = N >> l2;
-    if (log_n >= PASS_TABLE_MIN_LOG_N && pass_is_fast(l2, l3, N) && (rc = get_pass_table(ctx, log_n, 2, scaled_out, Ws29, R2, R3, R1, &p.Tpass29))) return rc;
-    p.tp_row = R3;
-    rc = launch_pass(ctx, l2, p, false, R1 * (R3 / BT), ncols);
-    if (rc) return rc;
-    p.Tpass29 = nullptr;
-    p = reads_scratch(p);
-    p.Wtw = W;
-    p.Wtw29 = W29;
-    p.lazy_store = scaled_out ? 1 : 0;
-    // pass 3: DFT over n3 (contiguous); v = k1 (in stride R2*R3, out stride 1); u = k2 (in stride R3, out stride R1)
-    p.out = out;
-    p.out_col_stride = out_col_stride;
-    p.in_stride_r = 1; p.in_stride_v = R2 * R3; p.in_stride_u = R3;
-    p.in_nat_r = 0; p.in_nat_v = 0; p.in_nat_u = 0;
-    p.out_stride_r = R1 * R2; p.out_stride_v = 1; p.out_stride_u = R1;
-    p.log_v = l1;
-    p.tw_mul = 0;
-    p.wr_step = N >> l3;
-    return launch_pass(ctx, l3, p, true, R2 * (R1 / BT), ncols);
+    return PK_OK;
 }
 
 int ntt_columns(pk_ctx* ctx, const fe* in, size_t in_col_stride, size_t nonzero, fe* out, size_t out_col_stride, fe* scratch,
                 unsigned log_n, unsigned ncols, bool scaled_out) {
     const NttInput src{in, in_col_stride, nullptr, 0, 0};
     return ntt_columns_in(ctx, src, nonzero, out, out_col_stride, scratch, log_n, ncols, scaled_out);
-}
-
-// can a transform of 2^log_n with `nonzero` leading inputs read de-interleaved polynomials in place (NttInput::polys)?  The pass
-// that loads them must be the register-radix kernel.
-bool ntt_reads_polys(unsigned log_n, size_t nonzero) {
-    if (log_n <= 9) return false;
-    const NttPlan q = ntt_plan(log_n, nonzero);
-    return q.pre || q.fast1;
 }
 
 int deinterleave(pk_ctx* ctx, const fe* coeffs, size_t n_coeffs, unsigned fold, fe* S, size_t col_stride) {
@@ -1022,12 +910,18 @@ int pk_ntt(pk_ctx* ctx, const uint64_t* d_in, uint64_t* d_out, unsigned log_n, u
 namespace pk {
 // the two encodes with a choice of output encoding (scaled = hash-ready, see ntt_scaled_available); the C entry points
 // below always return Montgomery images
-int rs_encode_x(pk_ctx* ctx, const uint64_t* const* d_coeffs, unsigned batch, unsigned n_vars, unsigned log_inv_rate, unsigned fold,
-                uint64_t* d_leaves, uint64_t* d_scratch, bool scaled) {
+static int check_encode_args(pk_ctx* ctx, const uint64_t* const* d_coeffs, unsigned batch, unsigned n_vars, unsigned log_inv_rate,
+                             unsigned fold, const uint64_t* d_leaves, const uint64_t* d_scratch) {
     PK_REQUIRE(ctx, d_coeffs && d_leaves && d_scratch, "null pointer");
     PK_REQUIRE(ctx, batch >= 1 && batch <= 16, "batch out of range");
     PK_REQUIRE(ctx, fold <= n_vars && fold <= 8, "fold out of range");
     PK_REQUIRE(ctx, n_vars + log_inv_rate >= fold && n_vars + log_inv_rate - fold <= 27, "domain too large (two-adicity 28)");
+    return PK_OK;
+}
+
+int rs_encode_x(pk_ctx* ctx, const uint64_t* const* d_coeffs, unsigned batch, unsigned n_vars, unsigned log_inv_rate, unsigned fold,
+                uint64_t* d_leaves, uint64_t* d_scratch, bool scaled) {
+    if (int rc = check_encode_args(ctx, d_coeffs, batch, n_vars, log_inv_rate, fold, d_leaves, d_scratch)) return rc;
     unsigned log_rows = n_vars + log_inv_rate - fold;
     size_t rows = (size_t)1 << log_rows, fw = (size_t)1 << fold;
     size_t L = ((size_t)1 << n_vars) / fw;
@@ -1051,10 +945,7 @@ int rs_encode_x(pk_ctx* ctx, const uint64_t* const* d_coeffs, unsigned batch, un
 // d_scratch: (batch*2^fold) * (rows + 2*rows/G) FEs.
 int rs_encode_shard_x(pk_ctx* ctx, const uint64_t* const* d_coeffs, unsigned batch, unsigned n_vars, unsigned log_inv_rate, unsigned fold,
                       unsigned shard, unsigned n_shards, uint64_t* d_leaves_local, uint64_t* d_scratch, bool scaled) {
-    PK_REQUIRE(ctx, d_coeffs && d_leaves_local && d_scratch, "null pointer");
-    PK_REQUIRE(ctx, batch >= 1 && batch <= 16, "batch out of range");
-    PK_REQUIRE(ctx, fold <= n_vars && fold <= 8, "fold out of range");
-    PK_REQUIRE(ctx, n_vars + log_inv_rate >= fold && n_vars + log_inv_rate - fold <= 27, "domain too large (two-adicity 28)");
+    if (int rc = check_encode_args(ctx, d_coeffs, batch, n_vars, log_inv_rate, fold, d_leaves_local, d_scratch)) return rc;
     PK_REQUIRE(ctx, is_pow2(n_shards) && shard < n_shards, "n_shards must be a power of two and shard < n_shards");
     const unsigned log_rows = n_vars + log_inv_rate - fold, log_g = ilog2(n_shards);
     PK_REQUIRE(ctx, log_g <= log_rows, "more shards than leaves");
