@@ -7,6 +7,7 @@
 // outputs are one Hadamard product -- formed on the device with the library's own field kernels.
 // Writes <out_prefix>.transcript (the WhirR1CSProof string) and <out_prefix>.ds (the domain separator);
 // tests/test_gpu_cpp_host.py hands both to the independent verifier.
+// Last, 8 proofs go through a 4-lane ProofEngine from this one thread; each must equal the single prove of the same seed.
 #include <cstdio>
 #include <cstdlib>
 #include <fstream>
@@ -169,10 +170,27 @@ int main(int argc, char** argv) {
         seen += pow.check(nonce) ? 1 : 0;
         if (seen != 5) throw Error(-101, "error-path checks: " + std::to_string(seen) + " of 5");
 
+        // many proofs in flight from this one thread: 8 jobs through a 4-lane engine, each against the lone prover's proof of the same seed
+        size_t engine_proofs = 0;
+        unsigned engine_lanes = 0;
+        {
+            ProofEngine engine(r1cs, m, m_0, WhirConfig::for_size(m, 8.0), WhirConfig::for_hiding_spartan(m_0, 8.0), 4);
+            engine_lanes = engine.lanes();
+            std::vector<const DeviceVec*> jobs(8, &d_z);
+            std::vector<ProofEngine::TestSeed> seeds;
+            for (uint64_t j = 0; j < jobs.size(); j++) seeds.push_back(WhirR1CSScheme::test_seed(42 + j));
+            const std::vector<WhirR1CSProof> many = engine.prove_many(jobs, seeds);
+            for (size_t j = 0; j < many.size(); j++)
+                if (many[j].transcript != scheme.prove(d_z, &seeds[j]).transcript) throw Error(-107, "engine job " + std::to_string(j) + " differs from the single prove of its seed");
+            if (many[0].transcript != proof.transcript) throw Error(-108, "engine job 0 differs from the proof written out");
+            engine_proofs = many.size();
+        }
+
         std::ofstream(prefix + ".transcript", std::ios::binary).write((const char*)proof.transcript.data(), (std::streamsize)proof.transcript.size());
         const std::string ds = scheme.domain_separator();
         std::ofstream(prefix + ".ds", std::ios::binary).write(ds.data(), (std::streamsize)ds.size());
         std::printf("ok transcript_bytes=%zu constraints=%zu witnesses=%zu pow_nonce=%llu\n", proof.transcript.size(), nc, nw, (unsigned long long)nonce);
+        std::printf("engine lanes=%u proofs=%zu identical_to_single_prove=yes\n", engine_lanes, engine_proofs);
         return 0;
     } catch (const Error& e) {
         std::fprintf(stderr, "provekit::Error %d: %s\n", e.code, e.what());

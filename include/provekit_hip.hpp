@@ -19,6 +19,8 @@
 //   provekit::compress_many       skyscraper::CompressManyFn (skyscraper/core/src/lib.rs:26)
 //   provekit::WitnessBuilders     R1CSSolver::solve_witness_vec over a postcard-encoded &[WitnessBuilder]
 //                                 (prover/src/r1cs.rs:29-40, prover/src/witness/witness_builder.rs:27-193)
+//   provekit::ProofEngine         what rayon is to the reference's prover: many WhirR1CSProver::prove calls in flight from one caller
+//                                 thread (include/provekit_engine.h; a program that uses it links libprovekit_engine.so as well)
 #pragma once
 #include <array>
 #include <cstdint>
@@ -29,6 +31,7 @@
 #include <utility>
 #include <vector>
 
+#include "provekit_engine.h"
 #include "provekit_hip.h"
 
 namespace provekit {
@@ -414,6 +417,64 @@ inline WhirR1CSProof noir_prove(const WhirR1CSScheme& scheme, const WitnessBuild
     p.transcript.resize(len);
     return p;
 }
+
+// Many proofs of one scheme in flight from ONE caller thread (include/provekit_engine.h): `lanes` provers, each with a context, a
+// scheme and an arena of its own, behind a job queue.  The reference gets this from rayon inside WhirR1CSProver::prove; here the
+// engine owns the threads and the caller keeps one.  lanes = 0 lets the library pick (at most 16, by free device memory).  The R1CS
+// is uploaded once by the caller (any context of the device) and must outlive the engine.
+class ProofEngine {
+   public:
+    using TestSeed = WhirR1CSScheme::TestSeed;
+    ProofEngine(const R1CS& r1cs, unsigned m, unsigned m_0, const WhirConfig& whir_witness, const WhirConfig& whir_for_hiding_spartan, unsigned lanes = 0,
+                int device = 0, unsigned flags = 0) {
+        pk_whir_config cw = whir_witness.to_c(), cb = whir_for_hiding_spartan.to_c();
+        if (int rc = pke_engine_create(device, r1cs.get(), r1cs.num_constraints(), r1cs.num_witnesses(), m, m_0, &cw, &cb, lanes, flags, &e_))
+            throw Error(rc, pke_create_error());
+    }
+    ~ProofEngine() {
+        if (e_) pke_engine_destroy(e_);
+    }
+    ProofEngine(const ProofEngine&) = delete;
+    ProofEngine& operator=(const ProofEngine&) = delete;
+    pke_engine* get() const { return e_; }
+    unsigned lanes() const { return (unsigned)pke_engine_lanes(e_); }
+    void set_io_pattern(const std::string& bytes) { check(pke_engine_set_io_pattern(e_, (const uint8_t*)bytes.data(), bytes.size())); }
+    void set_hash_version(int v) { check(pke_engine_set_hash_version(e_, v)); }
+    // One WhirR1CSProver::prove per witness (device vectors; entries may repeat), blocking; proofs come back in job order.  seeds:
+    // empty in production (fresh OS randomness per proof), or one TestSeed per job -- the test hook of WhirR1CSScheme::prove.
+    // Throws the first failed job's error ("job i: ..."); the other jobs still ran.
+    std::vector<WhirR1CSProof> prove_many(const std::vector<const DeviceVec*>& witnesses, const std::vector<TestSeed>& seeds = {}) const {
+        const size_t n = witnesses.size();
+        if (!seeds.empty() && seeds.size() != n) throw Error(PK_ERR_BAD_ARG, "ProofEngine::prove_many: one seed per witness, or none");
+        std::vector<WhirR1CSProof> proofs(n);
+        std::vector<const uint64_t*> d_w(n);
+        std::vector<const uint8_t*> sd(n, nullptr);
+        std::vector<uint8_t*> out(n);
+        std::vector<size_t> n_w(n), cap(n, (size_t)4 << 20), len(n);  // as WhirR1CSScheme::prove sizes its buffer
+        std::vector<int> status(n);
+        for (size_t i = 0; i < n; i++) {
+            proofs[i].transcript.resize(cap[i]);
+            d_w[i] = witnesses[i]->data();
+            n_w[i] = witnesses[i]->size();
+            if (!seeds.empty()) sd[i] = seeds[i].data();
+            out[i] = proofs[i].transcript.data();
+        }
+        pke_job first = 0;
+        if (int rc = pke_prove_many(e_, n, d_w.data(), n_w.data(), sd.data(), out.data(), cap.data(), len.data(), status.data(), &first)) {
+            size_t i = 0;
+            while (i < n && !status[i]) i++;
+            throw Error(rc, "job " + std::to_string(i) + ": " + pke_engine_last_error(e_, first + i));
+        }
+        for (size_t i = 0; i < n; i++) proofs[i].transcript.resize(len[i]);
+        return proofs;
+    }
+
+   private:
+    void check(int rc) const {
+        if (rc) throw Error(rc, pke_engine_last_error(e_, PKE_NO_JOB));
+    }
+    pke_engine* e_ = nullptr;
+};
 
 // skyscraper::CompressManyFn = fn(&[u8] /*64 n*/, &mut [u8] /*32 n*/); the reference panics on a length mismatch
 // (generic.rs:18-25), this throws

@@ -6,3 +6,13 @@ reference's plug-in interfaces for that path.  See DESIGN.md.
 """
 from ._lib import LIB_PATH, PK_COL_MAJOR, PK_LEAF_MAJOR, ProveKitHipError  # noqa: F401
 from .runtime import Context, DeviceBuffer, default_context  # noqa: F401
+
+
+def __getattr__(name):
+    # ProofEngine lives in a library of its own (libprovekit_engine.so); it is loaded when first asked for, so a caller of the product
+    # library alone never needs it -- and one who asks for it without the built library gets engine.py's ImportError
+    if name == "ProofEngine":
+        from .engine import ProofEngine
+
+        return ProofEngine
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -1423,8 +1423,10 @@ int pk_scheme_create(pk_ctx* ctx, const pk_r1cs* r1cs, size_t num_constraints, s
     s->domain_separator = whir_r1cs_io_pattern(s->m_0, s->whir_witness, s->whir_hiding);
     s->arena_bytes = scheme_arena_bytes(m, m_0, num_witnesses, s->whir_witness);
     if (hipMalloc((void**)&s->arena, s->arena_bytes) != hipSuccess) {
+        const size_t mib = s->arena_bytes >> 20;
         delete s;
-        return set_err(ctx, PK_ERR_OOM, "hipMalloc of the %zu MiB prover arena failed", s->arena_bytes >> 20);
+        (void)hipGetLastError();  // the refusal is reported here: it must not stay behind as this thread's "last error" and fail its next launch check
+        return set_err(ctx, PK_ERR_OOM, "hipMalloc of the %zu MiB prover arena failed", mib);
     }
     *out = s;
     return PK_OK;
