@@ -22,7 +22,7 @@
 #include <condition_variable>
 #include <mutex>
 
-#include "ctx.hpp"
+#include "internal.hpp"
 #include "fe29.hpp"
 
 using namespace pk;

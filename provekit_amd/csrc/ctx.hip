@@ -1,6 +1,6 @@
 // ctx.hip -- context, memory and timing entry points of the C ABI, plus the
 // elementwise field kernels (rows A1/A2).
-#include "ctx.hpp"
+#include "internal.hpp"
 #include "fe29.hpp"
 
 #include <sys/prctl.h>

@@ -1,4 +1,5 @@
-// ctx.hpp -- library context shared by all translation units of libprovekit_hip.
+// ctx.hpp -- library context shared by all translation units of libprovekit_hip: the struct, the macros and the inline helpers.
+// What one .hip defines and another calls is declared in internal.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -170,41 +171,5 @@ struct ProfScope {
         if (e1) (void)hipEventRecord(e1, c->stream);
     }
 };
-
-int ensure_scratch(pk_ctx* ctx, size_t bytes);
-int ensure_pinned(pk_ctx* ctx);                               // the 4 KiB result page
-// Every wait of the library for a stream goes through here (pk_device_set_host_wait): the runtime's hipStreamSynchronize -- spinning or
-// blocking, whichever the device's scheduling flag says -- or, in PK_WAIT_POLL, the library's own loop: hipStreamQuery with short sleeps.
-// test hooks, settable only through pk_selftest_set_hook (tools/probes/pk_selftest.h); 0 = off: a gated kernel's spin bound, microseconds the
-// host sleeps before it publishes a gate's challenge, take the RCCL branch for a repeated device
-enum { PK_HOOK_GATE_SPINS = 0, PK_HOOK_GATE_STALL_US = 1, PK_HOOK_RCCL_SAME_DEVICE = 2, PK_HOOK_COUNT = 3 };
-long test_hook(int which);
-hipError_t wait_stream(int device, hipStream_t stream);
-hipError_t wait_ctx(pk_ctx* ctx);  // wait_stream on the context's stream; with a deadline while an RCCL collective is pending on it (comm.hip comm_wait)
-int wait_ctx_rc(pk_ctx* ctx);      // the same as a status: PK_OK, PK_ERR_RCCL (the collective failed or timed out; pk_last_error says which) or PK_ERR_HIP
-bool comm_collective_pending(const pk_ctx* ctx);
-bool comm_rccl(const pk_ctx* ctx);
-hipError_t comm_wait(pk_ctx* ctx);
-int sync_stream(pk_ctx* ctx);                                 // wait_stream + rewind the mailbox
-int mail_alloc(pk_ctx* ctx, size_t bytes, void** out);        // 64-B aligned; valid until the next sync_stream
-int read_root(pk_ctx* ctx, const uint64_t* d_nodes, size_t n_leaves, uint64_t root[4]);  // hash.hip: after pk_merkle_*
-int ensure_ws(pk_ctx* ctx, size_t bytes);
-// comm.hip: rank / size of the context's communicator (0 / 1 without one) and its two collectives, enqueued on ctx->stream
-int comm_rank(const pk_ctx* ctx);
-int comm_world(const pk_ctx* ctx);
-int comm_all_gather(pk_ctx* ctx, const void* d_send, void* d_recv, size_t bytes_per_rank);
-int comm_all_reduce_sum_u64(pk_ctx* ctx, uint64_t* d_buf, size_t count);
-int comm_collect_fe(pk_ctx* ctx, int K, uint64_t* host_out);  // comm.hip: the cross-rank half of collect_reduction
-int red_across_begin(pk_ctx* ctx);                             // allocate d_xred if needed and set red_across
-void comm_turn_begin(pk_ctx* ctx);  // measurement aid of the in-process transport (comm.hip LocalGroup::turnstile)
-void comm_turn_end(pk_ctx* ctx);
-unsigned long long comm_collectives_issued(const pk_ctx* ctx);  // collectives this context's communicator has enqueued so far
-void comm_abort(pk_ctx* ctx);  // this rank will not reach a collective its peers wait in: LOCAL wakes them; RCCL aborts its OWN communicator (the peers time out, comm_wait)
-void comm_release(pk_ctx* ctx);
-int eval_univariate_multi(pk_ctx* ctx, const uint64_t* const* d_polys, unsigned np, size_t n, const uint64_t z[4], uint64_t* out);  // mle.hip
-int dot_rows(pk_ctx* ctx, const uint64_t* d_w, size_t row_stride, unsigned nrows, const uint64_t* d_f, const uint64_t* d_g, size_t n, uint64_t* out);
-int pow_solve_x(pk_ctx* ctx, const uint8_t challenge[32], double bits, uint64_t* nonce, bool striped);  // pow.hip
-void ntt_retain_ctx(pk_ctx* ctx);   // ntt.hip: one more context on this device shares its twiddle tables
-void ntt_release_ctx(pk_ctx* ctx);  // ntt.hip: the context lets go of the device's twiddle tables (freed with the last context)
 
 }  // namespace pk

@@ -11,7 +11,7 @@
 //   merkle_levels : lane i owns inner node i of the widest of up to 5 fused levels;
 //                   children 2i,2i+1 are adjacent in the heap, so a wave reads 4 KiB
 //                   contiguous; the workgroup then walks up its own subtree.
-#include "ctx.hpp"
+#include "internal.hpp"
 #include "skyscraper29s.hpp"
 
 using namespace pk;
@@ -135,6 +135,20 @@ int read_root(pk_ctx* ctx, const uint64_t* d_nodes, size_t n_leaves, uint64_t ro
     memcpy(root, (char*)ctx->h_pinned + PK_PIN_ROOT, 32);
     return PK_OK;
 }
+// the levels above heap slots [top_leaves, 2 top_leaves) (top_leaves <= 1024, a power of two), the root also to the pinned page:
+// the top of a subtree-sharded tree, whose G subtree roots arrive through an all-gather (tree.hip)
+int merkle_top_x(pk_ctx* ctx, uint64_t* d_nodes, size_t top_leaves) {
+    int rc = ensure_pinned(ctx);
+    if (rc) return rc;
+    fe* host_root = (fe*)((char*)ctx->h_pinned + PK_PIN_ROOT);
+    ProfScope prof(ctx, "merkle_inner");
+    if (ctx->hash_version == 2)
+        merkle_top_kernel<2><<<1, 512, 0, ctx->stream>>>((fe*)d_nodes, top_leaves, host_root);
+    else
+        merkle_top_kernel<1><<<1, 512, 0, ctx->stream>>>((fe*)d_nodes, top_leaves, host_root);
+    PK_LAUNCH_CHECK(ctx);
+    return PK_OK;
+}
 }  // namespace pk
 
 extern "C" {
@@ -219,27 +233,6 @@ int pk_merkle_inner(pk_ctx* ctx, uint64_t* d_nodes, size_t n_leaves) {
     PK_LAUNCH_CHECK(ctx);
     return PK_OK;
 }
-
-}  // extern "C"
-
-namespace pk {
-// the levels above heap slots [top_leaves, 2 top_leaves) (top_leaves <= 1024, a power of two), the root also to the pinned page:
-// the top of a subtree-sharded tree, whose G subtree roots arrive through an all-gather (tree.hip)
-int merkle_top_x(pk_ctx* ctx, uint64_t* d_nodes, size_t top_leaves) {
-    int rc = ensure_pinned(ctx);
-    if (rc) return rc;
-    fe* host_root = (fe*)((char*)ctx->h_pinned + PK_PIN_ROOT);
-    ProfScope prof(ctx, "merkle_inner");
-    if (ctx->hash_version == 2)
-        merkle_top_kernel<2><<<1, 512, 0, ctx->stream>>>((fe*)d_nodes, top_leaves, host_root);
-    else
-        merkle_top_kernel<1><<<1, 512, 0, ctx->stream>>>((fe*)d_nodes, top_leaves, host_root);
-    PK_LAUNCH_CHECK(ctx);
-    return PK_OK;
-}
-}  // namespace pk
-
-extern "C" {
 
 int pk_merkle_commit(pk_ctx* ctx, const uint64_t* d_leaves, size_t n_leaves, size_t width, int layout, uint64_t* d_nodes) {
     PK_ENTER(ctx);

@@ -1,0 +1,108 @@
+// internal.hpp -- the library's internal interface: every `pk::` function that one translation unit of libprovekit_hip defines and
+// another calls, grouped by the file that defines it.  Every .hip includes this header -- the defining file too, so a definition that
+// drifts from what its callers compile against (parameters, return type, default) is a compile error, not a surprise at load time.
+// The opaque handles (pk_tree, pk_r1cs, pk_witness_program) and pk_commit_layout are declared by the public header.
+#pragma once
+#include "ctx.hpp"
+
+namespace pk {
+
+// ---- ctx.hip ------------------------------------------------------------------------------------------------------------------
+int ensure_scratch(pk_ctx* ctx, size_t bytes);
+int ensure_pinned(pk_ctx* ctx);  // the 4 KiB result page
+int ensure_ws(pk_ctx* ctx, size_t bytes);
+// test hooks, settable only through pk_selftest_set_hook (tools/probes/pk_selftest.h); 0 = off: a gated kernel's spin bound, microseconds the
+// host sleeps before it publishes a gate's challenge, take the RCCL branch for a repeated device
+enum { PK_HOOK_GATE_SPINS = 0, PK_HOOK_GATE_STALL_US = 1, PK_HOOK_RCCL_SAME_DEVICE = 2, PK_HOOK_COUNT = 3 };
+long test_hook(int which);
+// Every wait of the library for a stream goes through here (pk_device_set_host_wait): the runtime's hipStreamSynchronize -- spinning or
+// blocking, whichever the device's scheduling flag says -- or, in PK_WAIT_POLL, the library's own loop: hipStreamQuery with short sleeps.
+hipError_t wait_stream(int device, hipStream_t stream);
+hipError_t wait_ctx(pk_ctx* ctx);  // wait_stream on the context's stream; with a deadline while an RCCL collective is pending on it (comm.hip comm_wait)
+int wait_ctx_rc(pk_ctx* ctx);      // the same as a status: PK_OK, PK_ERR_RCCL (the collective failed or timed out; pk_last_error says which) or PK_ERR_HIP
+int sync_stream(pk_ctx* ctx);                           // wait_stream + rewind the mailbox
+int mail_alloc(pk_ctx* ctx, size_t bytes, void** out);  // 64-B aligned; valid until the next sync_stream
+
+// ---- comm.hip: rank / size of the context's communicator (0 / 1 without one) and its collectives, enqueued on ctx->stream ----------
+int comm_rank(const pk_ctx* ctx);
+int comm_world(const pk_ctx* ctx);
+int comm_all_gather(pk_ctx* ctx, const void* d_send, void* d_recv, size_t bytes_per_rank);
+int comm_all_reduce_sum_u64(pk_ctx* ctx, uint64_t* d_buf, size_t count);
+int comm_collect_fe(pk_ctx* ctx, int K, uint64_t* host_out);  // the cross-rank half of collect_reduction (reduce.hpp)
+int red_across_begin(pk_ctx* ctx);                            // allocate d_xred if needed and set red_across
+bool comm_collective_pending(const pk_ctx* ctx);
+bool comm_rccl(const pk_ctx* ctx);
+hipError_t comm_wait(pk_ctx* ctx);
+void comm_turn_begin(pk_ctx* ctx);  // measurement aid of the in-process transport (LocalGroup::turnstile)
+void comm_turn_end(pk_ctx* ctx);
+unsigned long long comm_collectives_issued(const pk_ctx* ctx);  // collectives this context's communicator has enqueued so far
+void comm_abort(pk_ctx* ctx);  // this rank will not reach a collective its peers wait in: LOCAL wakes them; RCCL aborts its OWN communicator (the peers time out, comm_wait)
+void comm_release(pk_ctx* ctx);
+
+// ---- hash.hip -----------------------------------------------------------------------------------------------------------------
+// leaf hash of a column-major codeword in the commit's internal (hash-ready) encoding, or in Montgomery form
+int leaf_hash_x(pk_ctx* ctx, const uint64_t* d_leaves, size_t n_leaves, size_t width, uint64_t* d_digests, bool scaled_in);
+int merkle_top_x(pk_ctx* ctx, uint64_t* d_nodes, size_t top_leaves);  // the levels above heap slots [top_leaves, 2 top_leaves)
+int read_root(pk_ctx* ctx, const uint64_t* d_nodes, size_t n_leaves, uint64_t root[4]);  // after pk_merkle_*
+
+// ---- ntt.hip ------------------------------------------------------------------------------------------------------------------
+void ntt_retain_ctx(pk_ctx* ctx);   // one more context on this device shares its twiddle tables
+void ntt_release_ctx(pk_ctx* ctx);  // the context lets go of the device's twiddle tables (freed with the last context)
+bool ntt_scaled_available(unsigned log_n);  // can a transform of this size deliver the hash-ready encoding?
+// the two encodes with a choice of output encoding (scaled = hash-ready)
+int rs_encode_x(pk_ctx* ctx, const uint64_t* const* d_coeffs, unsigned batch, unsigned n_vars, unsigned log_inv_rate, unsigned fold,
+                uint64_t* d_leaves, uint64_t* d_scratch, bool scaled);
+int rs_encode_shard_x(pk_ctx* ctx, const uint64_t* const* d_coeffs, unsigned batch, unsigned n_vars, unsigned log_inv_rate, unsigned fold,
+                      unsigned shard, unsigned n_shards, uint64_t* d_leaves_local, uint64_t* d_scratch, bool scaled);
+
+// ---- pow.hip ------------------------------------------------------------------------------------------------------------------
+// striped: every rank of the context's device set is inside this call with the same challenge and searches its stripe of each window
+int pow_solve_x(pk_ctx* ctx, const uint8_t challenge[32], double bits, uint64_t* nonce, bool striped);
+
+// ---- tree.hip -----------------------------------------------------------------------------------------------------------------
+unsigned shard_factor(const pk_ctx* ctx, size_t rows);  // 1 = a commit of `rows` leaves is computed whole on every rank, G = sharded over the G ranks
+size_t commit_scratch_fes(const pk_ctx* ctx, size_t rows, size_t width);  // device scratch (in FEs) commit_into needs
+// RS-encode + Merkle commit into caller-owned device buffers (no allocation)
+int commit_into(pk_ctx* ctx, const uint64_t* const* d_coeffs, unsigned batch, unsigned n_vars, unsigned log_inv_rate, unsigned fold,
+                uint64_t* d_leaves, uint64_t* d_nodes, uint64_t* d_scratch, pk_commit_layout* layout_out);
+// open k leaves of a tree described by raw buffers (same outputs as pk_tree_open)
+int open_raw(pk_ctx* ctx, const uint64_t* d_leaves, const uint64_t* d_nodes, size_t n_leaves, size_t width, const pk_commit_layout& lay,
+             const uint64_t* indices, size_t k, int canonical_leaves, uint64_t* leaves_out, uint64_t* sibling_digests, uint64_t* auth_paths);
+
+// ---- mle.hip ------------------------------------------------------------------------------------------------------------------
+// np (1 or 2) polynomials of n coefficients each at the same z, one launch: out[4 * q] = poly_q(z)
+int eval_univariate_multi(pk_ctx* ctx, const uint64_t* const* d_polys, unsigned np, size_t n, const uint64_t z[4], uint64_t* out);
+// nrows (= 3) weight rows against f and (d_g != null: nv = 2) g in one pass: out[4 * (nv * k + v)]
+// defer: launch only -- the caller synchronises `ctx`'s stream later and takes the 3 * nv results from its pinned page (latency mode: the
+// statement's sums run on a side stream underneath the blinding WHIR proof)
+int dot_rows(pk_ctx* ctx, const uint64_t* d_w, size_t row_stride, unsigned nrows, const uint64_t* d_f, const uint64_t* d_g, size_t n, uint64_t* out,
+             bool defer = false);
+int lincomb2(pk_ctx* ctx, uint64_t* d_out, const uint64_t* d_a, const uint64_t* beta, const uint64_t* d_b, size_t n);  // out = a + beta * b
+// two arrays of the same length folded by the same challenge in one launch (the sumcheck's p and w)
+// r = NULL with gate_seq != 0: the challenge arrives through the gate (latency mode)
+int fold_pairs2(pk_ctx* ctx, const uint64_t* d_v0, uint64_t* d_out0, const uint64_t* d_v1, uint64_t* d_out1, size_t len, const uint64_t* r,
+                unsigned gate_seq = 0);
+// launch only: round results go to the pinned page under sequence number *red_seq_out.  gate_seq != 0 (latency mode, folding rounds
+// only): the folding challenge is not known yet -- the kernel waits for sumcheck_gate_publish(ctx, gate_seq, challenge)
+int sumcheck_cubic_launch(pk_ctx* ctx, uint64_t* d_a, uint64_t* d_b, uint64_t* d_c, uint64_t* d_eq, size_t len, const uint64_t* fold_or_null,
+                          unsigned gate_seq, unsigned* red_seq_out);
+int sumcheck_quadratic_launch(pk_ctx* ctx, const uint64_t* d_f, const uint64_t* d_w, size_t len, const uint64_t* fold_or_null, unsigned gate_seq,
+                              uint64_t* d_f_out, uint64_t* d_w_out, unsigned* red_seq_out);
+// the host's side of a gated launch and the wait for a launch's three results without draining the stream (latency mode)
+int sumcheck_collect_spin(pk_ctx* ctx, unsigned red_seq, uint64_t out[12]);
+unsigned sumcheck_gate_next(pk_ctx* ctx);
+void sumcheck_gate_publish(pk_ctx* ctx, unsigned gate_seq, const uint64_t challenge[4]);
+int sumcheck_gate_check(pk_ctx* ctx);   // PK_OK, or PK_ERR_HIP with the message set: a gated kernel of this context gave up on its challenge since the last call
+void sumcheck_gate_clear(pk_ctx* ctx);  // forget a give-up word without touching the error message
+
+// ---- r1cs.hip -----------------------------------------------------------------------------------------------------------------
+// rank `offset` of `stride` ranks: a, b, c for the rows i = j * stride + offset, j < 2^m0 / stride (sharded sumcheck)
+int witness_bounds_strided(pk_ctx* ctx, const pk_r1cs* r, const uint64_t* d_z, unsigned m0, unsigned stride, unsigned offset, uint64_t* d_a,
+                           uint64_t* d_b, uint64_t* d_c);
+// columns [first, last) of the three external rows, written at their absolute positions of d_out (3 x num_witnesses)
+int external_row_range(pk_ctx* ctx, const pk_r1cs* r, const uint64_t* d_eq_alpha, size_t first, size_t last, uint64_t* d_out);
+
+// ---- witness.hip --------------------------------------------------------------------------------------------------------------
+void witness_program_shape(const pk_witness_program* p, size_t* n_witnesses, size_t* n_challenges, size_t* n_acir);
+
+}  // namespace pk

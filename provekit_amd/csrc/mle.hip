@@ -7,7 +7,7 @@
 // transcript needs per round (grid reduction in reduce.hpp).
 // memory- / latency-bound kernels: their wavefronts issue ahead of the ALU-bound hash / NTT / grinder kernels they share SIMDs with
 #define PK_BASE_PRIO 2
-#include "ctx.hpp"
+#include "internal.hpp"
 #include "fe29.hpp"
 #include "reduce.hpp"
 
@@ -230,11 +230,8 @@ __global__ __launch_bounds__(256) void eq_accumulate_kernel(fe* __restrict__ w, 
 // provekit/prover/src/whir_r1cs.rs:284-291.
 template <bool FOLD>
 __global__ __launch_bounds__(RED_THREADS) void sumcheck_cubic_kernel(fe* __restrict__ a, fe* __restrict__ b, fe* __restrict__ c,
-                                                                     fe* __restrict__ eq, size_t len, fe_arg fold_arg, gate_args gate,
-                                                                     fe* __restrict__ partials, unsigned* __restrict__ ticket,
-                                                                     fe* __restrict__ result, unsigned seq) {
+                                                                     fe* __restrict__ eq, size_t len, fe_arg fold_arg, gate_args gate, red_out red) {
     PK_LATENCY_PRIO();
-    __shared__ uint4 smem[3 * 16];
     const fe alpha = (FOLD && gate.host) ? gate_wait(gate) : from_arg(fold_arg);
     const size_t npairs = FOLD ? len / 4 : len / 2;
     const size_t off = npairs;          // partner of i is i + off (quarter 1 after folding, or the upper half)
@@ -266,7 +263,7 @@ __global__ __launch_bounds__(RED_THREADS) void sumcheck_cubic_kernel(fe* __restr
         // f_inf = (eq1-eq0)(a1-a0)(b1-b0)
         acc[2] = fe_add(acc[2], fe_mulx(fe_mulx(fe_sub(e1, e0), fe_sub(a1, a0)), fe_sub(b1, b0)));
     }
-    grid_finish_fe<3>(acc, smem, partials, ticket, result, seq);
+    grid_finish_fe<3>(acc, red);
 }
 
 // ---------------------------------------------------------------- W3: quadratic sumcheck round
@@ -276,10 +273,8 @@ __global__ __launch_bounds__(RED_THREADS) void sumcheck_cubic_kernel(fe* __restr
 template <bool FOLD>
 __global__ __launch_bounds__(RED_THREADS) void sumcheck_quadratic_kernel(const fe* __restrict__ f, const fe* __restrict__ w,
                                                                          size_t out_len, fe_arg fold_arg, gate_args gate, fe* __restrict__ f_out,
-                                                                         fe* __restrict__ w_out, fe* __restrict__ partials,
-                                                                         unsigned* __restrict__ ticket, fe* __restrict__ result, unsigned seq) {
+                                                                         fe* __restrict__ w_out, red_out red) {
     PK_LATENCY_PRIO();
-    __shared__ uint4 smem[3 * 16];
     const fe r = (FOLD && gate.host) ? gate_wait(gate) : from_arg(fold_arg);
     fe acc[3] = {fe_zero(), fe_zero(), fe_zero()};
     const size_t npairs = out_len / 2;
@@ -307,7 +302,7 @@ __global__ __launch_bounds__(RED_THREADS) void sumcheck_quadratic_kernel(const f
         acc[1] = fe_add(acc[1], fe_mulx(f1, w1));
         acc[2] = fe_add(acc[2], fe_mulx(fe_sub(fe_dbl(f1), f0), fe_sub(fe_dbl(w1), w0)));
     }
-    grid_finish_fe<3>(acc, smem, partials, ticket, result, seq);
+    grid_finish_fe<3>(acc, red);
 }
 // ---- small rounds: the work of ONE pair spread over several lanes ------------------------------------------------------
 // Late sumcheck rounds have a handful of pairs; with a lane per pair the round is a chain of 16 (cubic, folding) or 7
@@ -318,11 +313,8 @@ __global__ __launch_bounds__(RED_THREADS) void sumcheck_quadratic_kernel(const f
 constexpr size_t SMALL_ROUND_PAIRS = 16384;
 
 __global__ __launch_bounds__(RED_THREADS) void sumcheck_cubic_small_kernel(fe* __restrict__ a, fe* __restrict__ b, fe* __restrict__ c,
-                                                                           fe* __restrict__ eq, size_t len, fe_arg fold_arg, gate_args gate,
-                                                                           fe* __restrict__ partials, unsigned* __restrict__ ticket,
-                                                                           fe* __restrict__ result, unsigned seq) {
+                                                                           fe* __restrict__ eq, size_t len, fe_arg fold_arg, gate_args gate, red_out red) {
     PK_LATENCY_PRIO();
-    __shared__ uint4 smem[3 * 16];
     __shared__ uint4 xs[2 * RED_THREADS];  // folded value of lane t at [t] (lo) and [RED_THREADS + t] (hi)
     const fe alpha = gate.host ? gate_wait(gate) : from_arg(fold_arg);
     const size_t npairs = len / 4, off = npairs, foff = len / 2;
@@ -367,16 +359,14 @@ __global__ __launch_bounds__(RED_THREADS) void sumcheck_cubic_small_kernel(fe* _
 #pragma unroll
             for (int w = 0; w < 8; w++) acc[r].v[w] = role == (unsigned)r ? t.v[w] : 0u;
     }
-    grid_finish_fe<3>(acc, smem, partials, ticket, result, seq);
+    grid_finish_fe<3>(acc, red);
 }
 
 template <bool FOLD>
 __global__ __launch_bounds__(RED_THREADS) void sumcheck_quadratic_small_kernel(const fe* __restrict__ f, const fe* __restrict__ w, size_t out_len,
                                                                                fe_arg fold_arg, gate_args gate, fe* __restrict__ f_out, fe* __restrict__ w_out,
-                                                                               fe* __restrict__ partials, unsigned* __restrict__ ticket,
-                                                                               fe* __restrict__ result, unsigned seq) {
+                                                                               red_out red) {
     PK_LATENCY_PRIO();
-    __shared__ uint4 smem[3 * 16];
     __shared__ uint4 xs[2 * RED_THREADS];
     const fe r = (FOLD && gate.host) ? gate_wait(gate) : from_arg(fold_arg);
     const size_t npairs = out_len / 2;
@@ -415,7 +405,7 @@ __global__ __launch_bounds__(RED_THREADS) void sumcheck_quadratic_small_kernel(c
 #pragma unroll
             for (int v = 0; v < 8; v++) acc[q].v[v] = role == (unsigned)q ? t.v[v] : 0u;
     }
-    grid_finish_fe<3>(acc, smem, partials, ticket, result, seq);
+    grid_finish_fe<3>(acc, red);
 }
 
 // the single-element tail of the fold (out_len == 1): v'[0] = v[0] + r (v[1]-v[0]); no pair to sum.  blockIdx.y selects
@@ -437,10 +427,8 @@ __global__ void fold_pairs_kernel(const fe* __restrict__ v0, fe* __restrict__ ou
 // <w,f> and optionally <w,g> in one pass over w (the statement needs both sums, whir_r1cs.rs:401-405)
 template <int NV>
 __global__ __launch_bounds__(RED_THREADS) void dot_kernel(const fe* __restrict__ w, const fe* __restrict__ f, const fe* __restrict__ g,
-                                                          size_t n, fe* __restrict__ partials, unsigned* __restrict__ ticket,
-                                                          fe* __restrict__ result, unsigned seq) {
+                                                          size_t n, red_out red) {
     PK_LATENCY_PRIO();
-    __shared__ uint4 smem[NV * 16];
     fe acc[NV];
 #pragma unroll
     for (int k = 0; k < NV; k++) acc[k] = fe_zero();
@@ -450,17 +438,15 @@ __global__ __launch_bounds__(RED_THREADS) void dot_kernel(const fe* __restrict__
         acc[0] = fe_add(acc[0], fe_mulx(wi, fe_load(f + i)));
         if (NV == 2) acc[NV - 1] = fe_add(acc[NV - 1], fe_mulx(wi, fe_load(g + i)));
     }
-    grid_finish_fe<NV>(acc, smem, partials, ticket, result, seq);
+    grid_finish_fe<NV>(acc, red);
 }
 
 // NR weight rows (row k at w + k * row_stride) against f (and g): <w_k, f>, <w_k, g> for every k in ONE pass over f and g -- the
 // three statement weights of whir_r1cs.rs:382-412 share their polynomials, so this is one launch and one round trip instead of three
 template <int NR, int NV>
 __global__ __launch_bounds__(RED_THREADS) void dot_rows_kernel(const fe* __restrict__ w, size_t row_stride, const fe* __restrict__ f,
-                                                               const fe* __restrict__ g, size_t n, fe* __restrict__ partials,
-                                                               unsigned* __restrict__ ticket, fe* __restrict__ result, unsigned seq) {
+                                                               const fe* __restrict__ g, size_t n, red_out red) {
     PK_LATENCY_PRIO();
-    __shared__ uint4 smem[NR * NV * 16];
     fe acc[NR * NV];
 #pragma unroll
     for (int k = 0; k < NR * NV; k++) acc[k] = fe_zero();
@@ -476,7 +462,7 @@ __global__ __launch_bounds__(RED_THREADS) void dot_rows_kernel(const fe* __restr
             if (NV == 2) acc[NV * k + 1] = fe_add(acc[NV * k + 1], fe_mulx(wi, gi));
         }
     }
-    grid_finish_fe<NR * NV>(acc, smem, partials, ticket, result, seq);
+    grid_finish_fe<NR * NV>(acc, red);
 }
 
 // ---------------------------------------------------------------- E1: univariate evaluation
@@ -500,10 +486,8 @@ __global__ __launch_bounds__(RED_THREADS) void zpow_table_kernel(pow2_args zp, f
 // NP polynomials of the same length at the same point in one launch (a batch commitment's OOD answers, mtUtilities.go:51-76)
 template <int NP>
 __global__ __launch_bounds__(RED_THREADS) void horner_kernel(const fe* __restrict__ c, const fe* __restrict__ c_second, size_t n, size_t cnt, pow2_args zp,
-                                                             const fe* __restrict__ ztab, fe* __restrict__ partials, unsigned* __restrict__ ticket,
-                                                             fe* __restrict__ result, unsigned seq) {
+                                                             const fe* __restrict__ ztab, red_out red) {
     PK_LATENCY_PRIO();
-    __shared__ uint4 smem[NP * 16];
     __shared__ unsigned s_zb[8];
     static_assert(RED_THREADS == 256, "the lane table has 256 entries");
     const size_t base = (size_t)blockIdx.x * cnt * RED_THREADS;
@@ -546,7 +530,7 @@ __global__ __launch_bounds__(RED_THREADS) void horner_kernel(const fe* __restric
 #pragma unroll
         for (int q = 0; q < NP; q++) acc[q] = fe_mulx(acc[q], zb);
     }
-    grid_finish_fe<NP>(acc, smem, partials, ticket, result, seq);
+    grid_finish_fe<NP>(acc, red);
 }
 
 // ---------------------------------------------------------------- W1: coefficient fold
@@ -626,7 +610,176 @@ __global__ __launch_bounds__(256) void axpy_kernel(fe* __restrict__ y, const fe*
         fe_store(y + i, fe_add(fe_load(y + i), fe_mulx(beta, fe_load(x + i))));
 }
 
+// <w,f> and (nv == 2) <w,g>: out[4 * v]
+int dot(pk_ctx* ctx, int nv, const uint64_t* d_w, const uint64_t* d_f, const uint64_t* d_g, size_t n, uint64_t* out) {
+    if (n == 0) return reduce_empty(ctx, nv, out);
+    red_out red;
+    unsigned blocks;
+    int rc = reduction_begin(ctx, n, &red, &blocks);
+    if (rc) return rc;
+    {
+        ProfScope prof(ctx, "dot");
+        auto kernel = nv == 2 ? dot_kernel<2> : dot_kernel<1>;
+        kernel<<<blocks, RED_THREADS, 0, ctx->stream>>>((const fe*)d_w, (const fe*)d_f, (const fe*)d_g, n, red);
+    }
+    PK_LAUNCH_CHECK(ctx);
+    return collect_reduction(ctx, nv, out);
+}
+
 }  // namespace
+
+namespace pk {
+
+// launch only: round results go to the pinned page under sequence number *red_seq_out.  gate_seq != 0 (latency mode, folding rounds
+// only): the folding challenge is not known yet -- the kernel waits for gate_publish(ctx, gate_seq, challenge) (reduce.hpp)
+int sumcheck_cubic_launch(pk_ctx* ctx, uint64_t* d_a, uint64_t* d_b, uint64_t* d_c, uint64_t* d_eq, size_t len, const uint64_t* fold_or_null,
+                          unsigned gate_seq, unsigned* red_seq_out) {
+    PK_REQUIRE(ctx, d_a && d_b && d_c && d_eq && red_seq_out, "null pointer");
+    PK_REQUIRE(ctx, is_pow2(len) && len >= 2, "size must be a power of two >= 2");  // sumcheck.rs:22-23
+    const bool fold = fold_or_null || gate_seq;
+    PK_REQUIRE(ctx, !fold || len >= 4, "size must be >= 4 when folding");    // sumcheck.rs:27
+    const size_t npairs = fold ? len / 4 : len / 2;
+    red_out red;
+    unsigned blocks;
+    int rc = reduction_begin(ctx, npairs, &red, &blocks);
+    if (rc) return rc;
+    *red_seq_out = red.seq;
+    // not folding: no challenge and no gate (fe_arg{}, gate_none())
+    const gate_args gate = gate_seq ? gate_for(ctx, gate_seq) : gate_none();
+    const fe_arg farg = fold_or_null ? to_arg(fold_or_null) : fe_arg{};
+    // a lane per pair, or -- folding rounds of few pairs only: there is no small kernel that does not fold -- eight lanes per pair
+    const bool small = fold && npairs <= SMALL_ROUND_PAIRS;
+    auto kernel = small ? sumcheck_cubic_small_kernel : fold ? sumcheck_cubic_kernel<true> : sumcheck_cubic_kernel<false>;
+    if (small) blocks = (unsigned)((npairs + RED_THREADS / 8 - 1) / (RED_THREADS / 8));
+    {
+        ProfScope prof(ctx, "sumcheck_cubic");
+        kernel<<<blocks, RED_THREADS, 0, ctx->stream>>>((fe*)d_a, (fe*)d_b, (fe*)d_c, (fe*)d_eq, len, farg, gate, red);
+    }
+    PK_LAUNCH_CHECK(ctx);
+    return PK_OK;
+}
+int sumcheck_quadratic_launch(pk_ctx* ctx, const uint64_t* d_f, const uint64_t* d_w, size_t len, const uint64_t* fold_or_null, unsigned gate_seq,
+                              uint64_t* d_f_out, uint64_t* d_w_out, unsigned* red_seq_out) {
+    PK_REQUIRE(ctx, d_f && d_w && red_seq_out, "null pointer");
+    PK_REQUIRE(ctx, is_pow2(len), "size must be a power of two");
+    const bool fold = fold_or_null || gate_seq;
+    const size_t out_len = fold ? len / 2 : len;
+    PK_REQUIRE(ctx, out_len >= 2, "at least one pair is needed after folding");
+    PK_REQUIRE(ctx, !fold || (d_f_out && d_w_out && d_f_out != d_f && d_w_out != d_w), "folding is out-of-place");
+    const size_t npairs = out_len / 2;
+    red_out red;
+    unsigned blocks;
+    int rc = reduction_begin(ctx, npairs, &red, &blocks);
+    if (rc) return rc;
+    *red_seq_out = red.seq;
+    // not folding: no challenge, no gate and no output arrays
+    const gate_args gate = gate_seq ? gate_for(ctx, gate_seq) : gate_none();
+    const fe_arg farg = fold_or_null ? to_arg(fold_or_null) : fe_arg{};
+    if (!fold) d_f_out = d_w_out = nullptr;
+    // a lane per pair, or -- rounds of few pairs, folding or not -- four lanes per pair
+    const bool small = npairs <= SMALL_ROUND_PAIRS;
+    auto kernel = small ? (fold ? sumcheck_quadratic_small_kernel<true> : sumcheck_quadratic_small_kernel<false>)
+                        : (fold ? sumcheck_quadratic_kernel<true> : sumcheck_quadratic_kernel<false>);
+    if (small) blocks = (unsigned)((npairs + RED_THREADS / 4 - 1) / (RED_THREADS / 4));
+    {
+        ProfScope prof(ctx, "sumcheck_quadratic");
+        kernel<<<blocks, RED_THREADS, 0, ctx->stream>>>((const fe*)d_f, (const fe*)d_w, out_len, farg, gate, (fe*)d_f_out, (fe*)d_w_out, red);
+    }
+    PK_LAUNCH_CHECK(ctx);
+    return PK_OK;
+}
+// the host's side of a gated launch and the wait for a launch's three results without draining the stream (prover.hip, latency mode)
+int sumcheck_collect_spin(pk_ctx* ctx, unsigned red_seq, uint64_t out[12]) { return collect_reduction_spin(ctx, 3, red_seq, out); }
+unsigned sumcheck_gate_next(pk_ctx* ctx) { return gate_next(ctx); }
+// 0 = no gated kernel of this context gave up on its challenge since the last call, else PK_ERR_HIP with the message set (reduce.hpp)
+void sumcheck_gate_clear(pk_ctx* ctx) { (void)gate_timed_out(ctx); }  // forget a give-up word without touching the error message
+int sumcheck_gate_check(pk_ctx* ctx) { return gate_timed_out(ctx) ? set_err(ctx, PK_ERR_HIP, "%s", PK_GATE_TIMEOUT_MSG) : PK_OK; }
+void sumcheck_gate_publish(pk_ctx* ctx, unsigned gate_seq, const uint64_t challenge[4]) {
+    fe c;
+    memcpy(c.v, challenge, 32);
+    gate_publish(ctx, gate_seq, c);
+}
+
+int lincomb2(pk_ctx* ctx, uint64_t* d_out, const uint64_t* d_a, const uint64_t* beta, const uint64_t* d_b, size_t n) {
+    PK_REQUIRE(ctx, beta && (n == 0 || (d_out && d_a && d_b)), "null pointer");
+    if (!n) return PK_OK;
+    ProfScope prof(ctx, "lincomb");
+    lincomb_kernel<<<grid_for(ctx, n, 256), 256, 0, ctx->stream>>>((fe*)d_out, (const fe*)d_a, (const fe*)d_b, n, to_arg(beta));
+    PK_LAUNCH_CHECK(ctx);
+    return PK_OK;
+}
+int fold_pairs2(pk_ctx* ctx, const uint64_t* d_v0, uint64_t* d_out0, const uint64_t* d_v1, uint64_t* d_out1, size_t len, const uint64_t* r,
+                unsigned gate_seq) {
+    PK_REQUIRE(ctx, d_v0 && d_out0 && d_v1 && d_out1 && (r || gate_seq), "null pointer");
+    PK_REQUIRE(ctx, is_pow2(len) && len >= 2, "size must be a power of two >= 2");
+    if (gate_seq) {
+        int rc = reduction_scratch(ctx);
+        if (rc) return rc;
+    }
+    ProfScope prof(ctx, "fold_pairs");
+    fold_pairs_kernel<<<dim3(grid_for(ctx, len / 2, 256), 2), 256, 0, ctx->stream>>>((const fe*)d_v0, (fe*)d_out0, (const fe*)d_v1, (fe*)d_out1,
+                                                                                     len / 2, r ? to_arg(r) : fe_arg{},
+                                                                                     gate_seq ? gate_for(ctx, gate_seq) : gate_none());
+    PK_LAUNCH_CHECK(ctx);
+    return PK_OK;
+}
+
+int eval_univariate_multi(pk_ctx* ctx, const uint64_t* const* d_polys, unsigned np, size_t n, const uint64_t z[4], uint64_t* out) {
+    PK_REQUIRE(ctx, np == 1 || np == 2, "one or two polynomials");
+    if (n == 0) return reduce_empty(ctx, (int)np, out);
+    PK_REQUIRE(ctx, (n >> 28) == 0, "polynomial too long for the evaluation kernel (2^28 coefficients)");
+    red_out red;
+    unsigned blocks;
+    int rc = reduction_begin(ctx, n, &red, &blocks);
+    if (rc) return rc;
+    // not reduction_blocks' grid: ~8 coefficients per lane, at most RED_MAX_BLOCKS (1024) workgroups, each over a contiguous segment
+    // of 256 * cnt coefficients
+    size_t want = (n / 8 + RED_THREADS - 1) / RED_THREADS;
+    const size_t cap = want < 1 ? 1 : (want > RED_MAX_BLOCKS ? RED_MAX_BLOCKS : want);
+    const size_t cnt = (n + cap * RED_THREADS - 1) / (cap * RED_THREADS);
+    blocks = (unsigned)((n + cnt * RED_THREADS - 1) / (cnt * RED_THREADS));
+    if (!ctx->d_ztab) PK_HIP(ctx, hipMalloc(&ctx->d_ztab, 256 * 32));
+    // z^(2^i) on the host (27 squarings)
+    pow2_args zp;
+    {
+        fe b;
+        memcpy(b.v, z, 32);
+        for (int i = 0; i < 28; i++) {
+            memcpy(zp.p[i].v, b.v, 32);
+            b = fe_mulx(b, b);
+        }
+    }
+    {
+        ProfScope prof(ctx, "eval_univariate");
+        zpow_table_kernel<<<1, RED_THREADS, 0, ctx->stream>>>(zp, (fe*)ctx->d_ztab);
+        auto kernel = np == 2 ? horner_kernel<2> : horner_kernel<1>;
+        kernel<<<blocks, RED_THREADS, 0, ctx->stream>>>((const fe*)d_polys[0], (const fe*)(np == 2 ? d_polys[1] : nullptr), n, cnt, zp,
+                                                        (const fe*)ctx->d_ztab, red);
+    }
+    PK_LAUNCH_CHECK(ctx);
+    return collect_reduction(ctx, (int)np, out);
+}
+int dot_rows(pk_ctx* ctx, const uint64_t* d_w, size_t row_stride, unsigned nrows, const uint64_t* d_f, const uint64_t* d_g, size_t n, uint64_t* out,
+             bool defer) {
+    const int nv = d_g ? 2 : 1;
+    PK_REQUIRE(ctx, nrows == 3 && (out || defer) && (n == 0 || (d_w && d_f)), "three weight rows");
+    PK_REQUIRE(ctx, !defer || (n != 0 && !ctx->red_across), "a deferred dot product needs work and a lone context");
+    if (n == 0) return reduce_empty(ctx, 3 * nv, out);
+    red_out red;
+    unsigned blocks;
+    int rc = reduction_begin(ctx, n, &red, &blocks);
+    if (rc) return rc;
+    {
+        ProfScope prof(ctx, "dot");
+        auto kernel = nv == 2 ? dot_rows_kernel<3, 2> : dot_rows_kernel<3, 1>;
+        kernel<<<blocks, RED_THREADS, 0, ctx->stream>>>((const fe*)d_w, row_stride, (const fe*)d_f, (const fe*)d_g, n, red);
+    }
+    PK_LAUNCH_CHECK(ctx);
+    if (defer) return PK_OK;
+    return collect_reduction(ctx, 3 * nv, out);
+}
+
+}  // namespace pk
 
 extern "C" {
 
@@ -691,89 +844,6 @@ int pk_eq_table(pk_ctx* ctx, const uint64_t* r, unsigned m, uint64_t* d_out) {
     return pk_eq_accumulate(ctx, d_out, m, r, one, 1, 1);
 }
 
-}  // extern "C"
-namespace pk {
-// launch only: round results go to the pinned page under sequence number *red_seq_out.  gate_seq != 0 (latency mode, folding rounds
-// only): the folding challenge is not known yet -- the kernel waits for gate_publish(ctx, gate_seq, challenge) (reduce.hpp)
-int sumcheck_cubic_launch(pk_ctx* ctx, uint64_t* d_a, uint64_t* d_b, uint64_t* d_c, uint64_t* d_eq, size_t len, const uint64_t* fold_or_null,
-                          unsigned gate_seq, unsigned* red_seq_out) {
-    PK_REQUIRE(ctx, d_a && d_b && d_c && d_eq && red_seq_out, "null pointer");
-    PK_REQUIRE(ctx, is_pow2(len) && len >= 2, "size must be a power of two >= 2");  // sumcheck.rs:22-23
-    const bool fold = fold_or_null || gate_seq;
-    PK_REQUIRE(ctx, !fold || len >= 4, "size must be >= 4 when folding");    // sumcheck.rs:27
-    int rc = reduction_scratch(ctx);
-    if (rc) return rc;
-    size_t npairs = fold ? len / 4 : len / 2;
-    unsigned blocks = reduction_blocks(ctx, npairs);
-    const gate_args gate = gate_seq ? gate_for(ctx, gate_seq) : gate_none();
-    const fe_arg farg = fold_or_null ? to_arg(fold_or_null) : fe_arg{};
-    const unsigned seq = next_seq(ctx);
-    *red_seq_out = seq;
-    {
-        ProfScope prof(ctx, "sumcheck_cubic");
-        if (fold && npairs <= SMALL_ROUND_PAIRS)
-            sumcheck_cubic_small_kernel<<<(unsigned)((npairs + RED_THREADS / 8 - 1) / (RED_THREADS / 8)), RED_THREADS, 0, ctx->stream>>>(
-                (fe*)d_a, (fe*)d_b, (fe*)d_c, (fe*)d_eq, len, farg, gate, red_partials(ctx), red_ticket(ctx), red_result(ctx), seq);
-        else if (fold)
-            sumcheck_cubic_kernel<true><<<blocks, RED_THREADS, 0, ctx->stream>>>((fe*)d_a, (fe*)d_b, (fe*)d_c, (fe*)d_eq, len, farg, gate,
-                                                                                  red_partials(ctx), red_ticket(ctx), red_result(ctx), seq);
-        else
-            sumcheck_cubic_kernel<false><<<blocks, RED_THREADS, 0, ctx->stream>>>((fe*)d_a, (fe*)d_b, (fe*)d_c, (fe*)d_eq, len, fe_arg{}, gate_none(),
-                                                                                   red_partials(ctx), red_ticket(ctx), red_result(ctx), seq);
-    }
-    PK_LAUNCH_CHECK(ctx);
-    return PK_OK;
-}
-int sumcheck_quadratic_launch(pk_ctx* ctx, const uint64_t* d_f, const uint64_t* d_w, size_t len, const uint64_t* fold_or_null, unsigned gate_seq,
-                              uint64_t* d_f_out, uint64_t* d_w_out, unsigned* red_seq_out) {
-    PK_REQUIRE(ctx, d_f && d_w && red_seq_out, "null pointer");
-    PK_REQUIRE(ctx, is_pow2(len), "size must be a power of two");
-    const bool fold = fold_or_null || gate_seq;
-    size_t out_len = fold ? len / 2 : len;
-    PK_REQUIRE(ctx, out_len >= 2, "at least one pair is needed after folding");
-    PK_REQUIRE(ctx, !fold || (d_f_out && d_w_out && d_f_out != d_f && d_w_out != d_w), "folding is out-of-place");
-    int rc = reduction_scratch(ctx);
-    if (rc) return rc;
-    unsigned blocks = reduction_blocks(ctx, out_len / 2);
-    const gate_args gate = gate_seq ? gate_for(ctx, gate_seq) : gate_none();
-    const fe_arg farg = fold_or_null ? to_arg(fold_or_null) : fe_arg{};
-    const unsigned seq = next_seq(ctx);
-    *red_seq_out = seq;
-    {
-        ProfScope prof(ctx, "sumcheck_quadratic");
-        const size_t npairs = out_len / 2;
-        const unsigned sblocks = (unsigned)((npairs + RED_THREADS / 4 - 1) / (RED_THREADS / 4));
-        if (npairs <= SMALL_ROUND_PAIRS && fold)
-            sumcheck_quadratic_small_kernel<true><<<sblocks, RED_THREADS, 0, ctx->stream>>>((const fe*)d_f, (const fe*)d_w, out_len, farg, gate, (fe*)d_f_out,
-                                                                                            (fe*)d_w_out, red_partials(ctx), red_ticket(ctx),
-                                                                                            red_result(ctx), seq);
-        else if (npairs <= SMALL_ROUND_PAIRS)
-            sumcheck_quadratic_small_kernel<false><<<sblocks, RED_THREADS, 0, ctx->stream>>>((const fe*)d_f, (const fe*)d_w, out_len, fe_arg{}, gate_none(),
-                                                                                             nullptr, nullptr, red_partials(ctx), red_ticket(ctx),
-                                                                                             red_result(ctx), seq);
-        else if (fold)
-            sumcheck_quadratic_kernel<true><<<blocks, RED_THREADS, 0, ctx->stream>>>((const fe*)d_f, (const fe*)d_w, out_len, farg, gate, (fe*)d_f_out,
-                                                                                      (fe*)d_w_out, red_partials(ctx), red_ticket(ctx), red_result(ctx), seq);
-        else
-            sumcheck_quadratic_kernel<false><<<blocks, RED_THREADS, 0, ctx->stream>>>((const fe*)d_f, (const fe*)d_w, out_len, fe_arg{}, gate_none(), nullptr,
-                                                                                       nullptr, red_partials(ctx), red_ticket(ctx), red_result(ctx), seq);
-    }
-    PK_LAUNCH_CHECK(ctx);
-    return PK_OK;
-}
-// the host's side of a gated launch and the wait for a launch's three results without draining the stream (prover.hip, latency mode)
-int sumcheck_collect_spin(pk_ctx* ctx, unsigned red_seq, uint64_t out[12]) { return collect_reduction_spin<3>(ctx, red_seq, out); }
-unsigned sumcheck_gate_next(pk_ctx* ctx) { return gate_next(ctx); }
-// 0 = no gated kernel of this context gave up on its challenge since the last call, else PK_ERR_HIP with the message set (reduce.hpp)
-void sumcheck_gate_clear(pk_ctx* ctx) { (void)gate_timed_out(ctx); }  // forget a give-up word without touching the error message
-int sumcheck_gate_check(pk_ctx* ctx) { return gate_timed_out(ctx) ? set_err(ctx, PK_ERR_HIP, "%s", PK_GATE_TIMEOUT_MSG) : PK_OK; }
-void sumcheck_gate_publish(pk_ctx* ctx, unsigned gate_seq, const uint64_t challenge[4]) {
-    fe c;
-    memcpy(c.v, challenge, 32);
-    gate_publish(ctx, gate_seq, c);
-}
-}  // namespace pk
-extern "C" {
 
 int pk_sumcheck_cubic_round(pk_ctx* ctx, uint64_t* d_a, uint64_t* d_b, uint64_t* d_c, uint64_t* d_eq, size_t len,
                             const uint64_t* fold_or_null, uint64_t out[12]) {
@@ -782,7 +852,7 @@ int pk_sumcheck_cubic_round(pk_ctx* ctx, uint64_t* d_a, uint64_t* d_b, uint64_t*
     unsigned seq = 0;
     int rc = sumcheck_cubic_launch(ctx, d_a, d_b, d_c, d_eq, len, fold_or_null, 0, &seq);
     if (rc) return rc;
-    return collect_reduction<3>(ctx, out);
+    return collect_reduction(ctx, 3, out);
 }
 
 int pk_sumcheck_quadratic_round(pk_ctx* ctx, const uint64_t* d_f, const uint64_t* d_w, size_t len, const uint64_t* fold_or_null,
@@ -792,7 +862,7 @@ int pk_sumcheck_quadratic_round(pk_ctx* ctx, const uint64_t* d_f, const uint64_t
     unsigned seq = 0;
     int rc = sumcheck_quadratic_launch(ctx, d_f, d_w, len, fold_or_null, 0, d_f_out, d_w_out, &seq);
     if (rc) return rc;
-    return collect_reduction<3>(ctx, out);
+    return collect_reduction(ctx, 3, out);
 }
 
 int pk_fold_pairs(pk_ctx* ctx, const uint64_t* d_v, size_t len, const uint64_t* r, uint64_t* d_out) {
@@ -803,84 +873,17 @@ int pk_fold_pairs(pk_ctx* ctx, const uint64_t* d_v, size_t len, const uint64_t* 
     PK_LAUNCH_CHECK(ctx);
     return PK_OK;
 }
-}  // extern "C"
-namespace pk {
-int lincomb2(pk_ctx* ctx, uint64_t* d_out, const uint64_t* d_a, const uint64_t* beta, const uint64_t* d_b, size_t n) {
-    PK_REQUIRE(ctx, beta && (n == 0 || (d_out && d_a && d_b)), "null pointer");
-    if (!n) return PK_OK;
-    ProfScope prof(ctx, "lincomb");
-    lincomb_kernel<<<grid_for(ctx, n, 256), 256, 0, ctx->stream>>>((fe*)d_out, (const fe*)d_a, (const fe*)d_b, n, to_arg(beta));
-    PK_LAUNCH_CHECK(ctx);
-    return PK_OK;
-}
-// two arrays of the same length folded by the same challenge in one launch (the sumcheck's p and w)
-// r = NULL with gate_seq != 0: the challenge arrives through the gate (latency mode)
-int fold_pairs2_gated(pk_ctx* ctx, const uint64_t* d_v0, uint64_t* d_out0, const uint64_t* d_v1, uint64_t* d_out1, size_t len, const uint64_t* r,
-                      unsigned gate_seq) {
-    PK_REQUIRE(ctx, d_v0 && d_out0 && d_v1 && d_out1 && (r || gate_seq), "null pointer");
-    PK_REQUIRE(ctx, is_pow2(len) && len >= 2, "size must be a power of two >= 2");
-    if (gate_seq) {
-        int rc = reduction_scratch(ctx);
-        if (rc) return rc;
-    }
-    ProfScope prof(ctx, "fold_pairs");
-    fold_pairs_kernel<<<dim3(grid_for(ctx, len / 2, 256), 2), 256, 0, ctx->stream>>>((const fe*)d_v0, (fe*)d_out0, (const fe*)d_v1, (fe*)d_out1,
-                                                                                     len / 2, r ? to_arg(r) : fe_arg{},
-                                                                                     gate_seq ? gate_for(ctx, gate_seq) : gate_none());
-    PK_LAUNCH_CHECK(ctx);
-    return PK_OK;
-}
-int fold_pairs2(pk_ctx* ctx, const uint64_t* d_v0, uint64_t* d_out0, const uint64_t* d_v1, uint64_t* d_out1, size_t len, const uint64_t* r) {
-    PK_REQUIRE(ctx, r, "null pointer");
-    return fold_pairs2_gated(ctx, d_v0, d_out0, d_v1, d_out1, len, r, 0);
-}
-}  // namespace pk
-extern "C" {
 
 int pk_dot(pk_ctx* ctx, const uint64_t* d_w, const uint64_t* d_f, size_t n, uint64_t out[4]) {
     PK_ENTER(ctx);
     PK_REQUIRE(ctx, out && (n == 0 || (d_w && d_f)), "null pointer");
-    if (n == 0 && ctx->red_across) {  // an empty share still takes part in the exchange of the ranks' partial sums
-        PK_HIP(ctx, hipMemsetAsync(ctx->d_xred, 0, 32, ctx->stream));
-        return collect_reduction<1>(ctx, out);
-    }
-    if (n == 0) {
-        memset(out, 0, 32);
-        return PK_OK;
-    }
-    int rc = reduction_scratch(ctx);
-    if (rc) return rc;
-    unsigned blocks = reduction_blocks(ctx, n);
-    {
-        ProfScope prof(ctx, "dot");
-        dot_kernel<1><<<blocks, RED_THREADS, 0, ctx->stream>>>((const fe*)d_w, (const fe*)d_f, nullptr, n, red_partials(ctx), red_ticket(ctx),
-                                                               red_result(ctx), next_seq(ctx));
-    }
-    PK_LAUNCH_CHECK(ctx);
-    return collect_reduction<1>(ctx, out);
+    return dot(ctx, 1, d_w, d_f, nullptr, n, out);
 }
 
 int pk_dot2(pk_ctx* ctx, const uint64_t* d_w, const uint64_t* d_f, const uint64_t* d_g, size_t n, uint64_t out[8]) {
     PK_ENTER(ctx);
     PK_REQUIRE(ctx, out && (n == 0 || (d_w && d_f && d_g)), "null pointer");
-    if (n == 0 && ctx->red_across) {
-        PK_HIP(ctx, hipMemsetAsync(ctx->d_xred, 0, 64, ctx->stream));
-        return collect_reduction<2>(ctx, out);
-    }
-    if (n == 0) {
-        memset(out, 0, 64);
-        return PK_OK;
-    }
-    int rc = reduction_scratch(ctx);
-    if (rc) return rc;
-    unsigned blocks = reduction_blocks(ctx, n);
-    {
-        ProfScope prof(ctx, "dot");
-        dot_kernel<2><<<blocks, RED_THREADS, 0, ctx->stream>>>((const fe*)d_w, (const fe*)d_f, (const fe*)d_g, n, red_partials(ctx), red_ticket(ctx),
-                                                               red_result(ctx), next_seq(ctx));
-    }
-    PK_LAUNCH_CHECK(ctx);
-    return collect_reduction<2>(ctx, out);
+    return dot(ctx, 2, d_w, d_f, d_g, n, out);
 }
 
 int pk_eval_univariate(pk_ctx* ctx, const uint64_t* d_coeffs, size_t n, const uint64_t z[4], uint64_t out[4]) {
@@ -889,90 +892,6 @@ int pk_eval_univariate(pk_ctx* ctx, const uint64_t* d_coeffs, size_t n, const ui
     const uint64_t* polys[1] = {d_coeffs};
     return pk::eval_univariate_multi(ctx, polys, 1, n, z, out);
 }
-}  // extern "C"
-namespace pk {
-// np (1 or 2) polynomials of n coefficients each at the same z, one launch: out[4 * q] = poly_q(z)
-int eval_univariate_multi(pk_ctx* ctx, const uint64_t* const* d_polys, unsigned np, size_t n, const uint64_t z[4], uint64_t* out) {
-    PK_REQUIRE(ctx, np == 1 || np == 2, "one or two polynomials");
-    if (n == 0) {
-        if (ctx->red_across) {
-            PK_HIP(ctx, hipMemsetAsync(ctx->d_xred, 0, 32 * np, ctx->stream));
-            return np == 1 ? collect_reduction<1>(ctx, out) : collect_reduction<2>(ctx, out);
-        }
-        memset(out, 0, 32 * np);
-        return PK_OK;
-    }
-    int rc = reduction_scratch(ctx);
-    if (rc) return rc;
-    // ~8 coefficients per lane, at most RED_MAX_BLOCKS (1024) workgroups, each over a contiguous segment of 256 * cnt coefficients
-    size_t want = (n / 8 + RED_THREADS - 1) / RED_THREADS;
-    const size_t cap = want < 1 ? 1 : (want > RED_MAX_BLOCKS ? RED_MAX_BLOCKS : want);
-    const size_t cnt = (n + cap * RED_THREADS - 1) / (cap * RED_THREADS);
-    const unsigned blocks = (unsigned)((n + cnt * RED_THREADS - 1) / (cnt * RED_THREADS));
-    PK_REQUIRE(ctx, (n >> 28) == 0, "polynomial too long for the evaluation kernel (2^28 coefficients)");
-    if (!ctx->d_ztab) PK_HIP(ctx, hipMalloc(&ctx->d_ztab, 256 * 32));
-    // z^(2^i) on the host (27 squarings)
-    pow2_args zp;
-    {
-        fe b;
-        memcpy(b.v, z, 32);
-        for (int i = 0; i < 28; i++) {
-            memcpy(zp.p[i].v, b.v, 32);
-            b = fe_mulx(b, b);
-        }
-    }
-    {
-        ProfScope prof(ctx, "eval_univariate");
-        zpow_table_kernel<<<1, RED_THREADS, 0, ctx->stream>>>(zp, (fe*)ctx->d_ztab);
-        if (np == 1)
-            horner_kernel<1><<<blocks, RED_THREADS, 0, ctx->stream>>>((const fe*)d_polys[0], nullptr, n, cnt, zp, (const fe*)ctx->d_ztab, red_partials(ctx),
-                                                                     red_ticket(ctx), red_result(ctx), next_seq(ctx));
-        else
-            horner_kernel<2><<<blocks, RED_THREADS, 0, ctx->stream>>>((const fe*)d_polys[0], (const fe*)d_polys[1], n, cnt, zp, (const fe*)ctx->d_ztab,
-                                                                     red_partials(ctx), red_ticket(ctx), red_result(ctx), next_seq(ctx));
-    }
-    PK_LAUNCH_CHECK(ctx);
-    return np == 1 ? collect_reduction<1>(ctx, out) : collect_reduction<2>(ctx, out);
-}
-// nrows (1..3) weight rows against f and (nv == 2) g in one pass: out[4 * (nv * k + v)]
-// defer: launch only -- the caller synchronises `ctx`'s stream later and takes the 3 * nv results from its pinned page (latency mode: the
-// statement's sums run on a side stream underneath the blinding WHIR proof)
-int dot_rows_x(pk_ctx* ctx, const uint64_t* d_w, size_t row_stride, unsigned nrows, const uint64_t* d_f, const uint64_t* d_g, size_t n, uint64_t* out,
-               bool defer);
-int dot_rows(pk_ctx* ctx, const uint64_t* d_w, size_t row_stride, unsigned nrows, const uint64_t* d_f, const uint64_t* d_g, size_t n, uint64_t* out) {
-    return dot_rows_x(ctx, d_w, row_stride, nrows, d_f, d_g, n, out, false);
-}
-int dot_rows_x(pk_ctx* ctx, const uint64_t* d_w, size_t row_stride, unsigned nrows, const uint64_t* d_f, const uint64_t* d_g, size_t n, uint64_t* out,
-               bool defer) {
-    const int nv = d_g ? 2 : 1;
-    PK_REQUIRE(ctx, nrows == 3 && (out || defer) && (n == 0 || (d_w && d_f)), "three weight rows");
-    PK_REQUIRE(ctx, !defer || (n != 0 && !ctx->red_across), "a deferred dot product needs work and a lone context");
-    if (n == 0) {
-        if (ctx->red_across) {
-            PK_HIP(ctx, hipMemsetAsync(ctx->d_xred, 0, 32 * 3 * nv, ctx->stream));
-            return nv == 2 ? collect_reduction<6>(ctx, out) : collect_reduction<3>(ctx, out);
-        }
-        memset(out, 0, 32 * 3 * (size_t)nv);
-        return PK_OK;
-    }
-    int rc = reduction_scratch(ctx);
-    if (rc) return rc;
-    unsigned blocks = reduction_blocks(ctx, n);
-    {
-        ProfScope prof(ctx, "dot");
-        if (nv == 2)
-            dot_rows_kernel<3, 2><<<blocks, RED_THREADS, 0, ctx->stream>>>((const fe*)d_w, row_stride, (const fe*)d_f, (const fe*)d_g, n, red_partials(ctx),
-                                                                          red_ticket(ctx), red_result(ctx), next_seq(ctx));
-        else
-            dot_rows_kernel<3, 1><<<blocks, RED_THREADS, 0, ctx->stream>>>((const fe*)d_w, row_stride, (const fe*)d_f, nullptr, n, red_partials(ctx),
-                                                                          red_ticket(ctx), red_result(ctx), next_seq(ctx));
-    }
-    PK_LAUNCH_CHECK(ctx);
-    if (defer) return PK_OK;
-    return nv == 2 ? collect_reduction<6>(ctx, out) : collect_reduction<3>(ctx, out);
-}
-}  // namespace pk
-extern "C" {
 
 int pk_fold_coeffs(pk_ctx* ctx, const uint64_t* d_coeffs, unsigned n_vars, const uint64_t* r, unsigned k, uint64_t* d_out) {
     PK_ENTER(ctx);

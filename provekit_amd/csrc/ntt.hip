@@ -29,7 +29,7 @@
 
 // partly memory-bound (VALUBusy ~75 %): between the pure-ALU hash kernels (0) and the memory-bound kernels (2)
 #define PK_BASE_PRIO 1
-#include "ctx.hpp"
+#include "internal.hpp"
 #include "ntt_regs.hpp"
 
 using namespace pk;
@@ -885,29 +885,6 @@ int deinterleave(pk_ctx* ctx, const fe* coeffs, size_t n_coeffs, unsigned fold, 
     return PK_OK;
 }
 
-}  // namespace pk
-
-extern "C" {
-
-int pk_ntt(pk_ctx* ctx, const uint64_t* d_in, uint64_t* d_out, unsigned log_n, unsigned ncols) {
-    PK_ENTER(ctx);
-    PK_REQUIRE(ctx, d_in && d_out, "null pointer");
-    PK_REQUIRE(ctx, ncols >= 1, "ncols must be >= 1");
-    size_t N = (size_t)1 << log_n;
-    fe* scratch = nullptr;
-    if (log_n > 9) PK_HIP(ctx, hipMalloc((void**)&scratch, 32 * N * ncols));
-    int rc = pk::ntt_columns(ctx, (const fe*)d_in, N, N, (fe*)d_out, N, scratch, log_n, ncols, false);
-    if (scratch) {
-        hipError_t e = wait_ctx(ctx);
-        (void)hipFree(scratch);
-        if (!rc && e != hipSuccess) rc = set_err(ctx, PK_ERR_HIP, "ntt failed: %s", hipGetErrorString(e));
-    }
-    return rc;
-}
-
-}  // extern "C"
-
-namespace pk {
 // the two encodes with a choice of output encoding (scaled = hash-ready, see ntt_scaled_available); the C entry points
 // below always return Montgomery images
 static int check_encode_args(pk_ctx* ctx, const uint64_t* const* d_coeffs, unsigned batch, unsigned n_vars, unsigned log_inv_rate,
@@ -975,6 +952,22 @@ int rs_encode_shard_x(pk_ctx* ctx, const uint64_t* const* d_coeffs, unsigned bat
 }  // namespace pk
 
 extern "C" {
+
+int pk_ntt(pk_ctx* ctx, const uint64_t* d_in, uint64_t* d_out, unsigned log_n, unsigned ncols) {
+    PK_ENTER(ctx);
+    PK_REQUIRE(ctx, d_in && d_out, "null pointer");
+    PK_REQUIRE(ctx, ncols >= 1, "ncols must be >= 1");
+    size_t N = (size_t)1 << log_n;
+    fe* scratch = nullptr;
+    if (log_n > 9) PK_HIP(ctx, hipMalloc((void**)&scratch, 32 * N * ncols));
+    int rc = pk::ntt_columns(ctx, (const fe*)d_in, N, N, (fe*)d_out, N, scratch, log_n, ncols, false);
+    if (scratch) {
+        hipError_t e = wait_ctx(ctx);
+        (void)hipFree(scratch);
+        if (!rc && e != hipSuccess) rc = set_err(ctx, PK_ERR_HIP, "ntt failed: %s", hipGetErrorString(e));
+    }
+    return rc;
+}
 
 int pk_rs_encode(pk_ctx* ctx, const uint64_t* const* d_coeffs, unsigned batch, unsigned n_vars, unsigned log_inv_rate,
                  unsigned fold, uint64_t* d_leaves, uint64_t* d_scratch) {

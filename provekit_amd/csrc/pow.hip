@@ -10,7 +10,7 @@
 
 // pure ALU like the hash, but a prover is waiting for the nonce: one step above the hash kernels
 #define PK_BASE_PRIO 1
-#include "ctx.hpp"
+#include "internal.hpp"
 #include "skyscraper29s.hpp"
 
 using namespace pk;
@@ -113,23 +113,6 @@ int pow_words(pk_ctx* ctx, unsigned long long** best, unsigned** ticket, unsigne
 
 }  // namespace
 
-extern "C" {
-
-// pow.rs:14-22
-int pk_pow_threshold(double difficulty, uint64_t out[4]) {
-    if (!out || !(difficulty >= 0.0 && difficulty < 80.0)) return PK_ERR_BAD_ARG;  // "Difficulty must be in the range [0, 80)"
-    const double modulus = (double)0x30644e72e131a029ull * std::ldexp(1.0, 192);
-    const double prob = std::exp2(-difficulty);
-    f64_to_u256(prob * modulus, out);
-    return PK_OK;
-}
-
-// PowStrategy::solve (provekit/common/src/skyscraper/pow.rs:27-29) -> pow::solve (pow.rs:33-41)
-int pk_pow_solve(pk_ctx* ctx, const uint8_t challenge[32], double bits, uint64_t* nonce) {
-    PK_ENTER(ctx);
-    return pk::pow_solve_x(ctx, challenge, bits, nonce, false);
-}
-}  // extern "C"
 namespace pk {
 // striped = every rank of the context's device set is inside this call with the same challenge: the nonce space of each window
 // is striped over the ranks (rank g tries base + t, t = g mod G), then ONE all-gather of the ranks' 8-byte minima; the result is
@@ -197,7 +180,23 @@ int pow_solve_x(pk_ctx* ctx, const uint8_t challenge[32], double bits, uint64_t*
     return PK_OK;
 }
 }  // namespace pk
+
 extern "C" {
+
+// pow.rs:14-22
+int pk_pow_threshold(double difficulty, uint64_t out[4]) {
+    if (!out || !(difficulty >= 0.0 && difficulty < 80.0)) return PK_ERR_BAD_ARG;  // "Difficulty must be in the range [0, 80)"
+    const double modulus = (double)0x30644e72e131a029ull * std::ldexp(1.0, 192);
+    const double prob = std::exp2(-difficulty);
+    f64_to_u256(prob * modulus, out);
+    return PK_OK;
+}
+
+// PowStrategy::solve (provekit/common/src/skyscraper/pow.rs:27-29) -> pow::solve (pow.rs:33-41)
+int pk_pow_solve(pk_ctx* ctx, const uint8_t challenge[32], double bits, uint64_t* nonce) {
+    PK_ENTER(ctx);
+    return pk::pow_solve_x(ctx, challenge, bits, nonce, false);
+}
 
 // PowStrategy::check (skyscraper/pow.rs:23-25) -> pow::verify (pow.rs:24-26): NO prover bias
 int pk_pow_check(pk_ctx* ctx, const uint8_t challenge[32], double bits, uint64_t nonce, int* ok) {

@@ -21,40 +21,11 @@
 #include <string>
 #include <vector>
 
-#include "ctx.hpp"
+#include "internal.hpp"
 #include "shard_map.hpp"
 #include "transcript.hpp"
 
 using namespace pk;
-
-namespace pk {
-int commit_into(pk_ctx* ctx, const uint64_t* const* d_coeffs, unsigned batch, unsigned n_vars, unsigned log_inv_rate, unsigned fold,
-                uint64_t* d_leaves, uint64_t* d_nodes, uint64_t* d_scratch, pk_commit_layout* layout_out);
-int open_raw(pk_ctx* ctx, const uint64_t* d_leaves, const uint64_t* d_nodes, size_t n_leaves, size_t width, const pk_commit_layout& lay,
-             const uint64_t* indices, size_t k, int canonical_leaves, uint64_t* leaves_out, uint64_t* sibling_digests, uint64_t* auth_paths);
-unsigned shard_factor(const pk_ctx* ctx, size_t rows);
-size_t commit_scratch_fes(const pk_ctx* ctx, size_t rows, size_t width);
-int dot_rows_x(pk_ctx* ctx, const uint64_t* d_w, size_t row_stride, unsigned nrows, const uint64_t* d_f, const uint64_t* d_g, size_t n, uint64_t* out,
-               bool defer);
-int lincomb2(pk_ctx* ctx, uint64_t* d_out, const uint64_t* d_a, const uint64_t* beta, const uint64_t* d_b, size_t n);
-int fold_pairs2(pk_ctx* ctx, const uint64_t* d_v0, uint64_t* d_out0, const uint64_t* d_v1, uint64_t* d_out1, size_t len, const uint64_t* r);
-// latency mode (ctx.hpp): launch-only rounds, gated on a challenge the host publishes later (mle.hip, reduce.hpp)
-int fold_pairs2_gated(pk_ctx* ctx, const uint64_t* d_v0, uint64_t* d_out0, const uint64_t* d_v1, uint64_t* d_out1, size_t len, const uint64_t* r,
-                      unsigned gate_seq);
-int sumcheck_cubic_launch(pk_ctx* ctx, uint64_t* d_a, uint64_t* d_b, uint64_t* d_c, uint64_t* d_eq, size_t len, const uint64_t* fold_or_null,
-                          unsigned gate_seq, unsigned* red_seq_out);
-int sumcheck_quadratic_launch(pk_ctx* ctx, const uint64_t* d_f, const uint64_t* d_w, size_t len, const uint64_t* fold_or_null, unsigned gate_seq,
-                              uint64_t* d_f_out, uint64_t* d_w_out, unsigned* red_seq_out);
-int sumcheck_collect_spin(pk_ctx* ctx, unsigned red_seq, uint64_t out[12]);
-unsigned sumcheck_gate_next(pk_ctx* ctx);
-int sumcheck_gate_check(pk_ctx* ctx);
-void sumcheck_gate_clear(pk_ctx* ctx);
-void sumcheck_gate_publish(pk_ctx* ctx, unsigned gate_seq, const uint64_t challenge[4]);
-int witness_bounds_strided(pk_ctx* ctx, const pk_r1cs* r, const uint64_t* d_z, unsigned m0, unsigned stride, unsigned offset, uint64_t* d_a,
-                           uint64_t* d_b, uint64_t* d_c);
-int external_row_range(pk_ctx* ctx, const pk_r1cs* r, const uint64_t* d_eq_alpha, size_t first, size_t last, uint64_t* d_out);
-void witness_program_shape(const pk_witness_program* p, size_t* n_witnesses, size_t* n_challenges, size_t* n_acir);  // witness.hip
-}
 
 struct pk_scheme {
     const pk_r1cs* r1cs = nullptr;
@@ -551,7 +522,7 @@ struct WhirProver {
                 if (more || len >= 2) {
                     gate.arm(sumcheck_gate_next(ctx));
                     if (more) CK(sumcheck_quadratic_launch(ctx, U(bp[cur]), U(bw[cur]), len, nullptr, gate.seq, U(bp[1 - cur]), U(bw[1 - cur]), &red_next));
-                    else CK(fold_pairs2_gated(ctx, U(bp[cur]), U(bp[1 - cur]), U(bw[cur]), U(bw[1 - cur]), len, nullptr, gate.seq));
+                    else CK(fold_pairs2(ctx, U(bp[cur]), U(bp[1 - cur]), U(bw[cur]), U(bw[1 - cur]), len, nullptr, gate.seq));
                     flip();
                 }
                 CK(sumcheck_collect_spin(ctx, red_cur, out));
@@ -1127,7 +1098,7 @@ int external_rows(pk_ctx* ctx, Proof& P) {
     if (P.st_sharded) CK(external_row_range(ctx, P.s->r1cs, U(d_eq_alpha), P.blk_lo, std::min(nw, P.blk_lo + P.blk), U(rows)));  // this rank's columns
     else CK(pk_r1cs_external_row(ctx, P.s->r1cs, U(d_eq_alpha), U(rows)));
     if (ctx == P.ctx) return PK_OK;
-    return dot_rows_x(ctx, U(rows), nw, 3, U(P.W.f_evals), U(P.W.g_evals), nw, nullptr, /*defer=*/true);
+    return dot_rows(ctx, U(rows), nw, 3, U(P.W.f_evals), U(P.W.g_evals), nw, nullptr, /*defer=*/true);
 }
 
 // --- commit to the masked witness polynomial (whir_r1cs.rs:57-69).  Latency mode: the blinding commitment depends on nothing but the

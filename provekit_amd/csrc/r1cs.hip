@@ -17,17 +17,11 @@
 
 // memory- / latency-bound kernels: their wavefronts issue ahead of the ALU-bound hash / NTT / grinder kernels they share SIMDs with
 #define PK_BASE_PRIO 2
-#include "ctx.hpp"
+#include "internal.hpp"
 #include "fe29.hpp"
 #include "reduce.hpp"
 
 using namespace pk;
-
-namespace pk {
-int witness_bounds_strided(pk_ctx* ctx, const pk_r1cs* r, const uint64_t* d_z, unsigned m0, unsigned stride, unsigned offset, uint64_t* d_a,
-                           uint64_t* d_b, uint64_t* d_c);
-int external_row_range(pk_ctx* ctx, const pk_r1cs* r, const uint64_t* d_eq_alpha, size_t first, size_t last, uint64_t* d_out);
-}
 
 constexpr uint32_t HEAVY_DEGREE = 64;    // longer lines are summed by workgroups
 constexpr uint32_t HEAVY_CHUNK = 2048;   // entries per workgroup
@@ -81,14 +75,11 @@ __global__ __launch_bounds__(RED_THREADS) void heavy_dot_kernel(const uint32_t* 
                                                                 const heavy_chunk* __restrict__ chunks, const fe* __restrict__ interner,
                                                                 const fe* __restrict__ x, fe* __restrict__ partials) {
     PK_LATENCY_PRIO();
-    __shared__ uint4 smem[16];
     const heavy_chunk c = chunks[blockIdx.x];
     dot29 d;
     dot29_init(d);
     for (uint32_t k = c.begin + threadIdx.x; k < c.end; k += RED_THREADS) dot29_add(d, unpack29<0>(fe_load(interner + val[k])), unpack29<5>(fe_load(x + idx[k])));
-    wide w[1] = {wide_zero()};
-    wide_add_fe(w[0], dot29_result(d));
-    const fe sum = block_reduce_wide<1>(w, smem);
+    const fe sum = block_sum(dot29_result(d));
     if (threadIdx.x == 0) fe_store(partials + blockIdx.x, sum);
 }
 // one workgroup per heavy line: the sum of its chunks' partials
@@ -96,13 +87,10 @@ __global__ __launch_bounds__(RED_THREADS) void heavy_sum_kernel(const uint32_t* 
                                                                 uint32_t first_slot, uint32_t first_chunk, const fe* __restrict__ partials,
                                                                 fe* __restrict__ heavy_vals) {
     PK_LATENCY_PRIO();
-    __shared__ uint4 smem[16];
     const uint32_t slot = first_slot + blockIdx.x, c0 = slot_chunk0[slot] - first_chunk, n = slot_nchunks[slot];
     fe acc = fe_zero();
     for (uint32_t j = threadIdx.x; j < n; j += RED_THREADS) acc = fe_add(acc, fe_load(partials + c0 + j));
-    wide w[1] = {wide_zero()};
-    wide_add_fe(w[0], acc);
-    const fe sum = block_reduce_wide<1>(w, smem);
+    const fe sum = block_sum(acc);
     if (threadIdx.x == 0) fe_store(heavy_vals + slot, sum);
 }
 
@@ -197,6 +185,40 @@ int heavy_prepare(pk_ctx* ctx, const pk_r1cs* r, unsigned mask, const fe* x, con
 }
 
 }  // namespace
+
+namespace pk {
+// rank `offset` of `stride` ranks: a, b, c for the rows i = j * stride + offset, j < 2^m0 / stride (prover.hip, sharded sumcheck)
+int witness_bounds_strided(pk_ctx* ctx, const pk_r1cs* r, const uint64_t* d_z, unsigned m0, unsigned stride, unsigned offset, uint64_t* d_a,
+                           uint64_t* d_b, uint64_t* d_c) {
+    PK_REQUIRE(ctx, r && d_z && d_a && d_b && d_c, "null pointer");
+    PK_REQUIRE(ctx, m0 <= 30 && r->num_constraints <= ((size_t)1 << m0) && stride && offset < stride, "bad shard of the witness bounds");
+    const size_t padded = ((size_t)1 << m0) / stride;
+    ProfScope prof(ctx, "witness_bounds");
+    const fe* hv = nullptr;  // heavy rows are summed whole on every rank of a sharded sumcheck (they are few)
+    int rc = heavy_prepare(ctx, r, 3u, (const fe*)d_z, &hv);
+    if (rc) return rc;
+    witness_bounds_kernel<<<(unsigned)((padded + 255) / 256), 256, 0, ctx->stream>>>(set_of(r, 0), set_of(r, 1), r->d_interner, hv, (const fe*)d_z,
+                                                                                     r->num_constraints, padded, (fe*)d_a, (fe*)d_b, (fe*)d_c, stride, offset);
+    PK_LAUNCH_CHECK(ctx);
+    return PK_OK;
+}
+// columns [first, last) of the three external rows, written at their absolute positions of d_out (3 x num_witnesses)
+int external_row_range(pk_ctx* ctx, const pk_r1cs* r, const uint64_t* d_eq_alpha, size_t first, size_t last, uint64_t* d_out) {
+    PK_REQUIRE(ctx, r && d_eq_alpha && d_out, "null pointer");
+    if (last > r->num_witnesses) last = r->num_witnesses;
+    if (first >= last) return PK_OK;
+    csc3 m;
+    for (int k = 0; k < 3; k++) m.m[k] = set_of(r, 3 + k);
+    ProfScope prof(ctx, "sparse_matvec");
+    const fe* hv = nullptr;
+    int rc = heavy_prepare(ctx, r, 7u << 3, (const fe*)d_eq_alpha, &hv);
+    if (rc) return rc;
+    sparse_gather3_kernel<<<(unsigned)((last - first + 255) / 256), 256, 0, ctx->stream>>>(m, r->d_interner, hv, (const fe*)d_eq_alpha, r->num_witnesses,
+                                                                                         (fe*)d_out, first, last);
+    PK_LAUNCH_CHECK(ctx);
+    return PK_OK;
+}
+}  // namespace pk
 
 extern "C" {
 
@@ -472,37 +494,3 @@ int pk_r1cs_external_row(pk_ctx* ctx, const pk_r1cs* r, const uint64_t* d_eq_alp
 }
 
 }  // extern "C"
-
-namespace pk {
-// rank `offset` of `stride` ranks: a, b, c for the rows i = j * stride + offset, j < 2^m0 / stride (prover.hip, sharded sumcheck)
-int witness_bounds_strided(pk_ctx* ctx, const pk_r1cs* r, const uint64_t* d_z, unsigned m0, unsigned stride, unsigned offset, uint64_t* d_a,
-                           uint64_t* d_b, uint64_t* d_c) {
-    PK_REQUIRE(ctx, r && d_z && d_a && d_b && d_c, "null pointer");
-    PK_REQUIRE(ctx, m0 <= 30 && r->num_constraints <= ((size_t)1 << m0) && stride && offset < stride, "bad shard of the witness bounds");
-    const size_t padded = ((size_t)1 << m0) / stride;
-    ProfScope prof(ctx, "witness_bounds");
-    const fe* hv = nullptr;  // heavy rows are summed whole on every rank of a sharded sumcheck (they are few)
-    int rc = heavy_prepare(ctx, r, 3u, (const fe*)d_z, &hv);
-    if (rc) return rc;
-    witness_bounds_kernel<<<(unsigned)((padded + 255) / 256), 256, 0, ctx->stream>>>(set_of(r, 0), set_of(r, 1), r->d_interner, hv, (const fe*)d_z,
-                                                                                     r->num_constraints, padded, (fe*)d_a, (fe*)d_b, (fe*)d_c, stride, offset);
-    PK_LAUNCH_CHECK(ctx);
-    return PK_OK;
-}
-// columns [first, last) of the three external rows, written at their absolute positions of d_out (3 x num_witnesses)
-int external_row_range(pk_ctx* ctx, const pk_r1cs* r, const uint64_t* d_eq_alpha, size_t first, size_t last, uint64_t* d_out) {
-    PK_REQUIRE(ctx, r && d_eq_alpha && d_out, "null pointer");
-    if (last > r->num_witnesses) last = r->num_witnesses;
-    if (first >= last) return PK_OK;
-    csc3 m;
-    for (int k = 0; k < 3; k++) m.m[k] = set_of(r, 3 + k);
-    ProfScope prof(ctx, "sparse_matvec");
-    const fe* hv = nullptr;
-    int rc = heavy_prepare(ctx, r, 7u << 3, (const fe*)d_eq_alpha, &hv);
-    if (rc) return rc;
-    sparse_gather3_kernel<<<(unsigned)((last - first + 255) / 256), 256, 0, ctx->stream>>>(m, r->d_interner, hv, (const fe*)d_eq_alpha, r->num_witnesses,
-                                                                                         (fe*)d_out, first, last);
-    PK_LAUNCH_CHECK(ctx);
-    return PK_OK;
-}
-}  // namespace pk

@@ -1,9 +1,10 @@
-// reduce.hpp -- block / grid reduction of field-element sums (used by sumcheck, dot, Horner).
+// reduce.hpp -- block / grid reduction of field-element sums: the grid reductions of mle.hip (sumcheck rounds, dot products,
+// Horner) with their host half, and the one-sum workgroup epilogue of the heavy-line / heavy-sum kernels (r1cs.hip, witness.hip).
 #pragma once
 #include <chrono>
 #include <atomic>
 
-#include "ctx.hpp"
+#include "internal.hpp"
 #include "fe.hpp"
 
 namespace pk {
@@ -72,7 +73,7 @@ __device__ __forceinline__ u64 shfl_down_u64(u64 x, unsigned off) {
 }
 
 // Sum K wide values per thread across the 256-thread block.  Returns the reduced sum number k in thread k (k < K);
-// other threads return garbage.  smem: at least 4*K*8 u64 (the callers' K*256 fe buffer is far larger).
+// other threads return garbage.  smem: at least 4*K*8 u64.
 template <int K>
 __device__ __forceinline__ fe block_reduce_wide(wide (&w)[K], uint4* smem) {
 #pragma unroll
@@ -100,6 +101,14 @@ __device__ __forceinline__ fe block_reduce_wide(wide (&w)[K], uint4* smem) {
     }
     return wide_reduce(t);
 }
+// Sum ONE field element per thread across the 256-thread block: thread 0 returns the sum, fully reduced; the others return garbage.
+// The epilogue of the kernels that give a workgroup one line or one chunk to sum (r1cs.hip heavy lines, witness.hip heavy sums).
+__device__ __forceinline__ fe block_sum(const fe& x) {
+    __shared__ uint4 smem[16];
+    wide w[1] = {wide_zero()};
+    wide_add_fe(w[0], x);
+    return block_reduce_wide<1>(w, smem);
+}
 
 // Single-launch grid reduction: every block stores its K partial sums (write-through, sc1), drains them
 // (`s_waitcnt vmcnt(0)`), takes a ticket, and the block that draws the last ticket sums all partials and writes the K
@@ -123,7 +132,7 @@ __device__ __forceinline__ fe fe_load_sc1(const fe* p) {
 // table (rows padded by one: conflict-free both ways), then 8K x PARTS lanes of the FIRST wavefront each add up one word over
 // 256/PARTS threads (a sum of 256 words fits 40 bits) and thread k collects its 8 limb sums.  The block's other three wavefronts
 // are done after one store per word: ~600 wave-instructions per block for K = 3 where the shuffle tree of 64-bit limb sums
-// (block_reduce_wide, still used by the one-sum kernels) took ~4,800.
+// (block_reduce_wide, which stays behind block_sum) took ~4,800.
 template <int K>
 __device__ __forceinline__ fe block_reduce_fe(const fe (&acc)[K]) {
     constexpr int W = 8 * K;
@@ -163,12 +172,21 @@ __device__ __forceinline__ fe block_reduce_fe(const fe (&acc)[K]) {
     return wide_reduce(t);  // limb sums of 256 values < p
 }
 
+// Where a reducing kernel leaves its K sums: the last kernel argument of every one of them, filled in by reduction_begin.
+struct red_out {
+    fe* partials;      // [workgroup][K] sums, device scratch
+    unsigned* ticket;  // workgroups finished so far; the one that draws the last ticket re-arms it
+    fe* result;        // the K results: the pinned page, or d_xred while the context reduces across ranks
+    unsigned seq;      // published in the pinned page's completion word after the results (never 0)
+};
 template <int K>
-__device__ __forceinline__ void grid_finish_fe(fe (&acc)[K], uint4* smem, fe* __restrict__ partials, unsigned* __restrict__ ticket,
-                                               fe* __restrict__ result, unsigned seq = 0) {
+__device__ __forceinline__ void grid_finish_fe(fe (&acc)[K], const red_out& o) {
     static_assert(K <= 64, "the K results live in the first wavefront");
     __shared__ unsigned s_last;
-    (void)smem;
+    fe* __restrict__ const partials = o.partials;
+    unsigned* __restrict__ const ticket = o.ticket;
+    fe* __restrict__ const result = o.result;
+    const unsigned seq = o.seq;
     fe mine = block_reduce_fe<K>(acc);  // thread k holds sum k
     const unsigned tid = threadIdx.x;
     if (gridDim.x == 1) {  // a single workgroup (the late, tiny rounds): its sums are the results -- no ticket, no second pass
@@ -239,12 +257,21 @@ inline unsigned next_seq(pk_ctx* ctx) {
 // Wait for the kernel and hand the K results -- already in pinned host memory -- to the caller.  (Spinning on the
 // completion word the finishing block publishes was measured: no gain over hipStreamSynchronize single-stream and a
 // loss with several provers per GPU, so the plain synchronisation is kept; the word stays for diagnostics.)
-template <int K>
-inline int collect_reduction(pk_ctx* ctx, uint64_t* host_out) {
+inline int collect_reduction(pk_ctx* ctx, int K, uint64_t* host_out) {
     if (ctx->red_across) return comm_collect_fe(ctx, K, host_out);  // partial sums of a sharded operand: sum over the ranks first
     int rc = sync_stream(ctx);
     if (rc) return rc;
-    memcpy(host_out, ctx->h_pinned, 32 * K);
+    memcpy(host_out, ctx->h_pinned, 32 * (size_t)K);
+    return PK_OK;
+}
+// The K sums of an empty operand, without a launch: zero -- and a sharded context's empty share still takes part in the exchange of
+// the ranks' partial sums.
+inline int reduce_empty(pk_ctx* ctx, int K, uint64_t* host_out) {
+    if (ctx->red_across) {
+        PK_HIP(ctx, hipMemsetAsync(ctx->d_xred, 0, 32 * (size_t)K, ctx->stream));
+        return collect_reduction(ctx, K, host_out);
+    }
+    memset(host_out, 0, 32 * (size_t)K);
     return PK_OK;
 }
 
@@ -353,8 +380,7 @@ inline bool gate_timed_out(pk_ctx* ctx) {
 #define PK_GATE_TIMEOUT_MSG "a gated sumcheck kernel gave up waiting for its challenge (the host thread was stalled for tens of seconds) and ran with a zero challenge: the proof is abandoned"
 // wait for the reduction launched with sequence number `seq` WITHOUT draining the stream (a gated kernel may already sit behind it):
 // spin on the completion word its finishing workgroup publishes after the K results
-template <int K>
-inline int collect_reduction_spin(pk_ctx* ctx, unsigned seq, uint64_t* host_out) {
+inline int collect_reduction_spin(pk_ctx* ctx, int K, unsigned seq, uint64_t* host_out) {
     const unsigned* flag = (const unsigned*)ctx->h_pinned + PK_FLAG_WORD;
     const auto t0 = std::chrono::steady_clock::now();
     unsigned polls = 0;
@@ -363,7 +389,7 @@ inline int collect_reduction_spin(pk_ctx* ctx, unsigned seq, uint64_t* host_out)
             return set_err(ctx, PK_ERR_HIP, "a gated reduction did not complete within 10 s");
     }
     if (gate_timed_out(ctx)) return set_err(ctx, PK_ERR_HIP, "%s", PK_GATE_TIMEOUT_MSG);
-    memcpy(host_out, ctx->h_pinned, 32 * K);
+    memcpy(host_out, ctx->h_pinned, 32 * (size_t)K);
     return PK_OK;
 }
 
@@ -379,6 +405,16 @@ inline unsigned reduction_blocks(const pk_ctx* ctx, size_t work_items) {
     if (cap > RED_MAX_BLOCKS) cap = RED_MAX_BLOCKS;
     if (need < 1) need = 1;
     return (unsigned)(need < cap ? need : cap);
+}
+// The host half of every reduction launch: the scratch and the pinned page exist, `*out` is the kernel's last argument (with the
+// next sequence number) and `*blocks` the grid for `work_items` items at reduction_blocks' items per thread.  Then: launch,
+// PK_LAUNCH_CHECK, collect_reduction (or collect_reduction_spin on out->seq).
+inline int reduction_begin(pk_ctx* ctx, size_t work_items, red_out* out, unsigned* blocks) {
+    int rc = reduction_scratch(ctx);
+    if (rc) return rc;
+    *blocks = reduction_blocks(ctx, work_items);
+    *out = red_out{red_partials(ctx), red_ticket(ctx), red_result(ctx), next_seq(ctx)};
+    return PK_OK;
 }
 
 }  // namespace pk

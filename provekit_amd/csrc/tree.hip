@@ -14,7 +14,7 @@
 
 // memory- / latency-bound kernels: their wavefronts issue ahead of the ALU-bound hash / NTT / grinder kernels they share SIMDs with
 #define PK_BASE_PRIO 2
-#include "ctx.hpp"
+#include "internal.hpp"
 #include "shard_map.hpp"
 #include "skyscraper29s.hpp"
 
@@ -32,16 +32,6 @@ struct pk_tree {
     // Montgomery images: the leaf hash consumes it without conversion, openings convert the ~100 opened rows
     bool scaled = false;
 };
-
-namespace pk {
-int rs_encode_x(pk_ctx* ctx, const uint64_t* const* d_coeffs, unsigned batch, unsigned n_vars, unsigned log_inv_rate, unsigned fold,
-                uint64_t* d_leaves, uint64_t* d_scratch, bool scaled);
-int rs_encode_shard_x(pk_ctx* ctx, const uint64_t* const* d_coeffs, unsigned batch, unsigned n_vars, unsigned log_inv_rate, unsigned fold,
-                      unsigned shard, unsigned n_shards, uint64_t* d_leaves_local, uint64_t* d_scratch, bool scaled);
-int leaf_hash_x(pk_ctx* ctx, const uint64_t* d_leaves, size_t n_leaves, size_t width, uint64_t* d_digests, bool scaled_in);
-int merkle_top_x(pk_ctx* ctx, uint64_t* d_nodes, size_t top_leaves);  // hash.hip: the levels above heap slots [top_leaves, 2 top_leaves)
-bool ntt_scaled_available(unsigned log_n);
-}
 
 namespace {
 

@@ -27,7 +27,7 @@
 #include <vector>
 
 #define PK_BASE_PRIO 2
-#include "ctx.hpp"
+#include "internal.hpp"
 #include "fe29.hpp"
 #include "feinv.hpp"
 #include "reduce.hpp"
@@ -269,7 +269,6 @@ struct HeavySum {
 __global__ __launch_bounds__(RED_THREADS) void heavy_sum_part_kernel(const SumChunk* __restrict__ chunks, const u32* __restrict__ extra, const fe* __restrict__ W,
                                                                      const fe* __restrict__ K, fe* __restrict__ partials) {
     PK_LATENCY_PRIO();
-    __shared__ uint4 smem[16];
     const SumChunk c = chunks[blockIdx.x];
     fe acc = fe_zero();
     for (u32 t = c.begin + threadIdx.x; t < c.end; t += RED_THREADS) {
@@ -277,21 +276,16 @@ __global__ __launch_bounds__(RED_THREADS) void heavy_sum_part_kernel(const SumCh
         if (extra[2 * t] != NONE) x = fe_mulx(fe_load(K + extra[2 * t]), x);
         acc = fe_add(acc, x);
     }
-    wide w[1] = {wide_zero()};
-    wide_add_fe(w[0], acc);
-    const fe sum = block_reduce_wide<1>(w, smem);
+    const fe sum = block_sum(acc);
     if (threadIdx.x == 0) fe_store(partials + blockIdx.x, sum);
 }
 __global__ __launch_bounds__(RED_THREADS) void heavy_sum_final_kernel(const HeavySum* __restrict__ sums, const fe* __restrict__ partials, u32 chunk_base,
                                                                       fe* __restrict__ W, unsigned char* __restrict__ is_set) {
     PK_LATENCY_PRIO();
-    __shared__ uint4 smem[16];
     const HeavySum hs = sums[blockIdx.x];
     fe acc = fe_zero();
     for (u32 j = threadIdx.x; j < hs.n_chunks; j += RED_THREADS) acc = fe_add(acc, fe_load(partials + (hs.chunk0 - chunk_base) + j));
-    wide w[1] = {wide_zero()};
-    wide_add_fe(w[0], acc);
-    const fe sum = block_reduce_wide<1>(w, smem);
+    const fe sum = block_sum(acc);
     if (threadIdx.x == 0) {
         fe_store(W + hs.out, sum);
         is_set[hs.out] = 1;
