@@ -799,7 +799,7 @@ u64 pko_pow_solve(const u64 challenge[4], double difficulty) { /* pow.rs:33-41; 
 /* The proof's random draws.  The reference takes the ZK mask, the random polynomial g and the blinding univariates from
  * rand's thread_rng (provekit/common/src/utils/zk_utils.rs:13-22, provekit/prover/src/whir_r1cs.rs:197,212-221): ChaCha12 under
  * an OS-seeded key -- nothing to be bit-exact with.  The HIP library expands ONE 256-bit key per proof with the same cipher
- * (csrc/prover.hip random_fe_kernel); with an injected key its draws are reproducible, and this is their restatement: elements
+ * (csrc/rng.hip random_fe_kernel); with an injected key its draws are reproducible, and this is their restatement: elements
  * 2j and 2j+1 of draw `stream` come from the ChaCha12 blocks (counter = j, nonce = {stream, attempt}), attempt = 0, 1, ...:
  * words 0..7 / 8..15 masked to 254 bits, accepted iff < p (ark-ff Fp::rand's rejection), stored as they are (a uniform
  * Montgomery image is a uniform element). */

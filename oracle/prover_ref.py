@@ -41,7 +41,7 @@ L.pko_pow_solve.argtypes = [C.c_void_p, C.c_double]
 L.pko_random_fe.argtypes = [C.c_char_p, C.c_uint32, C.c_void_p, C.c_size_t]
 L.pko_gather_rows_canonical.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]
 
-RNG_MASK, RNG_G, RNG_BLIND, RNG_MASK_B, RNG_G_B = 1, 2, 3, 4, 5  # the `stream` word of a draw (csrc/prover.hip)
+RNG_MASK, RNG_G, RNG_BLIND, RNG_MASK_B, RNG_G_B = 1, 2, 3, 4, 5  # the `stream` word of a draw (csrc/internal.hpp, rng.hip)
 
 
 from hostcores import usable_cores  # noqa: E402

@@ -102,7 +102,25 @@ int witness_bounds_strided(pk_ctx* ctx, const pk_r1cs* r, const uint64_t* d_z, u
 // columns [first, last) of the three external rows, written at their absolute positions of d_out (3 x num_witnesses)
 int external_row_range(pk_ctx* ctx, const pk_r1cs* r, const uint64_t* d_eq_alpha, size_t first, size_t last, uint64_t* d_out);
 
+// ---- rng.hip: the proof RNG ---------------------------------------------------------------------------------------------------
+struct RngKey {
+    uint32_t k[8];
+};
+enum { RNG_MASK = 1, RNG_G = 2, RNG_BLIND = 3, RNG_MASK_B = 4, RNG_G_B = 5, RNG_FILL = 6 };  // draws of one proof (the `stream` word of the nonce)
+int proof_key(pk_ctx* ctx, const uint8_t* rng_seed32, RngKey& key);  // fresh from the OS unless injected; the same on every rank of a device set
+int random_fe(pk_ctx* ctx, uint64_t* d_out, size_t n, const RngKey& key, uint32_t stream);  // launch only
+
 // ---- witness.hip --------------------------------------------------------------------------------------------------------------
 void witness_program_shape(const pk_witness_program* p, size_t* n_witnesses, size_t* n_challenges, size_t* n_acir);
+
+// ---- whir_config.hip: the scheme's shape (host only) --------------------------------------------------------------------------
+const char* whir_config_error(const pk_whir_config* c);  // nullptr if this prover runs `c`, else why not
+unsigned blinding_log_len(unsigned m_0);                 // the blinding polynomial's variables less one
+size_t scheme_arena_bytes(unsigned m, unsigned m_0, size_t num_witnesses, const pk_whir_config& w);
+std::string whir_r1cs_io_pattern(unsigned m_0, const pk_whir_config& w, const pk_whir_config& h);
+std::string witness_io_pattern(size_t n_public, size_t n_challenges);
+// "" if the caller's IO-pattern bytes declare the operations pk_prove performs for (m_0, w, h), else the first difference
+std::string io_pattern_mismatch(const std::string& theirs, unsigned m_0, const pk_whir_config& w, const pk_whir_config& h);
+void copy_out(const std::string& s, void* buf, size_t cap, size_t* len);  // *len = size; copied where it fits
 
 }  // namespace pk

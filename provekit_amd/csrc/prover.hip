@@ -10,12 +10,14 @@
 //    +- prove_blinding: small WHIR proof of the blinding polynomial
 //    +- witness_statement: external rows, weighted sums, claimed_evaluations hint (whir_r1cs.rs:81-91)
 //    +- prove_witness: whir_prove (whir::Prover::prove; structure pinned by recursive-verifier/app/circuit/whir.go:51-220)
-#include <sys/random.h>
+//
+// In this file: the sharding helpers of one proof over a device set, the blinding algebra, the WHIR prover, the stages of pk_prove,
+// and the entry points that share pk_scheme (create / destroy, pk_prove, pk_noir_prove, the scheme's IO pattern).  Elsewhere, reached
+// through internal.hpp: the proof RNG and the random draws (rng.hip); the scheme's shape -- config validation and derivation, the
+// arena size, the IO patterns -- which needs no device (whir_config.hip).
 #include <unistd.h>
 
 #include <algorithm>
-#include <cerrno>
-#include <cmath>
 #include <chrono>
 #include <cstdlib>
 #include <string>
@@ -41,94 +43,6 @@ struct pk_scheme {
 };
 
 namespace {
-
-// ------------------------------------------------------------------ device CSPRNG
-// The reference draws the ZK mask, the random polynomial g and the Spartan blinding univariates from thread_rng
-// (provekit/common/src/utils/zk_utils.rs:13-22, provekit/prover/src/whir_r1cs.rs:197,212-221): rand's ThreadRng, i.e. ChaCha12
-// seeded from the OS.  Here: one 256-bit key per proof (getrandom(2) inside pk_prove unless the caller injects a seed -- a test
-// hook), expanded on the device with the same cipher -- the ChaCha block function (RFC 8439 quarter rounds and state layout),
-// 12 rounds.  Elements 2j and 2j+1 of draw `stream` share the blocks (counter = j, nonce = {stream, attempt}): a block holds
-// two 254-bit candidates, the first for element 2j, the second for 2j+1, each accepted iff < p (what ark-ff's Fp::rand does,
-// so every element is uniform on [0, p)); an element whose candidate was rejected takes its candidate of the next attempt.
-struct RngKey {
-    u32 k[8];
-};
-constexpr int PK_RNG_ROUNDS = 12;
-#define PK_QR(a, b, c, d)                    \
-    a += b; d ^= a; d = (d << 16) | (d >> 16); \
-    c += d; b ^= c; b = (b << 12) | (b >> 20); \
-    a += b; d ^= a; d = (d << 8) | (d >> 24);  \
-    c += d; b ^= c; b = (b << 7) | (b >> 25)
-__host__ __device__ __forceinline__ void chacha_block(const RngKey& key, u64 counter, u32 n0, u32 n1, int rounds, u32 (&out)[16]) {
-    u32 s[16] = {0x61707865u, 0x3320646eu, 0x79622d32u, 0x6b206574u, key.k[0], key.k[1], key.k[2], key.k[3],
-                 key.k[4],    key.k[5],    key.k[6],    key.k[7],    (u32)counter, (u32)(counter >> 32), n0, n1};
-    u32 x[16];
-#pragma unroll
-    for (int i = 0; i < 16; i++) x[i] = s[i];
-#pragma unroll 1
-    for (int r = 0; r < rounds / 2; r++) {
-        PK_QR(x[0], x[4], x[8], x[12]);
-        PK_QR(x[1], x[5], x[9], x[13]);
-        PK_QR(x[2], x[6], x[10], x[14]);
-        PK_QR(x[3], x[7], x[11], x[15]);
-        PK_QR(x[0], x[5], x[10], x[15]);
-        PK_QR(x[1], x[6], x[11], x[12]);
-        PK_QR(x[2], x[7], x[8], x[13]);
-        PK_QR(x[3], x[4], x[9], x[14]);
-    }
-#pragma unroll
-    for (int i = 0; i < 16; i++) out[i] = x[i] + s[i];
-}
-#undef PK_QR
-// A lane walks its pairs j = g, g + stride, ... as a state machine (pair, attempt): one ChaCha block per loop iteration, whichever pair and
-// attempt the lane is at.  (Until round 5 the retry loop sat INSIDE the loop over pairs, so a wavefront repeated a pair's block until its
-// unluckiest lane -- 128 candidates, each rejected with probability 0.244 -- was done: ~4 blocks per pair instead of the 1.43 a lane needs.
-// Now the waiting averages out over a lane's pairs: launched with ~8 pairs per lane, a wavefront runs ~17 blocks for 8 pairs.)
-__global__ __launch_bounds__(256) void random_fe_kernel(fe* __restrict__ out, size_t n, RngKey key, u32 stream) {
-    PK_LATENCY_PRIO();
-    const size_t stride = (size_t)gridDim.x * blockDim.x, pairs = (n + 1) / 2;
-    size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    u32 attempt = 0;
-    bool done0 = false, done1 = 2 * j + 1 >= n;
-    while (j < pairs) {
-        u32 blk[16];
-        chacha_block(key, (u64)j, stream, attempt, PK_RNG_ROUNDS, blk);
-#pragma unroll
-        for (int half = 0; half < 2; half++) {
-            if (half == 0 ? done0 : done1) continue;
-            fe x;
-#pragma unroll
-            for (int w = 0; w < 8; w++) x.v[w] = blk[8 * half + w];
-            x.v[7] &= 0x3fffffffu;  // < 2^254
-            u32 borrow = 0;
-#pragma unroll
-            for (int k = 0; k < 8; k++) (void)__builtin_subc(x.v[k], kPlimb(k), borrow, &borrow);
-            if (borrow) {  // x < p: accepted
-                fe_store(out + 2 * j + half, x);
-                if (half == 0) done0 = true;
-                else done1 = true;
-            }
-        }
-        if (done0 && done1) {
-            j += stride;
-            attempt = 0;
-            done0 = false;
-            done1 = 2 * j + 1 >= n;
-        } else {
-            attempt++;
-        }
-    }
-}
-// ~8 pairs per lane (see the kernel), at least one wavefront per SIMD's worth of workgroups when the draw is long enough
-inline unsigned random_fe_grid(const pk_ctx* ctx, size_t n) {
-    const size_t pairs = (n + 1) / 2;
-    size_t blocks = (pairs + 256 * 8 - 1) / (256 * 8);
-    const size_t cap = (size_t)ctx->num_cus * 8;
-    if (blocks < 1) blocks = 1;
-    return (unsigned)(blocks < cap ? blocks : cap);
-}
-// draws of one proof (the `stream` word of the nonce)
-enum { RNG_MASK = 1, RNG_G = 2, RNG_BLIND = 3, RNG_MASK_B = 4, RNG_G_B = 5, RNG_FILL = 6 };
 
 // latency mode: a gated kernel is in the queue waiting for a challenge; whatever path leaves the scope, it must be released
 // (with a zero challenge on an error path: the proof is abandoned anyway) so that the stream can drain
@@ -509,37 +423,35 @@ struct WhirProver {
     int sumcheck_rounds(unsigned rounds) {
         rs.clear();
         const bool pipelined = ctx->latency_mode && G == 1 && rounds && len >= ((size_t)1 << rounds);
-        Across ac(ctx, sharded);
-        CK(ac.rc);
         unsigned red_cur = 0, red_next = 0;
         if (pipelined) CK(sumcheck_quadratic_launch(ctx, U(bp[cur]), U(bw[cur]), len, nullptr, 0, nullptr, nullptr, &red_cur));
-        for (unsigned t = 0; t < rounds; t++) {
+        for (unsigned t = 0; t < rounds; t++) {  // the same steps in the same order as Proof::zk_rounds
             PendingGate gate(ctx);
-            uint64_t out[12], f[4];
-            if (pipelined) {
-                // what consumes this round's challenge: the next round (folding first), or the closing fold
-                const bool more = t + 1 < rounds;
-                if (more || len >= 2) {
-                    gate.arm(sumcheck_gate_next(ctx));
-                    if (more) CK(sumcheck_quadratic_launch(ctx, U(bp[cur]), U(bw[cur]), len, nullptr, gate.seq, U(bp[1 - cur]), U(bw[1 - cur]), &red_next));
-                    else CK(fold_pairs2(ctx, U(bp[cur]), U(bp[1 - cur]), U(bw[cur]), U(bw[1 - cur]), len, nullptr, gate.seq));
-                    flip();
-                }
-                CK(sumcheck_collect_spin(ctx, red_cur, out));
-                red_cur = red_next;
-            } else if (t == 0) {
-                CK(pk_sumcheck_quadratic_round(ctx, U(bp[cur]), U(bw[cur]), len, nullptr, nullptr, nullptr, out));
-            } else {
-                h_store(f, rs.back());
-                CK(pk_sumcheck_quadratic_round(ctx, U(bp[cur]), U(bw[cur]), len, f, U(bp[1 - cur]), U(bw[1 - cur]), out));
+            // pipelined: what consumes this round's challenge -- the next round (folding first), or the closing fold -- goes into the queue, gated
+            const bool more = t + 1 < rounds;
+            if (pipelined && (more || len >= 2)) {
+                gate.arm(sumcheck_gate_next(ctx));
+                if (more) CK(sumcheck_quadratic_launch(ctx, U(bp[cur]), U(bw[cur]), len, nullptr, gate.seq, U(bp[1 - cur]), U(bw[1 - cur]), &red_next));
+                else CK(fold_pairs2(ctx, U(bp[cur]), U(bp[1 - cur]), U(bw[cur]), U(bw[1 - cur]), len, nullptr, gate.seq));
                 flip();
             }
-            const fe h[3] = {h_load(out), h_load(out + 4), h_load(out + 8)};
-            T.add_scalars(h, 3);
-            const fe fold = T.challenge_scalar();
-            gate.publish(fold);
-            rs.push_back(fold);
-            all_r.push_back(fold);
+            uint64_t out[12], f[4];
+            if (pipelined) {
+                CK(sumcheck_collect_spin(ctx, red_cur, out));
+                red_cur = red_next;
+            } else {
+                Across ac(ctx, sharded);  // sharded: h(0), h(1), h(2) are sums over the ranks' blocks
+                CK(ac.rc);
+                if (t) h_store(f, rs.back());
+                CK(pk_sumcheck_quadratic_round(ctx, U(bp[cur]), U(bw[cur]), len, t ? f : nullptr, U(bp[1 - cur]), U(bw[1 - cur]), out));  // round 0 folds nothing, writes nothing
+                if (t) flip();
+            }
+            const fe msg[3] = {h_load(out), h_load(out + 4), h_load(out + 8)};
+            T.add_scalars(msg, 3);
+            const fe r = T.challenge_scalar();
+            gate.publish(r);
+            rs.push_back(r);
+            all_r.push_back(r);
         }
         if (!pipelined && rounds && len >= 2) {  // apply the last challenge: p, w now describe the folded polynomial
             uint64_t f[4];
@@ -743,10 +655,9 @@ int batch_commit_compute(pk_ctx* ctx, Arena& A, unsigned m, const pk_whir_config
     CK(pk_memcpy_d2d(ctx, f, d_evals, 32 * n_evals));
     {
         ProfScope prof(ctx, "random_fe");
-        random_fe_kernel<<<random_fe_grid(ctx, half), 256, 0, ctx->stream>>>(f + half, half, key, stream_mask);
-        random_fe_kernel<<<random_fe_grid(ctx, N), 256, 0, ctx->stream>>>(g, N, key, stream_g);
+        CK(random_fe(ctx, U(f + half), half, key, stream_mask));
+        CK(random_fe(ctx, U(g), N, key, stream_g));
     }
-    PK_LAUNCH_CHECK(ctx);
     // f, g hold the evaluation forms (kept for the weighted sums); the coefficient forms go to fc, gc
     CK(pk_to_coeffs_into(ctx, U(f), U(fe_), m));
     CK(pk_to_coeffs_into(ctx, U(g), U(ge_), m));
@@ -759,185 +670,10 @@ int batch_commit_compute(pk_ctx* ctx, Arena& A, unsigned m, const pk_whir_config
     return rc;
 }
 
-// 256-bit key of one proof's random draws: fresh from the OS CSPRNG (the reference's thread_rng) unless injected.  One proof
-// sharded over a device set: every rank must mask with the SAME polynomials -- rank 0's key goes to everybody.
-int proof_key(pk_ctx* ctx, const uint8_t* rng_seed32, RngKey& key) {
-    if (rng_seed32) {
-        memcpy(key.k, rng_seed32, 32);
-        return PK_OK;
-    }
-    size_t got = 0;
-    while (got < 32) {
-        ssize_t r = getrandom((char*)key.k + got, 32 - got, 0);
-        if (r < 0) {
-            if (errno == EINTR) continue;
-            return set_err(ctx, PK_ERR_HIP, "getrandom failed: %s", strerror(errno));
-        }
-        got += (size_t)r;
-    }
-    if (comm_world(ctx) > 1) {
-        int rc = ensure_scratch(ctx, ((size_t)1 << 19) + 32 * (size_t)(PK_MAX_RANKS + 1));
-        if (rc) return rc;
-        char* d_key = (char*)ctx->d_scratch + ((size_t)1 << 19);  // clear of the reduction area (head) and the PoW words (tail)
-        PK_HIP(ctx, hipMemcpyAsync(d_key, key.k, 32, hipMemcpyHostToDevice, ctx->stream));
-        rc = comm_all_gather(ctx, d_key, d_key + 32, 32);
-        if (rc) return rc;
-        PK_HIP(ctx, hipMemcpyAsync(key.k, d_key + 32, 32, hipMemcpyDeviceToHost, ctx->stream));
-        PK_WAIT(ctx);
-    }
-    return PK_OK;
-}
-
-// fill_witness (provekit/prover/src/witness/mod.rs:15-30): every None entry takes FieldElement::from(rng.random::<u128>()).
-// Entry i reads the (i mod 4)-th 128-bit word of ChaCha block i / 4 of stream RNG_FILL, so the result does not depend on the
-// launch shape.  *n_filled counts them (the reference logs the count).
-__global__ __launch_bounds__(256) void fill_witness_kernel(fe* __restrict__ w, const uint8_t* __restrict__ is_set, size_t n, RngKey key, u32 stream,
-                                                           unsigned long long* n_filled) {
-    PK_LATENCY_PRIO();
-    const size_t stride = (size_t)gridDim.x * blockDim.x;
-    unsigned mine = 0;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        if (is_set[i]) continue;
-        u32 blk[16];
-        chacha_block(key, (u64)(i >> 2), stream, 0, PK_RNG_ROUNDS, blk);
-        fe x = fe_zero();
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            u32 v = 0;
-#pragma unroll
-            for (int q = 0; q < 4; q++) v = (i & 3) == (size_t)q ? blk[4 * q + k] : v;
-            x.v[k] = v;
-        }
-        fe_store(w + i, fe_to_montx(x));
-        mine++;
-    }
-    if (mine) atomicAdd(n_filled, (unsigned long long)mine);  // n_filled is DEVICE memory: agent-scope atomics are exact there
-}
-
 // public inputs of the witness transcript: the ACIR witness values at the circuit's public indices
 __global__ void gather_fe_kernel(const fe* __restrict__ src, const uint32_t* __restrict__ idx, size_t n, fe* __restrict__ dst) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) fe_store(dst + i, fe_load(src + idx[i]));
-}
-
-// create_witness_io_pattern (provekit/prover/src/noir_proof_scheme.rs:94-109) with witness_io_pattern.rs:18-41: the spongefish
-// op list "<domain>\0A2shape[\0A<n>pub_inputs][\0S<n>wb:challenges]"
-std::string witness_io_pattern(size_t n_public, size_t n_challenges) {
-    std::string d = "\xF0\x9F\x93\x9C";  // "📜"
-    d.push_back('\0');
-    d += "A2shape";
-    if (n_public) {
-        d.push_back('\0');
-        d += "A" + std::to_string(n_public) + "pub_inputs";
-    }
-    if (n_challenges) {
-        d.push_back('\0');
-        d += "S" + std::to_string(n_challenges) + "wb:challenges";
-    }
-    return d;
-}
-
-// WhirR1CSScheme::create_io_pattern (provekit/common/src/whir_r1cs.rs:28-39) restated:
-//   IOPattern::new("🌪️").commit_statement(w).add_rand(m_0).commit_statement(b).add_zk_sumcheck_polynomials(m_0)
-//            .add_whir_proof(b).hint("claimed_evaluations").add_whir_proof(w)
-// provekit's own labels (utils/sumcheck.rs:119-142) are in the tree.  commit_statement / add_whir_proof live in whir @3e7f8c2
-// (absent): their OPERATIONS are pinned by the in-tree Go verifier's read order (mtUtilities.go:51-76, whir.go:51-220) and the
-// labels "stir_answers", "merkle_proof", "deferred_weight_evaluations", "pow-nonce" by its pattern walker (common.go:41-100);
-// the remaining labels are whir's / spongefish-pow's as published (merkle_digest, ood_query, ood_ans, sumcheck_poly,
-// folding_randomness, combination_randomness, pow_queries, stir_queries, final_coeffs, final_queries) -- UNPINNED here, which is
-// why a caller that holds the reference's bytes overrides this string (pk_scheme_set_io_pattern).  Zero-count operations are
-// omitted exactly where whir guards them (no OOD samples, no grinding).
-std::string whir_r1cs_io_pattern(unsigned m_0, const pk_whir_config& w, const pk_whir_config& h) {
-    std::string d = "\xF0\x9F\x8C\xAA\xEF\xB8\x8F";  // "🌪️"
-    auto op = [&](char kind, size_t count, const char* label) {
-        d.push_back('\0');
-        d.push_back(kind);
-        if (kind == 'A' || kind == 'S') d += std::to_string(count);
-        d += label;
-    };
-    auto A = [&](size_t n, const char* l) { if (n) op('A', n, l); };
-    auto S = [&](size_t n, const char* l) { if (n) op('S', n, l); };
-    auto challenge_bytes = [&](size_t n, const char* l) { S((n + 14) / 15, l); };  // 15 uniform bytes per squeezed element
-    auto pow = [&](double bits) {  // spongefish-pow challenge_pow: 32 challenge bytes, 8-byte nonce
-        if (bits > 0.0) {
-            challenge_bytes(32, "pow_queries");
-            A(8, "pow-nonce");
-        }
-    };
-    auto add_ood = [&](size_t samples, size_t batch) {
-        S(samples, "ood_query");
-        A(samples * batch, "ood_ans");
-    };
-    auto add_sumcheck = [&](unsigned rounds) {
-        for (unsigned i = 0; i < rounds; i++) {
-            A(3, "sumcheck_poly");
-            S(1, "folding_randomness");
-        }
-    };
-    auto commit_statement = [&](const pk_whir_config& c) {
-        A(1, "merkle_digest");
-        add_ood(c.commitment_ood_samples, c.batch_size);
-        if (c.batch_size > 1) S(1, "batching_randomness");  // drawn right after the commitment (mtUtilities.go:71-75)
-    };
-    auto query_bytes = [](size_t domain, unsigned fold) {
-        const size_t folded = domain >> fold;
-        return (size_t)((ilog2(folded) + 7) / 8);
-    };
-    auto add_whir_proof = [&](const pk_whir_config& c) {
-        const unsigned k = c.folding_factor;
-        S(1, "initial_combination_randomness");
-        add_sumcheck(k);
-        size_t domain = (size_t)1 << (c.n_vars + c.starting_log_inv_rate);
-        for (unsigned r = 0; r < c.n_rounds; r++) {
-            A(1, "merkle_digest");
-            add_ood(c.ood_samples[r], 1);
-            pow(c.pow_bits[r]);
-            challenge_bytes((size_t)c.num_queries[r] * query_bytes(domain, k), "stir_queries");
-            op('H', 0, "stir_answers");
-            op('H', 0, "merkle_proof");
-            S(1, "combination_randomness");
-            add_sumcheck(k);
-            domain >>= 1;
-        }
-        const unsigned final_vars = c.n_vars - k * (c.n_rounds + 1);
-        A((size_t)1 << final_vars, "final_coeffs");
-        pow(c.final_pow_bits);
-        challenge_bytes((size_t)c.final_queries * query_bytes(domain, k), "final_queries");
-        op('H', 0, "stir_answers");
-        op('H', 0, "merkle_proof");
-        add_sumcheck(final_vars);
-        pow(c.final_folding_pow_bits);  // once, after the last round (whir.go:196-201)
-        op('H', 0, "deferred_weight_evaluations");
-    };
-    commit_statement(w);
-    S(m_0, "rand");
-    commit_statement(h);
-    A(1, "Sum of G over boolean hypercube");
-    S(1, "Rho");
-    for (unsigned i = 0; i < m_0; i++) {
-        A(4, "Sumcheck Polynomials");
-        S(1, "Sumcheck Random");
-    }
-    A(2, "Polynomial sums");
-    add_whir_proof(h);
-    op('H', 0, "claimed_evaluations");
-    add_whir_proof(w);
-    return d;
-}
-
-// do the caller's IO-pattern bytes declare the operations pk_prove performs for (m_0, w, h)?  "" = yes, else the first difference
-std::string io_pattern_mismatch(const std::string& theirs, unsigned m_0, const pk_whir_config& w, const pk_whir_config& h) {
-    std::vector<IoOp> a, b;
-    std::string err;
-    if (!io_pattern_parse(theirs, a, err)) return err;
-    if (!io_pattern_parse(whir_r1cs_io_pattern(m_0, w, h), b, err)) return "internal: " + err;
-    auto name = [](const IoOp& o) { return std::string(1, o.kind) + (o.kind == 'A' || o.kind == 'S' ? std::to_string(o.count) : std::string()); };
-    for (size_t i = 0; i < a.size() && i < b.size(); i++)
-        if (a[i].kind != b[i].kind || a[i].count != b[i].count)
-            return "IO pattern operation #" + std::to_string(i + 1) + " (after merging) is " + name(a[i]) + " but this scheme's prover performs " + name(b[i]);
-    if (a.size() != b.size())
-        return "IO pattern declares " + std::to_string(a.size()) + " operations (after merging), this scheme's prover performs " + std::to_string(b.size());
-    return "";
 }
 
 // One proof over a device set: a rank that leaves early (arena exhausted, a HIP error, an unsatisfied witness on this rank only)
@@ -968,23 +704,6 @@ struct AbortOnFailure {
         comm_abort(c);
     }
 };
-
-// the WHIR configs this prover runs: nullptr if `c` is one, else why not.  pk_scheme_create refuses the rest, and so does every
-// host-only entry point that takes a config.
-const char* whir_config_error(const pk_whir_config* c) {
-    if (!c) return "null pointer";
-    if (c->folding_factor < 1 || c->folding_factor > 8 || c->n_rounds > PK_MAX_WHIR_ROUNDS) return "bad WHIR config";
-    if (c->n_vars < c->folding_factor * (c->n_rounds + 1)) return "WHIR rounds exceed the number of variables";
-    if (c->commitment_ood_samples > 4) return "too many OOD samples";
-    if (c->batch_size < 1 || c->batch_size > 4) return "batch size out of range";
-    // the evaluation domain must exist in BN254-Fr (two-adicity 28) and the codeword must fit pk_rs_encode's bound
-    if (c->starting_log_inv_rate < 1 || c->starting_log_inv_rate > 28 || c->n_vars > 28 - c->starting_log_inv_rate)
-        return "n_vars + starting_log_inv_rate exceeds 28";
-    if (c->n_vars + c->starting_log_inv_rate - c->folding_factor > 27) return "codeword has more than 2^27 rows";
-    for (unsigned r = 0; r < c->n_rounds; r++)
-        if (c->ood_samples[r] > 4) return "too many OOD samples";
-    return nullptr;
-}
 
 // latency mode, one GPU: the scheme's second context (a stream and workspace of its own on the same device, created on first use)
 // runs the work that can overlap -- the blinding commitment underneath the witness commitment, the external rows underneath the
@@ -1062,7 +781,7 @@ struct Proof {
     int commit_witness();
     int blinding_transcript();
     int zk_sumcheck();
-    int zk_rounds(fe* z[4], size_t length, bool sharded);
+    int zk_rounds(fe* z[4], size_t len, bool sharded);
     int prove_blinding();
     int witness_statement();
     int prove_witness();
@@ -1075,8 +794,7 @@ int blinding_compute(pk_ctx* ctx, Proof& P) {
     const size_t NB = (size_t)1 << P.s->nb, n = P.g_univ.size();
     ALLOC(d_blind, NB);
     CK(pk_memset_zero(ctx, d_blind, 32 * NB));
-    random_fe_kernel<<<1, 256, 0, ctx->stream>>>(d_blind, n, P.key, RNG_BLIND);
-    PK_LAUNCH_CHECK(ctx);
+    CK(random_fe(ctx, U(d_blind), n, P.key, RNG_BLIND));  // n = 4 m_0 <= 108: one workgroup
     if (ctx == P.ctx) {
         CK(pk_memcpy_d2h(ctx, P.g_univ.data(), d_blind, 32 * n));
     } else {
@@ -1164,10 +882,10 @@ int Proof::zk_sumcheck() {
     return zk_rounds(z, length, sharded);
 }
 
-// the m_0 cubic rounds, each: the round's evaluations, the message, absorb, squeeze, record.  Latency mode (one GPU): round idx+1 is
-// in the queue, gated on a_idx, while round idx is absorbed.  Otherwise every round is a synchronous call that first folds by the
+// the m_0 cubic rounds, each: the round's evaluations, the message, absorb, squeeze, record.  Latency mode (one GPU): round t+1 is
+// in the queue, gated on a_t, while round t is absorbed.  Otherwise every round is a synchronous call that first folds by the
 // previous challenge (sharded: its evaluations are sums over the ranks' shares; short shares are gathered and finish replicated).
-int Proof::zk_rounds(fe* z[4], size_t length, bool sharded) {
+int Proof::zk_rounds(fe* z[4], size_t len, bool sharded) {
     const unsigned m_0 = s->m_0;
     // sum_over_hypercube (whir_r1cs.rs:172-180)
     fe gp[4];
@@ -1189,43 +907,45 @@ int Proof::zk_rounds(fe* z[4], size_t length, bool sharded) {
     }
     const bool pipelined = ctx->latency_mode && G == 1 && m_0 >= 2;
     unsigned red_cur = 0, red_next = 0;
-    if (pipelined) CK(sumcheck_cubic_launch(ctx, U(z[0]), U(z[1]), U(z[2]), U(z[3]), length, nullptr, 0, &red_cur));
+    if (pipelined) CK(sumcheck_cubic_launch(ctx, U(z[0]), U(z[1]), U(z[2]), U(z[3]), len, nullptr, 0, &red_cur));
     alpha.reserve(m_0);
-    for (unsigned idx = 0; idx < m_0; idx++) {  // the hot loop, whir_r1cs.rs:280-345
+    for (unsigned t = 0; t < m_0; t++) {  // the hot loop, whir_r1cs.rs:280-345; the same steps in the same order as WhirProver::sumcheck_rounds
         PendingGate gate(ctx);
-        if (pipelined && idx + 1 < m_0) {
+        // pipelined: what consumes this round's challenge -- the next round (folding first, in place); there is no closing fold -- goes into the queue, gated
+        const bool more = t + 1 < m_0;
+        if (pipelined && more) {
             gate.arm(sumcheck_gate_next(ctx));
-            CK(sumcheck_cubic_launch(ctx, U(z[0]), U(z[1]), U(z[2]), U(z[3]), length, nullptr, gate.seq, &red_next));
-            length /= 2;
+            CK(sumcheck_cubic_launch(ctx, U(z[0]), U(z[1]), U(z[2]), U(z[3]), len, nullptr, gate.seq, &red_next));
+            len /= 2;
         }
         // the round's blinding coefficients depend only on the earlier challenges: in latency mode computed while the kernel runs
-        blinding_coefficients_for_round(g_univ, idx, alpha.data(), gp);
+        blinding_coefficients_for_round(g_univ, t, alpha.data(), gp);
         uint64_t out[12], f[4];
         if (pipelined) {
             CK(sumcheck_collect_spin(ctx, red_cur, out));
             red_cur = red_next;
         } else {
-            if (sharded && length <= SHARD_MIN_LOCAL) {  // short shares: gather, re-interleave, finish replicated
+            if (sharded && len <= SHARD_MIN_LOCAL) {  // short shares: gather, re-interleave, finish replicated
                 for (int q = 0; q < 4; q++) {
-                    CK(gather_strided(ctx, z[q], length, ztmp, zfull[q]));
+                    CK(gather_strided(ctx, z[q], len, ztmp, zfull[q]));
                     z[q] = zfull[q];
                 }
-                length *= G;
+                len *= G;
                 sharded = false;
             }
             Across ac(ctx, sharded);  // sharded: the three evaluations are sums over the ranks' shares
             CK(ac.rc);
-            if (idx) h_store(f, alpha.back());
-            CK(pk_sumcheck_cubic_round(ctx, U(z[0]), U(z[1]), U(z[2]), U(z[3]), length, idx ? f : nullptr, out));
-            if (idx) length /= 2;
+            if (t) h_store(f, alpha.back());
+            CK(pk_sumcheck_cubic_round(ctx, U(z[0]), U(z[1]), U(z[2]), U(z[3]), len, t ? f : nullptr, out));
+            if (t) len /= 2;
         }
-        fe c[4];
-        zk_round_message(out, gp, rho, saved, c);
-        T.add_scalars(c, 4);
-        const fe a_i = T.challenge_scalar();
-        gate.publish(a_i);
-        alpha.push_back(a_i);
-        saved = eval_cubic(c, a_i);
+        fe msg[4];
+        zk_round_message(out, gp, rho, saved, msg);
+        T.add_scalars(msg, 4);
+        const fe r = T.challenge_scalar();
+        gate.publish(r);
+        alpha.push_back(r);
+        saved = eval_cubic(msg, r);
     }
     return PK_OK;
 }
@@ -1323,13 +1043,6 @@ int prove(pk_ctx* ctx, pk_scheme* s, const uint64_t* d_witness, size_t n_witness
     return PK_OK;
 }
 
-// the blinding polynomial's variables less one: 2^nb = next_power_of_two(4 m_0)
-unsigned blinding_log_len(unsigned m_0) {
-    unsigned nb = 0;
-    while (((size_t)1 << nb) < 4 * (size_t)m_0) nb++;
-    return nb;
-}
-
 }  // namespace
 
 extern "C" {
@@ -1342,23 +1055,6 @@ int pk_scheme_destroy(pk_ctx* ctx, pk_scheme* s) {
     (void)hipFree(s->noir_witness);
     if (s->side) (void)pk_ctx_destroy(s->side);
     delete s;
-    return PK_OK;
-}
-
-// arena = the sum of pk_prove's allocations (nothing is freed inside a proof).  With N = 2^m, R = 2^starting_log_inv_rate,
-// F = 2^folding_factor: f, g in both forms 4N; initial codeword batch*R*N and its tree 2R/F N; working polynomial and the
-// sumcheck ping-pong 4N; round codewords (domain halves each round) < R N, their trees < 2R/F N, folded polynomials
-// < 2/F N; deferred eq table N; a, b, c, eq and the second eq table 5*2^m_0; external rows 3*num_witnesses.  The small
-// blinding scheme (2^(nb+1) <= 2^9 elements) and alignment are covered by the constant.
-static size_t scheme_arena_bytes(unsigned m, unsigned m_0, size_t num_witnesses, const pk_whir_config& w) {
-    const double N = (double)((size_t)1 << m), R = (double)((size_t)1 << w.starting_log_inv_rate), F = (double)((size_t)1 << w.folding_factor);
-    const double units = 4.0 + w.batch_size * R + 2.0 * R / F + 4.0 + R + 2.0 * R / F + 2.0 / F + 1.0;
-    const double fes = units * N + 5.0 * (double)((size_t)1 << m_0) + 3.0 * (double)num_witnesses;
-    return (size_t)(1.05 * 32.0 * fes) + ((size_t)64 << 20);
-}
-int pk_scheme_arena_bytes(unsigned m, unsigned m_0, size_t num_witnesses, const pk_whir_config* whir_witness, size_t* bytes) {
-    if (!bytes || m > 28 || m_0 > m || whir_config_error(whir_witness)) return PK_ERR_BAD_ARG;
-    *bytes = scheme_arena_bytes(m, m_0, num_witnesses, *whir_witness);
     return PK_OK;
 }
 
@@ -1416,81 +1112,6 @@ int pk_prove(pk_ctx* ctx, pk_scheme* s, const uint64_t* d_witness, size_t n_witn
     return PK_OK;
 }
 
-// WhirConfig::new for provekit's parameters (provekit/r1cs-compiler/src/whir_r1cs.rs:38-53); see include/provekit_hip.h
-int pk_whir_config_derive(unsigned n_vars, unsigned batch_size, unsigned folding_factor, unsigned starting_log_inv_rate,
-                          unsigned security_level, int pow_bits, pk_whir_config* out) {
-    // n_vars < folding_factor: whir would run no folding round at all; this prover always folds folding_factor variables before
-    // the first re-commit (pk_scheme_create requires n_vars >= folding_factor * (n_rounds + 1)), so the smallest scheme is
-    // n_vars = folding_factor -- m_0 >= 2 for the blinding scheme at fold 4 (include/provekit_hip.h)
-    if (!out || folding_factor < 1 || folding_factor > 8 || n_vars < folding_factor || starting_log_inv_rate < 1 || batch_size < 1) return PK_ERR_BAD_ARG;
-    const unsigned k = folding_factor;
-    const double field_bits = 254.0, sec = (double)security_level;
-    // default_max_pow(num_variables, log_inv_rate) = num_variables + log_inv_rate - 3 (whir::parameters)
-    const double pow_param = pow_bits >= 0 ? (double)pow_bits : (double)(n_vars + starting_log_inv_rate) - 3.0;
-    const double protocol_sec = sec > pow_param ? sec - pow_param : 0.0;
-    // ConjectureList: log_eta = -(log_inv_rate + 1); list_size_bits = (nv + log_inv_rate) - log_eta
-    auto list_size_bits = [](unsigned nv, unsigned rate) { return (double)(nv + rate) + (double)(rate + 1); };
-    auto ood_for = [&](unsigned nv, unsigned rate) -> unsigned {
-        for (unsigned s = 1; s < 64; s++) {
-            double err = 2.0 * list_size_bits(nv, rate) + (double)nv * s;
-            if ((double)s * field_bits + 1.0 - err >= sec) return s;
-        }
-        return 64;
-    };
-    auto queries_for = [&](unsigned rate) { return (unsigned)ceil(protocol_sec / (double)rate); };
-    pk_whir_config c;
-    memset(&c, 0, sizeof c);
-    c.n_vars = n_vars;
-    c.batch_size = batch_size;
-    c.folding_factor = k;
-    c.starting_log_inv_rate = starting_log_inv_rate;
-    const unsigned final_vars = n_vars % k;
-    c.n_rounds = (n_vars - final_vars) / k - 1;
-    if (c.n_rounds > PK_MAX_WHIR_ROUNDS) return PK_ERR_BAD_ARG;
-    c.commitment_ood_samples = ood_for(n_vars, starting_log_inv_rate);
-    unsigned nv = n_vars - k, rate = starting_log_inv_rate;
-    for (unsigned r = 0; r < c.n_rounds; r++) {
-        const unsigned next_rate = rate + (k - 1);
-        c.num_queries[r] = queries_for(rate);  // queries against the OLD rate, the rest against the new one
-        c.ood_samples[r] = ood_for(nv, next_rate);
-        const double query_error = (double)c.num_queries[r] * rate;
-        const double combination_error = field_bits - (log2((double)(c.ood_samples[r] + c.num_queries[r])) + list_size_bits(nv, next_rate) + 1.0);
-        const double e = query_error < combination_error ? query_error : combination_error;
-        c.pow_bits[r] = sec > e ? sec - e : 0.0;
-        nv -= k;
-        rate = next_rate;
-    }
-    c.final_queries = queries_for(rate);
-    const double fq = (double)c.final_queries * rate;
-    c.final_pow_bits = sec > fq ? sec - fq : 0.0;
-    c.final_folding_pow_bits = sec > field_bits - 1.0 ? sec - (field_bits - 1.0) : 0.0;
-    *out = c;
-    return PK_OK;
-}
-
-// host-only: one block of the proof RNG's cipher (RFC 8439 layout: words 12,13 = counter, 14,15 = nonce); rounds = 20 for
-// the RFC's vectors, 12 (PK_RNG_ROUNDS) for what random_fe_kernel runs
-int pk_selftest_chacha(const uint8_t key[32], uint64_t counter, uint32_t n0, uint32_t n1, int rounds, uint8_t out[64]) {
-    if (!key || !out || rounds < 2 || (rounds & 1)) return PK_ERR_BAD_ARG;
-    RngKey k;
-    memcpy(k.k, key, 32);
-    u32 blk[16];
-    chacha_block(k, counter, n0, n1, rounds, blk);
-    memcpy(out, blk, 64);
-    return PK_OK;
-}
-// the device draw itself: n uniform field elements of stream `stream` under `seed32` (what pk_prove fills the mask with)
-int pk_selftest_random_fe(pk_ctx* ctx, const uint8_t seed32[32], uint32_t stream, uint64_t* d_out, size_t n) {
-    PK_ENTER(ctx);
-    PK_REQUIRE(ctx, seed32 && (n == 0 || d_out), "null pointer");
-    if (!n) return PK_OK;
-    RngKey k;
-    memcpy(k.k, seed32, 32);
-    random_fe_kernel<<<random_fe_grid(ctx, n), 256, 0, ctx->stream>>>((fe*)d_out, n, k, stream);
-    PK_LAUNCH_CHECK(ctx);
-    return PK_OK;
-}
-
 /* ---- NoirProofSchemeProver::prove after ACVM execution (provekit/prover/src/noir_proof_scheme.rs:63-92) ---- */
 
 // the witness transcript (host only): IOPattern + seed_witness_merlin (noir_proof_scheme.rs:111-133), then one
@@ -1503,32 +1124,6 @@ int pk_witness_challenges(size_t num_constraints, size_t num_witnesses, const ui
     T.add_scalar(h_from_u64(num_witnesses));
     for (size_t i = 0; i < n_public; i++) T.add_scalar(h_load(public_inputs + 4 * i));
     for (size_t i = 0; i < n_challenges; i++) h_store(challenges + 4 * i, T.challenge_scalar());
-    return PK_OK;
-}
-
-int pk_witness_fill(pk_ctx* ctx, uint64_t* d_witness, const uint8_t* d_is_set, size_t n, const uint8_t* rng_seed32, size_t* n_filled) {
-    PK_ENTER(ctx);
-    PK_REQUIRE(ctx, n == 0 || (d_witness && d_is_set), "null pointer");
-    if (n_filled) *n_filled = 0;
-    if (!n) return PK_OK;
-    RngKey key;
-    int rc = proof_key(ctx, rng_seed32, key);
-    if (rc) return rc;
-    // the count lives in device memory (the first word of the transient workspace; the stream is in order): atomics on the pinned
-    // host mailbox would need PCIe atomics, which not every host link provides
-    rc = ensure_ws(ctx, 256);
-    if (rc) return rc;
-    unsigned long long* d_count = (unsigned long long*)ctx->d_ws;
-    PK_HIP(ctx, hipMemsetAsync(d_count, 0, 8, ctx->stream));
-    fill_witness_kernel<<<grid_for(ctx, n, 256), 256, 0, ctx->stream>>>((fe*)d_witness, d_is_set, n, key, RNG_FILL, d_count);
-    PK_LAUNCH_CHECK(ctx);
-    if (n_filled) {
-        unsigned long long h = 0;
-        PK_HIP(ctx, hipMemcpyAsync(&h, d_count, 8, hipMemcpyDeviceToHost, ctx->stream));
-        rc = sync_stream(ctx);
-        if (rc) return rc;
-        *n_filled = (size_t)h;
-    }
     return PK_OK;
 }
 
@@ -1572,28 +1167,8 @@ int pk_noir_prove(pk_ctx* ctx, pk_scheme* s, pk_witness_program* builders, const
 
 int pk_scheme_domain_separator(const pk_scheme* s, char* buf, size_t cap, size_t* len) {
     if (!s || !len) return PK_ERR_BAD_ARG;
-    *len = s->domain_separator.size();
-    if (buf && cap >= *len) memcpy(buf, s->domain_separator.data(), *len);
+    copy_out(s->domain_separator, buf, cap, len);
     return PK_OK;
-}
-
-int pk_whir_r1cs_io_pattern(unsigned m_0, const pk_whir_config* whir_witness, const pk_whir_config* whir_for_hiding_spartan, uint8_t* buf,
-                            size_t cap, size_t* len) {
-    if (!len || m_0 < 1 || m_0 > 27 || whir_config_error(whir_witness) || whir_config_error(whir_for_hiding_spartan)) return PK_ERR_BAD_ARG;
-    const std::string p = whir_r1cs_io_pattern(m_0, *whir_witness, *whir_for_hiding_spartan);
-    *len = p.size();
-    if (buf && cap >= p.size()) memcpy(buf, p.data(), p.size());
-    return PK_OK;
-}
-
-int pk_io_pattern_check(const uint8_t* pattern, size_t n, unsigned m_0, const pk_whir_config* whir_witness,
-                        const pk_whir_config* whir_for_hiding_spartan, char* why, size_t why_cap) {
-    if (why && why_cap) why[0] = 0;
-    if (!pattern || m_0 < 1 || m_0 > 27 || whir_config_error(whir_witness) || whir_config_error(whir_for_hiding_spartan)) return PK_ERR_BAD_ARG;
-    const std::string bad = io_pattern_mismatch(std::string((const char*)pattern, n), m_0, *whir_witness, *whir_for_hiding_spartan);
-    if (bad.empty()) return PK_OK;
-    if (why && why_cap) snprintf(why, why_cap, "%s", bad.c_str());
-    return PK_ERR_IO_PATTERN;
 }
 
 int pk_scheme_set_io_pattern(pk_ctx* ctx, pk_scheme* s, const uint8_t* pattern, size_t n) {

@@ -1,0 +1,213 @@
+// rng.hip -- the proof RNG: a device CSPRNG keyed once per proof, and the draws made from it.
+//
+// The reference draws the ZK mask, the random polynomial g and the Spartan blinding univariates from thread_rng
+// (provekit/common/src/utils/zk_utils.rs:13-22, provekit/prover/src/whir_r1cs.rs:197,212-221): rand's ThreadRng, i.e. ChaCha12
+// seeded from the OS.  Here: one 256-bit key per proof (getrandom(2) inside pk_prove unless the caller injects a seed -- a test
+// hook), expanded on the device with the same cipher -- the ChaCha block function (RFC 8439 quarter rounds and state layout),
+// 12 rounds.  Elements 2j and 2j+1 of draw `stream` share the blocks (counter = j, nonce = {stream, attempt}): a block holds
+// two 254-bit candidates, the first for element 2j, the second for 2j+1, each accepted iff < p (what ark-ff's Fp::rand does,
+// so every element is uniform on [0, p)); an element whose candidate was rejected takes its candidate of the next attempt.
+#include <sys/random.h>
+
+#include <cerrno>
+
+#include "internal.hpp"
+#include "fe29.hpp"
+
+using namespace pk;
+
+namespace {
+
+constexpr int PK_RNG_ROUNDS = 12;
+#define PK_QR(a, b, c, d)                    \
+    a += b; d ^= a; d = (d << 16) | (d >> 16); \
+    c += d; b ^= c; b = (b << 12) | (b >> 20); \
+    a += b; d ^= a; d = (d << 8) | (d >> 24);  \
+    c += d; b ^= c; b = (b << 7) | (b >> 25)
+__host__ __device__ __forceinline__ void chacha_block(const RngKey& key, u64 counter, u32 n0, u32 n1, int rounds, u32 (&out)[16]) {
+    u32 s[16] = {0x61707865u, 0x3320646eu, 0x79622d32u, 0x6b206574u, key.k[0], key.k[1], key.k[2], key.k[3],
+                 key.k[4],    key.k[5],    key.k[6],    key.k[7],    (u32)counter, (u32)(counter >> 32), n0, n1};
+    u32 x[16];
+#pragma unroll
+    for (int i = 0; i < 16; i++) x[i] = s[i];
+#pragma unroll 1
+    for (int r = 0; r < rounds / 2; r++) {
+        PK_QR(x[0], x[4], x[8], x[12]);
+        PK_QR(x[1], x[5], x[9], x[13]);
+        PK_QR(x[2], x[6], x[10], x[14]);
+        PK_QR(x[3], x[7], x[11], x[15]);
+        PK_QR(x[0], x[5], x[10], x[15]);
+        PK_QR(x[1], x[6], x[11], x[12]);
+        PK_QR(x[2], x[7], x[8], x[13]);
+        PK_QR(x[3], x[4], x[9], x[14]);
+    }
+#pragma unroll
+    for (int i = 0; i < 16; i++) out[i] = x[i] + s[i];
+}
+#undef PK_QR
+// A lane walks its pairs j = g, g + stride, ... as a state machine (pair, attempt): one ChaCha block per loop iteration, whichever pair and
+// attempt the lane is at.  (Until round 5 the retry loop sat INSIDE the loop over pairs, so a wavefront repeated a pair's block until its
+// unluckiest lane -- 128 candidates, each rejected with probability 0.244 -- was done: ~4 blocks per pair instead of the 1.43 a lane needs.
+// Now the waiting averages out over a lane's pairs: launched with ~8 pairs per lane, a wavefront runs ~17 blocks for 8 pairs.)
+__global__ __launch_bounds__(256) void random_fe_kernel(fe* __restrict__ out, size_t n, RngKey key, u32 stream) {
+    PK_LATENCY_PRIO();
+    const size_t stride = (size_t)gridDim.x * blockDim.x, pairs = (n + 1) / 2;
+    size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    u32 attempt = 0;
+    bool done0 = false, done1 = 2 * j + 1 >= n;
+    while (j < pairs) {
+        u32 blk[16];
+        chacha_block(key, (u64)j, stream, attempt, PK_RNG_ROUNDS, blk);
+#pragma unroll
+        for (int half = 0; half < 2; half++) {
+            if (half == 0 ? done0 : done1) continue;
+            fe x;
+#pragma unroll
+            for (int w = 0; w < 8; w++) x.v[w] = blk[8 * half + w];
+            x.v[7] &= 0x3fffffffu;  // < 2^254
+            u32 borrow = 0;
+#pragma unroll
+            for (int k = 0; k < 8; k++) (void)__builtin_subc(x.v[k], kPlimb(k), borrow, &borrow);
+            if (borrow) {  // x < p: accepted
+                fe_store(out + 2 * j + half, x);
+                if (half == 0) done0 = true;
+                else done1 = true;
+            }
+        }
+        if (done0 && done1) {
+            j += stride;
+            attempt = 0;
+            done0 = false;
+            done1 = 2 * j + 1 >= n;
+        } else {
+            attempt++;
+        }
+    }
+}
+// ~8 pairs per lane (see the kernel), at least one wavefront per SIMD's worth of workgroups when the draw is long enough
+inline unsigned random_fe_grid(const pk_ctx* ctx, size_t n) {
+    const size_t pairs = (n + 1) / 2;
+    size_t blocks = (pairs + 256 * 8 - 1) / (256 * 8);
+    const size_t cap = (size_t)ctx->num_cus * 8;
+    if (blocks < 1) blocks = 1;
+    return (unsigned)(blocks < cap ? blocks : cap);
+}
+
+// fill_witness (provekit/prover/src/witness/mod.rs:15-30): every None entry takes FieldElement::from(rng.random::<u128>()).
+// Entry i reads the (i mod 4)-th 128-bit word of ChaCha block i / 4 of stream RNG_FILL, so the result does not depend on the
+// launch shape.  *n_filled counts them (the reference logs the count).
+__global__ __launch_bounds__(256) void fill_witness_kernel(fe* __restrict__ w, const uint8_t* __restrict__ is_set, size_t n, RngKey key, u32 stream,
+                                                           unsigned long long* n_filled) {
+    PK_LATENCY_PRIO();
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    unsigned mine = 0;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        if (is_set[i]) continue;
+        u32 blk[16];
+        chacha_block(key, (u64)(i >> 2), stream, 0, PK_RNG_ROUNDS, blk);
+        fe x = fe_zero();
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            u32 v = 0;
+#pragma unroll
+            for (int q = 0; q < 4; q++) v = (i & 3) == (size_t)q ? blk[4 * q + k] : v;
+            x.v[k] = v;
+        }
+        fe_store(w + i, fe_to_montx(x));
+        mine++;
+    }
+    if (mine) atomicAdd(n_filled, (unsigned long long)mine);  // n_filled is DEVICE memory: agent-scope atomics are exact there
+}
+
+}  // namespace
+
+namespace pk {
+
+// one draw: n uniform field elements of stream `stream` under `key` into d_out (launch only)
+int random_fe(pk_ctx* ctx, uint64_t* d_out, size_t n, const RngKey& key, uint32_t stream) {
+    random_fe_kernel<<<random_fe_grid(ctx, n), 256, 0, ctx->stream>>>((fe*)d_out, n, key, stream);
+    PK_LAUNCH_CHECK(ctx);
+    return PK_OK;
+}
+
+// 256-bit key of one proof's random draws: fresh from the OS CSPRNG (the reference's thread_rng) unless injected.  One proof
+// sharded over a device set: every rank must mask with the SAME polynomials -- rank 0's key goes to everybody.
+int proof_key(pk_ctx* ctx, const uint8_t* rng_seed32, RngKey& key) {
+    if (rng_seed32) {
+        memcpy(key.k, rng_seed32, 32);
+        return PK_OK;
+    }
+    size_t got = 0;
+    while (got < 32) {
+        ssize_t r = getrandom((char*)key.k + got, 32 - got, 0);
+        if (r < 0) {
+            if (errno == EINTR) continue;
+            return set_err(ctx, PK_ERR_HIP, "getrandom failed: %s", strerror(errno));
+        }
+        got += (size_t)r;
+    }
+    if (comm_world(ctx) > 1) {
+        int rc = ensure_scratch(ctx, ((size_t)1 << 19) + 32 * (size_t)(PK_MAX_RANKS + 1));
+        if (rc) return rc;
+        char* d_key = (char*)ctx->d_scratch + ((size_t)1 << 19);  // clear of the reduction area (head) and the PoW words (tail)
+        PK_HIP(ctx, hipMemcpyAsync(d_key, key.k, 32, hipMemcpyHostToDevice, ctx->stream));
+        rc = comm_all_gather(ctx, d_key, d_key + 32, 32);
+        if (rc) return rc;
+        PK_HIP(ctx, hipMemcpyAsync(key.k, d_key + 32, 32, hipMemcpyDeviceToHost, ctx->stream));
+        PK_WAIT(ctx);
+    }
+    return PK_OK;
+}
+
+}  // namespace pk
+
+extern "C" {
+
+// host-only: one block of the proof RNG's cipher (RFC 8439 layout: words 12,13 = counter, 14,15 = nonce); rounds = 20 for
+// the RFC's vectors, 12 (PK_RNG_ROUNDS) for what random_fe_kernel runs
+int pk_selftest_chacha(const uint8_t key[32], uint64_t counter, uint32_t n0, uint32_t n1, int rounds, uint8_t out[64]) {
+    if (!key || !out || rounds < 2 || (rounds & 1)) return PK_ERR_BAD_ARG;
+    RngKey k;
+    memcpy(k.k, key, 32);
+    u32 blk[16];
+    chacha_block(k, counter, n0, n1, rounds, blk);
+    memcpy(out, blk, 64);
+    return PK_OK;
+}
+// the device draw itself: n uniform field elements of stream `stream` under `seed32` (what pk_prove fills the mask with)
+int pk_selftest_random_fe(pk_ctx* ctx, const uint8_t seed32[32], uint32_t stream, uint64_t* d_out, size_t n) {
+    PK_ENTER(ctx);
+    PK_REQUIRE(ctx, seed32 && (n == 0 || d_out), "null pointer");
+    if (!n) return PK_OK;
+    RngKey k;
+    memcpy(k.k, seed32, 32);
+    return random_fe(ctx, d_out, n, k, stream);
+}
+
+int pk_witness_fill(pk_ctx* ctx, uint64_t* d_witness, const uint8_t* d_is_set, size_t n, const uint8_t* rng_seed32, size_t* n_filled) {
+    PK_ENTER(ctx);
+    PK_REQUIRE(ctx, n == 0 || (d_witness && d_is_set), "null pointer");
+    if (n_filled) *n_filled = 0;
+    if (!n) return PK_OK;
+    RngKey key;
+    int rc = proof_key(ctx, rng_seed32, key);
+    if (rc) return rc;
+    // the count lives in device memory (the first word of the transient workspace; the stream is in order): atomics on the pinned
+    // host mailbox would need PCIe atomics, which not every host link provides
+    rc = ensure_ws(ctx, 256);
+    if (rc) return rc;
+    unsigned long long* d_count = (unsigned long long*)ctx->d_ws;
+    PK_HIP(ctx, hipMemsetAsync(d_count, 0, 8, ctx->stream));
+    fill_witness_kernel<<<grid_for(ctx, n, 256), 256, 0, ctx->stream>>>((fe*)d_witness, d_is_set, n, key, RNG_FILL, d_count);
+    PK_LAUNCH_CHECK(ctx);
+    if (n_filled) {
+        unsigned long long h = 0;
+        PK_HIP(ctx, hipMemcpyAsync(&h, d_count, 8, hipMemcpyDeviceToHost, ctx->stream));
+        rc = sync_stream(ctx);
+        if (rc) return rc;
+        *n_filled = (size_t)h;
+    }
+    return PK_OK;
+}
+
+}  // extern "C"

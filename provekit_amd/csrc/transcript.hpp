@@ -13,7 +13,7 @@
 // reference's `create_io_pattern()` hands those bytes over (pk_scheme_set_io_pattern) and the transcript then both starts
 // from the reference's IV and ENFORCES the pattern op by op the way spongefish's HashStateWithInstructions does
 // (absorb / squeeze / hint against the declared stack), so a proof that would trip the reference verifier's pattern check
-// fails here first.  Without one the library's own restatement of the pattern is used (prover.hip `whir_r1cs_io_pattern`:
+// fails here first.  Without one the library's own restatement of the pattern is used (whir_config.hip `whir_r1cs_io_pattern`:
 // provekit's labels from the tree, whir's recalled -- DESIGN.md 6 lists which are pinned by the Go verifier's parser).
 #pragma once
 #include <chrono>
