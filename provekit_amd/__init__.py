@@ -15,4 +15,8 @@ def __getattr__(name):
         from .engine import ProofEngine
 
         return ProofEngine
+    if name == "Verifier":  # likewise libprovekit_verify.so
+        from .verify import Verifier
+
+        return Verifier
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
