@@ -4,7 +4,7 @@ Restates, on Python ints:
   * WhirR1CSVerifier::verify                      provekit/verifier/src/whir_r1cs.rs:38-90, 110-172
   * whir's verifier as the Go circuit spells it   recursive-verifier/app/circuit/whir.go:51-220,
     whir_utilities.go:13-186, mtUtilities.go:12-114, utilities/utilities.go:15-190
-  * the duplex-sponge transcript of provekit_amd/csrc/transcript.hpp (spongefish discipline; labels are ours)
+  * the duplex-sponge transcript of provekit_amd/csrc/protocol.hpp (spongefish discipline; labels are ours)
 It additionally checks what the Rust verifier leaves as a TODO but the Go one does (matrix_evaluation.go): that the
 deferred weight evaluations are the MLEs of eq(alpha)^T {A,B,C} at the folding point.
 Small sizes only (pure Python).

@@ -6,11 +6,10 @@
 // The reference returns *a* valid nonce that depends on thread timing; this grinder returns the
 // SMALLEST valid nonce (any valid nonce verifies; the smallest is reproducible): nonces are
 // searched in ascending windows, one compression per lane, device-wide atomicMin.
-#include <cmath>
-
 // pure ALU like the hash, but a prover is waiting for the nonce: one step above the hash kernels
 #define PK_BASE_PRIO 1
 #include "internal.hpp"
+#include "protocol.hpp"
 #include "skyscraper29s.hpp"
 
 using namespace pk;
@@ -64,33 +63,6 @@ __global__ __launch_bounds__(256) void pow_search_kernel(fe_arg challenge_arg, f
             __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             __hip_atomic_store(host_best, b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         }
-    }
-}
-
-// skyscraper/core/src/pow.rs:44-82
-void f64_to_u256(double f, uint64_t out[4]) {
-    uint64_t bits;
-    memcpy(&bits, &f, 8);
-    bool sign = bits >> 63;
-    int exp_bits = (int)((bits >> 52) & 0x7ff);
-    uint64_t frac = bits & ((1ull << 52) - 1);
-    int exp = exp_bits == 0 ? -1022 : exp_bits - 1023;
-    uint64_t significand = exp_bits == 0 ? frac : frac + (1ull << 52);
-    memset(out, 0, 32);
-    if (sign) return;
-    if (exp > 256) {
-        memset(out, 0xff, 32);
-        return;
-    }
-    int shift = exp - 52;
-    if (shift < 0) {
-        double r = std::round(f);
-        out[0] = r >= 18446744073709551616.0 ? UINT64_MAX : (r > 0 ? (uint64_t)r : 0);
-    } else {
-        unsigned limb = (unsigned)shift / 64, sh = (unsigned)shift % 64;
-        if (limb > 3) return;
-        out[limb] = significand << sh;
-        if (sh != 0 && limb < 3) out[limb + 1] = significand >> (64 - sh);
     }
 }
 
@@ -186,9 +158,7 @@ extern "C" {
 // pow.rs:14-22
 int pk_pow_threshold(double difficulty, uint64_t out[4]) {
     if (!out || !(difficulty >= 0.0 && difficulty < 80.0)) return PK_ERR_BAD_ARG;  // "Difficulty must be in the range [0, 80)"
-    const double modulus = (double)0x30644e72e131a029ull * std::ldexp(1.0, 192);
-    const double prob = std::exp2(-difficulty);
-    f64_to_u256(prob * modulus, out);
+    pow_threshold(difficulty, out);
     return PK_OK;
 }
 

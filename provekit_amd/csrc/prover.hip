@@ -25,7 +25,7 @@
 
 #include "internal.hpp"
 #include "shard_map.hpp"
-#include "transcript.hpp"
+#include "prover_transcript.hpp"
 
 using namespace pk;
 
@@ -88,15 +88,6 @@ struct Arena {
 
 inline uint64_t* U(fe* p) { return (uint64_t*)p; }
 inline const uint64_t* U(const fe* p) { return (const uint64_t*)p; }
-
-// ExpandFromUnivariate (recursive-verifier/app/utilities/utilities.go:182-190): point[n-1-i] = z^(2^i)
-void expand_from_univariate(const fe& z, unsigned n, fe* out) {
-    fe acc = z;
-    for (unsigned i = 0; i < n; i++) {
-        out[n - 1 - i] = acc;
-        acc = h_mul(acc, acc);
-    }
-}
 
 // ------------------------------------------------------------------ one proof over a device set
 // Besides the commits (tree.hip), the linear-size arrays of a sharded proof are split over the G ranks:
@@ -176,9 +167,6 @@ int eval_univariate_multi_x(pk_ctx* ctx, const fe* const* d_polys, unsigned np, 
 int eval_univariate_x(pk_ctx* ctx, const fe* d_poly, size_t n, const fe& z, fe& out) { return eval_univariate_multi_x(ctx, &d_poly, 1, n, z, &out); }
 
 // ------------------------------------------------------------------ S6: blinding algebra (host, O(m_0^2))
-fe eval_cubic(const fe c[4], const fe& x) {  // provekit/common/src/utils/sumcheck.rs:174-176
-    return h_add(c[0], h_mul(x, h_add(c[1], h_mul(x, h_add(c[2], h_mul(x, c[3]))))));
-}
 // compute_blinding_coefficients_for_round (provekit/prover/src/whir_r1cs.rs:103-170)
 void blinding_coefficients_for_round(const std::vector<fe>& g /*4 per variable*/, size_t compute_for, const fe* alphas, fe out[4]) {
     const size_t n = g.size() / 4;
@@ -208,49 +196,22 @@ void blinding_coefficients_for_round(const std::vector<fe>& g /*4 per variable*/
     for (int i = 0; i < 4; i++) out[i] = c[i];
 }
 
-// ------------------------------------------------------------------ STIR query indices
-// recursive-verifier/app/circuit/whir_utilities.go:48-77: per query ceil(log2(folded)/8) bytes, big-endian, low bits kept;
-// then sorted + deduplicated as whir does.
+// ------------------------------------------------------------------ STIR query indices, proof of work (the rules: protocol.hpp)
 std::vector<uint64_t> stir_queries(Transcript& T, size_t domain_size, unsigned fold, unsigned num_queries) {
-    const size_t folded = domain_size >> fold;
-    unsigned bits = ilog2(folded);
-    const size_t nbytes = (bits + 7) / 8;
-    std::vector<uint8_t> raw(nbytes * num_queries);
-    if (!raw.empty()) T.challenge_bytes(raw.data(), raw.size());
-    std::vector<uint64_t> idx(num_queries);
-    for (unsigned q = 0; q < num_queries; q++) {
-        uint64_t v = 0;
-        for (size_t j = 0; j < nbytes; j++) v = (v << 8) | raw[q * nbytes + j];
-        idx[q] = v & (folded - 1);
-    }
-    std::sort(idx.begin(), idx.end());
-    idx.erase(std::unique(idx.begin(), idx.end()), idx.end());
-    return idx;
+    std::vector<uint8_t> raw(stir_query_bytes(domain_size, fold) * num_queries);
+    T.challenge_bytes(raw.data(), raw.size());
+    return stir_indexes(raw.data(), domain_size, fold, num_queries);
 }
 
 int pow_round(pk_ctx* ctx, Transcript& T, double bits) {
     if (bits <= 0.0) return PK_OK;
-    uint8_t challenge[32];
-    T.challenge_bytes(challenge, 32);
+    uint8_t challenge[POW_CHALLENGE_BYTES], be[POW_NONCE_BYTES];
+    T.challenge_bytes(challenge, sizeof challenge);
     uint64_t nonce = 0;
     const int rc = pow_solve_x(ctx, challenge, bits, &nonce, comm_world(ctx) > 1);  // nonce ranges striped over the ranks of a device set
-    uint8_t be[8];
-    for (int i = 0; i < 8; i++) be[i] = (uint8_t)(nonce >> (56 - 8 * i));  // utilities.go:89-95
-    T.add_bytes(be, 8);
+    nonce_to_bytes(nonce, be);
+    T.add_bytes(be, sizeof be);
     return rc;
-}
-
-// hint payloads, ark-serialize uncompressed (common.go:36-73): a u64 little-endian, and a Vec<F> = its u64 length, then every
-// element's canonical 32 bytes (`montgomery`: the elements are still in Montgomery form)
-void put_u64(std::vector<uint8_t>& buf, uint64_t v) {
-    for (int i = 0; i < 8; i++) buf.push_back((uint8_t)(v >> (8 * i)));
-}
-void put_vec(std::vector<uint8_t>& buf, const fe* v, size_t n, bool montgomery = true) {
-    put_u64(buf, n);
-    for (size_t j = 0; j < n; j++) {
-        const fe c = montgomery ? h_to_canon(v[j]) : v[j];
-        buf.insert(buf.end(), (const uint8_t*)c.v, (const uint8_t*)c.v + 32);
-    }
 }
 
 // ------------------------------------------------------------------ WHIR
@@ -344,16 +305,6 @@ size_t in_block(size_t stored, size_t off, size_t len) {
     const size_t hi = stored < off + len ? stored : off + len;
     return hi > off ? hi - off : 0;
 }
-// generator of the domain of 2^log_size points, raised to the 2^fold-th power (whir.go:99)
-fe folded_domain_generator(unsigned log_size, unsigned fold) {
-    fe root28;
-    const uint64_t l[4] = {0x9bd61b6e725b19f0ULL, 0x402d111e41112ed4ULL, 0x00e0a7eb8ef62abcULL, 0x2a3c09f0a58a7e85ULL};
-    memcpy(root28.v, l, 32);
-    fe gen = h_from_canon(root28);
-    for (unsigned i = log_size; i < 28 + fold; i++) gen = h_mul(gen, gen);
-    return gen;
-}
-
 struct WhirProver {
     pk_ctx* ctx;
     Arena& A;
@@ -774,7 +725,7 @@ struct Proof {
         (void)wait_ctx(ctx);
         const auto t = std::chrono::steady_clock::now();
         fprintf(stderr, "[pk_prove] %-28s %8.3f ms (sponge: %u permutes, %.3f ms; hint serialisation so far %.3f ms)\n", what,
-                1e3 * std::chrono::duration<double>(t - t_lap).count(), T.permutes, 1e3 * T.permute_seconds, 1e3 * T.hint_seconds);
+                1e3 * std::chrono::duration<double>(t - t_lap).count(), T.permutes(), 1e3 * T.permute_seconds, 1e3 * T.hint_seconds);
         t_lap = t;
     }
 

@@ -18,6 +18,7 @@
 // memory- / latency-bound kernels: their wavefronts issue ahead of the ALU-bound hash / NTT / grinder kernels they share SIMDs with
 #define PK_BASE_PRIO 2
 #include "internal.hpp"
+#include "postcard.hpp"
 #include "fe29.hpp"
 #include "reduce.hpp"
 
@@ -341,36 +342,6 @@ int pk_r1cs_create(pk_ctx* ctx, size_t num_constraints, size_t num_witnesses, co
 //   Interner { values: serde_ark(Vec<FieldElement>) } = bytes( u64-LE count | count x 32-byte canonical LE )   (interner.rs:6-10,
 //                                                                               utils/serde_ark.rs:11-31, ark-serialize compressed)
 //   SparseMatrix { num_rows, num_cols: usize, new_row_indices: Vec<u32>, col_indices: Vec<u32>, values: Vec<usize> }
-namespace {
-struct PcReader {
-    const uint8_t* p;
-    size_t n, off = 0;
-    bool ok = true;
-    uint64_t varint() {
-        uint64_t v = 0;
-        for (unsigned shift = 0; shift < 70; shift += 7) {
-            if (off >= n) return ok = false, 0;
-            const uint8_t b = p[off++];
-            if (shift == 63 && b > 1) return ok = false, 0;
-            v |= (uint64_t)(b & 0x7f) << shift;
-            if (!(b & 0x80)) return v;
-        }
-        return ok = false, 0;
-    }
-    bool vec_u32(std::vector<uint32_t>& out) {
-        const uint64_t len = varint();
-        if (!ok || len > n - off) return ok = false;  // every item takes at least one byte
-        out.resize(len);
-        for (uint64_t i = 0; i < len; i++) {
-            const uint64_t v = varint();
-            if (!ok || v > 0xffffffffull) return ok = false;
-            out[i] = (uint32_t)v;
-        }
-        return true;
-    }
-};
-}  // namespace
-
 static int r1cs_from_postcard_impl(pk_ctx* ctx, const uint8_t* bytes, size_t len, pk_r1cs** out, size_t* num_constraints,
                                    size_t* num_witnesses, size_t* num_public_inputs, size_t* consumed);
 int pk_r1cs_from_postcard(pk_ctx* ctx, const uint8_t* bytes, size_t len, pk_r1cs** out, size_t* num_constraints, size_t* num_witnesses,
@@ -388,7 +359,7 @@ static int r1cs_from_postcard_impl(pk_ctx* ctx, const uint8_t* bytes, size_t len
     PK_ENTER(ctx);
     *out = nullptr;
     PK_REQUIRE(ctx, bytes, "null pointer");
-    PcReader rd{bytes, len};
+    postcard::Reader rd{bytes, len};
     const uint64_t n_pub = rd.varint();
     // interner: bytes( u64 count | count * 32 )
     const uint64_t blob = rd.varint();

@@ -1,14 +1,8 @@
-// transcript.hpp -- host-side Fiat-Shamir transcript: spongefish's DuplexSponge over the Skyscraper
-// permutation.
+// transcript.hpp -- the host layer under the Fiat-Shamir transcript: field helpers, the Skyscraper
+// permutation on the CPU, the Keccak tag of an IO pattern and the pattern's parser.
 //
-// Mirrors provekit/common/src/skyscraper/sponge.rs:42-60 (state = 2 field elements, rate 1, IV in the
-// capacity element, permutation = skyscraper::reference::permute) and the spongefish duplex discipline
-// (overwrite mode: absorbing replaces the rate element; a squeeze after an absorb permutes first).
-// spongefish is an un-pinned, un-vendored git dependency of the reference (Cargo.toml:130-131), so the byte
-// framing below follows what the in-tree Go verifier consumes (recursive-verifier/app/circuit/common.go:30-105,
-// utilities/utilities.go:84-101): scalars = 32-byte canonical little-endian, absorbed as field elements; hints =
-// u32-LE length + payload, not absorbed; PoW nonce = 8 bytes big-endian, absorbed byte-wise; challenge bytes are
-// taken 15 at a time from squeezed elements (spongefish's bytes_uniform_modp for a 254-bit modulus).
+// On top of it: protocol.hpp (spongefish's DuplexSponge over this permutation, the IO-pattern cursor, the byte framing -- what the
+// prover and the verifier share), then the two sides of the transcript: prover_transcript.hpp and verify/core.hpp's Arthur.
 // The sponge IV is the Keccak tag of the IO pattern's bytes (DomainSeparator::as_bytes()); a caller that holds the
 // reference's `create_io_pattern()` hands those bytes over (pk_scheme_set_io_pattern) and the transcript then both starts
 // from the reference's IV and ENFORCES the pattern op by op the way spongefish's HashStateWithInstructions does
@@ -16,7 +10,6 @@
 // fails here first.  Without one the library's own restatement of the pattern is used (whir_config.hip `whir_r1cs_io_pattern`:
 // provekit's labels from the tree, whir's recalled -- DESIGN.md 6 lists which are pinned by the Go verifier's parser).
 #pragma once
-#include <chrono>
 #include <cstdint>
 #include <cstring>
 #include <string>
@@ -120,16 +113,16 @@ inline void keccak_tag(const std::string& data, uint8_t tag[32]) {
 // shaped for the GPU's 32x32+64 mad).  Checked against the Python restatement by tests/test_fe29_host.py.
 namespace host64 {
 typedef unsigned __int128 u128;
-static const uint64_t P64[4] = {0x43e1f593f0000001ULL, 0x2833e84879b97091ULL, 0xb85045b68181585dULL, 0x30644e72e131a029ULL};
-static const uint64_t NP64 = 0xc2e1f593efffffffULL;  // -p^-1 mod 2^64
-inline bool geq_p(const uint64_t a[4]) {
+constexpr uint64_t P64[4] = {0x43e1f593f0000001ULL, 0x2833e84879b97091ULL, 0xb85045b68181585dULL, 0x30644e72e131a029ULL};
+constexpr uint64_t NP64 = 0xc2e1f593efffffffULL;  // -p^-1 mod 2^64
+constexpr bool geq_p(const uint64_t a[4]) {
     for (int i = 3; i >= 0; i--) {
         if (a[i] > P64[i]) return true;
         if (a[i] < P64[i]) return false;
     }
     return true;
 }
-inline void sub_p(uint64_t a[4]) {
+constexpr void sub_p(uint64_t a[4]) {
     uint64_t borrow = 0;
     for (int i = 0; i < 4; i++) {
         u128 d = (u128)a[i] - P64[i] - borrow;
@@ -138,7 +131,7 @@ inline void sub_p(uint64_t a[4]) {
     }
 }
 // a*b*2^-256 mod p, inputs < p
-inline void mont_mul(const uint64_t a[4], const uint64_t b[4], uint64_t r[4]) {
+constexpr void mont_mul(const uint64_t a[4], const uint64_t b[4], uint64_t r[4]) {
     uint64_t t[5] = {0, 0, 0, 0, 0};
     for (int i = 0; i < 4; i++) {
         u128 c = 0;
@@ -163,7 +156,7 @@ inline void mont_mul(const uint64_t a[4], const uint64_t b[4], uint64_t r[4]) {
     for (int i = 0; i < 4; i++) r[i] = t[i];
     if (t[4] || geq_p(r)) sub_p(r);
 }
-inline void add_mod(uint64_t a[4], const uint64_t b[4]) {  // a = a + b mod p, both < p
+constexpr void add_mod(uint64_t a[4], const uint64_t b[4]) {  // a = a + b mod p, both < p
     u128 c = 0;
     for (int i = 0; i < 4; i++) {
         c += (u128)a[i] + b[i];
@@ -258,120 +251,5 @@ inline bool io_pattern_parse(const std::string& bytes, std::vector<IoOp>& ops, s
     }
     return true;
 }
-
-class Transcript {
-  public:
-    std::vector<uint8_t> narg;  // the proof string (WhirR1CSProof::transcript)
-    double permute_seconds = 0.0;  // host time spent in the sponge permutation (PK_PROVE_TIMING)
-    double hint_seconds = 0.0;     // host time spent serialising opening hints (PK_PROVE_TIMING)
-    unsigned permutes = 0;
-
-    explicit Transcript(const std::string& io_pattern) {
-        uint8_t iv[32];
-        keccak_tag(io_pattern, iv);  // HashStateWithInstructions::generate_tag
-        st_[0] = fe_zero();
-        fe c;
-        memcpy(c.v, iv, 32);
-        st_[1] = fe_reduce_any(c);  // FieldElement::new(bigint_from_bytes_le(iv)), sponge.rs:46-49
-        if (!io_pattern_parse(io_pattern, ops_, violation_)) ops_.clear();
-    }
-    // "" while every operation so far matched the declared pattern; otherwise the first mismatch (spongefish: InvalidIOPattern)
-    const std::string& violation() const { return violation_; }
-    // ... and nothing declared was left undone (spongefish checks this when the state is dropped)
-    bool finished() const { return violation_.empty() && op_ == ops_.size(); }
-    // prover -> verifier: field elements (Montgomery in memory), written canonical LE and absorbed
-    void add_scalars(const fe* mont, size_t n) {
-        for (size_t i = 0; i < n; i++) add_canon(h_to_canon(mont[i]));
-    }
-    void add_scalar(const fe& mont) { add_scalars(&mont, 1); }
-    // a digest is already a canonical value (provekit/common/src/skyscraper/whir.rs:96-102)
-    void add_canon(const fe& canon) {
-        expect('A', 1);
-        append(canon.v, 32);
-        absorb(canon);
-    }
-    // verifier -> prover
-    fe challenge_scalar() {
-        expect('S', 1);
-        return h_from_canon(squeeze());
-    }
-    void challenge_scalars(fe* out, size_t n) {
-        for (size_t i = 0; i < n; i++) out[i] = challenge_scalar();
-    }
-    void challenge_bytes(uint8_t* out, size_t n) {
-        expect('S', (n + 14) / 15);
-        while (n) {
-            fe c = squeeze();
-            size_t take = n < 15 ? n : 15;
-            memcpy(out, c.v, take);
-            out += take;
-            n -= take;
-        }
-    }
-    void add_bytes(const uint8_t* b, size_t n) {
-        expect('A', n);
-        append(b, n);
-        for (size_t i = 0; i < n; i++) {
-            fe c = fe_zero();
-            c.v[0] = b[i];
-            absorb(c);
-        }
-    }
-    void hint(const void* payload, size_t len) {
-        expect('H', 1);
-        uint32_t l = (uint32_t)len;
-        append(&l, 4);
-        append(payload, len);
-    }
-
-  private:
-    void permute() {
-        auto t0 = std::chrono::steady_clock::now();
-        sky_permute_host(st_[0], st_[1]);
-        permute_seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        permutes++;
-    }
-    fe st_[2];
-    int absorb_pos_ = 0, squeeze_pos_ = 1;  // R = 1
-    std::vector<IoOp> ops_;
-    size_t op_ = 0, used_ = 0;  // position in ops_, units of ops_[op_] already consumed
-    std::string violation_;
-    void expect(char kind, size_t n) {
-        if (!n || !violation_.empty()) return;
-        if (op_ >= ops_.size() || ops_[op_].kind != kind || ops_[op_].count - used_ < n) {
-            violation_ = std::string("transcript operation ") + kind + std::to_string(n) + " does not follow the IO pattern: operation #" +
-                         std::to_string(op_ + 1) + " is " +
-                         (op_ < ops_.size() ? std::string(1, ops_[op_].kind) + std::to_string(ops_[op_].count - used_) + " (remaining)" : std::string("past the end"));
-            return;
-        }
-        used_ += n;
-        if (used_ == ops_[op_].count) {
-            op_++;
-            used_ = 0;
-        }
-    }
-    void append(const void* p, size_t n) {
-        const uint8_t* b = static_cast<const uint8_t*>(p);
-        narg.insert(narg.end(), b, b + n);
-    }
-    void absorb(const fe& canon) {
-        if (absorb_pos_ == 1) {
-            permute();
-            absorb_pos_ = 0;
-        }
-        st_[0] = canon;
-        absorb_pos_ = 1;
-        squeeze_pos_ = 1;
-    }
-    fe squeeze() {
-        if (squeeze_pos_ == 1) {
-            squeeze_pos_ = 0;
-            absorb_pos_ = 0;
-            permute();
-        }
-        squeeze_pos_ = 1;
-        return st_[0];
-    }
-};
 
 }  // namespace pk

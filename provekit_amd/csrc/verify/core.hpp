@@ -2,7 +2,7 @@
 //
 // Restates provekit/verifier/src/whir_r1cs.rs:38-90,110-172 and whir's verifier as the Go circuit spells it
 // (recursive-verifier/app/circuit/whir.go:51-220, whir_utilities.go:13-186, mtUtilities.go:12-114, utilities/utilities.go:15-190)
-// against this repository's wire format (transcript.hpp): the checks and their order are the acceptance oracle's.
+// against this repository's wire format (protocol.hpp, shared with the prover): the checks and their order are the acceptance oracle's.
 //
 // One body serves the host core and the device path (verify.hip).  The three data-parallel pieces -- does an opening reach its
 // root, an opening's fold value, the bilinear forms over the R1CS matrices -- go through a Backend:
@@ -15,18 +15,20 @@
 // read from a proof is bounded by the bytes that remain before anything is reserved.
 #pragma once
 #include <algorithm>
-#include <cmath>
 #include <cstdio>
 #include <string>
 #include <vector>
 
 #include "../../../include/provekit_verify.h"
-#include "../transcript.hpp"
+#include "../protocol.hpp"
 #include "../skyscraper29.hpp"
 
 namespace pkv {
 
 using pk::fe;
+using pk::HintFe;
+using pk::load_raw;
+using pk::Rd;
 
 struct Statement {
     unsigned m = 0, m_0 = 0;
@@ -40,37 +42,9 @@ struct Statement {
     std::vector<fe> interner;                         // Montgomery
 };
 
-// ---- field helpers above transcript.hpp's ------------------------------------------------------------------------------------
-inline fe load_raw(const uint8_t* p) {
-    fe r;
-    memcpy(r.v, p, 32);
-    return r;
-}
-inline bool is_canonical(const fe& raw) {
-    fe p;
-    for (int i = 0; i < 8; i++) p.v[i] = pk::kPlimb(i);
-    return pk::fe_lt(raw, p);
-}
+// ---- field helpers above protocol.hpp's ---------------------------------------------------------------------------------------
 inline fe f_one() { return pk::fe_one(); }
 inline fe f_zero() { return pk::fe_zero(); }
-inline fe f_u64(uint64_t v) { return pk::h_from_u64(v); }
-// 5^((p-1) >> 28): ark-bn254 Fr's two-adic root of unity
-inline fe root28() {
-    uint64_t e[4];
-    for (int i = 0; i < 4; i++) e[i] = pk::host64::P64[i];
-    e[0] -= 1;
-    for (int i = 0; i < 4; i++) e[i] = (e[i] >> 28) | (i < 3 ? e[i + 1] << 36 : 0);
-    fe acc = f_one(), base = f_u64(5);
-    for (int bit = 0; bit < 256; bit++) {
-        if ((e[bit >> 6] >> (bit & 63)) & 1) acc = pk::h_mul(acc, base);
-        base = pk::h_mul(base, base);
-    }
-    return acc;
-}
-inline fe sq_times(fe x, unsigned n) {
-    while (n--) x = pk::h_mul(x, x);
-    return x;
-}
 // compress on canonical values (any 256-bit input is taken mod p, as the reference's permutation does)
 inline fe h_compress(int version, const fe& l, const fe& r) {
     if (version == 2) {
@@ -79,33 +53,6 @@ inline fe h_compress(int version, const fe& l, const fe& r) {
         return pk::fe_add(a, l0);
     }
     return pk::pack29(pk::compress29<1, true>(pk::unpack_reduce29(l), pk::unpack_reduce29(r)));
-}
-// skyscraper/core/src/pow.rs:14-22, 44-82
-inline void pow_threshold(double difficulty, uint64_t out[4]) {
-    const double f = std::exp2(-difficulty) * ((double)0x30644e72e131a029ull * std::ldexp(1.0, 192));
-    uint64_t bits;
-    memcpy(&bits, &f, 8);
-    const bool sign = bits >> 63;
-    const int exp_bits = (int)((bits >> 52) & 0x7ff);
-    const uint64_t frac = bits & ((1ull << 52) - 1);
-    const int exp = exp_bits == 0 ? -1022 : exp_bits - 1023;
-    const uint64_t significand = exp_bits == 0 ? frac : frac + (1ull << 52);
-    memset(out, 0, 32);
-    if (sign) return;
-    if (exp > 256) {
-        memset(out, 0xff, 32);
-        return;
-    }
-    const int shift = exp - 52;
-    if (shift < 0) {
-        const double r = std::round(f);
-        out[0] = r >= 18446744073709551616.0 ? UINT64_MAX : (r > 0 ? (uint64_t)r : 0);
-    } else {
-        const unsigned limb = (unsigned)shift / 64, sh = (unsigned)shift % 64;
-        if (limb > 3) return;
-        out[limb] = significand << sh;
-        if (sh != 0 && limb < 3) out[limb + 1] = significand >> (64 - sh);
-    }
 }
 
 // ---- the verdict -------------------------------------------------------------------------------------------------------------
@@ -197,15 +144,10 @@ struct HostBackend : Backend {
     }
 };
 
-// ---- the verifier side of the duplex sponge (spongefish VerifierState over transcript.hpp's conventions) -----------------------
+// ---- the verifier side of the transcript (spongefish VerifierState): protocol.hpp's sponge and cursor over a bounded byte source ----
 class Arthur {
   public:
-    Arthur(const Statement& st, const uint8_t* t, size_t len, Verdict& v) : t_(t), len_(len), ops_(st.ops), v_(v) {
-        uint8_t iv[32];
-        pk::keccak_tag(st.pattern, iv);
-        st_[0] = f_zero();
-        st_[1] = pk::fe_reduce_any(load_raw(iv));
-    }
+    Arthur(const Statement& st, const uint8_t* t, size_t len, Verdict& v) : t_(t), len_(len), sponge_(st.pattern), cur_(st.ops), v_(v) {}
     size_t pos() const { return i_; }
     size_t remaining() const { return len_ - i_; }
     bool fail(int check, const std::string& msg) {
@@ -224,8 +166,8 @@ class Arthur {
             const uint8_t* p;
             if (!read(32, p)) return false;
             const fe c = load_raw(p);
-            if (!is_canonical(c)) return fail(PKV_CHECK_NON_CANONICAL, "non-canonical scalar");
-            absorb(c);
+            if (!pk::is_canonical(c)) return fail(PKV_CHECK_NON_CANONICAL, "non-canonical scalar");
+            sponge_.absorb(c);
             if (canon_out) canon_out[k] = c;
             mont_out[k] = pk::fe_to_montx(c);
         }
@@ -233,50 +175,38 @@ class Arthur {
     }
     bool challenge_scalars(size_t n, fe* out) {
         if (!expect('S', n)) return false;
-        for (size_t k = 0; k < n; k++) out[k] = pk::fe_to_montx(squeeze());
+        for (size_t k = 0; k < n; k++) out[k] = pk::fe_to_montx(sponge_.squeeze());
         return true;
     }
     bool challenge_bytes(size_t n, uint8_t* out) {
-        if (!expect('S', (n + 14) / 15)) return false;
-        while (n) {
-            const fe c = squeeze();
-            const size_t take = n < 15 ? n : 15;
-            memcpy(out, c.v, take);
-            out += take;
-            n -= take;
-        }
+        if (!expect('S', pk::units_for_bytes(n))) return false;
+        sponge_.squeeze_bytes(out, n);
         return true;
     }
     bool next_bytes(size_t n, uint8_t* out) {
         if (!expect('A', n)) return false;
         const uint8_t* p;
         if (!read(n, p)) return false;
-        for (size_t k = 0; k < n; k++) {
-            fe c = f_zero();
-            c.v[0] = p[k];
-            absorb(c);
-            out[k] = p[k];
-        }
+        sponge_.absorb_bytes(p, n);
+        memcpy(out, p, n);
         return true;
     }
     bool hint(const uint8_t*& p, size_t& n) {
         if (!expect('H', 1)) return false;
         const uint8_t* lp;
-        if (!read(4, lp)) return false;
-        uint32_t ln;
-        memcpy(&ln, lp, 4);
+        pk::hint_len_t ln;
+        if (!read(sizeof ln, lp)) return false;
+        memcpy(&ln, lp, sizeof ln);
         n = ln;
         return read(ln, p);
     }
-    bool done() const { return i_ == len_ && op_ == ops_.size(); }
+    bool done() const { return i_ == len_ && cur_.at_end(); }
 
   private:
     const uint8_t* t_;
     size_t len_, i_ = 0;
-    fe st_[2];
-    int absorb_pos_ = 0, squeeze_pos_ = 1;
-    const std::vector<pk::IoOp>& ops_;
-    size_t op_ = 0, used_ = 0;
+    pk::DuplexSponge sponge_;
+    pk::IoCursor cur_;
     Verdict& v_;
     bool read(size_t n, const uint8_t*& p) {
         if (n > len_ - i_) return fail(PKV_CHECK_TRANSCRIPT_SHORT, "transcript too short");
@@ -285,80 +215,13 @@ class Arthur {
         return true;
     }
     bool expect(char kind, size_t n) {
-        if (!n) return true;
-        if (op_ >= ops_.size() || ops_[op_].kind != kind || ops_[op_].count - used_ < n)
-            return fail(PKV_CHECK_IO_PATTERN, std::string("operation ") + kind + std::to_string(n) + " does not follow the IO pattern (operation #" +
-                                                  std::to_string(op_ + 1) + ")");
-        used_ += n;
-        if (used_ == ops_[op_].count) {
-            op_++;
-            used_ = 0;
-        }
-        return true;
-    }
-    void absorb(const fe& canon) {
-        if (absorb_pos_ == 1) {
-            pk::sky_permute_host(st_[0], st_[1]);
-            absorb_pos_ = 0;
-        }
-        st_[0] = canon;
-        absorb_pos_ = 1;
-        squeeze_pos_ = 1;
-    }
-    fe squeeze() {
-        if (squeeze_pos_ == 1) {
-            squeeze_pos_ = 0;
-            absorb_pos_ = 0;
-            pk::sky_permute_host(st_[0], st_[1]);
-        }
-        squeeze_pos_ = 1;
-        return st_[0];
+        if (cur_.take(kind, n)) return true;
+        return fail(PKV_CHECK_IO_PATTERN, std::string("operation ") + kind + std::to_string(n) + " does not follow the IO pattern (operation #" +
+                                              std::to_string(cur_.op_index() + 1) + ")");
     }
 };
-
-// ---- bounded readers over a hint's payload -----------------------------------------------------------------------------------
-struct Rd {
-    const uint8_t* b;
-    size_t n, i = 0;
-    size_t left() const { return n - i; }
-    bool u64(uint64_t& v) {
-        if (left() < 8) return false;
-        memcpy(&v, b + i, 8);
-        i += 8;
-        return true;
-    }
-    // a count of items of at least `item_bytes` each: refused unless the payload can hold them
-    bool count(uint64_t& v, size_t item_bytes) { return u64(v) && v <= left() / item_bytes; }
-    bool skip(size_t bytes, const uint8_t*& p) {
-        if (left() < bytes) return false;
-        p = b + i;
-        i += bytes;
-        return true;
-    }
-    bool end() const { return i == n; }
-};
-struct HintFe {
-    fe mont;
-    bool canonical;
-};
-inline bool parse_vec(Rd& rd, std::vector<HintFe>& out) {  // Vec<F>, ark-serialize uncompressed
-    uint64_t c;
-    if (!rd.count(c, 32)) return false;
-    out.resize((size_t)c);
-    for (auto& x : out) {
-        const uint8_t* p;
-        rd.skip(32, p);
-        const fe raw = load_raw(p);
-        x.canonical = is_canonical(raw);
-        x.mont = pk::h_from_canon(raw);
-    }
-    return true;
-}
 
 // ---- algebra -----------------------------------------------------------------------------------------------------------------
-inline fe eval_cubic(const fe* c, const fe& x) {
-    return pk::h_add(c[0], pk::h_mul(x, pk::h_add(c[1], pk::h_mul(x, pk::h_add(c[2], pk::h_mul(x, c[3]))))));
-}
 inline fe eq_poly(const fe* a, const fe* b, size_t n) {  // EqPolyOutside
     fe acc = f_one();
     for (size_t i = 0; i < n; i++) {
@@ -383,14 +246,6 @@ inline std::vector<fe> expand_randomness(const fe& base, size_t n) {
         acc = pk::h_mul(acc, base);
     }
     return out;
-}
-inline std::vector<fe> expand_from_univariate(fe z, size_t n) {  // utilities.go:182-190
-    std::vector<fe> res(n);
-    for (size_t i = 0; i < n; i++) {
-        res[n - 1 - i] = z;
-        z = pk::h_mul(z, z);
-    }
-    return res;
 }
 inline fe multivar_poly(std::vector<fe> c, const std::vector<fe>& vs) {  // utilities.go:15-22: vs[t] <-> index bit t
     size_t len = c.size();
@@ -484,7 +339,7 @@ class Walk {
             if (!A.next_scalars(4, hhat) || !A.challenge_scalars(1, &a_i)) return false;
             const fe at01 = pk::h_add(pk::h_add(pk::h_add(hhat[0], hhat[0]), hhat[1]), pk::h_add(hhat[2], hhat[3]));
             if (!relation(pk::fe_eq(saved, at01), PKV_CHECK_ZK_SUMCHECK, "Sumcheck equality assertion failed")) return false;
-            saved = eval_cubic(hhat, a_i);
+            saved = pk::eval_cubic(hhat, a_i);
             alpha[i] = a_i;
         }
         fe bsums[2];
@@ -511,7 +366,7 @@ class Walk {
             size_t n;
             if (!A.hint(p, n)) return false;
             Rd rd{p, n};
-            if (!parse_vec(rd, f_sums) || !parse_vec(rd, g_sums) || !rd.end() || f_sums.size() != 3 || g_sums.size() != 3)
+            if (!pk::parse_vec(rd, f_sums) || !pk::parse_vec(rd, g_sums) || !rd.end() || f_sums.size() != 3 || g_sums.size() != 3)
                 return A.fail(PKV_CHECK_HINT_FORMAT, "bad claimed_evaluations hint");
         }
         std::vector<fe> claims(3);
@@ -570,36 +425,24 @@ class Walk {
     }
     bool check_pow(double bits) {  // utilities.go:84-101; pow.rs:24-26
         if (!(bits > 0)) return true;
-        uint8_t ch[32], nb[8];
-        if (!A.challenge_bytes(32, ch) || !A.next_bytes(8, nb)) return false;
-        uint64_t nonce = 0;
-        for (int i = 0; i < 8; i++) nonce = (nonce << 8) | nb[i];
+        uint8_t ch[pk::POW_CHALLENGE_BYTES], nb[pk::POW_NONCE_BYTES];
+        if (!A.challenge_bytes(sizeof ch, ch) || !A.next_bytes(sizeof nb, nb)) return false;
+        const uint64_t nonce = pk::nonce_from_bytes(nb);
         fe n = f_zero();
         n.v[0] = (uint32_t)nonce;
         n.v[1] = (uint32_t)(nonce >> 32);
         const fe h = h_compress(2, load_raw(ch), n);
         uint64_t thr[4];
-        pow_threshold(bits, thr);
+        pk::pow_threshold(bits, thr);
         fe t;
         memcpy(t.v, thr, 32);
         if (!pk::fe_lt(h, t)) return A.fail(PKV_CHECK_POW, "proof of work below difficulty");
         return true;
     }
     bool stir_indexes(uint64_t domain, unsigned fold, unsigned nq, std::vector<uint64_t>& out) {  // whir_utilities.go:48-77
-        const uint64_t folded = domain >> fold;
-        unsigned bits = 0;
-        while ((folded >> (bits + 1)) != 0) bits++;
-        const size_t nbytes = (bits + 7) / 8;
-        std::vector<uint8_t> raw(nbytes * nq);
+        std::vector<uint8_t> raw(pk::stir_query_bytes(domain, fold) * nq);
         if (!A.challenge_bytes(raw.size(), raw.data())) return false;
-        out.resize(nq);
-        for (unsigned q = 0; q < nq; q++) {
-            uint64_t v = 0;
-            for (size_t j = 0; j < nbytes; j++) v = (v << 8) | raw[q * nbytes + j];
-            out[q] = v & (folded - 1);
-        }
-        std::sort(out.begin(), out.end());
-        out.erase(std::unique(out.begin(), out.end()), out.end());
+        out = pk::stir_indexes(raw.data(), domain, fold, nq);
         return true;
     }
     // stir_answers (Vec<Vec<F>>) and merkle_proof (MultiPath, prefix-compressed) of the tree with 2^(depth+1) leaves
@@ -713,8 +556,7 @@ class Walk {
         std::vector<fe> rs, total;
         if (!sumcheck(k, last, rs)) return false;
         total = rs;
-        const fe gen = sq_times(root28(), 28 - (n + cfg.starting_log_inv_rate));
-        fe exp_gen = sq_times(gen, k);
+        fe exp_gen = pk::folded_domain_generator(n + cfg.starting_log_inv_rate, k);
         uint64_t domain = (uint64_t)1 << (n + cfg.starting_log_inv_rate);
         fe prev_root = com.root;
         bool first = true;
@@ -772,14 +614,15 @@ class Walk {
             size_t hn;
             if (!A.hint(p, hn)) return false;
             Rd rd{p, hn};
-            if (!parse_vec(rd, deferred) || !rd.end() || deferred.size() != claimed_sums.size())
+            if (!pk::parse_vec(rd, deferred) || !rd.end() || deferred.size() != claimed_sums.size())
                 return A.fail(PKV_CHECK_HINT_FORMAT, "bad deferred_weight_evaluations hint");
         }
         rev.assign(total.rbegin(), total.rend());
         // computeWPoly (whir_utilities.go:127-157)
         fe value = f_zero();
+        std::vector<fe> pt(n);
         for (size_t j = 0; j < n_ood; j++) {
-            const std::vector<fe> pt = expand_from_univariate(com.ood_pts[j], n);
+            pk::expand_from_univariate(com.ood_pts[j], n, pt.data());
             value = pk::h_add(value, pk::h_mul(comb0[j], eq_poly(pt.data(), rev.data(), n)));
         }
         for (size_t i = 0; i < deferred.size(); i++) value = pk::h_add(value, pk::h_mul(comb0[n_ood + i], deferred[i].mont));
@@ -787,7 +630,7 @@ class Walk {
         for (const RoundData& rd : rounds_data) {
             nv -= k;
             for (size_t i = 0; i < rd.pts.size(); i++) {
-                const std::vector<fe> pt = expand_from_univariate(rd.pts[i], nv);
+                pk::expand_from_univariate(rd.pts[i], nv, pt.data());
                 value = pk::h_add(value, pk::h_mul(rd.comb[i], eq_poly(pt.data(), rev.data(), nv)));
             }
         }

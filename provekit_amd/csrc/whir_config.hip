@@ -5,7 +5,7 @@
 #include <cmath>
 
 #include "internal.hpp"
-#include "transcript.hpp"
+#include "protocol.hpp"
 
 namespace pk {
 
@@ -82,11 +82,11 @@ std::string whir_r1cs_io_pattern(unsigned m_0, const pk_whir_config& w, const pk
     };
     auto A = [&](size_t n, const char* l) { if (n) op('A', n, l); };
     auto S = [&](size_t n, const char* l) { if (n) op('S', n, l); };
-    auto challenge_bytes = [&](size_t n, const char* l) { S((n + 14) / 15, l); };  // 15 uniform bytes per squeezed element
-    auto pow = [&](double bits) {  // spongefish-pow challenge_pow: 32 challenge bytes, 8-byte nonce
+    auto challenge_bytes = [&](size_t n, const char* l) { S(units_for_bytes(n), l); };
+    auto pow = [&](double bits) {  // spongefish-pow challenge_pow: the challenge bytes, then the nonce's
         if (bits > 0.0) {
-            challenge_bytes(32, "pow_queries");
-            A(8, "pow-nonce");
+            challenge_bytes(POW_CHALLENGE_BYTES, "pow_queries");
+            A(POW_NONCE_BYTES, "pow-nonce");
         }
     };
     auto add_ood = [&](size_t samples, size_t batch) {
@@ -104,10 +104,6 @@ std::string whir_r1cs_io_pattern(unsigned m_0, const pk_whir_config& w, const pk
         add_ood(c.commitment_ood_samples, c.batch_size);
         if (c.batch_size > 1) S(1, "batching_randomness");  // drawn right after the commitment (mtUtilities.go:71-75)
     };
-    auto query_bytes = [](size_t domain, unsigned fold) {
-        const size_t folded = domain >> fold;
-        return (size_t)((ilog2(folded) + 7) / 8);
-    };
     auto add_whir_proof = [&](const pk_whir_config& c) {
         const unsigned k = c.folding_factor;
         S(1, "initial_combination_randomness");
@@ -117,7 +113,7 @@ std::string whir_r1cs_io_pattern(unsigned m_0, const pk_whir_config& w, const pk
             A(1, "merkle_digest");
             add_ood(c.ood_samples[r], 1);
             pow(c.pow_bits[r]);
-            challenge_bytes((size_t)c.num_queries[r] * query_bytes(domain, k), "stir_queries");
+            challenge_bytes((size_t)c.num_queries[r] * stir_query_bytes(domain, k), "stir_queries");
             op('H', 0, "stir_answers");
             op('H', 0, "merkle_proof");
             S(1, "combination_randomness");
@@ -127,7 +123,7 @@ std::string whir_r1cs_io_pattern(unsigned m_0, const pk_whir_config& w, const pk
         const unsigned final_vars = c.n_vars - k * (c.n_rounds + 1);
         A((size_t)1 << final_vars, "final_coeffs");
         pow(c.final_pow_bits);
-        challenge_bytes((size_t)c.final_queries * query_bytes(domain, k), "final_queries");
+        challenge_bytes((size_t)c.final_queries * stir_query_bytes(domain, k), "final_queries");
         op('H', 0, "stir_answers");
         op('H', 0, "merkle_proof");
         add_sumcheck(final_vars);

@@ -28,6 +28,7 @@
 
 #define PK_BASE_PRIO 2
 #include "internal.hpp"
+#include "postcard.hpp"
 #include "fe29.hpp"
 #include "feinv.hpp"
 #include "reduce.hpp"
@@ -304,35 +305,10 @@ inline uint64_t program_item_budget(size_t input_bytes) {
     const uint64_t prop = (1ull << 20) + 64ull * (uint64_t)input_bytes;
     return prop < PK_MAX_PROGRAM_ITEMS ? prop : PK_MAX_PROGRAM_ITEMS;
 }
-struct Reader {
-    const uint8_t* p;
-    size_t n, off = 0;
-    bool ok = true;
-    uint64_t varint() {
-        uint64_t v = 0;
-        for (unsigned shift = 0; shift < 70; shift += 7) {
-            if (off >= n) return ok = false, 0;
-            const uint8_t b = p[off++];
-            if (shift == 63 && b > 1) return ok = false, 0;
-            v |= (uint64_t)(b & 0x7f) << shift;
-            if (!(b & 0x80)) return v;
-        }
-        return ok = false, 0;
-    }
+struct Reader : postcard::Reader {
     u32 index() {  // a usize that must be a witness index, an ACIR index or a table size: below 2^27 (a scheme holds at most 2^26
                    // witnesses, pk_scheme_create), so a corrupted list cannot ask for tables of gigabytes
-        const uint64_t v = varint();
-        if (v >= PK_MAX_WITNESS_INDEX) ok = false;
-        return (u32)v;
-    }
-    // serde_ark: bytes(32) = varint(32) | canonical little-endian (provekit/common/src/utils/serde_ark.rs:11-30)
-    bool field(fe& out) {
-        if (varint() != 32 || !ok || n - off < 32) return ok = false;
-        memcpy(out.v, p + off, 32);
-        off += 32;
-        fe red = fe_reduce_any(out);
-        if (memcmp(red.v, out.v, 32) != 0) return ok = false;  // Fp::deserialize_compressed rejects values >= p
-        return true;
+        return (u32)below(PK_MAX_WITNESS_INDEX);
     }
 };
 
@@ -426,8 +402,8 @@ bool parse_builder(Reader& rd, Program& P, u32 bi, Parsed& b) {
         }
         case 2: {  // Sum(idx, Vec<SumTerm(Option<F>, usize)>)
             WbItem it = item(OP_SUM, rd.index());
-            const uint64_t n = rd.varint();
-            if (!rd.ok || n > rd.n - rd.off) return rd.ok = false;
+            const uint64_t n = rd.vec_len();
+            if (!rd.ok) return false;
             it.w[0] = (u32)P.extra.size();
             it.w[1] = (u32)n;
             for (uint64_t i = 0; i < n; i++) {
@@ -462,8 +438,8 @@ bool parse_builder(Reader& rd, Program& P, u32 bi, Parsed& b) {
         }
         case 4: {  // MultiplicitiesForRange(start, range_size, Vec<usize>)
             const u32 start = rd.index(), range = rd.index();
-            const uint64_t n = rd.varint();
-            if (!rd.ok || n > rd.n - rd.off) return rd.ok = false;
+            const uint64_t n = rd.vec_len();
+            if (!rd.ok) return false;
             // the table is expanded to one work item per entry: an absurd size from untrusted bytes must not drive host allocations
             if (range > (1u << 26) || P.n_counts + range > (1ull << 28)) return rd.ok = false;
             if ((uint64_t)start + range > PK_MAX_WITNESS_INDEX || !budget(n + range)) return rd.ok = false;
@@ -529,12 +505,12 @@ bool parse_builder(Reader& rd, Program& P, u32 bi, Parsed& b) {
         }
         case 10: {  // DigitalDecomposition(DigitalDecompositionWitnesses) (witness/digits.rs:10-21 of common)
             std::vector<u32> log_bases, values;
-            uint64_t n = rd.varint();
-            if (!rd.ok || n > rd.n - rd.off) return rd.ok = false;
+            uint64_t n = rd.vec_len();
+            if (!rd.ok) return false;
             for (uint64_t i = 0; i < n; i++) log_bases.push_back(rd.index());
             const u32 declared = rd.index();
-            n = rd.varint();
-            if (!rd.ok || n > rd.n - rd.off) return rd.ok = false;
+            n = rd.vec_len();
+            if (!rd.ok) return false;
             for (uint64_t i = 0; i < n; i++) values.push_back(rd.index());
             const u32 first = rd.index();
             (void)rd.index();  // num_witnesses
@@ -589,8 +565,8 @@ bool parse_builder(Reader& rd, Program& P, u32 bi, Parsed& b) {
             sb.initial_start = rd.index();
             // three reads / writes per cell are recorded below: charged to the budget before anything is pushed
             if ((uint64_t)sb.initial_start + sb.memory_length > PK_MAX_WITNESS_INDEX || !budget(3ull * sb.memory_length)) return rd.ok = false;
-            const uint64_t n = rd.varint();
-            if (!rd.ok || n > rd.n - rd.off || !budget(n)) return rd.ok = false;
+            const uint64_t n = rd.vec_len();
+            if (!rd.ok || !budget(n)) return rd.ok = false;
             for (uint64_t i = 0; i < n; i++) {
                 const uint64_t kind = rd.varint();
                 SpiceOp op{};
@@ -640,8 +616,8 @@ bool parse_builder(Reader& rd, Program& P, u32 bi, Parsed& b) {
         }
         case 14: {  // MultiplicitiesForBinOp(idx, Vec<(CoW, CoW)>)
             const u32 start = rd.index();
-            const uint64_t n = rd.varint();
-            if (!rd.ok || n > rd.n - rd.off) return rd.ok = false;
+            const uint64_t n = rd.vec_len();
+            if (!rd.ok) return false;
             if (P.n_counts + 65536 > (1ull << 28)) return rd.ok = false;
             if ((uint64_t)start + 65536 > PK_MAX_WITNESS_INDEX || !budget(n + 65536)) return rd.ok = false;
             const u32 base = (u32)P.n_counts;
@@ -666,7 +642,7 @@ bool parse_builder(Reader& rd, Program& P, u32 bi, Parsed& b) {
 
 // decode + level.  Returns false with P.error set on malformed input or a list the reference itself would panic on.
 bool build_program(const uint8_t* bytes, size_t len, Program& P, size_t* consumed) {
-    Reader rd{bytes, len};
+    Reader rd{{bytes, len}};
     const uint64_t n = rd.varint();
     if (!rd.ok || n > len) return P.error = "postcard Vec<WitnessBuilder>: truncated", false;
     P.n_builders = (size_t)n;
