@@ -394,7 +394,7 @@ class Walk {
         return true;
     }
 
-  private:
+  protected:  // a walk of another statement around the same WHIR proof (whir_pcs/) derives from this one
     struct Commitment {
         fe root;  // canonical
         std::vector<fe> ood_pts;

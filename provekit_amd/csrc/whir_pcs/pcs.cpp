@@ -1,0 +1,415 @@
+// pcs.cpp -- the device half of libprovekit_whir.so's C ABI: the scheme and its arena, pkw_commit, pkw_open.
+//
+// pkw_open is whir::Prover::prove restated over the product library's PUBLIC entry points (provekit_hip.h) -- the same steps in the
+// same order as prover.hip's WhirProver, which drives them through the library's internals -- with the prover side of the sponge
+// (prover_transcript.hpp) enforcing pkw_io_pattern operation by operation.  The linear statements are the weights eq(point_i, .):
+// pk_eq_accumulate adds them to the OOD weights with their powers of the combination randomness, so no weight table is ever
+// materialised, and their deferred evaluations eq(point_i, folding point) are O(n) products on the host.
+#include <hip/hip_runtime.h>
+
+#include "../prover_transcript.hpp"
+#include "evaluate.hpp"
+#include "pcs.hpp"
+
+using pk::fe;
+
+struct pkw_scheme {
+    pk_ctx* ctx = nullptr;
+    pk_whir_config cfg{};
+    std::string pattern_cache[PKW_MAX_POINTS + 1];
+    std::string err;
+    hipStream_t stream = nullptr;  // the evaluation kernel's
+    uint64_t* arena = nullptr;
+    size_t arena_fes = 0;
+};
+
+struct pkw_commitment {
+    const pkw_scheme* scheme = nullptr;
+    pk_ctx* ctx = nullptr;
+    uint64_t* block = nullptr;  // one allocation: evaluations, coefficients, codeword, tree
+    const uint64_t* evals[4] = {};
+    const uint64_t* coeffs[4] = {};
+    uint64_t *leaves = nullptr, *nodes = nullptr;
+    size_t rows = 0, width = 0;
+    pk_commit_layout layout{};
+    uint8_t root[32] = {};
+};
+
+namespace pkw {
+namespace {
+
+#define CK(expr)                     \
+    do {                             \
+        const int rc_ = (expr);      \
+        if (rc_ != PK_OK) return rc_; \
+    } while (0)
+
+inline uint64_t* U(fe* p) { return reinterpret_cast<uint64_t*>(p); }
+inline const uint64_t* U(const fe* p) { return reinterpret_cast<const uint64_t*>(p); }
+
+int fail(pkw_scheme* s, int rc, const std::string& why) {
+    s->err = why;
+    return rc;
+}
+
+// the arena, handed out front to back; an opening starts from the front again
+struct Bump {
+    uint64_t* base;
+    size_t cap, used = 0;
+    uint64_t* take(size_t fes) {
+        fes = round8(fes ? fes : 1);
+        if (used + fes > cap) return nullptr;
+        uint64_t* p = base + 4 * used;
+        used += fes;
+        return p;
+    }
+};
+#define TAKE(var, fes)                         \
+    uint64_t* var = A.take(fes);               \
+    if (!var) return PK_ERR_OOM /* plan() and the opening disagree: a bug of this file */
+
+struct Tree {  // a committed codeword: what a round's STIR queries open
+    const uint64_t *leaves, *nodes;
+    size_t rows, width;
+    pk_commit_layout layout;
+};
+
+struct Opening {
+    pkw_scheme& S;
+    const pkw_commitment& C;
+    pk::Transcript& T;
+    Bump A;
+    pk_ctx* ctx;
+    const pk_whir_config& cfg;
+    const unsigned n, k;
+    uint64_t *p[2] = {}, *w[2] = {};
+    int cur = 0;
+    size_t len;
+    std::vector<fe> rs, all_r;
+
+    Opening(pkw_scheme& s, const pkw_commitment& c, pk::Transcript& t)
+        : S(s), C(c), T(t), A{s.arena, s.arena_fes}, ctx(s.ctx), cfg(s.cfg), n(s.cfg.n_vars), k(s.cfg.folding_factor), len((size_t)1 << s.cfg.n_vars) {}
+
+    // dst = sum_b beta^b x_b (mtUtilities.go:98-114)
+    int batch_combine(uint64_t* dst, const uint64_t* const* x, const fe& beta) {
+        const size_t N = (size_t)1 << n;
+        CK(pk_memcpy_d2d(ctx, dst, x[0], 32 * N));
+        fe bp = beta;
+        for (unsigned b = 1; b < cfg.batch_size; b++) {
+            CK(pk_fe_axpy(ctx, dst, U(&bp), x[b], N));
+            bp = pk::h_mul(bp, beta);
+        }
+        return PK_OK;
+    }
+    // w (+)= sum_j scale0 * gamma^j * eq(pts_j, .) over nv variables; *next = the following power
+    int eq_weights(uint64_t* dst, unsigned nv, const std::vector<fe>& pts, size_t count, const fe& gamma, fe g, int overwrite, fe* next) {
+        std::vector<fe> scales(count ? count : 1);
+        for (size_t j = 0; j < count; j++) {
+            scales[j] = g;
+            g = pk::h_mul(g, gamma);
+        }
+        *next = g;
+        if (!count) return pk_eq_accumulate(ctx, dst, nv, nullptr, nullptr, 0, overwrite);
+        for (size_t j0 = 0; j0 < count; j0 += 32) {  // the points travel through the context's pinned mailbox: modest pieces
+            const size_t c = std::min<size_t>(32, count - j0);
+            CK(pk_eq_accumulate(ctx, dst, nv, U(pts.data() + j0 * nv), U(scales.data() + j0), (unsigned)c, overwrite && j0 == 0));
+        }
+        return PK_OK;
+    }
+    void flip() {
+        cur = 1 - cur;
+        len /= 2;
+    }
+    // the same steps in the same order as WhirProver::sumcheck_rounds (prover.hip), synchronous form
+    int sumcheck_rounds(unsigned rounds) {
+        rs.clear();
+        for (unsigned t = 0; t < rounds; t++) {
+            uint64_t out[12];
+            CK(pk_sumcheck_quadratic_round(ctx, p[cur], w[cur], len, t ? U(&rs.back()) : nullptr, p[1 - cur], w[1 - cur], out));
+            if (t) flip();
+            const fe msg[3] = {pk::h_load(out), pk::h_load(out + 4), pk::h_load(out + 8)};
+            T.add_scalars(msg, 3);
+            const fe r = T.challenge_scalar();
+            rs.push_back(r);
+            all_r.push_back(r);
+        }
+        if (rounds && len >= 2) {  // apply the last challenge: p, w now describe the folded polynomial
+            CK(pk_fold_pairs(ctx, p[cur], len, U(&rs.back()), p[1 - cur]));
+            CK(pk_fold_pairs(ctx, w[cur], len, U(&rs.back()), w[1 - cur]));
+            flip();
+        }
+        return PK_OK;
+    }
+    std::vector<uint64_t> stir_queries(size_t domain, unsigned queries) {
+        std::vector<uint8_t> raw(pk::stir_query_bytes(domain, k) * queries);
+        T.challenge_bytes(raw.data(), raw.size());
+        return pk::stir_indexes(raw.data(), domain, k, queries);
+    }
+    int pow_round(double bits) {
+        if (bits <= 0.0) return PK_OK;
+        uint8_t challenge[pk::POW_CHALLENGE_BYTES], be[pk::POW_NONCE_BYTES];
+        T.challenge_bytes(challenge, sizeof challenge);
+        uint64_t nonce = 0;
+        CK(pk_pow_solve(ctx, challenge, bits, &nonce));
+        pk::nonce_to_bytes(nonce, be);
+        T.add_bytes(be, sizeof be);
+        return PK_OK;
+    }
+    // hints: stir_answers = Vec<Vec<F>> and merkle_proof = ark MultiPath (common.go:36-61)
+    int opening_hints(const Tree& t, const std::vector<uint64_t>& idx) {
+        const size_t q = idx.size();
+        unsigned logn = 0;
+        while (((size_t)1 << logn) < t.rows) logn++;
+        const size_t plen = logn ? logn - 1 : 0;
+        std::vector<uint64_t> leaves(4 * q * t.width + 4), sib(4 * q + 4), paths(4 * q * plen + 4);
+        CK(pk_commit_open(ctx, t.leaves, t.nodes, t.rows, t.width, &t.layout, idx.data(), q, /*canonical=*/1, leaves.data(), sib.data(), paths.data()));
+        std::vector<uint8_t> buf;
+        pk::put_u64(buf, q);
+        for (size_t j = 0; j < q; j++) pk::put_vec(buf, (const fe*)(leaves.data() + 4 * j * t.width), t.width, /*montgomery=*/false);
+        T.hint(buf.data(), buf.size());
+        size_t mlen = 0;
+        pk_multipath_serialize(idx.data(), q, plen, sib.data(), paths.data(), nullptr, 0, &mlen);
+        std::vector<uint8_t> mp(mlen ? mlen : 1);
+        CK(pk_multipath_serialize(idx.data(), q, plen, sib.data(), paths.data(), mp.data(), mlen, &mlen));
+        T.hint(mp.data(), mlen);
+        return PK_OK;
+    }
+
+    int run(const fe* points, unsigned q, fe* evals /* batch * q */) {
+        const size_t N = (size_t)1 << n;
+        const unsigned batch = cfg.batch_size;
+        TAKE(scratch, plan(cfg).scratch);
+        // 1-3: the commitment's transcript (mtUtilities.go:51-76)
+        T.add_canon(pk::load_raw(C.root));
+        std::vector<fe> ood(cfg.commitment_ood_samples), ood_ans((size_t)batch * ood.size());
+        T.challenge_scalars(ood.data(), ood.size());
+        for (unsigned b = 0; b < batch; b++)
+            for (size_t j = 0; j < ood.size(); j++) CK(pk_eval_univariate(ctx, C.coeffs[b], N, U(&ood[j]), U(&ood_ans[b * ood.size() + j])));
+        for (unsigned b = 0; b < batch; b++) T.add_scalars(&ood_ans[b * ood.size()], ood.size());
+        const fe beta = batch > 1 ? T.challenge_scalar() : pk::fe_one();
+        // 4, 5: the statement
+        T.add_scalars(points, (size_t)q * n);
+        {
+            TAKE(d_pts, (size_t)q * n);
+            TAKE(d_part, eval_partial_fes(batch, n));
+            TAKE(d_out, (size_t)batch * q);
+            CK(pk_memcpy_h2d(ctx, d_pts, points, 32 * (size_t)q * n));
+            CK(pk_ctx_sync(ctx));
+            CK(eval_launch(S.stream, C.evals, batch, n, d_pts, q, d_part, d_out));
+            if (hipStreamSynchronize(S.stream) != hipSuccess) return PK_ERR_HIP;
+            CK(pk_memcpy_d2h(ctx, evals, d_out, 32 * (size_t)batch * q));
+        }
+        T.add_scalars(evals, (size_t)batch * q);
+        // 6: whir::Prover::prove over the beta-combined polynomial
+        TAKE(d_c0, N);
+        uint64_t* d_c = d_c0;
+        CK(batch_combine(d_c, C.coeffs, beta));
+        TAKE(p0, N);
+        TAKE(p1, N / 2);
+        TAKE(w0, N);
+        TAKE(w1, N / 2);
+        p[0] = p0, p[1] = p1, w[0] = w0, w[1] = w1;
+        CK(batch_combine(p0, C.evals, beta));
+        fe gamma = T.challenge_scalar(), g;
+        {  // weights = sum gamma^i w_i over [OOD constraints..., eq(point_i, .)...]
+            std::vector<fe> pts((ood.size() + q) * n);
+            for (size_t j = 0; j < ood.size(); j++) pk::expand_from_univariate(ood[j], n, &pts[j * n]);
+            std::copy(points, points + (size_t)q * n, pts.begin() + ood.size() * n);
+            CK(eq_weights(w0, n, pts, ood.size() + q, gamma, pk::fe_one(), /*overwrite=*/1, &g));
+        }
+        CK(sumcheck_rounds(k));
+        Tree prev{C.leaves, C.nodes, C.rows, C.width, C.layout};
+        unsigned nv = n, rate = cfg.starting_log_inv_rate;
+        size_t domain = (size_t)1 << (n + rate);
+        fe exp_gen = pk::folded_domain_generator(n + rate, k);
+        for (unsigned r = 0; r < cfg.n_rounds; r++) {  // whir.go:51-220
+            const unsigned nv2 = nv - k;
+            TAKE(d_c2, (size_t)1 << nv2);
+            CK(pk_fold_coeffs(ctx, d_c, nv, U(rs.data()), k, d_c2));
+            d_c = d_c2;
+            nv = nv2;
+            rate += k - 1;
+            Tree next{};
+            next.rows = (size_t)1 << (nv + rate - k);
+            next.width = (size_t)1 << k;
+            TAKE(leaves, next.rows * next.width);
+            TAKE(nodes, 2 * next.rows);
+            next.leaves = leaves, next.nodes = nodes;
+            fe root;
+            const uint64_t* cp[1] = {d_c};
+            CK(pk_commit_into(ctx, cp, 1, nv, rate, k, leaves, nodes, scratch, (uint8_t*)root.v, &next.layout));
+            T.add_canon(root);
+            std::vector<fe> zs(cfg.ood_samples[r]), ans(cfg.ood_samples[r]);
+            T.challenge_scalars(zs.data(), zs.size());
+            for (size_t j = 0; j < zs.size(); j++) CK(pk_eval_univariate(ctx, d_c, (size_t)1 << nv, U(&zs[j]), U(&ans[j])));
+            T.add_scalars(ans.data(), ans.size());
+            CK(pow_round(cfg.pow_bits[r]));
+            const std::vector<uint64_t> idx = stir_queries(domain, cfg.num_queries[r]);
+            CK(opening_hints(prev, idx));
+            gamma = T.challenge_scalar();
+            for (uint64_t i : idx) zs.push_back(pk::h_pow(exp_gen, i));
+            std::vector<fe> pts(zs.size() * (nv ? nv : 1));
+            for (size_t j = 0; j < zs.size(); j++) pk::expand_from_univariate(zs[j], nv, &pts[j * nv]);
+            CK(eq_weights(w[cur], nv, pts, zs.size(), gamma, pk::fe_one(), 0, &g));
+            CK(sumcheck_rounds(k));
+            prev = next;
+            domain /= 2;
+            exp_gen = pk::h_mul(exp_gen, exp_gen);
+        }
+        // the final round: the folded polynomial in the clear, PoW, final STIR openings, final sumcheck
+        const unsigned final_vars = nv - k;
+        TAKE(d_final, (size_t)1 << final_vars);
+        CK(pk_fold_coeffs(ctx, d_c, nv, U(rs.data()), k, d_final));
+        std::vector<fe> fin((size_t)1 << final_vars);
+        CK(pk_memcpy_d2h(ctx, fin.data(), d_final, 32 * fin.size()));
+        T.add_scalars(fin.data(), fin.size());
+        CK(pow_round(cfg.final_pow_bits));
+        CK(opening_hints(prev, stir_queries(domain, cfg.final_queries)));
+        CK(sumcheck_rounds(final_vars));
+        CK(pow_round(cfg.final_folding_pow_bits));
+        // deferred_weight_evaluations: each weight's MLE at the folding point, reverse(all_r) in eval_eq's MSB-first order; for
+        // eq(point_i, .) that is eq(point_i, folding point)
+        const std::vector<fe> point(all_r.rbegin(), all_r.rend());
+        std::vector<fe> deferred(q);
+        for (unsigned i = 0; i < q; i++) deferred[i] = pkv::eq_poly(points + (size_t)i * n, point.data(), n);
+        std::vector<uint8_t> buf;
+        pk::put_vec(buf, deferred.data(), q);
+        T.hint(buf.data(), buf.size());
+        return PK_OK;
+    }
+};
+
+}  // namespace
+}  // namespace pkw
+
+extern "C" {
+
+const char* pkw_last_error(const pkw_scheme* s) { return s ? s->err.c_str() : "null scheme"; }
+
+int pkw_scheme_create(pk_ctx* ctx, const pk_whir_config* cfg, pkw_scheme** out) {
+    if (out) *out = nullptr;
+    if (!ctx || !out) return pkw::refuse("null pointer");
+    std::string why;
+    if (!pkw::config_ok(cfg, why)) return pkw::refuse(why);
+    int rank = 0, world = 1, kind = 0;
+    if (pk_comm_info(ctx, &rank, &world, &kind) == PK_OK && world > 1) return pkw::refuse("contexts of a device set are not supported");
+    try {
+        pkw_scheme* s = new pkw_scheme();
+        s->ctx = ctx;
+        s->cfg = *cfg;
+        s->arena_fes = pkw::plan(*cfg).total;
+        int rc = pk_ctx_sync(ctx);  // selects the context's device on this thread
+        if (!rc) rc = pk_malloc(ctx, 32 * s->arena_fes, (void**)&s->arena);
+        if (!rc && hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess) rc = PK_ERR_HIP;
+        if (rc) {
+            pkw::g_error = std::string("arena: ") + pk_last_error(ctx);
+            pkw_scheme_destroy(s);
+            return rc;
+        }
+        *out = s;
+        pkw::g_error.clear();
+        return PK_OK;
+    } catch (...) {
+        pkw::g_error = "out of memory";
+        return PK_ERR_OOM;
+    }
+}
+
+int pkw_scheme_destroy(pkw_scheme* s) {
+    if (!s) return PK_OK;
+    pk_ctx_sync(s->ctx);  // also selects the device
+    if (s->stream) (void)hipStreamDestroy(s->stream);
+    if (s->arena) pk_free(s->ctx, s->arena);
+    delete s;
+    return PK_OK;
+}
+
+int pkw_commit(pkw_scheme* s, const uint64_t* const* d_evals, pkw_commitment** out) {
+    if (out) *out = nullptr;
+    if (!s) return PK_ERR_BAD_ARG;
+    if (!d_evals || !out) return pkw::fail(s, PK_ERR_BAD_ARG, "null pointer");
+    const pk_whir_config& c = s->cfg;
+    for (unsigned b = 0; b < c.batch_size; b++)
+        if (!d_evals[b]) return pkw::fail(s, PK_ERR_BAD_ARG, "null polynomial");
+    pkw_commitment* com = nullptr;
+    try {
+        com = new pkw_commitment();
+    } catch (...) {
+        return pkw::fail(s, PK_ERR_OOM, "out of memory");
+    }
+    com->scheme = s;
+    com->ctx = s->ctx;
+    const size_t N = (size_t)1 << c.n_vars;
+    size_t leaves_fes = 0, nodes_fes = 0, scratch_fes = 0;
+    int rc = pk_commit_sizes(s->ctx, c.batch_size, c.n_vars, c.starting_log_inv_rate, c.folding_factor, &leaves_fes, &nodes_fes, &scratch_fes);
+    if (!rc && scratch_fes > s->arena_fes) rc = PK_ERR_OOM;
+    if (!rc) rc = pk_malloc(s->ctx, 32 * (2 * c.batch_size * N + leaves_fes + nodes_fes), (void**)&com->block);
+    if (!rc) {
+        uint64_t* at = com->block;
+        for (unsigned b = 0; b < c.batch_size && !rc; b++) {
+            uint64_t *ev = at, *co = at + 4 * N;
+            at += 8 * N;
+            com->evals[b] = ev;
+            com->coeffs[b] = co;
+            rc = pk_memcpy_d2d(s->ctx, ev, d_evals[b], 32 * N);
+            if (!rc) rc = pk_to_coeffs_into(s->ctx, ev, co, c.n_vars);
+        }
+        com->leaves = at;
+        com->nodes = at + 4 * leaves_fes;
+        com->rows = (size_t)1 << (c.n_vars + c.starting_log_inv_rate - c.folding_factor);
+        com->width = (size_t)c.batch_size << c.folding_factor;
+        if (!rc)
+            rc = pk_commit_into(s->ctx, com->coeffs, c.batch_size, c.n_vars, c.starting_log_inv_rate, c.folding_factor, com->leaves, com->nodes, s->arena,
+                                com->root, &com->layout);
+    }
+    if (rc) {
+        s->err = std::string("commit: ") + pk_last_error(s->ctx);
+        pkw_commitment_destroy(com);
+        return rc;
+    }
+    *out = com;
+    return PK_OK;
+}
+
+int pkw_commitment_root(const pkw_commitment* com, uint8_t root[32]) {
+    if (!com || !root) return PK_ERR_BAD_ARG;
+    memcpy(root, com->root, 32);
+    return PK_OK;
+}
+
+int pkw_commitment_destroy(pkw_commitment* com) {
+    if (!com) return PK_OK;
+    if (com->block) {
+        pk_ctx_sync(com->ctx);
+        pk_free(com->ctx, com->block);
+    }
+    delete com;
+    return PK_OK;
+}
+
+int pkw_open(pkw_scheme* s, const pkw_commitment* com, const uint64_t* points, unsigned q, uint64_t* evals_out, uint8_t* proof_out, size_t cap,
+             size_t* len) {
+    if (!s) return PK_ERR_BAD_ARG;
+    if (!com || !points || !len || (cap && !proof_out)) return pkw::fail(s, PK_ERR_BAD_ARG, "null pointer");
+    if (com->scheme != s) return pkw::fail(s, PK_ERR_BAD_ARG, "the commitment belongs to another scheme");
+    if (q < 1 || q > PKW_MAX_POINTS) return pkw::fail(s, PK_ERR_BAD_ARG, "the number of points must be 1..64");
+    try {
+        if (s->pattern_cache[q].empty()) s->pattern_cache[q] = pkw::io_pattern(s->cfg, q);
+        pk::Transcript T(s->pattern_cache[q]);
+        std::vector<fe> evals((size_t)s->cfg.batch_size * q);
+        pkw::Opening op(*s, *com, T);
+        const int rc = op.run(reinterpret_cast<const fe*>(points), q, evals.data());
+        if (rc) return pkw::fail(s, rc, rc == PK_ERR_OOM ? "the arena is too small for this opening" : std::string("open: ") + pk_last_error(s->ctx));
+        if (!T.finished())
+            return pkw::fail(s, PK_ERR_IO_PATTERN, T.violation().empty() ? "the proof ended before its IO pattern did" : T.violation());
+        *len = T.narg.size();
+        if (cap < T.narg.size()) return pkw::fail(s, PK_ERR_BAD_ARG, "proof buffer too small: " + std::to_string(T.narg.size()) + " bytes needed");
+        memcpy(proof_out, T.narg.data(), T.narg.size());
+        if (evals_out) memcpy(evals_out, evals.data(), 32 * evals.size());
+        return PK_OK;
+    } catch (...) {
+        return pkw::fail(s, PK_ERR_OOM, "out of memory");
+    }
+}
+
+}  // extern "C"

@@ -1,0 +1,127 @@
+// pcs.hpp -- what the three sources of libprovekit_whir.so share: which configs the library takes, and the IO pattern of an opening
+// proof.  Host only.  The wire rules (sponge, hint framing, STIR indexes, PoW bytes) are protocol.hpp's; the verifier side of the
+// transcript and the WHIR walk are verify/core.hpp's.
+#pragma once
+#include <string>
+
+#include "../../../include/provekit_whir.h"
+#include "../verify/core.hpp"
+#include "evaluate.hpp"
+
+namespace pkw {
+
+using pk::fe;
+
+extern thread_local std::string g_error;  // pkw_create_error
+inline int refuse(const std::string& why) {
+    g_error = why;
+    return PK_ERR_BAD_ARG;
+}
+
+// a config both sides take: the prover's bounds (what pk_whir_r1cs_io_pattern refuses, the product library's own rule) and the
+// verifier core's
+inline bool config_ok(const pk_whir_config* c, std::string& why) {
+    if (!c) {
+        why = "null config";
+        return false;
+    }
+    size_t n = 0;
+    if (pk_whir_r1cs_io_pattern(1, c, c, nullptr, 0, &n) != PK_OK) {
+        why = "pk_whir_r1cs_io_pattern refuses this config";
+        return false;
+    }
+    return pkv::config_ok(*c, why);
+}
+
+// "<domain>" then commit_statement, the statement, add_whir_proof -- the operations and labels of whir_config.hip's restatement of
+// whir's pattern, zero-count operations omitted where whir guards them
+inline std::string io_pattern(const pk_whir_config& c, unsigned q) {
+    std::string d = "provekit-hip/whir-pcs/v1";
+    auto op = [&](char kind, size_t count, const char* label) {
+        d.push_back('\0');
+        d.push_back(kind);
+        if (kind == 'A' || kind == 'S') d += std::to_string(count);
+        d += label;
+    };
+    auto A = [&](size_t n, const char* l) { if (n) op('A', n, l); };
+    auto S = [&](size_t n, const char* l) { if (n) op('S', n, l); };
+    auto pow = [&](double bits) {
+        if (bits > 0.0) {
+            S(pk::units_for_bytes(pk::POW_CHALLENGE_BYTES), "pow_queries");
+            A(pk::POW_NONCE_BYTES, "pow-nonce");
+        }
+    };
+    auto sumcheck = [&](unsigned rounds) {
+        for (unsigned i = 0; i < rounds; i++) {
+            A(3, "sumcheck_poly");
+            S(1, "folding_randomness");
+        }
+    };
+    auto openings = [&](size_t domain, unsigned queries, const char* label) {
+        S(pk::units_for_bytes((size_t)queries * pk::stir_query_bytes(domain, c.folding_factor)), label);
+        op('H', 0, "stir_answers");
+        op('H', 0, "merkle_proof");
+    };
+    // commit_statement
+    A(1, "merkle_digest");
+    S(c.commitment_ood_samples, "ood_query");
+    A((size_t)c.commitment_ood_samples * c.batch_size, "ood_ans");
+    if (c.batch_size > 1) S(1, "batching_randomness");
+    // the statement: where, and what the polynomials are claimed to be there
+    A((size_t)q * c.n_vars, "points");
+    A((size_t)q * c.batch_size, "evaluations");
+    // add_whir_proof
+    const unsigned k = c.folding_factor;
+    S(1, "initial_combination_randomness");
+    sumcheck(k);
+    size_t domain = (size_t)1 << (c.n_vars + c.starting_log_inv_rate);
+    for (unsigned r = 0; r < c.n_rounds; r++) {
+        A(1, "merkle_digest");
+        S(c.ood_samples[r], "ood_query");
+        A(c.ood_samples[r], "ood_ans");
+        pow(c.pow_bits[r]);
+        openings(domain, c.num_queries[r], "stir_queries");
+        S(1, "combination_randomness");
+        sumcheck(k);
+        domain >>= 1;
+    }
+    const unsigned final_vars = c.n_vars - k * (c.n_rounds + 1);
+    A((size_t)1 << final_vars, "final_coeffs");
+    pow(c.final_pow_bits);
+    openings(domain, c.final_queries, "final_queries");
+    sumcheck(final_vars);
+    pow(c.final_folding_pow_bits);
+    op('H', 0, "deferred_weight_evaluations");
+    return d;
+}
+
+// the device memory one opening needs, in field elements, for a context outside a device set (pk_commit_sizes' rule there:
+// leaves = rows * width, nodes = 2 rows, scratch = 2 rows * width).  Every buffer is rounded up to 8 elements.
+struct Plan {
+    size_t total = 0, scratch = 0;
+};
+inline size_t round8(size_t fes) { return (fes + 7) & ~(size_t)7; }
+inline Plan plan(const pk_whir_config& c) {
+    Plan p;
+    const unsigned n = c.n_vars, k = c.folding_factor;
+    const size_t N = (size_t)1 << n;
+    auto commit_scratch = [&](unsigned nv, unsigned rate, unsigned batch) { return 2 * ((size_t)1 << (nv + rate - k)) * ((size_t)batch << k); };
+    p.scratch = commit_scratch(n, c.starting_log_inv_rate, c.batch_size);  // pkw_commit's
+    p.total += 3 * round8(N) + 2 * round8(N / 2 ? N / 2 : 1);              // combined coefficients, p and w with their halves
+    unsigned nv = n, rate = c.starting_log_inv_rate;
+    for (unsigned r = 0; r <= c.n_rounds; r++) {  // the folded polynomials, the last one being the final coefficients
+        nv -= k;
+        p.total += round8((size_t)1 << nv);
+        if (r == c.n_rounds) break;
+        rate += k - 1;
+        const size_t rows = (size_t)1 << (nv + rate - k);
+        p.total += round8(rows << k) + round8(2 * rows);
+        p.scratch = std::max(p.scratch, commit_scratch(nv, rate, 1));
+    }
+    p.total += round8(p.scratch);
+    // pkw_open's evaluations: the points, the kernel's partial sums, the results
+    p.total += round8((size_t)PKW_MAX_POINTS * n) + round8(eval_partial_fes(c.batch_size, n)) + round8((size_t)PKW_MAX_POINTS * c.batch_size);
+    return p;
+}
+
+}  // namespace pkw

@@ -1,0 +1,202 @@
+"""WHIR as a polynomial commitment scheme (libprovekit_whir.so, include/provekit_whir.h): commit to up to 4 multilinear
+polynomials, open them at points of the caller's choice, verify the opening.  PLAIN WHIR, not hiding.
+
+A fourth library above the product's C ABI, with its own loader and signature table (as provekit_amd.verify).  `verify` and
+`io_pattern` are host only; `Scheme` needs a Context.  A rejected proof is a Result, not an exception; only a failed CALL raises.
+There is no fallback: without the built library the import raises."""
+from __future__ import annotations
+
+import ctypes as C
+import os
+
+import numpy as np
+
+from ._lib import ProveKitHipError, sz, vp
+from .runtime import Context, DeviceBuffer
+from .scheme import WhirConfig, _cfg_struct
+from .verify import CHECKS as WALK_CHECKS
+from .verify import Result, ResultStruct
+
+WHIR_LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libprovekit_whir.so")
+MAX_POINTS = 64
+CHECKS = WALK_CHECKS + ("POINTS", "ROOT", "DEFERRED")
+
+# name -> (restype, argtypes); kept in the same order as include/provekit_whir.h
+SIGNATURES = {
+    "pkw_abi_version": (C.c_int, []),
+    "pkw_check_name": (C.c_char_p, [C.c_int]),
+    "pkw_create_error": (C.c_char_p, []),
+    "pkw_scheme_create": (C.c_int, [vp, vp, C.POINTER(vp)]),
+    "pkw_scheme_destroy": (C.c_int, [vp]),
+    "pkw_scheme_arena_bytes": (C.c_int, [vp, C.POINTER(sz)]),
+    "pkw_last_error": (C.c_char_p, [vp]),
+    "pkw_io_pattern": (C.c_int, [vp, C.c_uint, vp, sz, C.POINTER(sz)]),
+    "pkw_commit": (C.c_int, [vp, vp, C.POINTER(vp)]),
+    "pkw_commitment_root": (C.c_int, [vp, vp]),
+    "pkw_commitment_destroy": (C.c_int, [vp]),
+    "pkw_evaluate": (C.c_int, [vp, vp, C.c_uint, C.c_uint, vp, C.c_uint, vp]),
+    "pkw_evaluate_low_vars": (C.c_uint, []),
+    "pkw_open": (C.c_int, [vp, vp, vp, C.c_uint, vp, vp, sz, C.POINTER(sz)]),
+    "pkw_verify": (C.c_int, [vp, vp, sz, C.c_int, vp, vp, C.c_uint, vp, sz, vp, C.POINTER(ResultStruct)]),
+}
+
+
+def _load():
+    if not os.path.exists(WHIR_LIB_PATH):
+        raise ImportError(
+            f"{WHIR_LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
+            "(or `make -C provekit_amd/csrc`). provekit_amd has no CPU fallback."
+        )
+    return C.CDLL(WHIR_LIB_PATH)  # its libprovekit_hip.so is the one _lib has loaded (same file, found next to it)
+
+
+lib = _load()
+for _name, (_res, _args) in SIGNATURES.items():
+    _fn = getattr(lib, _name)  # AttributeError here == header/library mismatch: fail loudly
+    _fn.restype = _res
+    _fn.argtypes = _args
+
+
+def _result(r: ResultStruct) -> Result:
+    return Result(bool(r.accepted), CHECKS[r.check] if 0 <= r.check < len(CHECKS) else str(r.check), int(r.offset), r.message.decode(errors="replace"))
+
+
+def _points(points, n_vars: int) -> np.ndarray:
+    """[q, n_vars, 4] Montgomery limbs; variable 0 <-> the most significant index bit"""
+    p = np.ascontiguousarray(points, dtype=np.uint64)
+    if p.ndim != 3 or p.shape[1:] != (n_vars, 4) or p.shape[0] < 1:
+        raise ValueError(f"points must have shape [q, {n_vars}, 4]")
+    return p
+
+
+def _ptr_array(bufs):
+    return (vp * len(bufs))(*(b.ptr if isinstance(b, DeviceBuffer) else int(b) for b in bufs))
+
+
+def low_vars() -> int:
+    """the evaluation kernel's tile: 2^low_vars contiguous evaluations per workgroup step"""
+    return int(lib.pkw_evaluate_low_vars())
+
+
+def io_pattern(cfg: WhirConfig, q: int) -> bytes:
+    """the spongefish operation list (domain separator) of a proof that opens q points (pkw_io_pattern; host only)"""
+    c = _cfg_struct(cfg)
+    n = sz()
+    rc = lib.pkw_io_pattern(C.addressof(c), q, None, 0, C.byref(n))
+    if rc:
+        raise ProveKitHipError(rc, lib.pkw_create_error().decode())
+    buf = (C.c_uint8 * n.value)()
+    lib.pkw_io_pattern(C.addressof(c), q, buf, n.value, C.byref(n))
+    return bytes(buf)
+
+
+def arena_bytes(cfg: WhirConfig) -> int:
+    c = _cfg_struct(cfg)
+    n = sz()
+    rc = lib.pkw_scheme_arena_bytes(C.addressof(c), C.byref(n))
+    if rc:
+        raise ProveKitHipError(rc, lib.pkw_create_error().decode())
+    return n.value
+
+
+def evaluate(ctx: Context, d_evals, n_vars: int, points) -> np.ndarray:
+    """[batch, q, 4] Montgomery: the MLE of every polynomial (device buffers of 2^n_vars evaluations) at every point, each
+    polynomial read once per 8 points (pkw_evaluate)"""
+    p = _points(points, n_vars)
+    out = np.zeros((len(d_evals), p.shape[0], 4), dtype=np.uint64)
+    ctx._check(lib.pkw_evaluate(ctx.handle, C.cast(_ptr_array(d_evals), vp), len(d_evals), n_vars, p.ctypes.data, p.shape[0], out.ctypes.data))
+    return out
+
+
+def verify(cfg: WhirConfig, points, proof: bytes, expected_root: bytes | None = None, io_pattern: bytes | None = None, hash_version: int = 2):
+    """-> (Result, evaluations [batch, q, 4] Montgomery as the proof binds them).  Host only (pkw_verify)."""
+    c = _cfg_struct(cfg)
+    p = _points(points, cfg.n_vars)
+    proof = bytes(proof)
+    evals = np.zeros((cfg.batch_size, p.shape[0], 4), dtype=np.uint64)
+    r = ResultStruct()
+    pat = bytes(io_pattern) if io_pattern else None
+    root = bytes(expected_root) if expected_root is not None else None
+    if root is not None and len(root) != 32:
+        raise ValueError("a root is 32 bytes")
+    rc = lib.pkw_verify(C.addressof(c), pat, len(pat) if pat else 0, hash_version, root, p.ctypes.data, p.shape[0], proof, len(proof),
+                        evals.ctypes.data, C.byref(r))
+    if rc:
+        raise ProveKitHipError(rc, lib.pkw_create_error().decode())
+    return _result(r), evals
+
+
+class Commitment:
+    """What pkw_commit keeps: both forms of the polynomials, the codeword and its tree.  Open it any number of times."""
+
+    def __init__(self, scheme: "Scheme", handle: int):
+        self.scheme, self.handle = scheme, handle
+
+    def root(self) -> bytes:
+        buf = (C.c_uint8 * 32)()
+        self.scheme._check(lib.pkw_commitment_root(self.handle, buf))
+        return bytes(buf)
+
+    def close(self):
+        if self.handle is not None and self.scheme.handle is not None:
+            lib.pkw_commitment_destroy(self.handle)
+        self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Scheme:
+    """One WhirConfig (batch_size polynomials of n_vars variables) bound to a Context, with a device arena sized once."""
+
+    def __init__(self, ctx: Context, cfg: WhirConfig):
+        self.handle = None
+        self.ctx, self.cfg = ctx, cfg
+        c = _cfg_struct(cfg)
+        h = vp()
+        rc = lib.pkw_scheme_create(ctx.handle, C.addressof(c), C.byref(h))
+        if rc:
+            raise ProveKitHipError(rc, lib.pkw_create_error().decode())
+        self.handle = h.value
+        self._buf = None
+
+    def _check(self, rc):
+        if rc:
+            raise ProveKitHipError(rc, lib.pkw_last_error(self.handle).decode())
+
+    def commit(self, d_evals) -> Commitment:
+        """d_evals: batch_size device buffers of 2^n_vars evaluations over the hypercube (Montgomery); they are copied"""
+        if len(d_evals) != self.cfg.batch_size:
+            raise ValueError(f"expected {self.cfg.batch_size} polynomials")
+        h = vp()
+        self._check(lib.pkw_commit(self.handle, C.cast(_ptr_array(d_evals), vp), C.byref(h)))
+        return Commitment(self, h.value)
+
+    def open(self, commitment: Commitment, points, cap: int | None = None):
+        """-> (evaluations [batch, q, 4] Montgomery, proof bytes)"""
+        p = _points(points, self.cfg.n_vars)
+        evals = np.zeros((self.cfg.batch_size, p.shape[0], 4), dtype=np.uint64)
+        if cap is None:
+            if self._buf is None:
+                self._buf = (C.c_uint8 * (8 << 20))()
+            buf = self._buf
+        else:
+            buf = (C.c_uint8 * max(cap, 1))()
+        n = sz()
+        self._check(lib.pkw_open(self.handle, commitment.handle, p.ctypes.data, p.shape[0], evals.ctypes.data, buf, len(buf) if cap is None else cap,
+                                 C.byref(n)))
+        return evals, C.string_at(buf, n.value)
+
+    def close(self):
+        if self.handle is not None and self.ctx.handle is not None:
+            lib.pkw_scheme_destroy(self.handle)
+        self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
