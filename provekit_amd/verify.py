@@ -180,8 +180,9 @@ def openings_check(ctx, leaves, siblings, paths, indices, roots, weights=None, h
     (root -> leaf), indices [k], roots [k, 4], weights [width, 4] Montgomery or None -> (reached [k] bool, folds [k, 4] canonical)"""
     lv = np.ascontiguousarray(leaves, dtype=np.uint64)
     k, width = lv.shape[0], lv.shape[1]
-    pa = np.ascontiguousarray(paths, dtype=np.uint64).reshape(k, -1, 4)
-    depth = pa.shape[1]
+    pa = np.ascontiguousarray(paths, dtype=np.uint64)
+    depth = pa.shape[1] if pa.ndim == 3 else (pa.size // (4 * k) if k else 0)  # k = 0 or depth = 0: nothing for reshape to infer from
+    pa = pa.reshape(k, depth, 4)
     sb, rt = _fe_ptr(siblings, k), _fe_ptr(roots, k)
     ix = np.ascontiguousarray(indices, dtype=np.uint64)
     w = _fe_ptr(weights, width) if weights is not None else None

@@ -213,6 +213,28 @@ def test_agreement_with_the_oracle_under_tampering(oracle, case9):
         assert got.accepted == expected and got.check != "NONE", (name, got)
 
 
+def plus_p(oracle, proof, off):
+    """the 32-byte little-endian element v at `off` replaced by v + p (< 2^256: p < 2^254)"""
+    v = int.from_bytes(proof[off : off + 32], "little")
+    assert v < oracle.P, "not the start of an element"
+    return proof[:off] + (v + oracle.P).to_bytes(32, "little") + proof[off + 32 :]
+
+
+@pytest.mark.parametrize("region,counts_as_v", [("leaf_element", True), ("sibling_digest", True), ("path_digest", True), ("root_0", False),
+                                                ("cubic_message", False), ("final_coefficient", False)])
+def test_an_element_plus_p_gets_the_oracles_verdict(oracle, case9, region, counts_as_v):
+    """bytes a prover of this library never writes: one element v replaced by v + p.  The host core decides as oracle/verifier.py
+    does, and as DESIGN §10 states: leaf elements and digests are only hashed and folded, both mod p, so v + p counts as v; a scalar
+    the sponge absorbs must be canonical"""
+    c = case9
+    proof = plus_p(oracle, c.proof, walk_layout(c.proof, c.m_0, c.cw, c.cb)[region])
+    expected = c.oracle_verdict(proof)
+    got = c.verifier().verify(proof)
+    print(f"{region} + p: oracle {'accepts' if expected else 'rejects'}; compiled: {got}")
+    assert got.accepted == expected == counts_as_v, (region, expected, got)
+    assert got.check == ("NONE" if counts_as_v else "NON_CANONICAL"), got
+
+
 def hostile_cases(proof, pos):
     out = {"zero length": b"", "random bytes": np.random.default_rng(1).integers(0, 256, size=len(proof), dtype=np.uint8).tobytes()}
     for where in ("leaf_count", "sibling_count"):
