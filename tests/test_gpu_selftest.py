@@ -7,7 +7,9 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 
-@pytest.mark.parametrize("op", list(range(15)) + [21, 22, 23])  # 21-23: the safegcd inverse (feinv.hpp), both step forms
+# 15-20: the scaled Skyscraper path and dot29; 21-23: the safegcd inverse (feinv.hpp), both step forms; 24-26: the Shoup product, its
+# lazy-limb form and the NTT's in-register constants
+@pytest.mark.parametrize("op", list(range(27)))
 def test_device_equals_host(ctx, oracle, op):
     from provekit_amd._lib import lib
     from tools.pk_probes import lib as probes
@@ -21,6 +23,18 @@ def test_device_equals_host(ctx, oracle, op):
         rng = np.random.default_rng(op)
         a[6:600] = rng.integers(0, 2**64, size=(594, 4), dtype=np.uint64)
         b[6:600] = rng.integers(0, 2**64, size=(594, 4), dtype=np.uint64)
+    # the domains tests/test_fe29_host.py gives the later ops: 18 (a Montgomery image) and 20 (x, y < p) stay below p
+    if op in (15, 16, 17, 19):  # the scaled conversions take any 256-bit value
+        rng = np.random.default_rng(op)
+        a[6:600] = rng.integers(0, 2**64, size=(594, 4), dtype=np.uint64)
+        b[6:600] = rng.integers(0, 2**64, size=(594, 4), dtype=np.uint64)
+        a[600:604] = oracle.ints_to_limbs([oracle.P, oracle.P + 1, (1 << 256) - 1, 5 * oracle.P])
+        b[600:604] = oracle.ints_to_limbs([(1 << 256) - 1, 2 * oracle.P, oracle.P, 1 << 255])
+    if op in (24, 25):  # any 256-bit multiplicand, a multiplier below p
+        a[6:600] = np.random.default_rng(op).integers(0, 2**64, size=(594, 4), dtype=np.uint64)
+        a[600:603] = oracle.ints_to_limbs([(1 << 256) - 1, 5 * oracle.P, 2 * oracle.P + 1])
+    if op == 26:  # x in {1, 2, 3} selects w_8^x
+        a = oracle.ints_to_limbs([1 + i % 3 for i in range(n)])
     host = np.empty_like(a)
     assert lib.pk_selftest_arith(op, a.ctypes.data, b.ctypes.data, host.ctypes.data, n) == 0
     da, db, do = ctx.upload(a), ctx.upload(b), ctx.alloc_fe(n)

@@ -58,6 +58,48 @@ def test_evaluate_is_bit_exact_against_the_oracle(ctx, oracle, label, q, batch):
         b.free()
 
 
+WIDE_BATCH, WIDE_Q = 4, 17  # EVAL_MAX_BATCH polynomials; 17 points are two full passes of eight and a third pass of one
+
+
+@functools.lru_cache(maxsize=None)
+def wide_case(n):
+    """eval_case's two polynomials and nine points, two more polynomials and eight more points, and the oracle's evaluations"""
+    polys = K.polynomials(n, WIDE_BATCH, seed=11 + n)
+    pts = list(eval_case(n)[1]) + [K.random_ints(n, 1000 * n + i) for i in range(MAX_Q, WIDE_Q)]
+    pts[16] = list(pts[8])  # the third pass's point repeats the second pass's first
+    assert polys[:2] == eval_case(n)[0]
+    return polys, pts, K.expected_evals(polys, pts)
+
+
+def check_wide(ctx, oracle, n, batch, q):
+    from provekit_amd import whir_pcs
+
+    polys, pts, want = wide_case(n)
+    bufs = [ctx.upload(oracle.to_mont(oracle.ints_to_limbs(p))) for p in polys[:batch]]
+    got = whir_pcs.evaluate(ctx, bufs, n, K.mont_points(oracle, pts[:q]))
+    assert got.shape == (batch, q, 4)
+    expect = oracle.to_mont(oracle.ints_to_limbs([want[b][i] for b in range(batch) for i in range(q)])).reshape(batch, q, 4)
+    assert np.array_equal(got, expect)
+    assert len({got[b].tobytes() for b in range(batch)}) == batch  # every polynomial its own row
+    if q == WIDE_Q:
+        assert np.array_equal(got[:, 8], got[:, 16])
+    for b in bufs:
+        b.free()
+
+
+@pytest.mark.parametrize("batch", [3, 4])
+@pytest.mark.parametrize("q", [3, 9])
+@pytest.mark.parametrize("label", ["b-1", "b", "b+1"])
+def test_evaluate_with_three_and_four_polynomials(ctx, oracle, label, q, batch):
+    check_wide(ctx, oracle, resolve_n(label), batch, q)
+
+
+@pytest.mark.parametrize("batch", [1, 4])
+@pytest.mark.parametrize("q", [16, 17])
+def test_evaluate_with_a_full_second_and_a_third_pass_over_the_points(ctx, oracle, q, batch):
+    check_wide(ctx, oracle, resolve_n("b-1"), batch, q)
+
+
 @pytest.mark.parametrize("n,tiles", [(18, 2), (20, 8)])
 def test_evaluate_with_several_tiles_per_workgroup(ctx, oracle, n, tiles):
     """from 2^18 a workgroup streams more than one tile, four at a time: 2 tiles leave a group half empty, 8 make two groups.

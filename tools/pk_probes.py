@@ -28,6 +28,16 @@ SIGNATURES = {
     "pk_probe_mfma_reduce": (C.c_int, [vp, vp, vp, sz]),
     "pk_probe_mfma_reduce_rate": (C.c_int, [vp, C.c_uint, C.c_uint, C.POINTER(C.c_double)]),
     "pk_probe_mfma_valu_rate": (C.c_int, [vp, C.c_uint, C.c_uint, C.c_uint, C.POINTER(C.c_double)]),
+    # csrc/mle.hip's entry points without a C ABI (csrc/internal.hpp), for tests/test_gpu_mle_edges.py
+    "pk_probe_num_cus": (C.c_int, [vp, C.POINTER(C.c_int)]),
+    "pk_probe_reduction_blocks": (C.c_int, [vp, sz, C.POINTER(C.c_uint)]),
+    "pk_probe_dot_rows": (C.c_int, [vp, vp, sz, C.c_uint, vp, vp, sz, vp]),
+    "pk_probe_eval_univariate_multi": (C.c_int, [vp, vp, C.c_uint, sz, vp, vp]),
+    "pk_probe_lincomb2": (C.c_int, [vp, vp, vp, vp, vp, sz]),
+    "pk_probe_fold_pairs2": (C.c_int, [vp, vp, vp, vp, vp, sz, vp]),
+    "pk_probe_sumcheck_cubic_launch": (C.c_int, [vp, vp, vp, vp, vp, sz, vp, C.POINTER(C.c_uint)]),
+    "pk_probe_sumcheck_quadratic_launch": (C.c_int, [vp, vp, vp, sz, vp, vp, vp, C.POINTER(C.c_uint)]),
+    "pk_probe_sumcheck_collect_spin": (C.c_int, [vp, C.c_uint, vp]),
 }
 for _name, (_res, _args) in SIGNATURES.items():
     _fn = getattr(lib, _name)

@@ -53,6 +53,26 @@ int pk_probe_mfma_reduce(pk_ctx *ctx, const uint32_t *d_t_limbs, int32_t *d_out,
 int pk_probe_mfma_reduce_rate(pk_ctx *ctx, unsigned waves_per_simd, unsigned iters, double *squarings_per_s);
 int pk_probe_mfma_valu_rate(pk_ctx *ctx, unsigned waves_per_simd, unsigned ilp, unsigned iters, double *squarings_per_s);
 
+/* The entry points of csrc/mle.hip that have no C ABI of their own (csrc/internal.hpp: dot_rows, eval_univariate_multi, lincomb2,
+ * fold_pairs2 and the launch-only sumcheck rounds), for tests/test_gpu_mle_edges.py: the functions' own argument order, device
+ * pointers the caller owns.  dot_rows in its non-deferred form, fold_pairs2 and the sumcheck launches without a gate (gate_seq = 0)
+ * only.  pk_probe_sumcheck_collect_spin takes the three sums of the context's LAST launch (its *red_seq_out) without draining the
+ * stream.  pk_probe_num_cus / pk_probe_reduction_blocks: the compute-unit count the context sizes its grids by, and the grid
+ * reduce.hpp's reduction_blocks gives `work_items` items in the context's current mode. */
+int pk_probe_num_cus(pk_ctx *ctx, int *num_cus);
+int pk_probe_reduction_blocks(pk_ctx *ctx, size_t work_items, unsigned *blocks);
+int pk_probe_dot_rows(pk_ctx *ctx, const uint64_t *d_w, size_t row_stride, unsigned nrows, const uint64_t *d_f, const uint64_t *d_g, size_t n,
+                      uint64_t *out);
+int pk_probe_eval_univariate_multi(pk_ctx *ctx, const uint64_t *const *d_polys, unsigned np, size_t n, const uint64_t z[4], uint64_t *out);
+int pk_probe_lincomb2(pk_ctx *ctx, uint64_t *d_out, const uint64_t *d_a, const uint64_t *beta, const uint64_t *d_b, size_t n);
+int pk_probe_fold_pairs2(pk_ctx *ctx, const uint64_t *d_v0, uint64_t *d_out0, const uint64_t *d_v1, uint64_t *d_out1, size_t len,
+                         const uint64_t *r);
+int pk_probe_sumcheck_cubic_launch(pk_ctx *ctx, uint64_t *d_a, uint64_t *d_b, uint64_t *d_c, uint64_t *d_eq, size_t len,
+                                   const uint64_t *fold_or_null, unsigned *red_seq_out);
+int pk_probe_sumcheck_quadratic_launch(pk_ctx *ctx, const uint64_t *d_f, const uint64_t *d_w, size_t len, const uint64_t *fold_or_null,
+                                       uint64_t *d_f_out, uint64_t *d_w_out, unsigned *red_seq_out);
+int pk_probe_sumcheck_collect_spin(pk_ctx *ctx, unsigned red_seq, uint64_t out[12]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -886,3 +886,56 @@ extern "C" int pk_probe_launch_chain(pk_ctx* ctx, unsigned launches, unsigned th
     *us_per_launch = 1e6 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() / launches;
     return PK_OK;
 }
+
+// ============================================================================================================================
+// Entry points of mle.hip that have no C ABI of their own (internal.hpp), for tests/test_gpu_mle_edges.py: thin wrappers, the functions'
+// own argument order, device pointers the caller owns.  Launches that could wait on a gate are wrapped with gate_seq = 0 only: a gated
+// kernel whose challenge nobody publishes spins to its give-up bound, and that belongs to the whole-proof latency tests.
+extern "C" {
+int pk_probe_num_cus(pk_ctx* ctx, int* num_cus) {
+    if (!ctx || !num_cus) return PK_ERR_BAD_ARG;
+    *num_cus = ctx->num_cus;
+    return PK_OK;
+}
+// the grid reduce.hpp reduction_blocks gives `work_items` items in the context's current mode
+int pk_probe_reduction_blocks(pk_ctx* ctx, size_t work_items, unsigned* blocks) {
+    if (!ctx || !blocks) return PK_ERR_BAD_ARG;
+    *blocks = reduction_blocks(ctx, work_items);
+    return PK_OK;
+}
+int pk_probe_dot_rows(pk_ctx* ctx, const uint64_t* d_w, size_t row_stride, unsigned nrows, const uint64_t* d_f, const uint64_t* d_g, size_t n,
+                      uint64_t* out) {
+    PK_ENTER(ctx);
+    return dot_rows(ctx, d_w, row_stride, nrows, d_f, d_g, n, out, false);
+}
+int pk_probe_eval_univariate_multi(pk_ctx* ctx, const uint64_t* const* d_polys, unsigned np, size_t n, const uint64_t z[4], uint64_t* out) {
+    PK_ENTER(ctx);
+    PK_REQUIRE(ctx, d_polys && z && out && (np == 1 || np == 2) && (n == 0 || (d_polys[0] && d_polys[np - 1])), "null pointer");
+    return eval_univariate_multi(ctx, d_polys, np, n, z, out);
+}
+int pk_probe_lincomb2(pk_ctx* ctx, uint64_t* d_out, const uint64_t* d_a, const uint64_t* beta, const uint64_t* d_b, size_t n) {
+    PK_ENTER(ctx);
+    return lincomb2(ctx, d_out, d_a, beta, d_b, n);
+}
+int pk_probe_fold_pairs2(pk_ctx* ctx, const uint64_t* d_v0, uint64_t* d_out0, const uint64_t* d_v1, uint64_t* d_out1, size_t len, const uint64_t* r) {
+    PK_ENTER(ctx);
+    PK_REQUIRE(ctx, r, "null pointer");
+    return fold_pairs2(ctx, d_v0, d_out0, d_v1, d_out1, len, r, 0);
+}
+// launch only; the three sums are taken with pk_probe_sumcheck_collect_spin(*red_seq_out), which does not drain the stream
+int pk_probe_sumcheck_cubic_launch(pk_ctx* ctx, uint64_t* d_a, uint64_t* d_b, uint64_t* d_c, uint64_t* d_eq, size_t len, const uint64_t* fold_or_null,
+                                   unsigned* red_seq_out) {
+    PK_ENTER(ctx);
+    return sumcheck_cubic_launch(ctx, d_a, d_b, d_c, d_eq, len, fold_or_null, 0, red_seq_out);
+}
+int pk_probe_sumcheck_quadratic_launch(pk_ctx* ctx, const uint64_t* d_f, const uint64_t* d_w, size_t len, const uint64_t* fold_or_null,
+                                       uint64_t* d_f_out, uint64_t* d_w_out, unsigned* red_seq_out) {
+    PK_ENTER(ctx);
+    return sumcheck_quadratic_launch(ctx, d_f, d_w, len, fold_or_null, 0, d_f_out, d_w_out, red_seq_out);
+}
+int pk_probe_sumcheck_collect_spin(pk_ctx* ctx, unsigned red_seq, uint64_t out[12]) {
+    PK_ENTER(ctx);
+    PK_REQUIRE(ctx, out && red_seq && ctx->h_pinned && red_seq == ctx->red_seq, "not the sequence number of this context's last launch");
+    return sumcheck_collect_spin(ctx, red_seq, out);
+}
+}  // extern "C"
