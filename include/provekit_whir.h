@@ -4,7 +4,7 @@
  * Commit to `batch_size` multilinear polynomials, open them at points the caller chooses, verify the opening: what the `whir`
  * crate is used for outside WhirR1CSScheme (a lookup argument, a GR1CS variant, ...).  A fourth library above the product's C
  * ABI (like libprovekit_engine.so and libprovekit_verify.so): it links libprovekit_hip.so, calls only what provekit_hip.h
- * declares, and adds one HIP kernel pair of its own for gfx950 (csrc/whir_pcs/evaluate.hip).
+ * declares, and adds HIP kernels of its own for gfx950 (csrc/whir_pcs/evaluate.hip, csrc/whir_pcs/linear.hip).
  *
  * PLAIN WHIR, NOT HIDING.  There is no mask and no blinding polynomial: the proof contains openings of the committed
  * codeword and the evaluations themselves.  Use pk_prove where zero knowledge is needed.  Nothing here draws randomness: the
@@ -15,6 +15,10 @@
  *   the q * n_vars point coordinates (absorbed); the batch_size * q evaluations (absorbed, polynomial-major);
  *   whir::Prover::prove over sum_b beta^b poly_b with the q linear statements  <eq(point_i, .), poly> = sum_b beta^b v_{b,i},
  *   ending in the deferred_weight_evaluations hint (eq(point_i, folding point), which the verifier recomputes).
+ *
+ * A statement in WHIR is a list of constraints of two kinds, evaluation and linear.  pkw_open / pkw_verify state evaluations only;
+ * pkw_open_linear / pkw_verify_linear state q evaluations and l LINEAR constraints  <w_i, poly_b> = s_{b,i}  for dense weight
+ * tables w_i (the second half of this header).
  *
  * Conventions: those of provekit_hip.h (Montgomery 4 x u64 field elements, d_* = device pointers, PK_OK or a negative PK_ERR_*)
  * and of provekit_verify.h ("rejected" is a VERDICT in a pkv_result, not a call status; every count inside a proof is bounded
@@ -39,7 +43,7 @@ typedef struct pkw_commitment pkw_commitment;
 /* Verdicts of pkw_verify: the PKV_CHECK_* of the WHIR walk (provekit_verify.h), and three of the statement around it. */
 #define PKW_CHECK_POINTS (PKV_CHECK_COUNT + 0)   /* the points the proof binds are not the caller's */
 #define PKW_CHECK_ROOT (PKV_CHECK_COUNT + 1)     /* the root the proof binds is not expected_root */
-#define PKW_CHECK_DEFERRED (PKV_CHECK_COUNT + 2) /* a deferred weight evaluation is not eq(point_i, folding point) */
+#define PKW_CHECK_DEFERRED (PKV_CHECK_COUNT + 2) /* a deferred weight evaluation is not the weight's extension at the folding point */
 #define PKW_CHECK_COUNT (PKV_CHECK_COUNT + 3)
 
 int pkw_abi_version(void);
@@ -92,4 +96,10 @@ int pkw_verify(const pk_whir_config *cfg, const uint8_t *io_pattern, size_t io_p
 #ifdef __cplusplus
 }
 #endif
+
+/* The linear statements: pkw_weighted_sums, pkw_io_pattern_linear, pkw_open_linear, pkw_verify_linear.  Their declarations are a
+ * header of their own because their C names are exported by a companion library, libprovekit_whir_linear.so (link it next to
+ * libprovekit_whir.so); this header brings them along. */
+#include "provekit_whir_linear.h"
+
 #endif /* PROVEKIT_WHIR_H */

@@ -1,6 +1,7 @@
 // provekit_whir.hpp -- provekit::WhirPcs: the C++ face of libprovekit_whir.so (include/provekit_whir.h), next to provekit_hip.hpp's
-// prover types and provekit_verify.hpp's Verdict.  Commit to multilinear polynomials, open them at points, verify: PLAIN WHIR, not
-// hiding.  A rejected proof is a Verdict, not an exception; only a failed call throws provekit::Error.
+// prover types and provekit_verify.hpp's Verdict.  Commit to multilinear polynomials, open them at points or at linear statements
+// over dense weight tables, verify: PLAIN WHIR, not hiding.  open_linear / verify_linear need libprovekit_whir_linear.so linked next to
+// libprovekit_whir.so (provekit_whir_linear.h).  A rejected proof is a Verdict, not an exception; only a failed call throws provekit::Error.
 #pragma once
 #include "provekit_hip.hpp"
 #include "provekit_whir.h"
@@ -21,6 +22,24 @@ using Point = std::vector<FieldElement>;  // n_vars coordinates, variable 0 <-> 
 struct PcsOpening {
     std::vector<FieldElement> evaluations;  // [polynomial][point]
     std::vector<uint8_t> proof;
+};
+
+// a linear statement's opening: <w_i, poly_b> = sums[b * l + i] next to the evaluations at the points
+struct PcsLinearOpening {
+    std::vector<FieldElement> evaluations;  // [polynomial][point]
+    std::vector<FieldElement> sums;         // [polynomial][weight]
+    std::vector<uint8_t> proof;
+};
+
+// what pkw_verify_linear hands back: with `unchecked` > 0 the verdict holds PROVIDED deferred[i] is the multilinear extension of
+// weight i at fold_point, for every weight whose table the verifier was not given
+struct PcsLinearVerdict {
+    PcsVerdict verdict;
+    std::vector<FieldElement> evaluations, sums;
+    Point fold_point;
+    std::vector<FieldElement> deferred;  // one per weight
+    unsigned unchecked = 0;
+    explicit operator bool() const { return verdict.accepted; }
 };
 
 class WhirPcs;
@@ -91,16 +110,72 @@ class WhirPcs {
         if (evaluations_out) *evaluations_out = ev;
         return {r.accepted != 0, r.check, r.offset, r.message};
     }
+    // q >= 0 points and l >= 1 dense weight tables on the device, bound by the caller's tags (provekit_whir.h, "TAGS AND SOUNDNESS")
+    PcsLinearOpening open_linear(const PcsCommitment& com, const std::vector<Point>& points, const std::vector<const DeviceVec*>& weights,
+                                 const std::vector<FieldElement>& tags) const {
+        if (weights.size() != tags.size()) throw Error(PK_ERR_BAD_ARG, "as many tags as weights");
+        const std::vector<uint64_t> flat = flatten(points, cfg_.n_vars, /*may_be_empty=*/true);
+        std::vector<const uint64_t*> w;
+        for (const DeviceVec* v : weights) w.push_back(v->data());
+        PcsLinearOpening o;
+        o.evaluations.resize((size_t)cfg_.batch_size * points.size());
+        o.sums.resize((size_t)cfg_.batch_size * weights.size());
+        o.proof.resize(1 << 20);
+        size_t len = 0;
+        auto call = [&] {
+            return pkw_open_linear(s_, com.get(), flat.data(), (unsigned)points.size(), w.data(), tags.empty() ? nullptr : tags[0].data(),
+                                   (unsigned)weights.size(), o.evaluations.empty() ? nullptr : o.evaluations[0].data(),
+                                   o.sums.empty() ? nullptr : o.sums[0].data(), o.proof.data(), o.proof.size(), &len);
+        };
+        int rc = call();
+        if (rc == PK_ERR_BAD_ARG && len > o.proof.size()) {  // the proof is larger: *len says by how much
+            o.proof.resize(len);
+            rc = call();
+        }
+        check(rc);
+        o.proof.resize(len);
+        return o;
+    }
+    // host only.  weights: host tables (2^n_vars elements each), or nullptr entries / an empty vector for "not given"
+    static PcsLinearVerdict verify_linear(const WhirConfig& cfg, const std::vector<Point>& points, const std::vector<FieldElement>& tags,
+                                          const std::vector<const std::vector<FieldElement>*>& weights, const std::vector<uint8_t>& proof,
+                                          const std::array<uint8_t, 32>* expected_root = nullptr, int hash_version = 2) {
+        const pk_whir_config c = cfg.to_c();
+        const std::vector<uint64_t> flat = flatten(points, c.n_vars, /*may_be_empty=*/true);
+        if (!weights.empty() && weights.size() != tags.size()) throw Error(PK_ERR_BAD_ARG, "as many weights as tags, or none");
+        std::vector<const uint64_t*> w;
+        for (const std::vector<FieldElement>* t : weights) {
+            if (t && t->size() != (size_t)1 << c.n_vars) throw Error(PK_ERR_BAD_ARG, "a weight table has 2^n_vars elements");
+            w.push_back(t ? (*t)[0].data() : nullptr);
+        }
+        PcsLinearVerdict out;
+        out.evaluations.resize((size_t)c.batch_size * points.size());
+        out.sums.resize((size_t)c.batch_size * tags.size());
+        out.fold_point.resize(c.n_vars);
+        out.deferred.resize(tags.size());
+        std::vector<uint64_t> fold(4 * (size_t)c.n_vars + 4);  // flat storage: a valid pointer whatever n_vars is
+        pkv_result r;
+        if (int rc = pkw_verify_linear(&c, nullptr, 0, hash_version, expected_root ? expected_root->data() : nullptr, flat.data(), (unsigned)points.size(),
+                                       tags.empty() ? nullptr : tags[0].data(), w.empty() ? nullptr : w.data(), (unsigned)tags.size(), proof.data(),
+                                       proof.size(), out.evaluations.empty() ? nullptr : out.evaluations[0].data(),
+                                       out.sums.empty() ? nullptr : out.sums[0].data(), fold.data(),
+                                       out.deferred.empty() ? nullptr : out.deferred[0].data(), &out.unchecked, &r))
+            throw Error(rc, pkw_create_error());
+        for (unsigned j = 0; j < c.n_vars; j++) std::copy(fold.begin() + 4 * j, fold.begin() + 4 * j + 4, out.fold_point[j].begin());
+        out.verdict = {r.accepted != 0, r.check, r.offset, r.message};
+        return out;
+    }
     pkw_scheme* get() const { return s_; }
 
    private:
-    static std::vector<uint64_t> flatten(const std::vector<Point>& points, unsigned n_vars) {
+    static std::vector<uint64_t> flatten(const std::vector<Point>& points, unsigned n_vars, bool may_be_empty = false) {
         std::vector<uint64_t> flat;
         for (const Point& p : points) {
             if (p.size() != n_vars) throw Error(PK_ERR_BAD_ARG, "a point has n_vars coordinates");
             for (const FieldElement& x : p) flat.insert(flat.end(), x.begin(), x.end());
         }
-        if (flat.empty()) throw Error(PK_ERR_BAD_ARG, "at least one point");
+        if (flat.empty() && !may_be_empty) throw Error(PK_ERR_BAD_ARG, "at least one point");
+        if (flat.empty()) flat.resize(4);  // a valid pointer for q = 0
         return flat;
     }
     void check(int rc) const {

@@ -20,6 +20,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../fe29.hpp"
+#include "block_sum.hpp"
 #include "evaluate.hpp"
 
 using namespace pk;
@@ -57,21 +58,6 @@ __device__ __forceinline__ fe eq_bits(const fe* pt, int var0, unsigned nbits, un
         acc = fe_mulx(acc, (idx >> k) & 1 ? r : fe_sub(fe_one(), r));
     }
     return acc;
-}
-
-// sum of `v` over the workgroup's 256 lanes; valid in lane 0.  lds: 4 elements of its own
-__device__ __forceinline__ fe block_sum(fe v, fe* lds) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        fe o;
-#pragma unroll
-        for (int k = 0; k < 8; k++) o.v[k] = __shfl_down(v.v[k], off, 64);
-        v = fe_add(v, o);
-    }
-    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) v = fe_add(fe_add(lds[0], lds[1]), fe_add(lds[2], lds[3]));
-    return v;
 }
 
 constexpr unsigned THREADS = 256, MID_SLOTS = 1u << EVAL_MAX_MID;

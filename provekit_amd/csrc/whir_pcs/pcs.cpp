@@ -2,13 +2,18 @@
 //
 // pkw_open is whir::Prover::prove restated over the product library's PUBLIC entry points (provekit_hip.h) -- the same steps in the
 // same order as prover.hip's WhirProver, which drives them through the library's internals -- with the prover side of the sponge
-// (prover_transcript.hpp) enforcing pkw_io_pattern operation by operation.  The linear statements are the weights eq(point_i, .):
-// pk_eq_accumulate adds them to the OOD weights with their powers of the combination randomness, so no weight table is ever
-// materialised, and their deferred evaluations eq(point_i, folding point) are O(n) products on the host.
+// (prover_transcript.hpp) enforcing pkw_io_pattern operation by operation.  The evaluation constraints are the weights
+// eq(point_i, .): pk_eq_accumulate adds them to the OOD weights with their powers of the combination randomness, so no weight table
+// is ever materialised, and their deferred evaluations eq(point_i, folding point) are O(n) products on the host.  The linear
+// constraints of pkw_open_linear are dense tables on the device: linear.hip's kernels give their sums and add them to the same
+// weight table in one pass, and evaluate.hip's kernel reads them once more at the folding point for their deferred evaluations.
 #include <hip/hip_runtime.h>
+
+#include <map>
 
 #include "../prover_transcript.hpp"
 #include "evaluate.hpp"
+#include "linear.hpp"
 #include "pcs.hpp"
 
 using pk::fe;
@@ -17,6 +22,7 @@ struct pkw_scheme {
     pk_ctx* ctx = nullptr;
     pk_whir_config cfg{};
     std::string pattern_cache[PKW_MAX_POINTS + 1];
+    std::map<unsigned, std::string> linear_pattern_cache;  // by q * (PKW_MAX_WEIGHTS + 1) + l
     std::string err;
     hipStream_t stream = nullptr;  // the evaluation kernel's
     uint64_t* arena = nullptr;
@@ -175,7 +181,9 @@ struct Opening {
         return PK_OK;
     }
 
-    int run(const fe* points, unsigned q, fe* evals /* batch * q */) {
+    // q evaluation constraints, then l linear ones (l = 0: pkw_open); weights: l device tables, tags: l host elements
+    int run(const fe* points, unsigned q, fe* evals /* batch * q */, const uint64_t* const* weights, const fe* tags, unsigned l,
+            fe* sums /* batch * l */) {
         const size_t N = (size_t)1 << n;
         const unsigned batch = cfg.batch_size;
         TAKE(scratch, plan(cfg).scratch);
@@ -187,12 +195,16 @@ struct Opening {
             for (size_t j = 0; j < ood.size(); j++) CK(pk_eval_univariate(ctx, C.coeffs[b], N, U(&ood[j]), U(&ood_ans[b * ood.size() + j])));
         for (unsigned b = 0; b < batch; b++) T.add_scalars(&ood_ans[b * ood.size()], ood.size());
         const fe beta = batch > 1 ? T.challenge_scalar() : pk::fe_one();
-        // 4, 5: the statement
+        // 4, 5: the statement.  The partials of the sums go where the evaluation's went (the two uses are sequential; a pass of
+        // WSUM_PASS weights needs what a pass of EVAL_PASS points does, on a grid that is never larger)
         T.add_scalars(points, (size_t)q * n);
-        {
-            TAKE(d_pts, (size_t)q * n);
-            TAKE(d_part, eval_partial_fes(batch, n));
-            TAKE(d_out, (size_t)batch * q);
+        T.add_scalars(tags, l);
+        TAKE(d_pts, (size_t)PKW_MAX_POINTS * n);
+        TAKE(d_part, eval_partial_fes(batch, n));
+        TAKE(d_out, (size_t)PKW_MAX_POINTS * batch);
+        if (wsum_partial_fes(batch, n) > eval_partial_fes(batch, n)) return PK_ERR_OOM;
+        CK(pk_ctx_sync(ctx));
+        if (q) {
             CK(pk_memcpy_h2d(ctx, d_pts, points, 32 * (size_t)q * n));
             CK(pk_ctx_sync(ctx));
             CK(eval_launch(S.stream, C.evals, batch, n, d_pts, q, d_part, d_out));
@@ -200,6 +212,12 @@ struct Opening {
             CK(pk_memcpy_d2h(ctx, evals, d_out, 32 * (size_t)batch * q));
         }
         T.add_scalars(evals, (size_t)batch * q);
+        if (l) {
+            CK(wsum_launch(S.stream, C.evals, batch, n, weights, l, d_part, d_out));
+            if (hipStreamSynchronize(S.stream) != hipSuccess) return PK_ERR_HIP;
+            CK(pk_memcpy_d2h(ctx, sums, d_out, 32 * (size_t)batch * l));
+        }
+        T.add_scalars(sums, (size_t)batch * l);
         // 6: whir::Prover::prove over the beta-combined polynomial
         TAKE(d_c0, N);
         uint64_t* d_c = d_c0;
@@ -211,11 +229,21 @@ struct Opening {
         p[0] = p0, p[1] = p1, w[0] = w0, w[1] = w1;
         CK(batch_combine(p0, C.evals, beta));
         fe gamma = T.challenge_scalar(), g;
-        {  // weights = sum gamma^i w_i over [OOD constraints..., eq(point_i, .)...]
-            std::vector<fe> pts((ood.size() + q) * n);
+        {  // weights = sum gamma^i w_i over [OOD constraints..., eq(point_i, .)..., the dense tables...]
+            std::vector<fe> pts((ood.size() + q) * n + 1);
             for (size_t j = 0; j < ood.size(); j++) pk::expand_from_univariate(ood[j], n, &pts[j * n]);
             std::copy(points, points + (size_t)q * n, pts.begin() + ood.size() * n);
             CK(eq_weights(w0, n, pts, ood.size() + q, gamma, pk::fe_one(), /*overwrite=*/1, &g));
+            if (l) {
+                std::vector<fe> scales(l);
+                for (unsigned i = 0; i < l; i++) {
+                    scales[i] = g;
+                    g = pk::h_mul(g, gamma);
+                }
+                CK(pk_ctx_sync(ctx));  // the eq weights are the context's work: in the table before the kernel adds to it
+                CK(combine_launch(S.stream, w0, N, weights, U(scales.data()), l, /*accumulate=*/1));
+                if (hipStreamSynchronize(S.stream) != hipSuccess) return PK_ERR_HIP;
+            }
         }
         CK(sumcheck_rounds(k));
         Tree prev{C.leaves, C.nodes, C.rows, C.width, C.layout};
@@ -268,12 +296,22 @@ struct Opening {
         CK(sumcheck_rounds(final_vars));
         CK(pow_round(cfg.final_folding_pow_bits));
         // deferred_weight_evaluations: each weight's MLE at the folding point, reverse(all_r) in eval_eq's MSB-first order; for
-        // eq(point_i, .) that is eq(point_i, folding point)
+        // eq(point_i, .) that is eq(point_i, folding point); the dense tables are read once, EVAL_MAX_BATCH at a time, by the
+        // evaluation kernel (its partials for EVAL_MAX_BATCH tables go into the commit scratch, idle by now)
         const std::vector<fe> point(all_r.rbegin(), all_r.rend());
-        std::vector<fe> deferred(q);
+        std::vector<fe> deferred(q + l);
         for (unsigned i = 0; i < q; i++) deferred[i] = pkv::eq_poly(points + (size_t)i * n, point.data(), n);
+        if (l) {
+            if (eval_partial_fes(EVAL_MAX_BATCH, n) > plan(cfg).scratch) return PK_ERR_OOM;
+            CK(pk_memcpy_h2d(ctx, d_pts, point.data(), 32 * (size_t)n));
+            CK(pk_ctx_sync(ctx));
+            for (unsigned i0 = 0; i0 < l; i0 += EVAL_MAX_BATCH)
+                CK(eval_launch(S.stream, weights + i0, std::min(EVAL_MAX_BATCH, l - i0), n, d_pts, 1, scratch, d_out + 4 * (size_t)i0));
+            if (hipStreamSynchronize(S.stream) != hipSuccess) return PK_ERR_HIP;
+            CK(pk_memcpy_d2h(ctx, deferred.data() + q, d_out, 32 * (size_t)l));
+        }
         std::vector<uint8_t> buf;
-        pk::put_vec(buf, deferred.data(), q);
+        pk::put_vec(buf, deferred.data(), q + l);
         T.hint(buf.data(), buf.size());
         return PK_OK;
     }
@@ -387,6 +425,35 @@ int pkw_commitment_destroy(pkw_commitment* com) {
     return PK_OK;
 }
 
+}  // extern "C"
+
+namespace pkw {
+namespace {
+
+// the opening both entry points make once their arguments are checked; l = 0: pkw_open
+int open_checked(pkw_scheme* s, const pkw_commitment* com, const std::string& pattern, const uint64_t* points, unsigned q,
+             const uint64_t* const* d_weights, const uint64_t* tags, unsigned l, uint64_t* evals_out, uint64_t* sums_out, uint8_t* proof_out, size_t cap,
+             size_t* len) {
+    pk::Transcript T(pattern);
+    std::vector<fe> evals((size_t)s->cfg.batch_size * q + 1), sums((size_t)s->cfg.batch_size * l + 1);
+    pkw::Opening op(*s, *com, T);
+    const int rc = op.run(reinterpret_cast<const fe*>(points), q, evals.data(), d_weights, reinterpret_cast<const fe*>(tags), l, sums.data());
+    if (rc) return pkw::fail(s, rc, rc == PK_ERR_OOM ? "the arena is too small for this opening" : std::string("open: ") + pk_last_error(s->ctx));
+    if (!T.finished())
+        return pkw::fail(s, PK_ERR_IO_PATTERN, T.violation().empty() ? "the proof ended before its IO pattern did" : T.violation());
+    *len = T.narg.size();
+    if (cap < T.narg.size()) return pkw::fail(s, PK_ERR_BAD_ARG, "proof buffer too small: " + std::to_string(T.narg.size()) + " bytes needed");
+    memcpy(proof_out, T.narg.data(), T.narg.size());
+    if (evals_out) memcpy(evals_out, evals.data(), 32 * (size_t)s->cfg.batch_size * q);
+    if (sums_out) memcpy(sums_out, sums.data(), 32 * (size_t)s->cfg.batch_size * l);
+    return PK_OK;
+}
+
+}  // namespace
+}  // namespace pkw
+
+extern "C" {
+
 int pkw_open(pkw_scheme* s, const pkw_commitment* com, const uint64_t* points, unsigned q, uint64_t* evals_out, uint8_t* proof_out, size_t cap,
              size_t* len) {
     if (!s) return PK_ERR_BAD_ARG;
@@ -395,21 +462,38 @@ int pkw_open(pkw_scheme* s, const pkw_commitment* com, const uint64_t* points, u
     if (q < 1 || q > PKW_MAX_POINTS) return pkw::fail(s, PK_ERR_BAD_ARG, "the number of points must be 1..64");
     try {
         if (s->pattern_cache[q].empty()) s->pattern_cache[q] = pkw::io_pattern(s->cfg, q);
-        pk::Transcript T(s->pattern_cache[q]);
-        std::vector<fe> evals((size_t)s->cfg.batch_size * q);
-        pkw::Opening op(*s, *com, T);
-        const int rc = op.run(reinterpret_cast<const fe*>(points), q, evals.data());
-        if (rc) return pkw::fail(s, rc, rc == PK_ERR_OOM ? "the arena is too small for this opening" : std::string("open: ") + pk_last_error(s->ctx));
-        if (!T.finished())
-            return pkw::fail(s, PK_ERR_IO_PATTERN, T.violation().empty() ? "the proof ended before its IO pattern did" : T.violation());
-        *len = T.narg.size();
-        if (cap < T.narg.size()) return pkw::fail(s, PK_ERR_BAD_ARG, "proof buffer too small: " + std::to_string(T.narg.size()) + " bytes needed");
-        memcpy(proof_out, T.narg.data(), T.narg.size());
-        if (evals_out) memcpy(evals_out, evals.data(), 32 * evals.size());
-        return PK_OK;
+        return pkw::open_checked(s, com, s->pattern_cache[q], points, q, nullptr, nullptr, 0, evals_out, nullptr, proof_out, cap, len);
     } catch (...) {
         return pkw::fail(s, PK_ERR_OOM, "out of memory");
     }
 }
 
 }  // extern "C"
+
+namespace pkw {
+
+// the entry point behind pkw_open_linear (linear_abi.cpp)
+int open_linear(pkw_scheme* s, const pkw_commitment* com, const uint64_t* points, unsigned q, const uint64_t* const* d_weights, const uint64_t* tags,
+                unsigned l, uint64_t* evals_out, uint64_t* sums_out, uint8_t* proof_out, size_t cap, size_t* len) {
+    if (!s) return PK_ERR_BAD_ARG;
+    std::string why;
+    if (!linear_counts_ok(q, l, why)) return fail(s, PK_ERR_BAD_ARG, why);
+    if (!com || (q && !points) || !d_weights || !tags || !len || (cap && !proof_out)) return fail(s, PK_ERR_BAD_ARG, "null pointer");
+    for (unsigned i = 0; i < l; i++)
+        if (!d_weights[i]) return fail(s, PK_ERR_BAD_ARG, "weight " + std::to_string(i) + " is a null pointer");
+    if (com->scheme != s) return fail(s, PK_ERR_BAD_ARG, "the commitment belongs to another scheme");
+    // the scratch both kernels borrow, checked before any work: the sums' partials go where the evaluation's do, the deferred
+    // evaluation's (EVAL_MAX_BATCH tables per launch) into the commit scratch
+    const unsigned n = s->cfg.n_vars, batch = s->cfg.batch_size;
+    if (wsum_partial_fes(batch, n) > eval_partial_fes(batch, n) || eval_partial_fes(EVAL_MAX_BATCH, n) > plan(s->cfg).scratch)
+        return fail(s, PK_ERR_BAD_ARG, "this config's arena is too small for a linear opening");
+    try {
+        std::string& pattern = s->linear_pattern_cache[q * (PKW_MAX_WEIGHTS + 1) + l];
+        if (pattern.empty()) pattern = io_pattern(s->cfg, q, l);
+        return open_checked(s, com, pattern, points, q, d_weights, tags, l, evals_out, sums_out, proof_out, cap, len);
+    } catch (...) {
+        return fail(s, PK_ERR_OOM, "out of memory");
+    }
+}
+
+}  // namespace pkw

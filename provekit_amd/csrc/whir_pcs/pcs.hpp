@@ -25,18 +25,21 @@ inline bool config_ok(const pk_whir_config* c, std::string& why) {
         why = "null config";
         return false;
     }
+#ifndef PKW_HOST_ONLY  // the sanitizer build of the verifier (asan_main.cpp) links no product library: the core's rule alone
     size_t n = 0;
     if (pk_whir_r1cs_io_pattern(1, c, c, nullptr, 0, &n) != PK_OK) {
         why = "pk_whir_r1cs_io_pattern refuses this config";
         return false;
     }
+#endif
     return pkv::config_ok(*c, why);
 }
 
 // "<domain>" then commit_statement, the statement, add_whir_proof -- the operations and labels of whir_config.hip's restatement of
-// whir's pattern, zero-count operations omitted where whir guards them
-inline std::string io_pattern(const pk_whir_config& c, unsigned q) {
-    std::string d = "provekit-hip/whir-pcs/v1";
+// whir's pattern, zero-count operations omitted where whir guards them.  l = 0: the evaluation statement of pkw_open; l >= 1: the
+// linear statement of pkw_open_linear (its own domain label, the tags after the points, the sums after the evaluations)
+inline std::string io_pattern(const pk_whir_config& c, unsigned q, unsigned l = 0) {
+    std::string d = l ? "provekit-hip/whir-pcs-linear/v1" : "provekit-hip/whir-pcs/v1";
     auto op = [&](char kind, size_t count, const char* label) {
         d.push_back('\0');
         d.push_back(kind);
@@ -69,7 +72,9 @@ inline std::string io_pattern(const pk_whir_config& c, unsigned q) {
     if (c.batch_size > 1) S(1, "batching_randomness");
     // the statement: where, and what the polynomials are claimed to be there
     A((size_t)q * c.n_vars, "points");
+    A(l, "tags");
     A((size_t)q * c.batch_size, "evaluations");
+    A((size_t)l * c.batch_size, "sums");
     // add_whir_proof
     const unsigned k = c.folding_factor;
     S(1, "initial_combination_randomness");
@@ -122,6 +127,30 @@ inline Plan plan(const pk_whir_config& c) {
     // pkw_open's evaluations: the points, the kernel's partial sums, the results
     p.total += round8((size_t)PKW_MAX_POINTS * n) + round8(eval_partial_fes(c.batch_size, n)) + round8((size_t)PKW_MAX_POINTS * c.batch_size);
     return p;
+}
+
+// The linear statement's entry points (include/provekit_whir_linear.h says what they do).  They are C++ functions of this library;
+// their C names pkw_weighted_sums, pkw_io_pattern_linear, pkw_open_linear and pkw_verify_linear are exported by the companion
+// library libprovekit_whir_linear.so (linear_abi.cpp), because this library's own export list stays the 15 symbols it had.
+int weighted_sums(pk_ctx* ctx, const uint64_t* const* d_evals, unsigned batch, unsigned n_vars, const uint64_t* const* d_weights, unsigned l, uint64_t* out);
+int io_pattern_linear(const pk_whir_config* cfg, unsigned q, unsigned l, uint8_t* buf, size_t cap, size_t* len);
+int open_linear(pkw_scheme* s, const pkw_commitment* com, const uint64_t* points, unsigned q, const uint64_t* const* d_weights, const uint64_t* tags,
+                unsigned l, uint64_t* evals_out, uint64_t* sums_out, uint8_t* proof_out, size_t cap, size_t* len);
+int verify_linear(const pk_whir_config* cfg, const uint8_t* io_pattern, size_t io_pattern_len, int hash_version, const uint8_t* expected_root,
+                  const uint64_t* points, unsigned q, const uint64_t* tags, const uint64_t* const* weights, unsigned l, const uint8_t* proof, size_t len,
+                  uint64_t* evals_out, uint64_t* sums_out, uint64_t* fold_point_out, uint64_t* deferred_out, unsigned* unchecked_out, pkv_result* result);
+
+// the counts of a linear statement, refused with a reason
+inline bool linear_counts_ok(unsigned q, unsigned l, std::string& why) {
+    if (q > PKW_MAX_POINTS) {
+        why = "the number of points must be 0..64";
+        return false;
+    }
+    if (l < 1 || l > PKW_MAX_WEIGHTS) {
+        why = "the number of weights must be 1..16";
+        return false;
+    }
+    return true;
 }
 
 }  // namespace pkw

@@ -1,7 +1,9 @@
 // verify_host.cpp -- the host half of libprovekit_whir.so: the IO pattern, the arena size and pkw_verify.  No device code and no
 // HIP call.  The WHIR proof inside an opening is walked by verify/core.hpp's Walk::whir_verify, unchanged; what is new here is the
 // statement around it: the points and evaluations on the transcript, and the deferred weight evaluations, which for the weights
-// eq(point_i, .) have the closed form eq(point_i, folding point).
+// eq(point_i, .) have the closed form eq(point_i, folding point).  A linear statement (pkw_verify_linear) adds tags, sums and dense
+// weight tables, whose deferred evaluations are their multilinear extensions at the folding point: 2^n_vars products per table the
+// caller hands over, the caller's own business for the others.
 #include "pcs.hpp"
 
 namespace pkw {
@@ -18,10 +20,13 @@ const char* const kWalkNames[PKV_CHECK_COUNT] = {
 class PcsWalk : public pkv::Walk {
   public:
     PcsWalk(const pkv::Statement& st, pkv::Backend& be, const uint8_t* proof, size_t len, pkv::Verdict& v, const pk_whir_config& cfg, const fe* points,
-            unsigned q, const fe* expected_root)
-        : Walk(st, be, proof, len, v), cfg_(cfg), points_(points), q_(q), expected_root_(expected_root) {}
+            unsigned q, const fe* expected_root, const fe* tags = nullptr, const uint64_t* const* weights = nullptr, unsigned l = 0)
+        : Walk(st, be, proof, len, v), cfg_(cfg), points_(points), q_(q), expected_root_(expected_root), tags_(tags), weights_(weights), l_(l) {}
 
     std::vector<fe> evals;  // [polynomial][point], Montgomery: what the proof binds, once the walk got past them
+    std::vector<fe> sums;   // [polynomial][weight], likewise
+    std::vector<fe> fold_point, weight_deferred;  // once the WHIR walk is through: the folding point, the l deferred values of the weights
+    unsigned unchecked = 0;                       // weights without a table: their deferred values are the caller's to check
 
     bool run_opening() {
         const unsigned n = cfg_.n_vars, batch = cfg_.batch_size;
@@ -29,18 +34,24 @@ class PcsWalk : public pkv::Walk {
         if (!parse_commitment(cfg_, com)) return false;
         if (expected_root_ && !pk::fe_eq(com.root, *expected_root_)) return A.fail(PKW_CHECK_ROOT, "the proof's root is not the expected commitment");
         std::vector<fe> pts((size_t)q_ * n);
-        if (!A.next_scalars(pts.size(), pts.data())) return false;
+        if (!pts.empty() && !A.next_scalars(pts.size(), pts.data())) return false;
         for (size_t j = 0; j < pts.size(); j++)
             if (!pk::fe_eq(pts[j], points_[j]))
                 return A.fail(PKW_CHECK_POINTS, "point " + std::to_string(j / n) + " of the proof is not the caller's (coordinate " + std::to_string(j % n) + ")");
-        std::vector<fe> ev((size_t)batch * q_);
-        if (!A.next_scalars(ev.size(), ev.data())) return false;
+        std::vector<fe> tg(l_);
+        if (l_ && !A.next_scalars(l_, tg.data())) return false;
+        for (unsigned i = 0; i < l_; i++)
+            if (!pk::fe_eq(tg[i], tags_[i])) return A.fail(PKW_CHECK_POINTS, "tag " + std::to_string(i) + " of the proof is not the caller's");
+        std::vector<fe> ev((size_t)batch * q_), sm((size_t)batch * l_);
+        if (!ev.empty() && !A.next_scalars(ev.size(), ev.data())) return false;
         evals = ev;
-        std::vector<fe> claims(q_);
-        for (unsigned i = 0; i < q_; i++) {  // the statement of the beta-combined polynomial
+        if (!sm.empty() && !A.next_scalars(sm.size(), sm.data())) return false;
+        sums = sm;
+        std::vector<fe> claims(q_ + l_);
+        for (unsigned i = 0; i < q_ + l_; i++) {  // the statement of the beta-combined polynomial: evaluations, then sums
             fe acc = pkv::f_zero(), bp = pkv::f_one();
             for (unsigned b = 0; b < batch; b++) {
-                acc = pk::h_add(acc, pk::h_mul(bp, ev[(size_t)b * q_ + i]));
+                acc = pk::h_add(acc, pk::h_mul(bp, i < q_ ? ev[(size_t)b * q_ + i] : sm[(size_t)b * l_ + (i - q_)]));
                 bp = pk::h_mul(bp, com.beta);
             }
             claims[i] = acc;
@@ -48,11 +59,24 @@ class PcsWalk : public pkv::Walk {
         std::vector<fe> rev;
         std::vector<pk::HintFe> deferred;
         if (!whir_verify(com, cfg_, claims, rev, deferred)) return false;
+        fold_point = rev;
+        for (unsigned i = 0; i < l_; i++) weight_deferred.push_back(deferred[q_ + i].mont);
         if (!A.done()) return A.fail(PKV_CHECK_TRAILING_BYTES, "trailing bytes after the proof");
         for (unsigned i = 0; i < q_; i++)  // the MLE of eq(point_i, .) at the folding point
             if (!relation(deferred[i].canonical && pk::fe_eq(deferred[i].mont, pkv::eq_poly(points_ + (size_t)i * n, rev.data(), n)), PKW_CHECK_DEFERRED,
                           "deferred evaluation of weight " + std::to_string(i) + " is not eq(point, folding point)"))
                 return false;
+        for (unsigned i = 0; i < l_; i++) {  // the MLE of a dense table at the folding point, where the caller gave the table
+            const pk::HintFe& d = deferred[q_ + i];
+            if (!relation(d.canonical, PKW_CHECK_DEFERRED, "deferred evaluation of weight " + std::to_string(i) + " is not canonical")) return false;
+            if (!weights_ || !weights_[i]) {
+                unchecked++;
+                continue;
+            }
+            if (!relation(pk::fe_eq(d.mont, table_at(weights_[i], rev)), PKW_CHECK_DEFERRED,
+                          "deferred evaluation of weight " + std::to_string(i) + " is not the extension of the caller's table at the folding point"))
+                return false;
+        }
         v_.offset = A.pos();
         return true;
     }
@@ -62,7 +86,69 @@ class PcsWalk : public pkv::Walk {
     const fe* points_;
     unsigned q_;
     const fe* expected_root_;
+    const fe* tags_;
+    const uint64_t* const* weights_;
+    unsigned l_;
+
+    // the multilinear extension of a dense table (2^n Montgomery elements, any 256-bit values) at `point`, variable 0 <-> the most
+    // significant index bit: the first fold reads the caller's table, the rest work on the half-size copy
+    static fe table_at(const uint64_t* table, const std::vector<fe>& point) {
+        auto at = [&](size_t i) { return pk::fe_reduce_any(pk::h_load(table + 4 * i)); };
+        if (point.empty()) return at(0);
+        size_t len = (size_t)1 << (point.size() - 1);
+        std::vector<fe> v(len);
+        for (size_t i = 0; i < len; i++) {
+            const fe lo = at(i);
+            v[i] = pk::h_add(lo, pk::h_mul(point[0], pk::h_sub(at(i + len), lo)));
+        }
+        for (size_t j = 1; j < point.size(); j++) {
+            len /= 2;
+            for (size_t i = 0; i < len; i++) v[i] = pk::h_add(v[i], pk::h_mul(point[j], pk::h_sub(v[i + len], v[i])));
+        }
+        return v[0];
+    }
 };
+
+// what pkw_verify and pkw_verify_linear share once their counts are checked; l = 0: pkw_verify
+int verify_checked(const pk_whir_config* cfg, const uint8_t* io_pattern, size_t io_pattern_len, int hash_version, const uint8_t* expected_root,
+                   const uint64_t* points, unsigned q, const uint64_t* tags, const uint64_t* const* weights, unsigned l, const uint8_t* proof, size_t len,
+                   uint64_t* evals_out, uint64_t* sums_out, uint64_t* fold_point_out, uint64_t* deferred_out, unsigned* unchecked_out, pkv_result* result) {
+    std::string why;
+    if (hash_version != 1 && hash_version != 2) return refuse("hash version must be 1 or 2");
+    try {
+        pkv::Statement st;
+        st.w = st.b = *cfg;
+        st.hash_version = hash_version;
+        if (io_pattern && io_pattern_len)
+            st.pattern.assign(reinterpret_cast<const char*>(io_pattern), io_pattern_len);
+        else
+            st.pattern = pkw::io_pattern(*cfg, q, l);
+        if (!pk::io_pattern_parse(st.pattern, st.ops, why)) {
+            g_error = why;
+            return PK_ERR_IO_PATTERN;
+        }
+        static const uint8_t none = 0;
+        pk::fe root;
+        if (expected_root) root = pk::load_raw(expected_root);
+        pkv::Verdict verdict;
+        pkv::HostBackend be;
+        PcsWalk walk(st, be, len ? proof : &none, len, verdict, *cfg, reinterpret_cast<const pk::fe*>(points), q, expected_root ? &root : nullptr,
+                     reinterpret_cast<const pk::fe*>(tags), weights, l);
+        walk.run_opening();
+        pkv::to_result(verdict, result);
+        auto give = [](uint64_t* out, const std::vector<fe>& v) {
+            if (out && !v.empty()) memcpy(out, v.data(), 32 * v.size());
+        };
+        give(evals_out, walk.evals);
+        give(sums_out, walk.sums);
+        give(fold_point_out, walk.fold_point);
+        give(deferred_out, walk.weight_deferred);
+        if (unchecked_out) *unchecked_out = walk.unchecked;
+        return PK_OK;
+    } catch (...) {
+        return PK_ERR_OOM;
+    }
+}
 
 }  // namespace
 }  // namespace pkw
@@ -79,6 +165,7 @@ const char* pkw_check_name(int check) {
 
 const char* pkw_create_error(void) { return pkw::g_error.c_str(); }
 
+#ifndef PKW_HOST_ONLY  // the arena's plan asks the evaluation kernel's launch code, which the sanitizer build does not have
 int pkw_scheme_arena_bytes(const pk_whir_config* cfg, size_t* bytes) {
     std::string why;
     if (!bytes) return pkw::refuse("null pointer");
@@ -86,6 +173,7 @@ int pkw_scheme_arena_bytes(const pk_whir_config* cfg, size_t* bytes) {
     *bytes = 32 * pkw::plan(*cfg).total;
     return PK_OK;
 }
+#endif
 
 int pkw_io_pattern(const pk_whir_config* cfg, unsigned q, uint8_t* buf, size_t cap, size_t* len) {
     std::string why;
@@ -108,32 +196,38 @@ int pkw_verify(const pk_whir_config* cfg, const uint8_t* io_pattern, size_t io_p
     if (!result || !points || (len && !proof)) return pkw::refuse("null pointer");
     if (!pkw::config_ok(cfg, why)) return pkw::refuse(why);
     if (q < 1 || q > PKW_MAX_POINTS) return pkw::refuse("the number of points must be 1..64");
-    if (hash_version != 1 && hash_version != 2) return pkw::refuse("hash version must be 1 or 2");
+    return pkw::verify_checked(cfg, io_pattern, io_pattern_len, hash_version, expected_root, points, q, nullptr, nullptr, 0, proof, len, evals_out, nullptr,
+                               nullptr, nullptr, nullptr, result);
+}
+
+}  // extern "C"
+
+namespace pkw {
+
+// the entry points behind pkw_io_pattern_linear and pkw_verify_linear (linear_abi.cpp)
+int io_pattern_linear(const pk_whir_config* cfg, unsigned q, unsigned l, uint8_t* buf, size_t cap, size_t* len) {
+    std::string why;
+    if (!len) return refuse("null pointer");
+    if (!config_ok(cfg, why) || !linear_counts_ok(q, l, why)) return refuse(why);
     try {
-        pkv::Statement st;
-        st.w = st.b = *cfg;
-        st.hash_version = hash_version;
-        if (io_pattern && io_pattern_len)
-            st.pattern.assign(reinterpret_cast<const char*>(io_pattern), io_pattern_len);
-        else
-            st.pattern = pkw::io_pattern(*cfg, q);
-        if (!pk::io_pattern_parse(st.pattern, st.ops, why)) {
-            pkw::g_error = why;
-            return PK_ERR_IO_PATTERN;
-        }
-        static const uint8_t none = 0;
-        pk::fe root;
-        if (expected_root) root = pk::load_raw(expected_root);
-        pkv::Verdict verdict;
-        pkv::HostBackend be;
-        pkw::PcsWalk walk(st, be, len ? proof : &none, len, verdict, *cfg, reinterpret_cast<const pk::fe*>(points), q, expected_root ? &root : nullptr);
-        walk.run_opening();
-        pkv::to_result(verdict, result);
-        if (evals_out && !walk.evals.empty()) memcpy(evals_out, walk.evals.data(), 32 * walk.evals.size());
+        const std::string d = io_pattern(*cfg, q, l);
+        *len = d.size();
+        if (buf && cap >= d.size()) memcpy(buf, d.data(), d.size());
         return PK_OK;
     } catch (...) {
         return PK_ERR_OOM;
     }
 }
 
-}  // extern "C"
+int verify_linear(const pk_whir_config* cfg, const uint8_t* io_pattern, size_t io_pattern_len, int hash_version, const uint8_t* expected_root,
+                  const uint64_t* points, unsigned q, const uint64_t* tags, const uint64_t* const* weights, unsigned l, const uint8_t* proof, size_t len,
+                  uint64_t* evals_out, uint64_t* sums_out, uint64_t* fold_point_out, uint64_t* deferred_out, unsigned* unchecked_out,
+                  pkv_result* result) {
+    std::string why;
+    if (!config_ok(cfg, why) || !linear_counts_ok(q, l, why)) return refuse(why);
+    if (!result || (q && !points) || !tags || (len && !proof)) return refuse("null pointer");
+    return verify_checked(cfg, io_pattern, io_pattern_len, hash_version, expected_root, points, q, tags, weights, l, proof, len, evals_out, sums_out,
+                          fold_point_out, deferred_out, unchecked_out, result);
+}
+
+}  // namespace pkw

@@ -1,5 +1,6 @@
 """WHIR as a polynomial commitment scheme (libprovekit_whir.so, include/provekit_whir.h): commit to up to 4 multilinear
-polynomials, open them at points of the caller's choice, verify the opening.  PLAIN WHIR, not hiding.
+polynomials, open them at points of the caller's choice -- or at LINEAR statements <w, f> = s over dense weight tables
+(open_linear / verify_linear; the caller's tags bind the weights) -- and verify the opening.  PLAIN WHIR, not hiding.
 
 A fourth library above the product's C ABI, with its own loader and signature table (as provekit_amd.verify).  `verify` and
 `io_pattern` are host only; `Scheme` needs a Context.  A rejected proof is a Result, not an exception; only a failed CALL raises.
@@ -19,6 +20,7 @@ from .verify import Result, ResultStruct
 
 WHIR_LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libprovekit_whir.so")
 MAX_POINTS = 64
+MAX_WEIGHTS = 16
 CHECKS = WALK_CHECKS + ("POINTS", "ROOT", "DEFERRED")
 
 # name -> (restype, argtypes); kept in the same order as include/provekit_whir.h
@@ -41,6 +43,17 @@ SIGNATURES = {
 }
 
 
+# the linear statements: the same library's code under C names a companion library exports (include/provekit_whir_linear.h)
+LINEAR_LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libprovekit_whir_linear.so")
+LINEAR_SIGNATURES = {
+    "pkw_weighted_sums": (C.c_int, [vp, vp, C.c_uint, C.c_uint, vp, C.c_uint, vp]),
+    "pkw_io_pattern_linear": (C.c_int, [vp, C.c_uint, C.c_uint, vp, sz, C.POINTER(sz)]),
+    "pkw_open_linear": (C.c_int, [vp, vp, vp, C.c_uint, vp, vp, C.c_uint, vp, vp, vp, sz, C.POINTER(sz)]),
+    "pkw_verify_linear": (C.c_int, [vp, vp, sz, C.c_int, vp, vp, C.c_uint, vp, vp, C.c_uint, vp, sz, vp, vp, vp, vp, C.POINTER(C.c_uint),
+                                    C.POINTER(ResultStruct)]),
+}
+
+
 def _load():
     if not os.path.exists(WHIR_LIB_PATH):
         raise ImportError(
@@ -51,10 +64,14 @@ def _load():
 
 
 lib = _load()
-for _name, (_res, _args) in SIGNATURES.items():
-    _fn = getattr(lib, _name)  # AttributeError here == header/library mismatch: fail loudly
-    _fn.restype = _res
-    _fn.argtypes = _args
+if not os.path.exists(LINEAR_LIB_PATH):
+    raise ImportError(f"{LINEAR_LIB_PATH} is missing: build it with `make -C provekit_amd/csrc`. provekit_amd has no CPU fallback.")
+linear_lib = C.CDLL(LINEAR_LIB_PATH)
+for _lib, _table in ((lib, SIGNATURES), (linear_lib, LINEAR_SIGNATURES)):
+    for _name, (_res, _args) in _table.items():
+        _fn = getattr(_lib, _name)  # AttributeError here == header/library mismatch: fail loudly
+        _fn.restype = _res
+        _fn.argtypes = _args
 
 
 def _result(r: ResultStruct) -> Result:
@@ -67,6 +84,20 @@ def _points(points, n_vars: int) -> np.ndarray:
     if p.ndim != 3 or p.shape[1:] != (n_vars, 4) or p.shape[0] < 1:
         raise ValueError(f"points must have shape [q, {n_vars}, 4]")
     return p
+
+
+def _points_or_none(points, n_vars: int) -> np.ndarray:
+    """a linear statement may have no points: None or an empty sequence -> [0, n_vars, 4]"""
+    if points is None or len(points) == 0:
+        return np.zeros((0, n_vars, 4), dtype=np.uint64)
+    return _points(points, n_vars)
+
+
+def _tags(tags) -> np.ndarray:
+    t = np.ascontiguousarray(tags, dtype=np.uint64)
+    if t.ndim != 2 or t.shape[1] != 4:
+        raise ValueError("tags must have shape [l, 4]")
+    return t
 
 
 def _ptr_array(bufs):
@@ -90,6 +121,18 @@ def io_pattern(cfg: WhirConfig, q: int) -> bytes:
     return bytes(buf)
 
 
+def io_pattern_linear(cfg: WhirConfig, q: int, l: int) -> bytes:
+    """the operation list of a proof that opens q points and l dense weights (pkw_io_pattern_linear; host only)"""
+    c = _cfg_struct(cfg)
+    n = sz()
+    rc = linear_lib.pkw_io_pattern_linear(C.addressof(c), q, l, None, 0, C.byref(n))
+    if rc:
+        raise ProveKitHipError(rc, lib.pkw_create_error().decode())
+    buf = (C.c_uint8 * n.value)()
+    linear_lib.pkw_io_pattern_linear(C.addressof(c), q, l, buf, n.value, C.byref(n))
+    return bytes(buf)
+
+
 def arena_bytes(cfg: WhirConfig) -> int:
     c = _cfg_struct(cfg)
     n = sz()
@@ -106,6 +149,58 @@ def evaluate(ctx: Context, d_evals, n_vars: int, points) -> np.ndarray:
     out = np.zeros((len(d_evals), p.shape[0], 4), dtype=np.uint64)
     ctx._check(lib.pkw_evaluate(ctx.handle, C.cast(_ptr_array(d_evals), vp), len(d_evals), n_vars, p.ctypes.data, p.shape[0], out.ctypes.data))
     return out
+
+
+def weighted_sums(ctx: Context, d_evals, n_vars: int, d_weights) -> np.ndarray:
+    """[batch, l, 4] Montgomery: <w_i, f_b> = sum_x w_i[x] f_b[x] for device buffers of 2^n_vars elements, a 2 x 2 tile of them (1 x 4 for one polynomial) per
+    pass over memory (pkw_weighted_sums)"""
+    out = np.zeros((len(d_evals), len(d_weights), 4), dtype=np.uint64)
+    ctx._check(linear_lib.pkw_weighted_sums(ctx.handle, C.cast(_ptr_array(d_evals), vp), len(d_evals), n_vars, C.cast(_ptr_array(d_weights), vp),
+                                     len(d_weights), out.ctypes.data))
+    return out
+
+
+class LinearResult:
+    """what pkw_verify_linear hands back next to the verdict.  `unchecked` weights had no table: the verdict then holds PROVIDED
+    deferred[i] is the multilinear extension of weight i at fold_point"""
+
+    def __init__(self, result, evals, sums, fold_point, deferred, unchecked):
+        self.result, self.evals, self.sums, self.fold_point, self.deferred, self.unchecked = result, evals, sums, fold_point, deferred, unchecked
+
+
+def verify_linear(cfg: WhirConfig, points, tags, weights, proof: bytes, expected_root: bytes | None = None, io_pattern: bytes | None = None,
+                  hash_version: int = 2) -> LinearResult:
+    """Host only (pkw_verify_linear).  weights: None, or a list of l entries, each None or a HOST table [2^n_vars, 4] (Montgomery)"""
+    c = _cfg_struct(cfg)
+    p = _points_or_none(points, cfg.n_vars)
+    t = _tags(tags)
+    q, l = p.shape[0], t.shape[0]
+    proof = bytes(proof)
+    tables = None
+    if weights is not None:
+        if len(weights) != l:
+            raise ValueError("as many weights as tags")
+        keep = [None if w is None else np.ascontiguousarray(w, dtype=np.uint64) for w in weights]
+        for w in keep:
+            if w is not None and w.shape != (1 << cfg.n_vars, 4):
+                raise ValueError(f"a weight table has shape [{1 << cfg.n_vars}, 4]")
+        tables = (vp * max(l, 1))(*(None if w is None else w.ctypes.data for w in keep))
+    evals = np.zeros((cfg.batch_size, q, 4), dtype=np.uint64)
+    sums = np.zeros((cfg.batch_size, l, 4), dtype=np.uint64)
+    fold = np.zeros((cfg.n_vars, 4), dtype=np.uint64)
+    deferred = np.zeros((max(l, 1), 4), dtype=np.uint64)
+    unchecked = C.c_uint(0)
+    r = ResultStruct()
+    pat = bytes(io_pattern) if io_pattern else None
+    root = bytes(expected_root) if expected_root is not None else None
+    if root is not None and len(root) != 32:
+        raise ValueError("a root is 32 bytes")
+    rc = linear_lib.pkw_verify_linear(C.addressof(c), pat, len(pat) if pat else 0, hash_version, root, p.ctypes.data if q else None, q, t.ctypes.data,
+                               C.cast(tables, vp) if tables is not None else None, l, proof, len(proof), evals.ctypes.data if q else None,
+                               sums.ctypes.data, fold.ctypes.data, deferred.ctypes.data, C.byref(unchecked), C.byref(r))
+    if rc:
+        raise ProveKitHipError(rc, lib.pkw_create_error().decode())
+    return LinearResult(_result(r), evals, sums, fold, deferred[:l], unchecked.value)
 
 
 def verify(cfg: WhirConfig, points, proof: bytes, expected_root: bytes | None = None, io_pattern: bytes | None = None, hash_version: int = 2):
@@ -189,6 +284,28 @@ class Scheme:
         self._check(lib.pkw_open(self.handle, commitment.handle, p.ctypes.data, p.shape[0], evals.ctypes.data, buf, len(buf) if cap is None else cap,
                                  C.byref(n)))
         return evals, C.string_at(buf, n.value)
+
+    def open_linear(self, commitment: Commitment, points, d_weights, tags, cap: int | None = None):
+        """open at q >= 0 points and l >= 1 dense weights (device buffers of 2^n_vars elements) bound by `tags` [l, 4]
+        -> (evaluations [batch, q, 4], sums [batch, l, 4], proof bytes)"""
+        p = _points_or_none(points, self.cfg.n_vars)
+        t = _tags(tags)
+        q, l = p.shape[0], t.shape[0]
+        if len(d_weights) != l:
+            raise ValueError("as many weights as tags")
+        evals = np.zeros((self.cfg.batch_size, q, 4), dtype=np.uint64)
+        sums = np.zeros((self.cfg.batch_size, max(l, 1), 4), dtype=np.uint64)
+        if cap is None:
+            if self._buf is None:
+                self._buf = (C.c_uint8 * (8 << 20))()
+            buf = self._buf
+        else:
+            buf = (C.c_uint8 * max(cap, 1))()
+        n = sz()
+        self._check(linear_lib.pkw_open_linear(self.handle, commitment.handle, p.ctypes.data if q else None, q, C.cast(_ptr_array(d_weights), vp) if l else None,
+                                        t.ctypes.data, l, evals.ctypes.data if q else None, sums.ctypes.data, buf, len(buf) if cap is None else cap,
+                                        C.byref(n)))
+        return evals, sums[:l], C.string_at(buf, n.value)
 
     def close(self):
         if self.handle is not None and self.ctx.handle is not None:

@@ -38,6 +38,11 @@ SIGNATURES = {
     "pk_probe_sumcheck_cubic_launch": (C.c_int, [vp, vp, vp, vp, vp, sz, vp, C.POINTER(C.c_uint)]),
     "pk_probe_sumcheck_quadratic_launch": (C.c_int, [vp, vp, vp, sz, vp, vp, vp, C.POINTER(C.c_uint)]),
     "pk_probe_sumcheck_collect_spin": (C.c_int, [vp, C.c_uint, vp]),
+    # libprovekit_whir.so's linear-statement kernels where its C ABI does not reach (tools/probes/whir_linear.hip)
+    "pk_probe_whir_combine": (C.c_int, [vp, vp, sz, vp, vp, C.c_uint, C.c_int]),
+    "pk_probe_whir_weighted_sums": (C.c_int, [vp, vp, C.c_uint, C.c_uint, vp, C.c_uint, C.c_uint, C.c_int, vp]),
+    "pk_probe_whir_wsum_grid": (C.c_uint, [C.c_uint]),
+    "pk_probe_wsum_tile_host": (C.c_int, [vp, vp, C.c_uint, vp]),
 }
 for _name, (_res, _args) in SIGNATURES.items():
     _fn = getattr(lib, _name)

@@ -73,6 +73,20 @@ int pk_probe_sumcheck_quadratic_launch(pk_ctx *ctx, const uint64_t *d_f, const u
                                        uint64_t *d_f_out, uint64_t *d_w_out, unsigned *red_seq_out);
 int pk_probe_sumcheck_collect_spin(pk_ctx *ctx, unsigned red_seq, uint64_t out[12]);
 
+/* libprovekit_whir.so's linear-statement kernels (csrc/whir_pcs/linear.hip) where its C ABI does not reach, for
+ * tests/test_gpu_whir_pcs_linear.py and tools/whir_pcs_linear_bench.py.  This library links libprovekit_whir.so for them.
+ * pk_probe_whir_combine: d_w[x] = (accumulate ? d_w[x] : 0) + sum_i scales[i] * d_weights[i][x], x < len (d_weights: HOST array of
+ * l device tables; scales: l HOST elements, Montgomery).  pk_probe_whir_weighted_sums: pkw_weighted_sums on a grid of `grid`
+ * workgroups (0 or 1..pk_probe_whir_wsum_grid(n_vars)) with register tile 0 (what ships: 2 x 2, and 1 x 4 for batch = 1), 1 (1 x 4), 2 (2 x 1) or 3 (2 x 2 always).
+ * pk_probe_wsum_tile_host: the shipped tile's accumulate / flush / result code on the HOST, f = 2 x terms and w = 2 x terms
+ * elements (operand-major), out = 4 elements out[u * 2 + v] = sum_t f[u][t] * w[v][t] * 2^-256 mod p. */
+int pk_probe_whir_combine(pk_ctx *ctx, uint64_t *d_w, size_t len, const uint64_t *const *d_weights, const uint64_t *scales, unsigned l,
+                          int accumulate);
+int pk_probe_whir_weighted_sums(pk_ctx *ctx, const uint64_t *const *d_evals, unsigned batch, unsigned n_vars, const uint64_t *const *d_weights,
+                                unsigned l, unsigned grid, int tile, uint64_t *out);
+unsigned pk_probe_whir_wsum_grid(unsigned n_vars);
+int pk_probe_wsum_tile_host(const uint64_t *f, const uint64_t *w, unsigned terms, uint64_t *out);
+
 #ifdef __cplusplus
 }
 #endif
