@@ -270,13 +270,18 @@ __global__ __launch_bounds__(RED_THREADS) void sumcheck_cubic_kernel(fe* __restr
 // adjacent pairs (2i, 2i+1): h(0)=sum f0 w0, h(1)=sum f1 w1, h(2)=sum (2f1-f0)(2w1-w0)
 // (recursive-verifier/app/circuit/whir_utilities.go:102-125; utilities.go:148-154).
 // FOLD: first v'[i] = v[2i] + r (v[2i+1]-v[2i]) written to the *_out arrays (out-of-place).
-template <bool FOLD>
+// NS = 3: h(0), h(1), h(2).  NS = 2: h(0), h(2) only -- a caller that holds the round's claim h(0) + h(1) (the prover's own
+// sumcheck loop does: it is what the verifier checks) takes h(1) = claim - h(0) on the host; one product per pair less.
+template <bool FOLD, int NS>
 __global__ __launch_bounds__(RED_THREADS) void sumcheck_quadratic_kernel(const fe* __restrict__ f, const fe* __restrict__ w,
                                                                          size_t out_len, fe_arg fold_arg, gate_args gate, fe* __restrict__ f_out,
                                                                          fe* __restrict__ w_out, red_out red) {
     PK_LATENCY_PRIO();
+    static_assert(NS == 2 || NS == 3, "two or three sums");
     const fe r = (FOLD && gate.host) ? gate_wait(gate) : from_arg(fold_arg);
-    fe acc[3] = {fe_zero(), fe_zero(), fe_zero()};
+    fe acc[NS];
+#pragma unroll
+    for (int q = 0; q < NS; q++) acc[q] = fe_zero();
     const size_t npairs = out_len / 2;
     const size_t stride = (size_t)gridDim.x * blockDim.x;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < npairs; i += stride) {
@@ -299,10 +304,10 @@ __global__ __launch_bounds__(RED_THREADS) void sumcheck_quadratic_kernel(const f
             w1 = fe_load(w + 2 * i + 1);
         }
         acc[0] = fe_add(acc[0], fe_mulx(f0, w0));
-        acc[1] = fe_add(acc[1], fe_mulx(f1, w1));
-        acc[2] = fe_add(acc[2], fe_mulx(fe_sub(fe_dbl(f1), f0), fe_sub(fe_dbl(w1), w0)));
+        if (NS == 3) acc[1] = fe_add(acc[1], fe_mulx(f1, w1));
+        acc[NS - 1] = fe_add(acc[NS - 1], fe_mulx(fe_sub(fe_dbl(f1), f0), fe_sub(fe_dbl(w1), w0)));
     }
-    grid_finish_fe<3>(acc, red);
+    grid_finish_fe<NS>(acc, red);
 }
 // ---- small rounds: the work of ONE pair spread over several lanes ------------------------------------------------------
 // Late sumcheck rounds have a handful of pairs; with a lane per pair the round is a chain of 16 (cubic, folding) or 7
@@ -311,6 +316,7 @@ __global__ __launch_bounds__(RED_THREADS) void sumcheck_quadratic_kernel(const f
 // the folded values are exchanged through LDS, and three lanes form the three evaluations: 3 resp. 2 multiplications deep.
 // Same arithmetic, same order of the (exact) field operations per value: results are bit-identical to the wide kernels.
 constexpr size_t SMALL_ROUND_PAIRS = 16384;
+constexpr unsigned EQ_SUFFIX_ONE_WG_VARS = 11;  // suffix equality tables of up to this many variables come from one workgroup
 
 __global__ __launch_bounds__(RED_THREADS) void sumcheck_cubic_small_kernel(fe* __restrict__ a, fe* __restrict__ b, fe* __restrict__ c,
                                                                            fe* __restrict__ eq, size_t len, fe_arg fold_arg, gate_args gate, red_out red) {
@@ -362,7 +368,7 @@ __global__ __launch_bounds__(RED_THREADS) void sumcheck_cubic_small_kernel(fe* _
     grid_finish_fe<3>(acc, red);
 }
 
-template <bool FOLD>
+template <bool FOLD, int NS>
 __global__ __launch_bounds__(RED_THREADS) void sumcheck_quadratic_small_kernel(const fe* __restrict__ f, const fe* __restrict__ w, size_t out_len,
                                                                                fe_arg fold_arg, gate_args gate, fe* __restrict__ f_out, fe* __restrict__ w_out,
                                                                                red_out red) {
@@ -386,24 +392,166 @@ __global__ __launch_bounds__(RED_THREADS) void sumcheck_quadratic_small_kernel(c
         lds_put(xs, xs + RED_THREADS, tid, x);
     }
     __syncthreads();
-    fe acc[3] = {fe_zero(), fe_zero(), fe_zero()};
-    if (i < npairs && role < 3) {
+    fe acc[NS];
+#pragma unroll
+    for (int q = 0; q < NS; q++) acc[q] = fe_zero();
+    if (i < npairs && role < NS) {
         const unsigned base = tid & ~3u;
         const fe f0 = lds_get(xs, xs + RED_THREADS, base), f1 = lds_get(xs, xs + RED_THREADS, base + 1);
         const fe w0 = lds_get(xs, xs + RED_THREADS, base + 2), w1 = lds_get(xs, xs + RED_THREADS, base + 3);
-        // one multiplication on operands selected by role: h(0) = f0 w0, h(1) = f1 w1, h(2) = (2f1-f0)(2w1-w0)
+        // one multiplication on operands selected by role: h(0) = f0 w0, h(1) = f1 w1, h(2) = (2f1-f0)(2w1-w0); two sums: role 1 forms h(2)
+        const unsigned ev = NS == 3 ? role : 2 * role;
         const fe tf = fe_sub(fe_dbl(f1), f0), tw = fe_sub(fe_dbl(w1), w0);
         fe X, Y;
 #pragma unroll
         for (int v = 0; v < 8; v++) {
-            X.v[v] = role == 0 ? f0.v[v] : role == 1 ? f1.v[v] : tf.v[v];
-            Y.v[v] = role == 0 ? w0.v[v] : role == 1 ? w1.v[v] : tw.v[v];
+            X.v[v] = ev == 0 ? f0.v[v] : ev == 1 ? f1.v[v] : tf.v[v];
+            Y.v[v] = ev == 0 ? w0.v[v] : ev == 1 ? w1.v[v] : tw.v[v];
         }
         const fe t = fe_mulx(X, Y);
 #pragma unroll
-        for (int q = 0; q < 3; q++)
+        for (int q = 0; q < NS; q++)
 #pragma unroll
             for (int v = 0; v < 8; v++) acc[q].v[v] = role == (unsigned)q ? t.v[v] : 0u;
+    }
+    grid_finish_fe<NS>(acc, red);
+}
+
+// ---------------------------------------------------------------- S2 / S3 without the folded eq array
+// eq is a product table: with variables 0 .. i-1 bound to alpha, the folded eq array of round i is
+//   eq0[x] = P_i (1 - r_i) E_i[x],  eq1[x] = P_i r_i E_i[x],   P_i = prod_{k<i} eq(r_k, alpha_k),  E_i = eq(r[i+1 .. n), .),
+// so the round's three sums are P_i (1 - r_i) Q(0), P_i (2 - 3 r_i) Q(-1), P_i (2 r_i - 1) Q_inf with
+//   Q(0) = sum E (a0 b0 - c0),  Q(-1) = sum E ((2a0-a1)(2b0-b1) - (2c0-c1)),  Q_inf = sum E (a1-a0)(b1-b0):
+// the kernels below fold a, b, c only, read one entry of the read-only level E_i per pair and return the three Q; the scalars are
+// three host products (sumcheck_spliteq_correct).  12 products per folding pair instead of 15, three arrays moved instead of four.
+//
+// The levels E_0 .. E_{n-1} (2^(n-1), ..., 1 entries; variable 0 <-> most significant index bit, eval_eq's order) sit back to back
+// in one buffer of 2^n elements: E_i at 2^n - 2^(n-i).  E_{n-1} = {1}; E_{i-1}[h + j] = r_i E_i[j], E_{i-1}[j] = E_i[j] - that, h = |E_i|.
+struct point_args {
+    fe_arg x[27];  // m_0 <= 27 (pk_scheme_create)
+};
+// one workgroup per point (blockIdx.x: 0 or 1): every level of the nv-variable point x[first, first + nv) by the recursion above,
+// level by level as eq_half_tables_kernel, each level kept.  nv <= 14: the largest level has 2^13 entries.
+__global__ __launch_bounds__(256) void eq_suffix_levels_kernel(point_args pt, unsigned first0, unsigned nv0, fe* __restrict__ out0, unsigned first1,
+                                                               unsigned nv1, fe* __restrict__ out1) {
+    PK_LATENCY_PRIO();
+    __shared__ uint4 xs[2 * 16];
+    const unsigned first = blockIdx.x ? first1 : first0, nv = blockIdx.x ? nv1 : nv0;
+    fe* const out = blockIdx.x ? out1 : out0;
+    const size_t N = (size_t)1 << nv;
+    if (threadIdx.x < nv) lds_put(xs, xs + 16, threadIdx.x, from_arg(pt.x[first + threadIdx.x]));
+    if (threadIdx.x == 32) fe_store(out + N - 2, fe_one());  // level nv - 1
+    __threadfence_block();
+    __syncthreads();
+    for (unsigned l = nv - 1; l >= 1; l--) {  // level l - 1 from level l
+        const size_t h = N >> (l + 1);
+        const fe* in = out + N - (N >> l);
+        fe* o = out + N - (N >> (l - 1));
+        const fe xv = lds_get(xs, xs + 16, l);
+        for (size_t j = threadIdx.x; j < h; j += 256) {
+            const fe t = fe_load(in + j);
+            const fe up = fe_mulx(t, xv);
+            fe_store(o + h + j, up);
+            fe_store(o + j, fe_sub(t, up));
+        }
+        __threadfence_block();
+        __syncthreads();
+    }
+}
+// the long levels 0 .. L-1 of an n-variable point, grid-wide, one product per entry: E_i[xhi, xlo] = F_i[xhi] E_L[xlo], where E_L (the
+// tail of E itself, n-1-L index bits) and F = the levels of the point r[0, L] (F_i = eq(r[i+1 .. L], .)) come from the kernel above
+__global__ __launch_bounds__(256) void eq_suffix_expand_kernel(fe* __restrict__ E, const fe* __restrict__ F, unsigned n, unsigned L) {
+    PK_LATENCY_PRIO();
+    const size_t N = (size_t)1 << n, total = N - (N >> L), NF = (size_t)2 << L;
+    const unsigned nlo = n - 1 - L;
+    const fe* EL = E + total;
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x; g < total; g += stride) {
+        const unsigned i = n - 1 - (63 - (unsigned)__clzll((long long)(N - g - 1)));  // N - g lies in (2^(n-i-1), 2^(n-i)]
+        const size_t x = g - (N - (N >> i));
+        fe_store(E + g, fe_mulx(fe_load(F + (NF - (NF >> i)) + (x >> nlo)), fe_load(EL + (x & (((size_t)1 << nlo) - 1)))));
+    }
+}
+
+template <bool FOLD>
+__global__ __launch_bounds__(RED_THREADS) void sumcheck_cubic_spliteq_kernel(fe* __restrict__ a, fe* __restrict__ b, fe* __restrict__ c,
+                                                                             const fe* __restrict__ E, size_t len, fe_arg fold_arg, gate_args gate,
+                                                                             red_out red) {
+    PK_LATENCY_PRIO();
+    const fe alpha = (FOLD && gate.host) ? gate_wait(gate) : from_arg(fold_arg);
+    const size_t npairs = FOLD ? len / 4 : len / 2;
+    const size_t off = npairs, foff = len / 2;  // as sumcheck_cubic_kernel
+    fe acc[3] = {fe_zero(), fe_zero(), fe_zero()};
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < npairs; i += stride) {
+        fe v[3][2];
+        fe* arr[3] = {a, b, c};
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            fe x0 = fe_load(arr[k] + i), x1 = fe_load(arr[k] + i + off);
+            if (FOLD) {
+                fe x2 = fe_load(arr[k] + i + foff), x3 = fe_load(arr[k] + i + off + foff);
+                x0 = fe_add(x0, fe_mulx(alpha, fe_sub(x2, x0)));
+                x1 = fe_add(x1, fe_mulx(alpha, fe_sub(x3, x1)));
+                fe_store(arr[k] + i, x0);
+                fe_store(arr[k] + i + off, x1);
+            }
+            v[k][0] = x0;
+            v[k][1] = x1;
+        }
+        const fe &a0 = v[0][0], &a1 = v[0][1], &b0 = v[1][0], &b1 = v[1][1], &c0 = v[2][0], &c1 = v[2][1];
+        const fe e = fe_load(E + i);
+        acc[0] = fe_add(acc[0], fe_mulx(e, fe_sub(fe_mulx(a0, b0), c0)));
+        fe ta = fe_sub(fe_dbl(a0), a1), tb = fe_sub(fe_dbl(b0), b1), tc = fe_sub(fe_dbl(c0), c1);
+        acc[1] = fe_add(acc[1], fe_mulx(e, fe_sub(fe_mulx(ta, tb), tc)));
+        acc[2] = fe_add(acc[2], fe_mulx(e, fe_mulx(fe_sub(a1, a0), fe_sub(b1, b0))));
+    }
+    grid_finish_fe<3>(acc, red);
+}
+// few pairs: eight lanes per pair as sumcheck_cubic_small_kernel -- six fold a value each, the seventh fetches the pair's E entry --
+// then three lanes form E * (Y*Z - S): one fold product and two more deep
+__global__ __launch_bounds__(RED_THREADS) void sumcheck_cubic_spliteq_small_kernel(fe* __restrict__ a, fe* __restrict__ b, fe* __restrict__ c,
+                                                                                   const fe* __restrict__ E, size_t len, fe_arg fold_arg, gate_args gate,
+                                                                                   red_out red) {
+    PK_LATENCY_PRIO();
+    __shared__ uint4 xs[2 * RED_THREADS];
+    const fe alpha = gate.host ? gate_wait(gate) : from_arg(fold_arg);
+    const size_t npairs = len / 4, off = npairs, foff = len / 2;
+    const unsigned tid = threadIdx.x, g = tid >> 3, role = tid & 7, k = role >> 1, which = role & 1;
+    const size_t i = (size_t)blockIdx.x * (RED_THREADS / 8) + g;
+    if (i < npairs && k < 3) {
+        fe* p = (k == 0 ? a : k == 1 ? b : c) + i + (which ? off : 0);
+        fe x = fe_load(p), x2 = fe_load(p + foff);
+        x = fe_add(x, fe_mulx(alpha, fe_sub(x2, x)));
+        fe_store(p, x);
+        lds_put(xs, xs + RED_THREADS, tid, x);
+    } else if (i < npairs && role == 6) {
+        lds_put(xs, xs + RED_THREADS, tid, fe_load(E + i));
+    }
+    __syncthreads();
+    fe acc[3] = {fe_zero(), fe_zero(), fe_zero()};
+    if (i < npairs && role < 3) {
+        const unsigned base = tid & ~7u;
+        auto v = [&](unsigned kk, unsigned w) { return lds_get(xs, xs + RED_THREADS, base + 2 * kk + w); };
+        const fe a0 = v(0, 0), a1 = v(0, 1), b0 = v(1, 0), b1 = v(1, 1), c0 = v(2, 0), c1 = v(2, 1), e = v(3, 0);
+        //   role 0: Q(0)  = E * (a0*b0 - c0)
+        //   role 1: Q(-1) = E * ((2a0-a1)(2b0-b1) - (2c0-c1))
+        //   role 2: Q_inf = E * ((a1-a0)(b1-b0) - 0)
+        auto pick = [&](const fe& x0, const fe& x1) {
+            fe m1 = fe_sub(fe_dbl(x0), x1), d = fe_sub(x1, x0), r;
+#pragma unroll
+            for (int w = 0; w < 8; w++) r.v[w] = role == 0 ? x0.v[w] : role == 1 ? m1.v[w] : d.v[w];
+            return r;
+        };
+        const fe pa = pick(a0, a1), pb = pick(b0, b1);
+        fe S = pick(c0, c1);
+#pragma unroll
+        for (int w = 0; w < 8; w++) S.v[w] = role == 2 ? 0u : S.v[w];
+        const fe t = fe_mulx(e, fe_sub(fe_mulx(pa, pb), S));
+#pragma unroll
+        for (int r = 0; r < 3; r++)
+#pragma unroll
+            for (int w = 0; w < 8; w++) acc[r].v[w] = role == (unsigned)r ? t.v[w] : 0u;
     }
     grid_finish_fe<3>(acc, red);
 }
@@ -658,9 +806,78 @@ int sumcheck_cubic_launch(pk_ctx* ctx, uint64_t* d_a, uint64_t* d_b, uint64_t* d
     PK_LAUNCH_CHECK(ctx);
     return PK_OK;
 }
+// the same round without the eq array: d_level = E_i of the round the kernel evaluates (npairs entries, read only); the sums are Q(0), Q(-1), Q_inf
+int sumcheck_cubic_spliteq_launch(pk_ctx* ctx, uint64_t* d_a, uint64_t* d_b, uint64_t* d_c, const uint64_t* d_level, size_t len,
+                                  const uint64_t* fold_or_null, unsigned gate_seq, unsigned* red_seq_out) {
+    PK_REQUIRE(ctx, d_a && d_b && d_c && d_level && red_seq_out, "null pointer");
+    PK_REQUIRE(ctx, is_pow2(len) && len >= 2, "size must be a power of two >= 2");
+    const bool fold = fold_or_null || gate_seq;
+    PK_REQUIRE(ctx, !fold || len >= 4, "size must be >= 4 when folding");
+    const size_t npairs = fold ? len / 4 : len / 2;
+    red_out red;
+    unsigned blocks;
+    int rc = reduction_begin(ctx, npairs, &red, &blocks);
+    if (rc) return rc;
+    *red_seq_out = red.seq;
+    const gate_args gate = gate_seq ? gate_for(ctx, gate_seq) : gate_none();
+    const fe_arg farg = fold_or_null ? to_arg(fold_or_null) : fe_arg{};
+    const bool small = fold && npairs <= SMALL_ROUND_PAIRS;  // the same routing as sumcheck_cubic_launch
+    auto kernel = small ? sumcheck_cubic_spliteq_small_kernel : fold ? sumcheck_cubic_spliteq_kernel<true> : sumcheck_cubic_spliteq_kernel<false>;
+    if (small) blocks = (unsigned)((npairs + RED_THREADS / 8 - 1) / (RED_THREADS / 8));
+    {
+        ProfScope prof(ctx, "sumcheck_cubic");
+        kernel<<<blocks, RED_THREADS, 0, ctx->stream>>>((fe*)d_a, (fe*)d_b, (fe*)d_c, (const fe*)d_level, len, farg, gate, red);
+    }
+    PK_LAUNCH_CHECK(ctx);
+    return PK_OK;
+}
+// out[0..12) = Q(0), Q(-1), Q_inf of round i  ->  the round's f(0), f(-1), f_inf;  P = P_i, r_i = the round's coordinate of the eq point
+void sumcheck_spliteq_correct(const uint64_t P[4], const uint64_t r_i[4], uint64_t out[12]) {
+    fe p, r, q[3];
+    memcpy(p.v, P, 32);
+    memcpy(r.v, r_i, 32);
+    memcpy(q, out, 96);
+    const fe one = fe_one(), r2 = fe_dbl(r);
+    q[0] = fe_mulx(fe_mulx(p, fe_sub(one, r)), q[0]);                          // P (1 - r)
+    q[1] = fe_mulx(fe_mulx(p, fe_sub(fe_dbl(one), fe_add(r2, r))), q[1]);      // P (2 - 3r)
+    q[2] = fe_mulx(fe_mulx(p, fe_sub(r2, one)), q[2]);                         // P (2r - 1)
+    memcpy(out, q, 96);
+}
+// P_{i+1} = P_i eq(r_i, alpha_i)
+void sumcheck_spliteq_advance(uint64_t P[4], const uint64_t r_i[4], const uint64_t alpha_i[4]) {
+    fe p, r, a;
+    memcpy(p.v, P, 32);
+    memcpy(r.v, r_i, 32);
+    memcpy(a.v, alpha_i, 32);
+    const fe one = fe_one(), ra = fe_mulx(r, a);
+    p = fe_mulx(p, fe_add(fe_sub(fe_sub(one, r), a), fe_dbl(ra)));  // (1-r)(1-a) + r a = 1 - r - a + 2 r a
+    memcpy(P, p.v, 32);
+}
+// every level E_0 .. E_{n-1} of the point r[0, n) into d_out (2^n elements; the layout above)
+int eq_suffix_tables(pk_ctx* ctx, const uint64_t* r, unsigned n, uint64_t* d_out) {
+    PK_REQUIRE(ctx, r && d_out, "null pointer");
+    PK_REQUIRE(ctx, n >= 1 && n <= 27, "1 .. 27 variables");
+    point_args pt{};
+    for (unsigned i = 0; i < n; i++) pt.x[i] = to_arg(r + 4 * i);
+    fe* E = (fe*)d_out;
+    ProfScope prof(ctx, "eq_suffix_tables");
+    if (n <= EQ_SUFFIX_ONE_WG_VARS) {  // one workgroup builds everything
+        eq_suffix_levels_kernel<<<1, 256, 0, ctx->stream>>>(pt, 0, n, E, 0, 0, nullptr);
+    } else {  // levels L .. n-1 (the point r[L, n)) and the factor tables (the point r[0, L]) by one workgroup each, levels 0 .. L-1 grid-wide
+        const unsigned L = n / 2;
+        const size_t N = (size_t)1 << n, total = N - (N >> L);
+        int rc = ensure_ws(ctx, (size_t)64 << L);
+        if (rc) return rc;
+        eq_suffix_levels_kernel<<<2, 256, 0, ctx->stream>>>(pt, L, n - L, E + total, 0, L + 1, (fe*)ctx->d_ws);
+        eq_suffix_expand_kernel<<<grid_for(ctx, total, 256), 256, 0, ctx->stream>>>(E, (const fe*)ctx->d_ws, n, L);
+    }
+    PK_LAUNCH_CHECK(ctx);
+    return PK_OK;
+}
+// nsums = 3: h(0), h(1), h(2); nsums = 2: h(0), h(2) -- the caller holds the claim h(0) + h(1)
 int sumcheck_quadratic_launch(pk_ctx* ctx, const uint64_t* d_f, const uint64_t* d_w, size_t len, const uint64_t* fold_or_null, unsigned gate_seq,
-                              uint64_t* d_f_out, uint64_t* d_w_out, unsigned* red_seq_out) {
-    PK_REQUIRE(ctx, d_f && d_w && red_seq_out, "null pointer");
+                              uint64_t* d_f_out, uint64_t* d_w_out, int nsums, unsigned* red_seq_out) {
+    PK_REQUIRE(ctx, d_f && d_w && red_seq_out && (nsums == 2 || nsums == 3), "null pointer");
     PK_REQUIRE(ctx, is_pow2(len), "size must be a power of two");
     const bool fold = fold_or_null || gate_seq;
     const size_t out_len = fold ? len / 2 : len;
@@ -678,8 +895,10 @@ int sumcheck_quadratic_launch(pk_ctx* ctx, const uint64_t* d_f, const uint64_t* 
     if (!fold) d_f_out = d_w_out = nullptr;
     // a lane per pair, or -- rounds of few pairs, folding or not -- four lanes per pair
     const bool small = npairs <= SMALL_ROUND_PAIRS;
-    auto kernel = small ? (fold ? sumcheck_quadratic_small_kernel<true> : sumcheck_quadratic_small_kernel<false>)
-                        : (fold ? sumcheck_quadratic_kernel<true> : sumcheck_quadratic_kernel<false>);
+    auto kernel = nsums == 3 ? (small ? (fold ? sumcheck_quadratic_small_kernel<true, 3> : sumcheck_quadratic_small_kernel<false, 3>)
+                                      : (fold ? sumcheck_quadratic_kernel<true, 3> : sumcheck_quadratic_kernel<false, 3>))
+                             : (small ? (fold ? sumcheck_quadratic_small_kernel<true, 2> : sumcheck_quadratic_small_kernel<false, 2>)
+                                      : (fold ? sumcheck_quadratic_kernel<true, 2> : sumcheck_quadratic_kernel<false, 2>));
     if (small) blocks = (unsigned)((npairs + RED_THREADS / 4 - 1) / (RED_THREADS / 4));
     {
         ProfScope prof(ctx, "sumcheck_quadratic");
@@ -689,7 +908,17 @@ int sumcheck_quadratic_launch(pk_ctx* ctx, const uint64_t* d_f, const uint64_t* 
     return PK_OK;
 }
 // the host's side of a gated launch and the wait for a launch's three results without draining the stream (prover.hip, latency mode)
-int sumcheck_collect_spin(pk_ctx* ctx, unsigned red_seq, uint64_t out[12]) { return collect_reduction_spin(ctx, 3, red_seq, out); }
+int sumcheck_collect_spin(pk_ctx* ctx, int nsums, unsigned red_seq, uint64_t out[12]) { return collect_reduction_spin(ctx, nsums, red_seq, out); }
+int sumcheck_collect(pk_ctx* ctx, int nsums, uint64_t out[12]) { return collect_reduction(ctx, nsums, out); }  // after a launch without a gate
+// the three-sum message of a two-sum round: out = h(0), h(2)  ->  h(0), h(1) = claim - h(0), h(2)
+void sumcheck_quadratic_from_claim(const uint64_t claim[4], uint64_t out[12]) {
+    fe cl, h0;
+    memcpy(cl.v, claim, 32);
+    memcpy(h0.v, out, 32);
+    const fe h1 = fe_sub(cl, h0);
+    memcpy(out + 8, out + 4, 32);
+    memcpy(out + 4, h1.v, 32);
+}
 unsigned sumcheck_gate_next(pk_ctx* ctx) { return gate_next(ctx); }
 // 0 = no gated kernel of this context gave up on its challenge since the last call, else PK_ERR_HIP with the message set (reduce.hpp)
 void sumcheck_gate_clear(pk_ctx* ctx) { (void)gate_timed_out(ctx); }  // forget a give-up word without touching the error message
@@ -860,9 +1089,47 @@ int pk_sumcheck_quadratic_round(pk_ctx* ctx, const uint64_t* d_f, const uint64_t
     PK_ENTER(ctx);
     PK_REQUIRE(ctx, out, "null pointer");
     unsigned seq = 0;
-    int rc = sumcheck_quadratic_launch(ctx, d_f, d_w, len, fold_or_null, 0, d_f_out, d_w_out, &seq);
+    int rc = sumcheck_quadratic_launch(ctx, d_f, d_w, len, fold_or_null, 0, d_f_out, d_w_out, 3, &seq);
     if (rc) return rc;
     return collect_reduction(ctx, 3, out);
+}
+
+// test entry points (tools/probes/pk_selftest.h): the routes of Proof::zk_rounds and WhirProver::sumcheck_rounds, one round per call
+int pk_selftest_eq_suffix_tables(pk_ctx* ctx, const uint64_t* r, unsigned n, uint64_t* d_out) {
+    PK_ENTER(ctx);
+    return eq_suffix_tables(ctx, r, n, d_out);
+}
+// round `round` of the n-variable cubic sumcheck on a, b, c as they stand after round - 1 rounds (2^(n - round + 1) entries; 2^n for round 0): folds by
+// alphas[round - 1] if round > 0, then out = f(0), f(-1), f_inf as pk_sumcheck_cubic_round gives them for the eq table of r folded by the same alphas
+int pk_selftest_sumcheck_cubic_spliteq(pk_ctx* ctx, uint64_t* d_a, uint64_t* d_b, uint64_t* d_c, const uint64_t* d_tables, unsigned n, unsigned round,
+                                       const uint64_t* r, const uint64_t* alphas, uint64_t out[12]) {
+    PK_ENTER(ctx);
+    PK_REQUIRE(ctx, out && r && d_tables && n >= 1 && n <= 27 && round < n && (round == 0 || alphas), "bad round");
+    const size_t N = (size_t)1 << n, len = round ? N >> (round - 1) : N;
+    unsigned seq = 0;
+    int rc = sumcheck_cubic_spliteq_launch(ctx, d_a, d_b, d_c, d_tables + 4 * (N - (N >> round)), len, round ? alphas + 4 * (round - 1) : nullptr, 0, &seq);
+    if (rc) return rc;
+    rc = collect_reduction(ctx, 3, out);
+    if (rc) return rc;
+    uint64_t P[4];
+    const fe one = fe_one();
+    memcpy(P, one.v, 32);
+    for (unsigned k = 0; k < round; k++) sumcheck_spliteq_advance(P, r + 4 * k, alphas + 4 * k);
+    sumcheck_spliteq_correct(P, r + 4 * round, out);
+    return PK_OK;
+}
+// pk_sumcheck_quadratic_round by the two-sum kernels: out = h(0), claim - h(0), h(2)
+int pk_selftest_sumcheck_quadratic_claim(pk_ctx* ctx, const uint64_t* d_f, const uint64_t* d_w, size_t len, const uint64_t* fold_or_null,
+                                         uint64_t* d_f_out, uint64_t* d_w_out, const uint64_t claim[4], uint64_t out[12]) {
+    PK_ENTER(ctx);
+    PK_REQUIRE(ctx, out && claim, "null pointer");
+    unsigned seq = 0;
+    int rc = sumcheck_quadratic_launch(ctx, d_f, d_w, len, fold_or_null, 0, d_f_out, d_w_out, 2, &seq);
+    if (rc) return rc;
+    rc = collect_reduction(ctx, 2, out);
+    if (rc) return rc;
+    sumcheck_quadratic_from_claim(claim, out);
+    return PK_OK;
 }
 
 int pk_fold_pairs(pk_ctx* ctx, const uint64_t* d_v, size_t len, const uint64_t* r, uint64_t* d_out) {

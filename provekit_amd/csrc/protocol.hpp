@@ -223,6 +223,13 @@ inline fe eval_cubic(const fe c[4], const fe& x) {  // provekit/common/src/utils
     return h_add(c[0], h_mul(x, h_add(c[1], h_mul(x, h_add(c[2], h_mul(x, c[3]))))));
 }
 
+// the quadratic through h(0), h(1), h(2) = h[0..3) at x: the WHIR sumcheck's next claim (whir_utilities.go:102-125)
+inline fe eval_quadratic_012(const fe h[3], const fe& x) {
+    const fe c2 = h_mul(h_half(), h_add(h_sub(h_sub(h[2], h[1]), h[1]), h[0]));  // h(2) = 2 h(1) - h(0) + 2 c2
+    const fe c1 = h_sub(h_sub(h[1], h[0]), c2);
+    return h_add(h[0], h_mul(x, h_add(c1, h_mul(x, c2))));
+}
+
 // ---- proof of work (utilities.go:84-101): POW_CHALLENGE_BYTES challenge bytes are squeezed, the nonce is absorbed as 8 big-endian
 // bytes; compress(challenge, nonce) must lie below the threshold ----------------------------------------------------------------------
 constexpr size_t POW_CHALLENGE_BYTES = 32, POW_NONCE_BYTES = 8;

@@ -321,6 +321,8 @@ struct WhirProver {
     int cur = 0;
     size_t len;             // local length of p and w
     std::vector<fe> rs;     // the challenges of the last sumcheck_rounds call
+    fe claim;               // <p, w>, the sum the next sumcheck round's h(0) + h(1) must equal -- while have_claim
+    bool have_claim = false;
     std::vector<fe> all_r;  // every folding challenge, in squeeze order
 
     WhirProver(pk_ctx* c, Arena& a, const pk_whir_config& cf, const Commitment& com, Transcript& t)
@@ -367,7 +369,9 @@ struct WhirProver {
     }
 
     // `rounds` quadratic sumcheck rounds on p, w, each: the round's h(0), h(1), h(2), absorb, squeeze the folding challenge, record
-    // it; afterwards p, w describe the folded polynomial.  Latency mode (one GPU): round t+1's kernel -- after the last round the
+    // it; afterwards p, w describe the folded polynomial.  A round whose claim h(0) + h(1) the prover holds -- every round but the
+    // first after new weights went into w: the claim is the previous round's h(r), and before the first call the statement's own
+    // sum (start) -- asks its kernel for h(0) and h(2) only and takes h(1) = claim - h(0).  Latency mode (one GPU): round t+1's kernel -- after the last round the
     // fold -- is enqueued BEFORE round t's result is read, gated on the challenge the host publishes once it has squeezed it; the
     // round trip then costs the link, not a launch + sync.  Otherwise every round is a synchronous call that first folds by the
     // previous challenge (sharded: its h(0), h(1), h(2) are sums over the ranks' blocks).
@@ -375,27 +379,36 @@ struct WhirProver {
         rs.clear();
         const bool pipelined = ctx->latency_mode && G == 1 && rounds && len >= ((size_t)1 << rounds);
         unsigned red_cur = 0, red_next = 0;
-        if (pipelined) CK(sumcheck_quadratic_launch(ctx, U(bp[cur]), U(bw[cur]), len, nullptr, 0, nullptr, nullptr, &red_cur));
+        const int ns0 = have_claim ? 2 : 3;  // sums of round 0; the later rounds always have their claim
+        if (pipelined) CK(sumcheck_quadratic_launch(ctx, U(bp[cur]), U(bw[cur]), len, nullptr, 0, nullptr, nullptr, ns0, &red_cur));
         for (unsigned t = 0; t < rounds; t++) {  // the same steps in the same order as Proof::zk_rounds
             PendingGate gate(ctx);
+            const int ns = t ? 2 : ns0;
             // pipelined: what consumes this round's challenge -- the next round (folding first), or the closing fold -- goes into the queue, gated
             const bool more = t + 1 < rounds;
             if (pipelined && (more || len >= 2)) {
                 gate.arm(sumcheck_gate_next(ctx));
-                if (more) CK(sumcheck_quadratic_launch(ctx, U(bp[cur]), U(bw[cur]), len, nullptr, gate.seq, U(bp[1 - cur]), U(bw[1 - cur]), &red_next));
+                if (more) CK(sumcheck_quadratic_launch(ctx, U(bp[cur]), U(bw[cur]), len, nullptr, gate.seq, U(bp[1 - cur]), U(bw[1 - cur]), 2, &red_next));
                 else CK(fold_pairs2(ctx, U(bp[cur]), U(bp[1 - cur]), U(bw[cur]), U(bw[1 - cur]), len, nullptr, gate.seq));
                 flip();
             }
             uint64_t out[12], f[4];
             if (pipelined) {
-                CK(sumcheck_collect_spin(ctx, red_cur, out));
+                CK(sumcheck_collect_spin(ctx, ns, red_cur, out));
                 red_cur = red_next;
             } else {
-                Across ac(ctx, sharded);  // sharded: h(0), h(1), h(2) are sums over the ranks' blocks
+                Across ac(ctx, sharded);  // sharded: the sums are sums over the ranks' blocks
                 CK(ac.rc);
                 if (t) h_store(f, rs.back());
-                CK(pk_sumcheck_quadratic_round(ctx, U(bp[cur]), U(bw[cur]), len, t ? f : nullptr, U(bp[1 - cur]), U(bw[1 - cur]), out));  // round 0 folds nothing, writes nothing
+                unsigned seq = 0;
+                CK(sumcheck_quadratic_launch(ctx, U(bp[cur]), U(bw[cur]), len, t ? f : nullptr, 0, U(bp[1 - cur]), U(bw[1 - cur]), ns, &seq));  // round 0 folds nothing, writes nothing
+                CK(sumcheck_collect(ctx, ns, out));
                 if (t) flip();
+            }
+            if (ns == 2) {
+                uint64_t cl[4];
+                h_store(cl, claim);
+                sumcheck_quadratic_from_claim(cl, out);
             }
             const fe msg[3] = {h_load(out), h_load(out + 4), h_load(out + 8)};
             T.add_scalars(msg, 3);
@@ -403,6 +416,8 @@ struct WhirProver {
             gate.publish(r);
             rs.push_back(r);
             all_r.push_back(r);
+            claim = eval_quadratic_012(msg, r);  // the next round's h(0) + h(1)
+            have_claim = true;
         }
         if (!pipelined && rounds && len >= 2) {  // apply the last challenge: p, w now describe the folded polynomial
             uint64_t f[4];
@@ -428,7 +443,8 @@ struct WhirProver {
     int maybe_gather() { return sharded && len <= SHARD_MIN_LOCAL ? gather(gathered[0], gathered[1], gathered[2], gathered[3]) : PK_OK; }
 
     // the working polynomial, the sumcheck tables, the initial weights and the first k sumcheck rounds
-    int start(fe* const* d_weights, const size_t* weight_len, unsigned n_weights) {
+    // weight_sums[i * batch + b] = <weight i, polynomial b>, as the transcript holds them (may be null: the first round then forms three sums)
+    int start(fe* const* d_weights, const size_t* weight_len, unsigned n_weights, const fe* weight_sums) {
         const size_t N = (size_t)1 << n;
         ALLOC(dc, N);
         d_c = dc;
@@ -453,11 +469,23 @@ struct WhirProver {
         const fe gamma = T.challenge_scalar();
         fe g;
         CK(eq_weights(w0, n, C.ood_points, gamma, /*overwrite=*/1, &g));
+        // <p, w> of the tables just built, from values the transcript holds: an OOD constraint's sum is its answer, a statement weight's its claimed sum
+        auto batched = [&](const fe* v, size_t step) {  // sum_b beta^b v[b * step]
+            fe acc = v[0], bb = C.beta;
+            for (unsigned b = 1; b < C.batch; b++, bb = h_mul(bb, C.beta)) acc = h_add(acc, h_mul(bb, v[b * step]));
+            return acc;
+        };
+        const size_t q = C.ood_points.size();
+        claim = fe_zero();
+        fe gq = fe_one();
+        for (size_t j = 0; j < q; j++, gq = h_mul(gq, gamma)) claim = h_add(claim, h_mul(gq, batched(&C.ood_answers[j], q)));
+        have_claim = weight_sums || !n_weights;
         for (unsigned i = 0; i < n_weights; i++) {
             uint64_t s[4];
             h_store(s, g);
             const size_t cnt = in_block(weight_len[i], off0, B0);
             if (cnt) CK(pk_fe_axpy(ctx, U(w0), s, U(d_weights[i] + off0), cnt));
+            if (weight_sums) claim = h_add(claim, h_mul(g, batched(weight_sums + (size_t)i * C.batch, 1)));
             g = h_mul(g, gamma);
         }
         if (sharded) {
@@ -509,6 +537,7 @@ struct WhirProver {
             for (uint64_t i : idx) zs.push_back(h_pow(exp_gen, i));
             fe g;
             CK(eq_weights(bw[cur], nv, zs, gamma, 0, &g));
+            have_claim = false;  // the new weights' sums include the folded polynomial at the STIR points, which the prover never evaluates
             // W3
             CK(sumcheck_rounds(k));
             CK(maybe_gather());
@@ -580,9 +609,9 @@ struct WhirProver {
     }
 };
 int whir_prove(pk_ctx* ctx, Arena& A, const pk_whir_config& cfg, const Commitment& C, fe* const* d_weights, const size_t* weight_len,
-               unsigned n_weights, Transcript& T) {
+               unsigned n_weights, const fe* weight_sums, Transcript& T) {
     WhirProver P(ctx, A, cfg, C, T);
-    CK(P.start(d_weights, weight_len, n_weights));
+    CK(P.start(d_weights, weight_len, n_weights, weight_sums));
     CK(P.rounds());
     return P.deferred_hint(d_weights, weight_len, n_weights);
 }
@@ -699,6 +728,7 @@ struct Proof {
     fe* h_univ = nullptr;    // ... as the side stream copied them into its mailbox
     std::vector<fe> alpha;   // the zk sumcheck's challenges
     fe* rows = nullptr;      // the three external rows, n_witness each
+    fe row_sums[6];          // their sums against f and g: [row][f, g]
     const bool timing = getenv("PK_PROVE_TIMING") != nullptr;
     std::chrono::steady_clock::time_point t_lap = std::chrono::steady_clock::now();
 
@@ -732,7 +762,7 @@ struct Proof {
     int commit_witness();
     int blinding_transcript();
     int zk_sumcheck();
-    int zk_rounds(fe* z[4], size_t len, bool sharded);
+    int zk_rounds(fe* z[4], size_t len, bool sharded, const fe* r);
     int prove_blinding();
     int witness_statement();
     int prove_witness();
@@ -824,20 +854,32 @@ int Proof::zk_sumcheck() {
         CK(pk_eq_accumulate(ctx, U(d_eq), m_0 - lgG, (const uint64_t*)r.data(), (const uint64_t*)&sc, 1, 1));  // S2
     } else {
         CK(pk_r1cs_witness_bounds(ctx, s->r1cs, U(d_witness), m_0, U(d_a), U(d_b), U(d_cc)));  // S1
-        CK(pk_eq_table(ctx, (const uint64_t*)r.data(), m_0, U(d_eq)));                       // S2
+        CK(eq_suffix_tables(ctx, (const uint64_t*)r.data(), m_0, U(d_eq)));                  // S2: the levels E_i instead of the table (mle.hip)
     }
     if (aux == ctx) CK(blinding_compute(ctx, *this));  // else the side stream finished it long ago
     CK(blinding_transcript());
     lap("bounds+eq+blinding commit");
     fe* z[4] = {d_a, d_b, d_cc, d_eq};
-    return zk_rounds(z, length, sharded);
+    return zk_rounds(z, length, sharded, sharded ? nullptr : r.data());
 }
 
 // the m_0 cubic rounds, each: the round's evaluations, the message, absorb, squeeze, record.  Latency mode (one GPU): round t+1 is
 // in the queue, gated on a_t, while round t is absorbed.  Otherwise every round is a synchronous call that first folds by the
 // previous challenge (sharded: its evaluations are sums over the ranks' shares; short shares are gathered and finish replicated).
-int Proof::zk_rounds(fe* z[4], size_t len, bool sharded) {
+// r != null (every proof that is not sharded): z[3] holds the suffix equality tables of r instead of the eq array, the kernels fold a, b,
+// c only and return Q(0), Q(-1), Q_inf; the round's scalars P_t (1 - r_t), P_t (2 - 3 r_t), P_t (2 r_t - 1) are applied here.  A sharded
+// proof (r == null) keeps the four-array kernels: its arrays are split by the LOW index bits, which a level E_t does not factor over.
+int Proof::zk_rounds(fe* z[4], size_t len, bool sharded, const fe* r) {
     const unsigned m_0 = s->m_0;
+    const bool split = r != nullptr;
+    const size_t M = len;
+    uint64_t P[4];  // P_t = prod_{k<t} eq(r_k, alpha_k)
+    h_store(P, fe_one());
+    // round t's kernel (folding first by `fold` or by the gate's challenge): the level E_t or the eq array
+    auto launch = [&](unsigned t, size_t l, const uint64_t* fold, unsigned gate_seq, unsigned* seq) {
+        return split ? sumcheck_cubic_spliteq_launch(ctx, U(z[0]), U(z[1]), U(z[2]), U(z[3] + (M - (M >> t))), l, fold, gate_seq, seq)
+                     : sumcheck_cubic_launch(ctx, U(z[0]), U(z[1]), U(z[2]), U(z[3]), l, fold, gate_seq, seq);
+    };
     // sum_over_hypercube (whir_r1cs.rs:172-180)
     fe gp[4];
     blinding_coefficients_for_round(g_univ, 0, nullptr, gp);
@@ -858,7 +900,7 @@ int Proof::zk_rounds(fe* z[4], size_t len, bool sharded) {
     }
     const bool pipelined = ctx->latency_mode && G == 1 && m_0 >= 2;
     unsigned red_cur = 0, red_next = 0;
-    if (pipelined) CK(sumcheck_cubic_launch(ctx, U(z[0]), U(z[1]), U(z[2]), U(z[3]), len, nullptr, 0, &red_cur));
+    if (pipelined) CK(launch(0, len, nullptr, 0, &red_cur));
     alpha.reserve(m_0);
     for (unsigned t = 0; t < m_0; t++) {  // the hot loop, whir_r1cs.rs:280-345; the same steps in the same order as WhirProver::sumcheck_rounds
         PendingGate gate(ctx);
@@ -866,14 +908,14 @@ int Proof::zk_rounds(fe* z[4], size_t len, bool sharded) {
         const bool more = t + 1 < m_0;
         if (pipelined && more) {
             gate.arm(sumcheck_gate_next(ctx));
-            CK(sumcheck_cubic_launch(ctx, U(z[0]), U(z[1]), U(z[2]), U(z[3]), len, nullptr, gate.seq, &red_next));
+            CK(launch(t + 1, len, nullptr, gate.seq, &red_next));
             len /= 2;
         }
         // the round's blinding coefficients depend only on the earlier challenges: in latency mode computed while the kernel runs
         blinding_coefficients_for_round(g_univ, t, alpha.data(), gp);
         uint64_t out[12], f[4];
         if (pipelined) {
-            CK(sumcheck_collect_spin(ctx, red_cur, out));
+            CK(sumcheck_collect_spin(ctx, 3, red_cur, out));
             red_cur = red_next;
         } else {
             if (sharded && len <= SHARD_MIN_LOCAL) {  // short shares: gather, re-interleave, finish replicated
@@ -887,16 +929,24 @@ int Proof::zk_rounds(fe* z[4], size_t len, bool sharded) {
             Across ac(ctx, sharded);  // sharded: the three evaluations are sums over the ranks' shares
             CK(ac.rc);
             if (t) h_store(f, alpha.back());
-            CK(pk_sumcheck_cubic_round(ctx, U(z[0]), U(z[1]), U(z[2]), U(z[3]), len, t ? f : nullptr, out));
+            unsigned seq = 0;
+            CK(launch(t, len, t ? f : nullptr, 0, &seq));
+            CK(sumcheck_collect(ctx, 3, out));
             if (t) len /= 2;
         }
+        if (split) sumcheck_spliteq_correct(P, U(r + t), out);
         fe msg[4];
         zk_round_message(out, gp, rho, saved, msg);
         T.add_scalars(msg, 4);
-        const fe r = T.challenge_scalar();
-        gate.publish(r);
-        alpha.push_back(r);
-        saved = eval_cubic(msg, r);
+        const fe a = T.challenge_scalar();
+        gate.publish(a);
+        alpha.push_back(a);
+        if (split) {
+            uint64_t aw[4];
+            h_store(aw, a);
+            sumcheck_spliteq_advance(P, U(r + t), aw);
+        }
+        saved = eval_cubic(msg, a);
     }
     return PK_OK;
 }
@@ -921,7 +971,7 @@ int Proof::prove_blinding() {
     const fe sums[2] = {h_load(fg), h_load(fg + 4)};
     T.add_scalars(sums, 2);
     fe* wts[1] = {d_bw};
-    return whir_prove(ctx, A, s->whir_hiding, B.com, wts, &nbw, 1, T);
+    return whir_prove(ctx, A, s->whir_hiding, B.com, wts, &nbw, 1, sums, T);
 }
 
 // --- the statement over the witness commitment (whir_r1cs.rs:81-91): external rows, their six sums, the claimed_evaluations hint
@@ -942,8 +992,8 @@ int Proof::witness_statement() {
     // hint::<(Vec<F>, Vec<F>)>: the three sums against f, then the three against g
     fe fsum[3], gsum[3];
     for (int k = 0; k < 3; k++) {
-        fsum[k] = h_load(o + 8 * k);
-        gsum[k] = h_load(o + 8 * k + 4);
+        fsum[k] = row_sums[2 * k] = h_load(o + 8 * k);
+        gsum[k] = row_sums[2 * k + 1] = h_load(o + 8 * k + 4);
     }
     std::vector<uint8_t> claimed;
     put_vec(claimed, fsum, 3);
@@ -956,7 +1006,7 @@ int Proof::witness_statement() {
 int Proof::prove_witness() {
     fe* wts[3] = {rows, rows + n_witness, rows + 2 * n_witness};
     const size_t wlen[3] = {n_witness, n_witness, n_witness};
-    CK(whir_prove(ctx, A, s->whir_witness, W.com, wts, wlen, 3, T));
+    CK(whir_prove(ctx, A, s->whir_witness, W.com, wts, wlen, 3, row_sums, T));
     return pk_ctx_sync(ctx);
 }
 

@@ -33,6 +33,18 @@ int pk_selftest_dft(const uint64_t *in, const uint64_t *tw, uint64_t *out, int l
  * >= live past the nonzero inputs; out = the lazy result (selftest.hip). */
 int pk_selftest_pre_load(const uint64_t *x, const uint64_t *tw, uint64_t *out, int terms, int live, size_t n);
 
+/* the routes of the prover's two sumcheck loops that do without redundant work, one step per call (csrc/mle.hip):
+ * the suffix equality tables of r[0, n): the levels E_i = eq(r[i+1 .. n), .), i = 0 .. n-1, back to back in d_out (2^n elements, E_i at
+ * 2^n - 2^(n-i), variable 0 <-> the most significant index bit);
+ * round `round` of the n-variable cubic sumcheck on a, b, c as they stand after the earlier rounds: folds by alphas[round - 1] (round > 0), sums
+ * against the level E_round of d_tables and applies the host scalars: out = what pk_sumcheck_cubic_round returns for the eq array;
+ * pk_sumcheck_quadratic_round by the two-sum kernels: out = h(0), claim - h(0), h(2) */
+int pk_selftest_eq_suffix_tables(pk_ctx *ctx, const uint64_t *r, unsigned n, uint64_t *d_out);
+int pk_selftest_sumcheck_cubic_spliteq(pk_ctx *ctx, uint64_t *d_a, uint64_t *d_b, uint64_t *d_c, const uint64_t *d_tables, unsigned n, unsigned round,
+                                       const uint64_t *r, const uint64_t *alphas, uint64_t out[12]);
+int pk_selftest_sumcheck_quadratic_claim(pk_ctx *ctx, const uint64_t *d_f, const uint64_t *d_w, size_t len, const uint64_t *fold_or_null,
+                                         uint64_t *d_f_out, uint64_t *d_w_out, const uint64_t claim[4], uint64_t out[12]);
+
 /* hooks of the GPU suite (process-wide, 0 = off; the library reads no test switch from the environment): which = 0 the spin bound of a
  * latency-mode gated kernel (to reach its give-up path in milliseconds), 1 microseconds the host sleeps before publishing each gate's
  * challenge (a stalled host thread), 2 non-zero = pk_ctx_create_set takes the RCCL branch for a repeated device (with PK_RCCL_LIB naming the

@@ -931,11 +931,11 @@ int pk_probe_sumcheck_cubic_launch(pk_ctx* ctx, uint64_t* d_a, uint64_t* d_b, ui
 int pk_probe_sumcheck_quadratic_launch(pk_ctx* ctx, const uint64_t* d_f, const uint64_t* d_w, size_t len, const uint64_t* fold_or_null,
                                        uint64_t* d_f_out, uint64_t* d_w_out, unsigned* red_seq_out) {
     PK_ENTER(ctx);
-    return sumcheck_quadratic_launch(ctx, d_f, d_w, len, fold_or_null, 0, d_f_out, d_w_out, red_seq_out);
+    return sumcheck_quadratic_launch(ctx, d_f, d_w, len, fold_or_null, 0, d_f_out, d_w_out, 3, red_seq_out);
 }
 int pk_probe_sumcheck_collect_spin(pk_ctx* ctx, unsigned red_seq, uint64_t out[12]) {
     PK_ENTER(ctx);
     PK_REQUIRE(ctx, out && red_seq && ctx->h_pinned && red_seq == ctx->red_seq, "not the sequence number of this context's last launch");
-    return sumcheck_collect_spin(ctx, red_seq, out);
+    return sumcheck_collect_spin(ctx, 3, red_seq, out);
 }
 }  // extern "C"
