@@ -1,10 +1,12 @@
 // provekit_whir.hpp -- provekit::WhirPcs: the C++ face of libprovekit_whir.so (include/provekit_whir.h), next to provekit_hip.hpp's
 // prover types and provekit_verify.hpp's Verdict.  Commit to multilinear polynomials, open them at points or at linear statements
 // over dense weight tables, verify: PLAIN WHIR, not hiding.  open_linear / verify_linear need libprovekit_whir_linear.so linked next to
-// libprovekit_whir.so (provekit_whir_linear.h).  A rejected proof is a Verdict, not an exception; only a failed call throws provekit::Error.
+// libprovekit_whir.so (provekit_whir_linear.h); open_sparse / verify_sparse, which state the same weights as index/value lists,
+// need libprovekit_whir_sparse.so (provekit_whir_sparse.h).  A rejected proof is a Verdict, not an exception; only a failed call throws provekit::Error.
 #pragma once
 #include "provekit_hip.hpp"
 #include "provekit_whir.h"
+#include "provekit_whir_sparse.h"
 
 namespace provekit {
 
@@ -40,6 +42,21 @@ struct PcsLinearVerdict {
     std::vector<FieldElement> deferred;  // one per weight
     unsigned unchecked = 0;
     explicit operator bool() const { return verdict.accepted; }
+};
+
+// l sparse weights on the host (provekit_whir_sparse.h): weight i owns entries offsets[i] .. offsets[i + 1]; indexes increase
+// strictly within a weight.  add() appends one weight
+struct PcsSparseWeights {
+    std::vector<uint64_t> offsets{0};
+    std::vector<uint32_t> index;
+    std::vector<FieldElement> value;
+    void add(const std::vector<uint32_t>& idx, const std::vector<FieldElement>& val) {
+        if (idx.size() != val.size()) throw Error(PK_ERR_BAD_ARG, "as many values as indexes");
+        index.insert(index.end(), idx.begin(), idx.end());
+        value.insert(value.end(), val.begin(), val.end());
+        offsets.push_back(index.size());
+    }
+    unsigned count() const { return (unsigned)offsets.size() - 1; }
 };
 
 class WhirPcs;
@@ -160,6 +177,59 @@ class WhirPcs {
                                        proof.size(), out.evaluations.empty() ? nullptr : out.evaluations[0].data(),
                                        out.sums.empty() ? nullptr : out.sums[0].data(), fold.data(),
                                        out.deferred.empty() ? nullptr : out.deferred[0].data(), &out.unchecked, &r))
+            throw Error(rc, pkw_create_error());
+        for (unsigned j = 0; j < c.n_vars; j++) std::copy(fold.begin() + 4 * j, fold.begin() + 4 * j + 4, out.fold_point[j].begin());
+        out.verdict = {r.accepted != 0, r.check, r.offset, r.message};
+        return out;
+    }
+    // open_linear with the weights as lists: the same statement and the same bytes.  The lists are copied to the device for the
+    // call (a caller that keeps them there calls pkw_open_sparse); the library validates the indexes before it uses one
+    PcsLinearOpening open_sparse(const Context& ctx, const PcsCommitment& com, const std::vector<Point>& points, const PcsSparseWeights& weights,
+                                 const std::vector<FieldElement>& tags) const {
+        if (weights.count() != tags.size()) throw Error(PK_ERR_BAD_ARG, "as many tags as weights");
+        const std::vector<uint64_t> flat = flatten(points, cfg_.n_vars, /*may_be_empty=*/true);
+        const size_t entries = weights.index.size();
+        const DeviceVec d_value(ctx, weights.value), d_index(ctx, (entries + 7) / 8);  // 8 indexes per 32 bytes
+        if (entries) ctx.check(pk_memcpy_h2d(ctx.get(), d_index.data(), weights.index.data(), 4 * entries));
+        PcsLinearOpening o;
+        o.evaluations.resize((size_t)cfg_.batch_size * points.size());
+        o.sums.resize((size_t)cfg_.batch_size * tags.size());
+        o.proof.resize(1 << 20);
+        size_t len = 0;
+        auto call = [&] {
+            return pkw_open_sparse(s_, com.get(), flat.data(), (unsigned)points.size(), weights.offsets.data(),
+                                   reinterpret_cast<const uint32_t*>(d_index.data()), d_value.data(), tags.empty() ? nullptr : tags[0].data(), weights.count(),
+                                   o.evaluations.empty() ? nullptr : o.evaluations[0].data(), o.sums.empty() ? nullptr : o.sums[0].data(), o.proof.data(),
+                                   o.proof.size(), &len);
+        };
+        int rc = call();
+        if (rc == PK_ERR_BAD_ARG && len > o.proof.size()) {  // the proof is larger: *len says by how much
+            o.proof.resize(len);
+            rc = call();
+        }
+        check(rc);
+        o.proof.resize(len);
+        return o;
+    }
+    // host only; every weight's deferred value is judged from its entries: `unchecked` stays 0 and the verdict is unconditional
+    static PcsLinearVerdict verify_sparse(const WhirConfig& cfg, const std::vector<Point>& points, const std::vector<FieldElement>& tags,
+                                          const PcsSparseWeights& weights, const std::vector<uint8_t>& proof,
+                                          const std::array<uint8_t, 32>* expected_root = nullptr, int hash_version = 2) {
+        const pk_whir_config c = cfg.to_c();
+        const std::vector<uint64_t> flat = flatten(points, c.n_vars, /*may_be_empty=*/true);
+        if (weights.count() != tags.size()) throw Error(PK_ERR_BAD_ARG, "as many weights as tags");
+        PcsLinearVerdict out;
+        out.evaluations.resize((size_t)c.batch_size * points.size());
+        out.sums.resize((size_t)c.batch_size * tags.size());
+        out.fold_point.resize(c.n_vars);
+        out.deferred.resize(tags.size());
+        std::vector<uint64_t> fold(4 * (size_t)c.n_vars + 4);
+        pkv_result r;
+        if (int rc = pkw_verify_sparse(&c, nullptr, 0, hash_version, expected_root ? expected_root->data() : nullptr, flat.data(), (unsigned)points.size(),
+                                       tags.empty() ? nullptr : tags[0].data(), weights.offsets.data(), weights.index.empty() ? nullptr : weights.index.data(),
+                                       weights.value.empty() ? nullptr : weights.value[0].data(), weights.count(), proof.data(), proof.size(),
+                                       out.evaluations.empty() ? nullptr : out.evaluations[0].data(), out.sums.empty() ? nullptr : out.sums[0].data(),
+                                       fold.data(), out.deferred.empty() ? nullptr : out.deferred[0].data(), &r))
             throw Error(rc, pkw_create_error());
         for (unsigned j = 0; j < c.n_vars; j++) std::copy(fold.begin() + 4 * j, fold.begin() + 4 * j + 4, out.fold_point[j].begin());
         out.verdict = {r.accepted != 0, r.check, r.offset, r.message};

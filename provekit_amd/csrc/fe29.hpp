@@ -345,9 +345,12 @@ PK_HD fe29 shoup_quotient29(const fe29& w) {
 
 // ---- sums of products with one reduction per group ------------------------------------------------
 // sum_t a_t * b_t (mod p) the cheap way: the 17 column accumulators take the partial products of up to DOT29_GROUP terms
-// before ONE Montgomery reduction (81 multiply-adds per term instead of 162).  a_t: any 256-bit value (unpack29<0>),
+// before ONE Montgomery reduction (81 multiply-adds per term instead of 162).  a_t < p (unpack29<0>),
 // b_t = unpack29<5>(y_t) with y_t < p, i.e. 32*y_t: a term adds < 2^61.2 to a column and a*32y/2^261 < 0.19p to the value.
-// Column bound: (DOT29_GROUP + 1) * 2^61.2 < 2^64.
+// Column bound: (DOT29_GROUP + 1) * 2^61.2 < 2^64; it holds for ANY 256-bit a_t.  The VALUE bound of the running sum does not: a
+// term with a_t up to 2^256 - 1 adds up to p, a group of four 5p, and the running sum then exceeds what reduce_almost29 takes
+// (eight terms in a row of 2^256 - 1 against p - 1 give a wrong result; single such terms among reduced ones stay inside the bound).
+// Callers whose first factors may be unreduced throughout reduce them first (whir_pcs/sparse.hpp).
 constexpr int DOT29_GROUP = 4;
 struct dot29 {
     u64 acc[17];

@@ -167,6 +167,11 @@ int eval_launch(hipStream_t stream, const uint64_t* const* d_evals, unsigned bat
     return hipGetLastError() == hipSuccess ? PK_OK : PK_ERR_HIP;
 }
 
+int eval_finish_launch(hipStream_t stream, const uint64_t* d_partial, unsigned n_wg, unsigned rows, unsigned count, uint64_t* d_out, unsigned out_stride) {
+    eval_finish_kernel<<<rows * count, THREADS, 0, stream>>>((const fe*)d_partial, n_wg, count, (fe*)d_out, out_stride);
+    return hipGetLastError() == hipSuccess ? PK_OK : PK_ERR_HIP;
+}
+
 }  // namespace pkw
 
 extern "C" {

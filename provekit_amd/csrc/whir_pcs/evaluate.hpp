@@ -16,5 +16,8 @@ size_t eval_partial_fes(unsigned batch, unsigned n_vars);
 // enqueue on `stream`: d_out[b * q + i] = MLE(d_evals[b])(d_points[i]); d_points = q * n_vars elements on the device
 int eval_launch(hipStream_t stream, const uint64_t* const* d_evals, unsigned batch, unsigned n_vars, const uint64_t* d_points, unsigned q,
                 uint64_t* d_partial, uint64_t* d_out);
+// enqueue on `stream`: d_out[y * out_stride + i] = the sum of the n_wg partials d_partial[(y * EVAL_PASS + i) * n_wg ..] for y < rows,
+// i < count <= EVAL_PASS: the second half of eval_launch, for kernels that leave their partials in the same layout (sparse.hip)
+int eval_finish_launch(hipStream_t stream, const uint64_t* d_partial, unsigned n_wg, unsigned rows, unsigned count, uint64_t* d_out, unsigned out_stride);
 
 }  // namespace pkw

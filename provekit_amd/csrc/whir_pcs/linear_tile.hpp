@@ -18,7 +18,8 @@ PK_HD void wsum_tile_init(WsumTile<TB, TW>& t) {
 #pragma unroll
         for (int v = 0; v < TW; v++) pk::dot29_init(t.d[u][v]);
 }
-// one element of every tiled operand: f any 256-bit value, w < p (dot29's contract: the second factor travels as 32 w)
+// one element of every tiled operand: f < p, w < p (dot29's contract: the second factor travels as 32 w; a first factor of p or more
+// is tolerated only now and then, see fe29.hpp -- sparse.hpp's step reduces gathered elements for that reason)
 template <int TB, int TW>
 PK_HD void wsum_tile_step(WsumTile<TB, TW>& t, const pk::fe (&f)[TB], const pk::fe (&w)[TW]) {
     pk::fe29 x[TB], y[TW];

@@ -7,6 +7,7 @@
 // is ever materialised, and their deferred evaluations eq(point_i, folding point) are O(n) products on the host.  The linear
 // constraints of pkw_open_linear are dense tables on the device: linear.hip's kernels give their sums and add them to the same
 // weight table in one pass, and evaluate.hip's kernel reads them once more at the folding point for their deferred evaluations.
+// pkw_open_sparse states the same constraints as index/value lists: the same three steps, each by its twin in sparse.hip.
 #include <hip/hip_runtime.h>
 
 #include <map>
@@ -15,6 +16,7 @@
 #include "evaluate.hpp"
 #include "linear.hpp"
 #include "pcs.hpp"
+#include "sparse.hpp"
 
 using pk::fe;
 
@@ -78,6 +80,13 @@ struct Tree {  // a committed codeword: what a round's STIR queries open
     const uint64_t *leaves, *nodes;
     size_t rows, width;
     pk_commit_layout layout;
+};
+
+// where the l weights of a linear statement come from: dense device tables, or validated index/value lists.  The three steps of an
+// opening that touch the weights ask this
+struct WeightSource {
+    const uint64_t* const* dense = nullptr;
+    const SparseWeights* sparse = nullptr;
 };
 
 struct Opening {
@@ -181,9 +190,28 @@ struct Opening {
         return PK_OK;
     }
 
-    // q evaluation constraints, then l linear ones (l = 0: pkw_open); weights: l device tables, tags: l host elements
-    int run(const fe* points, unsigned q, fe* evals /* batch * q */, const uint64_t* const* weights, const fe* tags, unsigned l,
-            fe* sums /* batch * l */) {
+    // the three steps that read the weights, each from either source.  d_out[b * l + i] = <w_i, poly_b>
+    int weight_sums(const WeightSource& W, unsigned l, uint64_t* d_part, uint64_t* d_out) {
+        if (W.sparse) return sparse_sums_launch(S.stream, C.evals, cfg.batch_size, n, *W.sparse, d_part, d_out);
+        return wsum_launch(S.stream, C.evals, cfg.batch_size, n, W.dense, l, d_part, d_out);
+    }
+    // d_w += sum_i scales[i] w_i
+    int weight_combine(const WeightSource& W, unsigned l, uint64_t* d_w, const fe* scales) {
+        if (W.sparse) return sparse_accumulate_launch(S.stream, d_w, *W.sparse, U(scales));
+        return combine_launch(S.stream, d_w, (size_t)1 << n, W.dense, U(scales), l, /*accumulate=*/1);
+    }
+    // d_out[i] = the extension of w_i at d_point.  The dense tables are read EVAL_MAX_BATCH at a time by the evaluation kernel (its
+    // partials for EVAL_MAX_BATCH tables go into the commit scratch, idle by now); the lists' partials go where the sums' went
+    int weight_deferred(const WeightSource& W, unsigned l, const uint64_t* d_point, uint64_t* d_part, uint64_t* scratch, uint64_t* d_out) {
+        if (W.sparse) return sparse_evaluate_launch(S.stream, n, *W.sparse, d_point, d_part, d_out);
+        if (eval_partial_fes(EVAL_MAX_BATCH, n) > plan(cfg).scratch) return PK_ERR_OOM;
+        for (unsigned i0 = 0; i0 < l; i0 += EVAL_MAX_BATCH)
+            CK(eval_launch(S.stream, W.dense + i0, std::min(EVAL_MAX_BATCH, l - i0), n, d_point, 1, scratch, d_out + 4 * (size_t)i0));
+        return PK_OK;
+    }
+
+    // q evaluation constraints, then l linear ones (l = 0: pkw_open); W: the l weights, tags: l host elements
+    int run(const fe* points, unsigned q, fe* evals /* batch * q */, const WeightSource& W, const fe* tags, unsigned l, fe* sums /* batch * l */) {
         const size_t N = (size_t)1 << n;
         const unsigned batch = cfg.batch_size;
         TAKE(scratch, plan(cfg).scratch);
@@ -202,7 +230,7 @@ struct Opening {
         TAKE(d_pts, (size_t)PKW_MAX_POINTS * n);
         TAKE(d_part, eval_partial_fes(batch, n));
         TAKE(d_out, (size_t)PKW_MAX_POINTS * batch);
-        if (wsum_partial_fes(batch, n) > eval_partial_fes(batch, n)) return PK_ERR_OOM;
+        if ((W.sparse ? sparse_partial_fes(batch, n) : wsum_partial_fes(batch, n)) > eval_partial_fes(batch, n)) return PK_ERR_OOM;
         CK(pk_ctx_sync(ctx));
         if (q) {
             CK(pk_memcpy_h2d(ctx, d_pts, points, 32 * (size_t)q * n));
@@ -213,7 +241,7 @@ struct Opening {
         }
         T.add_scalars(evals, (size_t)batch * q);
         if (l) {
-            CK(wsum_launch(S.stream, C.evals, batch, n, weights, l, d_part, d_out));
+            CK(weight_sums(W, l, d_part, d_out));
             if (hipStreamSynchronize(S.stream) != hipSuccess) return PK_ERR_HIP;
             CK(pk_memcpy_d2h(ctx, sums, d_out, 32 * (size_t)batch * l));
         }
@@ -229,7 +257,7 @@ struct Opening {
         p[0] = p0, p[1] = p1, w[0] = w0, w[1] = w1;
         CK(batch_combine(p0, C.evals, beta));
         fe gamma = T.challenge_scalar(), g;
-        {  // weights = sum gamma^i w_i over [OOD constraints..., eq(point_i, .)..., the dense tables...]
+        {  // weights = sum gamma^i w_i over [OOD constraints..., eq(point_i, .)..., the l weights...]
             std::vector<fe> pts((ood.size() + q) * n + 1);
             for (size_t j = 0; j < ood.size(); j++) pk::expand_from_univariate(ood[j], n, &pts[j * n]);
             std::copy(points, points + (size_t)q * n, pts.begin() + ood.size() * n);
@@ -241,7 +269,7 @@ struct Opening {
                     g = pk::h_mul(g, gamma);
                 }
                 CK(pk_ctx_sync(ctx));  // the eq weights are the context's work: in the table before the kernel adds to it
-                CK(combine_launch(S.stream, w0, N, weights, U(scales.data()), l, /*accumulate=*/1));
+                CK(weight_combine(W, l, w0, scales.data()));
                 if (hipStreamSynchronize(S.stream) != hipSuccess) return PK_ERR_HIP;
             }
         }
@@ -296,17 +324,14 @@ struct Opening {
         CK(sumcheck_rounds(final_vars));
         CK(pow_round(cfg.final_folding_pow_bits));
         // deferred_weight_evaluations: each weight's MLE at the folding point, reverse(all_r) in eval_eq's MSB-first order; for
-        // eq(point_i, .) that is eq(point_i, folding point); the dense tables are read once, EVAL_MAX_BATCH at a time, by the
-        // evaluation kernel (its partials for EVAL_MAX_BATCH tables go into the commit scratch, idle by now)
+        // eq(point_i, .) that is eq(point_i, folding point); the l weights are read once more (weight_deferred)
         const std::vector<fe> point(all_r.rbegin(), all_r.rend());
         std::vector<fe> deferred(q + l);
         for (unsigned i = 0; i < q; i++) deferred[i] = pkv::eq_poly(points + (size_t)i * n, point.data(), n);
         if (l) {
-            if (eval_partial_fes(EVAL_MAX_BATCH, n) > plan(cfg).scratch) return PK_ERR_OOM;
             CK(pk_memcpy_h2d(ctx, d_pts, point.data(), 32 * (size_t)n));
             CK(pk_ctx_sync(ctx));
-            for (unsigned i0 = 0; i0 < l; i0 += EVAL_MAX_BATCH)
-                CK(eval_launch(S.stream, weights + i0, std::min(EVAL_MAX_BATCH, l - i0), n, d_pts, 1, scratch, d_out + 4 * (size_t)i0));
+            CK(weight_deferred(W, l, d_pts, d_part, scratch, d_out));
             if (hipStreamSynchronize(S.stream) != hipSuccess) return PK_ERR_HIP;
             CK(pk_memcpy_d2h(ctx, deferred.data() + q, d_out, 32 * (size_t)l));
         }
@@ -430,14 +455,13 @@ int pkw_commitment_destroy(pkw_commitment* com) {
 namespace pkw {
 namespace {
 
-// the opening both entry points make once their arguments are checked; l = 0: pkw_open
-int open_checked(pkw_scheme* s, const pkw_commitment* com, const std::string& pattern, const uint64_t* points, unsigned q,
-             const uint64_t* const* d_weights, const uint64_t* tags, unsigned l, uint64_t* evals_out, uint64_t* sums_out, uint8_t* proof_out, size_t cap,
-             size_t* len) {
+// the opening every entry point makes once its arguments are checked; l = 0: pkw_open
+int open_checked(pkw_scheme* s, const pkw_commitment* com, const std::string& pattern, const uint64_t* points, unsigned q, const WeightSource& W,
+                 const uint64_t* tags, unsigned l, uint64_t* evals_out, uint64_t* sums_out, uint8_t* proof_out, size_t cap, size_t* len) {
     pk::Transcript T(pattern);
     std::vector<fe> evals((size_t)s->cfg.batch_size * q + 1), sums((size_t)s->cfg.batch_size * l + 1);
     pkw::Opening op(*s, *com, T);
-    const int rc = op.run(reinterpret_cast<const fe*>(points), q, evals.data(), d_weights, reinterpret_cast<const fe*>(tags), l, sums.data());
+    const int rc = op.run(reinterpret_cast<const fe*>(points), q, evals.data(), W, reinterpret_cast<const fe*>(tags), l, sums.data());
     if (rc) return pkw::fail(s, rc, rc == PK_ERR_OOM ? "the arena is too small for this opening" : std::string("open: ") + pk_last_error(s->ctx));
     if (!T.finished())
         return pkw::fail(s, PK_ERR_IO_PATTERN, T.violation().empty() ? "the proof ended before its IO pattern did" : T.violation());
@@ -462,7 +486,7 @@ int pkw_open(pkw_scheme* s, const pkw_commitment* com, const uint64_t* points, u
     if (q < 1 || q > PKW_MAX_POINTS) return pkw::fail(s, PK_ERR_BAD_ARG, "the number of points must be 1..64");
     try {
         if (s->pattern_cache[q].empty()) s->pattern_cache[q] = pkw::io_pattern(s->cfg, q);
-        return pkw::open_checked(s, com, s->pattern_cache[q], points, q, nullptr, nullptr, 0, evals_out, nullptr, proof_out, cap, len);
+        return pkw::open_checked(s, com, s->pattern_cache[q], points, q, pkw::WeightSource{}, nullptr, 0, evals_out, nullptr, proof_out, cap, len);
     } catch (...) {
         return pkw::fail(s, PK_ERR_OOM, "out of memory");
     }
@@ -490,7 +514,36 @@ int open_linear(pkw_scheme* s, const pkw_commitment* com, const uint64_t* points
     try {
         std::string& pattern = s->linear_pattern_cache[q * (PKW_MAX_WEIGHTS + 1) + l];
         if (pattern.empty()) pattern = io_pattern(s->cfg, q, l);
-        return open_checked(s, com, pattern, points, q, d_weights, tags, l, evals_out, sums_out, proof_out, cap, len);
+        return open_checked(s, com, pattern, points, q, WeightSource{d_weights, nullptr}, tags, l, evals_out, sums_out, proof_out, cap, len);
+    } catch (...) {
+        return fail(s, PK_ERR_OOM, "out of memory");
+    }
+}
+
+// the entry point behind pkw_open_sparse (sparse_abi.cpp): pkw_open_linear's counts, pattern and bytes; the lists are validated
+// here, once (the 8 bytes the pass reports through are the arena's first: an opening starts from its front afterwards)
+int open_sparse(pkw_scheme* s, const pkw_commitment* com, const uint64_t* points, unsigned q, const uint64_t* offsets, const uint32_t* d_index,
+                const uint64_t* d_value, const uint64_t* tags, unsigned l, uint64_t* evals_out, uint64_t* sums_out, uint8_t* proof_out, size_t cap, size_t* len) {
+    if (!s) return PK_ERR_BAD_ARG;
+    std::string why;
+    if (!linear_counts_ok(q, l, why)) return fail(s, PK_ERR_BAD_ARG, why);
+    if (!com || (q && !points) || !offsets || !tags || !len || (cap && !proof_out)) return fail(s, PK_ERR_BAD_ARG, "null pointer");
+    if (com->scheme != s) return fail(s, PK_ERR_BAD_ARG, "the commitment belongs to another scheme");
+    const unsigned n = s->cfg.n_vars, batch = s->cfg.batch_size;
+    if (!sparse_offsets_ok(offsets, l, n, why)) return fail(s, PK_ERR_BAD_ARG, why);
+    if (offsets[l] && (!d_index || !d_value)) return fail(s, PK_ERR_BAD_ARG, "null index or value list");
+    if (sparse_partial_fes(batch, n) > eval_partial_fes(batch, n)) return fail(s, PK_ERR_OOM, "this config's arena is too small for a sparse opening");
+    try {
+        const SparseWeights w{offsets, d_index, d_value, l};
+        size_t bad = 0;
+        uint32_t at = 0, prev = 0;
+        int rc = pk_ctx_sync(s->ctx);  // the lists are the context's work: there before the pass reads them
+        if (!rc) rc = sparse_validate(s->ctx, s->stream, w, n, s->arena, &bad, &at, &prev);
+        if (rc) return fail(s, rc, std::string("open: ") + pk_last_error(s->ctx));
+        if (bad != ~(size_t)0) return fail(s, PK_ERR_BAD_ARG, sparse_index_reason(w, bad, at, prev, n));
+        std::string& pattern = s->linear_pattern_cache[q * (PKW_MAX_WEIGHTS + 1) + l];
+        if (pattern.empty()) pattern = io_pattern(s->cfg, q, l);
+        return open_checked(s, com, pattern, points, q, WeightSource{nullptr, &w}, tags, l, evals_out, sums_out, proof_out, cap, len);
     } catch (...) {
         return fail(s, PK_ERR_OOM, "out of memory");
     }

@@ -140,6 +140,22 @@ int verify_linear(const pk_whir_config* cfg, const uint8_t* io_pattern, size_t i
                   const uint64_t* points, unsigned q, const uint64_t* tags, const uint64_t* const* weights, unsigned l, const uint8_t* proof, size_t len,
                   uint64_t* evals_out, uint64_t* sums_out, uint64_t* fold_point_out, uint64_t* deferred_out, unsigned* unchecked_out, pkv_result* result);
 
+// The sparse weights' entry points (include/provekit_whir_sparse.h says what they do), C++ functions of this library in the same way:
+// their C names pkw_sparse_sums, pkw_sparse_accumulate, pkw_sparse_evaluate, pkw_open_sparse and pkw_verify_sparse are exported by
+// libprovekit_whir_sparse.so (sparse_abi.cpp).  The first three are sparse.hip's, open_sparse is pcs.cpp's, verify_sparse verify_host.cpp's
+int sparse_sums(pk_ctx* ctx, const uint64_t* const* d_evals, unsigned batch, unsigned n_vars, const uint64_t* offsets, const uint32_t* d_index,
+                const uint64_t* d_value, unsigned l, uint64_t* out);
+int sparse_accumulate(pk_ctx* ctx, uint64_t* d_table, unsigned n_vars, const uint64_t* offsets, const uint32_t* d_index, const uint64_t* d_value, unsigned l,
+                      const uint64_t* scales);
+int sparse_evaluate(pk_ctx* ctx, unsigned n_vars, const uint64_t* offsets, const uint32_t* d_index, const uint64_t* d_value, unsigned l, const uint64_t* point,
+                    uint64_t* out);
+int open_sparse(pkw_scheme* s, const pkw_commitment* com, const uint64_t* points, unsigned q, const uint64_t* offsets, const uint32_t* d_index,
+                const uint64_t* d_value, const uint64_t* tags, unsigned l, uint64_t* evals_out, uint64_t* sums_out, uint8_t* proof_out, size_t cap, size_t* len);
+int verify_sparse(const pk_whir_config* cfg, const uint8_t* io_pattern, size_t io_pattern_len, int hash_version, const uint8_t* expected_root,
+                  const uint64_t* points, unsigned q, const uint64_t* tags, const uint64_t* offsets, const uint32_t* index, const uint64_t* value, unsigned l,
+                  const uint8_t* proof, size_t len, uint64_t* evals_out, uint64_t* sums_out, uint64_t* fold_point_out, uint64_t* deferred_out,
+                  pkv_result* result);
+
 // the counts of a linear statement, refused with a reason
 inline bool linear_counts_ok(unsigned q, unsigned l, std::string& why) {
     if (q > PKW_MAX_POINTS) {

@@ -3,8 +3,11 @@
 // statement around it: the points and evaluations on the transcript, and the deferred weight evaluations, which for the weights
 // eq(point_i, .) have the closed form eq(point_i, folding point).  A linear statement (pkw_verify_linear) adds tags, sums and dense
 // weight tables, whose deferred evaluations are their multilinear extensions at the folding point: 2^n_vars products per table the
-// caller hands over, the caller's own business for the others.
+// caller hands over, the caller's own business for the others.  Sparse weights (pkw_verify_sparse) are index/value lists: their
+// extensions at the folding point cost one product per 8 index bits and entry (sparse.hpp's chunked eq tables), so the verifier
+// always judges them itself.
 #include "pcs.hpp"
+#include "sparse.hpp"
 
 namespace pkw {
 
@@ -20,8 +23,9 @@ const char* const kWalkNames[PKV_CHECK_COUNT] = {
 class PcsWalk : public pkv::Walk {
   public:
     PcsWalk(const pkv::Statement& st, pkv::Backend& be, const uint8_t* proof, size_t len, pkv::Verdict& v, const pk_whir_config& cfg, const fe* points,
-            unsigned q, const fe* expected_root, const fe* tags = nullptr, const uint64_t* const* weights = nullptr, unsigned l = 0)
-        : Walk(st, be, proof, len, v), cfg_(cfg), points_(points), q_(q), expected_root_(expected_root), tags_(tags), weights_(weights), l_(l) {}
+            unsigned q, const fe* expected_root, const fe* tags = nullptr, const uint64_t* const* weights = nullptr, unsigned l = 0,
+            const SparseWeights* sparse = nullptr)
+        : Walk(st, be, proof, len, v), cfg_(cfg), points_(points), q_(q), expected_root_(expected_root), tags_(tags), weights_(weights), l_(l), sparse_(sparse) {}
 
     std::vector<fe> evals;  // [polynomial][point], Montgomery: what the proof binds, once the walk got past them
     std::vector<fe> sums;   // [polynomial][weight], likewise
@@ -66,9 +70,17 @@ class PcsWalk : public pkv::Walk {
             if (!relation(deferred[i].canonical && pk::fe_eq(deferred[i].mont, pkv::eq_poly(points_ + (size_t)i * n, rev.data(), n)), PKW_CHECK_DEFERRED,
                           "deferred evaluation of weight " + std::to_string(i) + " is not eq(point, folding point)"))
                 return false;
-        for (unsigned i = 0; i < l_; i++) {  // the MLE of a dense table at the folding point, where the caller gave the table
+        const SparseEqTables eq(rev.data(), sparse_ ? n : 0);  // sparse weights: the chunks' eq tables at the folding point, once for all l
+        for (unsigned i = 0; i < l_; i++) {  // the MLE of a weight at the folding point: of the entries, or of a dense table the caller gave
             const pk::HintFe& d = deferred[q_ + i];
             if (!relation(d.canonical, PKW_CHECK_DEFERRED, "deferred evaluation of weight " + std::to_string(i) + " is not canonical")) return false;
+            if (sparse_) {
+                const size_t at = sparse_->begin(i);
+                if (!relation(pk::fe_eq(d.mont, eq.weight_at(sparse_->index + at, sparse_->value + 4 * at, sparse_->nnz(i))), PKW_CHECK_DEFERRED,
+                              "deferred evaluation of weight " + std::to_string(i) + " is not the extension of the caller's entries at the folding point"))
+                    return false;
+                continue;
+            }
             if (!weights_ || !weights_[i]) {
                 unchecked++;
                 continue;
@@ -89,6 +101,7 @@ class PcsWalk : public pkv::Walk {
     const fe* tags_;
     const uint64_t* const* weights_;
     unsigned l_;
+    const SparseWeights* sparse_;
 
     // the multilinear extension of a dense table (2^n Montgomery elements, any 256-bit values) at `point`, variable 0 <-> the most
     // significant index bit: the first fold reads the caller's table, the rest work on the half-size copy
@@ -109,10 +122,11 @@ class PcsWalk : public pkv::Walk {
     }
 };
 
-// what pkw_verify and pkw_verify_linear share once their counts are checked; l = 0: pkw_verify
+// what pkw_verify, pkw_verify_linear and pkw_verify_sparse share once their counts are checked; l = 0: pkw_verify
 int verify_checked(const pk_whir_config* cfg, const uint8_t* io_pattern, size_t io_pattern_len, int hash_version, const uint8_t* expected_root,
                    const uint64_t* points, unsigned q, const uint64_t* tags, const uint64_t* const* weights, unsigned l, const uint8_t* proof, size_t len,
-                   uint64_t* evals_out, uint64_t* sums_out, uint64_t* fold_point_out, uint64_t* deferred_out, unsigned* unchecked_out, pkv_result* result) {
+                   uint64_t* evals_out, uint64_t* sums_out, uint64_t* fold_point_out, uint64_t* deferred_out, unsigned* unchecked_out, pkv_result* result,
+                   const SparseWeights* sparse = nullptr) {
     std::string why;
     if (hash_version != 1 && hash_version != 2) return refuse("hash version must be 1 or 2");
     try {
@@ -133,7 +147,7 @@ int verify_checked(const pk_whir_config* cfg, const uint8_t* io_pattern, size_t 
         pkv::Verdict verdict;
         pkv::HostBackend be;
         PcsWalk walk(st, be, len ? proof : &none, len, verdict, *cfg, reinterpret_cast<const pk::fe*>(points), q, expected_root ? &root : nullptr,
-                     reinterpret_cast<const pk::fe*>(tags), weights, l);
+                     reinterpret_cast<const pk::fe*>(tags), weights, l, sparse);
         walk.run_opening();
         pkv::to_result(verdict, result);
         auto give = [](uint64_t* out, const std::vector<fe>& v) {
@@ -228,6 +242,29 @@ int verify_linear(const pk_whir_config* cfg, const uint8_t* io_pattern, size_t i
     if (!result || (q && !points) || !tags || (len && !proof)) return refuse("null pointer");
     return verify_checked(cfg, io_pattern, io_pattern_len, hash_version, expected_root, points, q, tags, weights, l, proof, len, evals_out, sums_out,
                           fold_point_out, deferred_out, unchecked_out, result);
+}
+
+// the entry point behind pkw_verify_sparse (sparse_abi.cpp): pkw_verify_linear's walk over lists the host checks first, entry by entry
+int verify_sparse(const pk_whir_config* cfg, const uint8_t* io_pattern, size_t io_pattern_len, int hash_version, const uint8_t* expected_root,
+                  const uint64_t* points, unsigned q, const uint64_t* tags, const uint64_t* offsets, const uint32_t* index, const uint64_t* value, unsigned l,
+                  const uint8_t* proof, size_t len, uint64_t* evals_out, uint64_t* sums_out, uint64_t* fold_point_out, uint64_t* deferred_out,
+                  pkv_result* result) {
+    std::string why;
+    if (!config_ok(cfg, why) || !linear_counts_ok(q, l, why)) return refuse(why);
+    if (!result || (q && !points) || !tags || !offsets || (len && !proof)) return refuse("null pointer");
+    const unsigned n = cfg->n_vars;
+    if (!sparse_offsets_ok(offsets, l, n, why)) return refuse(why);
+    if (offsets[l] && (!index || !value)) return refuse("null index or value list");
+    const SparseWeights w{offsets, index, value, l};
+    for (unsigned i = 0; i < l; i++)
+        for (size_t k = w.begin(i); k < w.begin(i + 1); k++) {
+            const bool first = k == w.begin(i);
+            if (((uint64_t)index[k] >> n) != 0 || (!first && index[k - 1] >= index[k])) return refuse(sparse_index_reason(w, k, index[k], first ? 0 : index[k - 1], n));
+            if (!below_p(pk::h_load(value + 4 * k)))
+                return refuse("weight " + std::to_string(i) + ", entry " + std::to_string(k - w.begin(i)) + ": the value is not below p");
+        }
+    return verify_checked(cfg, io_pattern, io_pattern_len, hash_version, expected_root, points, q, tags, nullptr, l, proof, len, evals_out, sums_out,
+                          fold_point_out, deferred_out, nullptr, result, &w);
 }
 
 }  // namespace pkw

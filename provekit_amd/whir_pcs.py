@@ -1,6 +1,7 @@
 """WHIR as a polynomial commitment scheme (libprovekit_whir.so, include/provekit_whir.h): commit to up to 4 multilinear
 polynomials, open them at points of the caller's choice -- or at LINEAR statements <w, f> = s over dense weight tables
-(open_linear / verify_linear; the caller's tags bind the weights) -- and verify the opening.  PLAIN WHIR, not hiding.
+(open_linear / verify_linear; the caller's tags bind the weights), or over the same weights as sparse index/value lists
+(open_sparse / verify_sparse; SparseWeights) -- and verify the opening.  PLAIN WHIR, not hiding.
 
 A fourth library above the product's C ABI, with its own loader and signature table (as provekit_amd.verify).  `verify` and
 `io_pattern` are host only; `Scheme` needs a Context.  A rejected proof is a Result, not an exception; only a failed CALL raises.
@@ -53,6 +54,16 @@ LINEAR_SIGNATURES = {
                                     C.POINTER(ResultStruct)]),
 }
 
+# sparse weights (index/value lists) for the same statements: a second companion library (include/provekit_whir_sparse.h)
+SPARSE_LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libprovekit_whir_sparse.so")
+SPARSE_SIGNATURES = {
+    "pkw_sparse_sums": (C.c_int, [vp, vp, C.c_uint, C.c_uint, vp, vp, vp, C.c_uint, vp]),
+    "pkw_sparse_accumulate": (C.c_int, [vp, vp, C.c_uint, vp, vp, vp, C.c_uint, vp]),
+    "pkw_sparse_evaluate": (C.c_int, [vp, C.c_uint, vp, vp, vp, C.c_uint, vp, vp]),
+    "pkw_open_sparse": (C.c_int, [vp, vp, vp, C.c_uint, vp, vp, vp, vp, C.c_uint, vp, vp, vp, sz, C.POINTER(sz)]),
+    "pkw_verify_sparse": (C.c_int, [vp, vp, sz, C.c_int, vp, vp, C.c_uint, vp, vp, vp, vp, C.c_uint, vp, sz, vp, vp, vp, vp, C.POINTER(ResultStruct)]),
+}
+
 
 def _load():
     if not os.path.exists(WHIR_LIB_PATH):
@@ -67,7 +78,10 @@ lib = _load()
 if not os.path.exists(LINEAR_LIB_PATH):
     raise ImportError(f"{LINEAR_LIB_PATH} is missing: build it with `make -C provekit_amd/csrc`. provekit_amd has no CPU fallback.")
 linear_lib = C.CDLL(LINEAR_LIB_PATH)
-for _lib, _table in ((lib, SIGNATURES), (linear_lib, LINEAR_SIGNATURES)):
+if not os.path.exists(SPARSE_LIB_PATH):
+    raise ImportError(f"{SPARSE_LIB_PATH} is missing: build it with `make -C provekit_amd/csrc`. provekit_amd has no CPU fallback.")
+sparse_lib = C.CDLL(SPARSE_LIB_PATH)
+for _lib, _table in ((lib, SIGNATURES), (linear_lib, LINEAR_SIGNATURES), (sparse_lib, SPARSE_SIGNATURES)):
     for _name, (_res, _args) in _table.items():
         _fn = getattr(_lib, _name)  # AttributeError here == header/library mismatch: fail loudly
         _fn.restype = _res
@@ -203,6 +217,105 @@ def verify_linear(cfg: WhirConfig, points, tags, weights, proof: bytes, expected
     return LinearResult(_result(r), evals, sums, fold, deferred[:l], unchecked.value)
 
 
+class SparseWeights:
+    """l weights as index/value lists (include/provekit_whir_sparse.h): offsets [l + 1] uint64, index [nnz] uint32 -- strictly
+    increasing within a weight, each < 2^n_vars -- and value [nnz, 4] Montgomery limbs.  Built from one (indexes, values) pair per
+    weight; nothing is checked here, the library refuses what breaks the rules.  `upload` puts index and value on the device"""
+
+    def __init__(self, weights=(), offsets=None, index=None, value=None):
+        if offsets is None:
+            offsets = np.cumsum([0] + [len(i) for i, _ in weights], dtype=np.uint64)
+            index = np.concatenate([np.asarray(i, dtype=np.uint32).reshape(-1) for i, _ in weights] + [np.zeros(0, dtype=np.uint32)])
+            value = np.concatenate([np.asarray(v, dtype=np.uint64).reshape(-1, 4) for _, v in weights] + [np.zeros((0, 4), dtype=np.uint64)])
+        self.offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        self.index = np.ascontiguousarray(index, dtype=np.uint32)
+        self.value = np.ascontiguousarray(value, dtype=np.uint64).reshape(-1, 4)
+        self.l = len(self.offsets) - 1
+        self.d_index = self.d_value = None
+
+    def upload(self, ctx: Context) -> "SparseWeights":
+        self.free()
+        if len(self.index):
+            self.d_index, self.d_value = ctx.upload(self.index), ctx.upload(self.value)
+        return self
+
+    def free(self):
+        for b in (self.d_index, self.d_value):
+            if b is not None:
+                b.free()
+        self.d_index = self.d_value = None
+
+    def _device(self):
+        """(offsets, index, value) pointers for a device entry point"""
+        if len(self.index) and self.d_index is None:
+            raise ValueError("upload the lists first")
+        return self.offsets.ctypes.data, self.d_index.ptr if self.d_index else None, self.d_value.ptr if self.d_value else None
+
+    def _host(self):
+        return self.offsets.ctypes.data, self.index.ctypes.data if len(self.index) else None, self.value.ctypes.data if len(self.value) else None
+
+
+def _sparse_check(ctx: Context, rc: int):
+    """a refusal of the three pk_ctx entry points carries its reason in pkw_create_error; any other failure is the context's"""
+    if rc == -1:
+        raise ProveKitHipError(rc, lib.pkw_create_error().decode())
+    ctx._check(rc)
+
+
+def sparse_sums(ctx: Context, d_evals, n_vars: int, weights: SparseWeights) -> np.ndarray:
+    """[batch, l, 4] Montgomery: sum_k value_i[k] * f_b[index_i[k]], weighted_sums on the densified tables from nnz gathers (pkw_sparse_sums)"""
+    out = np.zeros((len(d_evals), max(weights.l, 1), 4), dtype=np.uint64)
+    _sparse_check(ctx, sparse_lib.pkw_sparse_sums(ctx.handle, C.cast(_ptr_array(d_evals), vp), len(d_evals), n_vars, *weights._device(), weights.l,
+                                                  out.ctypes.data))
+    return out[:, : weights.l]
+
+
+def sparse_accumulate(ctx: Context, d_table, n_vars: int, weights: SparseWeights, scales) -> None:
+    """d_table[index_i[k]] += scales[i] * value_i[k] in place; scales [l, 4] Montgomery on the host (pkw_sparse_accumulate)"""
+    s = np.ascontiguousarray(scales, dtype=np.uint64).reshape(-1, 4)
+    if s.shape[0] != weights.l:
+        raise ValueError("as many scales as weights")
+    _sparse_check(ctx, sparse_lib.pkw_sparse_accumulate(ctx.handle, d_table.ptr if isinstance(d_table, DeviceBuffer) else int(d_table), n_vars,
+                                                        *weights._device(), weights.l, s.ctypes.data if weights.l else None))
+
+
+def sparse_evaluate(ctx: Context, n_vars: int, weights: SparseWeights, point) -> np.ndarray:
+    """[l, 4] Montgomery: the multilinear extension of every weight at `point` [n_vars, 4], no dense table anywhere (pkw_sparse_evaluate)"""
+    p = np.ascontiguousarray(point, dtype=np.uint64).reshape(-1, 4)
+    if p.shape[0] != n_vars:
+        raise ValueError(f"a point has {n_vars} coordinates")
+    out = np.zeros((max(weights.l, 1), 4), dtype=np.uint64)
+    _sparse_check(ctx, sparse_lib.pkw_sparse_evaluate(ctx.handle, n_vars, *weights._device(), weights.l, p.ctypes.data if n_vars else None, out.ctypes.data))
+    return out[: weights.l]
+
+
+def verify_sparse(cfg: WhirConfig, points, tags, weights: SparseWeights, proof: bytes, expected_root: bytes | None = None,
+                  io_pattern: bytes | None = None, hash_version: int = 2) -> LinearResult:
+    """Host only (pkw_verify_sparse): every weight's deferred relation is judged from its entries, so `unchecked` is always 0"""
+    c = _cfg_struct(cfg)
+    p = _points_or_none(points, cfg.n_vars)
+    t = _tags(tags)
+    q, l = p.shape[0], t.shape[0]
+    if weights.l != l:
+        raise ValueError("as many weights as tags")
+    proof = bytes(proof)
+    evals = np.zeros((cfg.batch_size, q, 4), dtype=np.uint64)
+    sums = np.zeros((cfg.batch_size, l, 4), dtype=np.uint64)
+    fold = np.zeros((cfg.n_vars, 4), dtype=np.uint64)
+    deferred = np.zeros((max(l, 1), 4), dtype=np.uint64)
+    r = ResultStruct()
+    pat = bytes(io_pattern) if io_pattern else None
+    root = bytes(expected_root) if expected_root is not None else None
+    if root is not None and len(root) != 32:
+        raise ValueError("a root is 32 bytes")
+    rc = sparse_lib.pkw_verify_sparse(C.addressof(c), pat, len(pat) if pat else 0, hash_version, root, p.ctypes.data if q else None, q, t.ctypes.data,
+                                      *weights._host(), l, proof, len(proof), evals.ctypes.data if q else None, sums.ctypes.data, fold.ctypes.data,
+                                      deferred.ctypes.data, C.byref(r))
+    if rc:
+        raise ProveKitHipError(rc, lib.pkw_create_error().decode())
+    return LinearResult(_result(r), evals, sums, fold, deferred[:l], 0)
+
+
 def verify(cfg: WhirConfig, points, proof: bytes, expected_root: bytes | None = None, io_pattern: bytes | None = None, hash_version: int = 2):
     """-> (Result, evaluations [batch, q, 4] Montgomery as the proof binds them).  Host only (pkw_verify)."""
     c = _cfg_struct(cfg)
@@ -305,6 +418,27 @@ class Scheme:
         self._check(linear_lib.pkw_open_linear(self.handle, commitment.handle, p.ctypes.data if q else None, q, C.cast(_ptr_array(d_weights), vp) if l else None,
                                         t.ctypes.data, l, evals.ctypes.data if q else None, sums.ctypes.data, buf, len(buf) if cap is None else cap,
                                         C.byref(n)))
+        return evals, sums[:l], C.string_at(buf, n.value)
+
+    def open_sparse(self, commitment: Commitment, points, weights: SparseWeights, tags, cap: int | None = None):
+        """open_linear with the l weights as uploaded index/value lists: the same statement, the same bytes (pkw_open_sparse)
+        -> (evaluations [batch, q, 4], sums [batch, l, 4], proof bytes)"""
+        p = _points_or_none(points, self.cfg.n_vars)
+        t = _tags(tags)
+        q, l = p.shape[0], t.shape[0]
+        if weights.l != l:
+            raise ValueError("as many weights as tags")
+        evals = np.zeros((self.cfg.batch_size, q, 4), dtype=np.uint64)
+        sums = np.zeros((self.cfg.batch_size, max(l, 1), 4), dtype=np.uint64)
+        if cap is None:
+            if self._buf is None:
+                self._buf = (C.c_uint8 * (8 << 20))()
+            buf = self._buf
+        else:
+            buf = (C.c_uint8 * max(cap, 1))()
+        n = sz()
+        self._check(sparse_lib.pkw_open_sparse(self.handle, commitment.handle, p.ctypes.data if q else None, q, *weights._device(), t.ctypes.data, l,
+                                               evals.ctypes.data if q else None, sums.ctypes.data, buf, len(buf) if cap is None else cap, C.byref(n)))
         return evals, sums[:l], C.string_at(buf, n.value)
 
     def close(self):

@@ -43,6 +43,13 @@ SIGNATURES = {
     "pk_probe_whir_weighted_sums": (C.c_int, [vp, vp, C.c_uint, C.c_uint, vp, C.c_uint, C.c_uint, C.c_int, vp]),
     "pk_probe_whir_wsum_grid": (C.c_uint, [C.c_uint]),
     "pk_probe_wsum_tile_host": (C.c_int, [vp, vp, C.c_uint, vp]),
+    # ... and its sparse-weight code (tools/probes/whir_sparse.hip)
+    "pk_probe_whir_sparse_threads": (C.c_uint, []),
+    "pk_probe_whir_sparse_chunk_bits": (C.c_uint, []),
+    "pk_probe_whir_sparse_grid": (C.c_uint, [C.c_uint, sz, C.c_uint]),
+    "pk_probe_whir_sparse_sums": (C.c_int, [vp, vp, C.c_uint, C.c_uint, vp, vp, vp, C.c_uint, C.c_uint, vp]),
+    "pk_probe_sparse_tile_host": (C.c_int, [vp, vp, C.c_uint, vp]),
+    "pk_probe_sparse_eq_host": (C.c_int, [C.c_uint, vp, vp, vp, sz, vp]),
 }
 for _name, (_res, _args) in SIGNATURES.items():
     _fn = getattr(lib, _name)

@@ -87,6 +87,20 @@ int pk_probe_whir_weighted_sums(pk_ctx *ctx, const uint64_t *const *d_evals, uns
 unsigned pk_probe_whir_wsum_grid(unsigned n_vars);
 int pk_probe_wsum_tile_host(const uint64_t *f, const uint64_t *w, unsigned terms, uint64_t *out);
 
+/* ... and its sparse-weight code (csrc/whir_pcs/sparse.hip, sparse.hpp; whir_sparse.hip here), for tests/test_gpu_whir_pcs_sparse.py,
+ * tests/test_whir_pcs_sparse_host.py and tools/whir_pcs_sparse_bench.py.  pk_probe_whir_sparse_sums: pkw_sparse_sums on a grid of
+ * `grid` workgroups per weight (0 or 1..pk_probe_whir_wsum_grid(n_vars)).  pk_probe_whir_sparse_grid: the grid the library takes for
+ * weights of at most nnz entries at `steps` steps per workgroup (1: the sums, 8: the evaluation).  pk_probe_sparse_tile_host: the
+ * sums kernel's lanes on the HOST (two slices of two polynomials, as on the device), f = 4 x terms gathered elements, w = terms values, out = 4 elements.  pk_probe_sparse_eq_host:
+ * sum_k value[k] * eq(index[k], point) by the host verifier's chunked eq tables. */
+unsigned pk_probe_whir_sparse_threads(void);
+unsigned pk_probe_whir_sparse_chunk_bits(void);
+unsigned pk_probe_whir_sparse_grid(unsigned n_vars, size_t nnz, unsigned steps);
+int pk_probe_whir_sparse_sums(pk_ctx *ctx, const uint64_t *const *d_evals, unsigned batch, unsigned n_vars, const uint64_t *offsets,
+                              const uint32_t *d_index, const uint64_t *d_value, unsigned l, unsigned grid, uint64_t *out);
+int pk_probe_sparse_tile_host(const uint64_t *f, const uint64_t *w, unsigned terms, uint64_t *out);
+int pk_probe_sparse_eq_host(unsigned n_vars, const uint64_t *point, const uint32_t *index, const uint64_t *value, size_t nnz, uint64_t *out);
+
 #ifdef __cplusplus
 }
 #endif
