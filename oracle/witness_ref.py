@@ -121,7 +121,9 @@ def solve_witness_vec(builders, acir, challenges, num_witnesses):
             _, start, operands = b
             mult = [0] * (1 << (2 * BINOP_ATOMIC_BITS))
             for lhs, rhs in operands:
-                i = ((cow(lhs) & (2**64 - 1)) << BINOP_ATOMIC_BITS) + (cow(rhs) & (2**64 - 1))
+                # witness_builder.rs:184: `(lhs.0[0] << BINOP_ATOMIC_BITS) + rhs.0[0]` on u64 -- the shift drops lhs's high bits
+                # silently (the add would only overflow where debug and release Rust differ: not restated)
+                i = (((cow(lhs) & (2**64 - 1)) << BINOP_ATOMIC_BITS) & (2**64 - 1)) + (cow(rhs) & (2**64 - 1))
                 if i >= len(mult):
                     raise SolverPanic("index out of bounds")
                 mult[i] += 1

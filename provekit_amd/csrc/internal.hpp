@@ -123,6 +123,10 @@ int random_fe(pk_ctx* ctx, uint64_t* d_out, size_t n, const RngKey& key, uint32_
 
 // ---- witness.hip --------------------------------------------------------------------------------------------------------------
 void witness_program_shape(const pk_witness_program* p, size_t* n_witnesses, size_t* n_challenges, size_t* n_acir);
+// host only, for the lab: decode and level a postcard list; items per phase, items per phase and variant (wb::N_OPS per phase,
+// witness_shape.hpp), the Spice blocks and long sums that run right before each phase
+int witness_phase_shape(const uint8_t* bytes, size_t len, std::vector<uint32_t>& widths, std::vector<uint32_t>& op_counts, std::vector<uint32_t>& blocks_before,
+                        std::string& error);
 
 // ---- whir_config.hip: the scheme's shape (host only) --------------------------------------------------------------------------
 const char* whir_config_error(const pk_whir_config* c);  // nullptr if this prover runs `c`, else why not

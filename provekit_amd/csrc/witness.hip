@@ -23,6 +23,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
+#include <iterator>
 #include <string>
 #include <vector>
 
@@ -32,8 +33,10 @@
 #include "fe29.hpp"
 #include "feinv.hpp"
 #include "reduce.hpp"
+#include "witness_shape.hpp"
 
 using namespace pk;
+using namespace pk::wb;  // NARROW, SUM_HEAVY, SUM_CHUNK, N_OPS
 
 namespace {
 
@@ -41,6 +44,7 @@ enum : u32 {
     OP_CONST = 0, OP_ACIR, OP_SUM, OP_PRODUCT, OP_CHALLENGE, OP_IDX_LOGUP, OP_INVERSE, OP_PROD_LINEAR, OP_LOGUP, OP_SPICE_FACTOR,
     OP_BINOP_DENOM, OP_DIGIT, OP_DIGIT_CHECK, OP_HIST_RANGE, OP_HIST_BINOP, OP_COUNT_OUT
 };
+static_assert(OP_COUNT_OUT + 1 == N_OPS, "witness_shape.hpp counts the variants");
 constexpr u32 NONE = 0xffffffffu;
 constexpr u32 COW_CONST = 0x80000000u;  // ConstantOrR1CSWitness packed in one word: constant-table index | COW_CONST, or a witness index
 
@@ -193,7 +197,6 @@ __global__ __launch_bounds__(256) void wb_phase_kernel(const WbItem* __restrict_
     if (i < n) wb_eval(items[i], W, is_set, K, acir, challenges, extra, counts, err);
 }
 // a run of consecutive narrow phases in one launch: a single workgroup walks them, a barrier between phases
-constexpr u32 NARROW = 1024;
 __global__ __launch_bounds__(NARROW) void wb_narrow_run_kernel(const WbItem* __restrict__ items, const u32* __restrict__ phase_begin, u32 first_phase,
                                                                u32 n_phases, fe* W, unsigned char* is_set, const fe* K, const fe* acir,
                                                                const fe* challenges, const u32* extra, u32* counts, unsigned long long* err) {
@@ -259,8 +262,7 @@ __global__ __launch_bounds__(256) void spice_resolve_kernel(const SpiceOp* __res
 // ---- long sums (witness_builder.rs:45-60 with thousands of terms: a LogUp grand sum has one per lookup) --------------------------
 // A lane that walks 10^5 terms holds its level for 10^5 dependent products.  Sums longer than SUM_HEAVY terms leave the item list:
 // a workgroup per SUM_CHUNK terms forms a partial sum, a workgroup per sum adds the partials.  Exact field additions: the order
-// does not show in the result.
-constexpr u32 SUM_HEAVY = 128, SUM_CHUNK = 1024;
+// does not show in the result.  (SUM_HEAVY, SUM_CHUNK: witness_shape.hpp)
 struct SumChunk {
     u32 begin, end;  // term numbers (pairs of P.extra)
 };
@@ -337,6 +339,7 @@ struct Parsed {  // a builder before levelling
     std::vector<u32> copies;  // witnesses copied as Options, not unwrapped (Spice values): None is legal and stays None
     std::vector<WbItem> main, second;  // second = the phase after main (COUNT_OUT)
     int spice = -1, heavy_sum = -1;
+    bool lanes_share_witnesses = false;  // many lanes, reads and writes in ONE phase: Spice blocks, digital decompositions
 };
 
 u32 add_const(Program& P, const fe& canon) {
@@ -526,6 +529,7 @@ bool parse_builder(Reader& rd, Program& P, u32 bi, Parsed& b) {
                 if (lb > 256 || total + lb > 256) return rd.ok = false;  // field_to_le_bits yields 256 bits: a longer slice panics
                 total += lb;
             }
+            b.lanes_share_witnesses = true;
             for (size_t i = 0; i < values.size(); i++) {
                 b.reads.push_back(values[i]);
                 u32 start = 0;
@@ -601,6 +605,7 @@ bool parse_builder(Reader& rd, Program& P, u32 bi, Parsed& b) {
                 b.writes.push_back(sb.rv_start + a);
                 b.writes.push_back(sb.rt_start + a);
             }
+            b.lanes_share_witnesses = true;
             b.spice = (int)P.spice.size();
             P.spice.push_back(std::move(sb));
             break;
@@ -668,6 +673,20 @@ bool build_program(const uint8_t* bytes, size_t len, Program& P, size_t* consume
     u32 max_level = 0;
     for (size_t i = 0; i < B.size(); i++) {
         u32 lv = 0;
+        if (B[i].lanes_share_witnesses) {
+            // The reference replays a Spice block's operations (ram.rs:13-47) and a decomposition's values (digits.rs:17-29) in
+            // order, so an operation may read what an earlier one of the SAME builder wrote.  Here the lanes of such a builder read
+            // and write in one phase: a witness it both reads (or copies) and writes would be a race.  No compiled list has that
+            // shape: refused.  (A single-item builder reads before it writes, a multiplicity table writes one phase after it reads.)
+            std::vector<u32> ws(B[i].writes), rs(B[i].reads);
+            rs.insert(rs.end(), B[i].copies.begin(), B[i].copies.end());
+            std::sort(ws.begin(), ws.end());
+            std::sort(rs.begin(), rs.end());
+            std::vector<u32> both;
+            std::set_intersection(rs.begin(), rs.end(), ws.begin(), ws.end(), std::back_inserter(both));
+            if (!both.empty())
+                return P.error = "builder " + std::to_string(i) + " reads witness " + std::to_string(both[0]) + " that it also writes", false;
+        }
         for (u32 w : B[i].reads) {
             if (producer[w] < 0) return P.error = "builder " + std::to_string(i) + " reads witness " + std::to_string(w) + " before it is solved", false;
             lv = std::max(lv, level[(size_t)producer[w]] + 1);
@@ -735,6 +754,25 @@ bool build_program(const uint8_t* bytes, size_t len, Program& P, size_t* consume
     return true;
 }
 
+// the levelled program's shape for the lab (tools/probes): items per phase, items per phase and variant, and how many Spice blocks
+// and long sums run right before each phase
+bool program_phase_shape(const Program& P, std::vector<u32>& widths, std::vector<u32>& op_counts, std::vector<u32>& blocks_before) {
+    const size_t n_phases = P.phase_begin.size() - 1;
+    widths.assign(n_phases, 0);
+    op_counts.assign(n_phases * N_OPS, 0);
+    blocks_before.assign(n_phases, 0);
+    for (size_t ph = 0; ph < n_phases; ph++) {
+        widths[ph] = P.phase_begin[ph + 1] - P.phase_begin[ph];
+        for (u32 k = P.phase_begin[ph]; k < P.phase_begin[ph + 1]; k++) {
+            if (P.items[k].op >= N_OPS) return false;
+            op_counts[ph * N_OPS + P.items[k].op]++;
+        }
+    }
+    for (auto& sb : P.spice) blocks_before[2 * (size_t)sb.level + 1]++;
+    for (auto& hs : P.heavy_sums) blocks_before[2 * (size_t)hs.level + 1]++;
+    return true;
+}
+
 }  // namespace
 
 struct pk_witness_program {
@@ -759,6 +797,17 @@ void witness_program_shape(const pk_witness_program* p, size_t* n_witnesses, siz
     *n_witnesses = p->P.n_witnesses;
     *n_challenges = p->P.n_challenges;
     *n_acir = p->P.n_acir;
+}
+int witness_phase_shape(const uint8_t* bytes, size_t len, std::vector<uint32_t>& widths, std::vector<uint32_t>& op_counts, std::vector<uint32_t>& blocks_before,
+                        std::string& error) {
+    if (!bytes) return PK_ERR_BAD_ARG;
+    try {
+        Program P;
+        if (!build_program(bytes, len, P, nullptr)) return error = P.error, PK_ERR_BAD_ARG;
+        return program_phase_shape(P, widths, op_counts, blocks_before) ? PK_OK : PK_ERR_BAD_ARG;
+    } catch (const std::bad_alloc&) {
+        return PK_ERR_OOM;
+    }
 }
 }  // namespace pk
 

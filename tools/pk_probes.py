@@ -50,7 +50,36 @@ SIGNATURES = {
     "pk_probe_whir_sparse_sums": (C.c_int, [vp, vp, C.c_uint, C.c_uint, vp, vp, vp, C.c_uint, C.c_uint, vp]),
     "pk_probe_sparse_tile_host": (C.c_int, [vp, vp, C.c_uint, vp]),
     "pk_probe_sparse_eq_host": (C.c_int, [C.c_uint, vp, vp, vp, sz, vp]),
+    # csrc/witness.hip's thresholds and the shape of a levelled builder list (tools/probes/witness.hip): host only
+    "pk_probe_witness_narrow": (C.c_uint, []),
+    "pk_probe_witness_sum_heavy": (C.c_uint, []),
+    "pk_probe_witness_sum_chunk": (C.c_uint, []),
+    "pk_probe_witness_n_ops": (C.c_uint, []),
+    "pk_probe_witness_phases": (C.c_int, [C.c_char_p, sz, vp, vp, vp, sz, C.POINTER(C.c_size_t), C.c_char_p, sz]),
 }
 for _name, (_res, _args) in SIGNATURES.items():
     _fn = getattr(lib, _name)
     _fn.restype, _fn.argtypes = _res, _args
+
+
+def witness_thresholds() -> dict:
+    """csrc/witness_shape.hpp: the phase width up to which phases share a one-workgroup launch, the Sum length above which a sum is
+    summed by workgroups, and the terms per workgroup of such a sum"""
+    return {"NARROW": lib.pk_probe_witness_narrow(), "SUM_HEAVY": lib.pk_probe_witness_sum_heavy(), "SUM_CHUNK": lib.pk_probe_witness_sum_chunk()}
+
+
+def witness_phases(data: bytes) -> dict:
+    """postcard(Vec<WitnessBuilder>) after levelling (two phases per level): `widths[ph]` items per phase, `ops[ph]` items per phase
+    and variant (csrc/witness.hip's OP_* order), `blocks_before[ph]` Spice blocks and long sums that run right before the phase.
+    Raises ValueError with the library's reason for a list it refuses."""
+    n, err = C.c_size_t(), C.create_string_buffer(512)
+    rc = lib.pk_probe_witness_phases(data, len(data), None, None, None, 0, C.byref(n), err, 512)
+    if rc:
+        raise ValueError(err.value.decode() or f"pk_probe_witness_phases: {rc}")
+    n_ops, cap = lib.pk_probe_witness_n_ops(), max(n.value, 1)
+    w, ops, blocks = (C.c_uint32 * cap)(), (C.c_uint32 * (cap * n_ops))(), (C.c_uint32 * cap)()
+    rc = lib.pk_probe_witness_phases(data, len(data), w, ops, blocks, cap, C.byref(n), err, 512)
+    if rc:
+        raise ValueError(err.value.decode() or f"pk_probe_witness_phases: {rc}")
+    return {"widths": list(w[: n.value]), "ops": [list(ops[ph * n_ops : (ph + 1) * n_ops]) for ph in range(n.value)],
+            "blocks_before": list(blocks[: n.value])}

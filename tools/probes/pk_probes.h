@@ -101,6 +101,18 @@ int pk_probe_whir_sparse_sums(pk_ctx *ctx, const uint64_t *const *d_evals, unsig
 int pk_probe_sparse_tile_host(const uint64_t *f, const uint64_t *w, unsigned terms, uint64_t *out);
 int pk_probe_sparse_eq_host(unsigned n_vars, const uint64_t *point, const uint32_t *index, const uint64_t *value, size_t nnz, uint64_t *out);
 
+/* csrc/witness.hip's thresholds (csrc/witness_shape.hpp) and the shape of a levelled builder list (witness.hip here), for
+ * tests/test_witness_edge_cases_host.py and tests/test_gpu_witness_edges.py.  Host only.  pk_probe_witness_phases: *n_phases = the
+ * phases of postcard(Vec<WitnessBuilder>) after levelling (two per level); with cap >= *n_phases, widths[ph] = the items of phase
+ * ph, op_counts[ph * pk_probe_witness_n_ops() + op] = its items of variant op, blocks_before[ph] = the Spice blocks and long sums
+ * that run right before it (each of the three may be null).  A list the library refuses: PK_ERR_BAD_ARG, the reason in err. */
+unsigned pk_probe_witness_narrow(void);
+unsigned pk_probe_witness_sum_heavy(void);
+unsigned pk_probe_witness_sum_chunk(void);
+unsigned pk_probe_witness_n_ops(void);
+int pk_probe_witness_phases(const uint8_t *bytes, size_t len, uint32_t *widths, uint32_t *op_counts, uint32_t *blocks_before, size_t cap,
+                            size_t *n_phases, char *err, size_t err_cap);
+
 #ifdef __cplusplus
 }
 #endif
