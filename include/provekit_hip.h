@@ -297,7 +297,11 @@ int pk_fe_axpy(pk_ctx *ctx, uint64_t *d_y, const uint64_t *beta, const uint64_t 
  * indices into the Interner's table of distinct field elements (interner.rs).  mats = {A, B, C}.
  * A pk_r1cs is immutable once created: every context of its device may use it (one upload serves all the prover threads of a
  * GPU); destroy it after the schemes that were bound to it.  Rows and columns longer than 64 entries -- the constant-one
- * witness' column, a grand sum's row -- are summed by workgroups instead of one lane; nothing for the caller to do. */
+ * witness' column, a grand sum's row -- are summed by workgroups instead of one lane; nothing for the caller to do.
+ * Values: the n_interned interned elements, and the vectors the products below take (z, x, eq_alpha), are Montgomery images BELOW
+ * THE MODULUS (4 x u64 little-endian each).  pk_r1cs_create checks the interner and refuses an element >= p with PK_ERR_BAD_ARG
+ * (pk_last_error names its index); the vectors live on the device and are not checked -- they come from this library's own
+ * kernels, which deliver reduced values, or from a caller who reduced them. */
 typedef struct pk_sparse_matrix {
     const uint32_t *new_row_indices;
     const uint32_t *col_indices;

@@ -21,11 +21,12 @@
 #include "postcard.hpp"
 #include "fe29.hpp"
 #include "reduce.hpp"
+#include "r1cs_shape.hpp"
 
 using namespace pk;
+using r1cs_shape::HEAVY_CHUNK;   // entries per workgroup
+using r1cs_shape::HEAVY_DEGREE;  // longer lines are summed by workgroups
 
-constexpr uint32_t HEAVY_DEGREE = 64;    // longer lines are summed by workgroups
-constexpr uint32_t HEAVY_CHUNK = 2048;   // entries per workgroup
 struct heavy_chunk {
     uint32_t slot, begin, end;  // entries [begin, end) of the line set's arrays belong to heavy line number `slot` (R1CS-wide numbering)
 };
@@ -194,6 +195,7 @@ int witness_bounds_strided(pk_ctx* ctx, const pk_r1cs* r, const uint64_t* d_z, u
     PK_REQUIRE(ctx, r && d_z && d_a && d_b && d_c, "null pointer");
     PK_REQUIRE(ctx, m0 <= 30 && r->num_constraints <= ((size_t)1 << m0) && stride && offset < stride, "bad shard of the witness bounds");
     const size_t padded = ((size_t)1 << m0) / stride;
+    if (!padded) return PK_OK;  // more ranks than rows: this rank's share is empty (and a grid of no workgroups is not a launch)
     ProfScope prof(ctx, "witness_bounds");
     const fe* hv = nullptr;  // heavy rows are summed whole on every rank of a sharded sumcheck (they are few)
     int rc = heavy_prepare(ctx, r, 3u, (const fe*)d_z, &hv);
@@ -247,6 +249,14 @@ int pk_r1cs_create(pk_ctx* ctx, size_t num_constraints, size_t num_witnesses, co
     *out = nullptr;
     PK_REQUIRE(ctx, mats && (interner || n_interned == 0), "null pointer");
     PK_REQUIRE(ctx, num_constraints < (1ull << 32) && num_witnesses < (1ull << 32), "dimension above u32");
+    // the interned value is the first factor of every product of a line (sparse_row_dot): fe29.hpp dot29 bounds its running sum for
+    // first factors below p only, and a line of larger ones would come out wrong without an error
+    for (size_t i = 0; i < n_interned; i++) {
+        fe c;
+        memcpy(c.v, interner + 4 * i, 32);
+        const fe red = fe_reduce_any(c);
+        if (memcmp(red.v, c.v, 32) != 0) return set_err(ctx, PK_ERR_BAD_ARG, "bad argument: interned value %zu is not a Montgomery image below the modulus", i);
+    }
     pk_r1cs* r = new (std::nothrow) pk_r1cs();
     if (!r) return PK_ERR_OOM;
     r->num_constraints = num_constraints;

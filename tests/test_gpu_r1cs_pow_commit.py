@@ -146,6 +146,17 @@ def test_r1cs_rejects_bad_input(ctx):
         R1CS(ctx, good, bad_col, good, it)
     with pytest.raises(ProveKitHipError):  # "Value not in interner."
         R1CS(ctx, good, good, bad_val, it)
+    # interned values are Montgomery images below the modulus (include/provekit_hip.h): the dot product of a line bounds its running
+    # sum for such first factors only, so p and 2^256 - 1 are refused by index, and p - 1 is the largest value taken
+    p = 21888242871839275222246405745257275088548364400416034343698204186575808495617
+    for bad in (p, (1 << 256) - 1):
+        for at in (0, 1):
+            vals = [p - 1, p - 1]
+            vals[at] = bad
+            with pytest.raises(ProveKitHipError, match=f"interned value {at} is not") as e:
+                R1CS(ctx, good, good, good, np.frombuffer(b"".join(v.to_bytes(32, "little") for v in vals), dtype="<u8").reshape(2, 4))
+            assert e.value.code == -1
+    R1CS(ctx, good, good, good, np.frombuffer((p - 1).to_bytes(32, "little") * 2, dtype="<u8").reshape(2, 4)).close()
 
 
 @pytest.mark.parametrize("bits", [0.0, 3.141592653589793, 10.0, 16.0, 20.0])

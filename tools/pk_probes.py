@@ -56,10 +56,38 @@ SIGNATURES = {
     "pk_probe_witness_sum_chunk": (C.c_uint, []),
     "pk_probe_witness_n_ops": (C.c_uint, []),
     "pk_probe_witness_phases": (C.c_int, [C.c_char_p, sz, vp, vp, vp, sz, C.POINTER(C.c_size_t), C.c_char_p, sz]),
+    # csrc/r1cs.hip's thresholds, its two sharded entry points and fe29.hpp's dot29 on the host (tools/probes/r1cs.hip)
+    "pk_probe_r1cs_heavy_degree": (C.c_uint, []),
+    "pk_probe_r1cs_heavy_chunk": (C.c_uint, []),
+    "pk_probe_dot29_group": (C.c_uint, []),
+    "pk_probe_reduction_threads": (C.c_uint, []),
+    "pk_probe_r1cs_witness_bounds_strided": (C.c_int, [vp, vp, vp, C.c_uint, C.c_uint, C.c_uint, vp, vp, vp]),
+    "pk_probe_r1cs_external_row_range": (C.c_int, [vp, vp, vp, sz, sz, vp]),
+    "pk_probe_dot29_host": (C.c_int, [vp, vp, C.c_uint, vp]),
 }
 for _name, (_res, _args) in SIGNATURES.items():
     _fn = getattr(lib, _name)
     _fn.restype, _fn.argtypes = _res, _args
+
+
+def r1cs_thresholds() -> dict:
+    """csrc/r1cs_shape.hpp, fe29.hpp and reduce.hpp: the line length above which a line is summed by workgroups, the entries per
+    workgroup of such a line, the products per Montgomery reduction of a line's dot product, the lanes that stride a chunk"""
+    return {"HEAVY_DEGREE": lib.pk_probe_r1cs_heavy_degree(), "HEAVY_CHUNK": lib.pk_probe_r1cs_heavy_chunk(),
+            "DOT29_GROUP": lib.pk_probe_dot29_group(), "RED_THREADS": lib.pk_probe_reduction_threads()}
+
+
+def dot29_host(a, b):
+    """sum_t a[t] * b[t] * 2^-256 mod p by fe29.hpp's dot29 on the host; a, b: (terms, 4) u64 arrays -> (4,) u64"""
+    import numpy as np
+
+    a, b = (np.ascontiguousarray(x, dtype=np.uint64).reshape(-1, 4) for x in (a, b))
+    assert a.shape == b.shape
+    out = np.empty(4, dtype=np.uint64)
+    rc = lib.pk_probe_dot29_host(a.ctypes.data if len(a) else None, b.ctypes.data if len(b) else None, len(a), out.ctypes.data)
+    if rc:
+        raise ValueError(f"pk_probe_dot29_host: {rc}")
+    return out
 
 
 def witness_thresholds() -> dict:

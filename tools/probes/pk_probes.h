@@ -113,6 +113,21 @@ unsigned pk_probe_witness_n_ops(void);
 int pk_probe_witness_phases(const uint8_t *bytes, size_t len, uint32_t *widths, uint32_t *op_counts, uint32_t *blocks_before, size_t cap,
                             size_t *n_phases, char *err, size_t err_cap);
 
+/* csrc/r1cs.hip's thresholds (csrc/r1cs_shape.hpp: a line of more than heavy_degree entries is summed by workgroups, heavy_chunk
+ * entries each), the terms per Montgomery reduction of its dot product (csrc/fe29.hpp DOT29_GROUP) and the lanes a chunk's entries
+ * are strided by (csrc/reduce.hpp RED_THREADS); the two entry points only the sharded prover calls (csrc/internal.hpp: their own
+ * argument order, device pointers the caller owns); and pk_probe_dot29_host: the loop of a line's dot product on the HOST,
+ * out = sum_t a[t] * b[t] * 2^-256 mod p over `terms` pairs of 4 x u64 (a: the first factors, where the interned values go).  For
+ * tests/test_r1cs_edge_cases_host.py and tests/test_gpu_r1cs_edges.py (r1cs.hip here). */
+unsigned pk_probe_r1cs_heavy_degree(void);
+unsigned pk_probe_r1cs_heavy_chunk(void);
+unsigned pk_probe_dot29_group(void);
+unsigned pk_probe_reduction_threads(void);
+int pk_probe_r1cs_witness_bounds_strided(pk_ctx *ctx, const pk_r1cs *r, const uint64_t *d_z, unsigned m0, unsigned stride, unsigned offset,
+                                         uint64_t *d_a, uint64_t *d_b, uint64_t *d_c);
+int pk_probe_r1cs_external_row_range(pk_ctx *ctx, const pk_r1cs *r, const uint64_t *d_eq, size_t first, size_t last, uint64_t *d_out);
+int pk_probe_dot29_host(const uint64_t *a, const uint64_t *b, unsigned terms, uint64_t *out);
+
 #ifdef __cplusplus
 }
 #endif
