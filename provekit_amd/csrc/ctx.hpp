@@ -69,7 +69,7 @@ struct pk_ctx {
 
 // fixed slots in the 4 KiB h_pinned page: [0,1024) reduction results, word 256 completion flag (reduce.hpp)
 #define PK_PIN_ROOT 2048 /* 32 B: the root of the last Merkle tree built on this context (hash.hip) */
-#define PK_PIN_POW 2112  /* 8 B: the nonce found by the last proof-of-work launch (pow.hip) */
+#define PK_PIN_POW 2112  /* 8 B: the nonce found by the last proof-of-work search, or the 1 / 0 of the last check (pow.hip) */
 #define PK_PIN_GATE 2304 /* 48 B, 64-byte aligned: the gate through which the host publishes a round's challenge (reduce.hpp) */
 #define PK_PIN_GATE_TIMEOUT 2368 /* 4 B: sequence number of a gate whose kernel gave up waiting (reduce.hpp); 0 = none */
 

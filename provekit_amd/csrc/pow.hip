@@ -26,11 +26,33 @@ __device__ __forceinline__ fe from_arg(const fe_arg& a) {
     return r;
 }
 
+// what a lane keeps of (challenge, threshold), and the one question asked of a nonce: is C(challenge, nonce) < threshold?
+// The left input of every hash is the challenge: its round-0 square is computed once per lane, 13 squarings per hash instead of 14.
+struct PowHash {
+    fe29 challenge, s0;
+    fe threshold;
+    __device__ __forceinline__ PowHash(const fe_arg& challenge_arg, const fe_arg& threshold_arg) {
+        challenge = to_scaled29(from_arg(challenge_arg));  // generic.rs:81 reduce_partial on arbitrary input
+        fe29 zero;
+#pragma unroll
+        for (int k = 0; k < 9; k++) zero.v[k] = 0;
+        s0 = challenge;
+        sky_sq_round_s<0>(s0, zero);  // round 0 for r = 0, once per lane: s0 = 32 sq(challenge)
+        threshold = from_arg(threshold_arg);
+    }
+    __device__ __forceinline__ bool valid(unsigned long long nonce) const {
+        fe r = fe_zero();
+        r.v[0] = (u32)nonce;
+        r.v[1] = (u32)(nonce >> 32);
+        const fe h = from_scaled_canon(compress29s_v2_fixed_left(challenge, s0, unpack29<5>(r)));  // 32*nonce < 2^69: three limbs
+        return fe_lt(h, threshold);
+    }
+};
+
 // best / ticket: two device words, best == ~0 and ticket == 0 between launches.  Lanes walk the window in ascending
 // grid-stride order and stop as soon as a smaller valid nonce is known (a lane's later nonces are all larger), so the work
 // done is the expected 2^bits hashes plus about one stride, whatever the window; the result is still the SMALLEST valid
-// nonce (every nonce below the final `best` has been tried).  The left input of every hash is the challenge: its round-0
-// square is computed once per lane, 13 squarings per hash instead of 14.  The workgroup that draws the last ticket
+// nonce (every nonce below the final `best` has been tried).  The workgroup that draws the last ticket
 // publishes the result (or ~0) to pinned host memory and re-arms both words: a window costs one launch and one stream
 // synchronisation -- no copy operations.
 // (world, rank): nonce ranges striped over the ranks of a device set: this launch tries base + t for t = rank (mod
@@ -39,21 +61,12 @@ __global__ __launch_bounds__(256) void pow_search_kernel(fe_arg challenge_arg, f
                                                          unsigned long long count, unsigned long long* best, unsigned* ticket,
                                                          unsigned long long* host_best, unsigned world, unsigned rank) {
     PK_LATENCY_PRIO();
-    const fe29 challenge = to_scaled29(from_arg(challenge_arg));  // generic.rs:81 reduce_partial on arbitrary input
-    fe29 s0 = challenge, zero;
-#pragma unroll
-    for (int k = 0; k < 9; k++) zero.v[k] = 0;
-    sky_sq_round_s<0>(s0, zero);  // round 0 for r = 0, once per lane: s0 = 32 sq(challenge)
-    const fe threshold = from_arg(threshold_arg);
+    const PowHash pow(challenge_arg, threshold_arg);
     const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x * world;
     for (unsigned long long t = ((unsigned long long)blockIdx.x * blockDim.x + threadIdx.x) * world + rank; t < count; t += stride) {
         const unsigned long long nonce = base + t;
         if (nonce > __hip_atomic_load(best, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) break;
-        fe r = fe_zero();
-        r.v[0] = (u32)nonce;
-        r.v[1] = (u32)(nonce >> 32);
-        fe h = from_scaled_canon(compress29s_v2_fixed_left(challenge, s0, unpack29<5>(r)));  // 32*nonce < 2^69: three limbs
-        if (fe_lt(h, threshold)) atomicMin(best, nonce);
+        if (pow.valid(nonce)) atomicMin(best, nonce);
     }
     __syncthreads();  // every lane of the workgroup has issued its atomicMin
     if (threadIdx.x == 0) {
@@ -64,6 +77,20 @@ __global__ __launch_bounds__(256) void pow_search_kernel(fe_arg challenge_arg, f
             __hip_atomic_store(host_best, b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         }
     }
+}
+
+// pk_pow_check's launch: is ONE nonce valid?  Publishes 1 (its hash is below the threshold) or 0.  Not the search kernel over a
+// window of one: that reports the nonce it found, and at nonce = 2^64 - 1 the answer would be the word the search uses for
+// "nothing found".  The search's best / ticket words are not touched, so they stay armed.
+// One wavefront: lane k hashes nonce + k (wrapping) and bit 0 of the ballot, lane 0's answer, is what is published.  The other
+// lanes cost nothing, and a nonce that differs by lane keeps the hash on the vector ALU, where the search runs it: a hash of
+// uniform inputs is compiled for the scalar unit, and a check then takes 30 us instead of 24.
+__global__ __launch_bounds__(64) void pow_check_kernel(fe_arg challenge_arg, fe_arg threshold_arg, unsigned long long nonce,
+                                                       unsigned long long* host_ok) {
+    PK_LATENCY_PRIO();
+    const PowHash pow(challenge_arg, threshold_arg);
+    const unsigned long long ok = __ballot(pow.valid(nonce + threadIdx.x));
+    if (threadIdx.x == 0) __hip_atomic_store(host_ok, ok & 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
 // device words + the pinned result slot; first use (or a re-allocated scratch buffer) initialises best = ~0, ticket = 0
@@ -180,19 +207,17 @@ int pk_pow_check(pk_ctx* ctx, const uint8_t challenge[32], double bits, uint64_t
     uint64_t thr[4];
     int rc = pk_pow_threshold(bits, thr);
     if (rc) return set_err(ctx, rc, "threshold");
-    unsigned long long *d_best, *h_best;
-    unsigned* d_ticket;
-    rc = pow_words(ctx, &d_best, &d_ticket, &h_best);
+    rc = ensure_pinned(ctx);
     if (rc) return rc;
+    unsigned long long* h_ok = (unsigned long long*)((char*)ctx->h_pinned + PK_PIN_POW);
     fe_arg ch, th;
     memcpy(ch.v, challenge, 32);
     memcpy(th.v, thr, 32);
-    pow_search_kernel<<<1, 64, 0, ctx->stream>>>(ch, th, nonce, 1, d_best, d_ticket, h_best, 1, 0);
+    pow_check_kernel<<<1, 64, 0, ctx->stream>>>(ch, th, nonce, h_ok);
     PK_LAUNCH_CHECK(ctx);
     rc = sync_stream(ctx);
     if (rc) return rc;
-    const unsigned long long best = *(volatile unsigned long long*)h_best;
-    *ok = best == nonce;
+    *ok = *(volatile unsigned long long*)h_ok == 1;  // 1 or 0: no nonce, 2^64 - 1 included, can be mistaken for the answer
     return PK_OK;
 }
 
