@@ -100,18 +100,10 @@ class WhirPcs {
     }
     PcsOpening open(const PcsCommitment& com, const std::vector<Point>& points) const {
         const std::vector<uint64_t> flat = flatten(points, cfg_.n_vars);
-        PcsOpening o;
-        o.evaluations.resize((size_t)cfg_.batch_size * points.size());
-        o.proof.resize(1 << 20);
-        size_t len = 0;
-        int rc = pkw_open(s_, com.get(), flat.data(), (unsigned)points.size(), o.evaluations[0].data(), o.proof.data(), o.proof.size(), &len);
-        if (rc == PK_ERR_BAD_ARG && len > o.proof.size()) {  // the proof is larger: *len says by how much
-            o.proof.resize(len);
-            rc = pkw_open(s_, com.get(), flat.data(), (unsigned)points.size(), o.evaluations[0].data(), o.proof.data(), o.proof.size(), &len);
-        }
-        check(rc);
-        o.proof.resize(len);
-        return o;
+        PcsLinearOpening o = open_with(points.size(), 0, [&](uint64_t* evals, uint64_t*, uint8_t* proof, size_t cap, size_t* len) {
+            return pkw_open(s_, com.get(), flat.data(), (unsigned)points.size(), evals, proof, cap, len);
+        });
+        return {std::move(o.evaluations), std::move(o.proof)};
     }
     // host only; evaluations_out (optional) receives what the proof binds
     static PcsVerdict verify(const WhirConfig& cfg, const std::vector<Point>& points, const std::vector<uint8_t>& proof,
@@ -119,13 +111,11 @@ class WhirPcs {
                              int hash_version = 2) {
         const pk_whir_config c = cfg.to_c();
         const std::vector<uint64_t> flat = flatten(points, c.n_vars);
-        std::vector<FieldElement> ev((size_t)c.batch_size * points.size());
-        pkv_result r;
-        if (int rc = pkw_verify(&c, nullptr, 0, hash_version, expected_root ? expected_root->data() : nullptr, flat.data(), (unsigned)points.size(),
-                                proof.data(), proof.size(), ev.empty() ? nullptr : ev[0].data(), &r))
-            throw Error(rc, pkw_create_error());
-        if (evaluations_out) *evaluations_out = ev;
-        return {r.accepted != 0, r.check, r.offset, r.message};
+        const PcsLinearVerdict out = verify_with(c, points.size(), 0, [&](uint64_t* evals, uint64_t*, uint64_t*, uint64_t*, unsigned*, pkv_result* r) {
+            return pkw_verify(&c, nullptr, 0, hash_version, root_ptr(expected_root), flat.data(), (unsigned)points.size(), proof.data(), proof.size(), evals, r);
+        });
+        if (evaluations_out) *evaluations_out = out.evaluations;
+        return out.verdict;
     }
     // q >= 0 points and l >= 1 dense weight tables on the device, bound by the caller's tags (provekit_whir.h, "TAGS AND SOUNDNESS")
     PcsLinearOpening open_linear(const PcsCommitment& com, const std::vector<Point>& points, const std::vector<const DeviceVec*>& weights,
@@ -134,24 +124,10 @@ class WhirPcs {
         const std::vector<uint64_t> flat = flatten(points, cfg_.n_vars, /*may_be_empty=*/true);
         std::vector<const uint64_t*> w;
         for (const DeviceVec* v : weights) w.push_back(v->data());
-        PcsLinearOpening o;
-        o.evaluations.resize((size_t)cfg_.batch_size * points.size());
-        o.sums.resize((size_t)cfg_.batch_size * weights.size());
-        o.proof.resize(1 << 20);
-        size_t len = 0;
-        auto call = [&] {
-            return pkw_open_linear(s_, com.get(), flat.data(), (unsigned)points.size(), w.data(), tags.empty() ? nullptr : tags[0].data(),
-                                   (unsigned)weights.size(), o.evaluations.empty() ? nullptr : o.evaluations[0].data(),
-                                   o.sums.empty() ? nullptr : o.sums[0].data(), o.proof.data(), o.proof.size(), &len);
-        };
-        int rc = call();
-        if (rc == PK_ERR_BAD_ARG && len > o.proof.size()) {  // the proof is larger: *len says by how much
-            o.proof.resize(len);
-            rc = call();
-        }
-        check(rc);
-        o.proof.resize(len);
-        return o;
+        return open_with(points.size(), weights.size(), [&](uint64_t* evals, uint64_t* sums, uint8_t* proof, size_t cap, size_t* len) {
+            return pkw_open_linear(s_, com.get(), flat.data(), (unsigned)points.size(), w.data(), ptr(tags), (unsigned)weights.size(), evals, sums, proof, cap,
+                                   len);
+        });
     }
     // host only.  weights: host tables (2^n_vars elements each), or nullptr entries / an empty vector for "not given"
     static PcsLinearVerdict verify_linear(const WhirConfig& cfg, const std::vector<Point>& points, const std::vector<FieldElement>& tags,
@@ -165,22 +141,12 @@ class WhirPcs {
             if (t && t->size() != (size_t)1 << c.n_vars) throw Error(PK_ERR_BAD_ARG, "a weight table has 2^n_vars elements");
             w.push_back(t ? (*t)[0].data() : nullptr);
         }
-        PcsLinearVerdict out;
-        out.evaluations.resize((size_t)c.batch_size * points.size());
-        out.sums.resize((size_t)c.batch_size * tags.size());
-        out.fold_point.resize(c.n_vars);
-        out.deferred.resize(tags.size());
-        std::vector<uint64_t> fold(4 * (size_t)c.n_vars + 4);  // flat storage: a valid pointer whatever n_vars is
-        pkv_result r;
-        if (int rc = pkw_verify_linear(&c, nullptr, 0, hash_version, expected_root ? expected_root->data() : nullptr, flat.data(), (unsigned)points.size(),
-                                       tags.empty() ? nullptr : tags[0].data(), w.empty() ? nullptr : w.data(), (unsigned)tags.size(), proof.data(),
-                                       proof.size(), out.evaluations.empty() ? nullptr : out.evaluations[0].data(),
-                                       out.sums.empty() ? nullptr : out.sums[0].data(), fold.data(),
-                                       out.deferred.empty() ? nullptr : out.deferred[0].data(), &out.unchecked, &r))
-            throw Error(rc, pkw_create_error());
-        for (unsigned j = 0; j < c.n_vars; j++) std::copy(fold.begin() + 4 * j, fold.begin() + 4 * j + 4, out.fold_point[j].begin());
-        out.verdict = {r.accepted != 0, r.check, r.offset, r.message};
-        return out;
+        return verify_with(c, points.size(), tags.size(),
+                           [&](uint64_t* evals, uint64_t* sums, uint64_t* fold, uint64_t* deferred, unsigned* unchecked, pkv_result* r) {
+                               return pkw_verify_linear(&c, nullptr, 0, hash_version, root_ptr(expected_root), flat.data(), (unsigned)points.size(), ptr(tags),
+                                                        w.empty() ? nullptr : w.data(), (unsigned)tags.size(), proof.data(), proof.size(), evals, sums, fold,
+                                                        deferred, unchecked, r);
+                           });
     }
     // open_linear with the weights as lists: the same statement and the same bytes.  The lists are copied to the device for the
     // call (a caller that keeps them there calls pkw_open_sparse); the library validates the indexes before it uses one
@@ -191,25 +157,10 @@ class WhirPcs {
         const size_t entries = weights.index.size();
         const DeviceVec d_value(ctx, weights.value), d_index(ctx, (entries + 7) / 8);  // 8 indexes per 32 bytes
         if (entries) ctx.check(pk_memcpy_h2d(ctx.get(), d_index.data(), weights.index.data(), 4 * entries));
-        PcsLinearOpening o;
-        o.evaluations.resize((size_t)cfg_.batch_size * points.size());
-        o.sums.resize((size_t)cfg_.batch_size * tags.size());
-        o.proof.resize(1 << 20);
-        size_t len = 0;
-        auto call = [&] {
-            return pkw_open_sparse(s_, com.get(), flat.data(), (unsigned)points.size(), weights.offsets.data(),
-                                   reinterpret_cast<const uint32_t*>(d_index.data()), d_value.data(), tags.empty() ? nullptr : tags[0].data(), weights.count(),
-                                   o.evaluations.empty() ? nullptr : o.evaluations[0].data(), o.sums.empty() ? nullptr : o.sums[0].data(), o.proof.data(),
-                                   o.proof.size(), &len);
-        };
-        int rc = call();
-        if (rc == PK_ERR_BAD_ARG && len > o.proof.size()) {  // the proof is larger: *len says by how much
-            o.proof.resize(len);
-            rc = call();
-        }
-        check(rc);
-        o.proof.resize(len);
-        return o;
+        return open_with(points.size(), tags.size(), [&](uint64_t* evals, uint64_t* sums, uint8_t* proof, size_t cap, size_t* len) {
+            return pkw_open_sparse(s_, com.get(), flat.data(), (unsigned)points.size(), weights.offsets.data(), reinterpret_cast<const uint32_t*>(d_index.data()),
+                                   d_value.data(), ptr(tags), weights.count(), evals, sums, proof, cap, len);
+        });
     }
     // host only; every weight's deferred value is judged from its entries: `unchecked` stays 0 and the verdict is unconditional
     static PcsLinearVerdict verify_sparse(const WhirConfig& cfg, const std::vector<Point>& points, const std::vector<FieldElement>& tags,
@@ -218,22 +169,11 @@ class WhirPcs {
         const pk_whir_config c = cfg.to_c();
         const std::vector<uint64_t> flat = flatten(points, c.n_vars, /*may_be_empty=*/true);
         if (weights.count() != tags.size()) throw Error(PK_ERR_BAD_ARG, "as many weights as tags");
-        PcsLinearVerdict out;
-        out.evaluations.resize((size_t)c.batch_size * points.size());
-        out.sums.resize((size_t)c.batch_size * tags.size());
-        out.fold_point.resize(c.n_vars);
-        out.deferred.resize(tags.size());
-        std::vector<uint64_t> fold(4 * (size_t)c.n_vars + 4);
-        pkv_result r;
-        if (int rc = pkw_verify_sparse(&c, nullptr, 0, hash_version, expected_root ? expected_root->data() : nullptr, flat.data(), (unsigned)points.size(),
-                                       tags.empty() ? nullptr : tags[0].data(), weights.offsets.data(), weights.index.empty() ? nullptr : weights.index.data(),
-                                       weights.value.empty() ? nullptr : weights.value[0].data(), weights.count(), proof.data(), proof.size(),
-                                       out.evaluations.empty() ? nullptr : out.evaluations[0].data(), out.sums.empty() ? nullptr : out.sums[0].data(),
-                                       fold.data(), out.deferred.empty() ? nullptr : out.deferred[0].data(), &r))
-            throw Error(rc, pkw_create_error());
-        for (unsigned j = 0; j < c.n_vars; j++) std::copy(fold.begin() + 4 * j, fold.begin() + 4 * j + 4, out.fold_point[j].begin());
-        out.verdict = {r.accepted != 0, r.check, r.offset, r.message};
-        return out;
+        return verify_with(c, points.size(), tags.size(), [&](uint64_t* evals, uint64_t* sums, uint64_t* fold, uint64_t* deferred, unsigned*, pkv_result* r) {
+            return pkw_verify_sparse(&c, nullptr, 0, hash_version, root_ptr(expected_root), flat.data(), (unsigned)points.size(), ptr(tags),
+                                     weights.offsets.data(), weights.index.empty() ? nullptr : weights.index.data(), ptr(weights.value), weights.count(),
+                                     proof.data(), proof.size(), evals, sums, fold, deferred, r);
+        });
     }
     pkw_scheme* get() const { return s_; }
 
@@ -250,6 +190,42 @@ class WhirPcs {
     }
     void check(int rc) const {
         if (rc) throw Error(rc, pkw_last_error(s_));
+    }
+    static const uint64_t* ptr(const std::vector<FieldElement>& v) { return v.empty() ? nullptr : v[0].data(); }
+    static uint64_t* ptr(std::vector<FieldElement>& v) { return v.empty() ? nullptr : v[0].data(); }
+    static const uint8_t* root_ptr(const std::array<uint8_t, 32>* root) { return root ? root->data() : nullptr; }
+    // An opening at q points and l weights: call(evals, sums, proof, cap, &len) writes into buffers this owns; the proof buffer grows
+    // once when *len says the proof is larger
+    template <class Call>
+    PcsLinearOpening open_with(size_t q, size_t l, Call call) const {
+        PcsLinearOpening o;
+        o.evaluations.resize(cfg_.batch_size * q);
+        o.sums.resize(cfg_.batch_size * l);
+        o.proof.resize(1 << 20);
+        size_t len = 0;
+        int rc = call(ptr(o.evaluations), ptr(o.sums), o.proof.data(), o.proof.size(), &len);
+        if (rc == PK_ERR_BAD_ARG && len > o.proof.size()) {
+            o.proof.resize(len);
+            rc = call(ptr(o.evaluations), ptr(o.sums), o.proof.data(), o.proof.size(), &len);
+        }
+        check(rc);
+        o.proof.resize(len);
+        return o;
+    }
+    // A verification of q points and l weights: call(evals, sums, fold, deferred, &unchecked, &result) fills outputs sized here
+    template <class Call>
+    static PcsLinearVerdict verify_with(const pk_whir_config& c, size_t q, size_t l, Call call) {
+        PcsLinearVerdict out;
+        out.evaluations.resize(c.batch_size * q);
+        out.sums.resize(c.batch_size * l);
+        out.fold_point.resize(c.n_vars);
+        out.deferred.resize(l);
+        std::vector<uint64_t> fold(4 * (size_t)c.n_vars + 4);  // flat storage: a valid pointer whatever n_vars is
+        pkv_result r;
+        if (int rc = call(ptr(out.evaluations), ptr(out.sums), fold.data(), ptr(out.deferred), &out.unchecked, &r)) throw Error(rc, pkw_create_error());
+        for (unsigned j = 0; j < c.n_vars; j++) std::copy(fold.begin() + 4 * j, fold.begin() + 4 * j + 4, out.fold_point[j].begin());
+        out.verdict = {r.accepted != 0, r.check, r.offset, r.message};
+        return out;
     }
     pk_whir_config cfg_;
     pkw_scheme* s_ = nullptr;

@@ -12,15 +12,17 @@
 // eq_mid(g) is the same for all lanes: it sits in LDS pre-shifted (unpack29<5>) and is read as a broadcast.  The bracket stays
 // in registers (9 limbs per point); eq_lo(t), which every lane needs once, is the product of two 16-entry tables (4 + 4 variables)
 // in LDS, eq_top(wg) one element per point.  So no cross-lane traffic happens per tile: one workgroup reduction per point at the end,
-// one partial per (polynomial, point, workgroup), and eval_finish_kernel adds the partials.  LDS: 18 KiB eq_mid + 8 KiB eq_lo
-// halves + 1.3 KiB -- not the 64 KiB that whole 2^8-entry tables for 8 points would take -- so LDS never limits occupancy; the
-// registers do (DESIGN.md 11 records the compiled numbers).
+// one partial per (polynomial, point, workgroup), and finish_kernel adds the partials -- here and for every other kernel of the
+// library that leaves one partial per (output, workgroup): linear.hip's sums, sparse.hip's sums and evaluation.
+// LDS: 18 KiB eq_mid + 8 KiB eq_lo halves + 1.3 KiB -- not the 64 KiB that whole 2^8-entry tables for 8 points would take -- so LDS
+// never limits occupancy; the registers do (DESIGN.md 11 records the compiled numbers).
 //
 // Sizes below 2^8: the same kernel with the tile clamped to 2^n_vars (lanes beyond it idle).
 #include <hip/hip_runtime.h>
 
 #include "../fe29.hpp"
 #include "block_sum.hpp"
+#include "blocking.hpp"
 #include "evaluate.hpp"
 
 using namespace pk;
@@ -137,12 +139,13 @@ __global__ __launch_bounds__(THREADS) void mle_eval_kernel(Polys polys, const fe
     }
 }
 
-// out[y * out_stride + i] = sum of the n_wg partials of (poly y, point i); one workgroup per (y, i)
-__global__ __launch_bounds__(THREADS) void eval_finish_kernel(const fe* __restrict__ partial, unsigned n_wg, unsigned Q, fe* __restrict__ out,
-                                                              unsigned out_stride) {
+// out[y * out_stride + i] = sum of the n_wg partials of output (y, i), i < count, which start at partial[(y * row_stride + i) * n_wg];
+// one workgroup per output.  Lane j adds the partials j, j + 256, ...: field addition is exact, so the result does not depend on n_wg
+__global__ __launch_bounds__(THREADS) void finish_kernel(const fe* __restrict__ partial, unsigned n_wg, unsigned count, unsigned row_stride,
+                                                         fe* __restrict__ out, unsigned out_stride) {
     __shared__ fe red[4];
-    const unsigned y = blockIdx.x / Q, i = blockIdx.x % Q;
-    const fe* p = partial + ((size_t)y * EVAL_PASS + i) * n_wg;
+    const unsigned y = blockIdx.x / count, i = blockIdx.x % count;
+    const fe* p = partial + ((size_t)y * row_stride + i) * n_wg;
     fe acc = fe_zero();
     for (unsigned j = threadIdx.x; j < n_wg; j += THREADS) acc = fe_add(acc, fe_load(p + j));
     acc = block_sum(acc, red);
@@ -162,14 +165,14 @@ int eval_launch(hipStream_t stream, const uint64_t* const* d_evals, unsigned bat
     for (unsigned q0 = 0; q0 < q; q0 += EVAL_PASS) {  // stream order keeps a pass's partials until its finish kernel has read them
         const unsigned Q = q - q0 < EVAL_PASS ? q - q0 : EVAL_PASS;
         mle_eval_kernel<<<dim3(n_wg, batch), THREADS, 0, stream>>>(polys, (const fe*)d_points + (size_t)q0 * n_vars, Q, n_vars, s, (fe*)d_partial);
-        eval_finish_kernel<<<batch * Q, THREADS, 0, stream>>>((const fe*)d_partial, n_wg, Q, (fe*)d_out + q0, q);
+        finish_launch(stream, d_partial, n_wg, batch, Q, EVAL_PASS, d_out + 4 * (size_t)q0, q);
     }
     return hipGetLastError() == hipSuccess ? PK_OK : PK_ERR_HIP;
 }
 
-int eval_finish_launch(hipStream_t stream, const uint64_t* d_partial, unsigned n_wg, unsigned rows, unsigned count, uint64_t* d_out, unsigned out_stride) {
-    eval_finish_kernel<<<rows * count, THREADS, 0, stream>>>((const fe*)d_partial, n_wg, count, (fe*)d_out, out_stride);
-    return hipGetLastError() == hipSuccess ? PK_OK : PK_ERR_HIP;
+void finish_launch(hipStream_t stream, const uint64_t* d_partial, unsigned n_wg, unsigned rows, unsigned count, unsigned row_stride, uint64_t* d_out,
+                   unsigned out_stride) {
+    finish_kernel<<<rows * count, THREADS, 0, stream>>>((const fe*)d_partial, n_wg, count, row_stride, (fe*)d_out, out_stride);
 }
 
 }  // namespace pkw
@@ -184,19 +187,13 @@ int pkw_evaluate(pk_ctx* ctx, const uint64_t* const* d_evals, unsigned batch, un
     for (unsigned b = 0; b < batch; b++)
         if (!d_evals[b]) return PK_ERR_BAD_ARG;
     const size_t pts = (size_t)q * n_vars, part = pkw::eval_partial_fes(batch, n_vars), res = (size_t)batch * q;
-    void* d = nullptr;
-    int rc = pk_malloc(ctx, 32 * (pts + part + res), &d);
-    if (rc) return rc;
-    uint64_t* d_pts = (uint64_t*)d;
-    uint64_t* d_part = d_pts + 4 * pts;
-    uint64_t* d_res = d_part + 4 * part;
-    rc = pk_memcpy_h2d(ctx, d_pts, points, 32 * pts);
-    if (!rc) rc = pk_ctx_sync(ctx);  // the polynomials are the context's work: finished before the kernel reads them
-    if (!rc) rc = pkw::eval_launch(nullptr, d_evals, batch, n_vars, d_pts, q, d_part, d_res);
-    if (!rc && hipStreamSynchronize(nullptr) != hipSuccess) rc = PK_ERR_HIP;
-    if (!rc) rc = pk_memcpy_d2h(ctx, out, d_res, 32 * res);
-    pk_free(ctx, d);
-    return rc;
+    pkw::Scratch d(ctx, pts + part + res);
+    if (d.rc) return d.rc;
+    uint64_t *d_pts = d.take(pts), *d_part = d.take(part), *d_res = d.take(res);
+    if (int rc = pk_memcpy_h2d(ctx, d_pts, points, 32 * pts)) return rc;
+    // the polynomials are the context's work: finished before the kernel reads them
+    if (int rc = pkw::run_blocking(ctx, [&] { return pkw::eval_launch(nullptr, d_evals, batch, n_vars, d_pts, q, d_part, d_res); })) return rc;
+    return pk_memcpy_d2h(ctx, out, d_res, 32 * res);
 }
 
 }  // extern "C"

@@ -1,4 +1,5 @@
-// evaluate.hpp -- the evaluation kernel's launch, for pcs.hip (pkw_open runs it on the scheme's stream with arena scratch)
+// evaluate.hpp -- the launches of evaluate.hip: the evaluation kernel, for pcs.cpp (pkw_open runs it on the scheme's stream with arena
+// scratch), and the finish kernel and grid cap that linear.hip and sparse.hip share with it
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -16,8 +17,15 @@ size_t eval_partial_fes(unsigned batch, unsigned n_vars);
 // enqueue on `stream`: d_out[b * q + i] = MLE(d_evals[b])(d_points[i]); d_points = q * n_vars elements on the device
 int eval_launch(hipStream_t stream, const uint64_t* const* d_evals, unsigned batch, unsigned n_vars, const uint64_t* d_points, unsigned q,
                 uint64_t* d_partial, uint64_t* d_out);
-// enqueue on `stream`: d_out[y * out_stride + i] = the sum of the n_wg partials d_partial[(y * EVAL_PASS + i) * n_wg ..] for y < rows,
-// i < count <= EVAL_PASS: the second half of eval_launch, for kernels that leave their partials in the same layout (sparse.hip)
-int eval_finish_launch(hipStream_t stream, const uint64_t* d_partial, unsigned n_wg, unsigned rows, unsigned count, uint64_t* d_out, unsigned out_stride);
+// The library's one finish kernel, for every kernel that leaves one partial per (output, workgroup).  Enqueue on `stream`:
+// d_out[y * out_stride + i] = the sum of the n_wg partials d_partial[(y * row_stride + i) * n_wg ..] for y < rows, i < count <= row_stride.
+// row_stride is the pass width of the partial layout: EVAL_PASS here, SPARSE_PASS in sparse.hip, the pass's own count in linear.hip
+void finish_launch(hipStream_t stream, const uint64_t* d_partial, unsigned n_wg, unsigned rows, unsigned count, unsigned row_stride, uint64_t* d_out,
+                   unsigned out_stride);
+// a grid over n items, one per lane of 256-lane workgroups, at most 2048 workgroups (the kernels that take it stride by the grid)
+inline unsigned capped_grid(size_t n) {
+    const size_t blocks = (n + 255) / 256;
+    return (unsigned)(blocks < 2048 ? blocks : 2048);
+}
 
 }  // namespace pkw

@@ -6,7 +6,7 @@
 // each tiled operand (32 bytes as two 16-byte loads, 8 KiB contiguous per workgroup and operand) and makes TB * TW products of them,
 // so each polynomial is read ceil(l / TW) times and each weight ceil(batch / TB) times.  Workgroup x of the grid takes the elements
 // x * 256 + lane, then strides by the grid: no cross-lane traffic per step, one workgroup reduction per output at the end, one
-// partial per (output, workgroup), and sum_partials_kernel adds them -- the pattern of evaluate.hip.  Every partial is a fully
+// partial per (output, workgroup), and evaluate.hip's finish kernel adds them.  Every partial is a fully
 // reduced field element and field addition is exact, so the result does not depend on the grid.  Tile slots beyond batch or l
 // repeat the tile's first operand and are not stored; a single polynomial therefore takes a 1 x 4 tile, not 2 x 2 (wsum_launch).
 //
@@ -18,6 +18,8 @@
 #include <cstring>
 
 #include "block_sum.hpp"
+#include "blocking.hpp"
+#include "evaluate.hpp"
 #include "linear.hpp"
 #include "linear_tile.hpp"
 
@@ -66,18 +68,6 @@ __global__ __launch_bounds__(THREADS) void weighted_sums_kernel(WsumArgs a, unsi
         }
 }
 
-// out[b * out_stride + i] = sum of the n_wg partials of output (b, i), i < L; one workgroup per output
-__global__ __launch_bounds__(THREADS) void sum_partials_kernel(const fe* __restrict__ partial, unsigned n_wg, unsigned L, fe* __restrict__ out,
-                                                               unsigned out_stride) {
-    __shared__ fe red[4];
-    const unsigned b = blockIdx.x / L, i = blockIdx.x % L;
-    const fe* p = partial + (size_t)blockIdx.x * n_wg;
-    fe acc = fe_zero();
-    for (unsigned j = threadIdx.x; j < n_wg; j += THREADS) acc = fe_add(acc, fe_load(p + j));
-    acc = block_sum(acc, red);
-    if (threadIdx.x == 0) fe_store(out + (size_t)b * out_stride + i, acc);
-}
-
 struct CombArgs {
     const fe* w[COMB_TILE];
     fe s[COMB_TILE];
@@ -120,7 +110,7 @@ int wsum_launch(hipStream_t stream, const uint64_t* const* d_evals, unsigned bat
     const size_t N = (size_t)1 << n_vars;
     WsumArgs a{};
     for (unsigned b = 0; b < batch; b++) a.f[b] = (const fe*)d_evals[b];
-    for (unsigned i0 = 0; i0 < l; i0 += WSUM_PASS) {  // stream order keeps a pass's partials until sum_partials_kernel has read them
+    for (unsigned i0 = 0; i0 < l; i0 += WSUM_PASS) {  // stream order keeps a pass's partials until the finish kernel has read them
         const unsigned L = l - i0 < WSUM_PASS ? l - i0 : WSUM_PASS;
         for (unsigned i = 0; i < L; i++) a.w[i] = (const fe*)d_weights[i0 + i];
         // tile 0: 2 x 2, except that ONE polynomial takes 1 x 4 -- half of a 2 x 2 tile's products would repeat its first row
@@ -130,15 +120,14 @@ int wsum_launch(hipStream_t stream, const uint64_t* const* d_evals, unsigned bat
             wsum_pass<2, 1>(stream, a, batch, L, N, grid, (fe*)d_partial);
         else
             wsum_pass<(int)WSUM_TILE_B, (int)WSUM_TILE_W>(stream, a, batch, L, N, grid, (fe*)d_partial);
-        sum_partials_kernel<<<batch * L, THREADS, 0, stream>>>((const fe*)d_partial, grid, L, (fe*)d_out + i0, l);
+        finish_launch(stream, d_partial, grid, batch, L, L, d_out + 4 * (size_t)i0, l);
     }
     return hipGetLastError() == hipSuccess ? PK_OK : PK_ERR_HIP;
 }
 
 int combine_launch(hipStream_t stream, uint64_t* d_w, size_t len, const uint64_t* const* d_weights, const uint64_t* scales, unsigned l, int accumulate) {
     if (!len) return PK_OK;
-    const size_t blocks = (len + THREADS - 1) / THREADS;
-    const unsigned grid = (unsigned)(blocks < 2048 ? blocks : 2048);
+    const unsigned grid = capped_grid(len);
     if (!l && !accumulate) return hipMemsetAsync(d_w, 0, 32 * len, stream) == hipSuccess ? PK_OK : PK_ERR_HIP;
     for (unsigned i0 = 0; i0 < l; i0 += COMB_TILE) {
         const unsigned L = l - i0 < COMB_TILE ? l - i0 : COMB_TILE;
@@ -161,17 +150,12 @@ int weighted_sums(pk_ctx* ctx, const uint64_t* const* d_evals, unsigned batch, u
     for (unsigned i = 0; i < l; i++)
         if (!d_weights[i]) return PK_ERR_BAD_ARG;
     const size_t part = wsum_partial_fes(batch, n_vars), res = (size_t)batch * l;
-    void* d = nullptr;
-    int rc = pk_malloc(ctx, 32 * (part + res), &d);
-    if (rc) return rc;
-    uint64_t* d_part = (uint64_t*)d;
-    uint64_t* d_res = d_part + 4 * part;
-    rc = pk_ctx_sync(ctx);  // the operands are the context's work: finished before the kernel reads them
-    if (!rc) rc = wsum_launch(nullptr, d_evals, batch, n_vars, d_weights, l, d_part, d_res);
-    if (!rc && hipStreamSynchronize(nullptr) != hipSuccess) rc = PK_ERR_HIP;
-    if (!rc) rc = pk_memcpy_d2h(ctx, out, d_res, 32 * res);
-    pk_free(ctx, d);
-    return rc;
+    Scratch d(ctx, part + res);
+    if (d.rc) return d.rc;
+    uint64_t *d_part = d.take(part), *d_res = d.take(res);
+    // the operands are the context's work: finished before the kernel reads them
+    if (int rc = run_blocking(ctx, [&] { return wsum_launch(nullptr, d_evals, batch, n_vars, d_weights, l, d_part, d_res); })) return rc;
+    return pk_memcpy_d2h(ctx, out, d_res, 32 * res);
 }
 
 }  // namespace pkw

@@ -23,8 +23,7 @@ using pk::fe;
 struct pkw_scheme {
     pk_ctx* ctx = nullptr;
     pk_whir_config cfg{};
-    std::string pattern_cache[PKW_MAX_POINTS + 1];
-    std::map<unsigned, std::string> linear_pattern_cache;  // by q * (PKW_MAX_WEIGHTS + 1) + l
+    std::map<unsigned, std::string> pattern_cache;  // io_pattern(cfg, q, l) by q * (PKW_MAX_WEIGHTS + 1) + l; l = 0: pkw_open's
     std::string err;
     hipStream_t stream = nullptr;  // the evaluation kernel's
     uint64_t* arena = nullptr;
@@ -80,13 +79,6 @@ struct Tree {  // a committed codeword: what a round's STIR queries open
     const uint64_t *leaves, *nodes;
     size_t rows, width;
     pk_commit_layout layout;
-};
-
-// where the l weights of a linear statement come from: dense device tables, or validated index/value lists.  The three steps of an
-// opening that touch the weights ask this
-struct WeightSource {
-    const uint64_t* const* dense = nullptr;
-    const SparseWeights* sparse = nullptr;
 };
 
 struct Opening {
@@ -190,30 +182,32 @@ struct Opening {
         return PK_OK;
     }
 
-    // the three steps that read the weights, each from either source.  d_out[b * l + i] = <w_i, poly_b>
-    int weight_sums(const WeightSource& W, unsigned l, uint64_t* d_part, uint64_t* d_out) {
+    // the three steps that read the statement's weights: dense device tables, or validated index/value lists.
+    // d_out[b * l + i] = <w_i, poly_b>
+    int weight_sums(const Statement& W, uint64_t* d_part, uint64_t* d_out) {
         if (W.sparse) return sparse_sums_launch(S.stream, C.evals, cfg.batch_size, n, *W.sparse, d_part, d_out);
-        return wsum_launch(S.stream, C.evals, cfg.batch_size, n, W.dense, l, d_part, d_out);
+        return wsum_launch(S.stream, C.evals, cfg.batch_size, n, W.dense, W.l, d_part, d_out);
     }
     // d_w += sum_i scales[i] w_i
-    int weight_combine(const WeightSource& W, unsigned l, uint64_t* d_w, const fe* scales) {
+    int weight_combine(const Statement& W, uint64_t* d_w, const fe* scales) {
         if (W.sparse) return sparse_accumulate_launch(S.stream, d_w, *W.sparse, U(scales));
-        return combine_launch(S.stream, d_w, (size_t)1 << n, W.dense, U(scales), l, /*accumulate=*/1);
+        return combine_launch(S.stream, d_w, (size_t)1 << n, W.dense, U(scales), W.l, /*accumulate=*/1);
     }
     // d_out[i] = the extension of w_i at d_point.  The dense tables are read EVAL_MAX_BATCH at a time by the evaluation kernel (its
     // partials for EVAL_MAX_BATCH tables go into the commit scratch, idle by now); the lists' partials go where the sums' went
-    int weight_deferred(const WeightSource& W, unsigned l, const uint64_t* d_point, uint64_t* d_part, uint64_t* scratch, uint64_t* d_out) {
+    int weight_deferred(const Statement& W, const uint64_t* d_point, uint64_t* d_part, uint64_t* scratch, uint64_t* d_out) {
         if (W.sparse) return sparse_evaluate_launch(S.stream, n, *W.sparse, d_point, d_part, d_out);
         if (eval_partial_fes(EVAL_MAX_BATCH, n) > plan(cfg).scratch) return PK_ERR_OOM;
-        for (unsigned i0 = 0; i0 < l; i0 += EVAL_MAX_BATCH)
-            CK(eval_launch(S.stream, W.dense + i0, std::min(EVAL_MAX_BATCH, l - i0), n, d_point, 1, scratch, d_out + 4 * (size_t)i0));
+        for (unsigned i0 = 0; i0 < W.l; i0 += EVAL_MAX_BATCH)
+            CK(eval_launch(S.stream, W.dense + i0, std::min(EVAL_MAX_BATCH, W.l - i0), n, d_point, 1, scratch, d_out + 4 * (size_t)i0));
         return PK_OK;
     }
 
-    // q evaluation constraints, then l linear ones (l = 0: pkw_open); W: the l weights, tags: l host elements
-    int run(const fe* points, unsigned q, fe* evals /* batch * q */, const WeightSource& W, const fe* tags, unsigned l, fe* sums /* batch * l */) {
+    // q evaluation constraints, then l linear ones (l = 0: pkw_open)
+    int run(const Statement& W, fe* evals /* batch * q */, fe* sums /* batch * l */) {
         const size_t N = (size_t)1 << n;
-        const unsigned batch = cfg.batch_size;
+        const unsigned batch = cfg.batch_size, q = W.q, l = W.l;
+        const fe *points = reinterpret_cast<const fe*>(W.points), *tags = reinterpret_cast<const fe*>(W.tags);
         TAKE(scratch, plan(cfg).scratch);
         // 1-3: the commitment's transcript (mtUtilities.go:51-76)
         T.add_canon(pk::load_raw(C.root));
@@ -241,7 +235,7 @@ struct Opening {
         }
         T.add_scalars(evals, (size_t)batch * q);
         if (l) {
-            CK(weight_sums(W, l, d_part, d_out));
+            CK(weight_sums(W, d_part, d_out));
             if (hipStreamSynchronize(S.stream) != hipSuccess) return PK_ERR_HIP;
             CK(pk_memcpy_d2h(ctx, sums, d_out, 32 * (size_t)batch * l));
         }
@@ -269,7 +263,7 @@ struct Opening {
                     g = pk::h_mul(g, gamma);
                 }
                 CK(pk_ctx_sync(ctx));  // the eq weights are the context's work: in the table before the kernel adds to it
-                CK(weight_combine(W, l, w0, scales.data()));
+                CK(weight_combine(W, w0, scales.data()));
                 if (hipStreamSynchronize(S.stream) != hipSuccess) return PK_ERR_HIP;
             }
         }
@@ -331,7 +325,7 @@ struct Opening {
         if (l) {
             CK(pk_memcpy_h2d(ctx, d_pts, point.data(), 32 * (size_t)n));
             CK(pk_ctx_sync(ctx));
-            CK(weight_deferred(W, l, d_pts, d_part, scratch, d_out));
+            CK(weight_deferred(W, d_pts, d_part, scratch, d_out));
             if (hipStreamSynchronize(S.stream) != hipSuccess) return PK_ERR_HIP;
             CK(pk_memcpy_d2h(ctx, deferred.data() + q, d_out, 32 * (size_t)l));
         }
@@ -455,22 +449,34 @@ int pkw_commitment_destroy(pkw_commitment* com) {
 namespace pkw {
 namespace {
 
-// the opening every entry point makes once its arguments are checked; l = 0: pkw_open
-int open_checked(pkw_scheme* s, const pkw_commitment* com, const std::string& pattern, const uint64_t* points, unsigned q, const WeightSource& W,
-                 const uint64_t* tags, unsigned l, uint64_t* evals_out, uint64_t* sums_out, uint8_t* proof_out, size_t cap, size_t* len) {
-    pk::Transcript T(pattern);
-    std::vector<fe> evals((size_t)s->cfg.batch_size * q + 1), sums((size_t)s->cfg.batch_size * l + 1);
-    pkw::Opening op(*s, *com, T);
-    const int rc = op.run(reinterpret_cast<const fe*>(points), q, evals.data(), W, reinterpret_cast<const fe*>(tags), l, sums.data());
-    if (rc) return pkw::fail(s, rc, rc == PK_ERR_OOM ? "the arena is too small for this opening" : std::string("open: ") + pk_last_error(s->ctx));
-    if (!T.finished())
-        return pkw::fail(s, PK_ERR_IO_PATTERN, T.violation().empty() ? "the proof ended before its IO pattern did" : T.violation());
-    *len = T.narg.size();
-    if (cap < T.narg.size()) return pkw::fail(s, PK_ERR_BAD_ARG, "proof buffer too small: " + std::to_string(T.narg.size()) + " bytes needed");
-    memcpy(proof_out, T.narg.data(), T.narg.size());
-    if (evals_out) memcpy(evals_out, evals.data(), 32 * (size_t)s->cfg.batch_size * q);
-    if (sums_out) memcpy(sums_out, sums.data(), 32 * (size_t)s->cfg.batch_size * l);
+// What the three openings share once the entry's own count rule has passed.  open_refused: the pointers every opening needs and
+// the commitment's owner.  open_checked: the pattern, the opening, the proof into (proof_out, cap, *len)
+int open_refused(pkw_scheme* s, const pkw_commitment* com, const Statement& st, const uint8_t* proof_out, size_t cap, const size_t* len) {
+    if (!com || (st.q && !st.points) || (st.l && !st.tags) || !len || (cap && !proof_out)) return fail(s, PK_ERR_BAD_ARG, "null pointer");
+    if (com->scheme != s) return fail(s, PK_ERR_BAD_ARG, "the commitment belongs to another scheme");
     return PK_OK;
+}
+int open_checked(pkw_scheme* s, const pkw_commitment* com, const Statement& st, uint64_t* evals_out, uint64_t* sums_out, uint8_t* proof_out, size_t cap,
+                 size_t* len) {
+    try {
+        std::string& pattern = s->pattern_cache[st.q * (PKW_MAX_WEIGHTS + 1) + st.l];
+        if (pattern.empty()) pattern = io_pattern(s->cfg, st.q, st.l);
+        pk::Transcript T(pattern);
+        const size_t batch = s->cfg.batch_size;
+        std::vector<fe> evals(batch * st.q + 1), sums(batch * st.l + 1);
+        Opening op(*s, *com, T);
+        const int rc = op.run(st, evals.data(), sums.data());
+        if (rc) return fail(s, rc, rc == PK_ERR_OOM ? "the arena is too small for this opening" : std::string("open: ") + pk_last_error(s->ctx));
+        if (!T.finished()) return fail(s, PK_ERR_IO_PATTERN, T.violation().empty() ? "the proof ended before its IO pattern did" : T.violation());
+        *len = T.narg.size();
+        if (cap < T.narg.size()) return fail(s, PK_ERR_BAD_ARG, "proof buffer too small: " + std::to_string(T.narg.size()) + " bytes needed");
+        memcpy(proof_out, T.narg.data(), T.narg.size());
+        if (evals_out) memcpy(evals_out, evals.data(), 32 * batch * st.q);
+        if (sums_out) memcpy(sums_out, sums.data(), 32 * batch * st.l);
+        return PK_OK;
+    } catch (...) {
+        return fail(s, PK_ERR_OOM, "out of memory");
+    }
 }
 
 }  // namespace
@@ -481,15 +487,10 @@ extern "C" {
 int pkw_open(pkw_scheme* s, const pkw_commitment* com, const uint64_t* points, unsigned q, uint64_t* evals_out, uint8_t* proof_out, size_t cap,
              size_t* len) {
     if (!s) return PK_ERR_BAD_ARG;
-    if (!com || !points || !len || (cap && !proof_out)) return pkw::fail(s, PK_ERR_BAD_ARG, "null pointer");
-    if (com->scheme != s) return pkw::fail(s, PK_ERR_BAD_ARG, "the commitment belongs to another scheme");
     if (q < 1 || q > PKW_MAX_POINTS) return pkw::fail(s, PK_ERR_BAD_ARG, "the number of points must be 1..64");
-    try {
-        if (s->pattern_cache[q].empty()) s->pattern_cache[q] = pkw::io_pattern(s->cfg, q);
-        return pkw::open_checked(s, com, s->pattern_cache[q], points, q, pkw::WeightSource{}, nullptr, 0, evals_out, nullptr, proof_out, cap, len);
-    } catch (...) {
-        return pkw::fail(s, PK_ERR_OOM, "out of memory");
-    }
+    const pkw::Statement st{points, q};
+    if (int rc = pkw::open_refused(s, com, st, proof_out, cap, len)) return rc;
+    return pkw::open_checked(s, com, st, evals_out, nullptr, proof_out, cap, len);
 }
 
 }  // extern "C"
@@ -502,22 +503,17 @@ int open_linear(pkw_scheme* s, const pkw_commitment* com, const uint64_t* points
     if (!s) return PK_ERR_BAD_ARG;
     std::string why;
     if (!linear_counts_ok(q, l, why)) return fail(s, PK_ERR_BAD_ARG, why);
-    if (!com || (q && !points) || !d_weights || !tags || !len || (cap && !proof_out)) return fail(s, PK_ERR_BAD_ARG, "null pointer");
+    const Statement st{points, q, tags, l, d_weights};
+    if (int rc = open_refused(s, com, st, proof_out, cap, len)) return rc;
+    if (!d_weights) return fail(s, PK_ERR_BAD_ARG, "null pointer");
     for (unsigned i = 0; i < l; i++)
         if (!d_weights[i]) return fail(s, PK_ERR_BAD_ARG, "weight " + std::to_string(i) + " is a null pointer");
-    if (com->scheme != s) return fail(s, PK_ERR_BAD_ARG, "the commitment belongs to another scheme");
     // the scratch both kernels borrow, checked before any work: the sums' partials go where the evaluation's do, the deferred
     // evaluation's (EVAL_MAX_BATCH tables per launch) into the commit scratch
     const unsigned n = s->cfg.n_vars, batch = s->cfg.batch_size;
     if (wsum_partial_fes(batch, n) > eval_partial_fes(batch, n) || eval_partial_fes(EVAL_MAX_BATCH, n) > plan(s->cfg).scratch)
         return fail(s, PK_ERR_BAD_ARG, "this config's arena is too small for a linear opening");
-    try {
-        std::string& pattern = s->linear_pattern_cache[q * (PKW_MAX_WEIGHTS + 1) + l];
-        if (pattern.empty()) pattern = io_pattern(s->cfg, q, l);
-        return open_checked(s, com, pattern, points, q, WeightSource{d_weights, nullptr}, tags, l, evals_out, sums_out, proof_out, cap, len);
-    } catch (...) {
-        return fail(s, PK_ERR_OOM, "out of memory");
-    }
+    return open_checked(s, com, st, evals_out, sums_out, proof_out, cap, len);
 }
 
 // the entry point behind pkw_open_sparse (sparse_abi.cpp): pkw_open_linear's counts, pattern and bytes; the lists are validated
@@ -527,26 +523,25 @@ int open_sparse(pkw_scheme* s, const pkw_commitment* com, const uint64_t* points
     if (!s) return PK_ERR_BAD_ARG;
     std::string why;
     if (!linear_counts_ok(q, l, why)) return fail(s, PK_ERR_BAD_ARG, why);
-    if (!com || (q && !points) || !offsets || !tags || !len || (cap && !proof_out)) return fail(s, PK_ERR_BAD_ARG, "null pointer");
-    if (com->scheme != s) return fail(s, PK_ERR_BAD_ARG, "the commitment belongs to another scheme");
+    const SparseWeights w{offsets, d_index, d_value, l};
+    const Statement st{points, q, tags, l, nullptr, &w};
+    if (int rc = open_refused(s, com, st, proof_out, cap, len)) return rc;
+    if (!offsets) return fail(s, PK_ERR_BAD_ARG, "null pointer");
     const unsigned n = s->cfg.n_vars, batch = s->cfg.batch_size;
     if (!sparse_offsets_ok(offsets, l, n, why)) return fail(s, PK_ERR_BAD_ARG, why);
     if (offsets[l] && (!d_index || !d_value)) return fail(s, PK_ERR_BAD_ARG, "null index or value list");
     if (sparse_partial_fes(batch, n) > eval_partial_fes(batch, n)) return fail(s, PK_ERR_OOM, "this config's arena is too small for a sparse opening");
     try {
-        const SparseWeights w{offsets, d_index, d_value, l};
         size_t bad = 0;
         uint32_t at = 0, prev = 0;
         int rc = pk_ctx_sync(s->ctx);  // the lists are the context's work: there before the pass reads them
         if (!rc) rc = sparse_validate(s->ctx, s->stream, w, n, s->arena, &bad, &at, &prev);
         if (rc) return fail(s, rc, std::string("open: ") + pk_last_error(s->ctx));
         if (bad != ~(size_t)0) return fail(s, PK_ERR_BAD_ARG, sparse_index_reason(w, bad, at, prev, n));
-        std::string& pattern = s->linear_pattern_cache[q * (PKW_MAX_WEIGHTS + 1) + l];
-        if (pattern.empty()) pattern = io_pattern(s->cfg, q, l);
-        return open_checked(s, com, pattern, points, q, WeightSource{nullptr, &w}, tags, l, evals_out, sums_out, proof_out, cap, len);
     } catch (...) {
         return fail(s, PK_ERR_OOM, "out of memory");
     }
+    return open_checked(s, com, st, evals_out, sums_out, proof_out, cap, len);
 }
 
 }  // namespace pkw

@@ -1,6 +1,6 @@
-// pcs.hpp -- what the three sources of libprovekit_whir.so share: which configs the library takes, and the IO pattern of an opening
-// proof.  Host only.  The wire rules (sponge, hint framing, STIR indexes, PoW bytes) are protocol.hpp's; the verifier side of the
-// transcript and the WHIR walk are verify/core.hpp's.
+// pcs.hpp -- what the three sources of libprovekit_whir.so share: which configs the library takes, the IO pattern of an opening
+// proof, and the statement value every layer passes.  Host only.  The wire rules (sponge, hint framing, STIR indexes, PoW bytes) are
+// protocol.hpp's; the verifier side of the transcript and the WHIR walk are verify/core.hpp's.
 #pragma once
 #include <string>
 
@@ -128,6 +128,25 @@ inline Plan plan(const pk_whir_config& c) {
     p.total += round8((size_t)PKW_MAX_POINTS * n) + round8(eval_partial_fes(c.batch_size, n)) + round8((size_t)PKW_MAX_POINTS * c.batch_size);
     return p;
 }
+
+// ONE statement about the committed polynomials, as every layer between the C entry points and the transcript passes it: q points,
+// then l weights bound by the caller's tags (l = 0: the evaluation statement of pkw_open / pkw_verify).  The weights are dense tables
+// or index/value lists, never both -- device memory for an opening, host memory for a verification, where dense may also be null or
+// hold null entries: tables the verifier was not given
+struct SparseWeights;  // sparse.hpp
+struct Statement {
+    const uint64_t* points = nullptr;  // q * n_vars elements
+    unsigned q = 0;
+    const uint64_t* tags = nullptr;  // l elements
+    unsigned l = 0;
+    const uint64_t* const* dense = nullptr;
+    const SparseWeights* sparse = nullptr;
+};
+// what a verification hands back next to its verdict; every pointer may be null
+struct VerifyOutputs {
+    uint64_t *evals = nullptr, *sums = nullptr, *fold_point = nullptr, *deferred = nullptr;
+    unsigned* unchecked = nullptr;
+};
 
 // The linear statement's entry points (include/provekit_whir_linear.h says what they do).  They are C++ functions of this library;
 // their C names pkw_weighted_sums, pkw_io_pattern_linear, pkw_open_linear and pkw_verify_linear are exported by the companion

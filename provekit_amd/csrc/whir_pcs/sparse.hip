@@ -11,7 +11,7 @@
 // per polynomial (linear_tile.hpp's tile, B x 1; B <= 2, so three or four polynomials take two slices of the grid and load an
 // entry's index and value once per slice).  Workgroup x of weight y takes the entries x * 256 + lane of that weight, then
 // strides by the grid; a workgroup beyond its weight's entries still writes its partial, a zero.  One workgroup reduction per
-// (polynomial, weight), one partial per (polynomial, weight, workgroup) in eval_finish's layout, and evaluate.hip's finish kernel
+// (polynomial, weight), one partial per (polynomial, weight, workgroup) in rows of SPARSE_PASS, and evaluate.hip's finish kernel
 // adds them.
 //
 // Accumulation.  table[index[k]] += scale * value[k].  There are no 256-bit atomics, so the race is excluded by construction: ONE
@@ -26,6 +26,7 @@
 #include <algorithm>
 
 #include "block_sum.hpp"
+#include "blocking.hpp"
 #include "evaluate.hpp"
 #include "pcs.hpp"
 #include "sparse.hpp"
@@ -37,7 +38,6 @@ namespace pkw {
 namespace {
 
 constexpr unsigned THREADS = SPARSE_THREADS;
-static_assert(SPARSE_PASS == EVAL_PASS, "a pass's partials are laid out for eval_finish_launch");
 
 struct Spans {  // a launch's weights: where their entries start and how many they are
     unsigned long long begin[SPARSE_PASS], nnz[SPARSE_PASS];
@@ -173,9 +173,8 @@ int sparse_validate(pk_ctx* ctx, hipStream_t stream, const SparseWeights& w, uns
     if (!total) return PK_OK;
     Bounds b{};
     for (unsigned i = 0; i <= w.l; i++) b.at[i] = w.offsets[i];
-    const size_t blocks = (total + THREADS - 1) / THREADS;
     if (hipMemsetAsync(d_slot, 0xff, 8, stream) != hipSuccess) return PK_ERR_HIP;
-    sparse_validate_kernel<<<(unsigned)(blocks < 2048 ? blocks : 2048), THREADS, 0, stream>>>(w.index, b, w.l, n_vars, (unsigned long long*)d_slot);
+    sparse_validate_kernel<<<capped_grid(total), THREADS, 0, stream>>>(w.index, b, w.l, n_vars, (unsigned long long*)d_slot);
     if (hipGetLastError() != hipSuccess || hipStreamSynchronize(stream) != hipSuccess) return PK_ERR_HIP;
     uint64_t k = 0;
     int rc = pk_memcpy_d2h(ctx, &k, d_slot, 8);
@@ -203,7 +202,8 @@ int sparse_sums_launch(hipStream_t stream, const uint64_t* const* d_evals, unsig
             sparse_sums_kernel<1><<<dim3(g, L, 1), THREADS, 0, stream>>>(polys, batch, w.index, (const fe*)w.value, s, (fe*)d_partial);
         else
             sparse_sums_kernel<(int)SPARSE_TILE_B><<<dim3(g, L, (batch + SPARSE_TILE_B - 1) / SPARSE_TILE_B), THREADS, 0, stream>>>(polys, batch, w.index, (const fe*)w.value, s, (fe*)d_partial);
-        if (int rc = eval_finish_launch(stream, d_partial, g, batch, L, d_out + 4 * (size_t)i0, w.l)) return rc;
+        finish_launch(stream, d_partial, g, batch, L, SPARSE_PASS, d_out + 4 * (size_t)i0, w.l);
+        if (hipGetLastError() != hipSuccess) return PK_ERR_HIP;  // a failed pass ends the launch: nothing more is enqueued
     }
     return hipGetLastError() == hipSuccess ? PK_OK : PK_ERR_HIP;
 }
@@ -212,9 +212,8 @@ int sparse_accumulate_launch(hipStream_t stream, uint64_t* d_table, const Sparse
     for (unsigned i = 0; i < w.l; i++) {  // one launch per weight: see the head of this file
         const size_t nnz = w.nnz(i);
         if (!nnz) continue;
-        const size_t blocks = (nnz + THREADS - 1) / THREADS;
-        sparse_accumulate_kernel<<<(unsigned)(blocks < 2048 ? blocks : 2048), THREADS, 0, stream>>>((fe*)d_table, w.index + w.begin(i),
-                                                                                                 (const fe*)w.value + w.begin(i), nnz, h_load(scales + 4 * (size_t)i));
+        sparse_accumulate_kernel<<<capped_grid(nnz), THREADS, 0, stream>>>((fe*)d_table, w.index + w.begin(i), (const fe*)w.value + w.begin(i), nnz,
+                                                                           h_load(scales + 4 * (size_t)i));
     }
     return hipGetLastError() == hipSuccess ? PK_OK : PK_ERR_HIP;
 }
@@ -224,7 +223,8 @@ int sparse_evaluate_launch(hipStream_t stream, unsigned n_vars, const SparseWeig
         const unsigned L = w.l - i0 < SPARSE_PASS ? w.l - i0 : SPARSE_PASS;
         const unsigned g = sparse_grid(n_vars, max_nnz(w, i0, L), SPARSE_EVAL_STEPS);
         sparse_evaluate_kernel<<<dim3(g, L), THREADS, 0, stream>>>(w.index, (const fe*)w.value, spans(w, i0, L), (const fe*)d_point, n_vars, (fe*)d_partial);
-        if (int rc = eval_finish_launch(stream, d_partial, g, 1, L, d_out + 4 * (size_t)i0, w.l)) return rc;
+        finish_launch(stream, d_partial, g, 1, L, SPARSE_PASS, d_out + 4 * (size_t)i0, w.l);
+        if (hipGetLastError() != hipSuccess) return PK_ERR_HIP;  // a failed pass ends the launch: nothing more is enqueued
     }
     return hipGetLastError() == hipSuccess ? PK_OK : PK_ERR_HIP;
 }
@@ -233,16 +233,17 @@ int sparse_evaluate_launch(hipStream_t stream, unsigned n_vars, const SparseWeig
 
 namespace {
 
-// what the three share: the arguments' rule, then the validation pass on the null stream.  PK_OK with *empty set when there is
-// nothing to do
-int sparse_checked(pk_ctx* ctx, unsigned n_vars, const uint64_t* offsets, const uint32_t* d_index, const uint64_t* d_value, unsigned l, SparseWeights& w,
-                   uint64_t* d_slot) {
-    w = SparseWeights{offsets, d_index, d_value, l};
-    size_t bad = 0;
-    uint32_t at = 0, prev = 0;
-    if (int rc = sparse_validate(ctx, nullptr, w, n_vars, d_slot, &bad, &at, &prev)) return rc;
-    if (bad != ~(size_t)0) return refuse(sparse_index_reason(w, bad, at, prev, n_vars));
-    return PK_OK;
+// what the three share: the arguments' rule, and the validation pass followed by the entry's own launch, both on the null stream
+// and finished on return
+template <class Launch>
+int sparse_blocking(pk_ctx* ctx, const SparseWeights& w, unsigned n_vars, uint64_t* d_slot, Launch launch) {
+    return run_blocking(ctx, [&] {  // the operands are the context's work: finished before a kernel reads them
+        size_t bad = 0;
+        uint32_t at = 0, prev = 0;
+        if (int rc = sparse_validate(ctx, nullptr, w, n_vars, d_slot, &bad, &at, &prev)) return rc;
+        if (bad != ~(size_t)0) return refuse(sparse_index_reason(w, bad, at, prev, n_vars));
+        return launch();
+    });
 }
 int sparse_args(pk_ctx* ctx, unsigned n_vars, const uint64_t* offsets, const uint32_t* d_index, const uint64_t* d_value, unsigned l) {
     std::string why;
@@ -264,19 +265,12 @@ int sparse_sums(pk_ctx* ctx, const uint64_t* const* d_evals, unsigned batch, uns
         if (!d_evals[b]) return refuse("null polynomial");
     if (!l) return PK_OK;
     const size_t part = sparse_partial_fes(batch, n_vars), res = (size_t)batch * l;
-    void* d = nullptr;
-    int rc = pk_malloc(ctx, 32 * (part + res + 1), &d);
-    if (rc) return rc;
-    uint64_t* d_part = (uint64_t*)d;
-    uint64_t* d_res = d_part + 4 * part;
-    SparseWeights w;
-    rc = pk_ctx_sync(ctx);  // the operands are the context's work: finished before a kernel reads them
-    if (!rc) rc = sparse_checked(ctx, n_vars, offsets, d_index, d_value, l, w, d_res + 4 * res);
-    if (!rc) rc = sparse_sums_launch(nullptr, d_evals, batch, n_vars, w, d_part, d_res);
-    if (!rc && hipStreamSynchronize(nullptr) != hipSuccess) rc = PK_ERR_HIP;
-    if (!rc) rc = pk_memcpy_d2h(ctx, out, d_res, 32 * res);
-    pk_free(ctx, d);
-    return rc;
+    Scratch d(ctx, part + res + 1);
+    if (d.rc) return d.rc;
+    uint64_t *d_part = d.take(part), *d_res = d.take(res), *d_slot = d.take(1);
+    const SparseWeights w{offsets, d_index, d_value, l};
+    const int rc = sparse_blocking(ctx, w, n_vars, d_slot, [&] { return sparse_sums_launch(nullptr, d_evals, batch, n_vars, w, d_part, d_res); });
+    return rc ? rc : pk_memcpy_d2h(ctx, out, d_res, 32 * res);
 }
 
 int sparse_accumulate(pk_ctx* ctx, uint64_t* d_table, unsigned n_vars, const uint64_t* offsets, const uint32_t* d_index, const uint64_t* d_value, unsigned l,
@@ -286,16 +280,10 @@ int sparse_accumulate(pk_ctx* ctx, uint64_t* d_table, unsigned n_vars, const uin
     for (unsigned i = 0; i < l; i++)
         if (!below_p(h_load(scales + 4 * (size_t)i))) return refuse("scale " + std::to_string(i) + " is not below p");
     if (!l || !offsets[l]) return PK_OK;
-    void* d = nullptr;
-    int rc = pk_malloc(ctx, 32, &d);
-    if (rc) return rc;
-    SparseWeights w;
-    rc = pk_ctx_sync(ctx);
-    if (!rc) rc = sparse_checked(ctx, n_vars, offsets, d_index, d_value, l, w, (uint64_t*)d);
-    if (!rc) rc = sparse_accumulate_launch(nullptr, d_table, w, scales);
-    if (!rc && hipStreamSynchronize(nullptr) != hipSuccess) rc = PK_ERR_HIP;
-    pk_free(ctx, d);
-    return rc;
+    Scratch d(ctx, 1);
+    if (d.rc) return d.rc;
+    const SparseWeights w{offsets, d_index, d_value, l};
+    return sparse_blocking(ctx, w, n_vars, d.take(1), [&] { return sparse_accumulate_launch(nullptr, d_table, w, scales); });
 }
 
 int sparse_evaluate(pk_ctx* ctx, unsigned n_vars, const uint64_t* offsets, const uint32_t* d_index, const uint64_t* d_value, unsigned l, const uint64_t* point,
@@ -304,21 +292,14 @@ int sparse_evaluate(pk_ctx* ctx, unsigned n_vars, const uint64_t* offsets, const
     if ((n_vars && !point) || (l && !out)) return refuse("null pointer");
     if (!l) return PK_OK;
     const size_t part = sparse_partial_fes(1, n_vars), pts = n_vars ? n_vars : 1;
-    void* d = nullptr;
-    int rc = pk_malloc(ctx, 32 * (part + pts + l + 1), &d);
-    if (rc) return rc;
-    uint64_t* d_part = (uint64_t*)d;
-    uint64_t* d_pt = d_part + 4 * part;
-    uint64_t* d_res = d_pt + 4 * pts;
-    SparseWeights w;
-    if (n_vars) rc = pk_memcpy_h2d(ctx, d_pt, point, 32 * (size_t)n_vars);
-    if (!rc) rc = pk_ctx_sync(ctx);
-    if (!rc) rc = sparse_checked(ctx, n_vars, offsets, d_index, d_value, l, w, d_res + 4 * (size_t)l);
-    if (!rc) rc = sparse_evaluate_launch(nullptr, n_vars, w, d_pt, d_part, d_res);
-    if (!rc && hipStreamSynchronize(nullptr) != hipSuccess) rc = PK_ERR_HIP;
-    if (!rc) rc = pk_memcpy_d2h(ctx, out, d_res, 32 * (size_t)l);
-    pk_free(ctx, d);
-    return rc;
+    Scratch d(ctx, part + pts + l + 1);
+    if (d.rc) return d.rc;
+    uint64_t *d_part = d.take(part), *d_pt = d.take(pts), *d_res = d.take(l), *d_slot = d.take(1);
+    const SparseWeights w{offsets, d_index, d_value, l};
+    if (n_vars)
+        if (int rc = pk_memcpy_h2d(ctx, d_pt, point, 32 * (size_t)n_vars)) return rc;
+    const int rc = sparse_blocking(ctx, w, n_vars, d_slot, [&] { return sparse_evaluate_launch(nullptr, n_vars, w, d_pt, d_part, d_res); });
+    return rc ? rc : pk_memcpy_d2h(ctx, out, d_res, 32 * (size_t)l);
 }
 
 }  // namespace pkw

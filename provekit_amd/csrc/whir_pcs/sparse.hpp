@@ -30,7 +30,7 @@ struct SparseWeights {
 constexpr unsigned SPARSE_CHUNK_BITS = 8;  // eq(index, point) = one factor per chunk of 8 index bits: at most 4 tables of 2^8 entries
 constexpr unsigned SPARSE_MAX_CHUNKS = 4;  // n_vars <= 30
 constexpr unsigned SPARSE_THREADS = 256;   // lanes of a workgroup = entries it takes per step, in all of sparse.hip's kernels
-constexpr unsigned SPARSE_PASS = 8;        // weights per launch of the sums and the evaluation: their partials share eval_finish's layout
+constexpr unsigned SPARSE_PASS = 8;        // weights per launch of the sums and the evaluation: their partials lie in rows of it
 constexpr unsigned SPARSE_EVAL_STEPS = 8;  // steps a workgroup of the evaluation takes before the grid grows: its prologue builds the tables
 constexpr unsigned SPARSE_MAX_BATCH = WSUM_MAX_BATCH;
 constexpr unsigned SPARSE_TILE_B = 2;      // polynomials per lane of the sums kernel; more take further slices of the grid

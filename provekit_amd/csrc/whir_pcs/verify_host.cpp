@@ -22,10 +22,9 @@ const char* const kWalkNames[PKV_CHECK_COUNT] = {
 
 class PcsWalk : public pkv::Walk {
   public:
-    PcsWalk(const pkv::Statement& st, pkv::Backend& be, const uint8_t* proof, size_t len, pkv::Verdict& v, const pk_whir_config& cfg, const fe* points,
-            unsigned q, const fe* expected_root, const fe* tags = nullptr, const uint64_t* const* weights = nullptr, unsigned l = 0,
-            const SparseWeights* sparse = nullptr)
-        : Walk(st, be, proof, len, v), cfg_(cfg), points_(points), q_(q), expected_root_(expected_root), tags_(tags), weights_(weights), l_(l), sparse_(sparse) {}
+    PcsWalk(const pkv::Statement& st, pkv::Backend& be, const uint8_t* proof, size_t len, pkv::Verdict& v, const pk_whir_config& cfg, const Statement& s,
+            const fe* expected_root)
+        : Walk(st, be, proof, len, v), cfg_(cfg), s_(s), expected_root_(expected_root) {}
 
     std::vector<fe> evals;  // [polynomial][point], Montgomery: what the proof binds, once the walk got past them
     std::vector<fe> sums;   // [polynomial][weight], likewise
@@ -33,29 +32,31 @@ class PcsWalk : public pkv::Walk {
     unsigned unchecked = 0;                       // weights without a table: their deferred values are the caller's to check
 
     bool run_opening() {
-        const unsigned n = cfg_.n_vars, batch = cfg_.batch_size;
+        const unsigned n = cfg_.n_vars, batch = cfg_.batch_size, q = s_.q, l = s_.l;
+        const fe *points = reinterpret_cast<const fe*>(s_.points), *tags = reinterpret_cast<const fe*>(s_.tags);
+        const SparseWeights* sparse = s_.sparse;
         Commitment com;
         if (!parse_commitment(cfg_, com)) return false;
         if (expected_root_ && !pk::fe_eq(com.root, *expected_root_)) return A.fail(PKW_CHECK_ROOT, "the proof's root is not the expected commitment");
-        std::vector<fe> pts((size_t)q_ * n);
+        std::vector<fe> pts((size_t)q * n);
         if (!pts.empty() && !A.next_scalars(pts.size(), pts.data())) return false;
         for (size_t j = 0; j < pts.size(); j++)
-            if (!pk::fe_eq(pts[j], points_[j]))
+            if (!pk::fe_eq(pts[j], points[j]))
                 return A.fail(PKW_CHECK_POINTS, "point " + std::to_string(j / n) + " of the proof is not the caller's (coordinate " + std::to_string(j % n) + ")");
-        std::vector<fe> tg(l_);
-        if (l_ && !A.next_scalars(l_, tg.data())) return false;
-        for (unsigned i = 0; i < l_; i++)
-            if (!pk::fe_eq(tg[i], tags_[i])) return A.fail(PKW_CHECK_POINTS, "tag " + std::to_string(i) + " of the proof is not the caller's");
-        std::vector<fe> ev((size_t)batch * q_), sm((size_t)batch * l_);
+        std::vector<fe> tg(l);
+        if (l && !A.next_scalars(l, tg.data())) return false;
+        for (unsigned i = 0; i < l; i++)
+            if (!pk::fe_eq(tg[i], tags[i])) return A.fail(PKW_CHECK_POINTS, "tag " + std::to_string(i) + " of the proof is not the caller's");
+        std::vector<fe> ev((size_t)batch * q), sm((size_t)batch * l);
         if (!ev.empty() && !A.next_scalars(ev.size(), ev.data())) return false;
         evals = ev;
         if (!sm.empty() && !A.next_scalars(sm.size(), sm.data())) return false;
         sums = sm;
-        std::vector<fe> claims(q_ + l_);
-        for (unsigned i = 0; i < q_ + l_; i++) {  // the statement of the beta-combined polynomial: evaluations, then sums
+        std::vector<fe> claims(q + l);
+        for (unsigned i = 0; i < q + l; i++) {  // the statement of the beta-combined polynomial: evaluations, then sums
             fe acc = pkv::f_zero(), bp = pkv::f_one();
             for (unsigned b = 0; b < batch; b++) {
-                acc = pk::h_add(acc, pk::h_mul(bp, i < q_ ? ev[(size_t)b * q_ + i] : sm[(size_t)b * l_ + (i - q_)]));
+                acc = pk::h_add(acc, pk::h_mul(bp, i < q ? ev[(size_t)b * q + i] : sm[(size_t)b * l + (i - q)]));
                 bp = pk::h_mul(bp, com.beta);
             }
             claims[i] = acc;
@@ -64,28 +65,28 @@ class PcsWalk : public pkv::Walk {
         std::vector<pk::HintFe> deferred;
         if (!whir_verify(com, cfg_, claims, rev, deferred)) return false;
         fold_point = rev;
-        for (unsigned i = 0; i < l_; i++) weight_deferred.push_back(deferred[q_ + i].mont);
+        for (unsigned i = 0; i < l; i++) weight_deferred.push_back(deferred[q + i].mont);
         if (!A.done()) return A.fail(PKV_CHECK_TRAILING_BYTES, "trailing bytes after the proof");
-        for (unsigned i = 0; i < q_; i++)  // the MLE of eq(point_i, .) at the folding point
-            if (!relation(deferred[i].canonical && pk::fe_eq(deferred[i].mont, pkv::eq_poly(points_ + (size_t)i * n, rev.data(), n)), PKW_CHECK_DEFERRED,
+        for (unsigned i = 0; i < q; i++)  // the MLE of eq(point_i, .) at the folding point
+            if (!relation(deferred[i].canonical && pk::fe_eq(deferred[i].mont, pkv::eq_poly(points + (size_t)i * n, rev.data(), n)), PKW_CHECK_DEFERRED,
                           "deferred evaluation of weight " + std::to_string(i) + " is not eq(point, folding point)"))
                 return false;
-        const SparseEqTables eq(rev.data(), sparse_ ? n : 0);  // sparse weights: the chunks' eq tables at the folding point, once for all l
-        for (unsigned i = 0; i < l_; i++) {  // the MLE of a weight at the folding point: of the entries, or of a dense table the caller gave
-            const pk::HintFe& d = deferred[q_ + i];
+        const SparseEqTables eq(rev.data(), sparse ? n : 0);  // sparse weights: the chunks' eq tables at the folding point, once for all l
+        for (unsigned i = 0; i < l; i++) {  // the MLE of a weight at the folding point: of the entries, or of a dense table the caller gave
+            const pk::HintFe& d = deferred[q + i];
             if (!relation(d.canonical, PKW_CHECK_DEFERRED, "deferred evaluation of weight " + std::to_string(i) + " is not canonical")) return false;
-            if (sparse_) {
-                const size_t at = sparse_->begin(i);
-                if (!relation(pk::fe_eq(d.mont, eq.weight_at(sparse_->index + at, sparse_->value + 4 * at, sparse_->nnz(i))), PKW_CHECK_DEFERRED,
+            if (sparse) {
+                const size_t at = sparse->begin(i);
+                if (!relation(pk::fe_eq(d.mont, eq.weight_at(sparse->index + at, sparse->value + 4 * at, sparse->nnz(i))), PKW_CHECK_DEFERRED,
                               "deferred evaluation of weight " + std::to_string(i) + " is not the extension of the caller's entries at the folding point"))
                     return false;
                 continue;
             }
-            if (!weights_ || !weights_[i]) {
+            if (!s_.dense || !s_.dense[i]) {
                 unchecked++;
                 continue;
             }
-            if (!relation(pk::fe_eq(d.mont, table_at(weights_[i], rev)), PKW_CHECK_DEFERRED,
+            if (!relation(pk::fe_eq(d.mont, table_at(s_.dense[i], rev)), PKW_CHECK_DEFERRED,
                           "deferred evaluation of weight " + std::to_string(i) + " is not the extension of the caller's table at the folding point"))
                 return false;
         }
@@ -95,13 +96,8 @@ class PcsWalk : public pkv::Walk {
 
   private:
     const pk_whir_config& cfg_;
-    const fe* points_;
-    unsigned q_;
+    const Statement& s_;
     const fe* expected_root_;
-    const fe* tags_;
-    const uint64_t* const* weights_;
-    unsigned l_;
-    const SparseWeights* sparse_;
 
     // the multilinear extension of a dense table (2^n Montgomery elements, any 256-bit values) at `point`, variable 0 <-> the most
     // significant index bit: the first fold reads the caller's table, the rest work on the half-size copy
@@ -122,11 +118,9 @@ class PcsWalk : public pkv::Walk {
     }
 };
 
-// what pkw_verify, pkw_verify_linear and pkw_verify_sparse share once their counts are checked; l = 0: pkw_verify
+// what pkw_verify, pkw_verify_linear and pkw_verify_sparse share once their counts and pointers are checked; s.l = 0: pkw_verify
 int verify_checked(const pk_whir_config* cfg, const uint8_t* io_pattern, size_t io_pattern_len, int hash_version, const uint8_t* expected_root,
-                   const uint64_t* points, unsigned q, const uint64_t* tags, const uint64_t* const* weights, unsigned l, const uint8_t* proof, size_t len,
-                   uint64_t* evals_out, uint64_t* sums_out, uint64_t* fold_point_out, uint64_t* deferred_out, unsigned* unchecked_out, pkv_result* result,
-                   const SparseWeights* sparse = nullptr) {
+                   const Statement& s, const uint8_t* proof, size_t len, const VerifyOutputs& out, pkv_result* result) {
     std::string why;
     if (hash_version != 1 && hash_version != 2) return refuse("hash version must be 1 or 2");
     try {
@@ -136,7 +130,7 @@ int verify_checked(const pk_whir_config* cfg, const uint8_t* io_pattern, size_t 
         if (io_pattern && io_pattern_len)
             st.pattern.assign(reinterpret_cast<const char*>(io_pattern), io_pattern_len);
         else
-            st.pattern = pkw::io_pattern(*cfg, q, l);
+            st.pattern = pkw::io_pattern(*cfg, s.q, s.l);
         if (!pk::io_pattern_parse(st.pattern, st.ops, why)) {
             g_error = why;
             return PK_ERR_IO_PATTERN;
@@ -146,18 +140,29 @@ int verify_checked(const pk_whir_config* cfg, const uint8_t* io_pattern, size_t 
         if (expected_root) root = pk::load_raw(expected_root);
         pkv::Verdict verdict;
         pkv::HostBackend be;
-        PcsWalk walk(st, be, len ? proof : &none, len, verdict, *cfg, reinterpret_cast<const pk::fe*>(points), q, expected_root ? &root : nullptr,
-                     reinterpret_cast<const pk::fe*>(tags), weights, l, sparse);
+        PcsWalk walk(st, be, len ? proof : &none, len, verdict, *cfg, s, expected_root ? &root : nullptr);
         walk.run_opening();
         pkv::to_result(verdict, result);
-        auto give = [](uint64_t* out, const std::vector<fe>& v) {
-            if (out && !v.empty()) memcpy(out, v.data(), 32 * v.size());
+        auto give = [](uint64_t* to, const std::vector<fe>& v) {
+            if (to && !v.empty()) memcpy(to, v.data(), 32 * v.size());
         };
-        give(evals_out, walk.evals);
-        give(sums_out, walk.sums);
-        give(fold_point_out, walk.fold_point);
-        give(deferred_out, walk.weight_deferred);
-        if (unchecked_out) *unchecked_out = walk.unchecked;
+        give(out.evals, walk.evals);
+        give(out.sums, walk.sums);
+        give(out.fold_point, walk.fold_point);
+        give(out.deferred, walk.weight_deferred);
+        if (out.unchecked) *out.unchecked = walk.unchecked;
+        return PK_OK;
+    } catch (...) {
+        return PK_ERR_OOM;
+    }
+}
+
+// the pattern of a statement with q points and l weights into (buf, cap, *len): both pattern entry points, their counts checked
+int write_pattern(const pk_whir_config& cfg, unsigned q, unsigned l, uint8_t* buf, size_t cap, size_t* len) {
+    try {
+        const std::string d = io_pattern(cfg, q, l);
+        *len = d.size();
+        if (buf && cap >= d.size()) memcpy(buf, d.data(), d.size());
         return PK_OK;
     } catch (...) {
         return PK_ERR_OOM;
@@ -194,14 +199,7 @@ int pkw_io_pattern(const pk_whir_config* cfg, unsigned q, uint8_t* buf, size_t c
     if (!len) return pkw::refuse("null pointer");
     if (!pkw::config_ok(cfg, why)) return pkw::refuse(why);
     if (q < 1 || q > PKW_MAX_POINTS) return pkw::refuse("the number of points must be 1..64");
-    try {
-        const std::string d = pkw::io_pattern(*cfg, q);
-        *len = d.size();
-        if (buf && cap >= d.size()) memcpy(buf, d.data(), d.size());
-        return PK_OK;
-    } catch (...) {
-        return PK_ERR_OOM;
-    }
+    return pkw::write_pattern(*cfg, q, 0, buf, cap, len);
 }
 
 int pkw_verify(const pk_whir_config* cfg, const uint8_t* io_pattern, size_t io_pattern_len, int hash_version, const uint8_t* expected_root,
@@ -210,8 +208,8 @@ int pkw_verify(const pk_whir_config* cfg, const uint8_t* io_pattern, size_t io_p
     if (!result || !points || (len && !proof)) return pkw::refuse("null pointer");
     if (!pkw::config_ok(cfg, why)) return pkw::refuse(why);
     if (q < 1 || q > PKW_MAX_POINTS) return pkw::refuse("the number of points must be 1..64");
-    return pkw::verify_checked(cfg, io_pattern, io_pattern_len, hash_version, expected_root, points, q, nullptr, nullptr, 0, proof, len, evals_out, nullptr,
-                               nullptr, nullptr, nullptr, result);
+    return pkw::verify_checked(cfg, io_pattern, io_pattern_len, hash_version, expected_root, pkw::Statement{points, q}, proof, len,
+                               pkw::VerifyOutputs{evals_out}, result);
 }
 
 }  // extern "C"
@@ -223,14 +221,7 @@ int io_pattern_linear(const pk_whir_config* cfg, unsigned q, unsigned l, uint8_t
     std::string why;
     if (!len) return refuse("null pointer");
     if (!config_ok(cfg, why) || !linear_counts_ok(q, l, why)) return refuse(why);
-    try {
-        const std::string d = io_pattern(*cfg, q, l);
-        *len = d.size();
-        if (buf && cap >= d.size()) memcpy(buf, d.data(), d.size());
-        return PK_OK;
-    } catch (...) {
-        return PK_ERR_OOM;
-    }
+    return write_pattern(*cfg, q, l, buf, cap, len);
 }
 
 int verify_linear(const pk_whir_config* cfg, const uint8_t* io_pattern, size_t io_pattern_len, int hash_version, const uint8_t* expected_root,
@@ -240,8 +231,8 @@ int verify_linear(const pk_whir_config* cfg, const uint8_t* io_pattern, size_t i
     std::string why;
     if (!config_ok(cfg, why) || !linear_counts_ok(q, l, why)) return refuse(why);
     if (!result || (q && !points) || !tags || (len && !proof)) return refuse("null pointer");
-    return verify_checked(cfg, io_pattern, io_pattern_len, hash_version, expected_root, points, q, tags, weights, l, proof, len, evals_out, sums_out,
-                          fold_point_out, deferred_out, unchecked_out, result);
+    return verify_checked(cfg, io_pattern, io_pattern_len, hash_version, expected_root, Statement{points, q, tags, l, weights}, proof, len,
+                          VerifyOutputs{evals_out, sums_out, fold_point_out, deferred_out, unchecked_out}, result);
 }
 
 // the entry point behind pkw_verify_sparse (sparse_abi.cpp): pkw_verify_linear's walk over lists the host checks first, entry by entry
@@ -263,8 +254,8 @@ int verify_sparse(const pk_whir_config* cfg, const uint8_t* io_pattern, size_t i
             if (!below_p(pk::h_load(value + 4 * k)))
                 return refuse("weight " + std::to_string(i) + ", entry " + std::to_string(k - w.begin(i)) + ": the value is not below p");
         }
-    return verify_checked(cfg, io_pattern, io_pattern_len, hash_version, expected_root, points, q, tags, nullptr, l, proof, len, evals_out, sums_out,
-                          fold_point_out, deferred_out, nullptr, result, &w);
+    return verify_checked(cfg, io_pattern, io_pattern_len, hash_version, expected_root, Statement{points, q, tags, l, nullptr, &w}, proof, len,
+                          VerifyOutputs{evals_out, sums_out, fold_point_out, deferred_out}, result);
 }
 
 }  // namespace pkw

@@ -123,28 +123,26 @@ def low_vars() -> int:
     return int(lib.pkw_evaluate_low_vars())
 
 
-def io_pattern(cfg: WhirConfig, q: int) -> bytes:
-    """the spongefish operation list (domain separator) of a proof that opens q points (pkw_io_pattern; host only)"""
+def _io_pattern(fn, cfg: WhirConfig, *counts) -> bytes:
+    """a pattern entry point called twice: for the length, then into a buffer of that length"""
     c = _cfg_struct(cfg)
     n = sz()
-    rc = lib.pkw_io_pattern(C.addressof(c), q, None, 0, C.byref(n))
+    rc = fn(C.addressof(c), *counts, None, 0, C.byref(n))
     if rc:
         raise ProveKitHipError(rc, lib.pkw_create_error().decode())
     buf = (C.c_uint8 * n.value)()
-    lib.pkw_io_pattern(C.addressof(c), q, buf, n.value, C.byref(n))
+    fn(C.addressof(c), *counts, buf, n.value, C.byref(n))
     return bytes(buf)
+
+
+def io_pattern(cfg: WhirConfig, q: int) -> bytes:
+    """the spongefish operation list (domain separator) of a proof that opens q points (pkw_io_pattern; host only)"""
+    return _io_pattern(lib.pkw_io_pattern, cfg, q)
 
 
 def io_pattern_linear(cfg: WhirConfig, q: int, l: int) -> bytes:
     """the operation list of a proof that opens q points and l dense weights (pkw_io_pattern_linear; host only)"""
-    c = _cfg_struct(cfg)
-    n = sz()
-    rc = linear_lib.pkw_io_pattern_linear(C.addressof(c), q, l, None, 0, C.byref(n))
-    if rc:
-        raise ProveKitHipError(rc, lib.pkw_create_error().decode())
-    buf = (C.c_uint8 * n.value)()
-    linear_lib.pkw_io_pattern_linear(C.addressof(c), q, l, buf, n.value, C.byref(n))
-    return bytes(buf)
+    return _io_pattern(linear_lib.pkw_io_pattern_linear, cfg, q, l)
 
 
 def arena_bytes(cfg: WhirConfig) -> int:
@@ -182,23 +180,12 @@ class LinearResult:
         self.result, self.evals, self.sums, self.fold_point, self.deferred, self.unchecked = result, evals, sums, fold_point, deferred, unchecked
 
 
-def verify_linear(cfg: WhirConfig, points, tags, weights, proof: bytes, expected_root: bytes | None = None, io_pattern: bytes | None = None,
-                  hash_version: int = 2) -> LinearResult:
-    """Host only (pkw_verify_linear).  weights: None, or a list of l entries, each None or a HOST table [2^n_vars, 4] (Montgomery)"""
+def _verify(fn, cfg: WhirConfig, p: np.ndarray, statement: tuple, l: int, proof, expected_root, io_pattern, hash_version, outputs: int) -> LinearResult:
+    """One verification call: fn(config, pattern, hash version, root, points, q, *statement, proof, evaluations, ..., result).  statement:
+    what the entry point takes between q and the proof; outputs: how many of (sums, fold point, deferred, unchecked) it hands back"""
     c = _cfg_struct(cfg)
-    p = _points_or_none(points, cfg.n_vars)
-    t = _tags(tags)
-    q, l = p.shape[0], t.shape[0]
+    q = p.shape[0]
     proof = bytes(proof)
-    tables = None
-    if weights is not None:
-        if len(weights) != l:
-            raise ValueError("as many weights as tags")
-        keep = [None if w is None else np.ascontiguousarray(w, dtype=np.uint64) for w in weights]
-        for w in keep:
-            if w is not None and w.shape != (1 << cfg.n_vars, 4):
-                raise ValueError(f"a weight table has shape [{1 << cfg.n_vars}, 4]")
-        tables = (vp * max(l, 1))(*(None if w is None else w.ctypes.data for w in keep))
     evals = np.zeros((cfg.batch_size, q, 4), dtype=np.uint64)
     sums = np.zeros((cfg.batch_size, l, 4), dtype=np.uint64)
     fold = np.zeros((cfg.n_vars, 4), dtype=np.uint64)
@@ -209,12 +196,31 @@ def verify_linear(cfg: WhirConfig, points, tags, weights, proof: bytes, expected
     root = bytes(expected_root) if expected_root is not None else None
     if root is not None and len(root) != 32:
         raise ValueError("a root is 32 bytes")
-    rc = linear_lib.pkw_verify_linear(C.addressof(c), pat, len(pat) if pat else 0, hash_version, root, p.ctypes.data if q else None, q, t.ctypes.data,
-                               C.cast(tables, vp) if tables is not None else None, l, proof, len(proof), evals.ctypes.data if q else None,
-                               sums.ctypes.data, fold.ctypes.data, deferred.ctypes.data, C.byref(unchecked), C.byref(r))
+    outs = (sums.ctypes.data, fold.ctypes.data, deferred.ctypes.data, C.byref(unchecked))[:outputs]
+    rc = fn(C.addressof(c), pat, len(pat) if pat else 0, hash_version, root, p.ctypes.data if q else None, q, *statement, proof, len(proof),
+            evals.ctypes.data if q else None, *outs, C.byref(r))
     if rc:
         raise ProveKitHipError(rc, lib.pkw_create_error().decode())
     return LinearResult(_result(r), evals, sums, fold, deferred[:l], unchecked.value)
+
+
+def verify_linear(cfg: WhirConfig, points, tags, weights, proof: bytes, expected_root: bytes | None = None, io_pattern: bytes | None = None,
+                  hash_version: int = 2) -> LinearResult:
+    """Host only (pkw_verify_linear).  weights: None, or a list of l entries, each None or a HOST table [2^n_vars, 4] (Montgomery)"""
+    p = _points_or_none(points, cfg.n_vars)
+    t = _tags(tags)
+    l = t.shape[0]
+    tables = None
+    if weights is not None:
+        if len(weights) != l:
+            raise ValueError("as many weights as tags")
+        keep = [None if w is None else np.ascontiguousarray(w, dtype=np.uint64) for w in weights]
+        for w in keep:
+            if w is not None and w.shape != (1 << cfg.n_vars, 4):
+                raise ValueError(f"a weight table has shape [{1 << cfg.n_vars}, 4]")
+        tables = (vp * max(l, 1))(*(None if w is None else w.ctypes.data for w in keep))
+    statement = (t.ctypes.data, C.cast(tables, vp) if tables is not None else None, l)
+    return _verify(linear_lib.pkw_verify_linear, cfg, p, statement, l, proof, expected_root, io_pattern, hash_version, outputs=4)
 
 
 class SparseWeights:
@@ -292,46 +298,18 @@ def sparse_evaluate(ctx: Context, n_vars: int, weights: SparseWeights, point) ->
 def verify_sparse(cfg: WhirConfig, points, tags, weights: SparseWeights, proof: bytes, expected_root: bytes | None = None,
                   io_pattern: bytes | None = None, hash_version: int = 2) -> LinearResult:
     """Host only (pkw_verify_sparse): every weight's deferred relation is judged from its entries, so `unchecked` is always 0"""
-    c = _cfg_struct(cfg)
     p = _points_or_none(points, cfg.n_vars)
     t = _tags(tags)
-    q, l = p.shape[0], t.shape[0]
+    l = t.shape[0]
     if weights.l != l:
         raise ValueError("as many weights as tags")
-    proof = bytes(proof)
-    evals = np.zeros((cfg.batch_size, q, 4), dtype=np.uint64)
-    sums = np.zeros((cfg.batch_size, l, 4), dtype=np.uint64)
-    fold = np.zeros((cfg.n_vars, 4), dtype=np.uint64)
-    deferred = np.zeros((max(l, 1), 4), dtype=np.uint64)
-    r = ResultStruct()
-    pat = bytes(io_pattern) if io_pattern else None
-    root = bytes(expected_root) if expected_root is not None else None
-    if root is not None and len(root) != 32:
-        raise ValueError("a root is 32 bytes")
-    rc = sparse_lib.pkw_verify_sparse(C.addressof(c), pat, len(pat) if pat else 0, hash_version, root, p.ctypes.data if q else None, q, t.ctypes.data,
-                                      *weights._host(), l, proof, len(proof), evals.ctypes.data if q else None, sums.ctypes.data, fold.ctypes.data,
-                                      deferred.ctypes.data, C.byref(r))
-    if rc:
-        raise ProveKitHipError(rc, lib.pkw_create_error().decode())
-    return LinearResult(_result(r), evals, sums, fold, deferred[:l], 0)
+    return _verify(sparse_lib.pkw_verify_sparse, cfg, p, (t.ctypes.data, *weights._host(), l), l, proof, expected_root, io_pattern, hash_version, outputs=3)
 
 
 def verify(cfg: WhirConfig, points, proof: bytes, expected_root: bytes | None = None, io_pattern: bytes | None = None, hash_version: int = 2):
     """-> (Result, evaluations [batch, q, 4] Montgomery as the proof binds them).  Host only (pkw_verify)."""
-    c = _cfg_struct(cfg)
-    p = _points(points, cfg.n_vars)
-    proof = bytes(proof)
-    evals = np.zeros((cfg.batch_size, p.shape[0], 4), dtype=np.uint64)
-    r = ResultStruct()
-    pat = bytes(io_pattern) if io_pattern else None
-    root = bytes(expected_root) if expected_root is not None else None
-    if root is not None and len(root) != 32:
-        raise ValueError("a root is 32 bytes")
-    rc = lib.pkw_verify(C.addressof(c), pat, len(pat) if pat else 0, hash_version, root, p.ctypes.data, p.shape[0], proof, len(proof),
-                        evals.ctypes.data, C.byref(r))
-    if rc:
-        raise ProveKitHipError(rc, lib.pkw_create_error().decode())
-    return _result(r), evals
+    v = _verify(lib.pkw_verify, cfg, _points(points, cfg.n_vars), (), 0, proof, expected_root, io_pattern, hash_version, outputs=0)
+    return v.result, v.evals
 
 
 class Commitment:
@@ -383,10 +361,13 @@ class Scheme:
         self._check(lib.pkw_commit(self.handle, C.cast(_ptr_array(d_evals), vp), C.byref(h)))
         return Commitment(self, h.value)
 
-    def open(self, commitment: Commitment, points, cap: int | None = None):
-        """-> (evaluations [batch, q, 4] Montgomery, proof bytes)"""
-        p = _points(points, self.cfg.n_vars)
-        evals = np.zeros((self.cfg.batch_size, p.shape[0], 4), dtype=np.uint64)
+    def _open(self, fn, commitment: Commitment, p: np.ndarray, statement, l: int, cap):
+        """One opening call: fn(scheme, commitment, points, q, *statement, evaluations[, sums], proof buffer, cap, length).  statement: what
+        the entry point takes between q and the outputs, None for pkw_open, which has no sums either.  Without `cap` the proof goes
+        into a buffer of 8 MiB the scheme keeps"""
+        q = p.shape[0]
+        evals = np.zeros((self.cfg.batch_size, q, 4), dtype=np.uint64)
+        sums = np.zeros((self.cfg.batch_size, max(l, 1), 4), dtype=np.uint64)
         if cap is None:
             if self._buf is None:
                 self._buf = (C.c_uint8 * (8 << 20))()
@@ -394,52 +375,36 @@ class Scheme:
         else:
             buf = (C.c_uint8 * max(cap, 1))()
         n = sz()
-        self._check(lib.pkw_open(self.handle, commitment.handle, p.ctypes.data, p.shape[0], evals.ctypes.data, buf, len(buf) if cap is None else cap,
-                                 C.byref(n)))
-        return evals, C.string_at(buf, n.value)
+        outs = (evals.ctypes.data if q else None,) + (() if statement is None else (sums.ctypes.data,))
+        self._check(fn(self.handle, commitment.handle, p.ctypes.data if q else None, q, *(statement or ()), *outs, buf, len(buf) if cap is None else cap,
+                       C.byref(n)))
+        return evals, sums[:l], C.string_at(buf, n.value)
+
+    def open(self, commitment: Commitment, points, cap: int | None = None):
+        """-> (evaluations [batch, q, 4] Montgomery, proof bytes)"""
+        evals, _, proof = self._open(lib.pkw_open, commitment, _points(points, self.cfg.n_vars), None, 0, cap)
+        return evals, proof
 
     def open_linear(self, commitment: Commitment, points, d_weights, tags, cap: int | None = None):
         """open at q >= 0 points and l >= 1 dense weights (device buffers of 2^n_vars elements) bound by `tags` [l, 4]
         -> (evaluations [batch, q, 4], sums [batch, l, 4], proof bytes)"""
         p = _points_or_none(points, self.cfg.n_vars)
         t = _tags(tags)
-        q, l = p.shape[0], t.shape[0]
+        l = t.shape[0]
         if len(d_weights) != l:
             raise ValueError("as many weights as tags")
-        evals = np.zeros((self.cfg.batch_size, q, 4), dtype=np.uint64)
-        sums = np.zeros((self.cfg.batch_size, max(l, 1), 4), dtype=np.uint64)
-        if cap is None:
-            if self._buf is None:
-                self._buf = (C.c_uint8 * (8 << 20))()
-            buf = self._buf
-        else:
-            buf = (C.c_uint8 * max(cap, 1))()
-        n = sz()
-        self._check(linear_lib.pkw_open_linear(self.handle, commitment.handle, p.ctypes.data if q else None, q, C.cast(_ptr_array(d_weights), vp) if l else None,
-                                        t.ctypes.data, l, evals.ctypes.data if q else None, sums.ctypes.data, buf, len(buf) if cap is None else cap,
-                                        C.byref(n)))
-        return evals, sums[:l], C.string_at(buf, n.value)
+        statement = (C.cast(_ptr_array(d_weights), vp) if l else None, t.ctypes.data, l)
+        return self._open(linear_lib.pkw_open_linear, commitment, p, statement, l, cap)
 
     def open_sparse(self, commitment: Commitment, points, weights: SparseWeights, tags, cap: int | None = None):
         """open_linear with the l weights as uploaded index/value lists: the same statement, the same bytes (pkw_open_sparse)
         -> (evaluations [batch, q, 4], sums [batch, l, 4], proof bytes)"""
         p = _points_or_none(points, self.cfg.n_vars)
         t = _tags(tags)
-        q, l = p.shape[0], t.shape[0]
+        l = t.shape[0]
         if weights.l != l:
             raise ValueError("as many weights as tags")
-        evals = np.zeros((self.cfg.batch_size, q, 4), dtype=np.uint64)
-        sums = np.zeros((self.cfg.batch_size, max(l, 1), 4), dtype=np.uint64)
-        if cap is None:
-            if self._buf is None:
-                self._buf = (C.c_uint8 * (8 << 20))()
-            buf = self._buf
-        else:
-            buf = (C.c_uint8 * max(cap, 1))()
-        n = sz()
-        self._check(sparse_lib.pkw_open_sparse(self.handle, commitment.handle, p.ctypes.data if q else None, q, *weights._device(), t.ctypes.data, l,
-                                               evals.ctypes.data if q else None, sums.ctypes.data, buf, len(buf) if cap is None else cap, C.byref(n)))
-        return evals, sums[:l], C.string_at(buf, n.value)
+        return self._open(sparse_lib.pkw_open_sparse, commitment, p, (*weights._device(), t.ctypes.data, l), l, cap)
 
     def close(self):
         if self.handle is not None and self.ctx.handle is not None:

@@ -15,16 +15,9 @@ sys.path[:0] = [os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests")]
 DEMO = os.path.join(ROOT, "examples", "pcs_demo")
 
 import whir_pcs_cases as K  # noqa: E402
+from whir_pcs_cases import resolve_n  # noqa: E402
 
 MAX_Q = 9  # 9 points force the second pass over the polynomial
-
-
-def resolve_n(label):
-    from provekit_amd import whir_pcs
-
-    b = whir_pcs.low_vars()
-    assert b == 8  # the sizes below straddle it; a library with another tile needs another look at them
-    return {"1": 1, "4": 4, "b-1": b - 1, "b": b, "b+1": b + 1, "13": 13}[label]
 
 
 @functools.lru_cache(maxsize=None)
@@ -100,9 +93,11 @@ def test_evaluate_with_a_full_second_and_a_third_pass_over_the_points(ctx, oracl
     check_wide(ctx, oracle, resolve_n("b-1"), batch, q)
 
 
-@pytest.mark.parametrize("n,tiles", [(18, 2), (20, 8)])
+@pytest.mark.parametrize("n,tiles", [(17, 1), (18, 2), (20, 8)])
 def test_evaluate_with_several_tiles_per_workgroup(ctx, oracle, n, tiles):
     """from 2^18 a workgroup streams more than one tile, four at a time: 2 tiles leave a group half empty, 8 make two groups.
+    2^17 is the smallest size with 512 workgroups (one tile each): the nine points are a pass of eight and a pass of ONE, whose
+    single output the finish kernel sums from rows of EVAL_PASS = 8 with every lane making a second trip.
     Reference: the C oracle's eq table and dot product (mle_eval_table would take minutes here)."""
     from provekit_amd import whir_pcs
     from provekit_amd.field import random_field

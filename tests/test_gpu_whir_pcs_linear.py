@@ -16,28 +16,11 @@ sys.path[:0] = [os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests"), os.pa
 DEMO = os.path.join(ROOT, "examples", "pcs_linear_demo")
 
 import whir_pcs_cases as K  # noqa: E402
+from whir_pcs_cases import low_vars, ptrs, resolve_n  # noqa: E402
 import whir_pcs_linear_cases as L  # noqa: E402
 
 T_WS = (2, 4)  # the weight extents of the kernel's register tiles: 2 x 2, and 1 x 4 for a single polynomial (csrc/whir_pcs/linear.hpp)
 MAX_L = 17  # two full passes of eight weights and a third pass of one
-
-
-def low_vars():
-    """log2 of the elements one workgroup covers per step: the grid has one workgroup up to there, two above"""
-    import pk_probes
-
-    b = next(n for n in range(1, 31) if pk_probes.lib.pk_probe_whir_wsum_grid(n) == 2) - 1
-    assert b == 8  # the sizes below straddle it; a library with another step needs another look at them
-    return b
-
-
-def resolve_n(label):
-    b = low_vars()
-    return {"0": 0, "1": 1, "4": 4, "b-1": b - 1, "b": b, "b+1": b + 1, "13": 13}[label]
-
-
-def ptrs(bufs):
-    return C.cast((C.c_void_p * len(bufs))(*(b.ptr for b in bufs)), C.c_void_p)
 
 
 @functools.lru_cache(maxsize=None)
@@ -96,22 +79,39 @@ def test_weighted_sums_of_all_p_minus_1_at_every_phase_of_a_reduction_group(ctx,
         x.free()
 
 
-def test_weighted_sums_do_not_depend_on_the_grid_or_the_tile(ctx, oracle):
+@functools.lru_cache(maxsize=None)
+def finish_case(n):
+    """n_vars = 17, the smallest size whose grid reaches 512 workgroups: three polynomials and eight weights (one full pass) with
+    their Python-int inner products, computed once"""
+    polys = [K.many_ints(1 << n, 20 + b) for b in range(3)]
+    weights = [K.many_ints(1 << n, 30 + i) for i in range(8)]
+    return polys, weights, L.expected_sums(polys, weights)
+
+
+GRIDS_13 = ((1, 0), (5, 0), (31, 0), (32, 1), (7, 1), (32, 2), (3, 2), (32, 3), (9, 3))
+# the finish kernel sums 1, 2, 256 (one partial per lane), 257 (one lane makes a second trip) and 512 (all do) partials per output
+GRIDS_17 = ((1, 0), (2, 0), (256, 0), (257, 0), (512, 0), (257, 1), (257, 3))
+
+
+# l = 5: rows of five partial sums, fewer than a pass; l = 8: a full pass
+@pytest.mark.parametrize("n,l,full,grids", [(13, 5, 32, GRIDS_13), (17, 5, 512, GRIDS_17), (17, 8, 512, GRIDS_17)],
+                         ids=["13-l5", "17-l5", "17-l8"])
+def test_weighted_sums_do_not_depend_on_the_grid_or_the_tile(ctx, oracle, n, l, full, grids):
     import pk_probes
     from provekit_amd import whir_pcs
 
-    n = 13
-    polys, weights, want = sums_case(n)
+    polys, weights, want = sums_case(n) if n == 13 else finish_case(n)
     f = [ctx.upload(L.mont(oracle, p)) for p in polys[:3]]
-    w = [ctx.upload(L.mont(oracle, x)) for x in weights[:5]]
+    w = [ctx.upload(L.mont(oracle, x)) for x in weights[:l]]
     ref = whir_pcs.weighted_sums(ctx, f, n, w)
-    assert pk_probes.lib.pk_probe_whir_wsum_grid(n) == 32
-    for grid, tile in ((1, 0), (5, 0), (31, 0), (32, 1), (7, 1), (32, 2), (3, 2), (32, 3), (9, 3)):
+    assert oracle.limbs_to_ints(oracle.from_mont(ref.reshape(-1, 4))) == [want[b][i] for b in range(3) for i in range(l)]
+    assert pk_probes.lib.pk_probe_whir_wsum_grid(n) == full
+    for grid, tile in grids:
         out = np.zeros_like(ref)
-        ctx._check(pk_probes.lib.pk_probe_whir_weighted_sums(ctx.handle, ptrs(f), 3, n, ptrs(w), 5, grid, tile, out.ctypes.data))
+        ctx._check(pk_probes.lib.pk_probe_whir_weighted_sums(ctx.handle, ptrs(f), 3, n, ptrs(w), l, grid, tile, out.ctypes.data))
         assert np.array_equal(out, ref), (grid, tile)
     out = np.zeros_like(ref)
-    assert pk_probes.lib.pk_probe_whir_weighted_sums(ctx.handle, ptrs(f), 3, n, ptrs(w), 5, 33, 0, out.ctypes.data) == -1  # beyond the scratch
+    assert pk_probes.lib.pk_probe_whir_weighted_sums(ctx.handle, ptrs(f), 3, n, ptrs(w), l, full + 1, 0, out.ctypes.data) == -1  # beyond the scratch
     assert whir_pcs.linear_lib.pkw_weighted_sums(ctx.handle, ptrs(f), 3, n, ptrs(w), 0, out.ctypes.data) == -1  # l = 0
     assert np.array_equal(whir_pcs.weighted_sums(ctx, f, n, w), ref)
     for x in f + w:

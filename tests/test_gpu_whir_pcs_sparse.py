@@ -2,7 +2,6 @@
 against their dense twins on the densified tables and against Python ints, at the sizes at which the kernels take another path;
 the validation pass's refusals from every entry point (nothing is gathered or scattered through a bad index: no fault is provoked);
 pkw_open_sparse's bytes against pkw_open_linear's on the densified tables and against the oracle's transcript; examples/pcs_sparse_demo."""
-import ctypes as C
 import functools
 import os
 import re
@@ -18,6 +17,7 @@ sys.path[:0] = [os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests"), os.pa
 DEMO = os.path.join(ROOT, "examples", "pcs_sparse_demo")
 
 import whir_pcs_cases as K  # noqa: E402
+from whir_pcs_cases import ptrs  # noqa: E402
 import whir_pcs_linear_cases as L  # noqa: E402
 import whir_pcs_sparse_cases as S  # noqa: E402
 
@@ -31,10 +31,6 @@ def step():
     w = pk_probes.lib.pk_probe_whir_sparse_threads()
     assert w == 256  # the lengths below straddle it
     return w
-
-
-def ptrs(bufs):
-    return C.cast((C.c_void_p * len(bufs))(*(b.ptr for b in bufs)), C.c_void_p)
 
 
 def ints(oracle, limbs):
@@ -79,29 +75,51 @@ def test_sparse_sums_equal_the_dense_sums_and_python_ints(ctx, oracle, n):
         x.free()
 
 
-def test_sparse_sums_with_a_stride_loop_on_any_grid(ctx, oracle):
-    """a weight longer than its grid's extent: G workgroups of W lanes and G W - 1, G W, G W + 1 and 2 G W + 1 entries, on a small grid
-    handed to the launch through the probe (the library's own grid reaches this only at a large size); the bits do not depend on
-    the grid"""
-    import pk_probes
-    from provekit_amd import whir_pcs
+@functools.lru_cache(maxsize=None)
+def finish_case():
+    """n_vars = 17, the smallest size whose grid reaches 512 workgroups: three polynomials, a weight with an entry at every position
+    (every workgroup of every grid has one), a weight of 256 W + 1 entries (on a grid of 257 the last workgroup takes exactly one; on
+    512 the workgroups beyond it write zero partials) and an empty one, with their Python-int sums, computed once"""
+    n, W = 17, step()
+    polys = [K.many_ints(1 << n, 50 + b) for b in range(3)]
+    some = sorted(int(x) for x in np.random.default_rng(9).choice(1 << n, size=256 * W + 1, replace=False))
+    ws = [(list(range(1 << n)), K.many_ints(1 << n, 60)), (some, K.many_ints(len(some), 61)), ([], [])]
+    return n, polys, ws, S.sums(polys, ws)
 
+
+def stride_case():
+    """G workgroups of W lanes and G W - 1, G W, G W + 1 and 2 G W + 1 entries, on small grids"""
     n, W, G = 13, step(), 2
     polys = K.polynomials(n, 3, seed=5)
     ws = [S.random_weight(n, nnz, 40 + nnz) for nnz in (G * W - 1, G * W, G * W + 1, 2 * G * W + 1, 0, 1)]
-    want = [x for row in S.sums(polys, ws) for x in row]
+    return n, polys, ws, S.sums(polys, ws)
+
+
+# (the case, the library's own grid for its longest weight, wsum_grid(n), the grids handed to the probe)
+@pytest.mark.parametrize("case,own,full,grids", [(stride_case, 5, 32, (2, 1, 3, 32)), (finish_case, 512, 512, (1, 2, 256, 257, 512))],
+                         ids=["stride loop", "finish kernel"])
+def test_sparse_sums_with_a_stride_loop_on_any_grid(ctx, oracle, case, own, full, grids):
+    """a weight longer than its grid's extent, on a small grid handed to the launch through the probe (the library's own grid
+    reaches this only at a large size); the bits do not depend on the grid.  The second case is the finish kernel's: rows of
+    SPARSE_PASS = 8 partial sums of which three are used, summed over 1, 2, 256 (one partial per lane), 257 (one lane makes a
+    second trip) and 512 (all do) workgroups"""
+    import pk_probes
+    from provekit_amd import whir_pcs
+
+    n, polys, ws, sums = case()
+    want = [x for row in sums for x in row]
     f = [ctx.upload(L.mont(oracle, p)) for p in polys]
     sw = S.pack(oracle, ws).upload(ctx)
-    assert pk_probes.lib.pk_probe_whir_sparse_grid(n, 2 * G * W + 1, 1) == 5 and pk_probes.lib.pk_probe_whir_wsum_grid(n) == 32
+    assert pk_probes.lib.pk_probe_whir_sparse_grid(n, max(len(idx) for idx, _ in ws), 1) == own and pk_probes.lib.pk_probe_whir_wsum_grid(n) == full
     ref = whir_pcs.sparse_sums(ctx, f, n, sw)
     assert ints(oracle, ref) == want
-    for grid in (G, 1, 3, 32):
+    for grid in grids:
         out = np.zeros_like(ref)
         ctx._check(pk_probes.lib.pk_probe_whir_sparse_sums(ctx.handle, ptrs(f), 3, n, sw.offsets.ctypes.data, sw.d_index.ptr, sw.d_value.ptr, sw.l, grid,
                                                            out.ctypes.data))
         assert np.array_equal(out, ref), grid
     out = np.zeros_like(ref)
-    assert pk_probes.lib.pk_probe_whir_sparse_sums(ctx.handle, ptrs(f), 3, n, sw.offsets.ctypes.data, sw.d_index.ptr, sw.d_value.ptr, sw.l, 33,
+    assert pk_probes.lib.pk_probe_whir_sparse_sums(ctx.handle, ptrs(f), 3, n, sw.offsets.ctypes.data, sw.d_index.ptr, sw.d_value.ptr, sw.l, full + 1,
                                                    out.ctypes.data) == -1  # beyond the scratch
     for x in f + [sw]:
         x.free()

@@ -1,5 +1,6 @@
-"""Shared by test_whir_pcs_host.py and test_gpu_whir_pcs.py: small WHIR configs, deterministic polynomials and points, and an
-opening proof built on the CPU from the oracle prover's parts (oracle/prover_ref.py, imported, not edited)."""
+"""Shared by test_whir_pcs_host.py and test_gpu_whir_pcs*.py: small WHIR configs, deterministic polynomials and points, an
+opening proof built on the CPU from the oracle prover's parts (oracle/prover_ref.py, imported, not edited), and the device tests'
+size labels and pointer arrays."""
 import os
 import struct
 import sys
@@ -7,7 +8,9 @@ import sys
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests")]
+sys.path[:0] = [os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests"), os.path.join(ROOT, "tools")]
+
+from whir_pcs_helpers import ptrs  # noqa: E402,F401  (tools/: one definition for the bench tools and the device tests)
 
 P = 21888242871839275222246405745257275088548364400416034343698204186575808495617
 # (n_vars, batch, q): n_vars = 8 is fold 4 with one WHIR round, 12 has two; the sizes the CPU suite's other provers use
@@ -35,6 +38,12 @@ def vcfg(c):
 def random_ints(n, seed):
     rng = np.random.default_rng(seed)
     return [int.from_bytes(rng.bytes(40), "little") % P for _ in range(n)]
+
+
+def many_ints(n, seed):
+    """random_ints for large n: one draw of 40 n bytes cut into n values (other values than random_ints gives for the seed)"""
+    raw = np.random.default_rng(seed).bytes(40 * n)
+    return [int.from_bytes(raw[40 * i : 40 * i + 40], "little") % P for i in range(n)]
 
 
 def polynomials(n_vars, batch, seed=3):
@@ -103,6 +112,24 @@ def oracle_opening(oracle, cfg, polys, pts, pattern, hash_version=2, weight_poin
         PR.commit = saved
     assert T.finished(), "the proof ended before its IO pattern did"
     return bytes(T.out), com.tree[1][1].tobytes(), vals
+
+
+# ---- what the device tests of the three statement forms share (test_gpu_whir_pcs*.py) ---------------------------------------------------
+def low_vars():
+    """log2 of the elements one workgroup covers per step, in the evaluation (its tile) and in the weighted sums (the grid has one
+    workgroup up to there, two above)"""
+    import pk_probes
+    from provekit_amd import whir_pcs
+
+    b = next(n for n in range(1, 31) if pk_probes.lib.pk_probe_whir_wsum_grid(n) == 2) - 1
+    assert b == whir_pcs.low_vars() == 8  # the tests' sizes straddle it; a library with another tile or step needs another look at them
+    return b
+
+
+def resolve_n(label):
+    """a size label of a parametrised test -> n_vars"""
+    b = low_vars()
+    return {"0": 0, "1": 1, "4": 4, "b-1": b - 1, "b": b, "b+1": b + 1, "13": 13}[label]
 
 
 def deferred_offset(proof, q):

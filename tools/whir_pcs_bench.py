@@ -8,28 +8,17 @@ Every figure is host wall time of the blocking call (median of --reps after one 
 evaluation's achieved bandwidth counts the bytes the kernel must read: batch * 2^n * 32 * ceil(q / 8).  Without a GPU the file is
 written with null rates and says so."""
 import argparse
-import ctypes as C
 import json
 import os
-import statistics
 import sys
-import time
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tools")]
 ACHIEVABLE_GBPS = 6300.0  # what the project takes as achievable HBM bandwidth on MI355X
 
-
-def timed(fn, reps):
-    fn()
-    t = []
-    for _ in range(reps):
-        t0 = time.perf_counter()
-        fn()
-        t.append(time.perf_counter() - t0)
-    return statistics.median(t), min(t)
+from whir_pcs_helpers import timed  # noqa: E402
 
 
 def main():

@@ -16,12 +16,9 @@ the shipped tile T_b x T_w must read, 32 * 2^n * (batch * ceil(l / T_w) + l * ce
 achievable HBM bandwidth and 81 * 2^n * batch * l multiply-adds over the measured v_mad_u64_u32 rate
 (profiles/r03_ubench_valu_rates.txt).  Without a GPU the result's shape is printed with null figures and no file is written."""
 import argparse
-import ctypes as C
 import json
 import os
-import statistics
 import sys
-import time
 
 import numpy as np
 
@@ -31,27 +28,11 @@ ACHIEVABLE_GBPS = 6300.0  # what the project takes as achievable HBM bandwidth o
 MAD_PER_S = 27.9e12       # v_mad_u64_u32 lane-operations per second, 4 waves per SIMD (profiles/r03_ubench_valu_rates.txt)
 SHAPES = [(batch, l) for batch in (1, 2) for l in (1, 4, 16)]
 
-
-def ab(sides, reps):
-    """sides: {name: callable}; warm each once, then time them alternating -> {name: {median_ms, min_ms, spread}}"""
-    for fn in sides.values():
-        fn()
-    t = {k: [] for k in sides}
-    for _ in range(reps):
-        for k, fn in sides.items():
-            t0 = time.perf_counter()
-            fn()
-            t[k].append(time.perf_counter() - t0)
-    return {k: {"median_ms": round(1e3 * statistics.median(v), 4), "min_ms": round(1e3 * min(v), 4),
-                "spread": round((max(v) - min(v)) / statistics.median(v), 3)} for k, v in t.items()}
+from whir_pcs_helpers import ab, ptrs  # noqa: E402
 
 
 def not_slower(fused, public):
     return fused["median_ms"] <= public["median_ms"] * (1 + max(fused["spread"], public["spread"]))
-
-
-def ptrs(bufs):
-    return C.cast((C.c_void_p * len(bufs))(*(b.ptr for b in bufs)), C.c_void_p)
 
 
 def main():

@@ -18,12 +18,9 @@ copy the result back; the dense ones allocate, launch and copy); each side's spr
 outputs of the two routes are compared bit for bit before anything is timed.  Without a GPU the result's shape is printed with null
 figures and no file is written."""
 import argparse
-import ctypes as C
 import json
 import os
-import statistics
 import sys
-import time
 
 import numpy as np
 
@@ -32,23 +29,7 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "tools")]
 L_WEIGHTS = 4
 OPS = ("sums", "accumulation", "evaluation", "opening", "verification")
 
-
-def ab(sides, reps):
-    """sides: {name: callable}; warm each once, then time them alternating -> {name: {median_ms, min_ms, spread}}"""
-    for fn in sides.values():
-        fn()
-    t = {k: [] for k in sides}
-    for _ in range(reps):
-        for k, fn in sides.items():
-            t0 = time.perf_counter()
-            fn()
-            t[k].append(time.perf_counter() - t0)
-    return {k: {"median_ms": round(1e3 * statistics.median(v), 4), "min_ms": round(1e3 * min(v), 4),
-                "spread": round((max(v) - min(v)) / statistics.median(v), 3)} for k, v in t.items()}
-
-
-def ptrs(bufs):
-    return C.cast((C.c_void_p * len(bufs))(*(b.ptr for b in bufs)), C.c_void_p)
+from whir_pcs_helpers import ab, ptrs  # noqa: E402
 
 
 def densities(n):
