@@ -86,7 +86,9 @@ unsigned pkw_evaluate_low_vars(void);
 int pkw_open(pkw_scheme *scheme, const pkw_commitment *commitment, const uint64_t *points, unsigned q, uint64_t *evals_out,
              uint8_t *proof_out, size_t cap, size_t *len);
 
-/* Host only, no device.  io_pattern == NULL: pkw_io_pattern(cfg, q).  expected_root (canonical 32 bytes) may be NULL: the
+/* Host only, no device.  io_pattern == NULL: pkw_io_pattern(cfg, q).  A caller's pattern may spell the labels otherwise; it must
+ * declare the operations of pkw_io_pattern(cfg, q) -- another config's pattern is PKV_CHECK_IO_PATTERN before the proof is read.
+ * expected_root (canonical 32 bytes) may be NULL: the
  * proof's own root is then taken as the commitment.  evals_out (batch_size * q, may be NULL) receives the evaluations the proof
  * binds, whenever the walk got past them -- they are PROVEN only when result->accepted. */
 int pkw_verify(const pk_whir_config *cfg, const uint8_t *io_pattern, size_t io_pattern_len, int hash_version,

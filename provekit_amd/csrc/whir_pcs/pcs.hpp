@@ -112,7 +112,10 @@ inline Plan plan(const pk_whir_config& c) {
     const size_t N = (size_t)1 << n;
     auto commit_scratch = [&](unsigned nv, unsigned rate, unsigned batch) { return 2 * ((size_t)1 << (nv + rate - k)) * ((size_t)batch << k); };
     p.scratch = commit_scratch(n, c.starting_log_inv_rate, c.batch_size);  // pkw_commit's
-    p.total += 3 * round8(N) + 2 * round8(N / 2 ? N / 2 : 1);              // combined coefficients, p and w with their halves
+    // ... and a linear opening's deferred evaluations borrow it for the partials of EVAL_MAX_BATCH tables: more than the commit's
+    // where batch * 2^(n + rate) < 16
+    p.scratch = std::max(p.scratch, eval_partial_fes(EVAL_MAX_BATCH, n));
+    p.total+= 3 * round8(N) + 2 * round8(N / 2 ? N / 2 : 1);              // combined coefficients, p and w with their halves
     unsigned nv = n, rate = c.starting_log_inv_rate;
     for (unsigned r = 0; r <= c.n_rounds; r++) {  // the folded polynomials, the last one being the final coefficients
         nv -= k;

@@ -135,10 +135,27 @@ int verify_checked(const pk_whir_config* cfg, const uint8_t* io_pattern, size_t 
             g_error = why;
             return PK_ERR_IO_PATTERN;
         }
+        pkv::Verdict verdict;
+        if (io_pattern && io_pattern_len) {
+            // a caller's pattern may spell the labels otherwise; its operations are this config's.  Held against them here: under
+            // another config's pattern every challenge differs, and the walk would stop at its first relation, long before the
+            // operation that differs
+            std::vector<pk::IoOp> own;
+            if (!pk::io_pattern_parse(pkw::io_pattern(*cfg, s.q, s.l), own, why)) return refuse("internal: " + why);
+            size_t i = 0;
+            while (i < own.size() && i < st.ops.size() && own[i].kind == st.ops[i].kind && own[i].count == st.ops[i].count) i++;
+            if (i < own.size() || i < st.ops.size()) {
+                verdict.failed = true;
+                verdict.check = PKV_CHECK_IO_PATTERN;
+                verdict.message = "the IO pattern does not declare this config's operations (operation #" + std::to_string(i + 1) + ")";
+                pkv::to_result(verdict, result);
+                if (out.unchecked) *out.unchecked = 0;
+                return PK_OK;
+            }
+        }
         static const uint8_t none = 0;
         pk::fe root;
         if (expected_root) root = pk::load_raw(expected_root);
-        pkv::Verdict verdict;
         pkv::HostBackend be;
         PcsWalk walk(st, be, len ? proof : &none, len, verdict, *cfg, s, expected_root ? &root : nullptr);
         walk.run_opening();

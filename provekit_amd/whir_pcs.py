@@ -378,7 +378,7 @@ class Scheme:
         outs = (evals.ctypes.data if q else None,) + (() if statement is None else (sums.ctypes.data,))
         self._check(fn(self.handle, commitment.handle, p.ctypes.data if q else None, q, *(statement or ()), *outs, buf, len(buf) if cap is None else cap,
                        C.byref(n)))
-        return evals, sums[:l], C.string_at(buf, n.value)
+        return evals, sums[:, :l], C.string_at(buf, n.value)
 
     def open(self, commitment: Commitment, points, cap: int | None = None):
         """-> (evaluations [batch, q, 4] Montgomery, proof bytes)"""
