@@ -4,11 +4,13 @@
  * Commit to `batch_size` multilinear polynomials, open them at points the caller chooses, verify the opening: what the `whir`
  * crate is used for outside WhirR1CSScheme (a lookup argument, a GR1CS variant, ...).  A fourth library above the product's C
  * ABI (like libprovekit_engine.so and libprovekit_verify.so): it links libprovekit_hip.so, calls only what provekit_hip.h
- * declares, and adds HIP kernels of its own for gfx950 (csrc/whir_pcs/evaluate.hip, csrc/whir_pcs/linear.hip).
+ * declares, and adds HIP kernels of its own for gfx950 (csrc/whir_pcs/evaluate.hip, linear.hip, sparse.hip, hiding.hip).
  *
- * PLAIN WHIR, NOT HIDING.  There is no mask and no blinding polynomial: the proof contains openings of the committed
- * codeword and the evaluations themselves.  Use pk_prove where zero knowledge is needed.  Nothing here draws randomness: the
- * same polynomials, points and configuration give the same bytes.
+ * PLAIN OPENINGS ARE NOT HIDING.  pkw_commit / pkw_open use no mask and no blinding polynomial: the proof contains openings of the
+ * committed codeword and the evaluations themselves, and nothing here draws randomness: the same polynomials, points and
+ * configuration give the same bytes.  Where an opening must not leak them, see provekit_whir_hiding.h: pkw_commit_hiding /
+ * pkw_open_hiding / pkw_verify_hiding mask the polynomials as pk_prove masks its witness (a header and a companion library of
+ * their own; that header states the construction and what it claims).
  *
  * One proof = one spongefish transcript (pkw_io_pattern lists its operations):
  *   root; commitment_ood_samples OOD points; their answers per polynomial; beta when batch_size > 1;

@@ -1,11 +1,13 @@
 // provekit_whir.hpp -- provekit::WhirPcs: the C++ face of libprovekit_whir.so (include/provekit_whir.h), next to provekit_hip.hpp's
 // prover types and provekit_verify.hpp's Verdict.  Commit to multilinear polynomials, open them at points or at linear statements
-// over dense weight tables, verify: PLAIN WHIR, not hiding.  open_linear / verify_linear need libprovekit_whir_linear.so linked next to
+// over dense weight tables, verify.  Those openings are plain WHIR, not hiding; commit_hiding / open_hiding / verify_hiding mask the
+// polynomials (provekit_whir_hiding.h states the construction) and need libprovekit_whir_hiding.so.  open_linear / verify_linear need libprovekit_whir_linear.so linked next to
 // libprovekit_whir.so (provekit_whir_linear.h); open_sparse / verify_sparse, which state the same weights as index/value lists,
 // need libprovekit_whir_sparse.so (provekit_whir_sparse.h).  A rejected proof is a Verdict, not an exception; only a failed call throws provekit::Error.
 #pragma once
 #include "provekit_hip.hpp"
 #include "provekit_whir.h"
+#include "provekit_whir_hiding.h"
 #include "provekit_whir_sparse.h"
 
 namespace provekit {
@@ -80,10 +82,38 @@ class PcsCommitment {
     pkw_commitment* c_;
 };
 
+// a commitment to the caller's polynomials under masks (provekit_whir_hiding.h): opened once
+class PcsHidingCommitment {
+   public:
+    ~PcsHidingCommitment() { pkw_hiding_commitment_destroy(c_); }
+    PcsHidingCommitment(PcsHidingCommitment&& o) noexcept : c_(o.c_) { o.c_ = nullptr; }
+    PcsHidingCommitment(const PcsHidingCommitment&) = delete;
+    PcsHidingCommitment& operator=(const PcsHidingCommitment&) = delete;
+    std::array<uint8_t, 32> root() const {
+        std::array<uint8_t, 32> r{};
+        pkw_hiding_commitment_root(c_, r.data());
+        return r;
+    }
+    pkw_hiding_commitment* get() const { return c_; }
+
+   private:
+    friend class WhirPcs;
+    explicit PcsHidingCommitment(pkw_hiding_commitment* c) : c_(c) {}
+    pkw_hiding_commitment* c_;
+};
+
 class WhirPcs {
    public:
     WhirPcs(const Context& ctx, const WhirConfig& cfg) : cfg_(cfg.to_c()) {
         if (int rc = pkw_scheme_create(ctx.get(), &cfg_, &s_)) throw Error(rc, pkw_create_error());
+    }
+    // The scheme of hiding commitments: cfg describes the EXTENDED batch (n_vars = n + 1, batch_size = B + 1) and must keep their two
+    // rules.  A factory of its own, so that only its callers name pkw_hiding_scheme_create and need libprovekit_whir_hiding.so
+    static WhirPcs hiding(const Context& ctx, const WhirConfig& cfg) {
+        const pk_whir_config c = cfg.to_c();
+        pkw_scheme* s = nullptr;
+        if (int rc = pkw_hiding_scheme_create(ctx.get(), &c, &s)) throw Error(rc, pkw_create_error());
+        return WhirPcs(c, s);
     }
     ~WhirPcs() { pkw_scheme_destroy(s_); }
     WhirPcs(const WhirPcs&) = delete;
@@ -175,9 +205,44 @@ class WhirPcs {
                                      proof.data(), proof.size(), evals, sums, fold, deferred, r);
         });
     }
+    // batch_size - 1 tables of 2^(n_vars - 1) evaluations; the masks and g are drawn on the device.  seed: a test hook, nullptr
+    // takes the key from the OS
+    PcsHidingCommitment commit_hiding(const std::vector<const DeviceVec*>& evals, const std::array<uint8_t, 32>* seed = nullptr) const {
+        if (evals.size() + 1 != cfg_.batch_size) throw Error(PK_ERR_BAD_ARG, "one polynomial fewer than the config's batch_size");
+        std::vector<const uint64_t*> p;
+        for (const DeviceVec* v : evals) p.push_back(v->data());
+        pkw_hiding_commitment* c = nullptr;
+        check(pkw_commit_hiding(s_, p.data(), seed ? seed->data() : nullptr, &c));
+        return PcsHidingCommitment(c);
+    }
+    // points of n_vars - 1 coordinates; evaluations [polynomial][point] of the caller's polynomials.  Once per commitment
+    PcsOpening open_hiding(PcsHidingCommitment& com, const std::vector<Point>& points) const {
+        const std::vector<uint64_t> flat = flatten(points, cfg_.n_vars - 1);
+        PcsLinearOpening o = open_with(points.size(), 0, [&](uint64_t* evals, uint64_t*, uint8_t* proof, size_t cap, size_t* len) {
+            return pkw_open_hiding(s_, com.get(), flat.data(), (unsigned)points.size(), evals, proof, cap, len);
+        });
+        o.evaluations.resize((cfg_.batch_size - 1) * points.size());
+        return {std::move(o.evaluations), std::move(o.proof)};
+    }
+    // host only; evaluations_out (optional) receives f_b(z_i) as the proof binds them
+    static PcsVerdict verify_hiding(const WhirConfig& cfg, const std::vector<Point>& points, const std::vector<uint8_t>& proof,
+                                    const std::array<uint8_t, 32>* expected_root = nullptr, std::vector<FieldElement>* evaluations_out = nullptr,
+                                    int hash_version = 2) {
+        const pk_whir_config c = cfg.to_c();
+        if (c.n_vars < 2 || c.batch_size < 2) throw Error(PK_ERR_BAD_ARG, "not a hiding config");
+        const std::vector<uint64_t> flat = flatten(points, c.n_vars - 1);
+        PcsLinearVerdict out = verify_with(c, points.size(), 0, [&](uint64_t* evals, uint64_t*, uint64_t*, uint64_t*, unsigned*, pkv_result* r) {
+            return pkw_verify_hiding(&c, nullptr, 0, hash_version, root_ptr(expected_root), flat.data(), (unsigned)points.size(), proof.data(), proof.size(), evals,
+                                     r);
+        });
+        out.evaluations.resize((c.batch_size - 1) * points.size());
+        if (evaluations_out) *evaluations_out = out.evaluations;
+        return out.verdict;
+    }
     pkw_scheme* get() const { return s_; }
 
    private:
+    WhirPcs(const pk_whir_config& c, pkw_scheme* s) : cfg_(c), s_(s) {}
     static std::vector<uint64_t> flatten(const std::vector<Point>& points, unsigned n_vars, bool may_be_empty = false) {
         std::vector<uint64_t> flat;
         for (const Point& p : points) {

@@ -4,6 +4,7 @@
 // The opaque handles (pk_tree, pk_r1cs, pk_witness_program) and pk_commit_layout are declared by the public header.
 #pragma once
 #include "ctx.hpp"
+#include "rng_core.hpp"  // RngKey, the cipher block and the accept rule
 
 namespace pk {
 
@@ -114,9 +115,6 @@ int witness_bounds_strided(pk_ctx* ctx, const pk_r1cs* r, const uint64_t* d_z, u
 int external_row_range(pk_ctx* ctx, const pk_r1cs* r, const uint64_t* d_eq_alpha, size_t first, size_t last, uint64_t* d_out);
 
 // ---- rng.hip: the proof RNG ---------------------------------------------------------------------------------------------------
-struct RngKey {
-    uint32_t k[8];
-};
 enum { RNG_MASK = 1, RNG_G = 2, RNG_BLIND = 3, RNG_MASK_B = 4, RNG_G_B = 5, RNG_FILL = 6 };  // draws of one proof (the `stream` word of the nonce)
 int proof_key(pk_ctx* ctx, const uint8_t* rng_seed32, RngKey& key);  // fresh from the OS unless injected; the same on every rank of a device set
 int random_fe(pk_ctx* ctx, uint64_t* d_out, size_t n, const RngKey& key, uint32_t stream);  // launch only

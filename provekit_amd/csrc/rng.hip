@@ -1,5 +1,6 @@
 // rng.hip -- the proof RNG: a device CSPRNG keyed once per proof, and the draws made from it.
 //
+// The cipher block and the accept rule are rng_core.hpp's (whir_pcs/hiding.hip draws from the same cipher); here are the kernels.
 // The reference draws the ZK mask, the random polynomial g and the Spartan blinding univariates from thread_rng
 // (provekit/common/src/utils/zk_utils.rs:13-22, provekit/prover/src/whir_r1cs.rs:197,212-221): rand's ThreadRng, i.e. ChaCha12
 // seeded from the OS.  Here: one 256-bit key per proof (getrandom(2) inside pk_prove unless the caller injects a seed -- a test
@@ -18,33 +19,6 @@ using namespace pk;
 
 namespace {
 
-constexpr int PK_RNG_ROUNDS = 12;
-#define PK_QR(a, b, c, d)                    \
-    a += b; d ^= a; d = (d << 16) | (d >> 16); \
-    c += d; b ^= c; b = (b << 12) | (b >> 20); \
-    a += b; d ^= a; d = (d << 8) | (d >> 24);  \
-    c += d; b ^= c; b = (b << 7) | (b >> 25)
-__host__ __device__ __forceinline__ void chacha_block(const RngKey& key, u64 counter, u32 n0, u32 n1, int rounds, u32 (&out)[16]) {
-    u32 s[16] = {0x61707865u, 0x3320646eu, 0x79622d32u, 0x6b206574u, key.k[0], key.k[1], key.k[2], key.k[3],
-                 key.k[4],    key.k[5],    key.k[6],    key.k[7],    (u32)counter, (u32)(counter >> 32), n0, n1};
-    u32 x[16];
-#pragma unroll
-    for (int i = 0; i < 16; i++) x[i] = s[i];
-#pragma unroll 1
-    for (int r = 0; r < rounds / 2; r++) {
-        PK_QR(x[0], x[4], x[8], x[12]);
-        PK_QR(x[1], x[5], x[9], x[13]);
-        PK_QR(x[2], x[6], x[10], x[14]);
-        PK_QR(x[3], x[7], x[11], x[15]);
-        PK_QR(x[0], x[5], x[10], x[15]);
-        PK_QR(x[1], x[6], x[11], x[12]);
-        PK_QR(x[2], x[7], x[8], x[13]);
-        PK_QR(x[3], x[4], x[9], x[14]);
-    }
-#pragma unroll
-    for (int i = 0; i < 16; i++) out[i] = x[i] + s[i];
-}
-#undef PK_QR
 // A lane walks its pairs j = g, g + stride, ... as a state machine (pair, attempt): one ChaCha block per loop iteration, whichever pair and
 // attempt the lane is at.  (Until round 5 the retry loop sat INSIDE the loop over pairs, so a wavefront repeated a pair's block until its
 // unluckiest lane -- 128 candidates, each rejected with probability 0.244 -- was done: ~4 blocks per pair instead of the 1.43 a lane needs.
@@ -62,13 +36,7 @@ __global__ __launch_bounds__(256) void random_fe_kernel(fe* __restrict__ out, si
         for (int half = 0; half < 2; half++) {
             if (half == 0 ? done0 : done1) continue;
             fe x;
-#pragma unroll
-            for (int w = 0; w < 8; w++) x.v[w] = blk[8 * half + w];
-            x.v[7] &= 0x3fffffffu;  // < 2^254
-            u32 borrow = 0;
-#pragma unroll
-            for (int k = 0; k < 8; k++) (void)__builtin_subc(x.v[k], kPlimb(k), borrow, &borrow);
-            if (borrow) {  // x < p: accepted
+            if (rng_candidate(blk, half, x)) {  // x < p: accepted
                 fe_store(out + 2 * j + half, x);
                 if (half == 0) done0 = true;
                 else done1 = true;

@@ -8,12 +8,17 @@
 // constraints of pkw_open_linear are dense tables on the device: linear.hip's kernels give their sums and add them to the same
 // weight table in one pass, and evaluate.hip's kernel reads them once more at the folding point for their deferred evaluations.
 // pkw_open_sparse states the same constraints as index/value lists: the same three steps, each by its twin in sparse.hip.
+// pkw_commit_hiding / pkw_open_hiding (provekit_whir_hiding.h) are pkw_commit and pkw_open over the extended batch: hiding.hip draws
+// the masks and g, and the opening is the plain one at the points (0, z_i) under the hiding label.
 #include <hip/hip_runtime.h>
+#include <sys/random.h>
 
+#include <cerrno>
 #include <map>
 
 #include "../prover_transcript.hpp"
 #include "evaluate.hpp"
+#include "hiding.hpp"
 #include "linear.hpp"
 #include "pcs.hpp"
 #include "sparse.hpp"
@@ -23,7 +28,7 @@ using pk::fe;
 struct pkw_scheme {
     pk_ctx* ctx = nullptr;
     pk_whir_config cfg{};
-    std::map<unsigned, std::string> pattern_cache;  // io_pattern(cfg, q, l) by q * (PKW_MAX_WEIGHTS + 1) + l; l = 0: pkw_open's
+    std::map<unsigned, std::string> pattern_cache;  // io_pattern(cfg, q, l) by q * (PKW_MAX_WEIGHTS + 1) + l; l = 0: pkw_open's; a hiding opening's (l = 0) by HIDING_KEYS + q, above every plain key
     std::string err;
     hipStream_t stream = nullptr;  // the evaluation kernel's
     uint64_t* arena = nullptr;
@@ -40,6 +45,12 @@ struct pkw_commitment {
     size_t rows = 0, width = 0;
     pk_commit_layout layout{};
     uint8_t root[32] = {};
+};
+
+// a commitment to (f^_0 .. f^_{B-1}, g): the plain commitment of the extended batch, and whether its one opening was handed out
+struct pkw_hiding_commitment {
+    pkw_commitment* inner = nullptr;
+    bool opened = false;
 };
 
 namespace pkw {
@@ -459,8 +470,9 @@ int open_refused(pkw_scheme* s, const pkw_commitment* com, const Statement& st, 
 int open_checked(pkw_scheme* s, const pkw_commitment* com, const Statement& st, uint64_t* evals_out, uint64_t* sums_out, uint8_t* proof_out, size_t cap,
                  size_t* len) {
     try {
-        std::string& pattern = s->pattern_cache[st.q * (PKW_MAX_WEIGHTS + 1) + st.l];
-        if (pattern.empty()) pattern = io_pattern(s->cfg, st.q, st.l);
+        constexpr unsigned HIDING_KEYS = (PKW_MAX_POINTS + 1) * (PKW_MAX_WEIGHTS + 1);  // one more than the largest plain key
+        std::string& pattern = s->pattern_cache[st.hiding ? HIDING_KEYS + st.q : st.q * (PKW_MAX_WEIGHTS + 1) + st.l];
+        if (pattern.empty()) pattern = io_pattern(s->cfg, st.q, st.l, st.hiding);
         pk::Transcript T(pattern);
         const size_t batch = s->cfg.batch_size;
         std::vector<fe> evals(batch * st.q + 1), sums(batch * st.l + 1);
@@ -542,6 +554,113 @@ int open_sparse(pkw_scheme* s, const pkw_commitment* com, const uint64_t* points
         return fail(s, PK_ERR_OOM, "out of memory");
     }
     return open_checked(s, com, st, evals_out, sums_out, proof_out, cap, len);
+}
+
+}  // namespace pkw
+
+// ---- hiding commitments (include/provekit_whir_hiding.h; the C names are hiding_abi.cpp's) -------------------------------------------
+namespace pkw {
+
+int hiding_scheme_create(pk_ctx* ctx, const pk_whir_config* cfg, pkw_scheme** out) {
+    if (out) *out = nullptr;
+    if (!ctx || !out) return refuse("null pointer");
+    std::string why;
+    if (!config_ok(cfg, why) || !hiding_config_ok(*cfg, why)) return refuse(why);
+    return pkw_scheme_create(ctx, cfg, out);
+}
+
+// f^_b = [f_b || mask_b] and g in one temporary block: the lower halves are copies, the rest is hiding.hip's one launch on the scheme's
+// stream; then pkw_commit, which keeps its own copies
+int commit_hiding(pkw_scheme* s, const uint64_t* const* d_evals, const uint8_t* rng_seed32, pkw_hiding_commitment** out) {
+    if (out) *out = nullptr;
+    if (!s) return PK_ERR_BAD_ARG;
+    if (!d_evals || !out) return fail(s, PK_ERR_BAD_ARG, "null pointer");
+    std::string why;
+    if (!hiding_config_ok(s->cfg, why)) return fail(s, PK_ERR_BAD_ARG, "not a hiding scheme: " + why);
+    const unsigned polys = s->cfg.batch_size - 1, n = s->cfg.n_vars - 1;
+    for (unsigned b = 0; b < polys; b++)
+        if (!d_evals[b]) return fail(s, PK_ERR_BAD_ARG, "null polynomial");
+    uint8_t key[32];
+    if (rng_seed32) {
+        memcpy(key, rng_seed32, 32);
+    } else {
+        for (size_t got = 0; got < 32;) {
+            const ssize_t r = getrandom(key + got, 32 - got, 0);
+            if (r < 0 && errno == EINTR) continue;
+            if (r < 0) return fail(s, PK_ERR_HIP, std::string("getrandom failed: ") + strerror(errno));
+            got += (size_t)r;
+        }
+    }
+    pkw_hiding_commitment* com = nullptr;
+    try {
+        com = new pkw_hiding_commitment();
+    } catch (...) {
+        return fail(s, PK_ERR_OOM, "out of memory");
+    }
+    const size_t N = (size_t)1 << n;
+    uint64_t* block = nullptr;
+    int rc = pk_malloc(s->ctx, 32 * (size_t)(polys + 1) * 2 * N, (void**)&block);
+    if (rc) {
+        delete com;
+        return fail(s, rc, std::string("commit: ") + pk_last_error(s->ctx));
+    }
+    uint64_t* tables[HIDING_MAX_POLYS + 1] = {};
+    for (unsigned b = 0; b <= polys; b++) tables[b] = block + 4 * (size_t)b * 2 * N;
+    rc = pk_ctx_sync(s->ctx);  // also selects the device; the block is the context's allocation
+    if (rc) s->err = std::string("commit: ") + pk_last_error(s->ctx);
+    hipError_t launched = hipSuccess;
+    if (!rc && (rc = hiding_fill_launch(s->stream, tables, polys, n, key, 0, &launched)))
+        s->err = std::string("commit: the launch that draws the masks: ") + hipGetErrorString(launched);
+    for (unsigned b = 0; b < polys && !rc; b++)
+        if ((rc = pk_memcpy_d2d(s->ctx, tables[b], d_evals[b], 32 * N))) s->err = std::string("commit: ") + pk_last_error(s->ctx);
+    const hipError_t drawn = hipStreamSynchronize(s->stream);  // whatever failed above, the launch is over before the block goes
+    if (!rc && drawn != hipSuccess) {
+        rc = PK_ERR_HIP;
+        s->err = std::string("commit: the kernel that draws the masks: ") + hipGetErrorString(drawn);
+    }
+    if (!rc) rc = pkw_commit(s, tables, &com->inner);  // sets the scheme's error itself
+    pk_ctx_sync(s->ctx);  // the copies out of the block are done before it goes
+    pk_free(s->ctx, block);
+    explicit_bzero(key, sizeof key);
+    if (rc) {
+        delete com;
+        return rc;
+    }
+    *out = com;
+    return PK_OK;
+}
+
+int hiding_commitment_root(const pkw_hiding_commitment* com, uint8_t root[32]) { return com ? pkw_commitment_root(com->inner, root) : PK_ERR_BAD_ARG; }
+
+int hiding_commitment_destroy(pkw_hiding_commitment* com) {
+    if (!com) return PK_OK;
+    pkw_commitment_destroy(com->inner);
+    delete com;
+    return PK_OK;
+}
+
+// pkw_open of the extended batch at the points (0, z_i), once
+int open_hiding(pkw_scheme* s, pkw_hiding_commitment* com, const uint64_t* points, unsigned q, uint64_t* evals_out, uint8_t* proof_out, size_t cap,
+                size_t* len) {
+    if (!s) return PK_ERR_BAD_ARG;
+    if (q < 1 || q > PKW_MAX_POINTS) return fail(s, PK_ERR_BAD_ARG, "the number of points must be 1..64");
+    if (!com) return fail(s, PK_ERR_BAD_ARG, "null pointer");
+    try {
+        const unsigned nv = s->cfg.n_vars, batch = s->cfg.batch_size;
+        std::vector<uint64_t> ext(4 * (size_t)q * nv), evals(4 * (size_t)batch * q);
+        Statement st{points ? ext.data() : nullptr, q};
+        st.hiding = true;
+        if (int rc = open_refused(s, com->inner, st, proof_out, cap, len)) return rc;
+        if (com->opened) return fail(s, PK_ERR_BAD_ARG, "already opened: a hiding commitment is opened once");
+        for (unsigned i = 0; i < q; i++)  // (0, z_i): the leading coordinate stays zero
+            memcpy(&ext[4 * ((size_t)i * nv + 1)], points + 4 * (size_t)i * (nv - 1), 32 * (size_t)(nv - 1));
+        if (int rc = open_checked(s, com->inner, st, evals.data(), nullptr, proof_out, cap, len)) return rc;
+        com->opened = true;
+        if (evals_out) memcpy(evals_out, evals.data(), 32 * (size_t)(batch - 1) * q);  // the first B rows: f_b(z_i)
+        return PK_OK;
+    } catch (...) {
+        return fail(s, PK_ERR_OOM, "out of memory");
+    }
 }
 
 }  // namespace pkw

@@ -5,6 +5,7 @@
 #include <string>
 
 #include "../../../include/provekit_whir.h"
+#include "../../../include/provekit_whir_hiding.h"
 #include "../verify/core.hpp"
 #include "evaluate.hpp"
 
@@ -37,9 +38,10 @@ inline bool config_ok(const pk_whir_config* c, std::string& why) {
 
 // "<domain>" then commit_statement, the statement, add_whir_proof -- the operations and labels of whir_config.hip's restatement of
 // whir's pattern, zero-count operations omitted where whir guards them.  l = 0: the evaluation statement of pkw_open; l >= 1: the
-// linear statement of pkw_open_linear (its own domain label, the tags after the points, the sums after the evaluations)
-inline std::string io_pattern(const pk_whir_config& c, unsigned q, unsigned l = 0) {
-    std::string d = l ? "provekit-hip/whir-pcs-linear/v1" : "provekit-hip/whir-pcs/v1";
+// linear statement of pkw_open_linear (its own domain label, the tags after the points, the sums after the evaluations).  hiding: the
+// evaluation statement of pkw_open_hiding over the extended config -- the same operations under a label of their own
+inline std::string io_pattern(const pk_whir_config& c, unsigned q, unsigned l = 0, bool hiding = false) {
+    std::string d = hiding ? "provekit-hip/whir-pcs-hiding/v1" : l ? "provekit-hip/whir-pcs-linear/v1" : "provekit-hip/whir-pcs/v1";
     auto op = [&](char kind, size_t count, const char* label) {
         d.push_back('\0');
         d.push_back(kind);
@@ -144,6 +146,7 @@ struct Statement {
     unsigned l = 0;
     const uint64_t* const* dense = nullptr;
     const SparseWeights* sparse = nullptr;
+    bool hiding = false;  // the statement of a hiding opening (points (0, z_i), l = 0): the pattern carries the hiding label
 };
 // what a verification hands back next to its verdict; every pointer may be null
 struct VerifyOutputs {
@@ -177,6 +180,41 @@ int verify_sparse(const pk_whir_config* cfg, const uint8_t* io_pattern, size_t i
                   const uint64_t* points, unsigned q, const uint64_t* tags, const uint64_t* offsets, const uint32_t* index, const uint64_t* value, unsigned l,
                   const uint8_t* proof, size_t len, uint64_t* evals_out, uint64_t* sums_out, uint64_t* fold_point_out, uint64_t* deferred_out,
                   pkv_result* result);
+
+// The hiding commitments' entry points (include/provekit_whir_hiding.h says what they do and states the construction), C++ functions
+// of this library in the same way: their C names are exported by libprovekit_whir_hiding.so (hiding_abi.cpp).  The scheme, the
+// commitment and open_hiding are pcs.cpp's (the stage kernel is hiding.hip's), io_pattern_hiding and verify_hiding verify_host.cpp's
+int hiding_scheme_create(pk_ctx* ctx, const pk_whir_config* cfg, pkw_scheme** out);
+int commit_hiding(pkw_scheme* s, const uint64_t* const* d_evals, const uint8_t* rng_seed32, pkw_hiding_commitment** out);
+int hiding_commitment_root(const pkw_hiding_commitment* com, uint8_t root[32]);
+int hiding_commitment_destroy(pkw_hiding_commitment* com);
+int open_hiding(pkw_scheme* s, pkw_hiding_commitment* com, const uint64_t* points, unsigned q, uint64_t* evals_out, uint8_t* proof_out, size_t cap,
+                size_t* len);
+int io_pattern_hiding(const pk_whir_config* cfg, unsigned q, uint8_t* buf, size_t cap, size_t* len);
+int verify_hiding(const pk_whir_config* cfg, const uint8_t* io_pattern, size_t io_pattern_len, int hash_version, const uint8_t* expected_root,
+                  const uint64_t* points, unsigned q, const uint8_t* proof, size_t len, uint64_t* evals_out, pkv_result* result);
+
+// The two rules a config must keep for a hiding commitment (provekit_whir_hiding.h): the batch is the caller's 1..3 polynomials and
+// g, and the values of each masked polynomial that leave through the committed codeword's openings and the out-of-domain answers
+// do not outnumber its 2^(n_vars - 1) mask coefficients
+inline bool hiding_config_ok(const pk_whir_config& c, std::string& why) {
+    if (c.batch_size < 2 || c.batch_size > 4) {
+        why = "a hiding commitment holds 1..3 polynomials and g: batch_size must be 2..4";
+        return false;
+    }
+    if (c.n_vars < 2) {
+        why = "a hiding commitment holds polynomials of n_vars - 1 >= 1 variables: n_vars must be at least 2";
+        return false;
+    }
+    const uint64_t mask = (uint64_t)1 << (c.n_vars - 1);
+    const uint64_t leave = c.commitment_ood_samples + ((uint64_t)(c.n_rounds ? c.num_queries[0] : c.final_queries) << c.folding_factor);
+    if (leave > mask) {
+        why = "mask budget: " + std::to_string(leave) + " values of each masked polynomial leave through the proof (commitment_ood_samples + " +
+              (c.n_rounds ? "num_queries[0]" : "final_queries") + " * 2^folding_factor), more than its " + std::to_string(mask) + " mask coefficients";
+        return false;
+    }
+    return true;
+}
 
 // the counts of a linear statement, refused with a reason
 inline bool linear_counts_ok(unsigned q, unsigned l, std::string& why) {

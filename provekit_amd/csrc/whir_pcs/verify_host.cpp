@@ -130,7 +130,7 @@ int verify_checked(const pk_whir_config* cfg, const uint8_t* io_pattern, size_t 
         if (io_pattern && io_pattern_len)
             st.pattern.assign(reinterpret_cast<const char*>(io_pattern), io_pattern_len);
         else
-            st.pattern = pkw::io_pattern(*cfg, s.q, s.l);
+            st.pattern = pkw::io_pattern(*cfg, s.q, s.l, s.hiding);
         if (!pk::io_pattern_parse(st.pattern, st.ops, why)) {
             g_error = why;
             return PK_ERR_IO_PATTERN;
@@ -175,9 +175,9 @@ int verify_checked(const pk_whir_config* cfg, const uint8_t* io_pattern, size_t 
 }
 
 // the pattern of a statement with q points and l weights into (buf, cap, *len): both pattern entry points, their counts checked
-int write_pattern(const pk_whir_config& cfg, unsigned q, unsigned l, uint8_t* buf, size_t cap, size_t* len) {
+int write_pattern(const pk_whir_config& cfg, unsigned q, unsigned l, uint8_t* buf, size_t cap, size_t* len, bool hiding = false) {
     try {
-        const std::string d = io_pattern(cfg, q, l);
+        const std::string d = io_pattern(cfg, q, l, hiding);
         *len = d.size();
         if (buf && cap >= d.size()) memcpy(buf, d.data(), d.size());
         return PK_OK;
@@ -273,6 +273,36 @@ int verify_sparse(const pk_whir_config* cfg, const uint8_t* io_pattern, size_t i
         }
     return verify_checked(cfg, io_pattern, io_pattern_len, hash_version, expected_root, Statement{points, q, tags, l, nullptr, &w}, proof, len,
                           VerifyOutputs{evals_out, sums_out, fold_point_out, deferred_out}, result);
+}
+
+// the entry points behind pkw_io_pattern_hiding and pkw_verify_hiding (hiding_abi.cpp)
+int io_pattern_hiding(const pk_whir_config* cfg, unsigned q, uint8_t* buf, size_t cap, size_t* len) {
+    std::string why;
+    if (!len) return refuse("null pointer");
+    if (!config_ok(cfg, why) || !hiding_config_ok(*cfg, why)) return refuse(why);
+    if (q < 1 || q > PKW_MAX_POINTS) return refuse("the number of points must be 1..64");
+    return write_pattern(*cfg, q, 0, buf, cap, len, /*hiding=*/true);
+}
+
+// pkw_verify over the extended statement: every point prefixed by 0, the hiding pattern, the first B rows of evaluations handed back
+int verify_hiding(const pk_whir_config* cfg, const uint8_t* io_pattern, size_t io_pattern_len, int hash_version, const uint8_t* expected_root,
+                  const uint64_t* points, unsigned q, const uint8_t* proof, size_t len, uint64_t* evals_out, pkv_result* result) {
+    std::string why;
+    if (!result || !points || (len && !proof)) return refuse("null pointer");
+    if (!config_ok(cfg, why) || !hiding_config_ok(*cfg, why)) return refuse(why);
+    if (q < 1 || q > PKW_MAX_POINTS) return refuse("the number of points must be 1..64");
+    try {
+        const unsigned nv = cfg->n_vars, batch = cfg->batch_size;
+        std::vector<uint64_t> ext(4 * (size_t)q * nv), evals(4 * (size_t)batch * q);
+        for (unsigned i = 0; i < q; i++) memcpy(&ext[4 * ((size_t)i * nv + 1)], points + 4 * (size_t)i * (nv - 1), 32 * (size_t)(nv - 1));
+        Statement st{ext.data(), q};
+        st.hiding = true;
+        const int rc = verify_checked(cfg, io_pattern, io_pattern_len, hash_version, expected_root, st, proof, len, VerifyOutputs{evals.data()}, result);
+        if (!rc && evals_out) memcpy(evals_out, evals.data(), 32 * (size_t)(batch - 1) * q);
+        return rc;
+    } catch (...) {
+        return PK_ERR_OOM;
+    }
 }
 
 }  // namespace pkw

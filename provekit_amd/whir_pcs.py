@@ -1,7 +1,8 @@
 """WHIR as a polynomial commitment scheme (libprovekit_whir.so, include/provekit_whir.h): commit to up to 4 multilinear
 polynomials, open them at points of the caller's choice -- or at LINEAR statements <w, f> = s over dense weight tables
 (open_linear / verify_linear; the caller's tags bind the weights), or over the same weights as sparse index/value lists
-(open_sparse / verify_sparse; SparseWeights) -- and verify the opening.  PLAIN WHIR, not hiding.
+(open_sparse / verify_sparse; SparseWeights) -- and verify the opening.  Those openings are PLAIN WHIR, not hiding; commit_hiding / open_hiding / verify_hiding mask the
+polynomials as pk_prove masks its witness (include/provekit_whir_hiding.h states the construction and what it claims).
 
 A fourth library above the product's C ABI, with its own loader and signature table (as provekit_amd.verify).  `verify` and
 `io_pattern` are host only; `Scheme` needs a Context.  A rejected proof is a Result, not an exception; only a failed CALL raises.
@@ -63,6 +64,18 @@ SPARSE_SIGNATURES = {
     "pkw_open_sparse": (C.c_int, [vp, vp, vp, C.c_uint, vp, vp, vp, vp, C.c_uint, vp, vp, vp, sz, C.POINTER(sz)]),
     "pkw_verify_sparse": (C.c_int, [vp, vp, sz, C.c_int, vp, vp, C.c_uint, vp, vp, vp, vp, C.c_uint, vp, sz, vp, vp, vp, vp, C.POINTER(ResultStruct)]),
 }
+# hiding commitments: a third companion library (include/provekit_whir_hiding.h)
+HIDING_LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libprovekit_whir_hiding.so")
+HIDING_LABEL = b"provekit-hip/whir-pcs-hiding/v1"
+HIDING_SIGNATURES = {
+    "pkw_hiding_scheme_create": (C.c_int, [vp, vp, C.POINTER(vp)]),
+    "pkw_io_pattern_hiding": (C.c_int, [vp, C.c_uint, vp, sz, C.POINTER(sz)]),
+    "pkw_commit_hiding": (C.c_int, [vp, vp, vp, C.POINTER(vp)]),
+    "pkw_hiding_commitment_root": (C.c_int, [vp, vp]),
+    "pkw_hiding_commitment_destroy": (C.c_int, [vp]),
+    "pkw_open_hiding": (C.c_int, [vp, vp, vp, C.c_uint, vp, vp, sz, C.POINTER(sz)]),
+    "pkw_verify_hiding": (C.c_int, [vp, vp, sz, C.c_int, vp, vp, C.c_uint, vp, sz, vp, C.POINTER(ResultStruct)]),
+}
 
 
 def _load():
@@ -81,7 +94,10 @@ linear_lib = C.CDLL(LINEAR_LIB_PATH)
 if not os.path.exists(SPARSE_LIB_PATH):
     raise ImportError(f"{SPARSE_LIB_PATH} is missing: build it with `make -C provekit_amd/csrc`. provekit_amd has no CPU fallback.")
 sparse_lib = C.CDLL(SPARSE_LIB_PATH)
-for _lib, _table in ((lib, SIGNATURES), (linear_lib, LINEAR_SIGNATURES), (sparse_lib, SPARSE_SIGNATURES)):
+if not os.path.exists(HIDING_LIB_PATH):
+    raise ImportError(f"{HIDING_LIB_PATH} is missing: build it with `make -C provekit_amd/csrc`. provekit_amd has no CPU fallback.")
+hiding_lib = C.CDLL(HIDING_LIB_PATH)
+for _lib, _table in ((lib, SIGNATURES), (linear_lib, LINEAR_SIGNATURES), (sparse_lib, SPARSE_SIGNATURES), (hiding_lib, HIDING_SIGNATURES)):
     for _name, (_res, _args) in _table.items():
         _fn = getattr(_lib, _name)  # AttributeError here == header/library mismatch: fail loudly
         _fn.restype = _res
@@ -143,6 +159,12 @@ def io_pattern(cfg: WhirConfig, q: int) -> bytes:
 def io_pattern_linear(cfg: WhirConfig, q: int, l: int) -> bytes:
     """the operation list of a proof that opens q points and l dense weights (pkw_io_pattern_linear; host only)"""
     return _io_pattern(linear_lib.pkw_io_pattern_linear, cfg, q, l)
+
+
+def io_pattern_hiding(cfg: WhirConfig, q: int) -> bytes:
+    """the operation list of a hiding proof that opens q points: io_pattern(cfg, q)'s operations under HIDING_LABEL
+    (pkw_io_pattern_hiding; host only; cfg describes the extended batch and must keep the two hiding rules)"""
+    return _io_pattern(hiding_lib.pkw_io_pattern_hiding, cfg, q)
 
 
 def arena_bytes(cfg: WhirConfig) -> int:
@@ -312,6 +334,43 @@ def verify(cfg: WhirConfig, points, proof: bytes, expected_root: bytes | None = 
     return v.result, v.evals
 
 
+def verify_hiding(cfg: WhirConfig, points, proof: bytes, expected_root: bytes | None = None, io_pattern: bytes | None = None, hash_version: int = 2):
+    """-> (Result, evaluations [batch_size - 1, q, 4] Montgomery: f_b(z_i) as the proof binds them).  points: [q, n_vars - 1, 4], the
+    verifier prefixes each with 0.  Host only (pkw_verify_hiding)."""
+    p = _points(points, cfg.n_vars - 1)
+    v = _verify(hiding_lib.pkw_verify_hiding, cfg, p, (), 0, proof, expected_root, io_pattern, hash_version, outputs=0)
+    return v.result, _first_rows(v.evals, cfg.batch_size - 1)
+
+
+def _first_rows(evals: np.ndarray, rows: int) -> np.ndarray:
+    """a hiding entry point fills rows * q elements of a [batch, q, 4] buffer, contiguously"""
+    q = evals.shape[1]
+    return evals.reshape(-1, 4)[: rows * q].reshape(rows, q, 4).copy()
+
+
+class HidingCommitment:
+    """What pkw_commit_hiding keeps: the commitment to (f^_0 .. f^_{B-1}, g).  It is opened ONCE."""
+
+    def __init__(self, scheme: "Scheme", handle: int):
+        self.scheme, self.handle = scheme, handle
+
+    def root(self) -> bytes:
+        buf = (C.c_uint8 * 32)()
+        self.scheme._check(hiding_lib.pkw_hiding_commitment_root(self.handle, buf))
+        return bytes(buf)
+
+    def close(self):
+        if self.handle is not None and self.scheme.handle is not None:
+            hiding_lib.pkw_hiding_commitment_destroy(self.handle)
+        self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Commitment:
     """What pkw_commit keeps: both forms of the polynomials, the codeword and its tree.  Open it any number of times."""
 
@@ -338,12 +397,13 @@ class Commitment:
 class Scheme:
     """One WhirConfig (batch_size polynomials of n_vars variables) bound to a Context, with a device arena sized once."""
 
-    def __init__(self, ctx: Context, cfg: WhirConfig):
+    def __init__(self, ctx: Context, cfg: WhirConfig, hiding: bool = False):
+        """hiding: cfg describes the extended batch of hiding commitments, and must keep their two rules (pkw_hiding_scheme_create)"""
         self.handle = None
         self.ctx, self.cfg = ctx, cfg
         c = _cfg_struct(cfg)
         h = vp()
-        rc = lib.pkw_scheme_create(ctx.handle, C.addressof(c), C.byref(h))
+        rc = (hiding_lib.pkw_hiding_scheme_create if hiding else lib.pkw_scheme_create)(ctx.handle, C.addressof(c), C.byref(h))
         if rc:
             raise ProveKitHipError(rc, lib.pkw_create_error().decode())
         self.handle = h.value
@@ -405,6 +465,22 @@ class Scheme:
         if weights.l != l:
             raise ValueError("as many weights as tags")
         return self._open(sparse_lib.pkw_open_sparse, commitment, p, (*weights._device(), t.ctypes.data, l), l, cap)
+
+    def commit_hiding(self, d_evals, seed: bytes | None = None) -> HidingCommitment:
+        """d_evals: batch_size - 1 device buffers of 2^(n_vars - 1) evaluations; they are copied.  seed: 32 bytes, a TEST HOOK --
+        None draws the key of the masks and g from the OS (pkw_commit_hiding)"""
+        if len(d_evals) != self.cfg.batch_size - 1:
+            raise ValueError(f"expected {self.cfg.batch_size - 1} polynomials")
+        if seed is not None and len(seed) != 32:
+            raise ValueError("a seed is 32 bytes")
+        h = vp()
+        self._check(hiding_lib.pkw_commit_hiding(self.handle, C.cast(_ptr_array(d_evals), vp), seed, C.byref(h)))
+        return HidingCommitment(self, h.value)
+
+    def open_hiding(self, commitment: HidingCommitment, points, cap: int | None = None):
+        """points: [q, n_vars - 1, 4] -> (evaluations [batch_size - 1, q, 4] Montgomery, proof bytes); once per commitment"""
+        evals, _, proof = self._open(hiding_lib.pkw_open_hiding, commitment, _points(points, self.cfg.n_vars - 1), None, 0, cap)
+        return _first_rows(evals, self.cfg.batch_size - 1), proof
 
     def close(self):
         if self.handle is not None and self.ctx.handle is not None:

@@ -50,6 +50,11 @@ SIGNATURES = {
     "pk_probe_whir_sparse_sums": (C.c_int, [vp, vp, C.c_uint, C.c_uint, vp, vp, vp, C.c_uint, C.c_uint, vp]),
     "pk_probe_sparse_tile_host": (C.c_int, [vp, vp, C.c_uint, vp]),
     "pk_probe_sparse_eq_host": (C.c_int, [C.c_uint, vp, vp, vp, sz, vp]),
+    # ... and its hiding stage (tools/probes/whir_hiding.hip)
+    "pk_probe_whir_hiding_fill": (C.c_int, [vp, vp, C.c_uint, C.c_uint, vp, C.c_uint]),
+    "pk_probe_whir_hiding_grid": (C.c_uint, [C.c_uint, C.c_uint]),
+    "pk_probe_whir_hiding_threads": (C.c_uint, []),
+    "pk_probe_whir_hiding_pairs_per_lane": (C.c_uint, []),
     # csrc/witness.hip's thresholds and the shape of a levelled builder list (tools/probes/witness.hip): host only
     "pk_probe_witness_narrow": (C.c_uint, []),
     "pk_probe_witness_sum_heavy": (C.c_uint, []),

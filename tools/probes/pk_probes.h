@@ -101,6 +101,16 @@ int pk_probe_whir_sparse_sums(pk_ctx *ctx, const uint64_t *const *d_evals, unsig
 int pk_probe_sparse_tile_host(const uint64_t *f, const uint64_t *w, unsigned terms, uint64_t *out);
 int pk_probe_sparse_eq_host(unsigned n_vars, const uint64_t *point, const uint32_t *index, const uint64_t *value, size_t nnz, uint64_t *out);
 
+/* ... and its hiding stage (csrc/whir_pcs/hiding.hip; whir_hiding.hip here), for tests/test_gpu_whir_pcs_hiding.py and
+ * tools/whir_pcs_hiding_bench.py.  pk_probe_whir_hiding_fill: the one launch of pkw_commit_hiding on a grid of `grid` workgroups
+ * (0: pk_probe_whir_hiding_grid(polys, n)): d_tables = HOST array of polys + 1 device tables of 2^(n+1) elements; the upper halves
+ * of the first `polys` take the masks, the last table takes g, the lower halves are not touched.  polys 1..3, n 1..29.  The grid
+ * rule is one workgroup per threads * pairs_per_lane pairs of the (polys + 2) * 2^(n-1), rounded up. */
+int pk_probe_whir_hiding_fill(pk_ctx *ctx, uint64_t *const *d_tables, unsigned polys, unsigned n, const uint8_t key32[32], unsigned grid);
+unsigned pk_probe_whir_hiding_grid(unsigned polys, unsigned n);
+unsigned pk_probe_whir_hiding_threads(void);
+unsigned pk_probe_whir_hiding_pairs_per_lane(void);
+
 /* csrc/witness.hip's thresholds (csrc/witness_shape.hpp) and the shape of a levelled builder list (witness.hip here), for
  * tests/test_witness_edge_cases_host.py and tests/test_gpu_witness_edges.py.  Host only.  pk_probe_witness_phases: *n_phases = the
  * phases of postcard(Vec<WitnessBuilder>) after levelling (two per level); with cap >= *n_phases, widths[ph] = the items of phase
