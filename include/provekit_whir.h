@@ -9,8 +9,8 @@
  * PLAIN OPENINGS ARE NOT HIDING.  pkw_commit / pkw_open use no mask and no blinding polynomial: the proof contains openings of the
  * committed codeword and the evaluations themselves, and nothing here draws randomness: the same polynomials, points and
  * configuration give the same bytes.  Where an opening must not leak them, see provekit_whir_hiding.h: pkw_commit_hiding /
- * pkw_open_hiding / pkw_verify_hiding mask the polynomials as pk_prove masks its witness (a header and a companion library of
- * their own; that header states the construction and what it claims).
+ * pkw_open_hiding / pkw_verify_hiding mask the polynomials as pk_prove masks its witness (a header of their own, which
+ * states the construction and what it claims; the same library).
  *
  * One proof = one spongefish transcript (pkw_io_pattern lists its operations):
  *   root; commitment_ood_samples OOD points; their answers per polynomial; beta when batch_size > 1;
@@ -102,8 +102,8 @@ int pkw_verify(const pk_whir_config *cfg, const uint8_t *io_pattern, size_t io_p
 #endif
 
 /* The linear statements: pkw_weighted_sums, pkw_io_pattern_linear, pkw_open_linear, pkw_verify_linear.  Their declarations are a
- * header of their own because their C names are exported by a companion library, libprovekit_whir_linear.so (link it next to
- * libprovekit_whir.so); this header brings them along. */
+ * header of their own; this header brings them along.  Whichever headers a caller includes, the library is this one:
+ * -lprovekit_whir -lprovekit_hip. */
 #include "provekit_whir_linear.h"
 
 #endif /* PROVEKIT_WHIR_H */

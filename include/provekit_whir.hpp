@@ -1,9 +1,8 @@
 // provekit_whir.hpp -- provekit::WhirPcs: the C++ face of libprovekit_whir.so (include/provekit_whir.h), next to provekit_hip.hpp's
 // prover types and provekit_verify.hpp's Verdict.  Commit to multilinear polynomials, open them at points or at linear statements
-// over dense weight tables, verify.  Those openings are plain WHIR, not hiding; commit_hiding / open_hiding / verify_hiding mask the
-// polynomials (provekit_whir_hiding.h states the construction) and need libprovekit_whir_hiding.so.  open_linear / verify_linear need libprovekit_whir_linear.so linked next to
-// libprovekit_whir.so (provekit_whir_linear.h); open_sparse / verify_sparse, which state the same weights as index/value lists,
-// need libprovekit_whir_sparse.so (provekit_whir_sparse.h).  A rejected proof is a Verdict, not an exception; only a failed call throws provekit::Error.
+// over dense weight tables (provekit_whir_linear.h) or the same weights as index/value lists (provekit_whir_sparse.h), verify.  Those
+// openings are plain WHIR, not hiding; commit_hiding / open_hiding / verify_hiding mask the polynomials (provekit_whir_hiding.h states
+// the construction).  A rejected proof is a Verdict, not an exception; only a failed call throws provekit::Error.
 #pragma once
 #include "provekit_hip.hpp"
 #include "provekit_whir.h"
@@ -108,7 +107,7 @@ class WhirPcs {
         if (int rc = pkw_scheme_create(ctx.get(), &cfg_, &s_)) throw Error(rc, pkw_create_error());
     }
     // The scheme of hiding commitments: cfg describes the EXTENDED batch (n_vars = n + 1, batch_size = B + 1) and must keep their two
-    // rules.  A factory of its own, so that only its callers name pkw_hiding_scheme_create and need libprovekit_whir_hiding.so
+    // rules.  A factory of its own, so that only its callers name pkw_hiding_scheme_create
     static WhirPcs hiding(const Context& ctx, const WhirConfig& cfg) {
         const pk_whir_config c = cfg.to_c();
         pkw_scheme* s = nullptr;

@@ -2,8 +2,7 @@
  * provekit_whir_hiding.h -- HIDING commitments and openings for libprovekit_whir.so (provekit_whir.h; its conventions hold).
  * provekit_whir.h does not include this header: include it yourself.
  *
- * The code is libprovekit_whir.so's; the seven C names below are exported by a third companion library,
- * libprovekit_whir_hiding.so, which links it and adds nothing else.  Link -lprovekit_whir_hiding -lprovekit_whir -lprovekit_hip.
+ * libprovekit_whir.so exports the seven C names below.  Link -lprovekit_whir -lprovekit_hip.
  *
  * ---- the construction ---------------------------------------------------------------------------------------------------------
  * What pk_prove does to its witness (the reference: provekit/common/src/utils/zk_utils.rs:3-22,

@@ -1,8 +1,7 @@
 /*
  * provekit_whir_linear.h -- the LINEAR statements of libprovekit_whir.so (provekit_whir.h includes this header; its conventions hold).
  *
- * The code is libprovekit_whir.so's; the four C names below are exported by the companion library libprovekit_whir_linear.so,
- * which links it and adds nothing else.  Link both: -lprovekit_whir_linear -lprovekit_whir -lprovekit_hip.
+ * libprovekit_whir.so exports the four C names below.  Link -lprovekit_whir -lprovekit_hip.
  */
 #ifndef PROVEKIT_WHIR_LINEAR_H
 #define PROVEKIT_WHIR_LINEAR_H

@@ -2,9 +2,7 @@
  * provekit_whir_sparse.h -- SPARSE weights for the linear statements of libprovekit_whir.so (provekit_whir_linear.h; its
  * conventions hold).  provekit_whir.h does not include this header: include it yourself.
  *
- * The code is libprovekit_whir.so's; the five C names below are exported by a second companion library,
- * libprovekit_whir_sparse.so, which links it and adds nothing else.  Link -lprovekit_whir_sparse -lprovekit_whir -lprovekit_hip
- * (and -lprovekit_whir_linear for the dense names).
+ * libprovekit_whir.so exports the five C names below.  Link -lprovekit_whir -lprovekit_hip.
  */
 #ifndef PROVEKIT_WHIR_SPARSE_H
 #define PROVEKIT_WHIR_SPARSE_H

@@ -141,21 +141,24 @@ int combine_launch(hipStream_t stream, uint64_t* d_w, size_t len, const uint64_t
     return hipGetLastError() == hipSuccess ? PK_OK : PK_ERR_HIP;
 }
 
-// the entry point behind pkw_weighted_sums (linear_abi.cpp)
-int weighted_sums(pk_ctx* ctx, const uint64_t* const* d_evals, unsigned batch, unsigned n_vars, const uint64_t* const* d_weights, unsigned l,
-                  uint64_t* out) {
-    if (!ctx || !d_evals || !d_weights || !out || batch < 1 || batch > WSUM_MAX_BATCH || n_vars > 30 || l < 1) return PK_ERR_BAD_ARG;
+}  // namespace pkw
+
+extern "C" {
+
+int pkw_weighted_sums(pk_ctx* ctx, const uint64_t* const* d_evals, unsigned batch, unsigned n_vars, const uint64_t* const* d_weights, unsigned l,
+                      uint64_t* out) {
+    if (!ctx || !d_evals || !d_weights || !out || batch < 1 || batch > pkw::WSUM_MAX_BATCH || n_vars > 30 || l < 1) return PK_ERR_BAD_ARG;
     for (unsigned b = 0; b < batch; b++)
         if (!d_evals[b]) return PK_ERR_BAD_ARG;
     for (unsigned i = 0; i < l; i++)
         if (!d_weights[i]) return PK_ERR_BAD_ARG;
-    const size_t part = wsum_partial_fes(batch, n_vars), res = (size_t)batch * l;
-    Scratch d(ctx, part + res);
+    const size_t part = pkw::wsum_partial_fes(batch, n_vars), res = (size_t)batch * l;
+    pkw::Scratch d(ctx, part + res);
     if (d.rc) return d.rc;
     uint64_t *d_part = d.take(part), *d_res = d.take(res);
     // the operands are the context's work: finished before the kernel reads them
-    if (int rc = run_blocking(ctx, [&] { return wsum_launch(nullptr, d_evals, batch, n_vars, d_weights, l, d_part, d_res); })) return rc;
+    if (int rc = pkw::run_blocking(ctx, [&] { return pkw::wsum_launch(nullptr, d_evals, batch, n_vars, d_weights, l, d_part, d_res); })) return rc;
     return pk_memcpy_d2h(ctx, out, d_res, 32 * res);
 }
 
-}  // namespace pkw
+}  // extern "C"

@@ -505,81 +505,75 @@ int pkw_open(pkw_scheme* s, const pkw_commitment* com, const uint64_t* points, u
     return pkw::open_checked(s, com, st, evals_out, nullptr, proof_out, cap, len);
 }
 
-}  // extern "C"
-
-namespace pkw {
-
-// the entry point behind pkw_open_linear (linear_abi.cpp)
-int open_linear(pkw_scheme* s, const pkw_commitment* com, const uint64_t* points, unsigned q, const uint64_t* const* d_weights, const uint64_t* tags,
-                unsigned l, uint64_t* evals_out, uint64_t* sums_out, uint8_t* proof_out, size_t cap, size_t* len) {
+// provekit_whir_linear.h
+int pkw_open_linear(pkw_scheme* s, const pkw_commitment* com, const uint64_t* points, unsigned q, const uint64_t* const* d_weights, const uint64_t* tags,
+                    unsigned l, uint64_t* evals_out, uint64_t* sums_out, uint8_t* proof_out, size_t cap, size_t* len) {
     if (!s) return PK_ERR_BAD_ARG;
     std::string why;
-    if (!linear_counts_ok(q, l, why)) return fail(s, PK_ERR_BAD_ARG, why);
-    const Statement st{points, q, tags, l, d_weights};
-    if (int rc = open_refused(s, com, st, proof_out, cap, len)) return rc;
-    if (!d_weights) return fail(s, PK_ERR_BAD_ARG, "null pointer");
+    if (!pkw::linear_counts_ok(q, l, why)) return pkw::fail(s, PK_ERR_BAD_ARG, why);
+    const pkw::Statement st{points, q, tags, l, d_weights};
+    if (int rc = pkw::open_refused(s, com, st, proof_out, cap, len)) return rc;
+    if (!d_weights) return pkw::fail(s, PK_ERR_BAD_ARG, "null pointer");
     for (unsigned i = 0; i < l; i++)
-        if (!d_weights[i]) return fail(s, PK_ERR_BAD_ARG, "weight " + std::to_string(i) + " is a null pointer");
+        if (!d_weights[i]) return pkw::fail(s, PK_ERR_BAD_ARG, "weight " + std::to_string(i) + " is a null pointer");
     // the scratch both kernels borrow, checked before any work: the sums' partials go where the evaluation's do, the deferred
     // evaluation's (EVAL_MAX_BATCH tables per launch) into the commit scratch
     const unsigned n = s->cfg.n_vars, batch = s->cfg.batch_size;
-    if (wsum_partial_fes(batch, n) > eval_partial_fes(batch, n) || eval_partial_fes(EVAL_MAX_BATCH, n) > plan(s->cfg).scratch)
-        return fail(s, PK_ERR_BAD_ARG, "this config's arena is too small for a linear opening");
-    return open_checked(s, com, st, evals_out, sums_out, proof_out, cap, len);
+    if (pkw::wsum_partial_fes(batch, n) > pkw::eval_partial_fes(batch, n) || pkw::eval_partial_fes(pkw::EVAL_MAX_BATCH, n) > pkw::plan(s->cfg).scratch)
+        return pkw::fail(s, PK_ERR_BAD_ARG, "this config's arena is too small for a linear opening");
+    return pkw::open_checked(s, com, st, evals_out, sums_out, proof_out, cap, len);
 }
 
-// the entry point behind pkw_open_sparse (sparse_abi.cpp): pkw_open_linear's counts, pattern and bytes; the lists are validated
-// here, once (the 8 bytes the pass reports through are the arena's first: an opening starts from its front afterwards)
-int open_sparse(pkw_scheme* s, const pkw_commitment* com, const uint64_t* points, unsigned q, const uint64_t* offsets, const uint32_t* d_index,
-                const uint64_t* d_value, const uint64_t* tags, unsigned l, uint64_t* evals_out, uint64_t* sums_out, uint8_t* proof_out, size_t cap, size_t* len) {
+// provekit_whir_sparse.h: pkw_open_linear's counts, pattern and bytes; the lists are validated here, once (the 8 bytes the pass reports
+// through are the arena's first: an opening starts from its front afterwards)
+int pkw_open_sparse(pkw_scheme* s, const pkw_commitment* com, const uint64_t* points, unsigned q, const uint64_t* offsets, const uint32_t* d_index,
+                    const uint64_t* d_value, const uint64_t* tags, unsigned l, uint64_t* evals_out, uint64_t* sums_out, uint8_t* proof_out, size_t cap,
+                    size_t* len) {
     if (!s) return PK_ERR_BAD_ARG;
     std::string why;
-    if (!linear_counts_ok(q, l, why)) return fail(s, PK_ERR_BAD_ARG, why);
-    const SparseWeights w{offsets, d_index, d_value, l};
-    const Statement st{points, q, tags, l, nullptr, &w};
-    if (int rc = open_refused(s, com, st, proof_out, cap, len)) return rc;
-    if (!offsets) return fail(s, PK_ERR_BAD_ARG, "null pointer");
+    if (!pkw::linear_counts_ok(q, l, why)) return pkw::fail(s, PK_ERR_BAD_ARG, why);
+    const pkw::SparseWeights w{offsets, d_index, d_value, l};
+    const pkw::Statement st{points, q, tags, l, nullptr, &w};
+    if (int rc = pkw::open_refused(s, com, st, proof_out, cap, len)) return rc;
+    if (!offsets) return pkw::fail(s, PK_ERR_BAD_ARG, "null pointer");
     const unsigned n = s->cfg.n_vars, batch = s->cfg.batch_size;
-    if (!sparse_offsets_ok(offsets, l, n, why)) return fail(s, PK_ERR_BAD_ARG, why);
-    if (offsets[l] && (!d_index || !d_value)) return fail(s, PK_ERR_BAD_ARG, "null index or value list");
-    if (sparse_partial_fes(batch, n) > eval_partial_fes(batch, n)) return fail(s, PK_ERR_OOM, "this config's arena is too small for a sparse opening");
+    if (!pkw::sparse_offsets_ok(offsets, l, n, why)) return pkw::fail(s, PK_ERR_BAD_ARG, why);
+    if (offsets[l] && (!d_index || !d_value)) return pkw::fail(s, PK_ERR_BAD_ARG, "null index or value list");
+    if (pkw::sparse_partial_fes(batch, n) > pkw::eval_partial_fes(batch, n)) return pkw::fail(s, PK_ERR_OOM, "this config's arena is too small for a sparse opening");
     try {
         size_t bad = 0;
         uint32_t at = 0, prev = 0;
         int rc = pk_ctx_sync(s->ctx);  // the lists are the context's work: there before the pass reads them
-        if (!rc) rc = sparse_validate(s->ctx, s->stream, w, n, s->arena, &bad, &at, &prev);
-        if (rc) return fail(s, rc, std::string("open: ") + pk_last_error(s->ctx));
-        if (bad != ~(size_t)0) return fail(s, PK_ERR_BAD_ARG, sparse_index_reason(w, bad, at, prev, n));
+        if (!rc) rc = pkw::sparse_validate(s->ctx, s->stream, w, n, s->arena, &bad, &at, &prev);
+        if (rc) return pkw::fail(s, rc, std::string("open: ") + pk_last_error(s->ctx));
+        if (bad != ~(size_t)0) return pkw::fail(s, PK_ERR_BAD_ARG, pkw::sparse_index_reason(w, bad, at, prev, n));
     } catch (...) {
-        return fail(s, PK_ERR_OOM, "out of memory");
+        return pkw::fail(s, PK_ERR_OOM, "out of memory");
     }
-    return open_checked(s, com, st, evals_out, sums_out, proof_out, cap, len);
+    return pkw::open_checked(s, com, st, evals_out, sums_out, proof_out, cap, len);
 }
 
-}  // namespace pkw
+// ---- hiding commitments (include/provekit_whir_hiding.h) ------------------------------------------------------------------------
 
-// ---- hiding commitments (include/provekit_whir_hiding.h; the C names are hiding_abi.cpp's) -------------------------------------------
-namespace pkw {
-
-int hiding_scheme_create(pk_ctx* ctx, const pk_whir_config* cfg, pkw_scheme** out) {
+int pkw_hiding_scheme_create(pk_ctx* ctx, const pk_whir_config* cfg, pkw_scheme** out) {
     if (out) *out = nullptr;
-    if (!ctx || !out) return refuse("null pointer");
+    if (!ctx || !out) return pkw::refuse("null pointer");
     std::string why;
-    if (!config_ok(cfg, why) || !hiding_config_ok(*cfg, why)) return refuse(why);
+    if (!pkw::config_ok(cfg, why) || !pkw::hiding_config_ok(*cfg, why)) return pkw::refuse(why);
     return pkw_scheme_create(ctx, cfg, out);
 }
 
 // f^_b = [f_b || mask_b] and g in one temporary block: the lower halves are copies, the rest is hiding.hip's one launch on the scheme's
 // stream; then pkw_commit, which keeps its own copies
-int commit_hiding(pkw_scheme* s, const uint64_t* const* d_evals, const uint8_t* rng_seed32, pkw_hiding_commitment** out) {
+int pkw_commit_hiding(pkw_scheme* s, const uint64_t* const* d_evals, const uint8_t* rng_seed32, pkw_hiding_commitment** out) {
     if (out) *out = nullptr;
     if (!s) return PK_ERR_BAD_ARG;
-    if (!d_evals || !out) return fail(s, PK_ERR_BAD_ARG, "null pointer");
+    if (!d_evals || !out) return pkw::fail(s, PK_ERR_BAD_ARG, "null pointer");
     std::string why;
-    if (!hiding_config_ok(s->cfg, why)) return fail(s, PK_ERR_BAD_ARG, "not a hiding scheme: " + why);
+    if (!pkw::hiding_config_ok(s->cfg, why)) return pkw::fail(s, PK_ERR_BAD_ARG, "not a hiding scheme: " + why);
     const unsigned polys = s->cfg.batch_size - 1, n = s->cfg.n_vars - 1;
     for (unsigned b = 0; b < polys; b++)
-        if (!d_evals[b]) return fail(s, PK_ERR_BAD_ARG, "null polynomial");
+        if (!d_evals[b]) return pkw::fail(s, PK_ERR_BAD_ARG, "null polynomial");
     uint8_t key[32];
     if (rng_seed32) {
         memcpy(key, rng_seed32, 32);
@@ -587,7 +581,7 @@ int commit_hiding(pkw_scheme* s, const uint64_t* const* d_evals, const uint8_t* 
         for (size_t got = 0; got < 32;) {
             const ssize_t r = getrandom(key + got, 32 - got, 0);
             if (r < 0 && errno == EINTR) continue;
-            if (r < 0) return fail(s, PK_ERR_HIP, std::string("getrandom failed: ") + strerror(errno));
+            if (r < 0) return pkw::fail(s, PK_ERR_HIP, std::string("getrandom failed: ") + strerror(errno));
             got += (size_t)r;
         }
     }
@@ -595,21 +589,21 @@ int commit_hiding(pkw_scheme* s, const uint64_t* const* d_evals, const uint8_t* 
     try {
         com = new pkw_hiding_commitment();
     } catch (...) {
-        return fail(s, PK_ERR_OOM, "out of memory");
+        return pkw::fail(s, PK_ERR_OOM, "out of memory");
     }
     const size_t N = (size_t)1 << n;
     uint64_t* block = nullptr;
     int rc = pk_malloc(s->ctx, 32 * (size_t)(polys + 1) * 2 * N, (void**)&block);
     if (rc) {
         delete com;
-        return fail(s, rc, std::string("commit: ") + pk_last_error(s->ctx));
+        return pkw::fail(s, rc, std::string("commit: ") + pk_last_error(s->ctx));
     }
-    uint64_t* tables[HIDING_MAX_POLYS + 1] = {};
+    uint64_t* tables[pkw::HIDING_MAX_POLYS + 1] = {};
     for (unsigned b = 0; b <= polys; b++) tables[b] = block + 4 * (size_t)b * 2 * N;
     rc = pk_ctx_sync(s->ctx);  // also selects the device; the block is the context's allocation
     if (rc) s->err = std::string("commit: ") + pk_last_error(s->ctx);
     hipError_t launched = hipSuccess;
-    if (!rc && (rc = hiding_fill_launch(s->stream, tables, polys, n, key, 0, &launched)))
+    if (!rc && (rc = pkw::hiding_fill_launch(s->stream, tables, polys, n, key, 0, &launched)))
         s->err = std::string("commit: the launch that draws the masks: ") + hipGetErrorString(launched);
     for (unsigned b = 0; b < polys && !rc; b++)
         if ((rc = pk_memcpy_d2d(s->ctx, tables[b], d_evals[b], 32 * N))) s->err = std::string("commit: ") + pk_last_error(s->ctx);
@@ -630,9 +624,9 @@ int commit_hiding(pkw_scheme* s, const uint64_t* const* d_evals, const uint8_t* 
     return PK_OK;
 }
 
-int hiding_commitment_root(const pkw_hiding_commitment* com, uint8_t root[32]) { return com ? pkw_commitment_root(com->inner, root) : PK_ERR_BAD_ARG; }
+int pkw_hiding_commitment_root(const pkw_hiding_commitment* com, uint8_t root[32]) { return com ? pkw_commitment_root(com->inner, root) : PK_ERR_BAD_ARG; }
 
-int hiding_commitment_destroy(pkw_hiding_commitment* com) {
+int pkw_hiding_commitment_destroy(pkw_hiding_commitment* com) {
     if (!com) return PK_OK;
     pkw_commitment_destroy(com->inner);
     delete com;
@@ -640,27 +634,27 @@ int hiding_commitment_destroy(pkw_hiding_commitment* com) {
 }
 
 // pkw_open of the extended batch at the points (0, z_i), once
-int open_hiding(pkw_scheme* s, pkw_hiding_commitment* com, const uint64_t* points, unsigned q, uint64_t* evals_out, uint8_t* proof_out, size_t cap,
-                size_t* len) {
+int pkw_open_hiding(pkw_scheme* s, pkw_hiding_commitment* com, const uint64_t* points, unsigned q, uint64_t* evals_out, uint8_t* proof_out, size_t cap,
+                    size_t* len) {
     if (!s) return PK_ERR_BAD_ARG;
-    if (q < 1 || q > PKW_MAX_POINTS) return fail(s, PK_ERR_BAD_ARG, "the number of points must be 1..64");
-    if (!com) return fail(s, PK_ERR_BAD_ARG, "null pointer");
+    if (q < 1 || q > PKW_MAX_POINTS) return pkw::fail(s, PK_ERR_BAD_ARG, "the number of points must be 1..64");
+    if (!com) return pkw::fail(s, PK_ERR_BAD_ARG, "null pointer");
     try {
         const unsigned nv = s->cfg.n_vars, batch = s->cfg.batch_size;
         std::vector<uint64_t> ext(4 * (size_t)q * nv), evals(4 * (size_t)batch * q);
-        Statement st{points ? ext.data() : nullptr, q};
+        pkw::Statement st{points ? ext.data() : nullptr, q};
         st.hiding = true;
-        if (int rc = open_refused(s, com->inner, st, proof_out, cap, len)) return rc;
-        if (com->opened) return fail(s, PK_ERR_BAD_ARG, "already opened: a hiding commitment is opened once");
+        if (int rc = pkw::open_refused(s, com->inner, st, proof_out, cap, len)) return rc;
+        if (com->opened) return pkw::fail(s, PK_ERR_BAD_ARG, "already opened: a hiding commitment is opened once");
         for (unsigned i = 0; i < q; i++)  // (0, z_i): the leading coordinate stays zero
             memcpy(&ext[4 * ((size_t)i * nv + 1)], points + 4 * (size_t)i * (nv - 1), 32 * (size_t)(nv - 1));
-        if (int rc = open_checked(s, com->inner, st, evals.data(), nullptr, proof_out, cap, len)) return rc;
+        if (int rc = pkw::open_checked(s, com->inner, st, evals.data(), nullptr, proof_out, cap, len)) return rc;
         com->opened = true;
         if (evals_out) memcpy(evals_out, evals.data(), 32 * (size_t)(batch - 1) * q);  // the first B rows: f_b(z_i)
         return PK_OK;
     } catch (...) {
-        return fail(s, PK_ERR_OOM, "out of memory");
+        return pkw::fail(s, PK_ERR_OOM, "out of memory");
     }
 }
 
-}  // namespace pkw
+}  // extern "C"

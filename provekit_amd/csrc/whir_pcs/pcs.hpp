@@ -1,11 +1,13 @@
-// pcs.hpp -- what the three sources of libprovekit_whir.so share: which configs the library takes, the IO pattern of an opening
-// proof, and the statement value every layer passes.  Host only.  The wire rules (sponge, hint framing, STIR indexes, PoW bytes) are
-// protocol.hpp's; the verifier side of the transcript and the WHIR walk are verify/core.hpp's.
+// pcs.hpp -- what the sources of libprovekit_whir.so share: which configs the library takes, the IO pattern of an opening proof, and
+// the statement value every layer passes.  Host only.  The entry points are declared by the public headers alone, included here.
+// The wire rules (sponge, hint framing, STIR indexes, PoW bytes) are protocol.hpp's; the verifier side of the transcript and the WHIR
+// walk are verify/core.hpp's.
 #pragma once
 #include <string>
 
 #include "../../../include/provekit_whir.h"
 #include "../../../include/provekit_whir_hiding.h"
+#include "../../../include/provekit_whir_sparse.h"
 #include "../verify/core.hpp"
 #include "evaluate.hpp"
 
@@ -153,46 +155,6 @@ struct VerifyOutputs {
     uint64_t *evals = nullptr, *sums = nullptr, *fold_point = nullptr, *deferred = nullptr;
     unsigned* unchecked = nullptr;
 };
-
-// The linear statement's entry points (include/provekit_whir_linear.h says what they do).  They are C++ functions of this library;
-// their C names pkw_weighted_sums, pkw_io_pattern_linear, pkw_open_linear and pkw_verify_linear are exported by the companion
-// library libprovekit_whir_linear.so (linear_abi.cpp), because this library's own export list stays the 15 symbols it had.
-int weighted_sums(pk_ctx* ctx, const uint64_t* const* d_evals, unsigned batch, unsigned n_vars, const uint64_t* const* d_weights, unsigned l, uint64_t* out);
-int io_pattern_linear(const pk_whir_config* cfg, unsigned q, unsigned l, uint8_t* buf, size_t cap, size_t* len);
-int open_linear(pkw_scheme* s, const pkw_commitment* com, const uint64_t* points, unsigned q, const uint64_t* const* d_weights, const uint64_t* tags,
-                unsigned l, uint64_t* evals_out, uint64_t* sums_out, uint8_t* proof_out, size_t cap, size_t* len);
-int verify_linear(const pk_whir_config* cfg, const uint8_t* io_pattern, size_t io_pattern_len, int hash_version, const uint8_t* expected_root,
-                  const uint64_t* points, unsigned q, const uint64_t* tags, const uint64_t* const* weights, unsigned l, const uint8_t* proof, size_t len,
-                  uint64_t* evals_out, uint64_t* sums_out, uint64_t* fold_point_out, uint64_t* deferred_out, unsigned* unchecked_out, pkv_result* result);
-
-// The sparse weights' entry points (include/provekit_whir_sparse.h says what they do), C++ functions of this library in the same way:
-// their C names pkw_sparse_sums, pkw_sparse_accumulate, pkw_sparse_evaluate, pkw_open_sparse and pkw_verify_sparse are exported by
-// libprovekit_whir_sparse.so (sparse_abi.cpp).  The first three are sparse.hip's, open_sparse is pcs.cpp's, verify_sparse verify_host.cpp's
-int sparse_sums(pk_ctx* ctx, const uint64_t* const* d_evals, unsigned batch, unsigned n_vars, const uint64_t* offsets, const uint32_t* d_index,
-                const uint64_t* d_value, unsigned l, uint64_t* out);
-int sparse_accumulate(pk_ctx* ctx, uint64_t* d_table, unsigned n_vars, const uint64_t* offsets, const uint32_t* d_index, const uint64_t* d_value, unsigned l,
-                      const uint64_t* scales);
-int sparse_evaluate(pk_ctx* ctx, unsigned n_vars, const uint64_t* offsets, const uint32_t* d_index, const uint64_t* d_value, unsigned l, const uint64_t* point,
-                    uint64_t* out);
-int open_sparse(pkw_scheme* s, const pkw_commitment* com, const uint64_t* points, unsigned q, const uint64_t* offsets, const uint32_t* d_index,
-                const uint64_t* d_value, const uint64_t* tags, unsigned l, uint64_t* evals_out, uint64_t* sums_out, uint8_t* proof_out, size_t cap, size_t* len);
-int verify_sparse(const pk_whir_config* cfg, const uint8_t* io_pattern, size_t io_pattern_len, int hash_version, const uint8_t* expected_root,
-                  const uint64_t* points, unsigned q, const uint64_t* tags, const uint64_t* offsets, const uint32_t* index, const uint64_t* value, unsigned l,
-                  const uint8_t* proof, size_t len, uint64_t* evals_out, uint64_t* sums_out, uint64_t* fold_point_out, uint64_t* deferred_out,
-                  pkv_result* result);
-
-// The hiding commitments' entry points (include/provekit_whir_hiding.h says what they do and states the construction), C++ functions
-// of this library in the same way: their C names are exported by libprovekit_whir_hiding.so (hiding_abi.cpp).  The scheme, the
-// commitment and open_hiding are pcs.cpp's (the stage kernel is hiding.hip's), io_pattern_hiding and verify_hiding verify_host.cpp's
-int hiding_scheme_create(pk_ctx* ctx, const pk_whir_config* cfg, pkw_scheme** out);
-int commit_hiding(pkw_scheme* s, const uint64_t* const* d_evals, const uint8_t* rng_seed32, pkw_hiding_commitment** out);
-int hiding_commitment_root(const pkw_hiding_commitment* com, uint8_t root[32]);
-int hiding_commitment_destroy(pkw_hiding_commitment* com);
-int open_hiding(pkw_scheme* s, pkw_hiding_commitment* com, const uint64_t* points, unsigned q, uint64_t* evals_out, uint8_t* proof_out, size_t cap,
-                size_t* len);
-int io_pattern_hiding(const pk_whir_config* cfg, unsigned q, uint8_t* buf, size_t cap, size_t* len);
-int verify_hiding(const pk_whir_config* cfg, const uint8_t* io_pattern, size_t io_pattern_len, int hash_version, const uint8_t* expected_root,
-                  const uint64_t* points, unsigned q, const uint8_t* proof, size_t len, uint64_t* evals_out, pkv_result* result);
 
 // The two rules a config must keep for a hiding commitment (provekit_whir_hiding.h): the batch is the caller's 1..3 polynomials and
 // g, and the values of each masked polynomial that leave through the committed codeword's openings and the out-of-domain answers

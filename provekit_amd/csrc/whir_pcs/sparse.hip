@@ -229,7 +229,7 @@ int sparse_evaluate_launch(hipStream_t stream, unsigned n_vars, const SparseWeig
     return hipGetLastError() == hipSuccess ? PK_OK : PK_ERR_HIP;
 }
 
-// ---- the entry points behind pkw_sparse_sums, pkw_sparse_accumulate and pkw_sparse_evaluate (sparse_abi.cpp) --------------------------
+// ---- pkw_sparse_sums, pkw_sparse_accumulate and pkw_sparse_evaluate ----------------------------------------------------------------
 
 namespace {
 
@@ -256,50 +256,53 @@ int sparse_args(pk_ctx* ctx, unsigned n_vars, const uint64_t* offsets, const uin
 }
 
 }  // namespace
+}  // namespace pkw
 
-int sparse_sums(pk_ctx* ctx, const uint64_t* const* d_evals, unsigned batch, unsigned n_vars, const uint64_t* offsets, const uint32_t* d_index,
-                const uint64_t* d_value, unsigned l, uint64_t* out) {
-    if (int rc = sparse_args(ctx, n_vars, offsets, d_index, d_value, l)) return rc;
-    if (!d_evals || (l && !out) || batch < 1 || batch > SPARSE_MAX_BATCH) return refuse("the number of polynomials must be 1..4, none null");
+extern "C" {
+
+int pkw_sparse_sums(pk_ctx* ctx, const uint64_t* const* d_evals, unsigned batch, unsigned n_vars, const uint64_t* offsets, const uint32_t* d_index,
+                    const uint64_t* d_value, unsigned l, uint64_t* out) {
+    if (int rc = pkw::sparse_args(ctx, n_vars, offsets, d_index, d_value, l)) return rc;
+    if (!d_evals || (l && !out) || batch < 1 || batch > pkw::SPARSE_MAX_BATCH) return pkw::refuse("the number of polynomials must be 1..4, none null");
     for (unsigned b = 0; b < batch; b++)
-        if (!d_evals[b]) return refuse("null polynomial");
+        if (!d_evals[b]) return pkw::refuse("null polynomial");
     if (!l) return PK_OK;
-    const size_t part = sparse_partial_fes(batch, n_vars), res = (size_t)batch * l;
-    Scratch d(ctx, part + res + 1);
+    const size_t part = pkw::sparse_partial_fes(batch, n_vars), res = (size_t)batch * l;
+    pkw::Scratch d(ctx, part + res + 1);
     if (d.rc) return d.rc;
     uint64_t *d_part = d.take(part), *d_res = d.take(res), *d_slot = d.take(1);
-    const SparseWeights w{offsets, d_index, d_value, l};
-    const int rc = sparse_blocking(ctx, w, n_vars, d_slot, [&] { return sparse_sums_launch(nullptr, d_evals, batch, n_vars, w, d_part, d_res); });
+    const pkw::SparseWeights w{offsets, d_index, d_value, l};
+    const int rc = pkw::sparse_blocking(ctx, w, n_vars, d_slot, [&] { return pkw::sparse_sums_launch(nullptr, d_evals, batch, n_vars, w, d_part, d_res); });
     return rc ? rc : pk_memcpy_d2h(ctx, out, d_res, 32 * res);
 }
 
-int sparse_accumulate(pk_ctx* ctx, uint64_t* d_table, unsigned n_vars, const uint64_t* offsets, const uint32_t* d_index, const uint64_t* d_value, unsigned l,
-                      const uint64_t* scales) {
-    if (int rc = sparse_args(ctx, n_vars, offsets, d_index, d_value, l)) return rc;
-    if (!d_table || (l && !scales)) return refuse("null pointer");
+int pkw_sparse_accumulate(pk_ctx* ctx, uint64_t* d_table, unsigned n_vars, const uint64_t* offsets, const uint32_t* d_index, const uint64_t* d_value, unsigned l,
+                          const uint64_t* scales) {
+    if (int rc = pkw::sparse_args(ctx, n_vars, offsets, d_index, d_value, l)) return rc;
+    if (!d_table || (l && !scales)) return pkw::refuse("null pointer");
     for (unsigned i = 0; i < l; i++)
-        if (!below_p(h_load(scales + 4 * (size_t)i))) return refuse("scale " + std::to_string(i) + " is not below p");
+        if (!pkw::below_p(pk::h_load(scales + 4 * (size_t)i))) return pkw::refuse("scale " + std::to_string(i) + " is not below p");
     if (!l || !offsets[l]) return PK_OK;
-    Scratch d(ctx, 1);
+    pkw::Scratch d(ctx, 1);
     if (d.rc) return d.rc;
-    const SparseWeights w{offsets, d_index, d_value, l};
-    return sparse_blocking(ctx, w, n_vars, d.take(1), [&] { return sparse_accumulate_launch(nullptr, d_table, w, scales); });
+    const pkw::SparseWeights w{offsets, d_index, d_value, l};
+    return pkw::sparse_blocking(ctx, w, n_vars, d.take(1), [&] { return pkw::sparse_accumulate_launch(nullptr, d_table, w, scales); });
 }
 
-int sparse_evaluate(pk_ctx* ctx, unsigned n_vars, const uint64_t* offsets, const uint32_t* d_index, const uint64_t* d_value, unsigned l, const uint64_t* point,
-                    uint64_t* out) {
-    if (int rc = sparse_args(ctx, n_vars, offsets, d_index, d_value, l)) return rc;
-    if ((n_vars && !point) || (l && !out)) return refuse("null pointer");
+int pkw_sparse_evaluate(pk_ctx* ctx, unsigned n_vars, const uint64_t* offsets, const uint32_t* d_index, const uint64_t* d_value, unsigned l, const uint64_t* point,
+                        uint64_t* out) {
+    if (int rc = pkw::sparse_args(ctx, n_vars, offsets, d_index, d_value, l)) return rc;
+    if ((n_vars && !point) || (l && !out)) return pkw::refuse("null pointer");
     if (!l) return PK_OK;
-    const size_t part = sparse_partial_fes(1, n_vars), pts = n_vars ? n_vars : 1;
-    Scratch d(ctx, part + pts + l + 1);
+    const size_t part = pkw::sparse_partial_fes(1, n_vars), pts = n_vars ? n_vars : 1;
+    pkw::Scratch d(ctx, part + pts + l + 1);
     if (d.rc) return d.rc;
     uint64_t *d_part = d.take(part), *d_pt = d.take(pts), *d_res = d.take(l), *d_slot = d.take(1);
-    const SparseWeights w{offsets, d_index, d_value, l};
+    const pkw::SparseWeights w{offsets, d_index, d_value, l};
     if (n_vars)
         if (int rc = pk_memcpy_h2d(ctx, d_pt, point, 32 * (size_t)n_vars)) return rc;
-    const int rc = sparse_blocking(ctx, w, n_vars, d_slot, [&] { return sparse_evaluate_launch(nullptr, n_vars, w, d_pt, d_part, d_res); });
+    const int rc = pkw::sparse_blocking(ctx, w, n_vars, d_slot, [&] { return pkw::sparse_evaluate_launch(nullptr, n_vars, w, d_pt, d_part, d_res); });
     return rc ? rc : pk_memcpy_d2h(ctx, out, d_res, 32 * (size_t)l);
 }
 
-}  // namespace pkw
+}  // extern "C"

@@ -229,75 +229,71 @@ int pkw_verify(const pk_whir_config* cfg, const uint8_t* io_pattern, size_t io_p
                                pkw::VerifyOutputs{evals_out}, result);
 }
 
-}  // extern "C"
-
-namespace pkw {
-
-// the entry points behind pkw_io_pattern_linear and pkw_verify_linear (linear_abi.cpp)
-int io_pattern_linear(const pk_whir_config* cfg, unsigned q, unsigned l, uint8_t* buf, size_t cap, size_t* len) {
+// provekit_whir_linear.h
+int pkw_io_pattern_linear(const pk_whir_config* cfg, unsigned q, unsigned l, uint8_t* buf, size_t cap, size_t* len) {
     std::string why;
-    if (!len) return refuse("null pointer");
-    if (!config_ok(cfg, why) || !linear_counts_ok(q, l, why)) return refuse(why);
-    return write_pattern(*cfg, q, l, buf, cap, len);
+    if (!len) return pkw::refuse("null pointer");
+    if (!pkw::config_ok(cfg, why) || !pkw::linear_counts_ok(q, l, why)) return pkw::refuse(why);
+    return pkw::write_pattern(*cfg, q, l, buf, cap, len);
 }
 
-int verify_linear(const pk_whir_config* cfg, const uint8_t* io_pattern, size_t io_pattern_len, int hash_version, const uint8_t* expected_root,
-                  const uint64_t* points, unsigned q, const uint64_t* tags, const uint64_t* const* weights, unsigned l, const uint8_t* proof, size_t len,
-                  uint64_t* evals_out, uint64_t* sums_out, uint64_t* fold_point_out, uint64_t* deferred_out, unsigned* unchecked_out,
-                  pkv_result* result) {
+int pkw_verify_linear(const pk_whir_config* cfg, const uint8_t* io_pattern, size_t io_pattern_len, int hash_version, const uint8_t* expected_root,
+                      const uint64_t* points, unsigned q, const uint64_t* tags, const uint64_t* const* weights, unsigned l, const uint8_t* proof, size_t len,
+                      uint64_t* evals_out, uint64_t* sums_out, uint64_t* fold_point_out, uint64_t* deferred_out, unsigned* unchecked_out,
+                      pkv_result* result) {
     std::string why;
-    if (!config_ok(cfg, why) || !linear_counts_ok(q, l, why)) return refuse(why);
-    if (!result || (q && !points) || !tags || (len && !proof)) return refuse("null pointer");
-    return verify_checked(cfg, io_pattern, io_pattern_len, hash_version, expected_root, Statement{points, q, tags, l, weights}, proof, len,
-                          VerifyOutputs{evals_out, sums_out, fold_point_out, deferred_out, unchecked_out}, result);
+    if (!pkw::config_ok(cfg, why) || !pkw::linear_counts_ok(q, l, why)) return pkw::refuse(why);
+    if (!result || (q && !points) || !tags || (len && !proof)) return pkw::refuse("null pointer");
+    return pkw::verify_checked(cfg, io_pattern, io_pattern_len, hash_version, expected_root, pkw::Statement{points, q, tags, l, weights}, proof, len,
+                               pkw::VerifyOutputs{evals_out, sums_out, fold_point_out, deferred_out, unchecked_out}, result);
 }
 
-// the entry point behind pkw_verify_sparse (sparse_abi.cpp): pkw_verify_linear's walk over lists the host checks first, entry by entry
-int verify_sparse(const pk_whir_config* cfg, const uint8_t* io_pattern, size_t io_pattern_len, int hash_version, const uint8_t* expected_root,
-                  const uint64_t* points, unsigned q, const uint64_t* tags, const uint64_t* offsets, const uint32_t* index, const uint64_t* value, unsigned l,
-                  const uint8_t* proof, size_t len, uint64_t* evals_out, uint64_t* sums_out, uint64_t* fold_point_out, uint64_t* deferred_out,
-                  pkv_result* result) {
+// provekit_whir_sparse.h: pkw_verify_linear's walk over lists the host checks first, entry by entry
+int pkw_verify_sparse(const pk_whir_config* cfg, const uint8_t* io_pattern, size_t io_pattern_len, int hash_version, const uint8_t* expected_root,
+                      const uint64_t* points, unsigned q, const uint64_t* tags, const uint64_t* offsets, const uint32_t* index, const uint64_t* value, unsigned l,
+                      const uint8_t* proof, size_t len, uint64_t* evals_out, uint64_t* sums_out, uint64_t* fold_point_out, uint64_t* deferred_out,
+                      pkv_result* result) {
     std::string why;
-    if (!config_ok(cfg, why) || !linear_counts_ok(q, l, why)) return refuse(why);
-    if (!result || (q && !points) || !tags || !offsets || (len && !proof)) return refuse("null pointer");
+    if (!pkw::config_ok(cfg, why) || !pkw::linear_counts_ok(q, l, why)) return pkw::refuse(why);
+    if (!result || (q && !points) || !tags || !offsets || (len && !proof)) return pkw::refuse("null pointer");
     const unsigned n = cfg->n_vars;
-    if (!sparse_offsets_ok(offsets, l, n, why)) return refuse(why);
-    if (offsets[l] && (!index || !value)) return refuse("null index or value list");
-    const SparseWeights w{offsets, index, value, l};
+    if (!pkw::sparse_offsets_ok(offsets, l, n, why)) return pkw::refuse(why);
+    if (offsets[l] && (!index || !value)) return pkw::refuse("null index or value list");
+    const pkw::SparseWeights w{offsets, index, value, l};
     for (unsigned i = 0; i < l; i++)
         for (size_t k = w.begin(i); k < w.begin(i + 1); k++) {
             const bool first = k == w.begin(i);
-            if (((uint64_t)index[k] >> n) != 0 || (!first && index[k - 1] >= index[k])) return refuse(sparse_index_reason(w, k, index[k], first ? 0 : index[k - 1], n));
-            if (!below_p(pk::h_load(value + 4 * k)))
-                return refuse("weight " + std::to_string(i) + ", entry " + std::to_string(k - w.begin(i)) + ": the value is not below p");
+            if (((uint64_t)index[k] >> n) != 0 || (!first && index[k - 1] >= index[k])) return pkw::refuse(pkw::sparse_index_reason(w, k, index[k], first ? 0 : index[k - 1], n));
+            if (!pkw::below_p(pk::h_load(value + 4 * k)))
+                return pkw::refuse("weight " + std::to_string(i) + ", entry " + std::to_string(k - w.begin(i)) + ": the value is not below p");
         }
-    return verify_checked(cfg, io_pattern, io_pattern_len, hash_version, expected_root, Statement{points, q, tags, l, nullptr, &w}, proof, len,
-                          VerifyOutputs{evals_out, sums_out, fold_point_out, deferred_out}, result);
+    return pkw::verify_checked(cfg, io_pattern, io_pattern_len, hash_version, expected_root, pkw::Statement{points, q, tags, l, nullptr, &w}, proof, len,
+                               pkw::VerifyOutputs{evals_out, sums_out, fold_point_out, deferred_out}, result);
 }
 
-// the entry points behind pkw_io_pattern_hiding and pkw_verify_hiding (hiding_abi.cpp)
-int io_pattern_hiding(const pk_whir_config* cfg, unsigned q, uint8_t* buf, size_t cap, size_t* len) {
+// provekit_whir_hiding.h
+int pkw_io_pattern_hiding(const pk_whir_config* cfg, unsigned q, uint8_t* buf, size_t cap, size_t* len) {
     std::string why;
-    if (!len) return refuse("null pointer");
-    if (!config_ok(cfg, why) || !hiding_config_ok(*cfg, why)) return refuse(why);
-    if (q < 1 || q > PKW_MAX_POINTS) return refuse("the number of points must be 1..64");
-    return write_pattern(*cfg, q, 0, buf, cap, len, /*hiding=*/true);
+    if (!len) return pkw::refuse("null pointer");
+    if (!pkw::config_ok(cfg, why) || !pkw::hiding_config_ok(*cfg, why)) return pkw::refuse(why);
+    if (q < 1 || q > PKW_MAX_POINTS) return pkw::refuse("the number of points must be 1..64");
+    return pkw::write_pattern(*cfg, q, 0, buf, cap, len, /*hiding=*/true);
 }
 
 // pkw_verify over the extended statement: every point prefixed by 0, the hiding pattern, the first B rows of evaluations handed back
-int verify_hiding(const pk_whir_config* cfg, const uint8_t* io_pattern, size_t io_pattern_len, int hash_version, const uint8_t* expected_root,
-                  const uint64_t* points, unsigned q, const uint8_t* proof, size_t len, uint64_t* evals_out, pkv_result* result) {
+int pkw_verify_hiding(const pk_whir_config* cfg, const uint8_t* io_pattern, size_t io_pattern_len, int hash_version, const uint8_t* expected_root,
+                      const uint64_t* points, unsigned q, const uint8_t* proof, size_t len, uint64_t* evals_out, pkv_result* result) {
     std::string why;
-    if (!result || !points || (len && !proof)) return refuse("null pointer");
-    if (!config_ok(cfg, why) || !hiding_config_ok(*cfg, why)) return refuse(why);
-    if (q < 1 || q > PKW_MAX_POINTS) return refuse("the number of points must be 1..64");
+    if (!result || !points || (len && !proof)) return pkw::refuse("null pointer");
+    if (!pkw::config_ok(cfg, why) || !pkw::hiding_config_ok(*cfg, why)) return pkw::refuse(why);
+    if (q < 1 || q > PKW_MAX_POINTS) return pkw::refuse("the number of points must be 1..64");
     try {
         const unsigned nv = cfg->n_vars, batch = cfg->batch_size;
         std::vector<uint64_t> ext(4 * (size_t)q * nv), evals(4 * (size_t)batch * q);
         for (unsigned i = 0; i < q; i++) memcpy(&ext[4 * ((size_t)i * nv + 1)], points + 4 * (size_t)i * (nv - 1), 32 * (size_t)(nv - 1));
-        Statement st{ext.data(), q};
+        pkw::Statement st{ext.data(), q};
         st.hiding = true;
-        const int rc = verify_checked(cfg, io_pattern, io_pattern_len, hash_version, expected_root, st, proof, len, VerifyOutputs{evals.data()}, result);
+        const int rc = pkw::verify_checked(cfg, io_pattern, io_pattern_len, hash_version, expected_root, st, proof, len, pkw::VerifyOutputs{evals.data()}, result);
         if (!rc && evals_out) memcpy(evals_out, evals.data(), 32 * (size_t)(batch - 1) * q);
         return rc;
     } catch (...) {
@@ -305,4 +301,4 @@ int verify_hiding(const pk_whir_config* cfg, const uint8_t* io_pattern, size_t i
     }
 }
 
-}  // namespace pkw
+}  // extern "C"

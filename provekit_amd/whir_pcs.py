@@ -4,7 +4,7 @@ polynomials, open them at points of the caller's choice -- or at LINEAR statemen
 (open_sparse / verify_sparse; SparseWeights) -- and verify the opening.  Those openings are PLAIN WHIR, not hiding; commit_hiding / open_hiding / verify_hiding mask the
 polynomials as pk_prove masks its witness (include/provekit_whir_hiding.h states the construction and what it claims).
 
-A fourth library above the product's C ABI, with its own loader and signature table (as provekit_amd.verify).  `verify` and
+A fourth library above the product's C ABI, with its own loader and one signature table for its four headers (as provekit_amd.verify).  `verify` and
 `io_pattern` are host only; `Scheme` needs a Context.  A rejected proof is a Result, not an exception; only a failed CALL raises.
 There is no fallback: without the built library the import raises."""
 from __future__ import annotations
@@ -25,7 +25,9 @@ MAX_POINTS = 64
 MAX_WEIGHTS = 16
 CHECKS = WALK_CHECKS + ("POINTS", "ROOT", "DEFERRED")
 
-# name -> (restype, argtypes); kept in the same order as include/provekit_whir.h
+HIDING_LABEL = b"provekit-hip/whir-pcs-hiding/v1"
+
+# name -> (restype, argtypes); kept in the same order as the headers: include/provekit_whir.h, ...
 SIGNATURES = {
     "pkw_abi_version": (C.c_int, []),
     "pkw_check_name": (C.c_char_p, [C.c_int]),
@@ -42,32 +44,19 @@ SIGNATURES = {
     "pkw_evaluate_low_vars": (C.c_uint, []),
     "pkw_open": (C.c_int, [vp, vp, vp, C.c_uint, vp, vp, sz, C.POINTER(sz)]),
     "pkw_verify": (C.c_int, [vp, vp, sz, C.c_int, vp, vp, C.c_uint, vp, sz, vp, C.POINTER(ResultStruct)]),
-}
-
-
-# the linear statements: the same library's code under C names a companion library exports (include/provekit_whir_linear.h)
-LINEAR_LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libprovekit_whir_linear.so")
-LINEAR_SIGNATURES = {
+    # ... provekit_whir_linear.h: linear statements over dense weight tables
     "pkw_weighted_sums": (C.c_int, [vp, vp, C.c_uint, C.c_uint, vp, C.c_uint, vp]),
     "pkw_io_pattern_linear": (C.c_int, [vp, C.c_uint, C.c_uint, vp, sz, C.POINTER(sz)]),
     "pkw_open_linear": (C.c_int, [vp, vp, vp, C.c_uint, vp, vp, C.c_uint, vp, vp, vp, sz, C.POINTER(sz)]),
     "pkw_verify_linear": (C.c_int, [vp, vp, sz, C.c_int, vp, vp, C.c_uint, vp, vp, C.c_uint, vp, sz, vp, vp, vp, vp, C.POINTER(C.c_uint),
                                     C.POINTER(ResultStruct)]),
-}
-
-# sparse weights (index/value lists) for the same statements: a second companion library (include/provekit_whir_sparse.h)
-SPARSE_LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libprovekit_whir_sparse.so")
-SPARSE_SIGNATURES = {
+    # ... provekit_whir_sparse.h: the same statements over index/value lists
     "pkw_sparse_sums": (C.c_int, [vp, vp, C.c_uint, C.c_uint, vp, vp, vp, C.c_uint, vp]),
     "pkw_sparse_accumulate": (C.c_int, [vp, vp, C.c_uint, vp, vp, vp, C.c_uint, vp]),
     "pkw_sparse_evaluate": (C.c_int, [vp, C.c_uint, vp, vp, vp, C.c_uint, vp, vp]),
     "pkw_open_sparse": (C.c_int, [vp, vp, vp, C.c_uint, vp, vp, vp, vp, C.c_uint, vp, vp, vp, sz, C.POINTER(sz)]),
     "pkw_verify_sparse": (C.c_int, [vp, vp, sz, C.c_int, vp, vp, C.c_uint, vp, vp, vp, vp, C.c_uint, vp, sz, vp, vp, vp, vp, C.POINTER(ResultStruct)]),
-}
-# hiding commitments: a third companion library (include/provekit_whir_hiding.h)
-HIDING_LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libprovekit_whir_hiding.so")
-HIDING_LABEL = b"provekit-hip/whir-pcs-hiding/v1"
-HIDING_SIGNATURES = {
+    # ... provekit_whir_hiding.h: hiding commitments
     "pkw_hiding_scheme_create": (C.c_int, [vp, vp, C.POINTER(vp)]),
     "pkw_io_pattern_hiding": (C.c_int, [vp, C.c_uint, vp, sz, C.POINTER(sz)]),
     "pkw_commit_hiding": (C.c_int, [vp, vp, vp, C.POINTER(vp)]),
@@ -88,20 +77,10 @@ def _load():
 
 
 lib = _load()
-if not os.path.exists(LINEAR_LIB_PATH):
-    raise ImportError(f"{LINEAR_LIB_PATH} is missing: build it with `make -C provekit_amd/csrc`. provekit_amd has no CPU fallback.")
-linear_lib = C.CDLL(LINEAR_LIB_PATH)
-if not os.path.exists(SPARSE_LIB_PATH):
-    raise ImportError(f"{SPARSE_LIB_PATH} is missing: build it with `make -C provekit_amd/csrc`. provekit_amd has no CPU fallback.")
-sparse_lib = C.CDLL(SPARSE_LIB_PATH)
-if not os.path.exists(HIDING_LIB_PATH):
-    raise ImportError(f"{HIDING_LIB_PATH} is missing: build it with `make -C provekit_amd/csrc`. provekit_amd has no CPU fallback.")
-hiding_lib = C.CDLL(HIDING_LIB_PATH)
-for _lib, _table in ((lib, SIGNATURES), (linear_lib, LINEAR_SIGNATURES), (sparse_lib, SPARSE_SIGNATURES), (hiding_lib, HIDING_SIGNATURES)):
-    for _name, (_res, _args) in _table.items():
-        _fn = getattr(_lib, _name)  # AttributeError here == header/library mismatch: fail loudly
-        _fn.restype = _res
-        _fn.argtypes = _args
+for _name, (_res, _args) in SIGNATURES.items():
+    _fn = getattr(lib, _name)  # AttributeError here == header/library mismatch: fail loudly
+    _fn.restype = _res
+    _fn.argtypes = _args
 
 
 def _result(r: ResultStruct) -> Result:
@@ -158,13 +137,13 @@ def io_pattern(cfg: WhirConfig, q: int) -> bytes:
 
 def io_pattern_linear(cfg: WhirConfig, q: int, l: int) -> bytes:
     """the operation list of a proof that opens q points and l dense weights (pkw_io_pattern_linear; host only)"""
-    return _io_pattern(linear_lib.pkw_io_pattern_linear, cfg, q, l)
+    return _io_pattern(lib.pkw_io_pattern_linear, cfg, q, l)
 
 
 def io_pattern_hiding(cfg: WhirConfig, q: int) -> bytes:
     """the operation list of a hiding proof that opens q points: io_pattern(cfg, q)'s operations under HIDING_LABEL
     (pkw_io_pattern_hiding; host only; cfg describes the extended batch and must keep the two hiding rules)"""
-    return _io_pattern(hiding_lib.pkw_io_pattern_hiding, cfg, q)
+    return _io_pattern(lib.pkw_io_pattern_hiding, cfg, q)
 
 
 def arena_bytes(cfg: WhirConfig) -> int:
@@ -189,8 +168,8 @@ def weighted_sums(ctx: Context, d_evals, n_vars: int, d_weights) -> np.ndarray:
     """[batch, l, 4] Montgomery: <w_i, f_b> = sum_x w_i[x] f_b[x] for device buffers of 2^n_vars elements, a 2 x 2 tile of them (1 x 4 for one polynomial) per
     pass over memory (pkw_weighted_sums)"""
     out = np.zeros((len(d_evals), len(d_weights), 4), dtype=np.uint64)
-    ctx._check(linear_lib.pkw_weighted_sums(ctx.handle, C.cast(_ptr_array(d_evals), vp), len(d_evals), n_vars, C.cast(_ptr_array(d_weights), vp),
-                                     len(d_weights), out.ctypes.data))
+    ctx._check(lib.pkw_weighted_sums(ctx.handle, C.cast(_ptr_array(d_evals), vp), len(d_evals), n_vars, C.cast(_ptr_array(d_weights), vp),
+                              len(d_weights), out.ctypes.data))
     return out
 
 
@@ -242,7 +221,7 @@ def verify_linear(cfg: WhirConfig, points, tags, weights, proof: bytes, expected
                 raise ValueError(f"a weight table has shape [{1 << cfg.n_vars}, 4]")
         tables = (vp * max(l, 1))(*(None if w is None else w.ctypes.data for w in keep))
     statement = (t.ctypes.data, C.cast(tables, vp) if tables is not None else None, l)
-    return _verify(linear_lib.pkw_verify_linear, cfg, p, statement, l, proof, expected_root, io_pattern, hash_version, outputs=4)
+    return _verify(lib.pkw_verify_linear, cfg, p, statement, l, proof, expected_root, io_pattern, hash_version, outputs=4)
 
 
 class SparseWeights:
@@ -293,8 +272,8 @@ def _sparse_check(ctx: Context, rc: int):
 def sparse_sums(ctx: Context, d_evals, n_vars: int, weights: SparseWeights) -> np.ndarray:
     """[batch, l, 4] Montgomery: sum_k value_i[k] * f_b[index_i[k]], weighted_sums on the densified tables from nnz gathers (pkw_sparse_sums)"""
     out = np.zeros((len(d_evals), max(weights.l, 1), 4), dtype=np.uint64)
-    _sparse_check(ctx, sparse_lib.pkw_sparse_sums(ctx.handle, C.cast(_ptr_array(d_evals), vp), len(d_evals), n_vars, *weights._device(), weights.l,
-                                                  out.ctypes.data))
+    _sparse_check(ctx, lib.pkw_sparse_sums(ctx.handle, C.cast(_ptr_array(d_evals), vp), len(d_evals), n_vars, *weights._device(), weights.l,
+                                           out.ctypes.data))
     return out[:, : weights.l]
 
 
@@ -303,8 +282,8 @@ def sparse_accumulate(ctx: Context, d_table, n_vars: int, weights: SparseWeights
     s = np.ascontiguousarray(scales, dtype=np.uint64).reshape(-1, 4)
     if s.shape[0] != weights.l:
         raise ValueError("as many scales as weights")
-    _sparse_check(ctx, sparse_lib.pkw_sparse_accumulate(ctx.handle, d_table.ptr if isinstance(d_table, DeviceBuffer) else int(d_table), n_vars,
-                                                        *weights._device(), weights.l, s.ctypes.data if weights.l else None))
+    _sparse_check(ctx, lib.pkw_sparse_accumulate(ctx.handle, d_table.ptr if isinstance(d_table, DeviceBuffer) else int(d_table), n_vars,
+                                                 *weights._device(), weights.l, s.ctypes.data if weights.l else None))
 
 
 def sparse_evaluate(ctx: Context, n_vars: int, weights: SparseWeights, point) -> np.ndarray:
@@ -313,7 +292,7 @@ def sparse_evaluate(ctx: Context, n_vars: int, weights: SparseWeights, point) ->
     if p.shape[0] != n_vars:
         raise ValueError(f"a point has {n_vars} coordinates")
     out = np.zeros((max(weights.l, 1), 4), dtype=np.uint64)
-    _sparse_check(ctx, sparse_lib.pkw_sparse_evaluate(ctx.handle, n_vars, *weights._device(), weights.l, p.ctypes.data if n_vars else None, out.ctypes.data))
+    _sparse_check(ctx, lib.pkw_sparse_evaluate(ctx.handle, n_vars, *weights._device(), weights.l, p.ctypes.data if n_vars else None, out.ctypes.data))
     return out[: weights.l]
 
 
@@ -325,7 +304,7 @@ def verify_sparse(cfg: WhirConfig, points, tags, weights: SparseWeights, proof: 
     l = t.shape[0]
     if weights.l != l:
         raise ValueError("as many weights as tags")
-    return _verify(sparse_lib.pkw_verify_sparse, cfg, p, (t.ctypes.data, *weights._host(), l), l, proof, expected_root, io_pattern, hash_version, outputs=3)
+    return _verify(lib.pkw_verify_sparse, cfg, p, (t.ctypes.data, *weights._host(), l), l, proof, expected_root, io_pattern, hash_version, outputs=3)
 
 
 def verify(cfg: WhirConfig, points, proof: bytes, expected_root: bytes | None = None, io_pattern: bytes | None = None, hash_version: int = 2):
@@ -338,7 +317,7 @@ def verify_hiding(cfg: WhirConfig, points, proof: bytes, expected_root: bytes | 
     """-> (Result, evaluations [batch_size - 1, q, 4] Montgomery: f_b(z_i) as the proof binds them).  points: [q, n_vars - 1, 4], the
     verifier prefixes each with 0.  Host only (pkw_verify_hiding)."""
     p = _points(points, cfg.n_vars - 1)
-    v = _verify(hiding_lib.pkw_verify_hiding, cfg, p, (), 0, proof, expected_root, io_pattern, hash_version, outputs=0)
+    v = _verify(lib.pkw_verify_hiding, cfg, p, (), 0, proof, expected_root, io_pattern, hash_version, outputs=0)
     return v.result, _first_rows(v.evals, cfg.batch_size - 1)
 
 
@@ -356,12 +335,12 @@ class HidingCommitment:
 
     def root(self) -> bytes:
         buf = (C.c_uint8 * 32)()
-        self.scheme._check(hiding_lib.pkw_hiding_commitment_root(self.handle, buf))
+        self.scheme._check(lib.pkw_hiding_commitment_root(self.handle, buf))
         return bytes(buf)
 
     def close(self):
         if self.handle is not None and self.scheme.handle is not None:
-            hiding_lib.pkw_hiding_commitment_destroy(self.handle)
+            lib.pkw_hiding_commitment_destroy(self.handle)
         self.handle = None
 
     def __del__(self):
@@ -403,7 +382,7 @@ class Scheme:
         self.ctx, self.cfg = ctx, cfg
         c = _cfg_struct(cfg)
         h = vp()
-        rc = (hiding_lib.pkw_hiding_scheme_create if hiding else lib.pkw_scheme_create)(ctx.handle, C.addressof(c), C.byref(h))
+        rc = (lib.pkw_hiding_scheme_create if hiding else lib.pkw_scheme_create)(ctx.handle, C.addressof(c), C.byref(h))
         if rc:
             raise ProveKitHipError(rc, lib.pkw_create_error().decode())
         self.handle = h.value
@@ -454,7 +433,7 @@ class Scheme:
         if len(d_weights) != l:
             raise ValueError("as many weights as tags")
         statement = (C.cast(_ptr_array(d_weights), vp) if l else None, t.ctypes.data, l)
-        return self._open(linear_lib.pkw_open_linear, commitment, p, statement, l, cap)
+        return self._open(lib.pkw_open_linear, commitment, p, statement, l, cap)
 
     def open_sparse(self, commitment: Commitment, points, weights: SparseWeights, tags, cap: int | None = None):
         """open_linear with the l weights as uploaded index/value lists: the same statement, the same bytes (pkw_open_sparse)
@@ -464,7 +443,7 @@ class Scheme:
         l = t.shape[0]
         if weights.l != l:
             raise ValueError("as many weights as tags")
-        return self._open(sparse_lib.pkw_open_sparse, commitment, p, (*weights._device(), t.ctypes.data, l), l, cap)
+        return self._open(lib.pkw_open_sparse, commitment, p, (*weights._device(), t.ctypes.data, l), l, cap)
 
     def commit_hiding(self, d_evals, seed: bytes | None = None) -> HidingCommitment:
         """d_evals: batch_size - 1 device buffers of 2^(n_vars - 1) evaluations; they are copied.  seed: 32 bytes, a TEST HOOK --
@@ -474,12 +453,12 @@ class Scheme:
         if seed is not None and len(seed) != 32:
             raise ValueError("a seed is 32 bytes")
         h = vp()
-        self._check(hiding_lib.pkw_commit_hiding(self.handle, C.cast(_ptr_array(d_evals), vp), seed, C.byref(h)))
+        self._check(lib.pkw_commit_hiding(self.handle, C.cast(_ptr_array(d_evals), vp), seed, C.byref(h)))
         return HidingCommitment(self, h.value)
 
     def open_hiding(self, commitment: HidingCommitment, points, cap: int | None = None):
         """points: [q, n_vars - 1, 4] -> (evaluations [batch_size - 1, q, 4] Montgomery, proof bytes); once per commitment"""
-        evals, _, proof = self._open(hiding_lib.pkw_open_hiding, commitment, _points(points, self.cfg.n_vars - 1), None, 0, cap)
+        evals, _, proof = self._open(lib.pkw_open_hiding, commitment, _points(points, self.cfg.n_vars - 1), None, 0, cap)
         return _first_rows(evals, self.cfg.batch_size - 1), proof
 
     def close(self):

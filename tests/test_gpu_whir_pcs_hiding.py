@@ -169,7 +169,7 @@ def test_refusals_each_with_its_message_leave_everything_usable(ctx, oracle):
     pts = np.concatenate([c.mpts] * 65)
     n_out, evals = whir_pcs.sz(), np.zeros((65, 4), dtype=np.uint64)
     big = (C.c_uint8 * (1 << 20))()
-    open_raw = whir_pcs.hiding_lib.pkw_open_hiding
+    open_raw = whir_pcs.lib.pkw_open_hiding
     for q in (0, 65):
         assert open_raw(scheme.handle, com.handle, pts.ctypes.data, q, evals.ctypes.data, big, len(big), C.byref(n_out)) == -1
         assert b"1..64" in whir_pcs.lib.pkw_last_error(scheme.handle)

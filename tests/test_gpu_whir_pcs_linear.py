@@ -112,7 +112,7 @@ def test_weighted_sums_do_not_depend_on_the_grid_or_the_tile(ctx, oracle, n, l, 
         assert np.array_equal(out, ref), (grid, tile)
     out = np.zeros_like(ref)
     assert pk_probes.lib.pk_probe_whir_weighted_sums(ctx.handle, ptrs(f), 3, n, ptrs(w), l, full + 1, 0, out.ctypes.data) == -1  # beyond the scratch
-    assert whir_pcs.linear_lib.pkw_weighted_sums(ctx.handle, ptrs(f), 3, n, ptrs(w), 0, out.ctypes.data) == -1  # l = 0
+    assert whir_pcs.lib.pkw_weighted_sums(ctx.handle, ptrs(f), 3, n, ptrs(w), 0, out.ctypes.data) == -1  # l = 0
     assert np.array_equal(whir_pcs.weighted_sums(ctx, f, n, w), ref)
     for x in f + w:
         x.free()
@@ -273,7 +273,7 @@ def test_refusals_of_a_linear_opening_leave_the_context_usable(ctx, oracle):
     holed = (C.c_void_p * 2)(d_w[0].ptr, None)
 
     def call(q, weights_arr, l):
-        return whir_pcs.linear_lib.pkw_open_linear(scheme.handle, com.handle, pts.ctypes.data, q, C.cast(weights_arr, C.c_void_p), tags.ctypes.data, l, None, None,
+        return whir_pcs.lib.pkw_open_linear(scheme.handle, com.handle, pts.ctypes.data, q, C.cast(weights_arr, C.c_void_p), tags.ctypes.data, l, None, None,
                                             big, len(big), C.byref(n_out))
 
     for q, arr, l, why in ((1, many, 0, b"1..16"), (1, many, 17, b"1..16"), (65, many, 1, b"0..64"), (1, holed, 2, b"weight 1 is a null pointer")):

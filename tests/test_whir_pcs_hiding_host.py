@@ -1,4 +1,4 @@
-"""CPU: hiding openings on the host (include/provekit_whir_hiding.h).  The symbols of the third companion library; the hiding pattern;
+"""CPU: hiding openings on the host (include/provekit_whir_hiding.h).  The symbols; the hiding pattern;
 pkw_verify_hiding on openings the ORACLE prover builds over host-built extended tables [f_b || mask_b], g -- acceptance with
 f_b(z_i) of oracle/verifier.py's mle_eval_table, the same bytes accepted by plain pkw_verify as a proof of the extended statement,
 every tampering with the verdict it must give; the two config rules; truncated proofs and hostile counts through the sanitizer
@@ -16,7 +16,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests"), os.path.join(ROOT, "tools")]
 HIDING_HEADER = os.path.join(ROOT, "include", "provekit_whir_hiding.h")
-ASAN = os.path.join(ROOT, "provekit_amd", "lib", "pkw_hiding_asan")
+ASAN = os.path.join(ROOT, "provekit_amd", "lib", "pkw_verify_asan")
 
 import whir_pcs_cases as K  # noqa: E402
 import whir_pcs_hiding_cases as H  # noqa: E402
@@ -26,7 +26,7 @@ HIDING = ["pkw_commit_hiding", "pkw_hiding_commitment_destroy", "pkw_hiding_comm
 STRUCTURAL = {"TRANSCRIPT_SHORT", "NON_CANONICAL", "IO_PATTERN", "HINT_FORMAT", "OPENING_COUNT"}
 
 
-def test_the_hiding_header_declares_what_the_third_companion_exports_and_the_other_export_lists_stay():
+def test_the_hiding_header_declares_seven_names_the_library_exports_and_the_other_lists_stay():
     from provekit_amd import whir_pcs
 
     def declared_in(path):
@@ -36,15 +36,15 @@ def test_the_hiding_header_declares_what_the_third_companion_exports_and_the_oth
         nm = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
         return sorted(set(re.findall(r" [A-Za-z] (pkw_[a-z0-9_]+)$", nm, flags=re.M)))
 
-    assert declared_in(HIDING_HEADER) == exported_by(whir_pcs.HIDING_LIB_PATH) == sorted(whir_pcs.HIDING_SIGNATURES) == sorted(HIDING)
-    sizes = [len(exported_by(p)) for p in (whir_pcs.WHIR_LIB_PATH, whir_pcs.LINEAR_LIB_PATH, whir_pcs.SPARSE_LIB_PATH)]
-    assert sizes == [15, 4, 5] == [len(whir_pcs.SIGNATURES), len(whir_pcs.LINEAR_SIGNATURES), len(whir_pcs.SPARSE_SIGNATURES)]
+    assert declared_in(HIDING_HEADER) == sorted(HIDING) and len(HIDING) == 7
+    assert set(HIDING) <= set(exported_by(whir_pcs.WHIR_LIB_PATH)) and set(HIDING) <= set(whir_pcs.SIGNATURES)
+    others = [declared_in(os.path.join(ROOT, "include", h)) for h in ("provekit_whir.h", "provekit_whir_linear.h", "provekit_whir_sparse.h")]
+    assert [len(o) for o in others] == [15, 4, 5] and all(set(o) <= set(whir_pcs.SIGNATURES) and not set(o) & set(HIDING) for o in others)
+    assert exported_by(whir_pcs.WHIR_LIB_PATH) == sorted(whir_pcs.SIGNATURES)
     plain = open(os.path.join(ROOT, "include", "provekit_whir.h")).read()
     assert '#include "provekit_whir_hiding.h"' not in plain and "PLAIN WHIR, NOT HIDING" not in plain and "see provekit_whir_hiding.h" in plain  # named, not included
     assert ctypes.CDLL(whir_pcs.WHIR_LIB_PATH).pkw_abi_version() == 1
     assert whir_pcs.CHECKS[-3:] == ("POINTS", "ROOT", "DEFERRED") and whir_pcs.lib.pkw_check_name(len(whir_pcs.CHECKS)) == b"UNKNOWN"  # no verdict added
-    und = subprocess.run(["nm", "-D", "--undefined-only", whir_pcs.HIDING_LIB_PATH], capture_output=True, text=True, check=True).stdout
-    assert not re.findall(r"\b_ZN2pk\w+", und) and not re.findall(r"\bpkv_\w+", und), und
     mask0, g, proof_streams = H.streams()
     mine = {mask0, mask0 + 1, mask0 + 2, g}
     assert len(mine) == 4 and len(proof_streams) == 6 and not mine & set(proof_streams)
@@ -52,7 +52,7 @@ def test_the_hiding_header_declares_what_the_third_companion_exports_and_the_oth
 
 def test_plain_users_of_the_cpp_header_name_no_symbol_of_the_hiding_library_even_unoptimised(tmp_path):
     """provekit_whir.hpp includes the hiding header, but only WhirPcs::hiding, commit_hiding, open_hiding and verify_hiding may name its
-    symbols: an -O0 object of a plain, linear or sparse user must link without libprovekit_whir_hiding.so"""
+    symbols: an -O0 object of a plain, linear or sparse user names none of the hiding entry points"""
     for demo, wants in (("pcs_demo", False), ("pcs_linear_demo", False), ("pcs_sparse_demo", False), ("pcs_hiding_demo", True)):
         obj = tmp_path / f"{demo}.o"
         subprocess.run(["g++", "-O0", "-std=c++17", "-I" + os.path.join(ROOT, "include"), "-c", os.path.join(ROOT, "examples", demo + ".cpp"), "-o", str(obj)],
@@ -172,7 +172,7 @@ def test_the_two_config_rules_are_enforced_with_a_reason(oracle):
 def test_truncated_proofs_and_hostile_counts_under_the_sanitizers(oracle, tmp_path):
     """pkw_verify_hiding alone, built with -fsanitize=address,undefined as a program of its own (make -C provekit_amd/csrc asan):
     points, proof and outputs live in exact-size heap blocks there, so a read or write past any of them is a report"""
-    assert os.path.exists(ASAN), "provekit_amd/lib/pkw_hiding_asan is missing: make -C provekit_amd/csrc asan"
+    assert os.path.exists(ASAN), "provekit_amd/lib/pkw_verify_asan is missing: make -C provekit_amd/csrc asan"
     from provekit_amd import whir_pcs
 
     c = H.case(oracle, (8, 3, 3))
@@ -191,7 +191,7 @@ def test_truncated_proofs_and_hostile_counts_under_the_sanitizers(oracle, tmp_pa
     f = tmp_path / "cases.bin"
     f.write_bytes(blob)
     env = {k: v for k, v in os.environ.items() if k != "ASAN_OPTIONS"}
-    p = subprocess.run([ASAN, str(f)], capture_output=True, text=True, env=env, timeout=600)
+    p = subprocess.run([ASAN, "hiding", str(f)], capture_output=True, text=True, env=env, timeout=600)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = p.stdout.splitlines()
     assert len(lines) == len(proofs) + len(counts)

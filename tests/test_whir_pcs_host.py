@@ -23,11 +23,19 @@ STRUCTURAL = {"TRANSCRIPT_SHORT", "NON_CANONICAL", "IO_PATTERN", "HINT_FORMAT", 
 def test_the_header_declares_what_the_library_exports_and_the_binding_binds():
     from provekit_amd import verify, whir_pcs
 
-    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    declared = sorted(set(re.findall(r"\b(pkw_[a-z0-9_]+)\s*\(", src)))
+    def declared_in(name):
+        src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", name)).read(), flags=re.S)
+        return sorted(set(re.findall(r"\b(pkw_[a-z0-9_]+)\s*\(", src)))
+
     nm = subprocess.run(["nm", "-D", "--defined-only", whir_pcs.WHIR_LIB_PATH], capture_output=True, text=True, check=True).stdout
     exported = sorted(set(re.findall(r" [A-Za-z] (pkw_[a-z0-9_]+)$", nm, flags=re.M)))
-    assert declared == exported == sorted(whir_pcs.SIGNATURES) and len(declared) == 15
+    declared = declared_in("provekit_whir.h")  # the header's own text: what it includes is the linear test's
+    assert len(declared) == 15 and set(declared) <= set(exported) and set(declared) <= set(whir_pcs.SIGNATURES)
+    # the whole: the four topical headers between them declare what the one library exports and the one table binds
+    topics = [declared, declared_in("provekit_whir_linear.h"), declared_in("provekit_whir_sparse.h"), declared_in("provekit_whir_hiding.h")]
+    assert [len(t) for t in topics] == [15, 4, 5, 7]
+    assert all(not set(a) & set(b) for i, a in enumerate(topics) for b in topics[i + 1 :])
+    assert sorted(sum(topics, [])) == exported == sorted(whir_pcs.SIGNATURES) and len(exported) == 31
     assert ctypes.CDLL(whir_pcs.WHIR_LIB_PATH).pkw_abi_version() == 1
     assert [whir_pcs.lib.pkw_check_name(i).decode() for i in range(len(whir_pcs.CHECKS))] == list(whir_pcs.CHECKS)
     assert whir_pcs.CHECKS[: len(verify.CHECKS)] == verify.CHECKS  # the walk's verdicts keep the verifier's numbers

@@ -25,9 +25,8 @@ STRUCTURAL = {"TRANSCRIPT_SHORT", "NON_CANONICAL", "IO_PATTERN", "HINT_FORMAT", 
 LINEAR = ["pkw_io_pattern_linear", "pkw_open_linear", "pkw_verify_linear", "pkw_weighted_sums"]
 
 
-def test_the_linear_header_declares_what_the_companion_library_exports_and_the_binding_binds():
-    """the four C names live in include/provekit_whir_linear.h (which provekit_whir.h includes) and libprovekit_whir_linear.so;
-    libprovekit_whir.so, whose code they run, exports what it exported"""
+def test_the_linear_header_declares_four_names_the_library_exports_and_the_binding_binds():
+    """the four C names live in include/provekit_whir_linear.h (which provekit_whir.h includes); libprovekit_whir.so exports them"""
     from provekit_amd import whir_pcs
 
     def declared_in(path):
@@ -37,16 +36,14 @@ def test_the_linear_header_declares_what_the_companion_library_exports_and_the_b
         nm = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
         return sorted(set(re.findall(r" [A-Za-z] (pkw_[a-z0-9_]+)$", nm, flags=re.M)))
 
-    assert declared_in(LINEAR_HEADER) == exported_by(whir_pcs.LINEAR_LIB_PATH) == sorted(whir_pcs.LINEAR_SIGNATURES) == sorted(LINEAR)
-    assert exported_by(whir_pcs.WHIR_LIB_PATH) == sorted(whir_pcs.SIGNATURES) and not set(LINEAR) & set(whir_pcs.SIGNATURES)
+    assert declared_in(LINEAR_HEADER) == sorted(LINEAR) and len(LINEAR) == 4
+    assert set(LINEAR) <= set(exported_by(whir_pcs.WHIR_LIB_PATH)) and set(LINEAR) <= set(whir_pcs.SIGNATURES)
+    assert exported_by(whir_pcs.WHIR_LIB_PATH) == sorted(whir_pcs.SIGNATURES)
     assert re.search(r'^#include "provekit_whir_linear.h"', open(HEADER).read(), flags=re.M)
     assert re.search(r"#define PKW_MAX_WEIGHTS 16\b", open(LINEAR_HEADER).read()) and whir_pcs.MAX_WEIGHTS == 16
     assert ctypes.CDLL(whir_pcs.WHIR_LIB_PATH).pkw_abi_version() == 1  # additive: the ABI version and every verdict number stay
     assert [whir_pcs.lib.pkw_check_name(i).decode() for i in range(len(whir_pcs.CHECKS))] == list(whir_pcs.CHECKS)
     assert whir_pcs.CHECKS[-3:] == ("POINTS", "ROOT", "DEFERRED")
-    # the companion reaches the product only through libprovekit_whir.so's functions and the C ABI
-    und = subprocess.run(["nm", "-D", "--undefined-only", whir_pcs.LINEAR_LIB_PATH], capture_output=True, text=True, check=True).stdout
-    assert not re.findall(r"\b_ZN2pk\w+", und) and not re.findall(r"\bpkv_\w+", und), und
 
 
 @pytest.mark.parametrize("q,l", [(0, 1), (2, 3), (64, 16)])
@@ -87,7 +84,7 @@ def test_io_pattern_linear_refuses_counts_out_of_range_with_a_reason():
     tags = np.zeros((17, 4), dtype=np.uint64)
     pts = np.zeros((65, 8, 4), dtype=np.uint64)
     for q, l, why in ((1, 0, b"1..16"), (1, 17, b"1..16"), (65, 1, b"0..64")):
-        rc = whir_pcs.linear_lib.pkw_verify_linear(ctypes.addressof(c), None, 0, 2, None, pts.ctypes.data, q, tags.ctypes.data, None, l, b"x", 1, None, None, None,
+        rc = whir_pcs.lib.pkw_verify_linear(ctypes.addressof(c), None, 0, 2, None, pts.ctypes.data, q, tags.ctypes.data, None, l, b"x", 1, None, None, None,
                                             None, None, ctypes.byref(r))
         assert rc == -1 and why in whir_pcs.lib.pkw_create_error()
 
@@ -279,7 +276,7 @@ def test_hostile_framing_is_rejected_structurally_under_the_sanitizers(cases, tm
     f = tmp_path / "cases.bin"
     f.write_bytes(blob)
     env = {k: v for k, v in os.environ.items() if k != "ASAN_OPTIONS"}
-    p = subprocess.run([ASAN, str(f)], capture_output=True, text=True, env=env, timeout=600)
+    p = subprocess.run([ASAN, "linear", str(f)], capture_output=True, text=True, env=env, timeout=600)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = p.stdout.splitlines()
     assert len(lines) == len(hostile)
