@@ -27,6 +27,7 @@
 #include <cstring>
 #include <optional>
 #include <stdexcept>
+#include <memory>
 #include <string>
 #include <utility>
 #include <vector>
@@ -55,6 +56,16 @@ class Context {
     }
     Context(const Context&) = delete;
     Context& operator=(const Context&) = delete;
+    // pk_ctx_create_set: one context per listed device, joined into a device set (RCCL over distinct devices, the in-process
+    // transport when a device is listed more than once).  Drive each context from a host thread of its own
+    static std::vector<std::unique_ptr<Context>> create_set(const std::vector<int>& devices) {
+        std::vector<pk_ctx*> raw(devices.size(), nullptr);
+        int rc = devices.empty() ? PK_ERR_BAD_ARG : pk_ctx_create_set(devices.data(), (int)devices.size(), raw.data());
+        if (rc) throw Error(rc, "pk_ctx_create_set failed");
+        std::vector<std::unique_ptr<Context>> out;
+        for (pk_ctx* c : raw) out.emplace_back(new Context(c));
+        return out;
+    }
     pk_ctx* get() const { return ctx_; }
     void check(int rc) const {
         if (rc) throw Error(rc, pk_last_error(ctx_));
@@ -63,6 +74,7 @@ class Context {
     void set_hash_version(int v) const { check(pk_ctx_set_hash_version(ctx_, v)); }
 
    private:
+    explicit Context(pk_ctx* made) : ctx_(made) {}
     pk_ctx* ctx_ = nullptr;
 };
 

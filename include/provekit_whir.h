@@ -25,7 +25,29 @@
  * Conventions: those of provekit_hip.h (Montgomery 4 x u64 field elements, d_* = device pointers, PK_OK or a negative PK_ERR_*)
  * and of provekit_verify.h ("rejected" is a VERDICT in a pkv_result, not a call status; every count inside a proof is bounded
  * by the bytes that remain).  A point is n_vars field elements, variable 0 <-> the MOST significant index bit, as pk_eq_table.
- * A pkw_scheme is single-caller and belongs to the context it was created on (which must not be part of a device set).
+ * A pkw_scheme is single-caller and belongs to the context it was created on.
+ *
+ * DEVICE SETS.  The context may belong to a device set (provekit_hip.h, "device sets": RCCL, the in-process transport or the host
+ * transport).  Each rank of the G creates its own scheme on its own context and drives it from its own host thread, and -- as for
+ * pk_prove -- EVERY RANK MAKES THE SAME CALLS WITH THE SAME INPUTS IN THE SAME ORDER: that is the caller's duty, the library cannot
+ * establish it.  Every rank then gets the root, the evaluations, the sums and the proof bytes a lone scheme gives for those inputs.
+ *   What is divided by G: the committed and the per-round codewords and trees (pk_commit_into / pk_commit_open, under the layouts
+ *   they report), and the two ALU-bound reductions of the statement -- the evaluations of pkw_open / pkw_open_hiding, the sums of
+ *   pkw_open_linear and the deferred values of dense weights: rank g runs the workgroups [g n_wg / G, (g + 1) n_wg / G) of the
+ *   kernel's grid, one pk_comm_all_gather per pass exchanges the partial sums, every rank adds them.  A pass whose grid has fewer
+ *   workgroups than ranks, or that G does not divide, runs whole on every rank.  Everything else of an opening is replicated:
+ *   the sumcheck rounds, the weight tables, the sparse kernels, proof of work, the host side.
+ *   What takes a bare pk_ctx stays whole on the calling rank: pkw_evaluate, pkw_weighted_sums, pkw_sparse_*.
+ *   No rank is left waiting.  A refusal that every rank makes identically (null pointers, counts, "already opened", a sparse list
+ *   that fails validation, a proof buffer that is too small) is made before any collective or after the last one, and leaves the
+ *   communicator usable.  After every step that can fail on one rank alone (the allocation and copies of pkw_commit, the sparse
+ *   validation's readback, a launch in a sliced pass) the ranks exchange their status in a small all-gather -- the sliced passes
+ *   carry it in the gather they make anyway -- and all of them return the first non-zero status in rank order before the next
+ *   sharded call.  Once per opening, after the statement is absorbed, the ranks compare 32 bytes squeezed from a copy of the
+ *   sponge: ranks that were handed different points, tags or polynomials all return PK_ERR_BAD_ARG ("ranks disagree on the
+ *   statement") before the first STIR opening, and the set stays usable.  A failure INSIDE a sharded call of the product library is
+ *   that library's (PK_ERR_RCCL and a poisoned communicator, see provekit_hip.h).  pkw_scheme_create makes no collective.
+ *   World size 1 and contexts without a communicator behave as before: nothing is exchanged, nothing is enqueued for it.
  */
 #ifndef PROVEKIT_WHIR_H
 #define PROVEKIT_WHIR_H
@@ -57,7 +79,13 @@ const char *pkw_check_name(int check); /* every PKV_CHECK_* and PKW_CHECK_* */
 const char *pkw_create_error(void);
 
 /* The scheme owns a device arena sized once for one opening (about (4 + 2 R (1 + 2/F)) 2^n_vars elements at rate 1/R, fold
- * log2 F), so pkw_open allocates nothing.  pkw_scheme_arena_bytes: that size, host only. */
+ * log2 F), so pkw_open allocates nothing.  pkw_scheme_arena_bytes: that size, host only -- it has no context, so it is the size
+ * outside a device set and the UPPER BOUND inside one, where the arena is sized by pk_commit_sizes under the context's set (a rank
+ * keeps 1 / G of every sharded codeword).  The bound carries one allowance, checked at creation and not assumed: the product's
+ * sharded commit stages local and gathered digests in its scratch, which at G = 2 (and for codewords two elements wide at G = 4)
+ * is up to 1.5 elements per row MORE than the lone commit's; a set's arena never exceeds pkw_scheme_arena_bytes by more than 64
+ * bytes per row of the committed codeword (2^(n_vars + starting_log_inv_rate - folding_factor) rows), or creation is refused.  A
+ * scheme in a set also owns the buffer its exchanges go through: under 2^14 + 2 G elements. */
 int pkw_scheme_create(pk_ctx *ctx, const pk_whir_config *cfg, pkw_scheme **out);
 int pkw_scheme_destroy(pkw_scheme *scheme);
 int pkw_scheme_arena_bytes(const pk_whir_config *cfg, size_t *bytes);

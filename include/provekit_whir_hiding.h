@@ -36,7 +36,12 @@
  *   ONE OPENING    per commitment.  beta is drawn before the points, so a second opening would reveal more of the same
  *                  f^ + beta g; the reference opens once.  The second pkw_open_hiding that would hand out a proof is
  *                  PK_ERR_BAD_ARG ("already opened").  A refused call hands out nothing and does not count.
- * Out of scope: linear and sparse statements on hiding commitments, a device verifier, device sets.
+ * DEVICE SETS (provekit_whir.h, "Device sets").  A hiding scheme may sit on a context of a device set under the rule stated there.
+ * The ranks must commit to ONE extended batch: with rng_seed32 == NULL every rank draws a key from the OS, the keys travel in one
+ * 32-byte-per-rank all-gather before the draw, and every rank takes RANK 0's (the others' are discarded and wiped).  A given seed
+ * is an input like any other: the same on every rank.  The one-opening flag and the mask budget are per-rank state that agrees
+ * by construction, so "already opened" is a refusal every rank makes alike, before any collective.
+ * Out of scope: linear and sparse statements on hiding commitments, a device verifier.
  */
 #ifndef PROVEKIT_WHIR_HIDING_H
 #define PROVEKIT_WHIR_HIDING_H

@@ -22,6 +22,12 @@ class Transcript {
     const std::string& violation() const { return violation_; }
     // ... and nothing declared was left undone (spongefish checks this when the state is dropped)
     bool finished() const { return violation_.empty() && cur_.at_end(); }
+    // what a verifier challenge would be at this point, from a copy of the sponge: the transcript itself does not move (the ranks
+    // of a device set compare it to see that they absorbed the same statement)
+    fe peek_challenge() const {
+        DuplexSponge copy = sponge_;
+        return copy.squeeze();
+    }
     // prover -> verifier: field elements (Montgomery in memory), written canonical LE and absorbed
     void add_scalars(const fe* mont, size_t n) {
         for (size_t i = 0; i < n; i++) add_canon(h_to_canon(mont[i]));

@@ -64,14 +64,15 @@ __device__ __forceinline__ fe eq_bits(const fe* pt, int var0, unsigned nbits, un
 
 constexpr unsigned THREADS = 256, MID_SLOTS = 1u << EVAL_MAX_MID;
 
-// partial[(blockIdx.y * EVAL_PASS + i) * gridDim.x + blockIdx.x] = this workgroup's share of poly blockIdx.y at point i < Q
-__global__ __launch_bounds__(THREADS) void mle_eval_kernel(Polys polys, const fe* __restrict__ points, unsigned Q, unsigned n, Split s,
+// partial[(blockIdx.y * EVAL_PASS + i) * gridDim.x + blockIdx.x] = the share of workgroup first_wg + blockIdx.x of the 2^s.top at point
+// i < Q of poly blockIdx.y.  The whole grid is first_wg = 0 and gridDim.x = 2^s.top; a rank of a device set launches its slice
+__global__ __launch_bounds__(THREADS) void mle_eval_kernel(Polys polys, const fe* __restrict__ points, unsigned Q, unsigned n, Split s, unsigned first_wg,
                                                            fe* __restrict__ partial) {
     __shared__ fe29 mid[EVAL_PASS][MID_SLOTS];
     __shared__ fe lo[EVAL_PASS][2][16];
     __shared__ fe top[EVAL_PASS];
     __shared__ fe red[EVAL_PASS][4];
-    const unsigned tid = threadIdx.x, wg = blockIdx.x;
+    const unsigned tid = threadIdx.x, wg = first_wg + blockIdx.x;
     const unsigned n_mid = 1u << s.c, n_lo = 1u << s.bl, n_hi = 1u << s.bh, per = 1 + n_mid + n_lo + n_hi;
     for (unsigned item = tid; item < Q * per; item += THREADS) {
         const unsigned i = item / per, e = item % per;
@@ -134,27 +135,42 @@ __global__ __launch_bounds__(THREADS) void mle_eval_kernel(Polys polys, const fe
             const fe w = fe_mulx(lo[i][1][(tid >> s.bl) & (n_hi - 1)], lo[i][0][tid & (n_lo - 1)]);
             fe v = live ? fe_mulx(pack_canon29(run[i]), w) : fe_zero();
             v = block_sum(v, red[i]);
-            if (tid == 0) fe_store(partial + ((size_t)blockIdx.y * EVAL_PASS + i) * gridDim.x + wg, fe_mulx(v, top[i]));
+            if (tid == 0) fe_store(partial + ((size_t)blockIdx.y * EVAL_PASS + i) * gridDim.x + blockIdx.x, fe_mulx(v, top[i]));
         }
     }
 }
 
-// out[y * out_stride + i] = sum of the n_wg partials of output (y, i), i < count, which start at partial[(y * row_stride + i) * n_wg];
-// one workgroup per output.  Lane j adds the partials j, j + 256, ...: field addition is exact, so the result does not depend on n_wg
-__global__ __launch_bounds__(THREADS) void finish_kernel(const fe* __restrict__ partial, unsigned n_wg, unsigned count, unsigned row_stride,
-                                                         fe* __restrict__ out, unsigned out_stride) {
+// out[y * out_stride + i] = sum of the n_wg partials of output (y, i), i < count; one workgroup per output.  The partials lie in
+// n_wg / chunk blocks, block_stride elements apart, of `chunk` workgroups each: partial j of the output is element
+// (y * row_stride + i) * chunk + j % chunk of block j / chunk.  One block (chunk = n_wg) is a grid's own output; G blocks are what the
+// ranks of a device set gathered from their slices.  Lane j adds the partials j, j + 256, ...: field addition is exact, so the
+// result depends neither on n_wg nor on how the blocks cut it
+__global__ __launch_bounds__(THREADS) void finish_kernel(const fe* __restrict__ partial, unsigned n_wg, unsigned chunk, size_t block_stride, unsigned count,
+                                                         unsigned row_stride, fe* __restrict__ out, unsigned out_stride) {
     __shared__ fe red[4];
     const unsigned y = blockIdx.x / count, i = blockIdx.x % count;
-    const fe* p = partial + ((size_t)y * row_stride + i) * n_wg;
+    const fe* p = partial + ((size_t)y * row_stride + i) * chunk;
     fe acc = fe_zero();
-    for (unsigned j = threadIdx.x; j < n_wg; j += THREADS) acc = fe_add(acc, fe_load(p + j));
+    for (unsigned j = threadIdx.x; j < n_wg; j += THREADS) acc = fe_add(acc, fe_load(p + (j / chunk) * block_stride + j % chunk));
     acc = block_sum(acc, red);
     if (threadIdx.x == 0) fe_store(out + (size_t)y * out_stride + i, acc);
 }
 
 }  // namespace
 
-size_t eval_partial_fes(unsigned batch, unsigned n_vars) { return (size_t)batch * EVAL_PASS * ((size_t)1 << split_for(n_vars).top); }
+unsigned eval_grid(unsigned n_vars) { return 1u << split_for(n_vars).top; }
+
+size_t eval_partial_fes(unsigned batch, unsigned n_vars) { return (size_t)batch * EVAL_PASS * eval_grid(n_vars); }
+
+int eval_slice_launch(hipStream_t stream, const uint64_t* const* d_evals, unsigned batch, unsigned n_vars, const uint64_t* d_points, unsigned Q,
+                      unsigned first_wg, unsigned count, uint64_t* d_partial) {
+    const Split s = split_for(n_vars);
+    if (batch < 1 || batch > EVAL_MAX_BATCH || Q < 1 || Q > EVAL_PASS || !count || first_wg > (1u << s.top) - count) return PK_ERR_BAD_ARG;
+    Polys polys{};
+    for (unsigned b = 0; b < batch; b++) polys.p[b] = (const fe*)d_evals[b];
+    mle_eval_kernel<<<dim3(count, batch), THREADS, 0, stream>>>(polys, (const fe*)d_points, Q, n_vars, s, first_wg, (fe*)d_partial);
+    return hipGetLastError() == hipSuccess ? PK_OK : PK_ERR_HIP;
+}
 
 int eval_launch(hipStream_t stream, const uint64_t* const* d_evals, unsigned batch, unsigned n_vars, const uint64_t* d_points, unsigned q,
                 uint64_t* d_partial, uint64_t* d_out) {
@@ -164,15 +180,16 @@ int eval_launch(hipStream_t stream, const uint64_t* const* d_evals, unsigned bat
     for (unsigned b = 0; b < batch; b++) polys.p[b] = (const fe*)d_evals[b];
     for (unsigned q0 = 0; q0 < q; q0 += EVAL_PASS) {  // stream order keeps a pass's partials until its finish kernel has read them
         const unsigned Q = q - q0 < EVAL_PASS ? q - q0 : EVAL_PASS;
-        mle_eval_kernel<<<dim3(n_wg, batch), THREADS, 0, stream>>>(polys, (const fe*)d_points + (size_t)q0 * n_vars, Q, n_vars, s, (fe*)d_partial);
+        mle_eval_kernel<<<dim3(n_wg, batch), THREADS, 0, stream>>>(polys, (const fe*)d_points + (size_t)q0 * n_vars, Q, n_vars, s, 0, (fe*)d_partial);
         finish_launch(stream, d_partial, n_wg, batch, Q, EVAL_PASS, d_out + 4 * (size_t)q0, q);
     }
     return hipGetLastError() == hipSuccess ? PK_OK : PK_ERR_HIP;
 }
 
 void finish_launch(hipStream_t stream, const uint64_t* d_partial, unsigned n_wg, unsigned rows, unsigned count, unsigned row_stride, uint64_t* d_out,
-                   unsigned out_stride) {
-    finish_kernel<<<rows * count, THREADS, 0, stream>>>((const fe*)d_partial, n_wg, count, row_stride, (fe*)d_out, out_stride);
+                   unsigned out_stride, unsigned chunk, size_t block_stride) {
+    finish_kernel<<<rows * count, THREADS, 0, stream>>>((const fe*)d_partial, n_wg, chunk ? chunk : n_wg, block_stride, count, row_stride, (fe*)d_out,
+                                                        out_stride);
 }
 
 }  // namespace pkw

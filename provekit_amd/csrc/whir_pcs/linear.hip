@@ -36,11 +36,13 @@ struct WsumArgs {
     const fe* w[WSUM_PASS];
 };
 
-// partial[((b * L + i) * gridDim.x + blockIdx.x] = this workgroup's share of <w_i, f_b>, b < batch, i < L (the pass's weights)
+// partial[((b * L + i) * gridDim.x + blockIdx.x] = the share of workgroup first_wg + blockIdx.x of a grid of n_wg of <w_i, f_b>, b < batch,
+// i < L (the pass's weights).  The whole grid is first_wg = 0 and gridDim.x = n_wg; a rank of a device set launches its slice
 template <int TB, int TW>
-__global__ __launch_bounds__(THREADS) void weighted_sums_kernel(WsumArgs a, unsigned batch, unsigned L, size_t N, fe* __restrict__ partial) {
+__global__ __launch_bounds__(THREADS) void weighted_sums_kernel(WsumArgs a, unsigned batch, unsigned L, size_t N, unsigned first_wg, unsigned n_wg,
+                                                                fe* __restrict__ partial) {
     __shared__ fe red[TB * TW][4];
-    const unsigned tid = threadIdx.x, wg = blockIdx.x;
+    const unsigned tid = threadIdx.x, wg = first_wg + blockIdx.x;
     const unsigned w_tiles = (L + TW - 1) / TW;
     const unsigned b0 = (blockIdx.y / w_tiles) * TB, i0 = (blockIdx.y % w_tiles) * TW;
     const fe* f[TB];
@@ -51,7 +53,7 @@ __global__ __launch_bounds__(THREADS) void weighted_sums_kernel(WsumArgs a, unsi
     for (int v = 0; v < TW; v++) w[v] = a.w[i0 + v < L ? i0 + v : i0];
     WsumTile<TB, TW> t;
     wsum_tile_init(t);
-    for (size_t x = (size_t)wg * THREADS + tid; x < N; x += (size_t)gridDim.x * THREADS) {
+    for (size_t x = (size_t)wg * THREADS + tid; x < N; x += (size_t)n_wg * THREADS) {
         fe fv[TB], wv[TW];
 #pragma unroll
         for (int u = 0; u < TB; u++) fv[u] = fe_load(f[u] + x);
@@ -64,7 +66,7 @@ __global__ __launch_bounds__(THREADS) void weighted_sums_kernel(WsumArgs a, unsi
 #pragma unroll
         for (int v = 0; v < TW; v++) {
             const fe s = block_sum(wsum_tile_result(t, u, v), red[u * TW + v]);
-            if (tid == 0 && b0 + u < batch && i0 + v < L) fe_store(partial + ((size_t)(b0 + u) * L + (i0 + v)) * gridDim.x + wg, s);
+            if (tid == 0 && b0 + u < batch && i0 + v < L) fe_store(partial + ((size_t)(b0 + u) * L + (i0 + v)) * gridDim.x + blockIdx.x, s);
         }
 }
 
@@ -88,9 +90,19 @@ __global__ __launch_bounds__(THREADS) void combine_kernel(fe* __restrict__ dst, 
 }
 
 template <int TB, int TW>
-void wsum_pass(hipStream_t stream, const WsumArgs& a, unsigned batch, unsigned L, size_t N, unsigned grid, fe* partial) {
+void wsum_pass(hipStream_t stream, const WsumArgs& a, unsigned batch, unsigned L, size_t N, unsigned grid, unsigned first_wg, unsigned count, fe* partial) {
     const unsigned tiles = ((batch + TB - 1) / TB) * ((L + TW - 1) / TW);
-    weighted_sums_kernel<TB, TW><<<dim3(grid, tiles), THREADS, 0, stream>>>(a, batch, L, N, partial);
+    weighted_sums_kernel<TB, TW><<<dim3(count, tiles), THREADS, 0, stream>>>(a, batch, L, N, first_wg, grid, partial);
+}
+// tile 0: 2 x 2, except that ONE polynomial takes 1 x 4 -- half of a 2 x 2 tile's products would repeat its first row
+void wsum_pass_tiled(hipStream_t stream, const WsumArgs& a, unsigned batch, unsigned L, size_t N, unsigned grid, unsigned first_wg, unsigned count,
+                     fe* partial, int tile) {
+    if (tile == 1 || (tile == 0 && batch == 1))
+        wsum_pass<1, 4>(stream, a, batch, L, N, grid, first_wg, count, partial);
+    else if (tile == 2)
+        wsum_pass<2, 1>(stream, a, batch, L, N, grid, first_wg, count, partial);
+    else
+        wsum_pass<(int)WSUM_TILE_B, (int)WSUM_TILE_W>(stream, a, batch, L, N, grid, first_wg, count, partial);
 }
 
 }  // namespace
@@ -113,15 +125,21 @@ int wsum_launch(hipStream_t stream, const uint64_t* const* d_evals, unsigned bat
     for (unsigned i0 = 0; i0 < l; i0 += WSUM_PASS) {  // stream order keeps a pass's partials until the finish kernel has read them
         const unsigned L = l - i0 < WSUM_PASS ? l - i0 : WSUM_PASS;
         for (unsigned i = 0; i < L; i++) a.w[i] = (const fe*)d_weights[i0 + i];
-        // tile 0: 2 x 2, except that ONE polynomial takes 1 x 4 -- half of a 2 x 2 tile's products would repeat its first row
-        if (tile == 1 || (tile == 0 && batch == 1))
-            wsum_pass<1, 4>(stream, a, batch, L, N, grid, (fe*)d_partial);
-        else if (tile == 2)
-            wsum_pass<2, 1>(stream, a, batch, L, N, grid, (fe*)d_partial);
-        else
-            wsum_pass<(int)WSUM_TILE_B, (int)WSUM_TILE_W>(stream, a, batch, L, N, grid, (fe*)d_partial);
+        wsum_pass_tiled(stream, a, batch, L, N, grid, 0, grid, (fe*)d_partial, tile);
         finish_launch(stream, d_partial, grid, batch, L, L, d_out + 4 * (size_t)i0, l);
     }
+    return hipGetLastError() == hipSuccess ? PK_OK : PK_ERR_HIP;
+}
+
+int wsum_slice_launch(hipStream_t stream, const uint64_t* const* d_evals, unsigned batch, unsigned n_vars, const uint64_t* const* d_weights, unsigned L,
+                      unsigned first_wg, unsigned count, uint64_t* d_partial, unsigned grid, int tile) {
+    if (!grid) grid = wsum_grid(n_vars);
+    if (batch < 1 || batch > WSUM_MAX_BATCH || L < 1 || L > WSUM_PASS || grid > wsum_grid(n_vars) || !count || count > grid || first_wg > grid - count)
+        return PK_ERR_BAD_ARG;
+    WsumArgs a{};
+    for (unsigned b = 0; b < batch; b++) a.f[b] = (const fe*)d_evals[b];
+    for (unsigned i = 0; i < L; i++) a.w[i] = (const fe*)d_weights[i];
+    wsum_pass_tiled(stream, a, batch, L, (size_t)1 << n_vars, grid, first_wg, count, (fe*)d_partial, tile);
     return hipGetLastError() == hipSuccess ? PK_OK : PK_ERR_HIP;
 }
 

@@ -24,6 +24,11 @@ size_t wsum_partial_fes(unsigned batch, unsigned n_vars);
 // against it: tools/whir_pcs_linear_bench.py).  Tile 3 = 2 x 2 always.
 int wsum_launch(hipStream_t stream, const uint64_t* const* d_evals, unsigned batch, unsigned n_vars, const uint64_t* const* d_weights, unsigned l,
                 uint64_t* d_partial, uint64_t* d_out, unsigned grid = 0, int tile = 0);
+// One pass (L <= WSUM_PASS weights) of the same kernel over the workgroups [first_wg, first_wg + count) of a grid of `grid` alone: what a
+// rank of a device set runs (pcs.cpp) and tools/probes measures.  d_partial[(b * L + i) * count + j] = the share of workgroup
+// first_wg + j: batch * L * count elements, to be finished with chunk = count next to the other slices' blocks
+int wsum_slice_launch(hipStream_t stream, const uint64_t* const* d_evals, unsigned batch, unsigned n_vars, const uint64_t* const* d_weights, unsigned L,
+                      unsigned first_wg, unsigned count, uint64_t* d_partial, unsigned grid = 0, int tile = 0);
 // enqueue on `stream`: d_w[x] = (accumulate ? d_w[x] : 0) + sum_i scales[i] * d_weights[i][x] over `len` elements; scales: l HOST
 // elements (Montgomery, < p).  Each weight is read once; d_w is read (when accumulating) and written once per COMB_TILE weights.
 int combine_launch(hipStream_t stream, uint64_t* d_w, size_t len, const uint64_t* const* d_weights, const uint64_t* scales, unsigned l, int accumulate);

@@ -10,6 +10,15 @@
 // pkw_open_sparse states the same constraints as index/value lists: the same three steps, each by its twin in sparse.hip.
 // pkw_commit_hiding / pkw_open_hiding (provekit_whir_hiding.h) are pkw_commit and pkw_open over the extended batch: hiding.hip draws
 // the masks and g, and the opening is the plain one at the points (0, z_i) under the hiding label.
+//
+// DEVICE SETS.  A scheme on a context of a device set (G ranks, one host thread each, every rank making the same calls with the same
+// inputs) shards what pk_commit_into / pk_commit_open shard, under the layouts they report, and the two ALU-bound reductions of the
+// statement: rank g runs the workgroups [g n_wg / G, (g + 1) n_wg / G) of the evaluation and weighted-sums kernels, one
+// pk_comm_all_gather per pass exchanges the slices' partials, and the finish kernel adds the gathered blocks on every rank -- the
+// partials are fully reduced and field addition is exact, so the bits are the lone grid's.  Everything else stays replicated.
+// The library can only call what provekit_hip.h declares, so a rank must never skip a collective its peers will enter: refusals
+// every rank makes identically come before any collective, and after every rank-local step that can fail the ranks exchange their
+// status (exchange() below; the slice passes carry it inside the gather they make anyway) and leave together.
 #include <hip/hip_runtime.h>
 #include <sys/random.h>
 
@@ -33,6 +42,12 @@ struct pkw_scheme {
     hipStream_t stream = nullptr;  // the evaluation kernel's
     uint64_t* arena = nullptr;
     size_t arena_fes = 0;
+    pkw::Plan plan;  // the arena's, under the context's device set
+    // a device set: this rank, the ranks, and the buffer their exchanges go through: a send block of xchg_send_fes elements, then
+    // room for every rank's
+    unsigned rank = 0, world = 1;
+    uint64_t* xchg = nullptr;
+    size_t xchg_send_fes = 0;
 };
 
 struct pkw_commitment {
@@ -70,6 +85,35 @@ int fail(pkw_scheme* s, int rc, const std::string& why) {
     return rc;
 }
 
+// ---- device sets: what the ranks tell each other outside the product's own sharded calls ------------------------------------------
+// One small all-gather: every rank contributes 32 bytes and the status of its rank-local work so far, and gets every rank's 32 bytes
+// (all: world * 32 bytes, may be null) and the FIRST non-zero status of the set in rank order, so that all ranks leave together before
+// the next sharded product call.  Outside a set: the status itself, nothing is enqueued.  A failure of the exchange itself is the
+// communicator's (PK_ERR_RCCL): the product has poisoned it for every rank by then
+int exchange(pkw_scheme* s, int status, const uint8_t mine[32], uint8_t* all) {
+    if (s->world == 1) {
+        if (all && mine) memcpy(all, mine, 32);
+        return status;
+    }
+    uint64_t block[8] = {};
+    if (mine) memcpy(block, mine, 32);
+    block[4] = (uint64_t)(int64_t)status;
+    std::vector<uint64_t> got(8 * (size_t)s->world);
+    uint64_t *send = s->xchg, *recv = s->xchg + 4 * s->xchg_send_fes;
+    int rc = pk_memcpy_h2d(s->ctx, send, block, sizeof block);
+    if (!rc) rc = pk_comm_all_gather(s->ctx, send, recv, sizeof block);
+    if (!rc) rc = pk_memcpy_d2h(s->ctx, got.data(), recv, sizeof block * s->world);
+    if (rc) return fail(s, rc, std::string("exchange between the ranks: ") + pk_last_error(s->ctx));
+    for (unsigned g = 0; g < s->world; g++)
+        if (all) memcpy(all + 32 * (size_t)g, &got[8 * (size_t)g], 32);
+    for (unsigned g = 0; g < s->world; g++)
+        if (const int theirs = (int)(int64_t)got[8 * (size_t)g + 4]) {
+            if (g != s->rank || s->err.empty()) s->err = "rank " + std::to_string(g) + " of the device set failed with status " + std::to_string(theirs);
+            return theirs;
+        }
+    return PK_OK;
+}
+
 // the arena, handed out front to back; an opening starts from the front again
 struct Bump {
     uint64_t* base;
@@ -82,6 +126,7 @@ struct Bump {
         return p;
     }
 };
+constexpr int RANKS_DISAGREE = -1000;  // Opening::run to open_checked, which names it: never a status of the ABI
 #define TAKE(var, fes)                         \
     uint64_t* var = A.take(fes);               \
     if (!var) return PK_ERR_OOM /* plan() and the opening disagree: a bug of this file */
@@ -193,11 +238,60 @@ struct Opening {
         return PK_OK;
     }
 
+    // ---- rank slices of the two reductions (a device set).  slice(n_wg) = the workgroups per rank, 0 = the pass runs replicated:
+    // outside a set, with fewer workgroups than ranks, or when the ranks do not divide them
+    unsigned slice(unsigned n_wg) const { return S.world > 1 && n_wg >= S.world && n_wg % S.world == 0 ? n_wg / S.world : 0; }
+    uint64_t* slice_partials() const { return S.xchg; }
+    // After this rank's slice of a pass was enqueued on the scheme's stream with `status`: its P partials and the status travel in one
+    // all-gather, every rank returns the first non-zero status of the set, and the finish kernel adds the G gathered blocks of
+    // `chunk` workgroups each: d_out[y * out_stride + i] for y < rows, i < count
+    int gather_finish(int status, size_t P, unsigned chunk, unsigned rows, unsigned count, unsigned row_stride, uint64_t* d_out, unsigned out_stride) {
+        if (hipStreamSynchronize(S.stream) != hipSuccess && !status) status = PK_ERR_HIP;
+        uint64_t *send = S.xchg, *recv = S.xchg + 4 * S.xchg_send_fes;
+        uint64_t st[4] = {(uint64_t)(int64_t)status, 0, 0, 0};
+        CK(pk_memcpy_h2d(ctx, send + 4 * P, st, sizeof st));
+        CK(pk_comm_all_gather(ctx, send, recv, 32 * (P + 1)));
+        CK(pk_ctx_sync(ctx));
+        for (unsigned g = 0; g < S.world; g++) {
+            CK(pk_memcpy_d2h(ctx, st, recv + 4 * (g * (P + 1) + P), 8));
+            if (const int theirs = (int)(int64_t)st[0]) {
+                S.err = "rank " + std::to_string(g) + " of the device set failed in its slice of a reduction with status " + std::to_string(theirs);
+                return theirs;
+            }
+        }
+        finish_launch(S.stream, recv, chunk * S.world, rows, count, row_stride, d_out, out_stride, chunk, P + 1);
+        return hipGetLastError() == hipSuccess ? PK_OK : PK_ERR_HIP;
+    }
+    // eval_launch, every pass sliced over the ranks where slice() allows
+    int evaluations(const uint64_t* const* d_evals, unsigned batch, const uint64_t* d_points, unsigned q, uint64_t* d_part, uint64_t* d_out) {
+        const unsigned per = slice(eval_grid(n));
+        if (!per) return eval_launch(S.stream, d_evals, batch, n, d_points, q, d_part, d_out);
+        if ((size_t)batch * EVAL_PASS * per + 1 > S.xchg_send_fes) return PK_ERR_OOM;  // every rank alike, before any launch or collective
+        for (unsigned q0 = 0; q0 < q; q0 += EVAL_PASS) {
+            const unsigned Q = std::min(EVAL_PASS, q - q0);
+            const int rc = eval_slice_launch(S.stream, d_evals, batch, n, d_points + 4 * (size_t)q0 * n, Q, S.rank * per, per, slice_partials());
+            CK(gather_finish(rc, (size_t)batch * EVAL_PASS * per, per, batch, Q, EVAL_PASS, d_out + 4 * (size_t)q0, q));
+        }
+        return PK_OK;
+    }
+    // wsum_launch, likewise
+    int dense_sums(const Statement& W, uint64_t* d_part, uint64_t* d_out) {
+        const unsigned batch = cfg.batch_size, per = slice(wsum_grid(n));
+        if (!per) return wsum_launch(S.stream, C.evals, batch, n, W.dense, W.l, d_part, d_out);
+        if ((size_t)batch * WSUM_PASS * per + 1 > S.xchg_send_fes) return PK_ERR_OOM;  // every rank alike, before any launch or collective
+        for (unsigned i0 = 0; i0 < W.l; i0 += WSUM_PASS) {
+            const unsigned L = std::min(WSUM_PASS, W.l - i0);
+            const int rc = wsum_slice_launch(S.stream, C.evals, batch, n, W.dense + i0, L, S.rank * per, per, slice_partials());
+            CK(gather_finish(rc, (size_t)batch * L * per, per, batch, L, L, d_out + 4 * (size_t)i0, W.l));
+        }
+        return PK_OK;
+    }
+
     // the three steps that read the statement's weights: dense device tables, or validated index/value lists.
     // d_out[b * l + i] = <w_i, poly_b>
     int weight_sums(const Statement& W, uint64_t* d_part, uint64_t* d_out) {
         if (W.sparse) return sparse_sums_launch(S.stream, C.evals, cfg.batch_size, n, *W.sparse, d_part, d_out);
-        return wsum_launch(S.stream, C.evals, cfg.batch_size, n, W.dense, W.l, d_part, d_out);
+        return dense_sums(W, d_part, d_out);
     }
     // d_w += sum_i scales[i] w_i
     int weight_combine(const Statement& W, uint64_t* d_w, const fe* scales) {
@@ -208,9 +302,9 @@ struct Opening {
     // partials for EVAL_MAX_BATCH tables go into the commit scratch, idle by now); the lists' partials go where the sums' went
     int weight_deferred(const Statement& W, const uint64_t* d_point, uint64_t* d_part, uint64_t* scratch, uint64_t* d_out) {
         if (W.sparse) return sparse_evaluate_launch(S.stream, n, *W.sparse, d_point, d_part, d_out);
-        if (eval_partial_fes(EVAL_MAX_BATCH, n) > plan(cfg).scratch) return PK_ERR_OOM;
+        if (eval_partial_fes(EVAL_MAX_BATCH, n) > S.plan.scratch) return PK_ERR_OOM;
         for (unsigned i0 = 0; i0 < W.l; i0 += EVAL_MAX_BATCH)
-            CK(eval_launch(S.stream, W.dense + i0, std::min(EVAL_MAX_BATCH, W.l - i0), n, d_point, 1, scratch, d_out + 4 * (size_t)i0));
+            CK(evaluations(W.dense + i0, std::min(EVAL_MAX_BATCH, W.l - i0), d_point, 1, scratch, d_out + 4 * (size_t)i0));
         return PK_OK;
     }
 
@@ -219,7 +313,7 @@ struct Opening {
         const size_t N = (size_t)1 << n;
         const unsigned batch = cfg.batch_size, q = W.q, l = W.l;
         const fe *points = reinterpret_cast<const fe*>(W.points), *tags = reinterpret_cast<const fe*>(W.tags);
-        TAKE(scratch, plan(cfg).scratch);
+        TAKE(scratch, S.plan.scratch);
         // 1-3: the commitment's transcript (mtUtilities.go:51-76)
         T.add_canon(pk::load_raw(C.root));
         std::vector<fe> ood(cfg.commitment_ood_samples), ood_ans((size_t)batch * ood.size());
@@ -240,7 +334,7 @@ struct Opening {
         if (q) {
             CK(pk_memcpy_h2d(ctx, d_pts, points, 32 * (size_t)q * n));
             CK(pk_ctx_sync(ctx));
-            CK(eval_launch(S.stream, C.evals, batch, n, d_pts, q, d_part, d_out));
+            CK(evaluations(C.evals, batch, d_pts, q, d_part, d_out));
             if (hipStreamSynchronize(S.stream) != hipSuccess) return PK_ERR_HIP;
             CK(pk_memcpy_d2h(ctx, evals, d_out, 32 * (size_t)batch * q));
         }
@@ -251,6 +345,13 @@ struct Opening {
             CK(pk_memcpy_d2h(ctx, sums, d_out, 32 * (size_t)batch * l));
         }
         T.add_scalars(sums, (size_t)batch * l);
+        if (S.world > 1) {  // the statement is absorbed: the ranks hold the same sponge, or leave together before the first STIR opening
+            const fe mine = T.peek_challenge();
+            std::vector<uint8_t> all(32 * (size_t)S.world);
+            CK(exchange(&S, PK_OK, (const uint8_t*)mine.v, all.data()));
+            for (unsigned g = 1; g < S.world; g++)
+                if (memcmp(all.data(), all.data() + 32 * (size_t)g, 32)) return RANKS_DISAGREE;
+        }
         // 6: whir::Prover::prove over the beta-combined polynomial
         TAKE(d_c0, N);
         uint64_t* d_c = d_c0;
@@ -293,8 +394,10 @@ struct Opening {
             Tree next{};
             next.rows = (size_t)1 << (nv + rate - k);
             next.width = (size_t)1 << k;
-            TAKE(leaves, next.rows * next.width);
-            TAKE(nodes, 2 * next.rows);
+            size_t leaves_fes = 0, nodes_fes = 0;  // a rank of a device set keeps its rows of a sharded codeword: what the arena was planned with
+            CK(pk_commit_sizes(ctx, 1, nv, rate, k, &leaves_fes, &nodes_fes, nullptr));
+            TAKE(leaves, leaves_fes);
+            TAKE(nodes, nodes_fes);
             next.leaves = leaves, next.nodes = nodes;
             fe root;
             const uint64_t* cp[1] = {d_c};
@@ -360,14 +463,40 @@ int pkw_scheme_create(pk_ctx* ctx, const pk_whir_config* cfg, pkw_scheme** out) 
     std::string why;
     if (!pkw::config_ok(cfg, why)) return pkw::refuse(why);
     int rank = 0, world = 1, kind = 0;
-    if (pk_comm_info(ctx, &rank, &world, &kind) == PK_OK && world > 1) return pkw::refuse("contexts of a device set are not supported");
+    if (pk_comm_info(ctx, &rank, &world, &kind) != PK_OK || world < 1 || rank < 0 || rank >= world) return pkw::refuse("the context's communicator");
+    // The arena under the context's device set: pk_commit_sizes for every commit of an opening.  A rank keeps 1 / G of a sharded
+    // codeword, never more than the whole; the sharded commit's scratch (the encode's staging plus local and gathered digests) may
+    // exceed the lone one's by up to 1.5 digests per row (G = 2, and narrow codewords at G = 4), which is what the bound below allows
+    // on top of the host-only figure of pkw_scheme_arena_bytes.  Checked here, not assumed
+    pkw::Plan planned;
+    const pkw::Plan lone = pkw::plan(*cfg);
+    bool leaves_grew = false;
+    const unsigned fold = cfg->folding_factor;
+    const int prc = pkw::plan_with(*cfg, [&](unsigned batch, unsigned nv, unsigned rate, size_t* leaves, size_t* nodes, size_t* scratch) {
+        const int rc = pk_commit_sizes(ctx, batch, nv, rate, fold, leaves, nodes, scratch);
+        const size_t rows = (size_t)1 << (nv + rate - fold), width = (size_t)batch << fold;
+        if (!rc && (*leaves > rows * width || *nodes > 2 * rows)) leaves_grew = true;
+        return rc;
+    }, planned);
+    if (prc) return pkw::refuse("pk_commit_sizes refuses this config");
+    const size_t rows0 = (size_t)1 << (cfg->n_vars + cfg->starting_log_inv_rate - fold);
+    if (leaves_grew || planned.total > lone.total + 2 * rows0)
+        return pkw::refuse("the arena under this device set exceeds pkw_scheme_arena_bytes by more than 64 bytes per row of the codeword");
     try {
         pkw_scheme* s = new pkw_scheme();
         s->ctx = ctx;
         s->cfg = *cfg;
-        s->arena_fes = pkw::plan(*cfg).total;
+        s->rank = (unsigned)rank, s->world = (unsigned)world;
+        s->plan = planned;
+        s->arena_fes = planned.total;
         int rc = pk_ctx_sync(ctx);  // selects the context's device on this thread
         if (!rc) rc = pk_malloc(ctx, 32 * s->arena_fes, (void**)&s->arena);
+        if (!rc && world > 1) {  // a slice's partials and its status; then every rank's
+            const unsigned n = cfg->n_vars;
+            const size_t pass = std::max(pkw::eval_partial_fes(pkw::EVAL_MAX_BATCH, n), pkw::wsum_partial_fes(pkw::WSUM_MAX_BATCH, n));
+            s->xchg_send_fes = pkw::round8(pass / 2 + 2);  // at least two ranks share a pass; never less than an Exchange block
+            rc = pk_malloc(ctx, 32 * (s->xchg_send_fes + pkw::round8(pass + 2 * (size_t)world)), (void**)&s->xchg);
+        }
         if (!rc && hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess) rc = PK_ERR_HIP;
         if (rc) {
             pkw::g_error = std::string("arena: ") + pk_last_error(ctx);
@@ -388,28 +517,36 @@ int pkw_scheme_destroy(pkw_scheme* s) {
     pk_ctx_sync(s->ctx);  // also selects the device
     if (s->stream) (void)hipStreamDestroy(s->stream);
     if (s->arena) pk_free(s->ctx, s->arena);
+    if (s->xchg) pk_free(s->ctx, s->xchg);
     delete s;
     return PK_OK;
 }
 
-int pkw_commit(pkw_scheme* s, const uint64_t* const* d_evals, pkw_commitment** out) {
-    if (out) *out = nullptr;
-    if (!s) return PK_ERR_BAD_ARG;
-    if (!d_evals || !out) return pkw::fail(s, PK_ERR_BAD_ARG, "null pointer");
+}  // extern "C"
+
+namespace pkw {
+namespace {
+
+// pkw_commit after its refusals.  `rc`: the status of the caller's own rank-local work (pkw_commit_hiding's block and masks); what
+// fails here before the commit is rank-local too (the allocation, the copies, the coefficient forms), so in a device set the ranks
+// exchange their status once, and all of them leave with the first failure before pk_commit_into enters its collectives
+int commit_checked(pkw_scheme* s, const uint64_t* const* d_evals, int rc, pkw_commitment** out) {
     const pk_whir_config& c = s->cfg;
-    for (unsigned b = 0; b < c.batch_size; b++)
-        if (!d_evals[b]) return pkw::fail(s, PK_ERR_BAD_ARG, "null polynomial");
     pkw_commitment* com = nullptr;
-    try {
-        com = new pkw_commitment();
-    } catch (...) {
-        return pkw::fail(s, PK_ERR_OOM, "out of memory");
+    if (!rc) {
+        s->err.clear();
+        try {
+            com = new pkw_commitment();
+        } catch (...) {
+            rc = fail(s, PK_ERR_OOM, "out of memory");
+        }
     }
+    if (rc) return exchange(s, rc, nullptr, nullptr);
     com->scheme = s;
     com->ctx = s->ctx;
     const size_t N = (size_t)1 << c.n_vars;
     size_t leaves_fes = 0, nodes_fes = 0, scratch_fes = 0;
-    int rc = pk_commit_sizes(s->ctx, c.batch_size, c.n_vars, c.starting_log_inv_rate, c.folding_factor, &leaves_fes, &nodes_fes, &scratch_fes);
+    rc = pk_commit_sizes(s->ctx, c.batch_size, c.n_vars, c.starting_log_inv_rate, c.folding_factor, &leaves_fes, &nodes_fes, &scratch_fes);
     if (!rc && scratch_fes > s->arena_fes) rc = PK_ERR_OOM;
     if (!rc) rc = pk_malloc(s->ctx, 32 * (2 * c.batch_size * N + leaves_fes + nodes_fes), (void**)&com->block);
     if (!rc) {
@@ -426,10 +563,14 @@ int pkw_commit(pkw_scheme* s, const uint64_t* const* d_evals, pkw_commitment** o
         com->nodes = at + 4 * leaves_fes;
         com->rows = (size_t)1 << (c.n_vars + c.starting_log_inv_rate - c.folding_factor);
         com->width = (size_t)c.batch_size << c.folding_factor;
-        if (!rc)
-            rc = pk_commit_into(s->ctx, com->coeffs, c.batch_size, c.n_vars, c.starting_log_inv_rate, c.folding_factor, com->leaves, com->nodes, s->arena,
-                                com->root, &com->layout);
     }
+    if (rc) s->err = std::string("commit: ") + pk_last_error(s->ctx);
+    if ((rc = exchange(s, rc, nullptr, nullptr))) {
+        pkw_commitment_destroy(com);
+        return rc;
+    }
+    rc = pk_commit_into(s->ctx, com->coeffs, c.batch_size, c.n_vars, c.starting_log_inv_rate, c.folding_factor, com->leaves, com->nodes, s->arena, com->root,
+                        &com->layout);
     if (rc) {
         s->err = std::string("commit: ") + pk_last_error(s->ctx);
         pkw_commitment_destroy(com);
@@ -437,6 +578,20 @@ int pkw_commit(pkw_scheme* s, const uint64_t* const* d_evals, pkw_commitment** o
     }
     *out = com;
     return PK_OK;
+}
+
+}  // namespace
+}  // namespace pkw
+
+extern "C" {
+
+int pkw_commit(pkw_scheme* s, const uint64_t* const* d_evals, pkw_commitment** out) {
+    if (out) *out = nullptr;
+    if (!s) return PK_ERR_BAD_ARG;
+    if (!d_evals || !out) return pkw::fail(s, PK_ERR_BAD_ARG, "null pointer");
+    for (unsigned b = 0; b < s->cfg.batch_size; b++)
+        if (!d_evals[b]) return pkw::fail(s, PK_ERR_BAD_ARG, "null polynomial");
+    return pkw::commit_checked(s, d_evals, PK_OK, out);
 }
 
 int pkw_commitment_root(const pkw_commitment* com, uint8_t root[32]) {
@@ -477,7 +632,10 @@ int open_checked(pkw_scheme* s, const pkw_commitment* com, const Statement& st, 
         const size_t batch = s->cfg.batch_size;
         std::vector<fe> evals(batch * st.q + 1), sums(batch * st.l + 1);
         Opening op(*s, *com, T);
+        s->err.clear();
         const int rc = op.run(st, evals.data(), sums.data());
+        if (rc == RANKS_DISAGREE) return fail(s, PK_ERR_BAD_ARG, "ranks disagree on the statement: every rank of a device set opens with the same inputs");
+        if (rc && !s->err.empty()) return rc;  // a status of the set, named by the exchange that found it
         if (rc) return fail(s, rc, rc == PK_ERR_OOM ? "the arena is too small for this opening" : std::string("open: ") + pk_last_error(s->ctx));
         if (!T.finished()) return fail(s, PK_ERR_IO_PATTERN, T.violation().empty() ? "the proof ended before its IO pattern did" : T.violation());
         *len = T.narg.size();
@@ -519,7 +677,7 @@ int pkw_open_linear(pkw_scheme* s, const pkw_commitment* com, const uint64_t* po
     // the scratch both kernels borrow, checked before any work: the sums' partials go where the evaluation's do, the deferred
     // evaluation's (EVAL_MAX_BATCH tables per launch) into the commit scratch
     const unsigned n = s->cfg.n_vars, batch = s->cfg.batch_size;
-    if (pkw::wsum_partial_fes(batch, n) > pkw::eval_partial_fes(batch, n) || pkw::eval_partial_fes(pkw::EVAL_MAX_BATCH, n) > pkw::plan(s->cfg).scratch)
+    if (pkw::wsum_partial_fes(batch, n) > pkw::eval_partial_fes(batch, n) || pkw::eval_partial_fes(pkw::EVAL_MAX_BATCH, n) > s->plan.scratch)
         return pkw::fail(s, PK_ERR_BAD_ARG, "this config's arena is too small for a linear opening");
     return pkw::open_checked(s, com, st, evals_out, sums_out, proof_out, cap, len);
 }
@@ -545,8 +703,13 @@ int pkw_open_sparse(pkw_scheme* s, const pkw_commitment* com, const uint64_t* po
         uint32_t at = 0, prev = 0;
         int rc = pk_ctx_sync(s->ctx);  // the lists are the context's work: there before the pass reads them
         if (!rc) rc = pkw::sparse_validate(s->ctx, s->stream, w, n, s->arena, &bad, &at, &prev);
-        if (rc) return pkw::fail(s, rc, std::string("open: ") + pk_last_error(s->ctx));
-        if (bad != ~(size_t)0) return pkw::fail(s, PK_ERR_BAD_ARG, pkw::sparse_index_reason(w, bad, at, prev, n));
+        // the pass and its readback are rank-local: the ranks of a device set exchange what they found and refuse or go on together
+        s->err.clear();
+        if (rc)
+            s->err = std::string("open: ") + pk_last_error(s->ctx);
+        else if (bad != ~(size_t)0)
+            rc = pkw::fail(s, PK_ERR_BAD_ARG, pkw::sparse_index_reason(w, bad, at, prev, n));
+        if ((rc = pkw::exchange(s, rc, nullptr, nullptr))) return rc;
     } catch (...) {
         return pkw::fail(s, PK_ERR_OOM, "out of memory");
     }
@@ -575,33 +738,44 @@ int pkw_commit_hiding(pkw_scheme* s, const uint64_t* const* d_evals, const uint8
     for (unsigned b = 0; b < polys; b++)
         if (!d_evals[b]) return pkw::fail(s, PK_ERR_BAD_ARG, "null polynomial");
     uint8_t key[32];
+    int rc = PK_OK;
+    s->err.clear();
     if (rng_seed32) {
         memcpy(key, rng_seed32, 32);
     } else {
-        for (size_t got = 0; got < 32;) {
+        for (size_t got = 0; got < 32 && !rc;) {
             const ssize_t r = getrandom(key + got, 32 - got, 0);
             if (r < 0 && errno == EINTR) continue;
-            if (r < 0) return pkw::fail(s, PK_ERR_HIP, std::string("getrandom failed: ") + strerror(errno));
-            got += (size_t)r;
+            if (r < 0) rc = pkw::fail(s, PK_ERR_HIP, std::string("getrandom failed: ") + strerror(errno));
+            got += r < 0 ? 0 : (size_t)r;
+        }
+        // a device set commits to ONE batch: every rank draws, rank 0's key is the set's (its block comes first)
+        if (s->world > 1) {
+            uint8_t all[32 * PK_MAX_RANKS];
+            if (s->world > PK_MAX_RANKS) return pkw::fail(s, PK_ERR_BAD_ARG, "more ranks than PK_MAX_RANKS");
+            rc = pkw::exchange(s, rc, key, all);
+            if (!rc) memcpy(key, all, 32);
+            explicit_bzero(all, sizeof all);
+        }
+        if (rc) {
+            explicit_bzero(key, sizeof key);
+            return rc;  // every rank alike
         }
     }
+    // from here on a failure is this rank's alone: it travels into pkw_commit's exchange (commit_checked), where the ranks leave together
     pkw_hiding_commitment* com = nullptr;
     try {
         com = new pkw_hiding_commitment();
     } catch (...) {
-        return pkw::fail(s, PK_ERR_OOM, "out of memory");
+        rc = pkw::fail(s, PK_ERR_OOM, "out of memory");
     }
     const size_t N = (size_t)1 << n;
     uint64_t* block = nullptr;
-    int rc = pk_malloc(s->ctx, 32 * (size_t)(polys + 1) * 2 * N, (void**)&block);
-    if (rc) {
-        delete com;
-        return pkw::fail(s, rc, std::string("commit: ") + pk_last_error(s->ctx));
-    }
+    if (!rc && (rc = pk_malloc(s->ctx, 32 * (size_t)(polys + 1) * 2 * N, (void**)&block))) s->err = std::string("commit: ") + pk_last_error(s->ctx);
     uint64_t* tables[pkw::HIDING_MAX_POLYS + 1] = {};
-    for (unsigned b = 0; b <= polys; b++) tables[b] = block + 4 * (size_t)b * 2 * N;
-    rc = pk_ctx_sync(s->ctx);  // also selects the device; the block is the context's allocation
-    if (rc) s->err = std::string("commit: ") + pk_last_error(s->ctx);
+    for (unsigned b = 0; b <= polys && block; b++) tables[b] = block + 4 * (size_t)b * 2 * N;
+    if (!rc && (rc = pk_ctx_sync(s->ctx)))  // also selects the device; the block is the context's allocation
+        s->err = std::string("commit: ") + pk_last_error(s->ctx);
     hipError_t launched = hipSuccess;
     if (!rc && (rc = pkw::hiding_fill_launch(s->stream, tables, polys, n, key, 0, &launched)))
         s->err = std::string("commit: the launch that draws the masks: ") + hipGetErrorString(launched);
@@ -612,9 +786,13 @@ int pkw_commit_hiding(pkw_scheme* s, const uint64_t* const* d_evals, const uint8
         rc = PK_ERR_HIP;
         s->err = std::string("commit: the kernel that draws the masks: ") + hipGetErrorString(drawn);
     }
-    if (!rc) rc = pkw_commit(s, tables, &com->inner);  // sets the scheme's error itself
+    {  // sets the scheme's error itself, unless the failure is the one handed in
+        pkw_commitment* inner = nullptr;
+        rc = pkw::commit_checked(s, tables, rc, &inner);
+        if (com) com->inner = inner;
+    }
     pk_ctx_sync(s->ctx);  // the copies out of the block are done before it goes
-    pk_free(s->ctx, block);
+    if (block) pk_free(s->ctx, block);
     explicit_bzero(key, sizeof key);
     if (rc) {
         delete com;

@@ -104,18 +104,22 @@ inline std::string io_pattern(const pk_whir_config& c, unsigned q, unsigned l = 
     return d;
 }
 
-// the device memory one opening needs, in field elements, for a context outside a device set (pk_commit_sizes' rule there:
-// leaves = rows * width, nodes = 2 rows, scratch = 2 rows * width).  Every buffer is rounded up to 8 elements.
+// the device memory one opening needs, in field elements.  Every buffer is rounded up to 8 elements.  The sizes of a commit's buffers
+// are `sizes(batch, n_vars, log_inv_rate, &leaves, &nodes, &scratch)`: pk_commit_sizes' rule outside a device set (leaves = rows * width,
+// nodes = 2 rows, scratch = 2 rows * width) for plan(), which is host only and has no context -- pkw_scheme_arena_bytes -- and
+// pk_commit_sizes itself under the context's set for the arena a scheme allocates (pcs.cpp)
 struct Plan {
     size_t total = 0, scratch = 0;
 };
 inline size_t round8(size_t fes) { return (fes + 7) & ~(size_t)7; }
-inline Plan plan(const pk_whir_config& c) {
-    Plan p;
+template <class Sizes>
+inline int plan_with(const pk_whir_config& c, Sizes sizes, Plan& p) {
+    p = Plan{};
     const unsigned n = c.n_vars, k = c.folding_factor;
     const size_t N = (size_t)1 << n;
-    auto commit_scratch = [&](unsigned nv, unsigned rate, unsigned batch) { return 2 * ((size_t)1 << (nv + rate - k)) * ((size_t)batch << k); };
-    p.scratch = commit_scratch(n, c.starting_log_inv_rate, c.batch_size);  // pkw_commit's
+    size_t leaves = 0, nodes = 0, scratch = 0;
+    if (int rc = sizes(c.batch_size, n, c.starting_log_inv_rate, &leaves, &nodes, &scratch)) return rc;
+    p.scratch = scratch;  // pkw_commit's
     // ... and a linear opening's deferred evaluations borrow it for the partials of EVAL_MAX_BATCH tables: more than the commit's
     // where batch * 2^(n + rate) < 16
     p.scratch = std::max(p.scratch, eval_partial_fes(EVAL_MAX_BATCH, n));
@@ -126,13 +130,22 @@ inline Plan plan(const pk_whir_config& c) {
         p.total += round8((size_t)1 << nv);
         if (r == c.n_rounds) break;
         rate += k - 1;
-        const size_t rows = (size_t)1 << (nv + rate - k);
-        p.total += round8(rows << k) + round8(2 * rows);
-        p.scratch = std::max(p.scratch, commit_scratch(nv, rate, 1));
+        if (int rc = sizes(1, nv, rate, &leaves, &nodes, &scratch)) return rc;
+        p.total += round8(leaves) + round8(nodes);
+        p.scratch = std::max(p.scratch, scratch);
     }
     p.total += round8(p.scratch);
     // pkw_open's evaluations: the points, the kernel's partial sums, the results
     p.total += round8((size_t)PKW_MAX_POINTS * n) + round8(eval_partial_fes(c.batch_size, n)) + round8((size_t)PKW_MAX_POINTS * c.batch_size);
+    return PK_OK;
+}
+inline Plan plan(const pk_whir_config& c) {
+    Plan p;
+    plan_with(c, [&](unsigned batch, unsigned nv, unsigned rate, size_t* leaves, size_t* nodes, size_t* scratch) {
+        const size_t rows = (size_t)1 << (nv + rate - c.folding_factor), width = (size_t)batch << c.folding_factor;
+        *leaves = rows * width, *nodes = 2 * rows, *scratch = 2 * rows * width;
+        return (int)PK_OK;
+    }, p);
     return p;
 }
 

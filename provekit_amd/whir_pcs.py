@@ -4,6 +4,10 @@ polynomials, open them at points of the caller's choice -- or at LINEAR statemen
 (open_sparse / verify_sparse; SparseWeights) -- and verify the opening.  Those openings are PLAIN WHIR, not hiding; commit_hiding / open_hiding / verify_hiding mask the
 polynomials as pk_prove masks its witness (include/provekit_whir_hiding.h states the construction and what it claims).
 
+A Scheme on a context of a device set (Context.create_set, comm_init_rank, device_set.py) works as on a lone context: one Scheme per
+rank, one thread per rank, the same calls with the same inputs on every rank, the lone scheme's root and proof bytes on every rank
+(include/provekit_whir.h, "Device sets").
+
 A fourth library above the product's C ABI, with its own loader and one signature table for its four headers (as provekit_amd.verify).  `verify` and
 `io_pattern` are host only; `Scheme` needs a Context.  A rejected proof is a Result, not an exception; only a failed CALL raises.
 There is no fallback: without the built library the import raises."""

@@ -43,6 +43,11 @@ SIGNATURES = {
     "pk_probe_whir_weighted_sums": (C.c_int, [vp, vp, C.c_uint, C.c_uint, vp, C.c_uint, C.c_uint, C.c_int, vp]),
     "pk_probe_whir_wsum_grid": (C.c_uint, [C.c_uint]),
     "pk_probe_wsum_tile_host": (C.c_int, [vp, vp, C.c_uint, vp]),
+    # ... and the rank slices of its two reductions with the finish kernel over gathered blocks, on one context
+    "pk_probe_whir_eval_grid": (C.c_uint, [C.c_uint]),
+    "pk_probe_whir_eval_slice": (C.c_int, [vp, vp, C.c_uint, C.c_uint, vp, C.c_uint, C.c_uint, C.c_uint, vp, C.POINTER(C.c_float)]),
+    "pk_probe_whir_wsum_slice": (C.c_int, [vp, vp, C.c_uint, C.c_uint, vp, C.c_uint, C.c_uint, C.c_uint, C.c_uint, C.c_int, vp, C.POINTER(C.c_float)]),
+    "pk_probe_whir_finish": (C.c_int, [vp, vp, sz, C.c_uint, C.c_uint, sz, C.c_uint, C.c_uint, C.c_uint, vp]),
     # ... and its sparse-weight code (tools/probes/whir_sparse.hip)
     "pk_probe_whir_sparse_threads": (C.c_uint, []),
     "pk_probe_whir_sparse_chunk_bits": (C.c_uint, []),

@@ -87,6 +87,22 @@ int pk_probe_whir_weighted_sums(pk_ctx *ctx, const uint64_t *const *d_evals, uns
 unsigned pk_probe_whir_wsum_grid(unsigned n_vars);
 int pk_probe_wsum_tile_host(const uint64_t *f, const uint64_t *w, unsigned terms, uint64_t *out);
 
+/* The rank slices of a device set (csrc/whir_pcs/pcs.cpp), on ONE context, for tests/test_gpu_whir_pcs_sharded.py and
+ * tools/whir_pcs_sharded_profile.py.  pk_probe_whir_eval_slice: one pass of the evaluation kernel (Q <= 8 HOST points) over the
+ * workgroups [first_wg, first_wg + count) of pk_probe_whir_eval_grid(n_vars); partial_out = batch * 8 * count HOST elements,
+ * [(b * 8 + i) * count + j].  pk_probe_whir_wsum_slice: one pass of the weighted-sums kernel (L <= 8 weights) over the same kind of
+ * slice of a grid of `grid` (0: pk_probe_whir_wsum_grid); partial_out = batch * L * count elements, [(b * L + i) * count + j].
+ * pk_probe_whir_finish: the library's finish kernel over HOST partials that lie in n_wg / chunk blocks of `chunk` workgroups each,
+ * block_stride elements apart (`total` elements in all): out[y * count + i], y < rows, i < count <= row_stride.  ms, where not
+ * null: the launch's time between two events on an otherwise idle context, in milliseconds. */
+unsigned pk_probe_whir_eval_grid(unsigned n_vars);
+int pk_probe_whir_eval_slice(pk_ctx *ctx, const uint64_t *const *d_evals, unsigned batch, unsigned n_vars, const uint64_t *points, unsigned Q,
+                             unsigned first_wg, unsigned count, uint64_t *partial_out, float *ms);
+int pk_probe_whir_wsum_slice(pk_ctx *ctx, const uint64_t *const *d_evals, unsigned batch, unsigned n_vars, const uint64_t *const *d_weights,
+                             unsigned L, unsigned grid, unsigned first_wg, unsigned count, int tile, uint64_t *partial_out, float *ms);
+int pk_probe_whir_finish(pk_ctx *ctx, const uint64_t *partials, size_t total, unsigned n_wg, unsigned chunk, size_t block_stride, unsigned rows,
+                         unsigned count, unsigned row_stride, uint64_t *out);
+
 /* ... and its sparse-weight code (csrc/whir_pcs/sparse.hip, sparse.hpp; whir_sparse.hip here), for tests/test_gpu_whir_pcs_sparse.py,
  * tests/test_whir_pcs_sparse_host.py and tools/whir_pcs_sparse_bench.py.  pk_probe_whir_sparse_sums: pkw_sparse_sums on a grid of
  * `grid` workgroups per weight (0 or 1..pk_probe_whir_wsum_grid(n_vars)).  pk_probe_whir_sparse_grid: the grid the library takes for
