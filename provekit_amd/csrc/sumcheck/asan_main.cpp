@@ -1,0 +1,135 @@
+// asan_main.cpp -- driver of the sanitizer build of this library's host code (make asan; CPU code only):
+//   pks_verify_asan verify <case file>
+//       u32 n, m, T, has_tau, n_bind, masks[4] | u64 coeffs[4][4] | u32 with_expected | u32 pattern length | pattern |
+//       tau (n elements, if has_tau) | bind (n_bind elements) | expected sum (if with_expected) | u32 count | count x (u64 length | bytes)
+//     verifies every proof with pks_verify and prints "rc accepted check offset" per proof.  A statement the library refuses prints one
+//     REFUSED line and nothing of the rest is read: its counts size nothing.  Proofs, tau and bind live in exact-size heap blocks, so
+//     that a read past an end is a report, not a read of the next item.
+//   pks_verify_asan lane <D> <lo> <hi> <coeff> <weight> <repeats>        (64 hex digits each, the raw 256-bit value, big-endian)
+//     runs lane.hpp's lane_accumulate<D, D> -- the kernel's arithmetic, compiled for the host -- `repeats` times on D tables that all hold
+//     (lo, hi), one term over all of them, and prints the D + 1 sums the same way.
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../../../include/provekit_sumcheck.h"
+#include "lane.hpp"
+
+namespace {
+
+std::vector<uint8_t> buf;  // the case file
+size_t at = 0;
+
+void take(void* dst, size_t n) {
+    if (buf.size() - at < n) exit(2);
+    if (n) memcpy(dst, buf.data() + at, n);
+    at += n;
+}
+void* take_block(size_t n) {  // the next n bytes in a heap block of exactly that size
+    if (buf.size() - at < n) exit(2);
+    void* p = malloc(n ? n : 1);
+    take(p, n);
+    return p;
+}
+
+int run_verify(const char* path) {
+    FILE* f = fopen(path, "rb");
+    if (!f) return 2;
+    uint8_t chunk[65536];
+    for (size_t got; (got = fread(chunk, 1, sizeof chunk, f)) > 0;) buf.insert(buf.end(), chunk, chunk + got);
+    fclose(f);
+    pks_statement st;
+    memset(&st, 0, sizeof st);
+    uint32_t head[9];
+    take(head, sizeof head);
+    st.n = head[0], st.m = head[1], st.T = head[2], st.has_tau = head[3], st.n_bind = head[4];
+    for (int t = 0; t < 4; t++) st.masks[t] = head[5 + t];
+    take(st.coeffs, sizeof st.coeffs);
+    size_t proof_len = 0;
+    if (int rc = pks_proof_bytes(&st, &proof_len)) {
+        printf("%d 0 REFUSED 0 %s\n", rc, pks_create_error());
+        return 0;
+    }
+    uint32_t with_expected, pattern_len;
+    take(&with_expected, 4);
+    take(&pattern_len, 4);
+    uint8_t* pattern = (uint8_t*)take_block(pattern_len);
+    uint64_t* tau = st.has_tau ? (uint64_t*)take_block(32 * (size_t)st.n) : nullptr;
+    uint64_t* bind = st.n_bind ? (uint64_t*)take_block(32 * (size_t)st.n_bind) : nullptr;
+    uint64_t* expected = with_expected ? (uint64_t*)take_block(32) : nullptr;
+    uint32_t count;
+    take(&count, 4);
+    uint64_t* point = (uint64_t*)malloc(32 * (size_t)st.n);
+    uint64_t* finals = (uint64_t*)malloc(32 * (size_t)st.m);
+    for (uint32_t c = 0; c < count; c++) {
+        uint64_t len;
+        take(&len, 8);
+        uint8_t* proof = (uint8_t*)take_block(len);
+        pkv_result r;
+        const int rc = pks_verify(&st, pattern_len ? pattern : nullptr, pattern_len, tau, bind, expected, proof, len, point, finals, &r);
+        if (rc)
+            printf("%d 0 REFUSED 0 %s\n", rc, pks_create_error());
+        else
+            printf("0 %d %s %llu\n", r.accepted, pks_check_name(r.check), (unsigned long long)r.offset);
+        free(proof);
+    }
+    free(point), free(finals), free(expected), free(bind), free(tau), free(pattern);
+    return 0;
+}
+
+bool parse_hex(const char* s, pk::fe& out) {
+    if (strlen(s) != 64) return false;
+    for (int i = 0; i < 8; i++) {
+        char word[9] = {0};
+        memcpy(word, s + 8 * (7 - i), 8);
+        char* end;
+        out.v[i] = (uint32_t)strtoul(word, &end, 16);
+        if (*end) return false;
+    }
+    return true;
+}
+void print_hex(const pk::fe& x) {
+    for (int i = 7; i >= 0; i--) printf("%08x", x.v[i]);
+    printf("\n");
+}
+
+template <int D>
+void lane(const pk::fe& lo_v, const pk::fe& hi_v, const pk::fe& coeff, const pk::fe& w, unsigned repeats) {
+    pk::fe lo[D], hi[D], acc[D + 1];
+    for (int j = 0; j < D; j++) lo[j] = lo_v, hi[j] = hi_v;
+    for (int k = 0; k <= D; k++) acc[k] = pk::fe_zero();
+    pks::Terms tm;
+    memset(&tm, 0, sizeof tm);
+    tm.T = 1, tm.masks[0] = (1u << D) - 1, tm.kind[0] = pks::COEFF_ANY, tm.coeff[0] = coeff;
+    for (unsigned r = 0; r < repeats; r++) pks::lane_accumulate<D, D>(lo, hi, tm, true, w, acc);
+    for (int k = 0; k <= D; k++) print_hex(acc[k]);
+}
+
+int run_lane(int argc, char** argv) {
+    pk::fe v[4];
+    if (argc != 8) return 2;
+    for (int i = 0; i < 4; i++)
+        if (!parse_hex(argv[3 + i], v[i])) return 2;
+    const int D = atoi(argv[2]);
+    const unsigned repeats = (unsigned)atoi(argv[7]);
+    if (D == 1)
+        lane<1>(v[0], v[1], v[2], v[3], repeats);
+    else if (D == 2)
+        lane<2>(v[0], v[1], v[2], v[3], repeats);
+    else if (D == 3)
+        lane<3>(v[0], v[1], v[2], v[3], repeats);
+    else
+        return 2;
+    return 0;
+}
+
+}  // namespace
+
+int main(int argc, char** argv) {
+    if (argc == 3 && !strcmp(argv[1], "verify")) return run_verify(argv[2]);
+    if (argc >= 2 && !strcmp(argv[1], "lane")) return run_lane(argc, argv);
+    fprintf(stderr, "usage: pks_verify_asan verify <case file> | lane <D> <lo> <hi> <coeff> <weight> <repeats>\n");
+    return 2;
+}

@@ -1,0 +1,128 @@
+// round.hip -- the one HIP kernel family libprovekit_sumcheck.so adds: "fold the previous round's variable and evaluate this round" of
+// a product sumcheck over up to 4 tables in one pass (the fold_or_null shape of pk_sumcheck_cubic_round).
+//
+// A lane takes index x of the lower half and loads lo = f_j[x], hi = f_j[x + pairs] of each of the m tables (32 bytes each: two 16-byte
+// loads).  With a fold challenge it loads both halves of the level above instead -- x, x + pairs, x + 2 pairs, x + 3 pairs -- folds them
+// into lo and hi and writes those to the output tables, so each table is read once per round at its current length and written once at
+// half; a lane writes only what it alone reads, so the output may be the input (the prover folds its arena in place; the caller's
+// tables are only ever an input).  lane.hpp then steps every table through X = 0 .. D, forms the terms under wave-uniform control
+// (masks, coefficient kinds and coefficients are kernel arguments: scalar registers) and multiplies by the lane's eq weight, the
+// product of one entry of each of the two split tables (round.hpp).
+//
+// Reduction: the partials-plus-finish pattern of whir_pcs/evaluate.hip.  A workgroup adds its lanes' D + 1 sums with reduce.hpp's
+// block_reduce_fe (column sums through LDS) and stores one partial per sum with ordinary vector stores; finish_kernel, one workgroup per
+// sum, adds the partials.  No atomics, no ticket: field addition is exact, so the result's bits depend neither on the grid nor on
+// the order.
+//
+// Specialised at compile time on what changes register pressure: D, m and whether the lane folds.  The term structure is uniform data.
+#include <hip/hip_runtime.h>
+
+#include "../reduce.hpp"
+#include "lane.hpp"
+#include "round.hpp"
+
+using namespace pk;
+
+namespace pks {
+
+namespace {
+
+constexpr unsigned THREADS = RED_THREADS;
+
+struct DevTables {
+    const fe* in[PKS_MAX_TABLES];
+    fe* out[PKS_MAX_TABLES];
+};
+
+// partial[k * gridDim.x + blockIdx.x] = this workgroup's share of sum k = h(k), k <= D
+template <int D, int M, bool FOLD>
+__global__ __launch_bounds__(THREADS) void round_kernel(DevTables tb, Terms tm, const fe* __restrict__ eq_hi, const fe* __restrict__ eq_lo, unsigned lo_bits,
+                                                        size_t pairs, fe alpha, fe* __restrict__ partial) {
+    fe acc[D + 1];
+#pragma unroll
+    for (int k = 0; k <= D; k++) acc[k] = fe_zero();
+    const bool weighted = eq_hi != nullptr;
+    const size_t lo_mask = ((size_t)1 << lo_bits) - 1;
+    const size_t stride = (size_t)gridDim.x * THREADS;
+    for (size_t x = (size_t)blockIdx.x * THREADS + threadIdx.x; x < pairs; x += stride) {
+        fe lo[M], hi[M];
+#pragma unroll
+        for (int j = 0; j < M; j++) {
+            const fe* f = tb.in[j];
+            fe x0 = fe_load(f + x), x1 = fe_load(f + x + pairs);
+            if (FOLD) {
+                const fe x2 = fe_load(f + x + 2 * pairs), x3 = fe_load(f + x + 3 * pairs);
+                x0 = fold_pair(x0, x2, alpha);
+                x1 = fold_pair(x1, x3, alpha);
+                fe_store(tb.out[j] + x, x0);
+                fe_store(tb.out[j] + x + pairs, x1);
+            }
+            lo[j] = x0;
+            hi[j] = x1;
+        }
+        fe w = fe_zero();
+        if (weighted) w = fe_mulx(fe_load(eq_hi + (x >> lo_bits)), fe_load(eq_lo + (x & lo_mask)));
+        lane_accumulate<D, M>(lo, hi, tm, weighted, w, acc);
+    }
+    const fe mine = block_reduce_fe<D + 1>(acc);  // thread k holds sum k
+    if (threadIdx.x <= D) fe_store(partial + (size_t)threadIdx.x * gridDim.x + blockIdx.x, mine);
+}
+
+// out[k] = the sum of partial[k * n_wg ..+ n_wg); one workgroup per sum, lane j adds the partials j, j + 256, ...
+__global__ __launch_bounds__(THREADS) void finish_kernel(const fe* __restrict__ partial, unsigned n_wg, fe* __restrict__ out) {
+    const fe* p = partial + (size_t)blockIdx.x * n_wg;
+    fe acc = fe_zero();
+    for (unsigned j = threadIdx.x; j < n_wg; j += THREADS) acc = fe_add(acc, fe_load(p + j));
+    acc = block_sum(acc);
+    if (threadIdx.x == 0) fe_store(out + blockIdx.x, acc);
+}
+
+template <int D, int M>
+void launch_dm(bool fold, unsigned grid, hipStream_t stream, const DevTables& tb, const Terms& tm, const fe* eq_hi, const fe* eq_lo, unsigned lo_bits,
+               size_t pairs, const fe& alpha, fe* partial) {
+    if (fold)
+        round_kernel<D, M, true><<<grid, THREADS, 0, stream>>>(tb, tm, eq_hi, eq_lo, lo_bits, pairs, alpha, partial);
+    else
+        round_kernel<D, M, false><<<grid, THREADS, 0, stream>>>(tb, tm, eq_hi, eq_lo, lo_bits, pairs, alpha, partial);
+}
+
+}  // namespace
+
+unsigned round_grid(size_t pairs) {
+    const size_t need = (pairs + 2 * THREADS - 1) / (2 * THREADS);
+    return (unsigned)(need < 1 ? 1 : need > PKS_MAX_GRID ? PKS_MAX_GRID : need);
+}
+
+int round_launch(hipStream_t stream, const pks_statement& st, const RoundTables& rt, size_t pairs, const uint64_t* fold_or_null, const uint64_t* d_eq_hi,
+                 const uint64_t* d_eq_lo, unsigned lo_bits, unsigned grid, uint64_t* d_scratch) {
+    if (!pairs || grid < 1 || grid > PKS_MAX_GRID) return PK_ERR_BAD_ARG;
+    DevTables tb{};
+    for (unsigned j = 0; j < st.m; j++) {
+        tb.in[j] = (const fe*)rt.in[j];
+        tb.out[j] = (fe*)rt.out[j];
+    }
+    Terms tm{};
+    tm.T = st.T;
+    const fe one = fe_one(), minus_one = fe_neg(fe_one());
+    for (unsigned t = 0; t < st.T; t++) {
+        tm.masks[t] = st.masks[t];
+        tm.coeff[t] = h_load(st.coeffs[t]);
+        tm.kind[t] = fe_eq(tm.coeff[t], one) ? COEFF_ONE : fe_eq(tm.coeff[t], minus_one) ? COEFF_MINUS_ONE : COEFF_ANY;
+    }
+    const fe alpha = fold_or_null ? h_load(fold_or_null) : fe_zero();
+    fe* const partial = (fe*)d_scratch;
+    const fe *hi = (const fe*)d_eq_hi, *lo = (const fe*)d_eq_lo;
+    const unsigned D = degree(st);
+    const bool fold = fold_or_null != nullptr;
+#define PKS_CASE(DEG, TABLES)                                                                      \
+    if (D == DEG && st.m == TABLES) {                                                              \
+        launch_dm<DEG, TABLES>(fold, grid, stream, tb, tm, hi, lo, lo_bits, pairs, alpha, partial); \
+    } else
+    PKS_CASE(1, 1) PKS_CASE(1, 2) PKS_CASE(1, 3) PKS_CASE(1, 4) PKS_CASE(2, 2) PKS_CASE(2, 3) PKS_CASE(2, 4) PKS_CASE(3, 3) PKS_CASE(3, 4)
+    return PK_ERR_BAD_ARG;  // D <= m: a term's tables are distinct
+#undef PKS_CASE
+    finish_kernel<<<D + 1, THREADS, 0, stream>>>(partial, grid, partial + (size_t)4 * PKS_MAX_GRID);
+    return hipGetLastError() == hipSuccess ? PK_OK : PK_ERR_HIP;
+}
+
+}  // namespace pks
