@@ -79,6 +79,15 @@ int eval_univariate_multi(pk_ctx* ctx, const uint64_t* const* d_polys, unsigned 
 int dot_rows(pk_ctx* ctx, const uint64_t* d_w, size_t row_stride, unsigned nrows, const uint64_t* d_f, const uint64_t* d_g, size_t n, uint64_t* out,
              bool defer = false);
 int lincomb2(pk_ctx* ctx, uint64_t* d_out, const uint64_t* d_a, const uint64_t* beta, const uint64_t* d_b, size_t n);  // out = a + beta * b
+// out0 = a0 + beta * b0 over n0 entries and out1 = a1 + beta * b1 over n1 in one launch (a batch of two: coefficient and evaluation tables)
+int lincomb2_pair(pk_ctx* ctx, uint64_t* d_out0, const uint64_t* d_a0, const uint64_t* d_b0, size_t n0, uint64_t* d_out1, const uint64_t* d_a1,
+                  const uint64_t* d_b1, size_t n1, const uint64_t* beta);
+// y += g3[0] r0 + g3[1] r1 + g3[2] r2 over n entries, row k at d_rows + k * row_stride elements: one pass over y (the bits three pk_fe_axpy calls leave)
+int axpy3(pk_ctx* ctx, uint64_t* d_y, const uint64_t* g3, const uint64_t* d_rows, size_t row_stride, size_t n);
+// f = [witness (zero padded to 2^(m-1)) || draw stream_mask], g = draw stream_g, both of 2^m elements: the evaluation tables AND their
+// to_coeffs, the tables assembled inside the first sweep instead of by a memset, a copy and two random_fe launches before it
+int to_coeffs_generated(pk_ctx* ctx, unsigned m, const uint64_t* d_wit, size_t n_wit, const RngKey& key, uint32_t stream_mask, uint32_t stream_g,
+                        uint64_t* d_f_evals, uint64_t* d_g_evals, uint64_t* d_f_coeffs, uint64_t* d_g_coeffs);
 // two arrays of the same length folded by the same challenge in one launch (the sumcheck's p and w)
 // r = NULL with gate_seq != 0: the challenge arrives through the gate (latency mode)
 int fold_pairs2(pk_ctx* ctx, const uint64_t* d_v0, uint64_t* d_out0, const uint64_t* d_v1, uint64_t* d_out1, size_t len, const uint64_t* r,

@@ -115,23 +115,70 @@ __global__ __launch_bounds__(256) void wavelet_high_kernel(fe* __restrict__ data
     }
 }
 
-// d_src == nullptr: in place; otherwise the first sweep reads d_src and writes d_data (saves a 32 B/element copy)
-template <bool SUB>
-int wavelet(pk_ctx* ctx, const uint64_t* d_src, uint64_t* d_data, unsigned n_vars) {
-    PK_REQUIRE(ctx, d_data, "null pointer");
-    PK_REQUIRE(ctx, n_vars <= 30, "too many variables");
-    fe* D = (fe*)d_data;
-    const fe* S = d_src ? (const fe*)d_src : D;
-    if (n_vars == 0) {
-        if (d_src && d_src != d_data) PK_HIP(ctx, hipMemcpyAsync(D, S, 32, hipMemcpyDeviceToDevice, ctx->stream));
-        return PK_OK;
+// The first to_coeffs sweep of a committed polynomial that does not exist yet (prover.hip batch_commit_compute): the tile is assembled
+// where it is first read.  Element i of the table is witness[i] for i < n_wit, zero up to rand_from, and from there element i - rand_from
+// of the draw `stream` of n_draw elements (rng_core.hpp).  Each element goes to the evaluation table (kept whole for the batch
+// combination and the weighted sums) and into the tile, whose sweep then runs as wavelet_low_kernel's.  blockIdx.y picks the table.
+struct gen_table {
+    const fe* wit;
+    size_t n_wit, rand_from, n_draw;
+    u32 stream;
+    fe* evals;
+    fe* coeffs;
+};
+__global__ __launch_bounds__(256) void wavelet_low_generated_kernel(gen_table ta, gen_table tb, RngKey key, unsigned logt) {
+    PK_LATENCY_PRIO();
+    extern __shared__ uint4 lds[];
+    const gen_table& S = blockIdx.y ? tb : ta;
+    const int T = 1 << logt;
+    uint4* lo = lds;
+    uint4* hi = lds + T;
+    const size_t t0 = (size_t)blockIdx.x * T;
+    for (int e = threadIdx.x; e < T && t0 + e < S.rand_from; e += 256) {  // a tile may straddle n_wit: per element
+        uint4 a = make_uint4(0, 0, 0, 0), b = a;
+        if (t0 + e < S.n_wit) {
+            const uint4* q = reinterpret_cast<const uint4*>(S.wit + t0 + e);
+            a = q[0];
+            b = q[1];
+        }
+        lo[e] = a;
+        hi[e] = b;
+        uint4* o = reinterpret_cast<uint4*>(S.evals + t0 + e);
+        o[0] = a;
+        o[1] = b;
     }
-    ProfScope prof(ctx, SUB ? "to_coeffs" : "to_evals");
-    unsigned logt = n_vars < 11 ? n_vars : 11;
-    size_t lds = ((size_t)2 << logt) * 16;
-    PK_HIP(ctx, hipFuncSetAttribute((const void*)wavelet_low_kernel<SUB>, hipFuncAttributeMaxDynamicSharedMemorySize, 1 << 16));
-    wavelet_low_kernel<SUB><<<(unsigned)((size_t)1 << (n_vars - logt)), 256, lds, ctx->stream>>>(S, D, logt);
-    unsigned s = logt;
+    if (t0 + T > S.rand_from) {  // rand_from is 0 or a power of two, t0 a multiple of T: the drawn part starts at an even element of the draw
+        const size_t d0 = (t0 > S.rand_from ? t0 : S.rand_from) - S.rand_from, d1 = t0 + T - S.rand_from;
+        fe* ev = S.evals + S.rand_from;
+        const size_t shift = S.rand_from - t0;  // tile slot of draw element i: i + rand_from - t0 (mod 2^64 where t0 > rand_from)
+        rng_draw_pairs(key, S.stream, d0 / 2 + threadIdx.x, 256, (d1 + 1) / 2, S.n_draw, [&](size_t i, const fe& x) {
+            fe_store(ev + i, x);
+            lds_put(lo, hi, (int)(i + shift), x);
+        });
+    }
+    __syncthreads();
+    for (unsigned s = 0; s < logt; s++) {
+        const int h = 1 << s;
+        for (int t = threadIdx.x; t < T / 2; t += 256) {
+            int pos = t & (h - 1);
+            int i0 = ((t - pos) << 1) + pos, i1 = i0 + h;
+            fe a = lds_get(lo, hi, i0), b = lds_get(lo, hi, i1);
+            lds_put(lo, hi, i1, fe_sub(b, a));
+        }
+        __syncthreads();
+    }
+    fe* base = S.coeffs + t0;
+    for (int e = threadIdx.x; e < T; e += 256) {
+        uint4* q = reinterpret_cast<uint4*>(base + e);
+        q[0] = lo[e];
+        q[1] = hi[e];
+    }
+}
+
+inline unsigned wavelet_low_bits(unsigned n_vars) { return n_vars < 11 ? n_vars : 11; }
+// the sweeps over the index bits [s, n_vars), in place
+template <bool SUB>
+int wavelet_high_sweeps(pk_ctx* ctx, fe* D, unsigned s, unsigned n_vars) {
     PK_HIP(ctx, hipFuncSetAttribute((const void*)wavelet_high_kernel<SUB, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 1 << 16));
     PK_HIP(ctx, hipFuncSetAttribute((const void*)wavelet_high_kernel<SUB, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 1 << 16));
     while (s < n_vars) {
@@ -150,6 +197,25 @@ int wavelet(pk_ctx* ctx, const uint64_t* d_src, uint64_t* d_data, unsigned n_var
     }
     PK_LAUNCH_CHECK(ctx);
     return PK_OK;
+}
+
+// d_src == nullptr: in place; otherwise the first sweep reads d_src and writes d_data (saves a 32 B/element copy)
+template <bool SUB>
+int wavelet(pk_ctx* ctx, const uint64_t* d_src, uint64_t* d_data, unsigned n_vars) {
+    PK_REQUIRE(ctx, d_data, "null pointer");
+    PK_REQUIRE(ctx, n_vars <= 30, "too many variables");
+    fe* D = (fe*)d_data;
+    const fe* S = d_src ? (const fe*)d_src : D;
+    if (n_vars == 0) {
+        if (d_src && d_src != d_data) PK_HIP(ctx, hipMemcpyAsync(D, S, 32, hipMemcpyDeviceToDevice, ctx->stream));
+        return PK_OK;
+    }
+    ProfScope prof(ctx, SUB ? "to_coeffs" : "to_evals");
+    const unsigned logt = wavelet_low_bits(n_vars);
+    size_t lds = ((size_t)2 << logt) * 16;
+    PK_HIP(ctx, hipFuncSetAttribute((const void*)wavelet_low_kernel<SUB>, hipFuncAttributeMaxDynamicSharedMemorySize, 1 << 16));
+    wavelet_low_kernel<SUB><<<(unsigned)((size_t)1 << (n_vars - logt)), 256, lds, ctx->stream>>>(S, D, logt);
+    return wavelet_high_sweeps<SUB>(ctx, D, logt, n_vars);
 }
 
 // ---------------------------------------------------------------- S2 / W2: eq tables
@@ -758,6 +824,40 @@ __global__ __launch_bounds__(256) void axpy_kernel(fe* __restrict__ y, const fe*
         fe_store(y + i, fe_add(fe_load(y + i), fe_mulx(beta, fe_load(x + i))));
 }
 
+// two such combinations with the same beta in one launch (blockIdx.y picks one): the coefficient and the evaluation tables of a batch of two
+__global__ __launch_bounds__(256) void lincomb_pair_kernel(fe* __restrict__ out0, const fe* __restrict__ a0, const fe* __restrict__ b0, size_t n0,
+                                                           fe* __restrict__ out1, const fe* __restrict__ a1, const fe* __restrict__ b1, size_t n1,
+                                                           fe_arg beta_arg) {
+    PK_LATENCY_PRIO();
+    const fe beta = from_arg(beta_arg);
+    fe* out = blockIdx.y ? out1 : out0;
+    const fe* a = blockIdx.y ? a1 : a0;
+    const fe* b = blockIdx.y ? b1 : b0;
+    const size_t n = blockIdx.y ? n1 : n0;
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
+        fe_store(out + i, fe_add(fe_load(a + i), fe_mulx(beta, fe_load(b + i))));
+}
+// y += g0 r0 + g1 r1 + g2 r2 with row k at rows + k * row_stride: one read and one write of y where three axpy launches make three,
+// and one Montgomery reduction for the three products (fe29.hpp dot29; the rows are reduced values).  Every step gives the reduced
+// representative, so y's bits are what the three launches leave.
+struct fe3_arg {
+    fe_arg g[3];
+};
+__global__ __launch_bounds__(256) void axpy3_kernel(fe* __restrict__ y, const fe* __restrict__ rows, size_t row_stride, size_t n, fe3_arg ga) {
+    PK_LATENCY_PRIO();
+    const fe29 g0 = unpack29<5>(from_arg(ga.g[0])), g1 = unpack29<5>(from_arg(ga.g[1])), g2 = unpack29<5>(from_arg(ga.g[2]));
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        dot29 d;
+        dot29_init(d);
+        dot29_add(d, unpack29<0>(fe_load(rows + i)), g0);
+        dot29_add(d, unpack29<0>(fe_load(rows + row_stride + i)), g1);
+        dot29_add(d, unpack29<0>(fe_load(rows + 2 * row_stride + i)), g2);
+        fe_store(y + i, fe_add(fe_load(y + i), dot29_result(d)));
+    }
+}
+
 // <w,f> and (nv == 2) <w,g>: out[4 * v]
 int dot(pk_ctx* ctx, int nv, const uint64_t* d_w, const uint64_t* d_f, const uint64_t* d_g, size_t n, uint64_t* out) {
     if (n == 0) return reduce_empty(ctx, nv, out);
@@ -936,6 +1036,40 @@ int lincomb2(pk_ctx* ctx, uint64_t* d_out, const uint64_t* d_a, const uint64_t* 
     lincomb_kernel<<<grid_for(ctx, n, 256), 256, 0, ctx->stream>>>((fe*)d_out, (const fe*)d_a, (const fe*)d_b, n, to_arg(beta));
     PK_LAUNCH_CHECK(ctx);
     return PK_OK;
+}
+int lincomb2_pair(pk_ctx* ctx, uint64_t* d_out0, const uint64_t* d_a0, const uint64_t* d_b0, size_t n0, uint64_t* d_out1, const uint64_t* d_a1,
+                  const uint64_t* d_b1, size_t n1, const uint64_t* beta) {
+    PK_REQUIRE(ctx, beta && (n0 == 0 || (d_out0 && d_a0 && d_b0)) && (n1 == 0 || (d_out1 && d_a1 && d_b1)), "null pointer");
+    if (!n0 && !n1) return PK_OK;
+    ProfScope prof(ctx, "lincomb");
+    lincomb_pair_kernel<<<dim3(grid_for(ctx, n0 > n1 ? n0 : n1, 256), 2), 256, 0, ctx->stream>>>(
+        (fe*)d_out0, (const fe*)d_a0, (const fe*)d_b0, n0, (fe*)d_out1, (const fe*)d_a1, (const fe*)d_b1, n1, to_arg(beta));
+    PK_LAUNCH_CHECK(ctx);
+    return PK_OK;
+}
+int axpy3(pk_ctx* ctx, uint64_t* d_y, const uint64_t* g3, const uint64_t* d_rows, size_t row_stride, size_t n) {
+    PK_REQUIRE(ctx, g3 && (n == 0 || (d_y && d_rows)), "null pointer");
+    if (!n) return PK_OK;
+    ProfScope prof(ctx, "lincomb");
+    fe3_arg ga;
+    for (int k = 0; k < 3; k++) ga.g[k] = to_arg(g3 + 4 * k);
+    axpy3_kernel<<<grid_for(ctx, n, 256), 256, 0, ctx->stream>>>((fe*)d_y, (const fe*)d_rows, row_stride, n, ga);
+    PK_LAUNCH_CHECK(ctx);
+    return PK_OK;
+}
+int to_coeffs_generated(pk_ctx* ctx, unsigned m, const uint64_t* d_wit, size_t n_wit, const RngKey& key, uint32_t stream_mask, uint32_t stream_g,
+                        uint64_t* d_f_evals, uint64_t* d_g_evals, uint64_t* d_f_coeffs, uint64_t* d_g_coeffs) {
+    PK_REQUIRE(ctx, d_f_evals && d_g_evals && d_f_coeffs && d_g_coeffs && (n_wit == 0 || d_wit), "null pointer");
+    PK_REQUIRE(ctx, m >= 1 && m <= 30 && n_wit <= ((size_t)1 << (m - 1)), "witness longer than half the table");
+    const size_t half = (size_t)1 << (m - 1), N = 2 * half;
+    const gen_table tf = {(const fe*)d_wit, n_wit, half, half, stream_mask, (fe*)d_f_evals, (fe*)d_f_coeffs};
+    const gen_table tg = {nullptr, 0, 0, N, stream_g, (fe*)d_g_evals, (fe*)d_g_coeffs};
+    ProfScope prof(ctx, "to_coeffs");
+    const unsigned logt = wavelet_low_bits(m);
+    PK_HIP(ctx, hipFuncSetAttribute((const void*)wavelet_low_generated_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 1 << 16));
+    wavelet_low_generated_kernel<<<dim3((unsigned)(N >> logt), 2), 256, ((size_t)2 << logt) * 16, ctx->stream>>>(tf, tg, key, logt);
+    int rc = wavelet_high_sweeps<true>(ctx, (fe*)d_f_coeffs, logt, m);
+    return rc ? rc : wavelet_high_sweeps<true>(ctx, (fe*)d_g_coeffs, logt, m);
 }
 int fold_pairs2(pk_ctx* ctx, const uint64_t* d_v0, uint64_t* d_out0, const uint64_t* d_v1, uint64_t* d_out1, size_t len, const uint64_t* r,
                 unsigned gate_seq) {

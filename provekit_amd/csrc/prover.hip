@@ -305,6 +305,11 @@ size_t in_block(size_t stored, size_t off, size_t len) {
     const size_t hi = stored < off + len ? stored : off + len;
     return hi > off ? hi - off : 0;
 }
+// the three external rows at equal stride and of one length: one pass serves all three (the statement weights into w0, the deferred hint)
+bool rows_at_equal_stride3(fe* const* d_weights, const size_t* weight_len, unsigned n_weights) {
+    return n_weights == 3 && weight_len[0] == weight_len[1] && weight_len[1] == weight_len[2] && d_weights[1] > d_weights[0] &&
+           d_weights[1] - d_weights[0] == d_weights[2] - d_weights[1];
+}
 struct WhirProver {
     pk_ctx* ctx;
     Arena& A;
@@ -448,7 +453,6 @@ struct WhirProver {
         const size_t N = (size_t)1 << n;
         ALLOC(dc, N);
         d_c = dc;
-        CK(batch_combine(d_c, C.polys, 0, N));
         ALLOC(p0, B0);
         ALLOC(p1, B0 / 2 ? B0 / 2 : 1);
         ALLOC(w0, B0);
@@ -456,8 +460,16 @@ struct WhirProver {
         bp[0] = p0; bp[1] = p1; bw[0] = w0; bw[1] = w1;
         bool have_evals = true;
         for (unsigned b = 0; b < C.batch; b++) have_evals = have_evals && C.evals[b] != nullptr;
+        const bool pair = have_evals && C.batch == 2;
+        if (pair) {  // the coefficient and the evaluation combination of a batch of two in one launch
+            uint64_t s[4];
+            h_store(s, C.beta);
+            CK(lincomb2_pair(ctx, U(d_c), U(C.polys[0]), U(C.polys[1]), N, U(p0), U(C.evals[0] + off0), U(C.evals[1] + off0), B0, s));
+        } else {
+            CK(batch_combine(d_c, C.polys, 0, N));
+        }
         if (have_evals) {
-            CK(batch_combine(p0, C.evals, off0, B0));  // to_evals is linear: combine the tables the committer kept instead of transforming d_c
+            if (!pair) CK(batch_combine(p0, C.evals, off0, B0));  // to_evals is linear: combine the tables the committer kept instead of transforming d_c
         } else if (!sharded) {
             CK(pk_to_evals_into(ctx, U(d_c), U(p0), n));
         } else {
@@ -480,11 +492,18 @@ struct WhirProver {
         fe gq = fe_one();
         for (size_t j = 0; j < q; j++, gq = h_mul(gq, gamma)) claim = h_add(claim, h_mul(gq, batched(&C.ood_answers[j], q)));
         have_claim = weight_sums || !n_weights;
+        const bool rows3 = rows_at_equal_stride3(d_weights, weight_len, n_weights);
+        if (rows3) {  // one read and one write of w0 instead of three
+            uint64_t s3[12];
+            fe g3 = g;
+            for (int i = 0; i < 3; i++, g3 = h_mul(g3, gamma)) h_store(s3 + 4 * i, g3);
+            CK(axpy3(ctx, U(w0), s3, U(d_weights[0] + off0), (size_t)(d_weights[1] - d_weights[0]), in_block(weight_len[0], off0, B0)));
+        }
         for (unsigned i = 0; i < n_weights; i++) {
             uint64_t s[4];
             h_store(s, g);
             const size_t cnt = in_block(weight_len[i], off0, B0);
-            if (cnt) CK(pk_fe_axpy(ctx, U(w0), s, U(d_weights[i] + off0), cnt));
+            if (cnt && !rows3) CK(pk_fe_axpy(ctx, U(w0), s, U(d_weights[i] + off0), cnt));
             if (weight_sums) claim = h_add(claim, h_mul(g, batched(weight_sums + (size_t)i * C.batch, 1)));
             g = h_mul(g, gamma);
         }
@@ -588,8 +607,7 @@ struct WhirProver {
         Across ac(ctx, sh);
         CK(ac.rc);
         std::vector<fe> evals(n_weights);
-        const bool rows3 = n_weights == 3 && weight_len[0] == weight_len[1] && weight_len[1] == weight_len[2] && d_weights[1] > d_weights[0] &&
-                           d_weights[1] - d_weights[0] == d_weights[2] - d_weights[1];
+        const bool rows3 = rows_at_equal_stride3(d_weights, weight_len, n_weights);
         if (rows3) {  // the three external rows against the eq table in one pass
             uint64_t o[12] = {};
             if (sh || weight_len[0])
@@ -631,16 +649,20 @@ int batch_commit_compute(pk_ctx* ctx, Arena& A, unsigned m, const pk_whir_config
     ALLOC(fe_, N);
     ALLOC(ge_, N);
     // f = [witness (zero padded) || mask]   (zk_utils.rs:3-22)
-    CK(pk_memset_zero(ctx, f, 32 * half));
-    CK(pk_memcpy_d2d(ctx, f, d_evals, 32 * n_evals));
-    {
-        ProfScope prof(ctx, "random_fe");
-        CK(random_fe(ctx, U(f + half), half, key, stream_mask));
-        CK(random_fe(ctx, U(g), N, key, stream_g));
+    // f, g hold the evaluation forms (kept for the weighted sums); the coefficient forms go to fe_, ge_
+    if (comm_world(ctx) <= 1) {  // the tables are assembled inside the first to_coeffs sweep (mle.hip to_coeffs_generated)
+        CK(to_coeffs_generated(ctx, m, U(d_evals), n_evals, key, stream_mask, stream_g, U(f), U(g), U(fe_), U(ge_)));
+    } else {
+        CK(pk_memset_zero(ctx, f, 32 * half));
+        CK(pk_memcpy_d2d(ctx, f, d_evals, 32 * n_evals));
+        {
+            ProfScope prof(ctx, "random_fe");
+            CK(random_fe(ctx, U(f + half), half, key, stream_mask));
+            CK(random_fe(ctx, U(g), N, key, stream_g));
+        }
+        CK(pk_to_coeffs_into(ctx, U(f), U(fe_), m));
+        CK(pk_to_coeffs_into(ctx, U(g), U(ge_), m));
     }
-    // f, g hold the evaluation forms (kept for the weighted sums); the coefficient forms go to fc, gc
-    CK(pk_to_coeffs_into(ctx, U(f), U(fe_), m));
-    CK(pk_to_coeffs_into(ctx, U(g), U(ge_), m));
     out.f_evals = f;
     out.g_evals = g;
     fe* polys[2] = {fe_, ge_};

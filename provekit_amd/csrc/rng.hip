@@ -19,38 +19,11 @@ using namespace pk;
 
 namespace {
 
-// A lane walks its pairs j = g, g + stride, ... as a state machine (pair, attempt): one ChaCha block per loop iteration, whichever pair and
-// attempt the lane is at.  (Until round 5 the retry loop sat INSIDE the loop over pairs, so a wavefront repeated a pair's block until its
-// unluckiest lane -- 128 candidates, each rejected with probability 0.244 -- was done: ~4 blocks per pair instead of the 1.43 a lane needs.
-// Now the waiting averages out over a lane's pairs: launched with ~8 pairs per lane, a wavefront runs ~17 blocks for 8 pairs.)
+// A lane walks its pairs j = g, g + stride, ... (rng_core.hpp rng_draw_pairs; launched with ~8 pairs per lane)
 __global__ __launch_bounds__(256) void random_fe_kernel(fe* __restrict__ out, size_t n, RngKey key, u32 stream) {
     PK_LATENCY_PRIO();
-    const size_t stride = (size_t)gridDim.x * blockDim.x, pairs = (n + 1) / 2;
-    size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    u32 attempt = 0;
-    bool done0 = false, done1 = 2 * j + 1 >= n;
-    while (j < pairs) {
-        u32 blk[16];
-        chacha_block(key, (u64)j, stream, attempt, PK_RNG_ROUNDS, blk);
-#pragma unroll
-        for (int half = 0; half < 2; half++) {
-            if (half == 0 ? done0 : done1) continue;
-            fe x;
-            if (rng_candidate(blk, half, x)) {  // x < p: accepted
-                fe_store(out + 2 * j + half, x);
-                if (half == 0) done0 = true;
-                else done1 = true;
-            }
-        }
-        if (done0 && done1) {
-            j += stride;
-            attempt = 0;
-            done0 = false;
-            done1 = 2 * j + 1 >= n;
-        } else {
-            attempt++;
-        }
-    }
+    rng_draw_pairs(key, stream, (size_t)blockIdx.x * blockDim.x + threadIdx.x, (size_t)gridDim.x * blockDim.x, (n + 1) / 2, n,
+                   [&](size_t i, const fe& x) { fe_store(out + i, x); });
 }
 // ~8 pairs per lane (see the kernel), at least one wavefront per SIMD's worth of workgroups when the draw is long enough
 inline unsigned random_fe_grid(const pk_ctx* ctx, size_t n) {

@@ -1,5 +1,6 @@
 // rng_core.hpp -- the proof RNG's cipher block and accept rule, stated once for every kernel that draws from it: rng.hip's
-// (pk_prove's mask, g and blinding draws, the witness fill) and whir_pcs/hiding.hip's (the masks and g of a hiding commitment).
+// (pk_prove's blinding draws, the witness fill), mle.hip's (pk_prove's mask and g, drawn inside the first to_coeffs sweep of the
+// tables they fill) and whir_pcs/hiding.hip's (the masks and g of a hiding commitment).
 //
 // The ChaCha block function (RFC 8439 quarter rounds and state layout: words 12, 13 = counter, 14, 15 = nonce), PK_RNG_ROUNDS
 // rounds.  Elements 2j and 2j+1 of draw `stream` share the blocks (counter = j, nonce = {stream, attempt}): a block holds two
@@ -56,6 +57,40 @@ __host__ __device__ __forceinline__ bool rng_candidate(const u32 (&blk)[16], int
 #pragma unroll
     for (int k = 0; k < 8; k++) (void)__builtin_subc(x.v[k], kPlimb(k), borrow, &borrow);
     return borrow != 0;
+}
+
+// The draw itself, for every kernel that makes one: a lane walks the pairs j = first, first + stride, ... < pairs_end of a draw of n
+// elements as a state machine (pair, attempt) -- one ChaCha block per loop iteration, whichever pair and attempt the lane is at -- and
+// hands element i's accepted word to put(i, x).  (Until round 5 the retry loop sat INSIDE the loop over pairs, so a wavefront repeated a
+// pair's block until its unluckiest lane -- 128 candidates, each rejected with probability 0.244 -- was done: ~4 blocks per pair instead of
+// the 1.43 a lane needs.  Now the waiting averages out over a lane's pairs: with ~8 pairs per lane a wavefront runs ~17 blocks for 8 pairs.)
+template <class Put>
+__device__ __forceinline__ void rng_draw_pairs(const RngKey& key, u32 stream, size_t first, size_t stride, size_t pairs_end, size_t n, Put put) {
+    size_t j = first;
+    u32 attempt = 0;
+    bool done0 = false, done1 = 2 * j + 1 >= n;
+    while (j < pairs_end) {
+        u32 blk[16];
+        chacha_block(key, (u64)j, stream, attempt, PK_RNG_ROUNDS, blk);
+#pragma unroll
+        for (int half = 0; half < 2; half++) {
+            if (half == 0 ? done0 : done1) continue;
+            fe x;
+            if (rng_candidate(blk, half, x)) {  // x < p: accepted
+                put(2 * j + half, x);
+                if (half == 0) done0 = true;
+                else done1 = true;
+            }
+        }
+        if (done0 && done1) {
+            j += stride;
+            attempt = 0;
+            done0 = false;
+            done1 = 2 * j + 1 >= n;
+        } else {
+            attempt++;
+        }
+    }
 }
 
 }  // namespace pk

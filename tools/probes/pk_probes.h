@@ -72,6 +72,15 @@ int pk_probe_sumcheck_cubic_launch(pk_ctx *ctx, uint64_t *d_a, uint64_t *d_b, ui
 int pk_probe_sumcheck_quadratic_launch(pk_ctx *ctx, const uint64_t *d_f, const uint64_t *d_w, size_t len, const uint64_t *fold_or_null,
                                        uint64_t *d_f_out, uint64_t *d_w_out, unsigned *red_seq_out);
 int pk_probe_sumcheck_collect_spin(pk_ctx *ctx, unsigned red_seq, uint64_t out[12]);
+/* ... and the fused steps of the commit and of WhirProver::start, for tests/test_gpu_commit_fused.py.  pk_probe_lincomb2_pair: two
+ * lincomb2 with one beta in one launch.  pk_probe_axpy3: y += g3[0] r0 + g3[1] r1 + g3[2] r2, g3 = 3 HOST elements, row k at
+ * d_rows + k * row_stride elements.  pk_probe_to_coeffs_generated: f = [witness, zero padded to 2^(m-1) || draw stream_mask],
+ * g = draw stream_g under seed32, 2^m elements each -- the evaluation tables and their to_coeffs, four tables the caller owns. */
+int pk_probe_lincomb2_pair(pk_ctx *ctx, uint64_t *d_out0, const uint64_t *d_a0, const uint64_t *d_b0, size_t n0, uint64_t *d_out1,
+                           const uint64_t *d_a1, const uint64_t *d_b1, size_t n1, const uint64_t *beta);
+int pk_probe_axpy3(pk_ctx *ctx, uint64_t *d_y, const uint64_t *g3, const uint64_t *d_rows, size_t row_stride, size_t n);
+int pk_probe_to_coeffs_generated(pk_ctx *ctx, unsigned m, const uint64_t *d_wit, size_t n_wit, const uint8_t seed32[32], uint32_t stream_mask,
+                                 uint32_t stream_g, uint64_t *d_f_evals, uint64_t *d_g_evals, uint64_t *d_f_coeffs, uint64_t *d_g_coeffs);
 
 /* libprovekit_whir.so's linear-statement kernels (csrc/whir_pcs/linear.hip) where its C ABI does not reach, for
  * tests/test_gpu_whir_pcs_linear.py and tools/whir_pcs_linear_bench.py.  This library links libprovekit_whir.so for them.

@@ -938,4 +938,21 @@ int pk_probe_sumcheck_collect_spin(pk_ctx* ctx, unsigned red_seq, uint64_t out[1
     PK_REQUIRE(ctx, out && red_seq && ctx->h_pinned && red_seq == ctx->red_seq, "not the sequence number of this context's last launch");
     return sumcheck_collect_spin(ctx, 3, red_seq, out);
 }
+int pk_probe_lincomb2_pair(pk_ctx* ctx, uint64_t* d_out0, const uint64_t* d_a0, const uint64_t* d_b0, size_t n0, uint64_t* d_out1, const uint64_t* d_a1,
+                           const uint64_t* d_b1, size_t n1, const uint64_t* beta) {
+    PK_ENTER(ctx);
+    return lincomb2_pair(ctx, d_out0, d_a0, d_b0, n0, d_out1, d_a1, d_b1, n1, beta);
+}
+int pk_probe_axpy3(pk_ctx* ctx, uint64_t* d_y, const uint64_t* g3, const uint64_t* d_rows, size_t row_stride, size_t n) {
+    PK_ENTER(ctx);
+    return axpy3(ctx, d_y, g3, d_rows, row_stride, n);
+}
+int pk_probe_to_coeffs_generated(pk_ctx* ctx, unsigned m, const uint64_t* d_wit, size_t n_wit, const uint8_t seed32[32], uint32_t stream_mask,
+                                 uint32_t stream_g, uint64_t* d_f_evals, uint64_t* d_g_evals, uint64_t* d_f_coeffs, uint64_t* d_g_coeffs) {
+    PK_ENTER(ctx);
+    PK_REQUIRE(ctx, seed32, "null pointer");
+    RngKey k;
+    memcpy(k.k, seed32, 32);
+    return to_coeffs_generated(ctx, m, d_wit, n_wit, k, stream_mask, stream_g, d_f_evals, d_g_evals, d_f_coeffs, d_g_coeffs);
+}
 }  // extern "C"
