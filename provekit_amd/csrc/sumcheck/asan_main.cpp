@@ -8,6 +8,12 @@
 //   pks_verify_asan lane <D> <lo> <hi> <coeff> <weight> <repeats>        (64 hex digits each, the raw 256-bit value, big-endian)
 //     runs lane.hpp's lane_accumulate<D, D> -- the kernel's arithmetic, compiled for the host -- `repeats` times on D tables that all hold
 //     (lo, hi), one term over all of them, and prints the D + 1 sums the same way.
+//   pks_verify_asan shard <n> <world>
+//     drives shard.hpp's ownership rule and pkss_plan for tables of 2^n (n <= 20) and `world` ranks.  It marks, in exact-size heap
+//     blocks, the slot expand(y, g, r) of every rank r and compacted index y < 2^n / world -- an index outside the table is a report --
+//     and checks that every slot is marked once, that owner and compact invert expand, and the pair property at every sharded round
+//     length.  Then pkss_plan for m = 1 .. 4 at this (n, world): prints "n m g c S local_len handover_len arena_bytes" per line, or the
+//     refusal.  exit 1: the rule is not a bijection.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -16,6 +22,7 @@
 
 #include "../../../include/provekit_sumcheck.h"
 #include "lane.hpp"
+#include "shard.hpp"
 
 namespace {
 
@@ -125,11 +132,51 @@ int run_lane(int argc, char** argv) {
     return 0;
 }
 
+int run_shard(unsigned n, unsigned world) {
+    pks_statement st;
+    memset(&st, 0, sizeof st);
+    st.n = n, st.T = 1;
+    const pk::fe one = pk::fe_one();
+    memcpy(st.coeffs[0], one.v, 32);
+    for (unsigned m = 1; m <= 4; m++) {
+        st.m = m, st.masks[0] = (1u << m) - 1;
+        if (m == 4) st.T = 2, st.masks[0] = 7, st.masks[1] = 8, memcpy(st.coeffs[1], one.v, 32);  // a term has at most 3 tables
+        struct pkss_plan plan;
+        if (int rc = pkss_plan(&st, world, &plan)) {
+            printf("%d REFUSED %s\n", rc, pks_create_error());
+            return 0;  // n and world are refused whatever m is
+        }
+        printf("%u %u %u %u %u %zu %zu %zu\n", n, m, plan.g, plan.c, plan.S, plan.local_len, plan.handover_len, plan.arena_bytes);
+        if (m > 1 || n > 20 || n < PKSS_CHUNK_LOG2 + plan.g) continue;  // the rule itself once, where every rank owns whole chunks
+        const unsigned g = plan.g;
+        const size_t N = (size_t)1 << n, local = N >> g;
+        uint8_t* seen = (uint8_t*)calloc(N, 1);
+        for (unsigned r = 0; r < world; r++)
+            for (size_t y = 0; y < local; y++) {
+                const size_t x = pkss::expand(y, g, r);
+                if (y && x <= pkss::expand(y - 1, g, r)) return free(seen), 1;  // in order
+                if (pkss::owner(x, g) != r || pkss::compact(x, g) != y) return free(seen), 1;
+                seen[x]++;
+            }
+        for (size_t x = 0; x < N; x++)
+            if (seen[x] != 1) return free(seen), 1;
+        free(seen);
+        for (unsigned i = 0; pkss::round_is_sharded(n, i, g); i++) {  // the pair (x, x + len/2) compacts to (y, y + len_local/2)
+            const size_t len = N >> i;
+            for (size_t x = 0; x < len / 2; x++)
+                if (pkss::owner(x + len / 2, g) != pkss::owner(x, g) || pkss::compact(x + len / 2, g) != pkss::compact(x, g) + (len >> g) / 2) return 1;
+        }
+        if (pkss::sharded_rounds(n, g) != plan.S) return 1;
+    }
+    return 0;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
     if (argc == 3 && !strcmp(argv[1], "verify")) return run_verify(argv[2]);
     if (argc >= 2 && !strcmp(argv[1], "lane")) return run_lane(argc, argv);
-    fprintf(stderr, "usage: pks_verify_asan verify <case file> | lane <D> <lo> <hi> <coeff> <weight> <repeats>\n");
+    if (argc == 4 && !strcmp(argv[1], "shard")) return run_shard((unsigned)atoi(argv[2]), (unsigned)atoi(argv[3]));
+    fprintf(stderr, "usage: pks_verify_asan verify <case file> | lane <D> <lo> <hi> <coeff> <weight> <repeats> | shard <n> <world>\n");
     return 2;
 }

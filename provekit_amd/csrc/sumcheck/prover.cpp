@@ -4,20 +4,9 @@
 
 #include "../prover_transcript.hpp"
 #include "lane.hpp"
-#include "round.hpp"
+#include "prover.hpp"
 
 using pk::fe;
-
-struct pks_prover {
-    pk_ctx* ctx = nullptr;
-    pks_statement st{};
-    std::string pattern, err;
-    unsigned D = 0;
-    uint64_t* arena = nullptr;  // [m tables of 2^(n-1)] [round scratch] [split eq tables]
-    size_t half = 0;            // 2^(n-1)
-    pks::EqSplit split;
-    std::vector<fe> eq_host;
-};
 
 namespace {
 
@@ -27,17 +16,6 @@ int fail(pks_prover* p, int rc, const std::string& why) {
 }
 // the caller's work on the context is finished before anything here reads its tables; the library's own launches go to the null stream
 int hip_rc(hipError_t e) { return e == hipSuccess ? PK_OK : PK_ERR_HIP; }
-
-bool elements_below_p(const uint64_t* v, size_t n) {
-    for (size_t i = 0; i < n; i++)
-        if (!pk::is_canonical(pk::h_load(v + 4 * i))) return false;
-    return true;
-}
-
-// s from round 0's values: (1 - tau_0) h(0) + tau_0 h(1), or h(0) + h(1)
-fe sum_from_round0(const fe* h, const fe* tau0) {
-    return tau0 ? pk::h_add(h[0], pk::h_mul(*tau0, pk::h_sub(h[1], h[0]))) : pk::h_add(h[0], h[1]);
-}
 
 }  // namespace
 
@@ -84,19 +62,13 @@ const char* pks_last_error(const pks_prover* p) { return p ? p->err.c_str() : "n
 int pks_prove(pks_prover* p, const uint64_t* const* d_tables, const uint64_t* tau_or_null, const uint64_t* bind, uint8_t* proof_out, size_t cap,
               size_t* len, uint64_t* point_out, uint64_t* finals_out) {
     if (!p) return PK_ERR_BAD_ARG;
+    if (p->sharded) return fail(p, PK_ERR_BAD_ARG, "a prover of pkss_prover_create proves with pkss_prove");
     const pks_statement& st = p->st;
     const unsigned n = st.n, m = st.m, D = p->D;
     if (!d_tables || !len || (!proof_out && cap)) return fail(p, PK_ERR_BAD_ARG, "null pointer");
     const size_t need = 32 * pks::proof_elems(st);
     *len = need;
-    if (cap < need) return fail(p, PK_ERR_BAD_ARG, "the proof buffer holds " + std::to_string(cap) + " bytes, the proof has " + std::to_string(need));
-    for (unsigned j = 0; j < m; j++)
-        if (!d_tables[j]) return fail(p, PK_ERR_BAD_ARG, "null table");
-    if (st.has_tau && !tau_or_null) return fail(p, PK_ERR_BAD_ARG, "the statement has a tau: pass it");
-    if (!st.has_tau && tau_or_null) return fail(p, PK_ERR_BAD_ARG, "the statement has no tau: pass NULL");
-    if (st.n_bind && !bind) return fail(p, PK_ERR_BAD_ARG, "the statement binds elements: pass them");
-    if (!elements_below_p(bind, st.n_bind) || !elements_below_p(tau_or_null, st.has_tau ? n : 0))
-        return fail(p, PK_ERR_BAD_ARG, "a bind or tau element is not below p");
+    if (int rc = pks::check_prove_arguments(st, d_tables, tau_or_null, bind, cap, need, p->err)) return rc;
     try {
         if (int rc = pk_ctx_sync(p->ctx)) return fail(p, rc, "pk_ctx_sync failed");
         uint64_t* const d_scratch = p->arena + 4 * (size_t)m * p->half;
@@ -133,7 +105,7 @@ int pks_prove(pks_prover* p, const uint64_t* const* d_tables, const uint64_t* ta
                                            st.has_tau ? d_eq + 4 * lo : nullptr, lo_bits, pks::round_grid(pairs), d_scratch))
                 return fail(p, rc, "the round kernel's launch failed");
             if (hipMemcpy(h, d_results, 32 * (size_t)(D + 1), hipMemcpyDeviceToHost) != hipSuccess) return fail(p, PK_ERR_HIP, "a round's results did not arrive");
-            if (i == 0) tr.add_scalar(sum_from_round0(h, st.has_tau ? &tau[0] : nullptr));
+            if (i == 0) tr.add_scalar(pks::sum_from_round0(h, st.has_tau ? &tau[0] : nullptr));
             tr.add_scalars(h, D + 1);
             point[i] = tr.challenge_scalar();
         }
@@ -170,7 +142,7 @@ int pks_round(pk_ctx* ctx, const pks_statement* stmt, const uint64_t* const* d_t
     const size_t pairs = fold_or_null ? len / 4 : len / 2;
     unsigned R = 0;  // the round's length is 2 * pairs = 2^(R + 1)
     while (((size_t)1 << R) < pairs) R++;
-    if ((fold_or_null && !pk::is_canonical(pk::h_load(fold_or_null))) || (tau_rest_or_null && !elements_below_p(tau_rest_or_null, R)))
+    if ((fold_or_null && !pk::is_canonical(pk::h_load(fold_or_null))) || (tau_rest_or_null && !pks::elements_below_p(tau_rest_or_null, R)))
         return pks::refuse("a fold or tau element is not below p");
     pks::RoundTables rt{};
     for (unsigned j = 0; j < stmt->m; j++) {

@@ -15,11 +15,17 @@
 // the order.
 //
 // Specialised at compile time on what changes register pressure: D, m and whether the lane folds.  The term structure is uniform data.
+//
+// Device sets (shard.hpp): round_kernel_sharded is one rank's slice of a round, a sibling kernel so that the lone instantiations stay
+// what they were.  Its lane index y runs over the rank's compacted pairs.  It differs from the lone kernel in two places: the input is
+// either the caller's full tables, read at the rank's own indices expand(y) (rounds 0 and 1), or the rank's compacted arena, read at y
+// (from round 2 on); and the eq weight is that of the global pair index expand(y).  Output and partials are the lone kernel's.
 #include <hip/hip_runtime.h>
 
 #include "../reduce.hpp"
 #include "lane.hpp"
 #include "round.hpp"
+#include "shard.hpp"
 
 using namespace pk;
 
@@ -68,6 +74,57 @@ __global__ __launch_bounds__(THREADS) void round_kernel(DevTables tb, Terms tm, 
     if (threadIdx.x <= D) fe_store(partial + (size_t)threadIdx.x * gridDim.x + blockIdx.x, mine);
 }
 
+// One rank's slice: `pairs` are the rank's own (the round's pairs / G), g and rank the ownership rule's.  in_global: the input tables
+// are full tables at the round's global length, read at expand(y) with the halves (quarters, with a fold) in_step = G * pairs apart;
+// otherwise compacted ones, read at y, in_step = pairs.  The output tables are compacted either way
+template <int D, int M, bool FOLD>
+__global__ __launch_bounds__(THREADS) void round_kernel_sharded(DevTables tb, Terms tm, const fe* __restrict__ eq_hi, const fe* __restrict__ eq_lo,
+                                                                unsigned lo_bits, size_t pairs, unsigned g, unsigned rank, bool in_global, fe alpha,
+                                                                fe* __restrict__ partial) {
+    fe acc[D + 1];
+#pragma unroll
+    for (int k = 0; k <= D; k++) acc[k] = fe_zero();
+    const bool weighted = eq_hi != nullptr;
+    const size_t lo_mask = ((size_t)1 << lo_bits) - 1;
+    const size_t stride = (size_t)gridDim.x * THREADS;
+    const size_t in_step = in_global ? pairs << g : pairs;
+    for (size_t y = (size_t)blockIdx.x * THREADS + threadIdx.x; y < pairs; y += stride) {
+        const size_t x = pkss::expand(y, g, rank);  // the global pair index
+        const size_t at = in_global ? x : y;
+        fe lo[M], hi[M];
+#pragma unroll
+        for (int j = 0; j < M; j++) {
+            const fe* f = tb.in[j] + at;
+            fe x0 = fe_load(f), x1 = fe_load(f + in_step);
+            if (FOLD) {
+                const fe x2 = fe_load(f + 2 * in_step), x3 = fe_load(f + 3 * in_step);
+                x0 = fold_pair(x0, x2, alpha);
+                x1 = fold_pair(x1, x3, alpha);
+                fe_store(tb.out[j] + y, x0);
+                fe_store(tb.out[j] + y + pairs, x1);
+            }
+            lo[j] = x0;
+            hi[j] = x1;
+        }
+        fe w = fe_zero();
+        if (weighted) w = fe_mulx(fe_load(eq_hi + (x >> lo_bits)), fe_load(eq_lo + (x & lo_mask)));
+        lane_accumulate<D, M>(lo, hi, tm, weighted, w, acc);
+    }
+    const fe mine = block_reduce_fe<D + 1>(acc);  // thread k holds sum k
+    if (threadIdx.x <= D) fe_store(partial + (size_t)threadIdx.x * gridDim.x + blockIdx.x, mine);
+}
+
+// The hand-over: gathered = G blocks of m tables of 2^(c+1) elements, block r rank r's lower-half and upper-half chunks; out = the m
+// tables in global order, `out_stride` elements apart.  One lane per element
+__global__ __launch_bounds__(THREADS) void handover_kernel(const fe* __restrict__ gathered, unsigned m, unsigned g, fe* __restrict__ out, size_t out_stride) {
+    const size_t local = (size_t)2 << pkss::C, total = ((size_t)m * local) << g;
+    const size_t i = (size_t)blockIdx.x * THREADS + threadIdx.x;
+    if (i >= total) return;
+    const size_t y = i % local, j = (i / local) % m;
+    const unsigned r = (unsigned)(i / (local * m));
+    fe_store(out + j * out_stride + pkss::expand(y, g, r), fe_load(gathered + i));
+}
+
 // out[k] = the sum of partial[k * n_wg ..+ n_wg); one workgroup per sum, lane j adds the partials j, j + 256, ...
 __global__ __launch_bounds__(THREADS) void finish_kernel(const fe* __restrict__ partial, unsigned n_wg, fe* __restrict__ out) {
     const fe* p = partial + (size_t)blockIdx.x * n_wg;
@@ -86,6 +143,15 @@ void launch_dm(bool fold, unsigned grid, hipStream_t stream, const DevTables& tb
         round_kernel<D, M, false><<<grid, THREADS, 0, stream>>>(tb, tm, eq_hi, eq_lo, lo_bits, pairs, alpha, partial);
 }
 
+template <int D, int M>
+void launch_sharded_dm(bool fold, unsigned grid, hipStream_t stream, const DevTables& tb, const Terms& tm, const fe* eq_hi, const fe* eq_lo, unsigned lo_bits,
+                       size_t pairs, const ShardSlice& sh, const fe& alpha, fe* partial) {
+    if (fold)
+        round_kernel_sharded<D, M, true><<<grid, THREADS, 0, stream>>>(tb, tm, eq_hi, eq_lo, lo_bits, pairs, sh.g, sh.rank, sh.in_global, alpha, partial);
+    else
+        round_kernel_sharded<D, M, false><<<grid, THREADS, 0, stream>>>(tb, tm, eq_hi, eq_lo, lo_bits, pairs, sh.g, sh.rank, sh.in_global, alpha, partial);
+}
+
 }  // namespace
 
 unsigned round_grid(size_t pairs) {
@@ -93,8 +159,11 @@ unsigned round_grid(size_t pairs) {
     return (unsigned)(need < 1 ? 1 : need > PKS_MAX_GRID ? PKS_MAX_GRID : need);
 }
 
-int round_launch(hipStream_t stream, const pks_statement& st, const RoundTables& rt, size_t pairs, const uint64_t* fold_or_null, const uint64_t* d_eq_hi,
-                 const uint64_t* d_eq_lo, unsigned lo_bits, unsigned grid, uint64_t* d_scratch) {
+namespace {
+
+// the two launches' common part: `shard` null is the lone round
+int launch(hipStream_t stream, const pks_statement& st, const RoundTables& rt, size_t pairs, const uint64_t* fold_or_null, const uint64_t* d_eq_hi,
+           const uint64_t* d_eq_lo, unsigned lo_bits, unsigned grid, uint64_t* d_scratch, const ShardSlice* shard) {
     if (!pairs || grid < 1 || grid > PKS_MAX_GRID) return PK_ERR_BAD_ARG;
     DevTables tb{};
     for (unsigned j = 0; j < st.m; j++) {
@@ -114,14 +183,38 @@ int round_launch(hipStream_t stream, const pks_statement& st, const RoundTables&
     const fe *hi = (const fe*)d_eq_hi, *lo = (const fe*)d_eq_lo;
     const unsigned D = degree(st);
     const bool fold = fold_or_null != nullptr;
-#define PKS_CASE(DEG, TABLES)                                                                      \
-    if (D == DEG && st.m == TABLES) {                                                              \
-        launch_dm<DEG, TABLES>(fold, grid, stream, tb, tm, hi, lo, lo_bits, pairs, alpha, partial); \
+#define PKS_CASE(DEG, TABLES)                                                                                      \
+    if (D == DEG && st.m == TABLES) {                                                                              \
+        if (shard)                                                                                                 \
+            launch_sharded_dm<DEG, TABLES>(fold, grid, stream, tb, tm, hi, lo, lo_bits, pairs, *shard, alpha, partial); \
+        else                                                                                                       \
+            launch_dm<DEG, TABLES>(fold, grid, stream, tb, tm, hi, lo, lo_bits, pairs, alpha, partial);             \
     } else
     PKS_CASE(1, 1) PKS_CASE(1, 2) PKS_CASE(1, 3) PKS_CASE(1, 4) PKS_CASE(2, 2) PKS_CASE(2, 3) PKS_CASE(2, 4) PKS_CASE(3, 3) PKS_CASE(3, 4)
     return PK_ERR_BAD_ARG;  // D <= m: a term's tables are distinct
 #undef PKS_CASE
     finish_kernel<<<D + 1, THREADS, 0, stream>>>(partial, grid, partial + (size_t)4 * PKS_MAX_GRID);
+    return hipGetLastError() == hipSuccess ? PK_OK : PK_ERR_HIP;
+}
+
+}  // namespace
+
+int round_launch(hipStream_t stream, const pks_statement& st, const RoundTables& rt, size_t pairs, const uint64_t* fold_or_null, const uint64_t* d_eq_hi,
+                 const uint64_t* d_eq_lo, unsigned lo_bits, unsigned grid, uint64_t* d_scratch) {
+    return launch(stream, st, rt, pairs, fold_or_null, d_eq_hi, d_eq_lo, lo_bits, grid, d_scratch, nullptr);
+}
+
+int round_shard_launch(hipStream_t stream, const pks_statement& st, const RoundTables& rt, size_t pairs, const uint64_t* fold_or_null, const uint64_t* d_eq_hi,
+                       const uint64_t* d_eq_lo, unsigned lo_bits, unsigned grid, uint64_t* d_scratch, const ShardSlice& shard) {
+    // whole chunks only: every index the slice reads lies inside the round's tables because expand() of a whole chunk does
+    if (shard.g < 1 || shard.g > PKSS_MAX_WORLD_LOG2 || shard.rank >> shard.g || pairs % ((size_t)1 << pkss::C)) return PK_ERR_BAD_ARG;
+    return launch(stream, st, rt, pairs, fold_or_null, d_eq_hi, d_eq_lo, lo_bits, grid, d_scratch, &shard);
+}
+
+int handover_launch(hipStream_t stream, const uint64_t* d_gathered, unsigned m, unsigned g, uint64_t* d_out, size_t out_stride) {
+    if (m < 1 || m > PKS_MAX_TABLES || g < 1 || g > PKSS_MAX_WORLD_LOG2 || out_stride < pkss::handover_len(g)) return PK_ERR_BAD_ARG;
+    const size_t total = ((size_t)m * ((size_t)2 << pkss::C)) << g;
+    handover_kernel<<<(unsigned)(total / THREADS), THREADS, 0, stream>>>((const fe*)d_gathered, m, g, (fe*)d_out, out_stride);
     return hipGetLastError() == hipSuccess ? PK_OK : PK_ERR_HIP;
 }
 

@@ -70,4 +70,19 @@ constexpr size_t ROUND_SCRATCH_FES = (size_t)4 * PKS_MAX_GRID + 8;
 int round_launch(hipStream_t stream, const pks_statement& st, const RoundTables& tb, size_t pairs, const uint64_t* fold_or_null, const uint64_t* d_eq_hi,
                  const uint64_t* d_eq_lo, unsigned lo_bits, unsigned grid, uint64_t* d_scratch);
 
+// ---- device sets (shard.hpp) -----------------------------------------------------------------------------------------------------
+// one rank's slice of a round: G = 2^g ranks, this is `rank`; in_global: the input tables are full tables at the round's global
+// length (the caller's, rounds 0 and 1), read at the rank's own indices; otherwise the rank's compacted ones.  Output tables are compacted
+struct ShardSlice {
+    unsigned g, rank;
+    bool in_global;
+};
+// round_launch for a slice: `pairs` the rank's own pairs (the round's / G, whole chunks), eq tables the round's, indexed by the global
+// pair index; the rank's D + 1 partial sums to d_scratch[4 * PKS_MAX_GRID ..)
+int round_shard_launch(hipStream_t stream, const pks_statement& st, const RoundTables& tb, size_t pairs, const uint64_t* fold_or_null, const uint64_t* d_eq_hi,
+                       const uint64_t* d_eq_lo, unsigned lo_bits, unsigned grid, uint64_t* d_scratch, const ShardSlice& shard);
+// the hand-over: d_gathered = G blocks (rank order) of m tables of 2^(c+1) elements -> d_out[j * out_stride + x], the m tables of
+// 2^(c+g+1) in global order
+int handover_launch(hipStream_t stream, const uint64_t* d_gathered, unsigned m, unsigned g, uint64_t* d_out, size_t out_stride);
+
 }  // namespace pks
