@@ -1,0 +1,76 @@
+// asan_main.cpp -- driver of the sanitizer build of this library's host verifier (make asan; CPU code only):
+//   pkl_verify_asan verify <case file>
+//       u32 n, k, n_bind, n_bind2 | u32 pattern length | pattern | bind (n_bind elements) | bind2 (n_bind2 elements) |
+//       u32 count | count x (u64 length | bytes)
+//     verifies every proof with pkl_verify and prints "rc accepted check side offset" per proof.  A statement the library refuses
+//     prints one REFUSED line and nothing of the rest is read: its counts size nothing.  Proofs and bind elements live in exact-size
+//     heap blocks, so that a read past an end is a report, not a read of the next item.
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+#include "../../../include/provekit_lookup.h"
+
+namespace {
+
+std::vector<uint8_t> buf;  // the case file
+size_t at = 0;
+
+void take(void* dst, size_t n) {
+    if (buf.size() - at < n) exit(2);
+    if (n) memcpy(dst, buf.data() + at, n);
+    at += n;
+}
+void* take_block(size_t n) {  // the next n bytes in a heap block of exactly that size
+    if (buf.size() - at < n) exit(2);
+    void* p = malloc(n ? n : 1);
+    take(p, n);
+    return p;
+}
+
+int run_verify(const char* path) {
+    FILE* f = fopen(path, "rb");
+    if (!f) return 2;
+    uint8_t chunk[65536];
+    for (size_t got; (got = fread(chunk, 1, sizeof chunk, f)) > 0;) buf.insert(buf.end(), chunk, chunk + got);
+    fclose(f);
+    uint32_t head[4];
+    take(head, sizeof head);
+    pkl_statement st{head[0], head[1], head[2], head[3]};
+    size_t proof_len = 0;
+    if (int rc = pkl_proof_bytes(&st, &proof_len)) {
+        printf("%d 0 REFUSED 0 0 %s\n", rc, pkl_create_error());
+        return 0;
+    }
+    uint32_t pattern_len, count;
+    take(&pattern_len, 4);
+    uint8_t* pattern = (uint8_t*)take_block(pattern_len);
+    uint64_t* bind = st.n_bind ? (uint64_t*)take_block(32 * (size_t)st.n_bind) : nullptr;
+    uint64_t* bind2 = st.n_bind2 ? (uint64_t*)take_block(32 * (size_t)st.n_bind2) : nullptr;
+    take(&count, 4);
+    pkl_claims* claims = (pkl_claims*)malloc(sizeof(pkl_claims));
+    for (uint32_t c = 0; c < count; c++) {
+        uint64_t len;
+        take(&len, 8);
+        uint8_t* proof = (uint8_t*)take_block(len);
+        pkv_result r;
+        int side = -1;
+        const int rc = pkl_verify(&st, pattern_len ? pattern : nullptr, pattern_len, bind, bind2, proof, len, claims, &side, &r);
+        if (rc)
+            printf("%d 0 REFUSED 0 0 %s\n", rc, pkl_create_error());
+        else
+            printf("0 %d %s %d %llu\n", r.accepted, pks_check_name(r.check), side, (unsigned long long)r.offset);
+        free(proof);
+    }
+    free(claims), free(bind2), free(bind), free(pattern);
+    return 0;
+}
+
+}  // namespace
+
+int main(int argc, char** argv) {
+    if (argc == 3 && !strcmp(argv[1], "verify")) return run_verify(argv[2]);
+    fprintf(stderr, "usage: pkl_verify_asan verify <case file>\n");
+    return 2;
+}

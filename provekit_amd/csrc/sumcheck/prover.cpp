@@ -34,9 +34,8 @@ int pks_prover_create(pk_ctx* ctx, const pks_statement* stmt, pks_prover** out) 
         p->pattern = pks::io_pattern(*stmt);
         p->half = (size_t)1 << (stmt->n - 1);
         p->split = pks::eq_split(stmt->n - 1);
-        const size_t fes = (size_t)stmt->m * p->half + pks::ROUND_SCRATCH_FES + p->split.fes();
         void* base = nullptr;
-        if (int rc = pk_malloc(ctx, 32 * fes, &base)) {
+        if (int rc = pk_malloc(ctx, 32 * pks::lone_arena_fes(stmt->n, stmt->m), &base)) {
             delete p;
             pks::g_error = "pk_malloc of the arena failed";
             return rc;

@@ -64,6 +64,9 @@ struct RoundTables {
 unsigned round_grid(size_t pairs);
 // scratch for one round's partial sums and its results, in field elements
 constexpr size_t ROUND_SCRATCH_FES = (size_t)4 * PKS_MAX_GRID + 8;
+// a lone prover's arena in field elements: the m folded copies of half length, one round's scratch and the split eq weights.  What
+// pks_prover_create allocates; libprovekit_lookup.so states its two provers' share from the same rule (pkl_prover_arena_bytes).
+inline size_t lone_arena_fes(unsigned n, unsigned m) { return (size_t)m * ((size_t)1 << (n - 1)) + ROUND_SCRATCH_FES + eq_split(n - 1).fes(); }
 // Enqueue on `stream`: the round of `pairs` pairs (tables of 2 * pairs elements; with a fold: of 4 * pairs, folded first into tb.out),
 // the D + 1 sums to d_scratch[4 * PKS_MAX_GRID ..).  d_eq_hi == nullptr: weight 1.  The sums are the workgroups' partials
 // (d_scratch[k * grid + workgroup]) added by a finish kernel: field addition is exact, so the bits do not depend on the grid.

@@ -64,6 +64,11 @@ SIGNATURES = {
     "pk_probe_whir_hiding_grid": (C.c_uint, [C.c_uint, C.c_uint]),
     "pk_probe_whir_hiding_threads": (C.c_uint, []),
     "pk_probe_whir_hiding_pairs_per_lane": (C.c_uint, []),
+    # either of libprovekit_lookup.so's two gather kernels by itself (tools/probes/lookup.hip);
+    "pk_probe_lookup_gather": (C.c_int, [vp, vp, vp, vp, C.c_uint, C.c_uint, vp, vp, C.c_int, C.c_uint, C.POINTER(C.c_float)]),
+    # a pkl_prover's grid and the phases of its last proof
+    "pk_probe_lookup_set_grid": (C.c_int, [vp, C.c_uint]),
+    "pk_probe_lookup_profile": (C.c_int, [vp, C.POINTER(C.c_double)]),
     # csrc/witness.hip's thresholds and the shape of a levelled builder list (tools/probes/witness.hip): host only
     "pk_probe_witness_narrow": (C.c_uint, []),
     "pk_probe_witness_sum_heavy": (C.c_uint, []),

@@ -136,6 +136,21 @@ unsigned pk_probe_whir_hiding_grid(unsigned polys, unsigned n);
 unsigned pk_probe_whir_hiding_threads(void);
 unsigned pk_probe_whir_hiding_pairs_per_lane(void);
 
+/* libprovekit_lookup.so's gather by itself (csrc/lookup/kernels.hpp), for tools/lookup_bench.py: staged != 0 its LDS-staged kernel
+ * (k <= pkl_gather_lds_max_k()), staged == 0 the kernel that reads through L2, whatever the library's rule would pick; grid 0: the
+ * kernel's own rule.  d_g, d_dt: 2^k elements; d_idx: 2^n indices; d_hf, d_df: 2^n elements, written.  *ms: the launch's device
+ * time.  Blocking. */
+int pk_probe_lookup_gather(pk_ctx *ctx, const uint32_t *d_idx, const uint64_t *d_g, const uint64_t *d_dt, unsigned n, unsigned k, uint64_t *d_hf,
+                           uint64_t *d_df, int staged, unsigned grid, float *ms);
+/* A pkl_prover's test and benchmark knobs, which the library's C ABI does not carry (csrc/lookup/prover.hpp).  Host only.
+ * pk_probe_lookup_set_grid: the workgroups of the prover's own kernels from the next call on, 1 .. 1024; 0: each kernel's rule.  No
+ * bit of any result depends on it (tests/test_gpu_lookup.py).
+ * pk_probe_lookup_profile: the last proof's phases in milliseconds -- ms5[0..3): count, table, gather, device time between events
+ * around each phase's launches; ms5[3..5): the f side's and the t side's pks_prove, host time.  A phase that has not run reads 0. */
+struct pkl_prover;
+int pk_probe_lookup_set_grid(struct pkl_prover *p, unsigned grid);
+int pk_probe_lookup_profile(const struct pkl_prover *p, double *ms5);
+
 /* csrc/witness.hip's thresholds (csrc/witness_shape.hpp) and the shape of a levelled builder list (witness.hip here), for
  * tests/test_witness_edge_cases_host.py and tests/test_gpu_witness_edges.py.  Host only.  pk_probe_witness_phases: *n_phases = the
  * phases of postcard(Vec<WitnessBuilder>) after levelling (two per level); with cap >= *n_phases, widths[ph] = the items of phase
