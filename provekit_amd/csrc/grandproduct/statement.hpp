@@ -1,0 +1,88 @@
+// statement.hpp -- what the sources of libprovekit_grandproduct.so share on the host: which statements the library takes, the two
+// outer IO patterns, the pks statement of a layer, the proof's framing and the step from one layer's claim to the next.  Host only; no
+// device, no product call.
+#pragma once
+#include <string>
+
+#include "../../../include/provekit_grandproduct.h"
+#include "../verify/core.hpp"
+
+namespace pkg {
+
+using pk::fe;
+
+extern thread_local std::string g_error;  // pkg_create_error
+inline int refuse(const std::string& why) {
+    g_error = why;
+    return PK_ERR_BAD_ARG;
+}
+
+inline bool statement_ok(const pkg_statement* s, std::string& why) {
+    if (!s) return why = "null statement", false;
+    if (s->n < 1 || s->n > PKG_MAX_VARS) return why = "n must be 1..28", false;
+    if (s->n_bind > PKG_MAX_BIND) return why = "n_bind must be 0..16", false;
+    return true;
+}
+inline bool statement_ok(const pkg_multiset_statement* s, std::string& why) {
+    if (!s) return why = "null statement", false;
+    if (s->n < 1 || s->n > PKG_MAX_VARS) return why = "n must be 1..28", false;
+    if (s->w < 1 || s->w > PKG_MAX_COLUMNS) return why = "w must be 1..4", false;
+    if (s->n_bind > PKG_MAX_BIND) return why = "n_bind must be 0..16", false;
+    return true;
+}
+inline bool elements_below_p(const uint64_t* v, size_t n, const char* what, std::string& why) {
+    for (size_t i = 0; i < n; i++)
+        if (!pk::is_canonical(pk::h_load(v + 4 * i))) return why = std::string(what) + " element " + std::to_string(i) + " is not below p", false;
+    return true;
+}
+
+// pks's zero-count rule: an operation of no elements is no operation
+inline void pattern_op(std::string& d, char kind, size_t n, const char* label) {
+    if (!n) return;
+    d.push_back('\0');
+    d += kind + std::to_string(n) + label;
+}
+inline std::string io_pattern(const pkg_statement& s) {
+    std::string d = "provekit-hip/grandproduct/v1/n" + std::to_string(s.n);
+    pattern_op(d, 'A', s.n_bind, "bind");
+    pattern_op(d, 'A', 2, "top");
+    pattern_op(d, 'S', 1, "rho");
+    for (unsigned layer = 1; layer < s.n; layer++) {
+        pattern_op(d, 'S', 1, "seed");
+        pattern_op(d, 'A', 2, "finals");
+        pattern_op(d, 'S', 1, "rho");
+    }
+    return d;
+}
+inline std::string io_pattern(const pkg_multiset_statement& s) {
+    std::string d = "provekit-hip/multiset/v1/n" + std::to_string(s.n) + "/w" + std::to_string(s.w);
+    pattern_op(d, 'A', s.n_bind, "bind");
+    pattern_op(d, 'S', 1, "gamma");
+    pattern_op(d, 'S', s.w > 1 ? 1 : 0, "beta");
+    pattern_op(d, 'S', 2, "seeds");
+    return d;
+}
+// each side of a multiset proof is a grand product that binds its seed
+inline pkg_statement side_statement(const pkg_multiset_statement& s) { return pkg_statement{s.n, 1}; }
+
+// Layer d's sumcheck, sum_x eq(z_d, x) L_d(x) R_d(x) = c_d over d variables: constant, so a prover creates its pks provers once.
+inline pks_statement layer_statement(unsigned d) {
+    pks_statement st{};
+    const fe one = pk::fe_one();
+    st.n = d, st.m = 2, st.T = 1, st.masks[0] = 3, st.has_tau = 1, st.n_bind = 1;
+    memcpy(st.coeffs[0], one.v, 32);
+    return st;
+}
+// bytes of layer d's pks proof: s, d rounds of 3 values, 2 finals
+inline size_t layer_bytes(unsigned d) { return (size_t)32 * (3 + 3 * (size_t)d); }
+// where layer d's proof starts: top | layer 1 | .. ; layer_at(n) is the whole proof's length, 64 + 48 (n - 1)(n + 2)
+inline size_t layer_at(unsigned d) { return 64 + (size_t)48 * (d - 1) * (d + 2); }
+inline size_t proof_bytes(const pkg_statement& s) { return layer_at(s.n); }
+inline size_t proof_bytes(const pkg_multiset_statement& s) { return 2 * layer_at(s.n); }
+
+// c' = (1 - rho) l + rho r
+inline fe next_claim(const fe& l, const fe& r, const fe& rho) { return pk::h_add(l, pk::h_mul(rho, pk::h_sub(r, l))); }
+
+inline void put_fe(uint64_t* dst, const fe& x) { memcpy(dst, x.v, 32); }
+
+}  // namespace pkg

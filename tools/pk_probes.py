@@ -69,6 +69,14 @@ SIGNATURES = {
     # a pkl_prover's grid and the phases of its last proof
     "pk_probe_lookup_set_grid": (C.c_int, [vp, C.c_uint]),
     "pk_probe_lookup_profile": (C.c_int, [vp, C.POINTER(C.c_double)]),
+    # libprovekit_grandproduct.so's tree and leaf kernels with their layers per launch and grid (tools/probes/grandproduct.hip);
+    "pk_probe_grandproduct_tree": (C.c_int, [vp, C.c_uint, vp, vp, C.c_uint, C.c_uint, C.POINTER(C.c_float)]),
+    "pk_probe_grandproduct_leaf_tree": (C.c_int, [vp, C.c_uint, C.c_uint, vp, vp, vp, vp, vp, C.c_uint, C.c_uint, C.POINTER(C.c_float)]),
+    "pk_probe_grandproduct_default_layers": (C.c_uint, []),
+    # a pkg_prover's two knobs and the phases of its last proof; the pkg_prover inside a multiset prover
+    "pk_probe_grandproduct_set_knobs": (C.c_int, [vp, C.c_uint, C.c_uint]),
+    "pk_probe_grandproduct_profile": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "pk_probe_multiset_inner": (vp, [vp]),
     # csrc/witness.hip's thresholds and the shape of a levelled builder list (tools/probes/witness.hip): host only
     "pk_probe_witness_narrow": (C.c_uint, []),
     "pk_probe_witness_sum_heavy": (C.c_uint, []),

@@ -151,6 +151,25 @@ struct pkl_prover;
 int pk_probe_lookup_set_grid(struct pkl_prover *p, unsigned grid);
 int pk_probe_lookup_profile(const struct pkl_prover *p, double *ms5);
 
+/* libprovekit_grandproduct.so's tree kernels by themselves (csrc/grandproduct/kernels.hpp) with the two knobs its C ABI does not carry:
+ * layers per launch of tree_kernel / leaf_kernel (1 .. 3; 0: the library's value, pk_probe_grandproduct_default_layers) and the grid
+ * (1 .. 1024; 0: one lane per low index).  No bit of any layer depends on either (tests/test_gpu_grandproduct.py).  d_v, d_tree,
+ * d_leaf: 2^n elements; d_cols: w device pointers (a host array); gamma, beta: one host element each.  *ms: the launches' device
+ * time.  Blocking. */
+int pk_probe_grandproduct_tree(pk_ctx *ctx, unsigned n, const uint64_t *d_v, uint64_t *d_tree, unsigned layers, unsigned grid, float *ms);
+int pk_probe_grandproduct_leaf_tree(pk_ctx *ctx, unsigned n, unsigned w, const uint64_t *const *d_cols, const uint64_t *gamma, const uint64_t *beta,
+                                    uint64_t *d_leaf, uint64_t *d_tree, unsigned layers, unsigned grid, float *ms);
+unsigned pk_probe_grandproduct_default_layers(void);
+/* A pkg_prover's test and benchmark knobs (csrc/grandproduct/prover.hpp).  Host only.  pk_probe_grandproduct_set_knobs: the same two
+ * knobs for the prover's proofs from the next call on.  pk_probe_grandproduct_profile: the last proof's tree phase in milliseconds of
+ * device time (events around its launches) and layer_ms28[d], 1 <= d < n, layer d's pks_prove in host time; what has not run reads 0.
+ * pk_probe_multiset_inner: the pkg_prover a multiset prover proves both sides through (its profile is the side proved last, B). */
+struct pkg_prover;
+struct pkg_multiset_prover;
+int pk_probe_grandproduct_set_knobs(struct pkg_prover *p, unsigned layers, unsigned grid);
+int pk_probe_grandproduct_profile(const struct pkg_prover *p, double *tree_ms, double *layer_ms28);
+struct pkg_prover *pk_probe_multiset_inner(struct pkg_multiset_prover *p);
+
 /* csrc/witness.hip's thresholds (csrc/witness_shape.hpp) and the shape of a levelled builder list (witness.hip here), for
  * tests/test_witness_edge_cases_host.py and tests/test_gpu_witness_edges.py.  Host only.  pk_probe_witness_phases: *n_phases = the
  * phases of postcard(Vec<WitnessBuilder>) after levelling (two per level); with cap >= *n_phases, widths[ph] = the items of phase
