@@ -182,7 +182,9 @@ int pk_malloc(pk_ctx* ctx, size_t bytes, void** d_ptr) {
     if (!ctx || !d_ptr) return PK_ERR_BAD_ARG;
     *d_ptr = nullptr;
     PK_HIP(ctx, hipSetDevice(ctx->device));
-    PK_HIP(ctx, hipMalloc(d_ptr, bytes ? bytes : 1));
+    const hipError_t e = hipMalloc(d_ptr, bytes ? bytes : 1);
+    if (e != hipSuccess) (void)hipGetLastError();  // reported by the return code: not left for the thread's next launch check to find
+    PK_HIP(ctx, e);
     return PK_OK;
 }
 int pk_free(pk_ctx* ctx, void* d_ptr) {

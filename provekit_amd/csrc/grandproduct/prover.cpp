@@ -1,23 +1,13 @@
 // prover.cpp -- the device half of libprovekit_grandproduct.so's C ABI: the two provers (one arena each, the launches of tree.hip,
 // the prover side of the outer transcripts, the chain of pks proofs) and the tree by itself.  Host code; of other libraries it calls
 // what provekit_hip.h and provekit_sumcheck.h declare.
-#include <chrono>
-
 #include "prover.hpp"
 
+using pk::fail;
 using pk::fe;
+using pk::host_ms_since;
 
 namespace {
-
-int fail(pkg_prover* p, int rc, const std::string& why) {
-    p->err = why;
-    return rc;
-}
-int fail(pkg_multiset_prover* p, int rc, const std::string& why) {
-    p->err = why;
-    return rc;
-}
-double host_ms_since(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
 
 // a prover of `stmt` with its arena, events and pks provers; the reason of a failure goes to pkg::g_error
 int make_prover(pk_ctx* ctx, const pkg_statement& stmt, std::unique_ptr<pkg_prover>& out) {
@@ -46,8 +36,7 @@ int read_top(pkg_prover* p, const uint64_t* d_bottom) {
     if (hipMemcpy(p->product.v, p->tree + 4, 32, hipMemcpyDeviceToHost) != hipSuccess ||
         hipMemcpy(p->top, n == 1 ? d_bottom : p->tree + 8, 64, hipMemcpyDeviceToHost) != hipSuccess)
         return fail(p, PK_ERR_HIP, "the top of the tree did not arrive");
-    float ms = 0;
-    p->prof.tree_ms = hipEventElapsedTime(&ms, p->ev[0], p->ev[1]) == hipSuccess ? (double)ms : 0.0;
+    p->prof.tree_ms = pk::between(p->ev[0], p->ev[1]);
     return PK_OK;
 }
 
@@ -121,11 +110,7 @@ int pkg_prover_create(pk_ctx* ctx, const pkg_statement* stmt, pkg_prover** out) 
         pkg::g_error.clear();
         return PK_OK;
     } catch (...) {
-        try {
-            pkg::g_error = "out of host memory while the prover was made";
-        } catch (...) {
-        }
-        return PK_ERR_OOM;
+        return pk::out_of_host_memory(pkg::g_error);
     }
 }
 
@@ -198,11 +183,7 @@ int pkg_multiset_prover_create(pk_ctx* ctx, const pkg_multiset_statement* stmt, 
         pkg::g_error.clear();
         return PK_OK;
     } catch (...) {
-        try {
-            pkg::g_error = "out of host memory while the prover was made";
-        } catch (...) {
-        }
-        return PK_ERR_OOM;
+        return pk::out_of_host_memory(pkg::g_error);
     }
 }
 

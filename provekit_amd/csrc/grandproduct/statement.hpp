@@ -5,17 +5,14 @@
 #include <string>
 
 #include "../../../include/provekit_grandproduct.h"
-#include "../verify/core.hpp"
+#include "../argument.hpp"
 
 namespace pkg {
 
 using pk::fe;
 
 extern thread_local std::string g_error;  // pkg_create_error
-inline int refuse(const std::string& why) {
-    g_error = why;
-    return PK_ERR_BAD_ARG;
-}
+inline int refuse(const std::string& why) { return pk::refuse(g_error, why); }
 
 inline bool statement_ok(const pkg_statement* s, std::string& why) {
     if (!s) return why = "null statement", false;
@@ -30,18 +27,10 @@ inline bool statement_ok(const pkg_multiset_statement* s, std::string& why) {
     if (s->n_bind > PKG_MAX_BIND) return why = "n_bind must be 0..16", false;
     return true;
 }
-inline bool elements_below_p(const uint64_t* v, size_t n, const char* what, std::string& why) {
-    for (size_t i = 0; i < n; i++)
-        if (!pk::is_canonical(pk::h_load(v + 4 * i))) return why = std::string(what) + " element " + std::to_string(i) + " is not below p", false;
-    return true;
-}
+using pk::elements_below_p;
+using pk::pattern_op;
+using pk::put_fe;
 
-// pks's zero-count rule: an operation of no elements is no operation
-inline void pattern_op(std::string& d, char kind, size_t n, const char* label) {
-    if (!n) return;
-    d.push_back('\0');
-    d += kind + std::to_string(n) + label;
-}
 inline std::string io_pattern(const pkg_statement& s) {
     std::string d = "provekit-hip/grandproduct/v1/n" + std::to_string(s.n);
     pattern_op(d, 'A', s.n_bind, "bind");
@@ -82,7 +71,5 @@ inline size_t proof_bytes(const pkg_multiset_statement& s) { return 2 * layer_at
 
 // c' = (1 - rho) l + rho r
 inline fe next_claim(const fe& l, const fe& r, const fe& rho) { return pk::h_add(l, pk::h_mul(rho, pk::h_sub(r, l))); }
-
-inline void put_fe(uint64_t* dst, const fe& x) { memcpy(dst, x.v, 32); }
 
 }  // namespace pkg

@@ -20,23 +20,7 @@ void verdict(pkv_result* r, int check, uint64_t offset, const std::string& msg) 
     pkv::to_result(v, r);
 }
 
-void put_canonical(std::vector<uint8_t>& bytes, const uint64_t* v, size_t n) {
-    for (size_t i = 0; i < n; i++) {
-        const fe c = pk::h_to_canon(pk::h_load(v + 4 * i));
-        bytes.insert(bytes.end(), (const uint8_t*)c.v, (const uint8_t*)c.v + 32);
-    }
-}
-
-bool parse_pattern(pkv::Statement& st, const uint8_t* given, size_t given_len, const std::string& own) {
-    if (given && given_len)
-        st.pattern.assign((const char*)given, given_len);
-    else
-        st.pattern = own;
-    std::string why;
-    if (pk::io_pattern_parse(st.pattern, st.ops, why)) return true;
-    pkg::g_error = why;
-    return false;
-}
+using pk::put_canonical;
 
 struct Product {
     fe product, value;
@@ -108,10 +92,7 @@ int pattern_out(const S* stmt, uint8_t* buf, size_t cap, size_t* len) {
     if (!len) return pkg::refuse("null pointer");
     if (!pkg::statement_ok(stmt, why)) return pkg::refuse(why);
     try {
-        const std::string d = pkg::io_pattern(*stmt);
-        *len = d.size();
-        if (buf && cap >= d.size()) memcpy(buf, d.data(), d.size());
-        return PK_OK;
+        return pk::pattern_out(pkg::io_pattern(*stmt), buf, cap, len);
     } catch (...) {
         return PK_ERR_OOM;
     }
@@ -153,7 +134,7 @@ int pkg_verify(const pkg_statement* stmt, const uint8_t* io_pattern_or_null, siz
     if (expected_product_or_null && !pkg::elements_below_p(expected_product_or_null, 1, "expected_product", why)) return pkg::refuse(why);
     try {
         pkv::Statement st;
-        if (!parse_pattern(st, io_pattern_or_null, io_pattern_len, pkg::io_pattern(s))) return PK_ERR_IO_PATTERN;
+        if (int rc = pk::parse_pattern(st, io_pattern_or_null, io_pattern_len, pkg::io_pattern(s), pkg::g_error)) return rc;
         if (layer_out) *layer_out = 0;
         // framing first: every part has a fixed length, so a proof of another length is judged before any part is read
         const size_t total = pkg::proof_bytes(s);
@@ -185,7 +166,7 @@ int pkg_multiset_verify(const pkg_multiset_statement* stmt, const uint8_t* io_pa
     if (!pkg::elements_below_p(bind, s.n_bind, "bind", why)) return pkg::refuse(why);
     try {
         pkv::Statement st;
-        if (!parse_pattern(st, io_pattern_or_null, io_pattern_len, pkg::io_pattern(s))) return PK_ERR_IO_PATTERN;
+        if (int rc = pk::parse_pattern(st, io_pattern_or_null, io_pattern_len, pkg::io_pattern(s), pkg::g_error)) return rc;
         if (layer_out) *layer_out = 0;
         if (side_out) *side_out = PKG_SIDE_A;
         const pkg_statement side = pkg::side_statement(s);
@@ -207,8 +188,7 @@ int pkg_multiset_verify(const pkg_multiset_statement* stmt, const uint8_t* io_pa
             return PK_OK;
         }
         pkv::Statement inner;
-        inner.pattern = pkg::io_pattern(side);
-        if (!pk::io_pattern_parse(inner.pattern, inner.ops, why)) return pkg::g_error = why, PK_ERR_IO_PATTERN;
+        if (int rc = pk::parse_pattern(inner, nullptr, 0, pkg::io_pattern(side), pkg::g_error)) return rc;
         Product out[2];
         for (int which = PKG_SIDE_A; which <= PKG_SIDE_B; which++) {
             unsigned layer = 0;

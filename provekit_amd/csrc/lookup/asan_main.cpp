@@ -5,36 +5,17 @@
 //     verifies every proof with pkl_verify and prints "rc accepted check side offset" per proof.  A statement the library refuses
 //     prints one REFUSED line and nothing of the rest is read: its counts size nothing.  Proofs and bind elements live in exact-size
 //     heap blocks, so that a read past an end is a report, not a read of the next item.
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
 
 #include "../../../include/provekit_lookup.h"
+#include "../asan_case.hpp"
 
 namespace {
 
-std::vector<uint8_t> buf;  // the case file
-size_t at = 0;
-
-void take(void* dst, size_t n) {
-    if (buf.size() - at < n) exit(2);
-    if (n) memcpy(dst, buf.data() + at, n);
-    at += n;
-}
-void* take_block(size_t n) {  // the next n bytes in a heap block of exactly that size
-    if (buf.size() - at < n) exit(2);
-    void* p = malloc(n ? n : 1);
-    take(p, n);
-    return p;
-}
+using asan_case::take;
+using asan_case::take_block;
 
 int run_verify(const char* path) {
-    FILE* f = fopen(path, "rb");
-    if (!f) return 2;
-    uint8_t chunk[65536];
-    for (size_t got; (got = fread(chunk, 1, sizeof chunk, f)) > 0;) buf.insert(buf.end(), chunk, chunk + got);
-    fclose(f);
+    if (!asan_case::read_file(path)) return 2;
     uint32_t head[4];
     take(head, sizeof head);
     pkl_statement st{head[0], head[1], head[2], head[3]};

@@ -1,31 +1,13 @@
 // prover.cpp -- the device half of libprovekit_lookup.so's C ABI: the prover (one arena, the launches of lookup.hip, the prover side
 // of the outer transcript, the two pks proofs).  Host code; of other libraries it calls what provekit_hip.h and provekit_sumcheck.h
 // declare.
-#include <chrono>
-
 #include "prover.hpp"
 
+using pk::between;
+using pk::elements_below_p;
+using pk::fail;
 using pk::fe;
-
-namespace {
-
-int fail(pkl_prover* p, int rc, const std::string& why) {
-    p->err = why;
-    return rc;
-}
-// device milliseconds between two recorded events whose work has completed
-double between(hipEvent_t a, hipEvent_t b) {
-    float ms = 0;
-    return hipEventElapsedTime(&ms, a, b) == hipSuccess ? (double)ms : 0.0;
-}
-double host_ms_since(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
-bool elements_below_p(const uint64_t* v, size_t n) {
-    for (size_t i = 0; i < n; i++)
-        if (!pk::is_canonical(pk::h_load(v + 4 * i))) return false;
-    return true;
-}
-
-}  // namespace
+using pk::host_ms_since;
 
 extern "C" {
 
@@ -56,11 +38,7 @@ int pkl_prover_create(pk_ctx* ctx, const pkl_statement* stmt, pkl_prover** out) 
         pkl::g_error.clear();
         return PK_OK;
     } catch (...) {
-        try {
-            pkl::g_error = "out of host memory while the prover was made";
-        } catch (...) {
-        }
-        return PK_ERR_OOM;
+        return pk::out_of_host_memory(pkl::g_error);
     }
 }
 

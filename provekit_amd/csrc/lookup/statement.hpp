@@ -5,17 +5,14 @@
 #include <string>
 
 #include "../../../include/provekit_lookup.h"
-#include "../verify/core.hpp"
+#include "../argument.hpp"
 
 namespace pkl {
 
 using pk::fe;
 
 extern thread_local std::string g_error;  // pkl_create_error
-inline int refuse(const std::string& why) {
-    g_error = why;
-    return PK_ERR_BAD_ARG;
-}
+inline int refuse(const std::string& why) { return pk::refuse(g_error, why); }
 
 inline bool statement_ok(const pkl_statement* s, std::string& why) {
     if (!s) return why = "null statement", false;
@@ -28,11 +25,7 @@ inline bool statement_ok(const pkl_statement* s, std::string& why) {
 
 inline std::string io_pattern(const pkl_statement& s) {
     std::string d = "provekit-hip/lookup/v1/n" + std::to_string(s.n) + "/k" + std::to_string(s.k);
-    auto op = [&](char kind, size_t n, const char* label) {  // pks's zero-count rule: no operation
-        if (!n) return;
-        d.push_back('\0');
-        d += kind + std::to_string(n) + label;
-    };
+    auto op = [&](char kind, size_t n, const char* label) { pk::pattern_op(d, kind, n, label); };
     op('A', s.n_bind, "bind");
     op('S', 1, "alpha");
     op('A', s.n_bind2, "helpers");
@@ -80,7 +73,7 @@ inline fe half_pow(unsigned vars) { return pk::h_pow(pk::h_half(), vars); }
 inline void derive_claims(const pkl_statement& st, const fe& alpha, const fe& s, const fe* r_f, const fe* r_t, const fe* finals_f, const fe* finals_t,
                           pkl_claims* c) {
     memset(c, 0, sizeof *c);
-    auto put = [](uint64_t* dst, const fe& x) { memcpy(dst, x.v, 32); };
+    const auto put = pk::put_fe;
     put(c->alpha, alpha);
     put(c->s, s);
     for (unsigned i = 0; i < st.n; i++) put(c->r_f[i], r_f[i]);

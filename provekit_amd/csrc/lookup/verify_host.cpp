@@ -13,12 +13,6 @@ namespace {
 
 using pk::fe;
 
-bool elements_below_p(const uint64_t* v, size_t n, const char* what, std::string& why) {
-    for (size_t i = 0; i < n; i++)
-        if (!pk::is_canonical(pk::h_load(v + 4 * i))) return why = std::string(what) + " element " + std::to_string(i) + " is not below p", false;
-    return true;
-}
-
 void verdict(pkv_result* r, int* side_out, int side, int check, uint64_t offset, const std::string& msg) {
     pkv::Verdict v;
     v.failed = check != PKV_CHECK_NONE, v.check = check, v.offset = offset, v.message = msg;
@@ -39,10 +33,7 @@ int pkl_io_pattern(const pkl_statement* stmt, uint8_t* buf, size_t cap, size_t* 
     if (!len) return pkl::refuse("null pointer");
     if (!pkl::statement_ok(stmt, why)) return pkl::refuse(why);
     try {
-        const std::string d = pkl::io_pattern(*stmt);
-        *len = d.size();
-        if (buf && cap >= d.size()) memcpy(buf, d.data(), d.size());
-        return PK_OK;
+        return pk::pattern_out(pkl::io_pattern(*stmt), buf, cap, len);
     } catch (...) {
         return PK_ERR_OOM;
     }
@@ -69,17 +60,10 @@ int pkl_verify(const pkl_statement* stmt, const uint8_t* io_pattern_or_null, siz
     const pkl_statement& s = *stmt;
     if (s.n_bind && !bind) return pkl::refuse("the statement binds elements: pass them");
     if (s.n_bind2 && !bind2) return pkl::refuse("the statement binds elements after the helper tables: pass them");
-    if (!elements_below_p(bind, s.n_bind, "bind", why) || !elements_below_p(bind2, s.n_bind2, "bind2", why)) return pkl::refuse(why);
+    if (!pk::elements_below_p(bind, s.n_bind, "bind", why) || !pk::elements_below_p(bind2, s.n_bind2, "bind2", why)) return pkl::refuse(why);
     try {
         pkv::Statement st;
-        if (io_pattern_or_null && io_pattern_len)
-            st.pattern.assign((const char*)io_pattern_or_null, io_pattern_len);
-        else
-            st.pattern = pkl::io_pattern(s);
-        if (!pk::io_pattern_parse(st.pattern, st.ops, why)) {
-            pkl::g_error = why;
-            return PK_ERR_IO_PATTERN;
-        }
+        if (int rc = pk::parse_pattern(st, io_pattern_or_null, io_pattern_len, pkl::io_pattern(s), pkl::g_error)) return rc;
         pkl::Framing fr;
         if (int rc = pkl::framing(s, fr)) return pkl::g_error = pks_create_error(), rc;
         // framing first: the three parts have fixed lengths, so a proof of another length is judged before any part is read
@@ -88,14 +72,8 @@ int pkl_verify(const pkl_statement* stmt, const uint8_t* io_pattern_or_null, siz
 
         // the outer transcript reads one string: bind | bind2 | s
         std::vector<uint8_t> bytes;
-        auto put = [&](const uint64_t* v, size_t n) {
-            for (size_t i = 0; i < n; i++) {
-                const fe c = pk::h_to_canon(pk::h_load(v + 4 * i));
-                bytes.insert(bytes.end(), (const uint8_t*)c.v, (const uint8_t*)c.v + 32);
-            }
-        };
-        put(bind, s.n_bind);
-        put(bind2, s.n_bind2);
+        pk::put_canonical(bytes, bind, s.n_bind);
+        pk::put_canonical(bytes, bind2, s.n_bind2);
         const size_t prefix = bytes.size();
         bytes.insert(bytes.end(), proof, proof + 32);
 

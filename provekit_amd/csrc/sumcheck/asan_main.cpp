@@ -8,45 +8,27 @@
 //   pks_verify_asan lane <D> <lo> <hi> <coeff> <weight> <repeats>        (64 hex digits each, the raw 256-bit value, big-endian)
 //     runs lane.hpp's lane_accumulate<D, D> -- the kernel's arithmetic, compiled for the host -- `repeats` times on D tables that all hold
 //     (lo, hi), one term over all of them, and prints the D + 1 sums the same way.
-//   pks_verify_asan shard <n> <world>
+//   pks_verify_asan shard <n> <world> [lone]
 //     drives shard.hpp's ownership rule and pkss_plan for tables of 2^n (n <= 20) and `world` ranks.  It marks, in exact-size heap
 //     blocks, the slot expand(y, g, r) of every rank r and compacted index y < 2^n / world -- an index outside the table is a report --
 //     and checks that every slot is marked once, that owner and compact invert expand, and the pair property at every sharded round
 //     length.  Then pkss_plan for m = 1 .. 4 at this (n, world): prints "n m g c S local_len handover_len arena_bytes" per line, or the
-//     refusal.  exit 1: the rule is not a bijection.
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
+//     refusal.  With `lone`, one more column: the bytes of the lone prover's arena at this (n, m), the layout of a device set of one.
+//     exit 1: the rule is not a bijection.
 #include <string>
-#include <vector>
 
 #include "../../../include/provekit_sumcheck.h"
+#include "../asan_case.hpp"
 #include "lane.hpp"
-#include "shard.hpp"
+#include "layout.hpp"
 
 namespace {
 
-std::vector<uint8_t> buf;  // the case file
-size_t at = 0;
-
-void take(void* dst, size_t n) {
-    if (buf.size() - at < n) exit(2);
-    if (n) memcpy(dst, buf.data() + at, n);
-    at += n;
-}
-void* take_block(size_t n) {  // the next n bytes in a heap block of exactly that size
-    if (buf.size() - at < n) exit(2);
-    void* p = malloc(n ? n : 1);
-    take(p, n);
-    return p;
-}
+using asan_case::take;
+using asan_case::take_block;
 
 int run_verify(const char* path) {
-    FILE* f = fopen(path, "rb");
-    if (!f) return 2;
-    uint8_t chunk[65536];
-    for (size_t got; (got = fread(chunk, 1, sizeof chunk, f)) > 0;) buf.insert(buf.end(), chunk, chunk + got);
-    fclose(f);
+    if (!asan_case::read_file(path)) return 2;
     pks_statement st;
     memset(&st, 0, sizeof st);
     uint32_t head[9];
@@ -132,7 +114,7 @@ int run_lane(int argc, char** argv) {
     return 0;
 }
 
-int run_shard(unsigned n, unsigned world) {
+int run_shard(unsigned n, unsigned world, bool lone) {
     pks_statement st;
     memset(&st, 0, sizeof st);
     st.n = n, st.T = 1;
@@ -146,7 +128,9 @@ int run_shard(unsigned n, unsigned world) {
             printf("%d REFUSED %s\n", rc, pks_create_error());
             return 0;  // n and world are refused whatever m is
         }
-        printf("%u %u %u %u %u %zu %zu %zu\n", n, m, plan.g, plan.c, plan.S, plan.local_len, plan.handover_len, plan.arena_bytes);
+        printf("%u %u %u %u %u %zu %zu %zu", n, m, plan.g, plan.c, plan.S, plan.local_len, plan.handover_len, plan.arena_bytes);
+        if (lone) printf(" %zu", 32 * pkss::layout(n, m, 0).total);
+        printf("\n");
         if (m > 1 || n > 20 || n < PKSS_CHUNK_LOG2 + plan.g) continue;  // the rule itself once, where every rank owns whole chunks
         const unsigned g = plan.g;
         const size_t N = (size_t)1 << n, local = N >> g;
@@ -176,7 +160,8 @@ int run_shard(unsigned n, unsigned world) {
 int main(int argc, char** argv) {
     if (argc == 3 && !strcmp(argv[1], "verify")) return run_verify(argv[2]);
     if (argc >= 2 && !strcmp(argv[1], "lane")) return run_lane(argc, argv);
-    if (argc == 4 && !strcmp(argv[1], "shard")) return run_shard((unsigned)atoi(argv[2]), (unsigned)atoi(argv[3]));
-    fprintf(stderr, "usage: pks_verify_asan verify <case file> | lane <D> <lo> <hi> <coeff> <weight> <repeats> | shard <n> <world>\n");
+    const bool lone = argc == 5 && !strcmp(argv[4], "lone");
+    if ((argc == 4 || lone) && !strcmp(argv[1], "shard")) return run_shard((unsigned)atoi(argv[2]), (unsigned)atoi(argv[3]), lone);
+    fprintf(stderr, "usage: pks_verify_asan verify <case file> | lane <D> <lo> <hi> <coeff> <weight> <repeats> | shard <n> <world> [lone]\n");
     return 2;
 }

@@ -1,19 +1,15 @@
-// prover.hpp -- what prover.cpp (the lone prover) and prover_sharded.cpp (the prover on a device set) share: the prover object and
-// the layout of a sharded prover's arena, which pkss_plan reports.  Host only.
+// prover.hpp -- what prover.cpp (the prover, lone or on a device set, and the lone entry points) and prover_sharded.cpp (the device
+// set's entry points) share: the prover object (layout.hpp states its arena).  Host only.
 #pragma once
+#include <memory>
 #include <string>
 #include <vector>
 
-#include "round.hpp"
-#include "shard.hpp"
+#include "layout.hpp"
 
 namespace pks {
 
-inline bool elements_below_p(const uint64_t* v, size_t n) {
-    for (size_t i = 0; i < n; i++)
-        if (!pk::is_canonical(pk::h_load(v + 4 * i))) return false;
-    return true;
-}
+using pk::elements_below_p;
 
 // what pks_prove and pkss_prove refuse of their arguments, with the reason
 inline int check_prove_arguments(const pks_statement& st, const uint64_t* const* d_tables, const uint64_t* tau, const uint64_t* bind, size_t cap, size_t need,
@@ -36,53 +32,49 @@ inline fe sum_from_round0(const fe* h, const fe* tau0) {
 
 }  // namespace pks
 
-namespace pkss {
-
-// what a rank contributes to the exchange behind a sharded round: up to D + 1 sums, and one element whose first limb is its status
-constexpr size_t XCHG_FES = PKS_MAX_TERM_TABLES + 2;
-
-// A sharded prover's arena, in field elements from its start:
-//   [compact: m tables of 2^(n-1) / G -- the rank's compacted tables from round 1 on; none with S < 2: nothing sharded is ever stored]
-//   [replicated: m tables of 2^(c+g+1) -- the hand-over's global tables, and what the replicated rounds fold in place]
-//   [gather: the rank's m x 2^(c+1) hand-over block, then the G gathered ones] [exchange: XCHG_FES, then G x XCHG_FES]
-//   [round scratch] [split eq tables of n - 1 coordinates]
-struct Layout {
-    unsigned g = 0, S = 0;
-    size_t local_half = 0, handover = 0;  // the strides of the compact and the replicated tables
-    size_t compact = 0, replicated = 0, gather_send = 0, gather_recv = 0, xchg_send = 0, xchg_recv = 0, scratch = 0, eq = 0, total = 0;
-};
-inline Layout layout(unsigned n, unsigned m, unsigned g) {
-    Layout L;
-    L.g = g, L.S = sharded_rounds(n, g);
-    L.local_half = L.S >= 2 ? ((size_t)1 << (n - 1)) >> g : 0;
-    L.handover = handover_len(g);
-    const size_t block = (size_t)m << (C + 1), G = (size_t)1 << g;
-    L.replicated = L.compact + m * L.local_half;
-    L.gather_send = L.replicated + m * L.handover;
-    L.gather_recv = L.gather_send + block;
-    L.xchg_send = L.gather_recv + G * block;
-    L.xchg_recv = L.xchg_send + XCHG_FES;
-    L.scratch = L.xchg_recv + G * XCHG_FES;
-    L.eq = L.scratch + pks::ROUND_SCRATCH_FES;
-    L.total = L.eq + pks::eq_split(n - 1).fes();
-    return L;
-}
-
-}  // namespace pkss
-
+// one statement's prover on a context: lone (pks_prover_create: world 1) or one rank of a device set (pkss_prover_create)
 struct pks_prover {
     pk_ctx* ctx = nullptr;
     pks_statement st{};
     std::string pattern, err;
     unsigned D = 0;
-    uint64_t* arena = nullptr;  // lone: [m tables of 2^(n-1)] [round scratch] [split eq tables]; sharded: pkss::Layout
-    size_t half = 0;            // 2^(n-1)
-    pks::EqSplit split;
-    std::vector<pk::fe> eq_host;
-    // a prover made by pkss_prover_create
-    bool sharded = false;
     unsigned rank = 0, world = 1;
     pkss::Layout lay;
+    uint64_t* arena = nullptr;
+    pks::EqSplit split;
+    std::vector<pk::fe> eq_host;
     std::vector<pkss_round_profile> profile;  // of the last proof (pkss_last_profile)
     double handover_seconds = 0, total_seconds = 0;
+
+    pks_prover() = default;
+    pks_prover(const pks_prover&) = delete;
+    pks_prover& operator=(const pks_prover&) = delete;
+    // gives the arena back, so a creation that stops half way leaks nothing
+    int give_back() {
+        const int rc = arena ? pk_free(ctx, arena) : PK_OK;
+        arena = nullptr;
+        return rc;
+    }
+    ~pks_prover() { (void)give_back(); }
 };
+
+namespace pks {
+
+// prover.cpp, for the two sets of entry points.  A prover on rank `rank` of `world` with its arena: of `stmt`, or, where a rank of a
+// device set has refused its statement (stmt null), of the smallest one, for the refusal to travel on.  The reason of a failure goes
+// to g_error
+int make_prover(pk_ctx* ctx, const pks_statement* stmt, unsigned rank, unsigned world, std::unique_ptr<pks_prover>& out);
+// One all-gather of 32 * (k + 1) bytes per rank: k elements (k < XCHG_FES) and the status of the rank's local work so far.
+// all: world x k.  Returns the first non-zero status of the set in rank order, else PK_OK.  A lone prover's is its own: no device
+// memory is touched, nothing is collective
+int exchange(pks_prover* p, int status, const fe* mine, unsigned k, std::vector<fe>& all);
+// the first rank whose element differs from rank 0's, or 0
+unsigned first_differing(const std::vector<fe>& all);
+// pks_prove and pkss_prove
+int prove(pks_prover* p, const uint64_t* const* d_tables, const uint64_t* tau_or_null, const uint64_t* bind, uint8_t* proof_out, size_t cap, size_t* len,
+          uint64_t* point_out, uint64_t* finals_out);
+// pks_round and pkss_round_shard after their own refusals: a round of `pairs` pairs by itself, or with `shard` that rank's `mine` of them
+int round_alone(pk_ctx* ctx, const pks_statement& st, const uint64_t* const* d_tables, uint64_t* const* d_out_tables, size_t pairs, size_t mine,
+                const uint64_t* tau_rest_or_null, const uint64_t* fold_or_null, unsigned grid, const ShardSlice* shard, uint64_t* out);
+
+}  // namespace pks

@@ -16,10 +16,11 @@
 //
 // Specialised at compile time on what changes register pressure: D, m and whether the lane folds.  The term structure is uniform data.
 //
-// Device sets (shard.hpp): round_kernel_sharded is one rank's slice of a round, a sibling kernel so that the lone instantiations stay
-// what they were.  Its lane index y runs over the rank's compacted pairs.  It differs from the lone kernel in two places: the input is
-// either the caller's full tables, read at the rank's own indices expand(y) (rounds 0 and 1), or the rank's compacted arena, read at y
-// (from round 2 on); and the eq weight is that of the global pair index expand(y).  Output and partials are the lone kernel's.
+// Device sets (shard.hpp): round_kernel_sharded is one rank's slice of a round, a sibling entry point of the same body (round_body)
+// so that the lone instantiations' arguments and registers stay what they were.  Its lane index y runs over the rank's compacted
+// pairs, and a slice policy states the two places where it differs: the input is either the caller's full tables, read at the rank's
+// own indices expand(y) (rounds 0 and 1), or the rank's compacted arena, read at y (from round 2 on); and the eq weight is that of the
+// global pair index expand(y).  Output and partials are the lone kernel's.
 #include <hip/hip_runtime.h>
 
 #include "../reduce.hpp"
@@ -40,28 +41,54 @@ struct DevTables {
     fe* out[PKS_MAX_TABLES];
 };
 
+// Where a slice's pairs lie.  The lane index y runs over the slice's `pairs`; a policy gives the global pair index x (the eq weight's),
+// the index the input tables are read at, the step between their halves (quarters, with a fold) and the index the output tables are
+// stored at, their halves `pairs` apart.  The lone round is the identity
+struct WholeRound {
+    size_t pairs;
+    __device__ size_t global(size_t y) const { return y; }
+    __device__ size_t load(size_t y, size_t) const { return y; }
+    __device__ size_t step() const { return pairs; }
+    __device__ size_t store(size_t y) const { return y; }
+};
+// One rank's slice: `pairs` are the rank's own (the round's pairs / G), g and rank the ownership rule's.  in_global: the input tables
+// are full tables at the round's global length, read at expand(y) with the halves G * pairs apart; otherwise compacted ones, read at y.
+// The output tables are compacted either way
+struct RankSlice {
+    size_t pairs;
+    unsigned g, rank;
+    bool in_global;
+    __device__ size_t global(size_t y) const { return pkss::expand(y, g, rank); }
+    __device__ size_t load(size_t y, size_t x) const { return in_global ? x : y; }
+    __device__ size_t step() const { return in_global ? pairs << g : pairs; }
+    __device__ size_t store(size_t y) const { return y; }
+};
+
 // partial[k * gridDim.x + blockIdx.x] = this workgroup's share of sum k = h(k), k <= D
-template <int D, int M, bool FOLD>
-__global__ __launch_bounds__(THREADS) void round_kernel(DevTables tb, Terms tm, const fe* __restrict__ eq_hi, const fe* __restrict__ eq_lo, unsigned lo_bits,
-                                                        size_t pairs, fe alpha, fe* __restrict__ partial) {
+template <int D, int M, bool FOLD, class Slice>
+__device__ __forceinline__ void round_body(const DevTables& tb, const Terms& tm, const fe* __restrict__ eq_hi, const fe* __restrict__ eq_lo, unsigned lo_bits,
+                                           const Slice sl, const fe& alpha, fe* __restrict__ partial) {
     fe acc[D + 1];
 #pragma unroll
     for (int k = 0; k <= D; k++) acc[k] = fe_zero();
     const bool weighted = eq_hi != nullptr;
     const size_t lo_mask = ((size_t)1 << lo_bits) - 1;
     const size_t stride = (size_t)gridDim.x * THREADS;
-    for (size_t x = (size_t)blockIdx.x * THREADS + threadIdx.x; x < pairs; x += stride) {
+    const size_t step = sl.step();
+    for (size_t y = (size_t)blockIdx.x * THREADS + threadIdx.x; y < sl.pairs; y += stride) {
+        const size_t x = sl.global(y);
+        const size_t at = sl.load(y, x), to = sl.store(y);
         fe lo[M], hi[M];
 #pragma unroll
         for (int j = 0; j < M; j++) {
-            const fe* f = tb.in[j];
-            fe x0 = fe_load(f + x), x1 = fe_load(f + x + pairs);
+            const fe* f = tb.in[j] + at;
+            fe x0 = fe_load(f), x1 = fe_load(f + step);
             if (FOLD) {
-                const fe x2 = fe_load(f + x + 2 * pairs), x3 = fe_load(f + x + 3 * pairs);
+                const fe x2 = fe_load(f + 2 * step), x3 = fe_load(f + 3 * step);
                 x0 = fold_pair(x0, x2, alpha);
                 x1 = fold_pair(x1, x3, alpha);
-                fe_store(tb.out[j] + x, x0);
-                fe_store(tb.out[j] + x + pairs, x1);
+                fe_store(tb.out[j] + to, x0);
+                fe_store(tb.out[j] + to + sl.pairs, x1);
             }
             lo[j] = x0;
             hi[j] = x1;
@@ -74,44 +101,17 @@ __global__ __launch_bounds__(THREADS) void round_kernel(DevTables tb, Terms tm, 
     if (threadIdx.x <= D) fe_store(partial + (size_t)threadIdx.x * gridDim.x + blockIdx.x, mine);
 }
 
-// One rank's slice: `pairs` are the rank's own (the round's pairs / G), g and rank the ownership rule's.  in_global: the input tables
-// are full tables at the round's global length, read at expand(y) with the halves (quarters, with a fold) in_step = G * pairs apart;
-// otherwise compacted ones, read at y, in_step = pairs.  The output tables are compacted either way
+template <int D, int M, bool FOLD>
+__global__ __launch_bounds__(THREADS) void round_kernel(DevTables tb, Terms tm, const fe* __restrict__ eq_hi, const fe* __restrict__ eq_lo, unsigned lo_bits,
+                                                        size_t pairs, fe alpha, fe* __restrict__ partial) {
+    round_body<D, M, FOLD>(tb, tm, eq_hi, eq_lo, lo_bits, WholeRound{pairs}, alpha, partial);
+}
+
 template <int D, int M, bool FOLD>
 __global__ __launch_bounds__(THREADS) void round_kernel_sharded(DevTables tb, Terms tm, const fe* __restrict__ eq_hi, const fe* __restrict__ eq_lo,
                                                                 unsigned lo_bits, size_t pairs, unsigned g, unsigned rank, bool in_global, fe alpha,
                                                                 fe* __restrict__ partial) {
-    fe acc[D + 1];
-#pragma unroll
-    for (int k = 0; k <= D; k++) acc[k] = fe_zero();
-    const bool weighted = eq_hi != nullptr;
-    const size_t lo_mask = ((size_t)1 << lo_bits) - 1;
-    const size_t stride = (size_t)gridDim.x * THREADS;
-    const size_t in_step = in_global ? pairs << g : pairs;
-    for (size_t y = (size_t)blockIdx.x * THREADS + threadIdx.x; y < pairs; y += stride) {
-        const size_t x = pkss::expand(y, g, rank);  // the global pair index
-        const size_t at = in_global ? x : y;
-        fe lo[M], hi[M];
-#pragma unroll
-        for (int j = 0; j < M; j++) {
-            const fe* f = tb.in[j] + at;
-            fe x0 = fe_load(f), x1 = fe_load(f + in_step);
-            if (FOLD) {
-                const fe x2 = fe_load(f + 2 * in_step), x3 = fe_load(f + 3 * in_step);
-                x0 = fold_pair(x0, x2, alpha);
-                x1 = fold_pair(x1, x3, alpha);
-                fe_store(tb.out[j] + y, x0);
-                fe_store(tb.out[j] + y + pairs, x1);
-            }
-            lo[j] = x0;
-            hi[j] = x1;
-        }
-        fe w = fe_zero();
-        if (weighted) w = fe_mulx(fe_load(eq_hi + (x >> lo_bits)), fe_load(eq_lo + (x & lo_mask)));
-        lane_accumulate<D, M>(lo, hi, tm, weighted, w, acc);
-    }
-    const fe mine = block_reduce_fe<D + 1>(acc);  // thread k holds sum k
-    if (threadIdx.x <= D) fe_store(partial + (size_t)threadIdx.x * gridDim.x + blockIdx.x, mine);
+    round_body<D, M, FOLD>(tb, tm, eq_hi, eq_lo, lo_bits, RankSlice{pairs, g, rank, in_global}, alpha, partial);
 }
 
 // The hand-over: gathered = G blocks of m tables of 2^(c+1) elements, block r rank r's lower-half and upper-half chunks; out = the m
@@ -134,22 +134,14 @@ __global__ __launch_bounds__(THREADS) void finish_kernel(const fe* __restrict__ 
     if (threadIdx.x == 0) fe_store(out + blockIdx.x, acc);
 }
 
-template <int D, int M>
-void launch_dm(bool fold, unsigned grid, hipStream_t stream, const DevTables& tb, const Terms& tm, const fe* eq_hi, const fe* eq_lo, unsigned lo_bits,
-               size_t pairs, const fe& alpha, fe* partial) {
-    if (fold)
-        round_kernel<D, M, true><<<grid, THREADS, 0, stream>>>(tb, tm, eq_hi, eq_lo, lo_bits, pairs, alpha, partial);
+// `sh` null: the lone round
+template <int D, int M, bool FOLD>
+void launch_dmf(unsigned grid, hipStream_t stream, const DevTables& tb, const Terms& tm, const fe* eq_hi, const fe* eq_lo, unsigned lo_bits, size_t pairs,
+                const ShardSlice* sh, const fe& alpha, fe* partial) {
+    if (sh)
+        round_kernel_sharded<D, M, FOLD><<<grid, THREADS, 0, stream>>>(tb, tm, eq_hi, eq_lo, lo_bits, pairs, sh->g, sh->rank, sh->in_global, alpha, partial);
     else
-        round_kernel<D, M, false><<<grid, THREADS, 0, stream>>>(tb, tm, eq_hi, eq_lo, lo_bits, pairs, alpha, partial);
-}
-
-template <int D, int M>
-void launch_sharded_dm(bool fold, unsigned grid, hipStream_t stream, const DevTables& tb, const Terms& tm, const fe* eq_hi, const fe* eq_lo, unsigned lo_bits,
-                       size_t pairs, const ShardSlice& sh, const fe& alpha, fe* partial) {
-    if (fold)
-        round_kernel_sharded<D, M, true><<<grid, THREADS, 0, stream>>>(tb, tm, eq_hi, eq_lo, lo_bits, pairs, sh.g, sh.rank, sh.in_global, alpha, partial);
-    else
-        round_kernel_sharded<D, M, false><<<grid, THREADS, 0, stream>>>(tb, tm, eq_hi, eq_lo, lo_bits, pairs, sh.g, sh.rank, sh.in_global, alpha, partial);
+        round_kernel<D, M, FOLD><<<grid, THREADS, 0, stream>>>(tb, tm, eq_hi, eq_lo, lo_bits, pairs, alpha, partial);
 }
 
 }  // namespace
@@ -183,12 +175,12 @@ int launch(hipStream_t stream, const pks_statement& st, const RoundTables& rt, s
     const fe *hi = (const fe*)d_eq_hi, *lo = (const fe*)d_eq_lo;
     const unsigned D = degree(st);
     const bool fold = fold_or_null != nullptr;
-#define PKS_CASE(DEG, TABLES)                                                                                      \
-    if (D == DEG && st.m == TABLES) {                                                                              \
-        if (shard)                                                                                                 \
-            launch_sharded_dm<DEG, TABLES>(fold, grid, stream, tb, tm, hi, lo, lo_bits, pairs, *shard, alpha, partial); \
-        else                                                                                                       \
-            launch_dm<DEG, TABLES>(fold, grid, stream, tb, tm, hi, lo, lo_bits, pairs, alpha, partial);             \
+#define PKS_CASE(DEG, TABLES)                                                                                    \
+    if (D == DEG && st.m == TABLES) {                                                                            \
+        if (fold)                                                                                                \
+            launch_dmf<DEG, TABLES, true>(grid, stream, tb, tm, hi, lo, lo_bits, pairs, shard, alpha, partial);  \
+        else                                                                                                     \
+            launch_dmf<DEG, TABLES, false>(grid, stream, tb, tm, hi, lo, lo_bits, pairs, shard, alpha, partial); \
     } else
     PKS_CASE(1, 1) PKS_CASE(1, 2) PKS_CASE(1, 3) PKS_CASE(1, 4) PKS_CASE(2, 2) PKS_CASE(2, 3) PKS_CASE(2, 4) PKS_CASE(3, 3) PKS_CASE(3, 4)
     return PK_ERR_BAD_ARG;  // D <= m: a term's tables are distinct

@@ -1,6 +1,6 @@
 // shard_host.cpp -- the host-only part of the sharded prover's C ABI (include/provekit_sumcheck_sharded.h): pkss_plan, what a
 // sharded proof of a statement takes on each of `world` ranks.  No device, no product call: the sanitizer build links it as it is.
-#include "prover.hpp"
+#include "layout.hpp"
 
 extern "C" {
 

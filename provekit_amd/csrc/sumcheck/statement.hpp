@@ -4,17 +4,14 @@
 #include <string>
 
 #include "../../../include/provekit_sumcheck.h"
-#include "../verify/core.hpp"
+#include "../argument.hpp"
 
 namespace pks {
 
 using pk::fe;
 
 extern thread_local std::string g_error;  // pks_create_error
-inline int refuse(const std::string& why) {
-    g_error = why;
-    return PK_ERR_BAD_ARG;
-}
+inline int refuse(const std::string& why) { return pk::refuse(g_error, why); }
 
 inline unsigned popcount4(unsigned mask) { return (mask & 1) + ((mask >> 1) & 1) + ((mask >> 2) & 1) + ((mask >> 3) & 1); }
 
@@ -54,11 +51,7 @@ inline std::string io_pattern(const pks_statement& s) {
     std::string d = "provekit-hip/sumcheck/v1/n" + std::to_string(s.n) + "/m" + std::to_string(s.m) + "/T" + std::to_string(s.T) + "/tau" +
                     std::to_string(s.has_tau) + "/masks";
     for (unsigned t = 0; t < s.T; t++) d += (t ? "." : "") + std::to_string(s.masks[t]);
-    auto A = [&](size_t n, const char* label) {  // whir_config.hip's zero-count rule: no operation
-        if (!n) return;
-        d.push_back('\0');
-        d += "A" + std::to_string(n) + label;
-    };
+    auto A = [&](size_t n, const char* label) { pk::pattern_op(d, 'A', n, label); };
     A(s.n_bind, "bind");
     if (s.has_tau) A(s.n, "tau");
     A(s.T, "coefficients");

@@ -19,18 +19,7 @@ using pk::fe;
 
 // the statement's public part as the transcript sees it: bind, tau, the coefficients, canonical.  false: an element is not below p
 bool public_prefix(const pks_statement& st, const uint64_t* tau, const uint64_t* bind, std::vector<uint8_t>& out, std::string& why) {
-    auto put = [&](const uint64_t* v, size_t n, const char* what) {
-        for (size_t i = 0; i < n; i++) {
-            const fe x = pk::h_load(v + 4 * i);
-            if (!pk::is_canonical(x)) {
-                why = std::string(what) + " element " + std::to_string(i) + " is not below p";
-                return false;
-            }
-            const fe c = pk::h_to_canon(x);
-            out.insert(out.end(), (const uint8_t*)c.v, (const uint8_t*)c.v + 32);
-        }
-        return true;
-    };
+    auto put = [&](const uint64_t* v, size_t n, const char* what) { return pk::elements_below_p(v, n, what, why) && (pk::put_canonical(out, v, n), true); };
     return put(bind, st.n_bind, "bind") && put(tau, st.has_tau ? st.n : 0, "tau") && put(&st.coeffs[0][0], st.T, "coefficient");
 }
 
@@ -52,10 +41,7 @@ int pks_io_pattern(const pks_statement* stmt, uint8_t* buf, size_t cap, size_t* 
     if (!len) return pks::refuse("null pointer");
     if (!pks::statement_ok(stmt, why)) return pks::refuse(why);
     try {
-        const std::string d = pks::io_pattern(*stmt);
-        *len = d.size();
-        if (buf && cap >= d.size()) memcpy(buf, d.data(), d.size());
-        return PK_OK;
+        return pk::pattern_out(pks::io_pattern(*stmt), buf, cap, len);
     } catch (...) {
         return PK_ERR_OOM;
     }
@@ -80,14 +66,7 @@ int pks_verify(const pks_statement* stmt, const uint8_t* io_pattern_or_null, siz
     if (s.n_bind && !bind) return pks::refuse("the statement binds elements: pass them");
     try {
         pkv::Statement st;
-        if (io_pattern_or_null && io_pattern_len)
-            st.pattern.assign((const char*)io_pattern_or_null, io_pattern_len);
-        else
-            st.pattern = pks::io_pattern(s);
-        if (!pk::io_pattern_parse(st.pattern, st.ops, why)) {
-            pks::g_error = why;
-            return PK_ERR_IO_PATTERN;
-        }
+        if (int rc = pk::parse_pattern(st, io_pattern_or_null, io_pattern_len, pks::io_pattern(s), pks::g_error)) return rc;
         // both sides absorb the public part first: it goes in front of the proof, and the transcript reads one string
         std::vector<uint8_t> bytes;
         bytes.reserve(32 * pks::public_elems(s) + len);

@@ -179,11 +179,13 @@ class Prover:
     """one statement's prover on a context: owns one device arena sized at creation; prove() allocates no device memory and never
     writes the caller's tables"""
 
+    _create = lib.pks_prover_create  # prodcheck_sharded.Prover: the device set's
+
     def __init__(self, ctx: Context, stmt: Statement):
         self.ctx, self.stmt = ctx, stmt
         s = stmt.struct()
         h = vp()
-        rc = lib.pks_prover_create(ctx.handle, C.addressof(s), C.byref(h))
+        rc = self._create(ctx.handle, C.addressof(s), C.byref(h))
         if rc:
             _refused(rc)
         self.handle = h
@@ -206,6 +208,10 @@ class Prover:
     def prove(self, d_tables, tau=None, bind=None, capacity: int | None = None) -> Proof:
         """d_tables: m DeviceBuffers (or device addresses) of 2^n Montgomery elements.  capacity: the proof buffer's size, the proof's
         own by default"""
+        return self._prove_with(lib.pks_prove, d_tables, tau, bind, capacity)
+
+    def _prove_with(self, fn, d_tables, tau, bind, capacity) -> Proof:
+        """pks_prove, or pkss_prove on a prover of a device set: each class's prove() names its own call"""
         st = self.stmt
         if len(d_tables) != st.m:
             raise ValueError(f"{st.m} tables expected")
@@ -216,24 +222,28 @@ class Prover:
         n = sz()
         point = np.zeros((st.n, 4), dtype=np.uint64)
         finals = np.zeros((st.m, 4), dtype=np.uint64)
-        rc = lib.pks_prove(self.handle, C.cast(_ptr_array(d_tables), vp), _ptr(tau_a), _ptr(bind_a), C.cast(buf, vp), cap, C.byref(n), point.ctypes.data,
-                           finals.ctypes.data)
+        rc = fn(self.handle, C.cast(_ptr_array(d_tables), vp), _ptr(tau_a), _ptr(bind_a), C.cast(buf, vp), cap, C.byref(n), point.ctypes.data, finals.ctypes.data)
         self.last_len = n.value
         if rc:
             raise ProveKitHipError(rc, self.last_error())
         return Proof(bytes(buf[: n.value]), point, finals)
 
 
-def round(ctx: Context, stmt: Statement, d_tables, length: int, tau_rest=None, fold=None, d_out_tables=None, grid: int = 0) -> np.ndarray:
-    """[D + 1, 4] Montgomery: h(0) .. h(D) of ONE round on tables of current length `length`, folded first by `fold` into d_out_tables if
-    given (pks_round).  grid = 0: the library's rule; the bits do not depend on it"""
+def _round(fn, ctx: Context, stmt: Statement, d_tables, length: int, tau_rest, fold, d_out_tables, *slice_and_grid) -> np.ndarray:
+    """pks_round, or pkss_round_shard with (world, rank) in front of the grid"""
     s = stmt.struct()
     out = np.zeros((stmt.degree + 1, 4), dtype=np.uint64)
     tau_a = np.ascontiguousarray(tau_rest, dtype=np.uint64).reshape(-1, 4) if tau_rest is not None else None
     fold_a = _fe(fold, 1, "fold") if fold is not None else None
     outs = C.cast(_ptr_array(d_out_tables), vp) if d_out_tables is not None else None
-    rc = lib.pks_round(ctx.handle, C.addressof(s), C.cast(_ptr_array(d_tables), vp), length, tau_a.ctypes.data if tau_a is not None else None,
-                       _ptr(fold_a), outs, grid, out.ctypes.data)
+    rc = fn(ctx.handle, C.addressof(s), C.cast(_ptr_array(d_tables), vp), length, tau_a.ctypes.data if tau_a is not None else None, _ptr(fold_a), outs,
+            *slice_and_grid, out.ctypes.data)
     if rc:
         _refused(rc)
     return out
+
+
+def round(ctx: Context, stmt: Statement, d_tables, length: int, tau_rest=None, fold=None, d_out_tables=None, grid: int = 0) -> np.ndarray:
+    """[D + 1, 4] Montgomery: h(0) .. h(D) of ONE round on tables of current length `length`, folded first by `fold` into d_out_tables if
+    given (pks_round).  grid = 0: the library's rule; the bits do not depend on it"""
+    return _round(lib.pks_round, ctx, stmt, d_tables, length, tau_rest, fold, d_out_tables, grid)

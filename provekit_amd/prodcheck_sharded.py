@@ -14,7 +14,7 @@ import numpy as np
 
 from . import prodcheck as _lone
 from ._lib import ProveKitHipError, sz, vp
-from .prodcheck import Proof, Statement, _fe, _ptr, _ptr_array
+from .prodcheck import Proof, Statement
 from .runtime import Context
 
 CHUNK_LOG2, MAX_WORLD_LOG2 = 8, 4
@@ -74,35 +74,15 @@ class Prover(_lone.Prover):
     """one statement's sharded prover on ONE context of a device set.  Creation and prove() are collective: every rank makes the same
     calls.  prove() returns the lone prover's Proof on every rank, allocates no device memory and never writes the caller's tables"""
 
+    _create = lib.pkss_prover_create
+
     def __init__(self, ctx: Context, stmt: Statement):
-        self.ctx, self.stmt = ctx, stmt
-        s = stmt.struct()
-        h = vp()
-        rc = lib.pkss_prover_create(ctx.handle, C.addressof(s), C.byref(h))
-        if rc:
-            _lone._refused(rc)
-        self.handle = h
-        self.proof_bytes = _lone.proof_bytes(stmt)
+        super().__init__(ctx, stmt)
         self.rank, self.world, _ = ctx.comm_info()
         self.plan = plan(stmt, self.world)
 
     def prove(self, d_tables, tau=None, bind=None, capacity: int | None = None) -> Proof:
-        st = self.stmt
-        if len(d_tables) != st.m:
-            raise ValueError(f"{st.m} tables expected")
-        tau_a = _fe(tau, st.n if st.has_tau else 0, "tau") if (tau is not None or st.has_tau) else None
-        bind_a = _fe(bind, st.n_bind, "bind") if (bind is not None or st.n_bind) else None
-        cap = self.proof_bytes if capacity is None else capacity
-        buf = (C.c_uint8 * max(cap, 1))()
-        n = sz()
-        point = np.zeros((st.n, 4), dtype=np.uint64)
-        finals = np.zeros((st.m, 4), dtype=np.uint64)
-        rc = lib.pkss_prove(self.handle, C.cast(_ptr_array(d_tables), vp), _ptr(tau_a), _ptr(bind_a), C.cast(buf, vp), cap, C.byref(n), point.ctypes.data,
-                            finals.ctypes.data)
-        self.last_len = n.value
-        if rc:
-            raise ProveKitHipError(rc, self.last_error())
-        return Proof(bytes(buf[: n.value]), point, finals)
+        return self._prove_with(lib.pkss_prove, d_tables, tau, bind, capacity)
 
     def last_profile(self) -> dict:
         """this rank's last proof, round by round (pkss_last_profile): {"rounds": [{"sharded", "pairs", "round_s", "exchange_s"}],
@@ -120,13 +100,4 @@ def round_shard(ctx: Context, stmt: Statement, d_tables, length: int, world: int
                 grid: int = 0) -> np.ndarray:
     """[D + 1, 4] Montgomery: rank `rank` of `world`'s partial sums of ONE sharded round on FULL tables of current length `length`,
     folded first by `fold` -- the rank's part, compacted -- into d_out_local if given (pkss_round_shard; a lone context)"""
-    s = stmt.struct()
-    out = np.zeros((stmt.degree + 1, 4), dtype=np.uint64)
-    tau_a = np.ascontiguousarray(tau_rest, dtype=np.uint64).reshape(-1, 4) if tau_rest is not None else None
-    fold_a = _fe(fold, 1, "fold") if fold is not None else None
-    outs = C.cast(_ptr_array(d_out_local), vp) if d_out_local is not None else None
-    rc = lib.pkss_round_shard(ctx.handle, C.addressof(s), C.cast(_ptr_array(d_tables), vp), length, tau_a.ctypes.data if tau_a is not None else None,
-                              _ptr(fold_a), outs, world, rank, grid, out.ctypes.data)
-    if rc:
-        _lone._refused(rc)
-    return out
+    return _lone._round(lib.pkss_round_shard, ctx, stmt, d_tables, length, tau_rest, fold, d_out_local, world, rank, grid)

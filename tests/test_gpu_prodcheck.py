@@ -237,6 +237,35 @@ def test_size_2_to_the_20_against_the_products_own_sums(ctx):
         b.free()
 
 
+def test_a_creation_whose_arena_the_device_cannot_hold_leaves_nothing_behind():
+    """pks_prover_create of a sound statement whose arena (n = 28, m = 4: 16 GiB of folded copies) does not fit the device: it fails
+    with its reason in pks_create_error, and the next creation on the same context succeeds and proves the reference's bytes.  Where
+    the device has room for 16 GiB the test holds all but 8 GiB of the free memory in one allocation while the creation is tried
+    (on an MI355X: 7 s to take 279 GiB and 2.4 s to give them back, of about 9.5 s)"""
+    import ctypes
+
+    import torch
+
+    torch.cuda.is_available()
+    import provekit_amd
+    from provekit_amd import prodcheck
+
+    c = provekit_amd.Context(0)
+    try:
+        free, _ = torch.cuda.mem_get_info(0)
+        held = torch.empty(free - (8 << 30), dtype=torch.uint8, device="cuda:0") if free > 4 * 32 << 27 else None
+        s, h = K.Shape("four", 28, n_bind=1).statement().struct(), ctypes.c_void_p()
+        rc = prodcheck.lib.pks_prover_create(c.handle, ctypes.addressof(s), ctypes.byref(h))
+        del held
+        torch.cuda.empty_cache()
+        assert rc != 0 and not h.value and prodcheck.lib.pks_create_error() != b""
+        shape, tables, tau, bind, want, point, finals, _ = reference("four", 3)
+        got = run(c, shape, tables, tau, bind)
+        assert got.bytes == want and K.unmont(got.point) == point and K.unmont(got.finals) == finals
+    finally:
+        c.close()
+
+
 def test_the_cpp_demo_commits_proves_opens_and_sees_the_tamperings_rejected():
     import subprocess
 

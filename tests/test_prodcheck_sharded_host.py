@@ -126,3 +126,23 @@ def test_the_rule_and_the_plan_under_the_sanitizers():
     for n, G, reason in ((0, 2, "n must be"), (29, 4, "n must be"), (12, 3, "power of two"), (12, 1, "at least 2"), (12, 32, "at most 16")):
         p = subprocess.run([ASAN, "shard", str(n), str(G)], capture_output=True, text=True, env=env, timeout=300)
         assert p.returncode == 0 and p.stdout.startswith("-1 REFUSED") and reason in p.stdout, (n, G, p.stdout, p.stderr[-2000:])
+
+
+def test_the_lone_prover_is_a_device_set_of_one_whose_arena_is_the_lone_rule():
+    """The layout at g = 0 -- what pks_prover_create allocates, and what pkl_/pkg_prover_arena_bytes add up -- against round.hpp's rule,
+    restated here: m folded copies of half length, one round's scratch (4 x 1024 partials and 8 results) and the split eq weights of
+    R = n - 1 coordinates, 2^(H+1) + 2^(L+1) - 2 elements with L = R // 2 trailing and H = R - L leading ones.  The sanitizer build
+    prints it as the shard mode's last column"""
+    assert os.path.exists(ASAN), "provekit_amd/lib/pks_verify_asan is missing: make -C provekit_amd/csrc asan"
+    env = {k: v for k, v in os.environ.items() if k != "ASAN_OPTIONS"}
+    for n in (1, 2, 9, 28):
+        p = subprocess.run([ASAN, "shard", str(n), "2", "lone"], capture_output=True, text=True, env=env, timeout=300)
+        assert p.returncode == 0, (n, p.stdout, p.stderr[-3000:])
+        lines = [line.split() for line in p.stdout.splitlines()]
+        assert [line[:2] for line in lines] == [[str(n), str(m)] for m in (1, 2, 3, 4)]
+        R_, L = n - 1, (n - 1) // 2
+        H = R_ - L
+        for m, line in zip((1, 2, 3, 4), lines):
+            lone_arena_fes = m * (1 << (n - 1)) + (4 * 1024 + 8) + (2 << H) + (2 << L) - 2
+            assert int(line[-1]) == 32 * lone_arena_fes, (n, m)
+            assert line[:-1] == [str(v) for v in (n, m) + R.plan(n, m, 2)]  # the other columns are the plan's, as without `lone`
