@@ -393,6 +393,8 @@ PK_HD fe fe_mul29(const fe& a, const fe& b) {
 }
 
 PK_HD fe fe_mulx(const fe& a, const fe& b) { return fe_mul29(a, b); }
+// binding a variable to r: the pair (lo, hi) = (value at 0, value at 1) becomes lo + r (hi - lo)  (sumcheck.rs:95-96)
+PK_HD fe fe_fold(const fe& lo, const fe& hi, const fe& r) { return fe_add(lo, fe_mulx(r, fe_sub(hi, lo))); }
 // a < p -> a^2 * 2^-256 mod p
 PK_HD fe fe_sqrx(const fe& a) {
     u64 acc[17];

@@ -93,19 +93,22 @@ int to_coeffs_generated(pk_ctx* ctx, unsigned m, const uint64_t* d_wit, size_t n
 int fold_pairs2(pk_ctx* ctx, const uint64_t* d_v0, uint64_t* d_out0, const uint64_t* d_v1, uint64_t* d_out1, size_t len, const uint64_t* r,
                 unsigned gate_seq = 0);
 // launch only: round results go to the pinned page under sequence number *red_seq_out.  gate_seq != 0 (latency mode, folding rounds
-// only): the folding challenge is not known yet -- the kernel waits for sumcheck_gate_publish(ctx, gate_seq, challenge)
-int sumcheck_cubic_launch(pk_ctx* ctx, uint64_t* d_a, uint64_t* d_b, uint64_t* d_c, uint64_t* d_eq, size_t len, const uint64_t* fold_or_null,
-                          unsigned gate_seq, unsigned* red_seq_out);
+// only): the folding challenge is not known yet -- the kernel waits for sumcheck_gate_publish(ctx, gate_seq, challenge).
+// The weight of the cubic round's pairs is d_weight, one of two kinds:
+//   EqArray: the eq table, folded in place with a, b, c; the sums are the round's f(0), f(-1), f_inf;
+//   Level:   the level E_i of the round the kernel evaluates (eq_suffix_tables below; npairs entries, read only); the sums are Q(0), Q(-1), Q_inf.
+enum class CubicWeight { EqArray, Level };
+int sumcheck_cubic_launch(pk_ctx* ctx, uint64_t* d_a, uint64_t* d_b, uint64_t* d_c, CubicWeight kind, uint64_t* d_weight, size_t len,
+                          const uint64_t* fold_or_null, unsigned gate_seq, unsigned* red_seq_out);
 // nsums = 3: the sums are h(0), h(1), h(2); nsums = 2: h(0), h(2) -- the caller holds the round's claim h(0) + h(1) (sumcheck_quadratic_from_claim)
 int sumcheck_quadratic_launch(pk_ctx* ctx, const uint64_t* d_f, const uint64_t* d_w, size_t len, const uint64_t* fold_or_null, unsigned gate_seq,
                               uint64_t* d_f_out, uint64_t* d_w_out, int nsums, unsigned* red_seq_out);
 void sumcheck_quadratic_from_claim(const uint64_t claim[4], uint64_t out[12]);  // out = h(0), h(2)  ->  h(0), claim - h(0), h(2)
 // The cubic round without the eq array.  eq_suffix_tables: the levels E_i = eq(r[i+1 .. n), .), i = 0 .. n-1, back to back in 2^n elements
-// (E_i at 2^n - 2^(n-i)).  The launch takes the level of the round it evaluates and returns Q(0), Q(-1), Q_inf; sumcheck_spliteq_correct turns
-// them into the round's f(0), f(-1), f_inf with P = prod_{k<i} eq(r_k, alpha_k), which sumcheck_spliteq_advance carries from round to round.
+// (E_i at 2^n - 2^(n-i)).  sumcheck_cubic_launch(CubicWeight::Level) takes the level of the round it evaluates and returns Q(0), Q(-1), Q_inf;
+// sumcheck_spliteq_correct turns them into the round's f(0), f(-1), f_inf with P = prod_{k<i} eq(r_k, alpha_k), which sumcheck_spliteq_advance
+// carries from round to round.
 int eq_suffix_tables(pk_ctx* ctx, const uint64_t* r, unsigned n, uint64_t* d_out);
-int sumcheck_cubic_spliteq_launch(pk_ctx* ctx, uint64_t* d_a, uint64_t* d_b, uint64_t* d_c, const uint64_t* d_level, size_t len,
-                                  const uint64_t* fold_or_null, unsigned gate_seq, unsigned* red_seq_out);
 void sumcheck_spliteq_correct(const uint64_t P[4], const uint64_t r_i[4], uint64_t out[12]);
 void sumcheck_spliteq_advance(uint64_t P[4], const uint64_t r_i[4], const uint64_t alpha_i[4]);
 // the host's side of a gated launch and the wait for a launch's results without draining the stream (latency mode); without a gate: after a stream sync

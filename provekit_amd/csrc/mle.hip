@@ -42,6 +42,23 @@ __device__ __forceinline__ void lds_put(uint4* lo, uint4* hi, int i, const fe& x
     hi[i] = make_uint4(x.v[4], x.v[5], x.v[6], x.v[7]);
 }
 
+// per-limb select: no divergent branch where the lanes of a wavefront differ in `pick`
+__device__ __forceinline__ fe fe_select(bool pick, const fe& x, const fe& y) {
+    fe r;
+#pragma unroll
+    for (int i = 0; i < 8; i++) r.v[i] = pick ? x.v[i] : y.v[i];
+    return r;
+}
+// a lane's contribution to a grid reduction of K sums when it holds a term of sum `slot` only: t in acc[slot], zero elsewhere
+// (slot by reference: by value the two-sum quadratic kernel comes out one compare shorter than the loops written out in it gave)
+template <int K>
+__device__ __forceinline__ void acc_only(fe (&acc)[K], const unsigned& slot, const fe& t) {
+#pragma unroll
+    for (int q = 0; q < K; q++)
+#pragma unroll
+        for (int i = 0; i < 8; i++) acc[q].v[i] = slot == (unsigned)q ? t.v[i] : 0u;
+}
+
 // ---------------------------------------------------------------- T1: evals <-> coeffs
 // EvaluationsList::to_coeffs (call sites provekit/prover/src/whir_r1cs.rs:195,198): for every
 // variable (index bit) h: v[i | h] -= v[i].  SUB=false gives the inverse (to_evals).
@@ -293,43 +310,67 @@ __global__ __launch_bounds__(256) void eq_accumulate_kernel(fe* __restrict__ w, 
 
 // ---------------------------------------------------------------- S3: cubic sumcheck round
 // sumcheck_fold_map_reduce::<4,3> (provekit/common/src/utils/sumcheck.rs:16-104) with the map of
-// provekit/prover/src/whir_r1cs.rs:284-291.
-template <bool FOLD>
-__global__ __launch_bounds__(RED_THREADS) void sumcheck_cubic_kernel(fe* __restrict__ a, fe* __restrict__ b, fe* __restrict__ c,
-                                                                     fe* __restrict__ eq, size_t len, fe_arg fold_arg, gate_args gate, red_out red) {
+// provekit/prover/src/whir_r1cs.rs:284-291.  The weight of a pair comes in one of two ways:
+//   CubicWeight::EqArray: a fourth array, folded with a, b, c; it enters the evaluations as eq0, eq1 and the sums are f(0), f(-1), f_inf;
+//   CubicWeight::Level:   one read-only entry E_i[i] per pair ("without the folded eq array" below); the sums are Q(0), Q(-1), Q_inf.
+template <CubicWeight W>
+using weight_elem = std::conditional_t<W == CubicWeight::Level, const fe, fe>;
+
+// A lane per pair.  The workgroup size is read through the builtin: blockDim.x in a function that is inlined into the kernel is not
+// folded to the dispatch's group size (that needs the kernel's own uniform-work-group-size attribute) and costs a vector load.
+template <bool FOLD, CubicWeight W>
+__device__ __forceinline__ void cubic_round_wide(fe* __restrict__ a, fe* __restrict__ b, fe* __restrict__ c, weight_elem<W>* __restrict__ wt, size_t len,
+                                                 fe_arg fold_arg, gate_args gate, red_out red) {
+    constexpr bool LEVEL = W == CubicWeight::Level;
+    constexpr int NA = LEVEL ? 3 : 4;  // arrays that fold
     PK_LATENCY_PRIO();
     const fe alpha = (FOLD && gate.host) ? gate_wait(gate) : from_arg(fold_arg);
     const size_t npairs = FOLD ? len / 4 : len / 2;
     const size_t off = npairs;          // partner of i is i + off (quarter 1 after folding, or the upper half)
     const size_t foff = len / 2;        // fold partner: p2 = p0 + len/2
     fe acc[3] = {fe_zero(), fe_zero(), fe_zero()};
-    const size_t stride = (size_t)gridDim.x * blockDim.x;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < npairs; i += stride) {
-        fe v[4][2];
-        fe* arr[4] = {a, b, c, eq};
+    const size_t stride = (size_t)gridDim.x * __builtin_amdgcn_workgroup_size_x();
+    for (size_t i = (size_t)blockIdx.x * __builtin_amdgcn_workgroup_size_x() + threadIdx.x; i < npairs; i += stride) {
+        fe v[NA][2];
+        fe* arr[4] = {a, b, c, nullptr};
+        if constexpr (!LEVEL) arr[3] = wt;
 #pragma unroll
-        for (int k = 0; k < 4; k++) {
+        for (int k = 0; k < NA; k++) {
             fe x0 = fe_load(arr[k] + i), x1 = fe_load(arr[k] + i + off);
             if (FOLD) {  // sumcheck.rs:95-96: p0 += fold*(p2-p0); p1 += fold*(p3-p1)
                 fe x2 = fe_load(arr[k] + i + foff), x3 = fe_load(arr[k] + i + off + foff);
-                x0 = fe_add(x0, fe_mulx(alpha, fe_sub(x2, x0)));
-                x1 = fe_add(x1, fe_mulx(alpha, fe_sub(x3, x1)));
+                x0 = fe_fold(x0, x2, alpha);
+                x1 = fe_fold(x1, x3, alpha);
                 fe_store(arr[k] + i, x0);
                 fe_store(arr[k] + i + off, x1);
             }
             v[k][0] = x0;
             v[k][1] = x1;
         }
-        const fe &a0 = v[0][0], &a1 = v[0][1], &b0 = v[1][0], &b1 = v[1][1], &c0 = v[2][0], &c1 = v[2][1], &e0 = v[3][0], &e1 = v[3][1];
+        const fe &a0 = v[0][0], &a1 = v[0][1], &b0 = v[1][0], &b1 = v[1][1], &c0 = v[2][0], &c1 = v[2][1];
+        fe e0, e1;  // Level: e0 = E_i[i] weighs all three sums
+        if constexpr (LEVEL) {
+            e0 = fe_load(wt + i);
+        } else {
+            e0 = v[NA - 1][0];
+            e1 = v[NA - 1][1];
+        }
         // f0 = eq0 * (a0*b0 - c0)
         acc[0] = fe_add(acc[0], fe_mulx(e0, fe_sub(fe_mulx(a0, b0), c0)));
         // f(-1) = (2eq0-eq1) * ((2a0-a1)(2b0-b1) - (2c0-c1))
-        fe ta = fe_sub(fe_dbl(a0), a1), tb = fe_sub(fe_dbl(b0), b1), tc = fe_sub(fe_dbl(c0), c1), te = fe_sub(fe_dbl(e0), e1);
+        fe ta = fe_sub(fe_dbl(a0), a1), tb = fe_sub(fe_dbl(b0), b1), tc = fe_sub(fe_dbl(c0), c1), te = e0;
+        if constexpr (!LEVEL) te = fe_sub(fe_dbl(e0), e1);
         acc[1] = fe_add(acc[1], fe_mulx(te, fe_sub(fe_mulx(ta, tb), tc)));
         // f_inf = (eq1-eq0)(a1-a0)(b1-b0)
-        acc[2] = fe_add(acc[2], fe_mulx(fe_mulx(fe_sub(e1, e0), fe_sub(a1, a0)), fe_sub(b1, b0)));
+        if constexpr (LEVEL) acc[2] = fe_add(acc[2], fe_mulx(e0, fe_mulx(fe_sub(a1, a0), fe_sub(b1, b0))));
+        else acc[2] = fe_add(acc[2], fe_mulx(fe_mulx(fe_sub(e1, e0), fe_sub(a1, a0)), fe_sub(b1, b0)));
     }
     grid_finish_fe<3>(acc, red);
+}
+template <bool FOLD>
+__global__ __launch_bounds__(RED_THREADS) void sumcheck_cubic_kernel(fe* __restrict__ a, fe* __restrict__ b, fe* __restrict__ c,
+                                                                     fe* __restrict__ eq, size_t len, fe_arg fold_arg, gate_args gate, red_out red) {
+    cubic_round_wide<FOLD, CubicWeight::EqArray>(a, b, c, eq, len, fold_arg, gate, red);
 }
 
 // ---------------------------------------------------------------- W3: quadratic sumcheck round
@@ -354,11 +395,11 @@ __global__ __launch_bounds__(RED_THREADS) void sumcheck_quadratic_kernel(const f
         fe f0, f1, w0, w1;
         if (FOLD) {
             fe x0 = fe_load(f + 4 * i), x1 = fe_load(f + 4 * i + 1), x2 = fe_load(f + 4 * i + 2), x3 = fe_load(f + 4 * i + 3);
-            f0 = fe_add(x0, fe_mulx(r, fe_sub(x1, x0)));
-            f1 = fe_add(x2, fe_mulx(r, fe_sub(x3, x2)));
+            f0 = fe_fold(x0, x1, r);
+            f1 = fe_fold(x2, x3, r);
             fe y0 = fe_load(w + 4 * i), y1 = fe_load(w + 4 * i + 1), y2 = fe_load(w + 4 * i + 2), y3 = fe_load(w + 4 * i + 3);
-            w0 = fe_add(y0, fe_mulx(r, fe_sub(y1, y0)));
-            w1 = fe_add(y2, fe_mulx(r, fe_sub(y3, y2)));
+            w0 = fe_fold(y0, y1, r);
+            w1 = fe_fold(y2, y3, r);
             fe_store(f_out + 2 * i, f0);
             fe_store(f_out + 2 * i + 1, f1);
             fe_store(w_out + 2 * i, w0);
@@ -384,54 +425,69 @@ __global__ __launch_bounds__(RED_THREADS) void sumcheck_quadratic_kernel(const f
 constexpr size_t SMALL_ROUND_PAIRS = 16384;
 constexpr unsigned EQ_SUFFIX_ONE_WG_VARS = 11;  // suffix equality tables of up to this many variables come from one workgroup
 
-__global__ __launch_bounds__(RED_THREADS) void sumcheck_cubic_small_kernel(fe* __restrict__ a, fe* __restrict__ b, fe* __restrict__ c,
-                                                                           fe* __restrict__ eq, size_t len, fe_arg fold_arg, gate_args gate, red_out red) {
+// eight lanes per pair, folding rounds only: lane 2k + j of a pair folds value j of array k (a, b, c; EqArray: and eq); Level: six fold, the
+// seventh fetches the pair's E entry.  Then three lanes form one evaluation each: one fold product and two more deep.
+template <CubicWeight W>
+__device__ __forceinline__ void cubic_round_small(fe* __restrict__ a, fe* __restrict__ b, fe* __restrict__ c, weight_elem<W>* __restrict__ wt, size_t len,
+                                                  fe_arg fold_arg, gate_args gate, red_out red) {
+    constexpr bool LEVEL = W == CubicWeight::Level;
     PK_LATENCY_PRIO();
     __shared__ uint4 xs[2 * RED_THREADS];  // folded value of lane t at [t] (lo) and [RED_THREADS + t] (hi)
     const fe alpha = gate.host ? gate_wait(gate) : from_arg(fold_arg);
     const size_t npairs = len / 4, off = npairs, foff = len / 2;
     const unsigned tid = threadIdx.x, g = tid >> 3, role = tid & 7, k = role >> 1, which = role & 1;
     const size_t i = (size_t)blockIdx.x * (RED_THREADS / 8) + g;
-    fe* arr = k == 0 ? a : k == 1 ? b : k == 2 ? c : eq;
-    if (i < npairs) {  // sumcheck.rs:95-96: p0 += fold*(p2-p0); p1 += fold*(p3-p1)
+    fe* arr = k == 0 ? a : k == 1 ? b : c;
+    if constexpr (!LEVEL) arr = k == 0 ? a : k == 1 ? b : k == 2 ? c : wt;
+    if (i < npairs && (!LEVEL || k < 3)) {  // sumcheck.rs:95-96: p0 += fold*(p2-p0); p1 += fold*(p3-p1)
         fe* p = arr + i + (which ? off : 0);
         fe x = fe_load(p), x2 = fe_load(p + foff);
-        x = fe_add(x, fe_mulx(alpha, fe_sub(x2, x)));
+        x = fe_fold(x, x2, alpha);
         fe_store(p, x);
         lds_put(xs, xs + RED_THREADS, tid, x);
+    } else if (LEVEL && i < npairs && role == 6) {
+        lds_put(xs, xs + RED_THREADS, tid, fe_load(wt + i));
     }
     __syncthreads();
     fe acc[3] = {fe_zero(), fe_zero(), fe_zero()};
     if (i < npairs && role < 3) {
         const unsigned base = tid & ~7u;
         auto v = [&](unsigned kk, unsigned w) { return lds_get(xs, xs + RED_THREADS, base + 2 * kk + w); };
-        const fe a0 = v(0, 0), a1 = v(0, 1), b0 = v(1, 0), b1 = v(1, 1), c0 = v(2, 0), c1 = v(2, 1), e0 = v(3, 0), e1 = v(3, 1);
+        const fe a0 = v(0, 0), a1 = v(0, 1), b0 = v(1, 0), b1 = v(1, 1), c0 = v(2, 0), c1 = v(2, 1), e0 = v(3, 0);
+        fe e1;  // EqArray only
+        if constexpr (!LEVEL) e1 = v(3, 1);
         // the three evaluations share one shape, X * (Y*Z - S), so the lanes of a pair run the same two multiplications on
         // operands selected by role (no divergent branches):
-        //   role 0: f0    = eq0 * (a0*b0 - c0)
-        //   role 1: f(-1) = (2eq0-eq1) * ((2a0-a1)(2b0-b1) - (2c0-c1))
-        //   role 2: f_inf = (b1-b0) * ((eq1-eq0)(a1-a0) - 0)
-        auto pick = [&](const fe& x0, const fe& x1) {
+        //            EqArray                                                  Level
+        //   role 0:  f0    = eq0 * (a0*b0 - c0)                               Q(0)  = E * (a0*b0 - c0)
+        //   role 1:  f(-1) = (2eq0-eq1) * ((2a0-a1)(2b0-b1) - (2c0-c1))       Q(-1) = E * ((2a0-a1)(2b0-b1) - (2c0-c1))
+        //   role 2:  f_inf = (b1-b0) * ((eq1-eq0)(a1-a0) - 0)                 Q_inf = E * ((a1-a0)(b1-b0) - 0)
+        auto pick = [&](const fe& x0, const fe& x1) {  // written out: as two fe_select the compiler holds all three operands, 7 VGPRs more
             fe m1 = fe_sub(fe_dbl(x0), x1), d = fe_sub(x1, x0), r;
 #pragma unroll
             for (int w = 0; w < 8; w++) r.v[w] = role == 0 ? x0.v[w] : role == 1 ? m1.v[w] : d.v[w];
             return r;
         };
-        const fe pa = pick(a0, a1), pb = pick(b0, b1), pc = pick(c0, c1), pe = pick(e0, e1);
-        fe X, Y, S;
-#pragma unroll
-        for (int w = 0; w < 8; w++) {
-            X.v[w] = role == 2 ? pb.v[w] : pe.v[w];
-            Y.v[w] = role == 2 ? pe.v[w] : pb.v[w];
-            S.v[w] = role == 2 ? 0u : pc.v[w];
+        const fe pa = pick(a0, a1), pb = pick(b0, b1), pc = pick(c0, c1);
+        fe X, Y, Z;
+        if constexpr (LEVEL) {
+            X = e0;
+            Y = pa;
+            Z = pb;
+        } else {
+            const fe pe = pick(e0, e1);
+            X = fe_select(role == 2, pb, pe);
+            Y = fe_select(role == 2, pe, pb);
+            Z = pa;
         }
-        const fe t = fe_mulx(X, fe_sub(fe_mulx(Y, pa), S));
-#pragma unroll
-        for (int r = 0; r < 3; r++)
-#pragma unroll
-            for (int w = 0; w < 8; w++) acc[r].v[w] = role == (unsigned)r ? t.v[w] : 0u;
+        const fe S = fe_select(role == 2, fe_zero(), pc);
+        acc_only(acc, role, fe_mulx(X, fe_sub(fe_mulx(Y, Z), S)));
     }
     grid_finish_fe<3>(acc, red);
+}
+__global__ __launch_bounds__(RED_THREADS) void sumcheck_cubic_small_kernel(fe* __restrict__ a, fe* __restrict__ b, fe* __restrict__ c,
+                                                                           fe* __restrict__ eq, size_t len, fe_arg fold_arg, gate_args gate, red_out red) {
+    cubic_round_small<CubicWeight::EqArray>(a, b, c, eq, len, fold_arg, gate, red);
 }
 
 template <bool FOLD, int NS>
@@ -450,7 +506,7 @@ __global__ __launch_bounds__(RED_THREADS) void sumcheck_quadratic_small_kernel(c
         fe x;
         if (FOLD) {
             fe x0 = fe_load(src + 4 * i + 2 * j), x1 = fe_load(src + 4 * i + 2 * j + 1);
-            x = fe_add(x0, fe_mulx(r, fe_sub(x1, x0)));
+            x = fe_fold(x0, x1, r);
             fe_store((role < 2 ? f_out : w_out) + 2 * i + j, x);
         } else {
             x = fe_load(src + 2 * i + j);
@@ -468,17 +524,8 @@ __global__ __launch_bounds__(RED_THREADS) void sumcheck_quadratic_small_kernel(c
         // one multiplication on operands selected by role: h(0) = f0 w0, h(1) = f1 w1, h(2) = (2f1-f0)(2w1-w0); two sums: role 1 forms h(2)
         const unsigned ev = NS == 3 ? role : 2 * role;
         const fe tf = fe_sub(fe_dbl(f1), f0), tw = fe_sub(fe_dbl(w1), w0);
-        fe X, Y;
-#pragma unroll
-        for (int v = 0; v < 8; v++) {
-            X.v[v] = ev == 0 ? f0.v[v] : ev == 1 ? f1.v[v] : tf.v[v];
-            Y.v[v] = ev == 0 ? w0.v[v] : ev == 1 ? w1.v[v] : tw.v[v];
-        }
-        const fe t = fe_mulx(X, Y);
-#pragma unroll
-        for (int q = 0; q < NS; q++)
-#pragma unroll
-            for (int v = 0; v < 8; v++) acc[q].v[v] = role == (unsigned)q ? t.v[v] : 0u;
+        const fe X = fe_select(ev == 0, f0, fe_select(ev == 1, f1, tf)), Y = fe_select(ev == 0, w0, fe_select(ev == 1, w1, tw));
+        acc_only(acc, role, fe_mulx(X, Y));
     }
     grid_finish_fe<NS>(acc, red);
 }
@@ -543,83 +590,12 @@ template <bool FOLD>
 __global__ __launch_bounds__(RED_THREADS) void sumcheck_cubic_spliteq_kernel(fe* __restrict__ a, fe* __restrict__ b, fe* __restrict__ c,
                                                                              const fe* __restrict__ E, size_t len, fe_arg fold_arg, gate_args gate,
                                                                              red_out red) {
-    PK_LATENCY_PRIO();
-    const fe alpha = (FOLD && gate.host) ? gate_wait(gate) : from_arg(fold_arg);
-    const size_t npairs = FOLD ? len / 4 : len / 2;
-    const size_t off = npairs, foff = len / 2;  // as sumcheck_cubic_kernel
-    fe acc[3] = {fe_zero(), fe_zero(), fe_zero()};
-    const size_t stride = (size_t)gridDim.x * blockDim.x;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < npairs; i += stride) {
-        fe v[3][2];
-        fe* arr[3] = {a, b, c};
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-            fe x0 = fe_load(arr[k] + i), x1 = fe_load(arr[k] + i + off);
-            if (FOLD) {
-                fe x2 = fe_load(arr[k] + i + foff), x3 = fe_load(arr[k] + i + off + foff);
-                x0 = fe_add(x0, fe_mulx(alpha, fe_sub(x2, x0)));
-                x1 = fe_add(x1, fe_mulx(alpha, fe_sub(x3, x1)));
-                fe_store(arr[k] + i, x0);
-                fe_store(arr[k] + i + off, x1);
-            }
-            v[k][0] = x0;
-            v[k][1] = x1;
-        }
-        const fe &a0 = v[0][0], &a1 = v[0][1], &b0 = v[1][0], &b1 = v[1][1], &c0 = v[2][0], &c1 = v[2][1];
-        const fe e = fe_load(E + i);
-        acc[0] = fe_add(acc[0], fe_mulx(e, fe_sub(fe_mulx(a0, b0), c0)));
-        fe ta = fe_sub(fe_dbl(a0), a1), tb = fe_sub(fe_dbl(b0), b1), tc = fe_sub(fe_dbl(c0), c1);
-        acc[1] = fe_add(acc[1], fe_mulx(e, fe_sub(fe_mulx(ta, tb), tc)));
-        acc[2] = fe_add(acc[2], fe_mulx(e, fe_mulx(fe_sub(a1, a0), fe_sub(b1, b0))));
-    }
-    grid_finish_fe<3>(acc, red);
+    cubic_round_wide<FOLD, CubicWeight::Level>(a, b, c, E, len, fold_arg, gate, red);
 }
-// few pairs: eight lanes per pair as sumcheck_cubic_small_kernel -- six fold a value each, the seventh fetches the pair's E entry --
-// then three lanes form E * (Y*Z - S): one fold product and two more deep
 __global__ __launch_bounds__(RED_THREADS) void sumcheck_cubic_spliteq_small_kernel(fe* __restrict__ a, fe* __restrict__ b, fe* __restrict__ c,
                                                                                    const fe* __restrict__ E, size_t len, fe_arg fold_arg, gate_args gate,
                                                                                    red_out red) {
-    PK_LATENCY_PRIO();
-    __shared__ uint4 xs[2 * RED_THREADS];
-    const fe alpha = gate.host ? gate_wait(gate) : from_arg(fold_arg);
-    const size_t npairs = len / 4, off = npairs, foff = len / 2;
-    const unsigned tid = threadIdx.x, g = tid >> 3, role = tid & 7, k = role >> 1, which = role & 1;
-    const size_t i = (size_t)blockIdx.x * (RED_THREADS / 8) + g;
-    if (i < npairs && k < 3) {
-        fe* p = (k == 0 ? a : k == 1 ? b : c) + i + (which ? off : 0);
-        fe x = fe_load(p), x2 = fe_load(p + foff);
-        x = fe_add(x, fe_mulx(alpha, fe_sub(x2, x)));
-        fe_store(p, x);
-        lds_put(xs, xs + RED_THREADS, tid, x);
-    } else if (i < npairs && role == 6) {
-        lds_put(xs, xs + RED_THREADS, tid, fe_load(E + i));
-    }
-    __syncthreads();
-    fe acc[3] = {fe_zero(), fe_zero(), fe_zero()};
-    if (i < npairs && role < 3) {
-        const unsigned base = tid & ~7u;
-        auto v = [&](unsigned kk, unsigned w) { return lds_get(xs, xs + RED_THREADS, base + 2 * kk + w); };
-        const fe a0 = v(0, 0), a1 = v(0, 1), b0 = v(1, 0), b1 = v(1, 1), c0 = v(2, 0), c1 = v(2, 1), e = v(3, 0);
-        //   role 0: Q(0)  = E * (a0*b0 - c0)
-        //   role 1: Q(-1) = E * ((2a0-a1)(2b0-b1) - (2c0-c1))
-        //   role 2: Q_inf = E * ((a1-a0)(b1-b0) - 0)
-        auto pick = [&](const fe& x0, const fe& x1) {
-            fe m1 = fe_sub(fe_dbl(x0), x1), d = fe_sub(x1, x0), r;
-#pragma unroll
-            for (int w = 0; w < 8; w++) r.v[w] = role == 0 ? x0.v[w] : role == 1 ? m1.v[w] : d.v[w];
-            return r;
-        };
-        const fe pa = pick(a0, a1), pb = pick(b0, b1);
-        fe S = pick(c0, c1);
-#pragma unroll
-        for (int w = 0; w < 8; w++) S.v[w] = role == 2 ? 0u : S.v[w];
-        const fe t = fe_mulx(e, fe_sub(fe_mulx(pa, pb), S));
-#pragma unroll
-        for (int r = 0; r < 3; r++)
-#pragma unroll
-            for (int w = 0; w < 8; w++) acc[r].v[w] = role == (unsigned)r ? t.v[w] : 0u;
-    }
-    grid_finish_fe<3>(acc, red);
+    cubic_round_small<CubicWeight::Level>(a, b, c, E, len, fold_arg, gate, red);
 }
 
 // the single-element tail of the fold (out_len == 1): v'[0] = v[0] + r (v[1]-v[0]); no pair to sum.  blockIdx.y selects
@@ -633,7 +609,7 @@ __global__ void fold_pairs_kernel(const fe* __restrict__ v0, fe* __restrict__ ou
     const size_t stride = (size_t)gridDim.x * blockDim.x;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < out_len; i += stride) {
         fe x0 = fe_load(v + 2 * i), x1 = fe_load(v + 2 * i + 1);
-        fe_store(out + i, fe_add(x0, fe_mulx(r, fe_sub(x1, x0))));
+        fe_store(out + i, fe_fold(x0, x1, r));
     }
 }
 
@@ -874,60 +850,53 @@ int dot(pk_ctx* ctx, int nv, const uint64_t* d_w, const uint64_t* d_f, const uin
     return collect_reduction(ctx, nv, out);
 }
 
+// What the launch of a sumcheck round, cubic or quadratic, does once its arguments are checked: the reduction (its sequence number goes
+// to the caller), the gate and the challenge argument -- not folding: no challenge and no gate (fe_arg{}, gate_none()) -- and the grid:
+// reduction_begin's with a lane per pair, enough workgroups for all pairs with `lanes_per_pair` lanes each in a small round.
+struct round_launch {
+    red_out red;
+    unsigned blocks;
+    gate_args gate;
+    fe_arg farg;
+};
+int round_launch_begin(pk_ctx* ctx, size_t npairs, unsigned lanes_per_pair, const uint64_t* fold_or_null, unsigned gate_seq, unsigned* red_seq_out,
+                       round_launch* L) {
+    int rc = reduction_begin(ctx, npairs, &L->red, &L->blocks);
+    if (rc) return rc;
+    *red_seq_out = L->red.seq;
+    L->gate = gate_seq ? gate_for(ctx, gate_seq) : gate_none();
+    L->farg = fold_or_null ? to_arg(fold_or_null) : fe_arg{};
+    const size_t pairs_per_wg = RED_THREADS / lanes_per_pair;
+    if (lanes_per_pair > 1) L->blocks = (unsigned)((npairs + pairs_per_wg - 1) / pairs_per_wg);
+    return PK_OK;
+}
+
 }  // namespace
 
 namespace pk {
 
 // launch only: round results go to the pinned page under sequence number *red_seq_out.  gate_seq != 0 (latency mode, folding rounds
 // only): the folding challenge is not known yet -- the kernel waits for gate_publish(ctx, gate_seq, challenge) (reduce.hpp)
-int sumcheck_cubic_launch(pk_ctx* ctx, uint64_t* d_a, uint64_t* d_b, uint64_t* d_c, uint64_t* d_eq, size_t len, const uint64_t* fold_or_null,
-                          unsigned gate_seq, unsigned* red_seq_out) {
-    PK_REQUIRE(ctx, d_a && d_b && d_c && d_eq && red_seq_out, "null pointer");
+int sumcheck_cubic_launch(pk_ctx* ctx, uint64_t* d_a, uint64_t* d_b, uint64_t* d_c, CubicWeight kind, uint64_t* d_weight, size_t len,
+                          const uint64_t* fold_or_null, unsigned gate_seq, unsigned* red_seq_out) {
+    PK_REQUIRE(ctx, d_a && d_b && d_c && d_weight && red_seq_out, "null pointer");
     PK_REQUIRE(ctx, is_pow2(len) && len >= 2, "size must be a power of two >= 2");  // sumcheck.rs:22-23
     const bool fold = fold_or_null || gate_seq;
     PK_REQUIRE(ctx, !fold || len >= 4, "size must be >= 4 when folding");    // sumcheck.rs:27
     const size_t npairs = fold ? len / 4 : len / 2;
-    red_out red;
-    unsigned blocks;
-    int rc = reduction_begin(ctx, npairs, &red, &blocks);
-    if (rc) return rc;
-    *red_seq_out = red.seq;
-    // not folding: no challenge and no gate (fe_arg{}, gate_none())
-    const gate_args gate = gate_seq ? gate_for(ctx, gate_seq) : gate_none();
-    const fe_arg farg = fold_or_null ? to_arg(fold_or_null) : fe_arg{};
     // a lane per pair, or -- folding rounds of few pairs only: there is no small kernel that does not fold -- eight lanes per pair
     const bool small = fold && npairs <= SMALL_ROUND_PAIRS;
-    auto kernel = small ? sumcheck_cubic_small_kernel : fold ? sumcheck_cubic_kernel<true> : sumcheck_cubic_kernel<false>;
-    if (small) blocks = (unsigned)((npairs + RED_THREADS / 8 - 1) / (RED_THREADS / 8));
-    {
-        ProfScope prof(ctx, "sumcheck_cubic");
-        kernel<<<blocks, RED_THREADS, 0, ctx->stream>>>((fe*)d_a, (fe*)d_b, (fe*)d_c, (fe*)d_eq, len, farg, gate, red);
-    }
-    PK_LAUNCH_CHECK(ctx);
-    return PK_OK;
-}
-// the same round without the eq array: d_level = E_i of the round the kernel evaluates (npairs entries, read only); the sums are Q(0), Q(-1), Q_inf
-int sumcheck_cubic_spliteq_launch(pk_ctx* ctx, uint64_t* d_a, uint64_t* d_b, uint64_t* d_c, const uint64_t* d_level, size_t len,
-                                  const uint64_t* fold_or_null, unsigned gate_seq, unsigned* red_seq_out) {
-    PK_REQUIRE(ctx, d_a && d_b && d_c && d_level && red_seq_out, "null pointer");
-    PK_REQUIRE(ctx, is_pow2(len) && len >= 2, "size must be a power of two >= 2");
-    const bool fold = fold_or_null || gate_seq;
-    PK_REQUIRE(ctx, !fold || len >= 4, "size must be >= 4 when folding");
-    const size_t npairs = fold ? len / 4 : len / 2;
-    red_out red;
-    unsigned blocks;
-    int rc = reduction_begin(ctx, npairs, &red, &blocks);
+    round_launch L;
+    int rc = round_launch_begin(ctx, npairs, small ? 8 : 1, fold_or_null, gate_seq, red_seq_out, &L);
     if (rc) return rc;
-    *red_seq_out = red.seq;
-    const gate_args gate = gate_seq ? gate_for(ctx, gate_seq) : gate_none();
-    const fe_arg farg = fold_or_null ? to_arg(fold_or_null) : fe_arg{};
-    const bool small = fold && npairs <= SMALL_ROUND_PAIRS;  // the same routing as sumcheck_cubic_launch
-    auto kernel = small ? sumcheck_cubic_spliteq_small_kernel : fold ? sumcheck_cubic_spliteq_kernel<true> : sumcheck_cubic_spliteq_kernel<false>;
-    if (small) blocks = (unsigned)((npairs + RED_THREADS / 8 - 1) / (RED_THREADS / 8));
-    {
+    auto launch = [&](auto kernel, auto* weight) {
         ProfScope prof(ctx, "sumcheck_cubic");
-        kernel<<<blocks, RED_THREADS, 0, ctx->stream>>>((fe*)d_a, (fe*)d_b, (fe*)d_c, (const fe*)d_level, len, farg, gate, red);
-    }
+        kernel<<<L.blocks, RED_THREADS, 0, ctx->stream>>>((fe*)d_a, (fe*)d_b, (fe*)d_c, weight, len, L.farg, L.gate, L.red);
+    };
+    if (kind == CubicWeight::Level)
+        launch(small ? sumcheck_cubic_spliteq_small_kernel : fold ? sumcheck_cubic_spliteq_kernel<true> : sumcheck_cubic_spliteq_kernel<false>, (const fe*)d_weight);
+    else
+        launch(small ? sumcheck_cubic_small_kernel : fold ? sumcheck_cubic_kernel<true> : sumcheck_cubic_kernel<false>, (fe*)d_weight);
     PK_LAUNCH_CHECK(ctx);
     return PK_OK;
 }
@@ -984,25 +953,22 @@ int sumcheck_quadratic_launch(pk_ctx* ctx, const uint64_t* d_f, const uint64_t* 
     PK_REQUIRE(ctx, out_len >= 2, "at least one pair is needed after folding");
     PK_REQUIRE(ctx, !fold || (d_f_out && d_w_out && d_f_out != d_f && d_w_out != d_w), "folding is out-of-place");
     const size_t npairs = out_len / 2;
-    red_out red;
-    unsigned blocks;
-    int rc = reduction_begin(ctx, npairs, &red, &blocks);
-    if (rc) return rc;
-    *red_seq_out = red.seq;
-    // not folding: no challenge, no gate and no output arrays
-    const gate_args gate = gate_seq ? gate_for(ctx, gate_seq) : gate_none();
-    const fe_arg farg = fold_or_null ? to_arg(fold_or_null) : fe_arg{};
-    if (!fold) d_f_out = d_w_out = nullptr;
     // a lane per pair, or -- rounds of few pairs, folding or not -- four lanes per pair
     const bool small = npairs <= SMALL_ROUND_PAIRS;
-    auto kernel = nsums == 3 ? (small ? (fold ? sumcheck_quadratic_small_kernel<true, 3> : sumcheck_quadratic_small_kernel<false, 3>)
-                                      : (fold ? sumcheck_quadratic_kernel<true, 3> : sumcheck_quadratic_kernel<false, 3>))
-                             : (small ? (fold ? sumcheck_quadratic_small_kernel<true, 2> : sumcheck_quadratic_small_kernel<false, 2>)
-                                      : (fold ? sumcheck_quadratic_kernel<true, 2> : sumcheck_quadratic_kernel<false, 2>));
-    if (small) blocks = (unsigned)((npairs + RED_THREADS / 4 - 1) / (RED_THREADS / 4));
+    round_launch L;
+    int rc = round_launch_begin(ctx, npairs, small ? 4 : 1, fold_or_null, gate_seq, red_seq_out, &L);
+    if (rc) return rc;
+    if (!fold) d_f_out = d_w_out = nullptr;  // not folding: no output arrays either
+    using kernel_t = void (*)(const fe*, const fe*, size_t, fe_arg, gate_args, fe*, fe*, red_out);
+    static const kernel_t kernels[2][2][2] = {  // [nsums - 2][small][fold]
+        {{sumcheck_quadratic_kernel<false, 2>, sumcheck_quadratic_kernel<true, 2>},
+         {sumcheck_quadratic_small_kernel<false, 2>, sumcheck_quadratic_small_kernel<true, 2>}},
+        {{sumcheck_quadratic_kernel<false, 3>, sumcheck_quadratic_kernel<true, 3>},
+         {sumcheck_quadratic_small_kernel<false, 3>, sumcheck_quadratic_small_kernel<true, 3>}}};
     {
         ProfScope prof(ctx, "sumcheck_quadratic");
-        kernel<<<blocks, RED_THREADS, 0, ctx->stream>>>((const fe*)d_f, (const fe*)d_w, out_len, farg, gate, (fe*)d_f_out, (fe*)d_w_out, red);
+        kernels[nsums - 2][small][fold]<<<L.blocks, RED_THREADS, 0, ctx->stream>>>((const fe*)d_f, (const fe*)d_w, out_len, L.farg, L.gate, (fe*)d_f_out,
+                                                                                  (fe*)d_w_out, L.red);
     }
     PK_LAUNCH_CHECK(ctx);
     return PK_OK;
@@ -1213,7 +1179,7 @@ int pk_sumcheck_cubic_round(pk_ctx* ctx, uint64_t* d_a, uint64_t* d_b, uint64_t*
     PK_ENTER(ctx);
     PK_REQUIRE(ctx, out, "null pointer");
     unsigned seq = 0;
-    int rc = sumcheck_cubic_launch(ctx, d_a, d_b, d_c, d_eq, len, fold_or_null, 0, &seq);
+    int rc = sumcheck_cubic_launch(ctx, d_a, d_b, d_c, CubicWeight::EqArray, d_eq, len, fold_or_null, 0, &seq);
     if (rc) return rc;
     return collect_reduction(ctx, 3, out);
 }
@@ -1241,7 +1207,8 @@ int pk_selftest_sumcheck_cubic_spliteq(pk_ctx* ctx, uint64_t* d_a, uint64_t* d_b
     PK_REQUIRE(ctx, out && r && d_tables && n >= 1 && n <= 27 && round < n && (round == 0 || alphas), "bad round");
     const size_t N = (size_t)1 << n, len = round ? N >> (round - 1) : N;
     unsigned seq = 0;
-    int rc = sumcheck_cubic_spliteq_launch(ctx, d_a, d_b, d_c, d_tables + 4 * (N - (N >> round)), len, round ? alphas + 4 * (round - 1) : nullptr, 0, &seq);
+    uint64_t* level = const_cast<uint64_t*>(d_tables) + 4 * (N - (N >> round));  // read only
+    int rc = sumcheck_cubic_launch(ctx, d_a, d_b, d_c, CubicWeight::Level, level, len, round ? alphas + 4 * (round - 1) : nullptr, 0, &seq);
     if (rc) return rc;
     rc = collect_reduction(ctx, 3, out);
     if (rc) return rc;

@@ -310,6 +310,56 @@ bool rows_at_equal_stride3(fe* const* d_weights, const size_t* weight_len, unsig
     return n_weights == 3 && weight_len[0] == weight_len[1] && weight_len[1] == weight_len[2] && d_weights[1] > d_weights[0] &&
            d_weights[1] - d_weights[0] == d_weights[2] - d_weights[1];
 }
+
+// ------------------------------------------------------------------ the round loop of the prover's sumchecks
+// `rounds` rounds, each: the round's sums, the message, absorb, squeeze the folding challenge, record it.  The Spartan cubic rounds
+// (ZkRounds) and the WHIR quadratic rounds (WhirProver) bring, as `s`, only what differs between them:
+//   launch(t, fold, gate_seq, &red_seq), nsums(t)  enqueue round t's kernel, which first folds by `fold` or by the gate's challenge (round 0: neither); its sums
+//   closing_fold(), fold(r, gate_seq)              whether the last challenge is applied by a fold of its own, and that fold
+//   meanwhile(t)                                   host work of round t that needs the earlier challenges only
+//   before_sync_launch(), sharded                  synchronous rounds: what precedes the launch; whether the sums are sums over the ranks
+//   message(t, out, msg), record(t, msg, r)        the kernel's sums -> the message msg[0 .. return value); round t's challenge r is known
+// Latency mode (pipelined): what consumes round t's challenge -- round t+1, or after the last round the closing fold -- is enqueued
+// BEFORE round t's result is read, gated on the challenge the host publishes once it has squeezed it, and meanwhile() runs under that
+// kernel; the round trip then costs the link, not a launch + sync.  A gated kernel waits on the host: PendingGate releases it on
+// whatever path leaves the round.  Otherwise every round is a synchronous call that first folds by the previous challenge.
+template <class S>
+int sumcheck_round_loop(pk_ctx* ctx, Transcript& T, unsigned rounds, bool pipelined, S& s) {
+    unsigned red_cur = 0, red_next = 0;
+    uint64_t f[4];  // the previous round's challenge
+    if (pipelined) CK(s.launch(0, nullptr, 0, &red_cur));
+    for (unsigned t = 0; t < rounds; t++) {
+        PendingGate gate(ctx);
+        const bool more = t + 1 < rounds;
+        if (pipelined && (more || s.closing_fold())) {
+            gate.arm(sumcheck_gate_next(ctx));
+            CK(more ? s.launch(t + 1, nullptr, gate.seq, &red_next) : s.fold(nullptr, gate.seq));
+        }
+        s.meanwhile(t);
+        uint64_t out[12];
+        if (pipelined) {
+            CK(sumcheck_collect_spin(ctx, s.nsums(t), red_cur, out));
+            red_cur = red_next;
+        } else {
+            CK(s.before_sync_launch());
+            Across ac(ctx, s.sharded);
+            CK(ac.rc);
+            unsigned seq = 0;
+            CK(s.launch(t, t ? f : nullptr, 0, &seq));
+            CK(sumcheck_collect(ctx, s.nsums(t), out));
+        }
+        fe msg[4];
+        const unsigned n = s.message(t, out, msg);
+        T.add_scalars(msg, n);
+        const fe r = T.challenge_scalar();
+        gate.publish(r);
+        h_store(f, r);
+        s.record(t, msg, r);
+    }
+    if (!pipelined && rounds && s.closing_fold()) CK(s.fold(f, 0));
+    return PK_OK;
+}
+
 struct WhirProver {
     pk_ctx* ctx;
     Arena& A;
@@ -373,64 +423,47 @@ struct WhirProver {
         len /= 2;
     }
 
-    // `rounds` quadratic sumcheck rounds on p, w, each: the round's h(0), h(1), h(2), absorb, squeeze the folding challenge, record
-    // it; afterwards p, w describe the folded polynomial.  A round whose claim h(0) + h(1) the prover holds -- every round but the
-    // first after new weights went into w: the claim is the previous round's h(r), and before the first call the statement's own
-    // sum (start) -- asks its kernel for h(0) and h(2) only and takes h(1) = claim - h(0).  Latency mode (one GPU): round t+1's kernel -- after the last round the
-    // fold -- is enqueued BEFORE round t's result is read, gated on the challenge the host publishes once it has squeezed it; the
-    // round trip then costs the link, not a launch + sync.  Otherwise every round is a synchronous call that first folds by the
-    // previous challenge (sharded: its h(0), h(1), h(2) are sums over the ranks' blocks).
+    // `rounds` quadratic sumcheck rounds on p, w (sumcheck_round_loop), each: the round's h(0), h(1), h(2), absorb, squeeze the folding
+    // challenge, record it; afterwards p, w describe the folded polynomial.  A round whose claim h(0) + h(1) the prover holds -- every
+    // round but the first after new weights went into w: the claim is the previous round's h(r), and before the first call the
+    // statement's own sum (start) -- asks its kernel for h(0) and h(2) only and takes h(1) = claim - h(0).  Latency mode: one GPU.
+    // Sharded, the sums of a round are sums over the ranks' blocks.
     int sumcheck_rounds(unsigned rounds) {
         rs.clear();
+        ns0 = have_claim ? 2 : 3;
         const bool pipelined = ctx->latency_mode && G == 1 && rounds && len >= ((size_t)1 << rounds);
-        unsigned red_cur = 0, red_next = 0;
-        const int ns0 = have_claim ? 2 : 3;  // sums of round 0; the later rounds always have their claim
-        if (pipelined) CK(sumcheck_quadratic_launch(ctx, U(bp[cur]), U(bw[cur]), len, nullptr, 0, nullptr, nullptr, ns0, &red_cur));
-        for (unsigned t = 0; t < rounds; t++) {  // the same steps in the same order as Proof::zk_rounds
-            PendingGate gate(ctx);
-            const int ns = t ? 2 : ns0;
-            // pipelined: what consumes this round's challenge -- the next round (folding first), or the closing fold -- goes into the queue, gated
-            const bool more = t + 1 < rounds;
-            if (pipelined && (more || len >= 2)) {
-                gate.arm(sumcheck_gate_next(ctx));
-                if (more) CK(sumcheck_quadratic_launch(ctx, U(bp[cur]), U(bw[cur]), len, nullptr, gate.seq, U(bp[1 - cur]), U(bw[1 - cur]), 2, &red_next));
-                else CK(fold_pairs2(ctx, U(bp[cur]), U(bp[1 - cur]), U(bw[cur]), U(bw[1 - cur]), len, nullptr, gate.seq));
-                flip();
-            }
-            uint64_t out[12], f[4];
-            if (pipelined) {
-                CK(sumcheck_collect_spin(ctx, ns, red_cur, out));
-                red_cur = red_next;
-            } else {
-                Across ac(ctx, sharded);  // sharded: the sums are sums over the ranks' blocks
-                CK(ac.rc);
-                if (t) h_store(f, rs.back());
-                unsigned seq = 0;
-                CK(sumcheck_quadratic_launch(ctx, U(bp[cur]), U(bw[cur]), len, t ? f : nullptr, 0, U(bp[1 - cur]), U(bw[1 - cur]), ns, &seq));  // round 0 folds nothing, writes nothing
-                CK(sumcheck_collect(ctx, ns, out));
-                if (t) flip();
-            }
-            if (ns == 2) {
-                uint64_t cl[4];
-                h_store(cl, claim);
-                sumcheck_quadratic_from_claim(cl, out);
-            }
-            const fe msg[3] = {h_load(out), h_load(out + 4), h_load(out + 8)};
-            T.add_scalars(msg, 3);
-            const fe r = T.challenge_scalar();
-            gate.publish(r);
-            rs.push_back(r);
-            all_r.push_back(r);
-            claim = eval_quadratic_012(msg, r);  // the next round's h(0) + h(1)
-            have_claim = true;
-        }
-        if (!pipelined && rounds && len >= 2) {  // apply the last challenge: p, w now describe the folded polynomial
-            uint64_t f[4];
-            h_store(f, rs.back());
-            CK(fold_pairs2(ctx, U(bp[cur]), U(bp[1 - cur]), U(bw[cur]), U(bw[1 - cur]), len, f));
-            flip();
-        }
+        return sumcheck_round_loop(ctx, T, rounds, pipelined, *this);
+    }
+    // what sumcheck_round_loop asks of its sumcheck
+    int ns0 = 3;  // sums of round 0; the later rounds always have their claim
+    int nsums(unsigned t) const { return t ? 2 : ns0; }
+    int launch(unsigned t, const uint64_t* fold, unsigned gate_seq, unsigned* red_seq) {  // round 0 folds nothing, writes nothing
+        CK(sumcheck_quadratic_launch(ctx, U(bp[cur]), U(bw[cur]), len, fold, gate_seq, U(bp[1 - cur]), U(bw[1 - cur]), nsums(t), red_seq));
+        if (fold || gate_seq) flip();
         return PK_OK;
+    }
+    bool closing_fold() const { return len >= 2; }  // applies the last challenge: p, w then describe the folded polynomial
+    int fold(const uint64_t* r, unsigned gate_seq) {
+        CK(fold_pairs2(ctx, U(bp[cur]), U(bp[1 - cur]), U(bw[cur]), U(bw[1 - cur]), len, r, gate_seq));
+        flip();
+        return PK_OK;
+    }
+    int before_sync_launch() { return PK_OK; }
+    void meanwhile(unsigned) {}
+    unsigned message(unsigned t, uint64_t out[12], fe msg[4]) {
+        if (nsums(t) == 2) {
+            uint64_t cl[4];
+            h_store(cl, claim);
+            sumcheck_quadratic_from_claim(cl, out);
+        }
+        for (int q = 0; q < 3; q++) msg[q] = h_load(out + 4 * q);
+        return 3;
+    }
+    void record(unsigned, const fe* msg, const fe& r) {
+        rs.push_back(r);
+        all_r.push_back(r);
+        claim = eval_quadratic_012(msg, r);  // the next round's h(0) + h(1)
+        have_claim = true;
     }
 
     // all-gather of the ranks' blocks of p and w into (p0, w0) -- block r of the gather IS index range r -- after which the rest of
@@ -885,92 +918,82 @@ int Proof::zk_sumcheck() {
     return zk_rounds(z, length, sharded, sharded ? nullptr : r.data());
 }
 
-// the m_0 cubic rounds, each: the round's evaluations, the message, absorb, squeeze, record.  Latency mode (one GPU): round t+1 is
-// in the queue, gated on a_t, while round t is absorbed.  Otherwise every round is a synchronous call that first folds by the
-// previous challenge (sharded: its evaluations are sums over the ranks' shares; short shares are gathered and finish replicated).
+// The m_0 cubic rounds (the hot loop, whir_r1cs.rs:280-345), as sumcheck_round_loop runs them: no closing fold, three sums per round.
+// Latency mode (one GPU): a round's blinding coefficients, which depend only on the earlier challenges, are computed while its
+// kernel runs.  Sharded, a round's evaluations are sums over the ranks' shares; short shares are gathered and finish replicated.
 // r != null (every proof that is not sharded): z[3] holds the suffix equality tables of r instead of the eq array, the kernels fold a, b,
 // c only and return Q(0), Q(-1), Q_inf; the round's scalars P_t (1 - r_t), P_t (2 - 3 r_t), P_t (2 r_t - 1) are applied here.  A sharded
 // proof (r == null) keeps the four-array kernels: its arrays are split by the LOW index bits, which a level E_t does not factor over.
-int Proof::zk_rounds(fe* z[4], size_t len, bool sharded, const fe* r) {
-    const unsigned m_0 = s->m_0;
-    const bool split = r != nullptr;
-    const size_t M = len;
-    uint64_t P[4];  // P_t = prod_{k<t} eq(r_k, alpha_k)
-    h_store(P, fe_one());
-    // round t's kernel (folding first by `fold` or by the gate's challenge): the level E_t or the eq array
-    auto launch = [&](unsigned t, size_t l, const uint64_t* fold, unsigned gate_seq, unsigned* seq) {
-        return split ? sumcheck_cubic_spliteq_launch(ctx, U(z[0]), U(z[1]), U(z[2]), U(z[3] + (M - (M >> t))), l, fold, gate_seq, seq)
-                     : sumcheck_cubic_launch(ctx, U(z[0]), U(z[1]), U(z[2]), U(z[3]), l, fold, gate_seq, seq);
-    };
-    // sum_over_hypercube (whir_r1cs.rs:172-180)
-    fe gp[4];
-    blinding_coefficients_for_round(g_univ, 0, nullptr, gp);
-    const fe sum_g = h_add(eval_cubic(gp, fe_zero()), eval_cubic(gp, fe_one()));
-    T.add_scalar(sum_g);
-    const fe rho = T.challenge_scalar();
-    fe saved = h_mul(rho, sum_g);
-    fe* zfull[4] = {nullptr, nullptr, nullptr, nullptr};
-    fe* ztmp = nullptr;
-    if (sharded) {
-        const size_t cap = G * SHARD_MIN_LOCAL;
-        for (int q = 0; q < 4; q++) {
-            ALLOC(zf, cap);
-            zfull[q] = zf;
-        }
-        ALLOC(zt, cap);
-        ztmp = zt;
+struct ZkRounds {
+    Proof& pf;
+    pk_ctx* ctx;
+    fe** z;
+    size_t len;
+    bool sharded;
+    const fe* r;
+    const size_t M;  // the tables' length at round 0: level E_t of z[3] starts at M - (M >> t)
+    fe rho, saved;   // the blinding's weight; the running claim
+    fe* zfull[4];    // sharded: where the gathered arrays go, and the gather's scratch
+    fe* ztmp;
+    fe gp[4];        // the blinding polynomial's coefficients of the round
+    uint64_t P[4];   // P_t = prod_{k<t} eq(r_k, alpha_k)
+
+    int nsums(unsigned) const { return 3; }
+    int launch(unsigned t, const uint64_t* fold, unsigned gate_seq, unsigned* red_seq) {  // in place; the level E_t or the eq array
+        CK(sumcheck_cubic_launch(ctx, U(z[0]), U(z[1]), U(z[2]), r ? CubicWeight::Level : CubicWeight::EqArray, U(z[3] + (r ? M - (M >> t) : 0)), len, fold,
+                                 gate_seq, red_seq));
+        if (fold || gate_seq) len /= 2;
+        return PK_OK;
     }
-    const bool pipelined = ctx->latency_mode && G == 1 && m_0 >= 2;
-    unsigned red_cur = 0, red_next = 0;
-    if (pipelined) CK(launch(0, len, nullptr, 0, &red_cur));
-    alpha.reserve(m_0);
-    for (unsigned t = 0; t < m_0; t++) {  // the hot loop, whir_r1cs.rs:280-345; the same steps in the same order as WhirProver::sumcheck_rounds
-        PendingGate gate(ctx);
-        // pipelined: what consumes this round's challenge -- the next round (folding first, in place); there is no closing fold -- goes into the queue, gated
-        const bool more = t + 1 < m_0;
-        if (pipelined && more) {
-            gate.arm(sumcheck_gate_next(ctx));
-            CK(launch(t + 1, len, nullptr, gate.seq, &red_next));
-            len /= 2;
+    bool closing_fold() const { return false; }
+    int fold(const uint64_t*, unsigned) { return PK_OK; }
+    void meanwhile(unsigned t) { blinding_coefficients_for_round(pf.g_univ, t, pf.alpha.data(), gp); }
+    int before_sync_launch() {
+        if (!sharded || len > SHARD_MIN_LOCAL) return PK_OK;
+        for (int q = 0; q < 4; q++) {  // short shares: gather, re-interleave, finish replicated
+            CK(gather_strided(ctx, z[q], len, ztmp, zfull[q]));
+            z[q] = zfull[q];
         }
-        // the round's blinding coefficients depend only on the earlier challenges: in latency mode computed while the kernel runs
-        blinding_coefficients_for_round(g_univ, t, alpha.data(), gp);
-        uint64_t out[12], f[4];
-        if (pipelined) {
-            CK(sumcheck_collect_spin(ctx, 3, red_cur, out));
-            red_cur = red_next;
-        } else {
-            if (sharded && len <= SHARD_MIN_LOCAL) {  // short shares: gather, re-interleave, finish replicated
-                for (int q = 0; q < 4; q++) {
-                    CK(gather_strided(ctx, z[q], len, ztmp, zfull[q]));
-                    z[q] = zfull[q];
-                }
-                len *= G;
-                sharded = false;
-            }
-            Across ac(ctx, sharded);  // sharded: the three evaluations are sums over the ranks' shares
-            CK(ac.rc);
-            if (t) h_store(f, alpha.back());
-            unsigned seq = 0;
-            CK(launch(t, len, t ? f : nullptr, 0, &seq));
-            CK(sumcheck_collect(ctx, 3, out));
-            if (t) len /= 2;
-        }
-        if (split) sumcheck_spliteq_correct(P, U(r + t), out);
-        fe msg[4];
+        len *= pf.G;
+        sharded = false;
+        return PK_OK;
+    }
+    unsigned message(unsigned t, uint64_t out[12], fe msg[4]) {
+        if (r) sumcheck_spliteq_correct(P, U(r + t), out);
         zk_round_message(out, gp, rho, saved, msg);
-        T.add_scalars(msg, 4);
-        const fe a = T.challenge_scalar();
-        gate.publish(a);
-        alpha.push_back(a);
-        if (split) {
+        return 4;
+    }
+    void record(unsigned t, const fe* msg, const fe& a) {
+        pf.alpha.push_back(a);
+        if (r) {
             uint64_t aw[4];
             h_store(aw, a);
             sumcheck_spliteq_advance(P, U(r + t), aw);
         }
         saved = eval_cubic(msg, a);
     }
-    return PK_OK;
+};
+int Proof::zk_rounds(fe* z[4], size_t len, bool sharded, const fe* r) {
+    const unsigned m_0 = s->m_0;
+    // sum_over_hypercube (whir_r1cs.rs:172-180)
+    fe gp[4];
+    blinding_coefficients_for_round(g_univ, 0, nullptr, gp);
+    const fe sum_g = h_add(eval_cubic(gp, fe_zero()), eval_cubic(gp, fe_one()));
+    T.add_scalar(sum_g);
+    const fe rho = T.challenge_scalar();
+    ZkRounds R{*this, ctx, z, len, sharded, r, len, rho, h_mul(rho, sum_g), {}, nullptr, {}, {}};
+    h_store(R.P, fe_one());
+    if (sharded) {
+        const size_t cap = G * SHARD_MIN_LOCAL;
+        for (int q = 0; q < 4; q++) {
+            ALLOC(zf, cap);
+            R.zfull[q] = zf;
+        }
+        ALLOC(zt, cap);
+        R.ztmp = zt;
+    }
+    alpha.reserve(m_0);
+    return sumcheck_round_loop(ctx, T, m_0, ctx->latency_mode && G == 1 && m_0 >= 2, R);
 }
 
 // --- statement over the blinding commitment: weight = expand_powers(alpha) zero-extended (whir_r1cs.rs:347-366,371-380), and its

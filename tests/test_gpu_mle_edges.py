@@ -2,7 +2,7 @@
 
 test_gpu_mle.py is the parity suite on uniformly random inputs in plain mode.  This file goes where that one does not: both grid
 rules of the reduction (plain and latency mode) on both sides of each of their boundaries, the entry points that have no C ABI
-(through tools/probes), Horner above 2^21 coefficients, the largest addends the accumulating kernels can be given, challenges
+(through tools/probes: sumcheck_cubic_launch with the eq array as the weight, sumcheck_quadratic_launch), Horner above 2^21 coefficients, the largest addends the accumulating kernels can be given, challenges
 0, 1 and -1, and to_coeffs / to_evals compared at every index up to 22 variables.  References are Python-int definitions and closed
 forms (tests/mle_edge_refs.py, checked on the CPU by test_mle_edge_refs_host.py); the C oracle where the size needs it."""
 import ctypes as C

@@ -453,12 +453,15 @@ def test_prove_under_a_caller_supplied_io_pattern(ctx, oracle):
     r1cs.close()
 
 
-@pytest.mark.parametrize("m,m_0,nc,n_in,pow_bits", [(9, 7, 100, 60, 5.0), (12, 9, 500, 700, 4.0), (17, 16, 60000, 5000, 8.0)])
+@pytest.mark.parametrize("m,m_0,nc,n_in,pow_bits",
+                         [(9, 7, 100, 60, 5.0), (12, 9, 500, 700, 4.0), (17, 16, 60000, 5000, 8.0), (18, 17, 60000, 5000, 8.0)])
 def test_latency_mode_gives_the_same_transcript(oracle, m, m_0, nc, n_in, pow_bits):
     """pk_ctx_set_latency_mode: every sumcheck round (20 cubic ones at the bench size, 4 per WHIR round) is enqueued one ahead,
     gated on a word of the pinned page the host writes once it has squeezed the challenge.  Same kernels, same challenges:
     the transcript must be byte for byte the one the plain mode writes -- seeded and, with both modes on one key, for fresh
-    randomness too -- and the verifier accepts it; switching the mode off again restores the plain path."""
+    randomness too -- and the verifier accepts it; switching the mode off again restores the plain path.  m_0 = 17 is the smallest
+    size at which a gated folding cubic round takes the lane-per-pair kernel (round 1 has 2^15 pairs; at m_0 = 16 it has 2^14 =
+    SMALL_ROUND_PAIRS and stays in the eight-lane kernel), with the same statement as the row before it."""
     import provekit_amd
     import verifier as V
     from provekit_amd.scheme import WhirConfig, WhirR1CSScheme, blinding_config_for

@@ -1,4 +1,6 @@
-"""GPU: the sumcheck routes that leave out redundant work (csrc/mle.hip), bit-exact against the routes they replace.
+"""GPU: the sumcheck routes that leave out redundant work, bit-exact against the routes they replace.  In csrc/mle.hip the two cubic
+routes are the two weight policies of one round body (cubic_round_wide, and cubic_round_small for few pairs): CubicWeight::Level
+against CubicWeight::EqArray, both behind sumcheck_cubic_launch; the two- and three-sum quadratic routes are the NS of one kernel.
 
   * suffix equality tables: every level E_i = eq(r[i+1 .. n), .) against oracle/pyref.py's eq table;
   * the cubic round without the eq array (a, b, c folded, one level entry per pair, three host scalars) against
@@ -23,7 +25,7 @@ import pyref as pr  # noqa: E402
 pytestmark = pytest.mark.gpu
 P = E.P
 HALF = pow(2, -1, P) * E.R % P  # stored 1/2
-SMALL_ROUND_PAIRS = 16384  # mle.hip: up to this many pairs a folding cubic round (any quadratic round) spreads a pair over several lanes
+SMALL_ROUND_PAIRS = 16384  # mle.hip (sumcheck_cubic_launch, sumcheck_quadratic_launch): up to this many pairs a folding cubic round (any quadratic round) spreads a pair over several lanes
 
 
 def rnd(n, seed):

@@ -926,7 +926,7 @@ int pk_probe_fold_pairs2(pk_ctx* ctx, const uint64_t* d_v0, uint64_t* d_out0, co
 int pk_probe_sumcheck_cubic_launch(pk_ctx* ctx, uint64_t* d_a, uint64_t* d_b, uint64_t* d_c, uint64_t* d_eq, size_t len, const uint64_t* fold_or_null,
                                    unsigned* red_seq_out) {
     PK_ENTER(ctx);
-    return sumcheck_cubic_launch(ctx, d_a, d_b, d_c, d_eq, len, fold_or_null, 0, red_seq_out);
+    return sumcheck_cubic_launch(ctx, d_a, d_b, d_c, CubicWeight::EqArray, d_eq, len, fold_or_null, 0, red_seq_out);
 }
 int pk_probe_sumcheck_quadratic_launch(pk_ctx* ctx, const uint64_t* d_f, const uint64_t* d_w, size_t len, const uint64_t* fold_or_null,
                                        uint64_t* d_f_out, uint64_t* d_w_out, unsigned* red_seq_out) {
