@@ -77,6 +77,15 @@ SIGNATURES = {
     "pk_probe_grandproduct_set_knobs": (C.c_int, [vp, C.c_uint, C.c_uint]),
     "pk_probe_grandproduct_profile": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "pk_probe_multiset_inner": (vp, [vp]),
+    # libprovekit_fracsum.so's tree, lookup-leaf and combine kernels with their layers per launch and grid (tools/probes/fracsum.hip);
+    "pk_probe_fracsum_tree": (C.c_int, [vp, C.c_uint, vp, vp, vp, vp, C.c_uint, C.c_uint, C.POINTER(C.c_float)]),
+    "pk_probe_fracsum_lookup_leaf": (C.c_int, [vp, C.c_uint, vp, vp, vp, vp, vp, vp, C.c_uint, C.c_uint, C.POINTER(C.c_float)]),
+    "pk_probe_fracsum_combine": (C.c_int, [vp, sz, vp, vp, vp, vp, C.c_uint, C.POINTER(C.c_float)]),
+    "pk_probe_fracsum_default_layers": (C.c_uint, []),
+    # a pkf_prover's two knobs and the phases of its last proof; the pkf_prover of a lookup prover's side
+    "pk_probe_fracsum_set_knobs": (C.c_int, [vp, C.c_uint, C.c_uint]),
+    "pk_probe_fracsum_profile": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "pk_probe_fracsum_lookup_side": (vp, [vp, C.c_int]),
     # csrc/witness.hip's thresholds and the shape of a levelled builder list (tools/probes/witness.hip): host only
     "pk_probe_witness_narrow": (C.c_uint, []),
     "pk_probe_witness_sum_heavy": (C.c_uint, []),

@@ -170,6 +170,28 @@ int pk_probe_grandproduct_set_knobs(struct pkg_prover *p, unsigned layers, unsig
 int pk_probe_grandproduct_profile(const struct pkg_prover *p, double *tree_ms, double *layer_ms28);
 struct pkg_prover *pk_probe_multiset_inner(struct pkg_multiset_prover *p);
 
+/* libprovekit_fracsum.so's kernels by themselves (csrc/fracsum/kernels.hpp) with the two knobs its C ABI does not carry: layers per
+ * launch of frac_tree_kernel / lookup_leaf_kernel (1 .. 3; 0: the library's value, pk_probe_fracsum_default_layers) and the grid
+ * (1 .. 1024; 0: one lane per index).  No bit of any layer depends on either (tests/test_gpu_fracsum.py).  d_p (NULL: unit
+ * numerators), d_q, d_table, d_m (NULL: unit), d_leaf, d_ptree, d_qtree: 2^n elements; alpha, lambda: one host element each;
+ * pk_probe_fracsum_combine: d_u[x] = d_pR[x] (NULL: 1) + lambda d_qR[x] for x < count.  *ms: the launches' device time.  Blocking. */
+int pk_probe_fracsum_tree(pk_ctx *ctx, unsigned n, const uint64_t *d_p_or_null, const uint64_t *d_q, uint64_t *d_ptree, uint64_t *d_qtree,
+                          unsigned layers, unsigned grid, float *ms);
+int pk_probe_fracsum_lookup_leaf(pk_ctx *ctx, unsigned n, const uint64_t *d_table, const uint64_t *d_m_or_null, const uint64_t *alpha,
+                                 uint64_t *d_leaf, uint64_t *d_ptree, uint64_t *d_qtree, unsigned layers, unsigned grid, float *ms);
+int pk_probe_fracsum_combine(pk_ctx *ctx, size_t count, const uint64_t *d_pR_or_null, const uint64_t *d_qR, const uint64_t *lambda, uint64_t *d_u,
+                             unsigned grid, float *ms);
+unsigned pk_probe_fracsum_default_layers(void);
+/* A pkf_prover's test and benchmark knobs (csrc/fracsum/prover.hpp).  Host only.  pk_probe_fracsum_set_knobs: the same two knobs for
+ * the prover's proofs from the next call on.  pk_probe_fracsum_profile: in milliseconds, the last proof's tree phase and, for
+ * 1 <= d < n, combine_ms28[d] layer d's combine pass in device time (events around their launches), and layer_ms28[d] layer d's
+ * pks_prove in host time; what has not run reads 0.  pk_probe_fracsum_lookup_side: the pkf_prover of a lookup prover's side (PKF_SIDE_*). */
+struct pkf_prover;
+struct pkf_lookup_prover;
+int pk_probe_fracsum_set_knobs(struct pkf_prover *p, unsigned layers, unsigned grid);
+int pk_probe_fracsum_profile(const struct pkf_prover *p, double *tree_ms, double *combine_ms28, double *layer_ms28);
+struct pkf_prover *pk_probe_fracsum_lookup_side(struct pkf_lookup_prover *p, int side);
+
 /* csrc/witness.hip's thresholds (csrc/witness_shape.hpp) and the shape of a levelled builder list (witness.hip here), for
  * tests/test_witness_edge_cases_host.py and tests/test_gpu_witness_edges.py.  Host only.  pk_probe_witness_phases: *n_phases = the
  * phases of postcard(Vec<WitnessBuilder>) after levelling (two per level); with cap >= *n_phases, widths[ph] = the items of phase
