@@ -78,6 +78,30 @@ int eval_univariate_multi(pk_ctx* ctx, const uint64_t* const* d_polys, unsigned 
 // statement's sums run on a side stream underneath the blinding WHIR proof)
 int dot_rows(pk_ctx* ctx, const uint64_t* d_w, size_t row_stride, unsigned nrows, const uint64_t* d_f, const uint64_t* d_g, size_t n, uint64_t* out,
              bool defer = false);
+// the same against the equality table of `point` (n_vars host elements, eval_eq's order) over the rows' first n entries, nrows = 1 or 3:
+// out[4 * k] = <row k, eq(point, .)>.  The table is never written: the lane forms each entry from the point's two half tables.
+int dot_rows_eq(pk_ctx* ctx, const uint64_t* d_w, size_t row_stride, unsigned nrows, const uint64_t* point, unsigned n_vars, size_t n, uint64_t* out);
+// Round 0 of a quadratic sumcheck (no fold) in the launch that forms its tables p and w, n entries each (a power of two >= 2):
+//   the opening's first launch: p = e0 + beta e1;  w = (overwrite ? 0 : w) + sum_j scales[j] eq(points[j], .) + sum_k row_scales[k] row_k, row k at
+//     d_rows + k * row_stride, nrows = 1 or 3 rows of row_len <= n leading entries;  nsums = 2 or 3
+//   a round's new weights:      d_e0 = null, nrows = 0: p stands;  w as above without rows;  nsums = 3
+// points (q x log2 n), scales, beta, row_scales: host.  p, w and the sums carry the bits pk_eq_accumulate, pk_fe_axpy / axpy3, lincomb2 and
+// sumcheck_quadratic_launch (no fold) leave.  grid: 0, or a cap on the workgroups (tests).  Launch only, as sumcheck_quadratic_launch.
+struct opening_first {
+    const uint64_t *d_e0, *d_e1, *beta;
+    uint64_t *d_p, *d_w;
+    size_t n;
+    const uint64_t *points, *scales;
+    unsigned q;
+    int overwrite;
+    const uint64_t* d_rows;
+    size_t row_stride;
+    unsigned nrows;
+    size_t row_len;
+    const uint64_t* row_scales;
+    int nsums;
+};
+int opening_first_launch(pk_ctx* ctx, const opening_first& a, unsigned grid, unsigned* red_seq_out);
 int lincomb2(pk_ctx* ctx, uint64_t* d_out, const uint64_t* d_a, const uint64_t* beta, const uint64_t* d_b, size_t n);  // out = a + beta * b
 // out0 = a0 + beta * b0 over n0 entries and out1 = a1 + beta * b1 over n1 in one launch (a batch of two: coefficient and evaluation tables)
 int lincomb2_pair(pk_ctx* ctx, uint64_t* d_out0, const uint64_t* d_a0, const uint64_t* d_b0, size_t n0, uint64_t* d_out1, const uint64_t* d_a1,

@@ -416,6 +416,88 @@ __global__ __launch_bounds__(RED_THREADS) void sumcheck_quadratic_kernel(const f
     }
     grid_finish_fe<NS>(acc, red);
 }
+// The round-0 launch of a quadratic sumcheck whose tables are still to be formed: one lane per adjacent pair (2i, 2i + 1) -- the pair the
+// round sums over, and the pair eq_accumulate_kernel shares a high half-table entry across -- makes the pair's entries of p and w where
+// they are first read, stores them and adds the pair's terms to the round's sums.  What is formed is chosen by flags; one body:
+//   COMBINE    p = e0 + beta e1 (lincomb_kernel's expression), stored; else p stands as it is and is only read
+//   q points   w = (overwrite ? 0 : w) + sum_j hi_j lo_j over the half tables (eq_accumulate_kernel's pair loop), stored
+//   NR rows    below row_len, w += g_0 r_0 (axpy_kernel's expression) or g_0 r_0 + g_1 r_1 + g_2 r_2 (axpy3_kernel's)
+// Every step gives the reduced representative, so p, w and the sums carry the bits the launches it replaces leave: eq_accumulate_kernel,
+// axpy_kernel / axpy3_kernel, lincomb_kernel and sumcheck_quadratic_kernel<false, NS>.  n >= 2 entries, so nlo >= 1.
+struct fe3_arg {
+    fe_arg g[3];
+};
+struct first_rows {
+    const fe* rows;  // row k at rows + k * stride
+    size_t stride, len;
+    fe3_arg g;
+};
+template <int NR>
+__device__ __forceinline__ fe first_rows_term(const first_rows& R, size_t i) {
+    static_assert(NR == 1 || NR == 3, "one row or three");
+    if constexpr (NR == 1) {
+        return fe_mulx(from_arg(R.g.g[0]), fe_load(R.rows + i));
+    } else {
+        dot29 d;
+        dot29_init(d);
+#pragma unroll
+        for (int k = 0; k < 3; k++) dot29_add(d, unpack29<0>(fe_load(R.rows + k * R.stride + i)), unpack29<5>(from_arg(R.g.g[k])));
+        return dot29_result(d);
+    }
+}
+template <bool COMBINE, int NR, int NS>
+__global__ __launch_bounds__(RED_THREADS) void opening_first_kernel(const fe* __restrict__ e0, const fe* __restrict__ e1, fe_arg beta_arg,
+                                                                    fe* __restrict__ p, fe* __restrict__ w, size_t n, unsigned nhi, unsigned nlo,
+                                                                    unsigned q, const fe* __restrict__ tables, int overwrite, first_rows R, red_out red) {
+    PK_LATENCY_PRIO();
+    static_assert(NS == 2 || NS == 3, "two or three sums");
+    const size_t per_pt = ((size_t)1 << nhi) + ((size_t)1 << nlo);
+    const size_t mask = ((size_t)1 << nlo) - 1;
+    fe acc[NS];
+#pragma unroll
+    for (int s = 0; s < NS; s++) acc[s] = fe_zero();
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x; j < n / 2; j += stride) {
+        const size_t i = 2 * j;
+        dot29 d0, d1;
+        dot29_init(d0);
+        dot29_init(d1);
+        const fe* T = tables;
+        for (unsigned pt = 0; pt < q; pt++, T += per_pt) {
+            const fe29 h = unpack29<0>(fe_load(T + (i >> nlo)));
+            const fe* lo = T + ((size_t)1 << nhi) + (i & mask);
+            dot29_add(d0, h, unpack29<5>(fe_load(lo)));
+            dot29_add(d1, h, unpack29<5>(fe_load(lo + 1)));
+        }
+        fe w0 = dot29_result(d0), w1 = dot29_result(d1);
+        if (!overwrite) {
+            w0 = fe_add(fe_load(w + i), w0);
+            w1 = fe_add(fe_load(w + i + 1), w1);
+        }
+        if constexpr (NR > 0) {  // a pair may straddle the rows' end
+            if (i < R.len) w0 = fe_add(w0, first_rows_term<NR>(R, i));
+            if (i + 1 < R.len) w1 = fe_add(w1, first_rows_term<NR>(R, i + 1));
+        }
+        fe_store(w + i, w0);
+        fe_store(w + i + 1, w1);
+        fe f0, f1;
+        if constexpr (COMBINE) {
+            const fe beta = from_arg(beta_arg);
+            f0 = fe_add(fe_load(e0 + i), fe_mulx(beta, fe_load(e1 + i)));
+            f1 = fe_add(fe_load(e0 + i + 1), fe_mulx(beta, fe_load(e1 + i + 1)));
+            fe_store(p + i, f0);
+            fe_store(p + i + 1, f1);
+        } else {
+            f0 = fe_load(p + i);
+            f1 = fe_load(p + i + 1);
+        }
+        acc[0] = fe_add(acc[0], fe_mulx(f0, w0));
+        if (NS == 3) acc[1] = fe_add(acc[1], fe_mulx(f1, w1));
+        acc[NS - 1] = fe_add(acc[NS - 1], fe_mulx(fe_sub(fe_dbl(f1), f0), fe_sub(fe_dbl(w1), w0)));
+    }
+    grid_finish_fe<NS>(acc, red);
+}
+
 // ---- small rounds: the work of ONE pair spread over several lanes ------------------------------------------------------
 // Late sumcheck rounds have a handful of pairs; with a lane per pair the round is a chain of 16 (cubic, folding) or 7
 // (quadratic, folding) dependent modular multiplications on one lane of one wavefront -- ~1 us each -- and the kernel holds a
@@ -633,16 +715,21 @@ __global__ __launch_bounds__(RED_THREADS) void dot_kernel(const fe* __restrict__
 
 // NR weight rows (row k at w + k * row_stride) against f (and g): <w_k, f>, <w_k, g> for every k in ONE pass over f and g -- the
 // three statement weights of whir_r1cs.rs:382-412 share their polynomials, so this is one launch and one round trip instead of three
-template <int NR, int NV>
+// EQF: f is the equality table of ONE point that is never written out -- `f` points at the point's half tables (eq_half_tables_kernel,
+// scale one) and the lane forms f[i] = hi[i >> nlo] lo[i & mask], the reduced product eq_accumulate_kernel would have stored
+template <int NR, int NV, bool EQF = false>
 __global__ __launch_bounds__(RED_THREADS) void dot_rows_kernel(const fe* __restrict__ w, size_t row_stride, const fe* __restrict__ f,
-                                                               const fe* __restrict__ g, size_t n, red_out red) {
+                                                               const fe* __restrict__ g, size_t n, unsigned nhi, unsigned nlo, red_out red) {
     PK_LATENCY_PRIO();
+    static_assert(!EQF || NV == 1, "the equality table stands in for f alone");
     fe acc[NR * NV];
 #pragma unroll
     for (int k = 0; k < NR * NV; k++) acc[k] = fe_zero();
     const size_t stride = (size_t)gridDim.x * blockDim.x;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        const fe fi = fe_load(f + i);
+        fe fi;
+        if constexpr (EQF) fi = fe_mulx(fe_load(f + (i >> nlo)), fe_load(f + ((size_t)1 << nhi) + (i & (((size_t)1 << nlo) - 1))));
+        else fi = fe_load(f + i);
         fe gi = fi;
         if (NV == 2) gi = fe_load(g + i);
 #pragma unroll
@@ -817,9 +904,6 @@ __global__ __launch_bounds__(256) void lincomb_pair_kernel(fe* __restrict__ out0
 // y += g0 r0 + g1 r1 + g2 r2 with row k at rows + k * row_stride: one read and one write of y where three axpy launches make three,
 // and one Montgomery reduction for the three products (fe29.hpp dot29; the rows are reduced values).  Every step gives the reduced
 // representative, so y's bits are what the three launches leave.
-struct fe3_arg {
-    fe_arg g[3];
-};
 __global__ __launch_bounds__(256) void axpy3_kernel(fe* __restrict__ y, const fe* __restrict__ rows, size_t row_stride, size_t n, fe3_arg ga) {
     PK_LATENCY_PRIO();
     const fe29 g0 = unpack29<5>(from_arg(ga.g[0])), g1 = unpack29<5>(from_arg(ga.g[1])), g2 = unpack29<5>(from_arg(ga.g[2]));
@@ -1101,11 +1185,96 @@ int dot_rows(pk_ctx* ctx, const uint64_t* d_w, size_t row_stride, unsigned nrows
     {
         ProfScope prof(ctx, "dot");
         auto kernel = nv == 2 ? dot_rows_kernel<3, 2> : dot_rows_kernel<3, 1>;
-        kernel<<<blocks, RED_THREADS, 0, ctx->stream>>>((const fe*)d_w, row_stride, (const fe*)d_f, (const fe*)d_g, n, red);
+        kernel<<<blocks, RED_THREADS, 0, ctx->stream>>>((const fe*)d_w, row_stride, (const fe*)d_f, (const fe*)d_g, n, 0, 0, red);
     }
     PK_LAUNCH_CHECK(ctx);
     if (defer) return PK_OK;
     return collect_reduction(ctx, 3 * nv, out);
+}
+
+namespace {
+// the half tables of q points over n_vars variables, scaled, into the context's workspace (pk_eq_accumulate's first launch): the points
+// and scales go through the pinned mailbox, which the table kernel reads directly.  *d_tables: [pt][2^nhi hi | 2^nlo lo].
+int eq_half_tables(pk_ctx* ctx, unsigned n_vars, const uint64_t* points, const uint64_t* scales, unsigned q, unsigned* nhi_out, unsigned* nlo_out,
+                   const fe** d_tables) {
+    const unsigned nlo = (n_vars + 1) / 2, nhi = n_vars - nlo;
+    PK_REQUIRE(ctx, n_vars <= 30 && nlo <= 16, "too many variables");
+    *nhi_out = nhi;
+    *nlo_out = nlo;
+    *d_tables = nullptr;
+    if (!q) return PK_OK;
+    const size_t per_pt = ((size_t)1 << nhi) + ((size_t)1 << nlo);
+    int rc = ensure_ws(ctx, 32 * (size_t)q * per_pt + 64);
+    if (rc) return rc;
+    char* mail = nullptr;
+    rc = mail_alloc(ctx, 32 * ((size_t)q * n_vars + q), (void**)&mail);
+    if (rc) return rc;
+    fe* d_points = (fe*)mail;
+    fe* d_scales = d_points + (size_t)q * n_vars;
+    if (n_vars) memcpy(d_points, points, 32 * (size_t)q * n_vars);
+    memcpy(d_scales, scales, 32 * (size_t)q);
+    eq_half_tables_kernel<<<dim3(q, 2), 256, 0, ctx->stream>>>(d_points, d_scales, n_vars, nhi, nlo, (fe*)ctx->d_ws);
+    *d_tables = (const fe*)ctx->d_ws;
+    return PK_OK;
+}
+}  // namespace
+
+int opening_first_launch(pk_ctx* ctx, const opening_first& a, unsigned grid, unsigned* red_seq_out) {
+    PK_REQUIRE(ctx, a.d_p && a.d_w && red_seq_out && (a.nsums == 2 || a.nsums == 3), "null pointer");
+    PK_REQUIRE(ctx, is_pow2(a.n) && a.n >= 2, "size must be a power of two >= 2");
+    PK_REQUIRE(ctx, a.q == 0 || (a.points && a.scales), "null pointer");
+    const bool combine = a.d_e0 != nullptr;
+    PK_REQUIRE(ctx, !combine || (a.d_e1 && a.beta), "null pointer");
+    PK_REQUIRE(ctx, a.nrows == 0 || ((a.nrows == 1 || a.nrows == 3) && a.row_scales && (a.row_len == 0 || a.d_rows) && a.row_len <= a.n), "one row or three");
+    PK_REQUIRE(ctx, combine == (a.nrows != 0) && (combine || a.nsums == 3), "either the opening's first launch (combination and rows) or a round's (neither, three sums)");
+    unsigned nhi, nlo;
+    const fe* d_tables;
+    ProfScope prof(ctx, "opening_first");
+    int rc = eq_half_tables(ctx, ilog2(a.n), a.points, a.scales, a.q, &nhi, &nlo, &d_tables);
+    if (rc) return rc;
+    const size_t npairs = a.n / 2;
+    red_out red;
+    unsigned blocks;
+    rc = reduction_begin(ctx, npairs, &red, &blocks);
+    if (rc) return rc;
+    *red_seq_out = red.seq;
+    // eq_accumulate_kernel's grid, a lane per pair, as far as the reduction's partial sums reach: the point loop is a chain of dependent
+    // loads and products, which more pairs per lane only lengthen
+    const size_t want = (npairs + RED_THREADS - 1) / RED_THREADS;
+    blocks = (unsigned)(want < (size_t)RED_MAX_BLOCKS ? want : (size_t)RED_MAX_BLOCKS);
+    if (grid && grid < blocks) blocks = grid;
+    first_rows R{(const fe*)a.d_rows, a.row_stride, a.row_len, {}};
+    for (unsigned k = 0; k < a.nrows; k++) R.g.g[k] = to_arg(a.row_scales + 4 * k);
+    using kernel_t = void (*)(const fe*, const fe*, fe_arg, fe*, fe*, size_t, unsigned, unsigned, unsigned, const fe*, int, first_rows, red_out);
+    kernel_t kernel = opening_first_kernel<false, 0, 3>;
+    if (combine && a.nrows == 1) kernel = a.nsums == 2 ? opening_first_kernel<true, 1, 2> : opening_first_kernel<true, 1, 3>;
+    if (combine && a.nrows == 3) kernel = a.nsums == 2 ? opening_first_kernel<true, 3, 2> : opening_first_kernel<true, 3, 3>;
+    kernel<<<blocks, RED_THREADS, 0, ctx->stream>>>((const fe*)a.d_e0, (const fe*)a.d_e1, combine ? to_arg(a.beta) : fe_arg{}, (fe*)a.d_p, (fe*)a.d_w, a.n,
+                                                    nhi, nlo, a.q, d_tables, a.overwrite, R, red);
+    PK_LAUNCH_CHECK(ctx);
+    return PK_OK;
+}
+
+int dot_rows_eq(pk_ctx* ctx, const uint64_t* d_w, size_t row_stride, unsigned nrows, const uint64_t* point, unsigned n_vars, size_t n, uint64_t* out) {
+    PK_REQUIRE(ctx, (nrows == 1 || nrows == 3) && out && point && (n == 0 || d_w), "one weight row or three");
+    PK_REQUIRE(ctx, n <= ((size_t)1 << n_vars), "rows longer than the table");
+    if (n == 0) return reduce_empty(ctx, (int)nrows, out);
+    static const uint64_t one[4] = {0xac96341c4ffffffbULL, 0x36fc76959f60cd29ULL, 0x666ea36f7879462eULL, 0x0e0a77c19a07df2fULL};
+    unsigned nhi, nlo;
+    const fe* d_tables;
+    int rc = eq_half_tables(ctx, n_vars, point, one, 1, &nhi, &nlo, &d_tables);
+    if (rc) return rc;
+    red_out red;
+    unsigned blocks;
+    rc = reduction_begin(ctx, n, &red, &blocks);
+    if (rc) return rc;
+    {
+        ProfScope prof(ctx, "dot");
+        auto kernel = nrows == 3 ? dot_rows_kernel<3, 1, true> : dot_rows_kernel<1, 1, true>;
+        kernel<<<blocks, RED_THREADS, 0, ctx->stream>>>((const fe*)d_w, row_stride, d_tables, nullptr, n, nhi, nlo, red);
+    }
+    PK_LAUNCH_CHECK(ctx);
+    return collect_reduction(ctx, (int)nrows, out);
 }
 
 }  // namespace pk
@@ -1142,24 +1311,13 @@ int pk_eq_accumulate(pk_ctx* ctx, uint64_t* d_w, unsigned n_vars, const uint64_t
         if (overwrite) PK_HIP(ctx, hipMemsetAsync(d_w, 0, 32 * n, ctx->stream));
         return PK_OK;
     }
-    const unsigned nlo = (n_vars + 1) / 2, nhi = n_vars - nlo;
-    const size_t per_pt = ((size_t)1 << nhi) + ((size_t)1 << nlo);
-    // tables use the context workspace; stream order keeps them clear of earlier kernels (NTT scratch).  The points and
-    // scales go through the pinned mailbox, which the table kernel reads directly (no copy operation).
-    int rc = ensure_ws(ctx, 32 * (size_t)q * per_pt + 64);
-    if (rc) return rc;
-    PK_REQUIRE(ctx, nlo <= 16, "too many variables");
-    char* mail = nullptr;
-    rc = mail_alloc(ctx, 32 * ((size_t)q * n_vars + q), (void**)&mail);
-    if (rc) return rc;
-    fe* d_points = (fe*)mail;
-    fe* d_scales = d_points + (size_t)q * n_vars;
-    fe* d_tables = (fe*)ctx->d_ws;
-    if (n_vars) memcpy(d_points, points, 32 * (size_t)q * n_vars);
-    memcpy(d_scales, scales, 32 * (size_t)q);
+    // tables use the context workspace; stream order keeps them clear of earlier kernels (NTT scratch)
+    unsigned nhi, nlo;
+    const fe* d_tables;
     {
         ProfScope prof(ctx, "eq_accumulate");
-        eq_half_tables_kernel<<<dim3(q, 2), 256, 0, ctx->stream>>>(d_points, d_scales, n_vars, nhi, nlo, d_tables);
+        int rc = eq_half_tables(ctx, n_vars, points, scales, q, &nhi, &nlo, &d_tables);
+        if (rc) return rc;
         eq_accumulate_kernel<<<grid_for(ctx, nlo ? (n + 1) / 2 : n, 256), 256, 0, ctx->stream>>>((fe*)d_w, n, nhi, nlo, q, d_tables, overwrite);
     }
     PK_LAUNCH_CHECK(ctx);

@@ -403,10 +403,15 @@ struct WhirProver {
     // equality weights of the univariate points zs (expand_from_univariate; variable 0 <-> the top index bit), scaled by 1, gamma,
     // gamma^2, ... and accumulated into a weight table; *next = the following power of gamma.  The whole table, or -- sharded -- this
     // rank's block, whose top lgG index bits are the rank: that factor of eq goes into the scale and the table is built over the rest.
-    int eq_weights(fe* dst, unsigned nv, const std::vector<fe>& zs, const fe& gamma, int overwrite, fe* next) {
+    // defer: the accumulation is left to round 0's own launch (launch(0), mle.hip opening_first_launch), which needs w's pairs anyway
+    int eq_weights(fe* dst, unsigned nv, const std::vector<fe>& zs, const fe& gamma, int overwrite, fe* next, bool defer = false) {
         const size_t q = zs.size();
         const unsigned lg = sharded ? lgG : 0, nl = nv - lg;
-        std::vector<fe> x(nv ? nv : 1), pts(q * (nl ? nl : 1)), scales(q ? q : 1);
+        std::vector<fe> x(nv ? nv : 1);
+        std::vector<fe>& pts = first.pts;  // they outlive this call when the launch is deferred
+        std::vector<fe>& scales = first.scales;
+        pts.assign(q * (nl ? nl : 1), fe_zero());
+        scales.assign(q ? q : 1, fe_zero());
         fe g = fe_one();
         for (size_t j = 0; j < q; j++) {
             expand_from_univariate(zs[j], nv, x.data());
@@ -415,8 +420,25 @@ struct WhirProver {
             g = h_mul(g, gamma);
         }
         *next = g;
-        return pk_eq_accumulate(ctx, U(dst), nl, (const uint64_t*)pts.data(), (const uint64_t*)scales.data(), (unsigned)q, overwrite);
+        if (!defer) return pk_eq_accumulate(ctx, U(dst), nl, (const uint64_t*)pts.data(), (const uint64_t*)scales.data(), (unsigned)q, overwrite);
+        first.a = opening_first{};
+        first.a.d_w = U(dst);
+        first.a.n = (size_t)1 << nl;
+        first.a.points = (const uint64_t*)pts.data();
+        first.a.scales = (const uint64_t*)scales.data();
+        first.a.q = (unsigned)q;
+        first.a.overwrite = overwrite;
+        first.pending = true;
+        return PK_OK;
     }
+    // Round 0's tables while they are still to be formed: the equality weights (eq_weights, deferred) and, in the opening's first launch,
+    // the batch combination and the statement rows (start).  launch(0) forms them in the round's own kernel.
+    struct First {
+        bool pending = false;
+        opening_first a{};
+        std::vector<fe> pts, scales;
+        uint64_t beta[4], row_scales[12];
+    } first;
 
     void flip() {
         cur = 1 - cur;
@@ -437,7 +459,13 @@ struct WhirProver {
     // what sumcheck_round_loop asks of its sumcheck
     int ns0 = 3;  // sums of round 0; the later rounds always have their claim
     int nsums(unsigned t) const { return t ? 2 : ns0; }
-    int launch(unsigned t, const uint64_t* fold, unsigned gate_seq, unsigned* red_seq) {  // round 0 folds nothing, writes nothing
+    int launch(unsigned t, const uint64_t* fold, unsigned gate_seq, unsigned* red_seq) {  // round 0 folds nothing; it writes what is pending
+        if (first.pending) {  // only ever ahead of a round 0
+            first.pending = false;
+            first.a.d_p = U(bp[cur]);
+            first.a.nsums = nsums(t);
+            return opening_first_launch(ctx, first.a, 0, red_seq);
+        }
         CK(sumcheck_quadratic_launch(ctx, U(bp[cur]), U(bw[cur]), len, fold, gate_seq, U(bp[1 - cur]), U(bw[1 - cur]), nsums(t), red_seq));
         if (fold || gate_seq) flip();
         return PK_OK;
@@ -494,7 +522,14 @@ struct WhirProver {
         bool have_evals = true;
         for (unsigned b = 0; b < C.batch; b++) have_evals = have_evals && C.evals[b] != nullptr;
         const bool pair = have_evals && C.batch == 2;
-        if (pair) {  // the coefficient and the evaluation combination of a batch of two in one launch
+        // The opening's first launch (mle.hip opening_first_launch): p0, w0 and round 0's sums from one pass over the two evaluation tables
+        // and the statement rows.  Everything else -- a rank's block, another batch, no tables, rows it does not take -- keeps the sequence below.
+        const bool rows3 = rows_at_equal_stride3(d_weights, weight_len, n_weights);
+        const bool fused = pair && !sharded && B0 >= 2 && k >= 1 && (rows3 || n_weights == 1) && weight_len[0] <= B0;
+        if (fused) {
+            h_store(first.beta, C.beta);
+            CK(lincomb2(ctx, U(d_c), U(C.polys[0]), first.beta, U(C.polys[1]), N));
+        } else if (pair) {  // the coefficient and the evaluation combination of a batch of two in one launch
             uint64_t s[4];
             h_store(s, C.beta);
             CK(lincomb2_pair(ctx, U(d_c), U(C.polys[0]), U(C.polys[1]), N, U(p0), U(C.evals[0] + off0), U(C.evals[1] + off0), B0, s));
@@ -513,7 +548,7 @@ struct WhirProver {
         // initial combination randomness; weights = sum gamma^i w_i over [OOD constraints..., statement weights...]
         const fe gamma = T.challenge_scalar();
         fe g;
-        CK(eq_weights(w0, n, C.ood_points, gamma, /*overwrite=*/1, &g));
+        CK(eq_weights(w0, n, C.ood_points, gamma, /*overwrite=*/1, &g, /*defer=*/fused));
         // <p, w> of the tables just built, from values the transcript holds: an OOD constraint's sum is its answer, a statement weight's its claimed sum
         auto batched = [&](const fe* v, size_t step) {  // sum_b beta^b v[b * step]
             fe acc = v[0], bb = C.beta;
@@ -525,8 +560,18 @@ struct WhirProver {
         fe gq = fe_one();
         for (size_t j = 0; j < q; j++, gq = h_mul(gq, gamma)) claim = h_add(claim, h_mul(gq, batched(&C.ood_answers[j], q)));
         have_claim = weight_sums || !n_weights;
-        const bool rows3 = rows_at_equal_stride3(d_weights, weight_len, n_weights);
-        if (rows3) {  // one read and one write of w0 instead of three
+        if (fused) {  // the rows join w0 where round 0 first reads it
+            fe g3 = g;
+            for (unsigned i = 0; i < n_weights; i++, g3 = h_mul(g3, gamma)) h_store(first.row_scales + 4 * i, g3);
+            first.a.d_e0 = U(C.evals[0]);
+            first.a.d_e1 = U(C.evals[1]);
+            first.a.beta = first.beta;
+            first.a.d_rows = U(d_weights[0]);
+            first.a.row_stride = rows3 ? (size_t)(d_weights[1] - d_weights[0]) : 0;
+            first.a.nrows = n_weights;
+            first.a.row_len = weight_len[0];
+            first.a.row_scales = first.row_scales;
+        } else if (rows3) {  // one read and one write of w0 instead of three
             uint64_t s3[12];
             fe g3 = g;
             for (int i = 0; i < 3; i++, g3 = h_mul(g3, gamma)) h_store(s3 + 4 * i, g3);
@@ -536,7 +581,7 @@ struct WhirProver {
             uint64_t s[4];
             h_store(s, g);
             const size_t cnt = in_block(weight_len[i], off0, B0);
-            if (cnt && !rows3) CK(pk_fe_axpy(ctx, U(w0), s, U(d_weights[i] + off0), cnt));
+            if (cnt && !rows3 && !fused) CK(pk_fe_axpy(ctx, U(w0), s, U(d_weights[i] + off0), cnt));
             if (weight_sums) claim = h_add(claim, h_mul(g, batched(weight_sums + (size_t)i * C.batch, 1)));
             g = h_mul(g, gamma);
         }
@@ -588,7 +633,9 @@ struct WhirProver {
             const fe gamma = T.challenge_scalar();
             for (uint64_t i : idx) zs.push_back(h_pow(exp_gen, i));
             fe g;
-            CK(eq_weights(bw[cur], nv, zs, gamma, 0, &g));
+            // not a rank's block: the round's first sumcheck launch adds them.  At every number of points: the fused kernel runs at three waves
+            // per SIMD where eq_accumulate_kernel has four, and the round of 110 points still came out ahead (EXPERIMENTS.md round 29)
+            CK(eq_weights(bw[cur], nv, zs, gamma, 0, &g, /*defer=*/!sharded && len >= 2 && k >= 1));
             have_claim = false;  // the new weights' sums include the folded polynomial at the STIR points, which the prover never evaluates
             // W3
             CK(sumcheck_rounds(k));
@@ -630,27 +677,33 @@ struct WhirProver {
         if (!n_weights) return PK_OK;
         std::vector<fe> point(all_r.rbegin(), all_r.rend());
         const bool sh = whir_sharded(ctx, n);  // the eq table and the dot products by blocks, like the weights themselves
-        ALLOC(d_eq, B0);
-        if (sh) {
-            const fe sc = eq_bits(point.data(), lgG, rank);
-            CK(pk_eq_accumulate(ctx, U(d_eq), n - lgG, (const uint64_t*)(point.data() + lgG), (const uint64_t*)&sc, 1, 1));
-        } else {
-            CK(pk_eq_table(ctx, (const uint64_t*)point.data(), n, U(d_eq)));
-        }
-        Across ac(ctx, sh);
-        CK(ac.rc);
         std::vector<fe> evals(n_weights);
         const bool rows3 = rows_at_equal_stride3(d_weights, weight_len, n_weights);
-        if (rows3) {  // the three external rows against the eq table in one pass
+        if (!sh && (rows3 || n_weights == 1)) {  // without the table: each lane forms its entries from the point's half tables
             uint64_t o[12] = {};
-            if (sh || weight_len[0])
-                CK(dot_rows(ctx, U(d_weights[0] + off0), (size_t)(d_weights[1] - d_weights[0]), 3, U(d_eq), nullptr, in_block(weight_len[0], off0, B0), o));
-            for (int i = 0; i < 3; i++) evals[i] = h_load(o + 4 * i);
+            CK(dot_rows_eq(ctx, U(d_weights[0]), rows3 ? (size_t)(d_weights[1] - d_weights[0]) : 0, n_weights, (const uint64_t*)point.data(), n,
+                           weight_len[0], o));
+            for (unsigned i = 0; i < n_weights; i++) evals[i] = h_load(o + 4 * i);
         } else {
-            for (unsigned i = 0; i < n_weights; i++) {
-                uint64_t o[4] = {};
-                if (sh || weight_len[i]) CK(pk_dot(ctx, U(d_weights[i] + off0), U(d_eq), in_block(weight_len[i], off0, B0), o));
-                evals[i] = h_load(o);
+            ALLOC(d_eq, B0);
+            if (sh) {
+                const fe sc = eq_bits(point.data(), lgG, rank);
+                CK(pk_eq_accumulate(ctx, U(d_eq), n - lgG, (const uint64_t*)(point.data() + lgG), (const uint64_t*)&sc, 1, 1));
+            } else {
+                CK(pk_eq_table(ctx, (const uint64_t*)point.data(), n, U(d_eq)));
+            }
+            Across ac(ctx, sh);
+            CK(ac.rc);
+            if (rows3) {  // the three external rows against the eq table in one pass
+                uint64_t o[12] = {};
+                CK(dot_rows(ctx, U(d_weights[0] + off0), (size_t)(d_weights[1] - d_weights[0]), 3, U(d_eq), nullptr, in_block(weight_len[0], off0, B0), o));
+                for (int i = 0; i < 3; i++) evals[i] = h_load(o + 4 * i);
+            } else {
+                for (unsigned i = 0; i < n_weights; i++) {
+                    uint64_t o[4] = {};
+                    if (sh || weight_len[i]) CK(pk_dot(ctx, U(d_weights[i] + off0), U(d_eq), in_block(weight_len[i], off0, B0), o));
+                    evals[i] = h_load(o);
+                }
             }
         }
         std::vector<uint8_t> buf;

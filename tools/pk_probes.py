@@ -42,6 +42,9 @@ SIGNATURES = {
     "pk_probe_lincomb2_pair": (C.c_int, [vp, vp, vp, vp, sz, vp, vp, vp, sz, vp]),
     "pk_probe_axpy3": (C.c_int, [vp, vp, vp, vp, sz, sz]),
     "pk_probe_to_coeffs_generated": (C.c_int, [vp, C.c_uint, vp, sz, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp]),
+    # ... and the fused steps of the WHIR opening, for tests/test_gpu_opening_fused.py
+    "pk_probe_opening_first": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_uint, vp, vp, C.c_uint, C.c_int, vp, sz, C.c_uint, sz, vp, C.c_int, C.c_uint, vp]),
+    "pk_probe_dot_rows_eq": (C.c_int, [vp, vp, sz, C.c_uint, vp, C.c_uint, sz, vp]),
     # libprovekit_whir.so's linear-statement kernels where its C ABI does not reach (tools/probes/whir_linear.hip)
     "pk_probe_whir_combine": (C.c_int, [vp, vp, sz, vp, vp, C.c_uint, C.c_int]),
     "pk_probe_whir_weighted_sums": (C.c_int, [vp, vp, C.c_uint, C.c_uint, vp, C.c_uint, C.c_uint, C.c_int, vp]),

@@ -81,6 +81,19 @@ int pk_probe_lincomb2_pair(pk_ctx *ctx, uint64_t *d_out0, const uint64_t *d_a0, 
 int pk_probe_axpy3(pk_ctx *ctx, uint64_t *d_y, const uint64_t *g3, const uint64_t *d_rows, size_t row_stride, size_t n);
 int pk_probe_to_coeffs_generated(pk_ctx *ctx, unsigned m, const uint64_t *d_wit, size_t n_wit, const uint8_t seed32[32], uint32_t stream_mask,
                                  uint32_t stream_g, uint64_t *d_f_evals, uint64_t *d_g_evals, uint64_t *d_f_coeffs, uint64_t *d_g_coeffs);
+/* ... and the fused steps of the WHIR opening, for tests/test_gpu_opening_fused.py.  pk_probe_opening_first: round 0 of a quadratic
+ * sumcheck in the launch that forms its tables (csrc/internal.hpp opening_first_launch), 2^n_vars entries, n_vars >= 1.  d_e0 != NULL: the
+ * opening's first launch -- d_p = d_e0 + beta d_e1, d_w = (overwrite ? 0 : d_w) + sum_j scales[j] eq(points[j], .) + sum_k row_scales[k] row_k
+ * with nrows = 1 or 3 rows of row_len leading entries at d_rows + k * row_stride, nsums = 2 (out = h(0), h(2)) or 3.  d_e0 == NULL: a
+ * round's new weights -- d_p is read only, no rows (nrows = 0), nsums = 3.  points (q x n_vars), scales, beta, row_scales: HOST.  grid:
+ * 0, or a cap on the workgroups.  pk_probe_dot_rows_eq: out[4 k] = <row k, eq(point, .)> over the rows' first n entries, nrows = 1 or
+ * 3, without the table (dot_rows_eq). */
+int pk_probe_opening_first(pk_ctx *ctx, const uint64_t *d_e0, const uint64_t *d_e1, const uint64_t *beta, uint64_t *d_p, uint64_t *d_w,
+                           unsigned n_vars, const uint64_t *points, const uint64_t *scales, unsigned q, int overwrite, const uint64_t *d_rows,
+                           size_t row_stride, unsigned nrows, size_t row_len, const uint64_t *row_scales, int nsums, unsigned grid,
+                           uint64_t out[12]);
+int pk_probe_dot_rows_eq(pk_ctx *ctx, const uint64_t *d_rows, size_t row_stride, unsigned nrows, const uint64_t *point, unsigned n_vars, size_t n,
+                         uint64_t *out);
 
 /* libprovekit_whir.so's linear-statement kernels (csrc/whir_pcs/linear.hip) where its C ABI does not reach, for
  * tests/test_gpu_whir_pcs_linear.py and tools/whir_pcs_linear_bench.py.  This library links libprovekit_whir.so for them.

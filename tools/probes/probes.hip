@@ -955,4 +955,20 @@ int pk_probe_to_coeffs_generated(pk_ctx* ctx, unsigned m, const uint64_t* d_wit,
     memcpy(k.k, seed32, 32);
     return to_coeffs_generated(ctx, m, d_wit, n_wit, k, stream_mask, stream_g, d_f_evals, d_g_evals, d_f_coeffs, d_g_coeffs);
 }
+int pk_probe_opening_first(pk_ctx* ctx, const uint64_t* d_e0, const uint64_t* d_e1, const uint64_t* beta, uint64_t* d_p, uint64_t* d_w, unsigned n_vars,
+                           const uint64_t* points, const uint64_t* scales, unsigned q, int overwrite, const uint64_t* d_rows, size_t row_stride,
+                           unsigned nrows, size_t row_len, const uint64_t* row_scales, int nsums, unsigned grid, uint64_t out[12]) {
+    PK_ENTER(ctx);
+    PK_REQUIRE(ctx, out && n_vars >= 1 && n_vars <= 30, "1 .. 30 variables");
+    const opening_first a{d_e0, d_e1, beta, d_p, d_w, (size_t)1 << n_vars, points, scales, q, overwrite, d_rows, row_stride, nrows, row_len, row_scales, nsums};
+    unsigned seq = 0;
+    int rc = opening_first_launch(ctx, a, grid, &seq);
+    if (rc) return rc;
+    return sumcheck_collect(ctx, nsums, out);
+}
+int pk_probe_dot_rows_eq(pk_ctx* ctx, const uint64_t* d_rows, size_t row_stride, unsigned nrows, const uint64_t* point, unsigned n_vars, size_t n,
+                         uint64_t* out) {
+    PK_ENTER(ctx);
+    return dot_rows_eq(ctx, d_rows, row_stride, nrows, point, n_vars, n, out);
+}
 }  // extern "C"
