@@ -89,6 +89,11 @@ SIGNATURES = {
     "pk_probe_fracsum_set_knobs": (C.c_int, [vp, C.c_uint, C.c_uint]),
     "pk_probe_fracsum_profile": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "pk_probe_fracsum_lookup_side": (vp, [vp, C.c_int]),
+    # libprovekit_tuplelookup.so's leaf kernel with its grid; a pkt_prover's grid knob and the phases of its last calls (tools/probes/tuplelookup.hip)
+    "pk_probe_tuple_leaves": (C.c_int, [vp, C.c_uint, C.c_uint, C.c_uint, vp, vp, vp, vp, C.c_uint, C.POINTER(C.c_float)]),
+    "pk_probe_tuple_set_grid": (C.c_int, [vp, C.c_uint]),
+    "pk_probe_tuple_profile": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "pk_probe_tuple_leaf_items": (C.c_uint, []),
     # csrc/witness.hip's thresholds and the shape of a levelled builder list (tools/probes/witness.hip): host only
     "pk_probe_witness_narrow": (C.c_uint, []),
     "pk_probe_witness_sum_heavy": (C.c_uint, []),

@@ -205,6 +205,19 @@ int pk_probe_fracsum_set_knobs(struct pkf_prover *p, unsigned layers, unsigned g
 int pk_probe_fracsum_profile(const struct pkf_prover *p, double *tree_ms, double *combine_ms28, double *layer_ms28);
 struct pkf_prover *pk_probe_fracsum_lookup_side(struct pkf_lookup_prover *p, int side);
 
+/* libprovekit_tuplelookup.so's leaf kernel by itself (csrc/tuplelookup/kernels.hpp) with the grid its C ABI does not carry (workgroups
+ * per group, 1 .. 1024; 0: the library's rule, pk_probe_tuple_leaf_items rows per lane).  No bit of the leaves depends on it
+ * (tests/test_gpu_tuplelookup.py).  d_cols: c * w device pointers on the host, as pkt_leaves; *ms: the launch's device time.  Blocking.
+ * A pkt_prover's test and benchmark knobs (csrc/tuplelookup/prover.hpp), host only: pk_probe_tuple_set_grid sets the grid of its leaf
+ * AND count kernels from the next call on; pk_probe_tuple_profile: in milliseconds, the last proof's two leaf launches and the last
+ * pkt_multiplicities' count and mont launches in device time, and side_ms2[PKT_SIDE_*] the two pkf_prove in host time. */
+struct pkt_prover;
+int pk_probe_tuple_leaves(pk_ctx *ctx, unsigned n, unsigned w, unsigned c, const uint64_t *const *d_cols, const uint64_t *alpha, const uint64_t *beta,
+                          uint64_t *d_leaf, unsigned grid, float *ms);
+int pk_probe_tuple_set_grid(struct pkt_prover *p, unsigned grid);
+int pk_probe_tuple_profile(const struct pkt_prover *p, double *leaf_ms, double *count_ms, double *side_ms2);
+unsigned pk_probe_tuple_leaf_items(void);
+
 /* csrc/witness.hip's thresholds (csrc/witness_shape.hpp) and the shape of a levelled builder list (witness.hip here), for
  * tests/test_witness_edge_cases_host.py and tests/test_gpu_witness_edges.py.  Host only.  pk_probe_witness_phases: *n_phases = the
  * phases of postcard(Vec<WitnessBuilder>) after levelling (two per level); with cap >= *n_phases, widths[ph] = the items of phase
