@@ -8,6 +8,9 @@
 //   pks_verify_asan lane <D> <lo> <hi> <coeff> <weight> <repeats>        (64 hex digits each, the raw 256-bit value, big-endian)
 //     runs lane.hpp's lane_accumulate<D, D> -- the kernel's arithmetic, compiled for the host -- `repeats` times on D tables that all hold
 //     (lo, hi), one term over all of them, and prints the D + 1 sums the same way.
+//   pks_verify_asan lanes <D> <m> <T> <weighted 0|1> <weight> <repeats> T x (<mask> <coeff>) m x (<lo> <hi>)
+//     runs lane_accumulate<D, m> for any (D, m) round.hip dispatches on the caller's terms (mask in decimal; the coefficient's kind is
+//     lane.hpp's coeff_kind of it, as the kernel's caller takes it) and per-table (lo, hi), weighted or not, and prints the same.
 //   pks_verify_asan shard <n> <world> [lone]
 //     drives shard.hpp's ownership rule and pkss_plan for tables of 2^n (n <= 20) and `world` ranks.  It marks, in exact-size heap
 //     blocks, the slot expand(y, g, r) of every rank r and compacted index y < 2^n / world -- an index outside the table is a report --
@@ -114,6 +117,43 @@ int run_lane(int argc, char** argv) {
     return 0;
 }
 
+template <int D, int M>
+void lanes(const pk::fe* lo_v, const pk::fe* hi_v, const pks::Terms& tm, bool weighted, const pk::fe& w, unsigned repeats) {
+    pk::fe lo[M], hi[M], acc[D + 1];
+    for (int j = 0; j < M; j++) lo[j] = lo_v[j], hi[j] = hi_v[j];
+    for (int k = 0; k <= D; k++) acc[k] = pk::fe_zero();
+    for (unsigned r = 0; r < repeats; r++) pks::lane_accumulate<D, M>(lo, hi, tm, weighted, w, acc);
+    for (int k = 0; k <= D; k++) print_hex(acc[k]);
+}
+
+int run_lanes(int argc, char** argv) {
+    if (argc < 8) return 2;
+    const unsigned D = (unsigned)atoi(argv[2]), m = (unsigned)atoi(argv[3]), T = (unsigned)atoi(argv[4]);
+    const bool weighted = atoi(argv[5]) != 0;
+    const unsigned repeats = (unsigned)atoi(argv[7]);
+    pk::fe w, lo[PKS_MAX_TABLES], hi[PKS_MAX_TABLES];
+    if (m < 1 || m > PKS_MAX_TABLES || T < 1 || T > PKS_MAX_TERMS || (unsigned)argc != 8 + 2 * T + 2 * m || !parse_hex(argv[6], w)) return 2;
+    pks::Terms tm;
+    memset(&tm, 0, sizeof tm);
+    tm.T = T;
+    unsigned degree = 0;
+    for (unsigned t = 0; t < T; t++) {
+        tm.masks[t] = (unsigned)atoi(argv[8 + 2 * t]);
+        if (!tm.masks[t] || tm.masks[t] >> m || !parse_hex(argv[9 + 2 * t], tm.coeff[t])) return 2;
+        tm.kind[t] = pks::coeff_kind(tm.coeff[t]);
+        const unsigned bits = (unsigned)__builtin_popcount(tm.masks[t]);
+        degree = bits > degree ? bits : degree;
+    }
+    if (degree != D) return 2;  // the kernel's caller takes D from the masks
+    for (unsigned j = 0; j < m; j++)
+        if (!parse_hex(argv[8 + 2 * T + 2 * j], lo[j]) || !parse_hex(argv[9 + 2 * T + 2 * j], hi[j])) return 2;
+#define PKS_CASE(DEG, TABLES) \
+    if (D == DEG && m == TABLES) return lanes<DEG, TABLES>(lo, hi, tm, weighted, w, repeats), 0;
+    PKS_CASE(1, 1) PKS_CASE(1, 2) PKS_CASE(1, 3) PKS_CASE(1, 4) PKS_CASE(2, 2) PKS_CASE(2, 3) PKS_CASE(2, 4) PKS_CASE(3, 3) PKS_CASE(3, 4)
+#undef PKS_CASE
+    return 2;
+}
+
 int run_shard(unsigned n, unsigned world, bool lone) {
     pks_statement st;
     memset(&st, 0, sizeof st);
@@ -160,8 +200,10 @@ int run_shard(unsigned n, unsigned world, bool lone) {
 int main(int argc, char** argv) {
     if (argc == 3 && !strcmp(argv[1], "verify")) return run_verify(argv[2]);
     if (argc >= 2 && !strcmp(argv[1], "lane")) return run_lane(argc, argv);
+    if (argc >= 2 && !strcmp(argv[1], "lanes")) return run_lanes(argc, argv);
     const bool lone = argc == 5 && !strcmp(argv[4], "lone");
     if ((argc == 4 || lone) && !strcmp(argv[1], "shard")) return run_shard((unsigned)atoi(argv[2]), (unsigned)atoi(argv[3]), lone);
-    fprintf(stderr, "usage: pks_verify_asan verify <case file> | lane <D> <lo> <hi> <coeff> <weight> <repeats> | shard <n> <world> [lone]\n");
+    fprintf(stderr, "usage: pks_verify_asan verify <case file> | lane <D> <lo> <hi> <coeff> <weight> <repeats> | "
+                    "lanes <D> <m> <T> <weighted> <weight> <repeats> T x (<mask> <coeff>) m x (<lo> <hi>) | shard <n> <world> [lone]\n");
     return 2;
 }

@@ -21,6 +21,11 @@ struct Terms {
     fe coeff[4];  // Montgomery
 };
 
+// the kind of a coefficient (Montgomery, below p), stated once for the kernel's caller (round.hip) and the sanitizer driver.  Host only
+inline unsigned coeff_kind(const fe& c) {
+    return pk::fe_eq(c, pk::fe_one()) ? COEFF_ONE : pk::fe_eq(c, pk::fe_neg(pk::fe_one())) ? COEFF_MINUS_ONE : COEFF_ANY;
+}
+
 // acc[X] += w * sum_t c_t prod_{j in S_t} f_j(X) for X = 0 .. D, f_j(X) = lo[j] + X (hi[j] - lo[j]).  weighted = false: w = 1
 template <int D, int M>
 PK_HD void lane_accumulate(const fe (&lo)[M], const fe (&hi)[M], const Terms& tm, bool weighted, const fe& w, fe (&acc)[D + 1]) {

@@ -164,11 +164,10 @@ int launch(hipStream_t stream, const pks_statement& st, const RoundTables& rt, s
     }
     Terms tm{};
     tm.T = st.T;
-    const fe one = fe_one(), minus_one = fe_neg(fe_one());
     for (unsigned t = 0; t < st.T; t++) {
         tm.masks[t] = st.masks[t];
         tm.coeff[t] = h_load(st.coeffs[t]);
-        tm.kind[t] = fe_eq(tm.coeff[t], one) ? COEFF_ONE : fe_eq(tm.coeff[t], minus_one) ? COEFF_MINUS_ONE : COEFF_ANY;
+        tm.kind[t] = coeff_kind(tm.coeff[t]);
     }
     const fe alpha = fold_or_null ? h_load(fold_or_null) : fe_zero();
     fe* const partial = (fe*)d_scratch;

@@ -30,11 +30,23 @@ SHAPES = {
     "four": (4, [(3, 0b0111), (P - 5, 0b1110), (1, 0b1001), (7, 0b0100)], True),
 }
 
+# The forms of the round kernel that the shapes above do not reach (csrc/sumcheck/round.hip dispatches on (D, m); lane.hpp on the
+# coefficient's kind): linear statements over several tables, coefficients 1, -1, 0 and others with and without tau, a mask in two
+# terms.  Kept apart: the suites over SHAPES run those six; these run where a test names FORMS
+FORMS = {
+    "lin2": (2, [(1, 0b01), (5, 0b10)], True),                                             # eq (f0 + 5 f1)
+    "lin3": (3, [(1, 0b001), (P - 1, 0b010), (7, 0b100)], False),                          # f0 - f1 + 7 f2
+    "lin4": (4, [(3, 0b0001), (1, 0b0010), (P - 1, 0b0100), (P - 2, 0b1000)], True),       # eq (3 f0 + f1 - f2 - 2 f3)
+    "lin2rep": (2, [(1, 0b01), (0, 0b10), (P - 1, 0b01), (9, 0b10)], False),               # f0 + 0 f1 - f0 + 9 f1
+    "deg3low": (3, [(P - 1, 0b111), (1, 0b011), (4, 0b100)], True),                        # eq (-a b c + a b + 4 c)
+    "pair2": (2, [(P - 1, 0b11), (1, 0b01), (1, 0b10)], False),                            # -a b + a + b
+}
+
 
 class Shape:
     def __init__(self, name, n, n_bind=0):
         self.name, self.n, self.n_bind = name, n, n_bind
-        self.m, self.terms, self.has_tau = SHAPES[name]
+        self.m, self.terms, self.has_tau = SHAPES[name] if name in SHAPES else FORMS[name]
         self.D = max(bin(mask).count("1") for _, mask in self.terms)
 
     def statement(self):
@@ -167,6 +179,26 @@ def prove(shape: Shape, tables, tau=None, bind=(), pattern=None):
     M.add(finals)
     assert M.a.done()
     return M.out, point, finals, s
+
+
+def round_values(shape: Shape, tables, tau_rest=None, fold=None):
+    """ONE round by the header's definition (pks_round): h(0) .. h(D) of the tables as they stand, or with a fold challenge
+    (h, folded tables) of the tables folded by it first.  The weight of pair x' is eq(tau_rest, x'), 1 where tau_rest is None --
+    whatever shape.has_tau says, as pks_round takes tau_rest_or_null on its own terms"""
+    f = [list(t) for t in tables]
+    if fold is not None:
+        half = len(f[0]) // 2
+        f = [[(t[x] + fold * (t[x + half] - t[x])) % P for x in range(half)] for t in f]
+    half = len(f[0]) // 2
+    assert half >= 1 and all(len(t) == 2 * half for t in f) and len(f) == shape.m
+    w = pr.eq_table(list(tau_rest)) if tau_rest is not None else [1] * half
+    assert len(w) == half
+    h = [0] * (shape.D + 1)
+    for x in range(half):
+        for X in range(shape.D + 1):
+            h[X] += w[x] * shape.terms_at([t[x] + X * (t[x + half] - t[x]) for t in f])
+    h = [v % P for v in h]
+    return h if fold is None else (h, f)
 
 
 class Rejected(Exception):

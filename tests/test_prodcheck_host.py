@@ -1,7 +1,8 @@
 """CPU: libprovekit_sumcheck.so's host side.  The header/library/binding symbol match; pks_io_pattern against the reference's pattern
 for every shape; every refusal with its reason; pks_verify on proofs the Python reference prover builds (tests/prodcheck_refs.py):
 acceptance, and every tampering with the check both verifiers must name; the kernel's lane arithmetic compiled for the host at the
-value bound; hostile framing through the sanitizer build of the host verifier (a program of its own, run as a subprocess)."""
+value bound, and for every (D, m) the round kernel dispatches with every coefficient kind (the statements of K.FORMS next to K.SHAPES;
+the catalogue is held to round.hip's dispatch list); the one-round reference the device tests use; hostile framing through the sanitizer build of the host verifier (a program of its own, run as a subprocess)."""
 import ctypes
 import os
 import re
@@ -20,7 +21,20 @@ ASAN = os.path.join(ROOT, "provekit_amd", "lib", "pks_verify_asan")
 import prodcheck_refs as K  # noqa: E402
 
 P = K.P
-SIZES = {"inner": 5, "r1cs": 6, "eval": 4, "triple": 5, "mixed": 5, "four": 6}  # a few variables each: the verifier's work is per round
+SIZES = {"inner": 5, "r1cs": 6, "eval": 4, "triple": 5, "mixed": 5, "four": 6,  # a few variables each: the verifier's work is per round
+         "lin2": 4, "lin3": 5, "lin4": 6, "lin2rep": 4, "deg3low": 6, "pair2": 5}
+ROUND_HIP = os.path.join(ROOT, "provekit_amd", "csrc", "sumcheck", "round.hip")
+EVERY_SHAPE = list(K.SHAPES) + list(K.FORMS)
+
+
+def test_the_catalogue_reaches_every_instantiation_the_round_kernel_dispatches():
+    """the (D, m) pairs of the twelve statements against the PKS_CASE uses of round.hip's launch(): an instantiation added there has no
+    statement that launches it until one is added here"""
+    dispatched = {(int(d), int(m)) for d, m in re.findall(r"PKS_CASE\((\d+),\s*(\d+)\)", open(ROUND_HIP).read())}
+    reached = {(s.D, s.m) for s in (K.Shape(name, 1) for name in EVERY_SHAPE)}
+    nine = {(1, 1), (1, 2), (1, 3), (1, 4), (2, 2), (2, 3), (2, 4), (3, 3), (3, 4)}
+    assert dispatched == nine and reached == nine, (sorted(dispatched), sorted(reached))
+    assert not set(K.SHAPES) & set(K.FORMS) and len(EVERY_SHAPE) == 12
 
 
 def test_the_header_declares_what_the_library_exports_and_the_binding_binds():
@@ -60,6 +74,23 @@ def test_io_pattern_is_the_references_for_every_shape_and_differs_between_shapes
     b = prodcheck.Statement(5, 3, [(1, 0b101), (1, 0b010)])
     pa, pb = prodcheck.io_pattern(a), prodcheck.io_pattern(b)
     assert pa != pb and pa.split(b"\0")[1:] == pb.split(b"\0")[1:]
+
+
+def test_io_pattern_is_the_references_for_the_forms_too_and_differs_between_all_twelve():
+    """a mask in two terms is spelled twice (lin2rep: masks1.2.1.2); a zero coefficient is a coefficient"""
+    from provekit_amd import prodcheck
+
+    pats = {}
+    for name in EVERY_SHAPE:
+        for n, n_bind in ((1, 0), (SIZES[name], 0), (SIZES[name], 2), (28, 16)):
+            shape = K.Shape(name, n, n_bind)
+            pat = prodcheck.io_pattern(shape.statement())
+            assert pat == shape.pattern(), (name, n, n_bind)
+            assert prodcheck.proof_bytes(shape.statement()) == shape.proof_bytes()
+            pats[(name, n, n_bind)] = pat
+    assert len(set(pats.values())) == len(pats)
+    assert pats[("lin2rep", 4, 0)].split(b"\0")[:3] == [prodcheck.LABEL + b"/n4/m2/T4/tau0/masks1.2.1.2", b"A4coefficients", b"A1sum"]
+    assert pats[("lin4", 6, 2)].split(b"\0")[1:6] == [b"A2bind", b"A6tau", b"A4coefficients", b"A1sum", b"A2round_values"]
 
 
 @pytest.mark.parametrize("stmt, reason", [
@@ -155,7 +186,12 @@ def _bump(proof, element, delta=1):
 
 @pytest.mark.parametrize("name", list(K.SHAPES))
 def test_every_tampering_is_rejected_at_the_named_check(cases, name):
-    c = cases[name]
+    every_tampering(cases[name], name)
+
+
+def every_tampering(c, name, cancelled=()):
+    """cancelled: the tables whose value the statement's terms do not depend on (none in SHAPES): a changed final value of such a table
+    is no tampering with the claim, and both verifiers must accept it"""
     n, D, m = c.shape.n, c.shape.D, c.shape.m
     for i in range(n):  # one changed value in each round: h_i(0) enters round i's own check
         res, _, _ = c.both(_bump(c.proof, 1 + i * (D + 1)))
@@ -166,7 +202,7 @@ def test_every_tampering_is_rejected_at_the_named_check(cases, name):
         assert res.check == "ROUND" and "round 1:" in res.message
         assert c.both(_bump(c.proof, 1 + (n - 1) * (D + 1) + D))[0].check == "FINAL"
     for j in range(m):
-        assert c.both(_bump(c.proof, 1 + n * (D + 1) + j))[0].check == "FINAL"
+        assert c.both(_bump(c.proof, 1 + n * (D + 1) + j))[0].check == ("NONE" if j in cancelled else "FINAL")
     # a changed s: against the expected sum, and without one against round 0
     assert c.both(expected_sum=(c.s + 1) % P)[0].check == "SUM"
     res, _, _ = c.both(_bump(c.proof, 0))
@@ -201,8 +237,82 @@ def test_every_tampering_is_rejected_at_the_named_check(cases, name):
     assert c.both(pattern=relabelled)[0].check == "ROUND"
 
 
+@pytest.fixture(scope="module")
+def form_cases():
+    return {name: Case(name) for name in K.FORMS}
+
+
+@pytest.mark.parametrize("name", list(K.FORMS))
+def test_reference_proofs_of_the_forms_are_accepted_with_the_references_point_and_finals(form_cases, name):
+    test_reference_proofs_are_accepted_with_the_references_point_and_finals(form_cases, name)
+
+
+@pytest.mark.parametrize("name", list(K.FORMS))
+def test_every_tampering_of_the_forms_is_rejected_at_the_named_check(form_cases, name):
+    """lin2rep is f0 + 0 f1 - f0 + 9 f1 = 9 f1: f0's final value enters no check, whatever it is"""
+    c = form_cases[name]
+    cancelled = (0,) if name == "lin2rep" else ()
+    for j in range(c.shape.m):  # ... which is the statement's property, not an allowance: its terms at the changed finals say so
+        changed = [(v + 1) % P if k == j else v for k, v in enumerate(c.finals)]
+        assert (c.shape.terms_at(changed) == c.shape.terms_at(c.finals)) == (j in cancelled)
+    every_tampering(c, name, cancelled)
+
+
+def _round_of(proof, D, i):
+    at = 32 * (1 + i * (D + 1))
+    return [int.from_bytes(proof[at + 32 * k : at + 32 * k + 32], "little") for k in range(D + 1)]
+
+
+@pytest.mark.parametrize("name", EVERY_SHAPE)
+def test_round_values_are_the_reference_provers_rounds_0_and_1(name):
+    """K.round_values -- the one-round reference the device tests of pks_round compare with -- against the round values inside
+    K.prove's bytes at n = 5: round 0 on the tables as they stand, round 1 after the fold by point[0], which also gives the folded tables"""
+    n = 5
+    shape = K.Shape(name, n)
+    tables = K.random_tables(shape.m, n, seed=40 + len(name))
+    tau = K.random_elements(n, seed=41) if shape.has_tau else None
+    proof, point, finals, _ = K.prove(shape, tables, tau)
+    assert K.round_values(shape, tables, tau[1:] if tau else None) == _round_of(proof, shape.D, 0)
+    h, folded = K.round_values(shape, tables, tau[2:] if tau else None, fold=point[0])
+    assert h == _round_of(proof, shape.D, 1)
+    half = 1 << (n - 1)
+    assert folded == [[(t[x] + point[0] * (t[x + half] - t[x])) % P for x in range(half)] for t in tables]
+    # ... and those are the tables the rest of the proof is about: bound by the other challenges they give the final values
+    eq_rest = K.pr.eq_table(point[1:])
+    assert finals == [sum(e * v for e, v in zip(eq_rest, t)) % P for t in folded]
+    # tau_rest None is weight 1 whatever the shape says: h(0) is then the plain sum of the terms over the lower half
+    assert K.round_values(shape, tables, None)[0] == sum(shape.terms_at([t[x] for t in tables]) for x in range(half)) % P
+
+
 def _hex(v):
     return "%064x" % v
+
+
+@pytest.mark.parametrize("name", EVERY_SHAPE)
+def test_the_lane_arithmetic_on_the_host_for_every_instantiation_and_coefficient_kind(name):
+    """lane_accumulate<D, m> of every (D, m) the kernel is instantiated for (pks_verify_asan lanes), on each statement's own masks and
+    coefficients -- their kinds taken by lane.hpp's coeff_kind, as round.hip's launch() takes them -- weighted and not, against Python
+    ints: per-table random values, and the value bound with a stepped value that wraps (every lo = p - 1 and every hi = 0, and the reverse)"""
+    assert os.path.exists(ASAN), "provekit_amd/lib/pks_verify_asan is missing: make -C provekit_amd/csrc asan"
+    env = {k: v for k, v in os.environ.items() if k != "ASAN_OPTIONS"}
+    shape = K.Shape(name, 1)
+    m, D, R, R_INV = shape.m, shape.D, K.R, K.R_INV
+    rnd = K.random_elements(2 * m + 1, seed=50 + len(name))
+    # raw 256-bit values as the lane holds them (Montgomery images): (lo per table, hi per table, weight)
+    values = [(rnd[:m], rnd[m : 2 * m], rnd[2 * m]), ([P - 1] * m, [0] * m, P - 1), ([0] * m, [P - 1] * m, P - 1)]
+    terms = [a for c, mask in shape.terms for a in (str(mask), _hex(c * R % P))]
+    for lo, hi, w in values:
+        for weighted in (True, False):
+            for repeats in (1, 3):
+                pairs = [_hex(v) for lh in zip(lo, hi) for v in lh]
+                p = subprocess.run([ASAN, "lanes", str(D), str(m), str(len(shape.terms)), str(int(weighted)), _hex(w), str(repeats)] + terms + pairs,
+                                   capture_output=True, text=True, env=env, timeout=120)
+                assert p.returncode == 0, p.stderr[-3000:]
+                got = [int(line, 16) for line in p.stdout.split()]
+                # an image x stands for x R^-1; the sums come back as images
+                weight = w * R_INV % P if weighted else 1
+                want = [repeats * weight * shape.terms_at([(a + X * (b - a)) * R_INV % P for a, b in zip(lo, hi)]) * R % P for X in range(D + 1)]
+                assert got == want, (name, lo[0], hi[0], weighted, repeats)
 
 
 @pytest.mark.parametrize("D", [1, 2, 3])
