@@ -5,28 +5,17 @@
 
 using pk::fail;
 using pk::fe;
-using pk::host_ms_since;
 
 namespace {
 
 // a prover of `stmt` with its arena, events and pks provers; the reason of a failure goes to pkf::g_error
-int make_prover(pk_ctx* ctx, const pkf_statement& stmt, std::unique_ptr<pkf_prover>& out) {
-    auto stop = [](int rc, const std::string& reason) { return pkf::g_error = reason, rc; };
-    std::unique_ptr<pkf_prover> p(new pkf_prover());  // its destructor gives back what a return or a throw below leaves behind
-    p->ctx = ctx;
+int make_prover(pk_ctx* ctx, const pkf_statement& stmt, std::unique_ptr<pkf_prover>& p) {
+    p.reset(new pkf_prover());  // its destructor gives back what a failure or a throw below leaves behind
     p->st = stmt;
     p->pattern = pkf::io_pattern(stmt);
-    void* base = nullptr;
-    if (int rc = pk_malloc(ctx, pkf::arena_bytes(stmt.n), &base)) return stop(rc, "pk_malloc of the arena failed");
-    p->arena = (uint64_t*)base;
+    auto layer_statement = [&](unsigned d) { return pkf::layer_statement(stmt, d); };
+    if (int rc = pk::gkr::make_frame(*p, ctx, pkf::arena_bytes(stmt.n), p->arena, stmt.n, layer_statement, pkf::g_error)) return rc;
     p->ptree = p->arena, p->qtree = p->ptree + 4 * pkf::tree_fes(stmt.n), p->u = p->qtree + 4 * pkf::tree_fes(stmt.n);
-    for (hipEvent_t& e : p->ev)
-        if (hipEventCreate(&e) != hipSuccess) return stop(PK_ERR_HIP, "hipEventCreate failed");
-    for (unsigned d = 1; d < stmt.n; d++) {
-        const pks_statement ps = pkf::layer_statement(stmt, d);
-        if (int rc = pks_prover_create(ctx, &ps, &p->layer[d])) return stop(rc, std::string("pks_prover_create failed: ") + pks_create_error());
-    }
-    out = std::move(p);
     return PK_OK;
 }
 
@@ -61,59 +50,43 @@ int build_lookup(pkf_prover* p, const uint64_t* d_table, const uint64_t* d_m, co
     return read_top(p, d_m, d_leaf);
 }
 
-bool is_zero(const fe& x) { return pk::fe_eq(x, pk::fe_zero()); }
+using pk::is_zero;
 
-// The protocol on the trees as they stand (build / build_lookup of the leaves (d_p, d_q)): the outer transcript and the n - 1 pks
-// proofs, into proof_out (pkf::proof_bytes(p->st) bytes).  point: n elements, the values: one each; any may be NULL.
-int chain(pkf_prover* p, const uint64_t* d_p, const uint64_t* d_q, const uint64_t* bind, uint8_t* proof_out, uint64_t* point_out, uint64_t* value_p_out,
-          uint64_t* value_q_out) {
-    const pkf_statement& st = p->st;
-    const unsigned n = st.n;
-    pk::Transcript tr(p->pattern);
-    for (unsigned i = 0; i < st.n_bind; i++) tr.add_scalar(pk::h_load(bind + 4 * i));
-    tr.add_scalars(p->top, 4);
-    for (int i = 0; i < 4; i++) {
-        const fe canon = pk::h_to_canon(p->top[i]);
-        memcpy(proof_out + 32 * i, canon.v, 32);
-    }
-    fe rho = tr.challenge_scalar();
-    fe z[PKF_MAX_VARS], r[PKF_MAX_VARS], finals[4];
-    pkf::Claims claim;
-    claim.from_top(p->top, rho);
-    claim.has_p = !(st.unit && n == 1);
-    z[0] = rho;
-    for (unsigned d = 1; d < n; d++) {
-        const fe lambda = tr.challenge_scalar(), seed = tr.challenge_scalar();
+// What the prover adds to the chain's rule (pkf::Chain, statement.hpp): layer d's combined table u_d, made on the way, its three or
+// four tables, and the combine pass's time
+struct Proving : pkf::Chain {
+    pkf_prover* p;
+    const uint64_t *d_p, *d_q;
+    Proving(pkf_prover* prover, const uint64_t* bottom_p, const uint64_t* bottom_q) : Chain(prover->st), p(prover), d_p(bottom_p), d_q(bottom_q) {}
+    int tables(unsigned d, const fe* ch, const uint64_t** out) const {
         // the children are the two halves of layer d + 1: of the caller's tables at the bottom, of the arena above it
-        const bool bottom = d + 1 == n, unit_leaves = pkf::unit_layer(st, d);
+        const bool bottom = d + 1 == s.n, unit_leaves = pkf::unit_layer(s, d);
         const size_t half = (size_t)4 << d;
         const uint64_t* const pL = bottom ? d_p : p->ptree + 2 * half;
         const uint64_t* const qL = bottom ? d_q : p->qtree + 2 * half;
         // u_d goes to the null stream, where the sumcheck library's own launches follow it: no synchronise between the two
         (void)hipEventRecord(p->ev[2], nullptr);
-        if (int rc = pkf::combine_launch(nullptr, (size_t)1 << d, unit_leaves ? nullptr : pL + half, qL + half, (const uint64_t*)lambda.v, p->u, p->grid))
+        if (int rc = pkf::combine_launch(nullptr, (size_t)1 << d, unit_leaves ? nullptr : pL + half, qL + half, (const uint64_t*)ch[0].v, p->u, p->grid))
             return fail(p, rc, "layer " + std::to_string(d) + "'s combine launch failed");
         (void)hipEventRecord(p->ev[3], nullptr);
-        const uint64_t* const with_p[4] = {pL, qL, qL + half, p->u};
-        const uint64_t* const without_p[3] = {qL, qL + half, p->u};
-        const unsigned m = pkf::layer_tables(st, d);
-        size_t part = 0;
-        const auto t0 = std::chrono::steady_clock::now();
-        if (int rc = pks_prove(p->layer[d], unit_leaves ? without_p : with_p, (const uint64_t*)z, (const uint64_t*)seed.v, proof_out + pkf::layer_at(st, d),
-                               pkf::layer_bytes(st, d), &part, (uint64_t*)r, (uint64_t*)finals))
-            return fail(p, rc, "layer " + std::to_string(d) + "'s sumcheck failed: " + pks_last_error(p->layer[d]));
-        p->prof.layer_ms[d] = host_ms_since(t0);
-        p->prof.combine_ms[d] = pk::between(p->ev[2], p->ev[3]);  // pks_prove is blocking: both events have completed
-        tr.add_scalars(finals, m);
-        rho = tr.challenge_scalar();
-        claim.step(unit_leaves, finals, lambda, rho);
-        for (unsigned i = 0; i < d; i++) z[i + 1] = r[i];
-        z[0] = rho;
+        if (!unit_leaves) *out++ = pL;
+        out[0] = qL, out[1] = qL + half, out[2] = p->u;
+        return PK_OK;
     }
-    if (!tr.finished()) return fail(p, PK_ERR_IO_PATTERN, "the transcript left its pattern: " + tr.violation());
-    if (point_out) memcpy(point_out, z, 32 * (size_t)n);
-    if (value_p_out && claim.has_p) pkf::put_fe(value_p_out, claim.cp);
-    if (value_q_out) pkf::put_fe(value_q_out, claim.cq);
+    void step(unsigned d, const fe* finals, const fe* ch, const fe& rho) {
+        p->prof.combine_ms[d] = pk::between(p->ev[2], p->ev[3]);  // pks_prove is blocking: both events have completed
+        Chain::step(d, finals, ch, rho);
+    }
+};
+
+// The protocol on the trees as they stand (build / build_lookup of the leaves (d_p, d_q)): gkr/chain.hpp's outer transcript and n - 1
+// pks proofs, into proof_out (pkf::proof_bytes(p->st) bytes).  point: n elements, the values: one each; any may be NULL.
+int chain(pkf_prover* p, const uint64_t* d_p, const uint64_t* d_q, const uint64_t* bind, uint8_t* proof_out, uint64_t* point_out, uint64_t* value_p_out,
+          uint64_t* value_q_out) {
+    Proving rule(p, d_p, d_q);
+    if (int rc = pk::gkr::prove_chain(p, rule, p->top, bind, proof_out, point_out)) return rc;
+    if (value_p_out && rule.claim.has_p) pkf::put_fe(value_p_out, rule.claim.cp);
+    if (value_q_out) pkf::put_fe(value_q_out, rule.claim.cq);
     return PK_OK;
 }
 
@@ -122,46 +95,23 @@ int chain(pkf_prover* p, const uint64_t* d_p, const uint64_t* d_q, const uint64_
 extern "C" {
 
 int pkf_prover_create(pk_ctx* ctx, const pkf_statement* stmt, pkf_prover** out) {
-    if (out) *out = nullptr;
-    std::string why;
-    if (!ctx || !out) return pkf::refuse("null pointer");
-    if (!pkf::statement_ok(stmt, why)) return pkf::refuse(why);
-    try {
-        std::unique_ptr<pkf_prover> p;
-        if (int rc = make_prover(ctx, *stmt, p)) return rc;
-        *out = p.release();
-        pkf::g_error.clear();
-        return PK_OK;
-    } catch (...) {
-        return pk::out_of_host_memory(pkf::g_error);
-    }
+    return pk::create<pkf::Lib>(ctx, stmt, out, [&](std::unique_ptr<pkf_prover>& p) { return make_prover(ctx, *stmt, p); });
 }
 
-int pkf_prover_destroy(pkf_prover* p) {
-    if (!p) return PK_OK;
-    const int rc = p->give_back();
-    delete p;
-    return rc;
-}
+int pkf_prover_destroy(pkf_prover* p) { return pk::destroy(p); }
 
 const char* pkf_last_error(const pkf_prover* p) { return p ? p->err.c_str() : "null prover"; }
 
 // Host only; here and not next to the verifier because the sumcheck provers' share comes from their launch header.
 int pkf_prover_arena_bytes(const pkf_statement* stmt, size_t* bytes) {
-    std::string why;
-    if (!bytes) return pkf::refuse("null pointer");
-    if (!pkf::statement_ok(stmt, why)) return pkf::refuse(why);
-    *bytes = pkf::arena_bytes(stmt->n) + pkf::layers_arena_bytes(*stmt);
-    return PK_OK;
+    return pk::size_out<pkf::Lib>(stmt, bytes, [](const pkf_statement& s) { return pkf::arena_bytes(s.n) + pkf::layers_arena_bytes(s); });
 }
 
 int pkf_lookup_prover_arena_bytes(const pkf_lookup_statement* stmt, size_t* bytes) {
-    std::string why;
-    if (!bytes) return pkf::refuse("null pointer");
-    if (!pkf::statement_ok(stmt, why)) return pkf::refuse(why);
-    const pkf_statement F = pkf::side_f(*stmt), T = pkf::side_t(*stmt);
-    *bytes = pkf::arena_bytes(F.n) + pkf::layers_arena_bytes(F) + pkf::arena_bytes(T.n) + pkf::layers_arena_bytes(T) + 32 * (pkf::tree_fes(F.n) + pkf::tree_fes(T.n));
-    return PK_OK;
+    return pk::size_out<pkf::Lib>(stmt, bytes, [](const pkf_lookup_statement& s) {
+        const pkf_statement F = pkf::side_f(s), T = pkf::side_t(s);
+        return pkf::arena_bytes(F.n) + pkf::layers_arena_bytes(F) + pkf::arena_bytes(T.n) + pkf::layers_arena_bytes(T) + 32 * (pkf::tree_fes(F.n) + pkf::tree_fes(T.n));
+    });
 }
 
 int pkf_tree(pk_ctx* ctx, unsigned n, const uint64_t* d_p_or_null, const uint64_t* d_q, uint64_t* d_ptree_out, uint64_t* d_qtree_out, uint64_t* fraction_out) {
@@ -181,12 +131,7 @@ int pkf_prove(pkf_prover* p, const uint64_t* d_p_or_null, const uint64_t* d_q, c
     const pkf_statement& st = p->st;
     if (!d_q || !len || (!proof_out && cap)) return fail(p, PK_ERR_BAD_ARG, "null pointer");
     if (!d_p_or_null != (st.unit == 1)) return fail(p, PK_ERR_BAD_ARG, "the numerator table is NULL exactly when the statement's unit is 1");
-    const size_t need = pkf::proof_bytes(st);
-    *len = need;
-    if (cap < need) return fail(p, PK_ERR_BAD_ARG, "the proof buffer holds " + std::to_string(cap) + " bytes, the proof has " + std::to_string(need));
-    if (st.n_bind && !bind) return fail(p, PK_ERR_BAD_ARG, "the statement binds elements: pass them");
-    std::string why;
-    if (!pkf::elements_below_p(bind, st.n_bind, "bind", why)) return fail(p, PK_ERR_BAD_ARG, why);
+    if (int rc = pk::proof_room_and_bind(p, pkf::proof_bytes(st), cap, len, bind, st.n_bind)) return rc;
     try {
         if (int rc = build(p, d_p_or_null, d_q)) return rc;
         if (is_zero(p->Q)) return fail(p, PK_ERR_UNSATISFIED, "a denominator is zero: Q = 0 and the sum of fractions is not defined");
@@ -200,12 +145,8 @@ int pkf_prove(pkf_prover* p, const uint64_t* d_p_or_null, const uint64_t* d_q, c
 }
 
 int pkf_lookup_prover_create(pk_ctx* ctx, const pkf_lookup_statement* stmt, pkf_lookup_prover** out) {
-    if (out) *out = nullptr;
-    std::string why;
-    if (!ctx || !out) return pkf::refuse("null pointer");
-    if (!pkf::statement_ok(stmt, why)) return pkf::refuse(why);
-    try {
-        std::unique_ptr<pkf_lookup_prover> p(new pkf_lookup_prover());
+    return pk::create<pkf::Lib>(ctx, stmt, out, [&](std::unique_ptr<pkf_lookup_prover>& p) {
+        p.reset(new pkf_lookup_prover());
         p->ctx = ctx;
         p->st = *stmt;
         p->pattern = pkf::io_pattern(*stmt);
@@ -218,20 +159,11 @@ int pkf_lookup_prover_create(pk_ctx* ctx, const pkf_lookup_statement* stmt, pkf_
             if (int rc = make_prover(ctx, sides[which], inner)) return rc;
             p->side[which] = inner.release();
         }
-        *out = p.release();
-        pkf::g_error.clear();
         return PK_OK;
-    } catch (...) {
-        return pk::out_of_host_memory(pkf::g_error);
-    }
+    });
 }
 
-int pkf_lookup_prover_destroy(pkf_lookup_prover* p) {
-    if (!p) return PK_OK;
-    const int rc = p->give_back();
-    delete p;
-    return rc;
-}
+int pkf_lookup_prover_destroy(pkf_lookup_prover* p) { return pk::destroy(p); }
 
 const char* pkf_lookup_last_error(const pkf_lookup_prover* p) { return p ? p->err.c_str() : "null prover"; }
 
@@ -241,12 +173,8 @@ int pkf_lookup_prove(pkf_lookup_prover* p, const uint64_t* d_f, const uint64_t* 
     const pkf_lookup_statement& st = p->st;
     if (!d_f || !d_t || !d_m || !len || (!proof_out && cap)) return fail(p, PK_ERR_BAD_ARG, "null pointer");
     pkf_prover *const F = p->side[PKF_SIDE_F], *const T = p->side[PKF_SIDE_T];
-    const size_t len_f = pkf::proof_bytes(F->st), need = len_f + pkf::proof_bytes(T->st);
-    *len = need;
-    if (cap < need) return fail(p, PK_ERR_BAD_ARG, "the proof buffer holds " + std::to_string(cap) + " bytes, the proof has " + std::to_string(need));
-    if (st.n_bind && !bind) return fail(p, PK_ERR_BAD_ARG, "the statement binds elements: pass them");
-    std::string why;
-    if (!pkf::elements_below_p(bind, st.n_bind, "bind", why)) return fail(p, PK_ERR_BAD_ARG, why);
+    const size_t len_f = pkf::proof_bytes(F->st);
+    if (int rc = pk::proof_room_and_bind(p, len_f + pkf::proof_bytes(T->st), cap, len, bind, st.n_bind)) return rc;
     try {
         pk::Transcript tr(p->pattern);
         for (unsigned i = 0; i < st.n_bind; i++) tr.add_scalar(pk::h_load(bind + 4 * i));

@@ -2,9 +2,6 @@
 // sets the grid and the layers per launch of a prover's kernels and reads where its last proof's time went: test and benchmark knobs
 // that the C ABI does not carry.
 #pragma once
-#include <memory>
-
-#include "../prover_transcript.hpp"
 #include "../sumcheck/round.hpp"
 #include "kernels.hpp"
 
@@ -27,38 +24,18 @@ inline size_t layers_arena_bytes(const pkf_statement& s) {
 
 }  // namespace pkf
 
-struct pkf_prover {
-    pk_ctx* ctx = nullptr;
+// gkr/chain.hpp's frame (ctx, pattern, err, layer[], grid, layers; ev[4]: around the tree phase and around a layer's combine pass, on
+// the null stream) and what is the fractional sum's own
+struct pkf_prover : pk::gkr::ProverFrame<4> {
     pkf_statement st{};
-    std::string pattern, err;
-    uint64_t* arena = nullptr;                 // ptree | qtree | u (layout.hpp)
+    uint64_t* arena = nullptr;  // ptree | qtree | u (layout.hpp)
     uint64_t *ptree = nullptr, *qtree = nullptr, *u = nullptr;
-    pks_prover* layer[PKF_MAX_VARS] = {};      // layer[d], 1 <= d < n
-    unsigned grid = 0;    // the workgroups of the tree, leaf and combine kernels; 0: the rule.  No bit of a result depends on it
-    unsigned layers = 0;  // layers per launch, 1 .. 3; 0: the library's value.  No bit of a result depends on it
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};  // around the tree phase and around a layer's combine pass, on the null stream
-    pk::fe top[4], P, Q;                    // of the trees as they stand (build / build_lookup)
+    pk::fe top[4], P, Q;  // of the trees as they stand (build / build_lookup)
     pkf::Profile prof;
 
-    pkf_prover() = default;
-    pkf_prover(const pkf_prover&) = delete;
-    pkf_prover& operator=(const pkf_prover&) = delete;
-    // gives back whatever the prover holds, so a creation that stops half way leaks nothing; rc: the first failure's code
     int give_back() {
-        int rc = PK_OK;
-        for (pks_prover*& s : layer) {
-            if (s)
-                if (int r = pks_prover_destroy(s)) rc = rc ? rc : r;
-            s = nullptr;
-        }
-        for (hipEvent_t& e : ev) {
-            if (e) (void)hipEventDestroy(e);
-            e = nullptr;
-        }
-        if (arena)
-            if (int r = pk_free(ctx, arena)) rc = rc ? rc : r;
-        arena = ptree = qtree = u = nullptr;
-        return rc;
+        ptree = qtree = u = nullptr;
+        return ProverFrame::give_back(arena);
     }
     ~pkf_prover() { (void)give_back(); }
 };

@@ -1,15 +1,18 @@
 // statement.hpp -- what the sources of libprovekit_fracsum.so share on the host: which statements the library takes, the two outer IO
-// patterns, the pks statement of a layer, the proof's framing and the steps from the top and from one layer's finals to the next
-// claims.  Host only; no device, no product call.
+// patterns, the pks statement of a layer, the proof's framing, the steps from the top and from one layer's finals to the next claims,
+// and with them the rule of this library's chain (gkr/chain.hpp) as far as prover and verifier share it.  Host only; no device, no
+// product call.
 #pragma once
 #include <string>
 
 #include "../../../include/provekit_fracsum.h"
-#include "../argument.hpp"
+#include "../gkr/chain.hpp"
 
 namespace pkf {
 
 using pk::fe;
+
+static_assert(PKF_MAX_VARS == pk::gkr::MAX_VARS && PKF_MAX_BIND == pk::gkr::MAX_BIND, "gkr/chain.hpp sizes its arrays by these");
 
 extern thread_local std::string g_error;  // pkf_create_error
 inline int refuse(const std::string& why) { return pk::refuse(g_error, why); }
@@ -118,5 +121,30 @@ struct Claims {
 };
 // over unit leaves the finals (b, c, e) must have e = 1 + lambda c: u is the table the statement says
 inline bool unit_final_ok(const fe* finals, const fe& lambda) { return pk::fe_eq(finals[2], pk::h_add(pk::fe_one(), pk::h_mul(lambda, finals[1]))); }
+
+// The rule of this library's chain, the part both sides of the transcript share: four top values, lambda and then the seed in front of
+// a layer's sumcheck, four tables and so four finals per layer (three over unit leaves), and the running claims (cp, cq).
+struct Chain {
+    static constexpr unsigned TOP = 4, MAX_FINALS = 4, CHALLENGES = 2;  // ch[0]: lambda, ch[1]: the seed
+    const pkf_statement& s;
+    Claims claim;
+    explicit Chain(const pkf_statement& st) : s(st) {}
+    pks_statement layer_statement(unsigned d) const { return pkf::layer_statement(s, d); }
+    size_t layer_at(unsigned d) const { return pkf::layer_at(s, d); }
+    size_t layer_bytes(unsigned d) const { return pkf::layer_bytes(s, d); }
+    unsigned finals(unsigned d) const { return layer_tables(s, d); }
+    void start(const fe* top, const fe& rho) { claim.from_top(top, rho), claim.has_p = !(s.unit && s.n == 1); }
+    fe expected(const fe* ch) const { return claim.expected(ch[0]); }
+    void step(unsigned d, const fe* finals, const fe* ch, const fe& rho) { claim.step(unit_layer(s, d), finals, ch[0], rho); }
+};
+
+// the library's overload sets, for argument.hpp's templates
+struct Lib {
+    static std::string& error() { return g_error; }
+    template <class S>
+    static bool ok(const S* s, std::string& why) { return statement_ok(s, why); }
+    template <class S>
+    static std::string pattern(const S& s) { return io_pattern(s); }
+};
 
 }  // namespace pkf

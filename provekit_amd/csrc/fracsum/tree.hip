@@ -137,30 +137,18 @@ __global__ __launch_bounds__(THREADS) void combine_kernel(size_t count, const fe
         fe_store(u + x, fe_add(pR ? fe_load(pR + x) : one, fe_mulx(lambda, fe_load(qR + x))));
 }
 
-int launched() { return hipGetLastError() == hipSuccess ? PK_OK : PK_ERR_HIP; }
-bool knobs_ok(unsigned layers, unsigned grid) { return layers <= TREE_MAX_LAYERS && grid <= PKF_MAX_GRID; }
-// how many layers the next launch takes when it reads layer D
-unsigned step(unsigned D, unsigned layers) { return D > TAIL_MAX_N ? (layers < D - TAIL_MAX_N ? layers : D - TAIL_MAX_N) : 0; }
+using pk::gkr::dispatch_layers;
+using pk::gkr::launched;
+bool knobs_ok(unsigned layers, unsigned grid) { return pk::gkr::knobs_ok(layers, grid, PKF_MAX_GRID); }
+unsigned step(unsigned D, unsigned layers) { return pk::gkr::step(D, layers, TAIL_MAX_N); }
 
 template <bool UNIT>
 void tree_step(hipStream_t stream, unsigned s, unsigned grid, const TableSource& src, unsigned D, fe* ptree, fe* qtree) {
-    if (s == 1)
-        frac_tree_kernel<1, UNIT><<<grid, THREADS, 0, stream>>>(src, D, ptree, qtree);
-    else if (s == 2)
-        frac_tree_kernel<2, UNIT><<<grid, THREADS, 0, stream>>>(src, D, ptree, qtree);
-    else
-        frac_tree_kernel<3, UNIT><<<grid, THREADS, 0, stream>>>(src, D, ptree, qtree);
+    dispatch_layers<1>(s, [&](auto S) { frac_tree_kernel<S(), UNIT><<<grid, THREADS, 0, stream>>>(src, D, ptree, qtree); });
 }
 template <bool UNIT>
 void leaf_step(hipStream_t stream, unsigned s, unsigned grid, const LookupSource& src, unsigned D, fe* ptree, fe* qtree) {
-    if (s == 0)
-        lookup_leaf_kernel<0, UNIT><<<grid, THREADS, 0, stream>>>(src, D, ptree, qtree);
-    else if (s == 1)
-        lookup_leaf_kernel<1, UNIT><<<grid, THREADS, 0, stream>>>(src, D, ptree, qtree);
-    else if (s == 2)
-        lookup_leaf_kernel<2, UNIT><<<grid, THREADS, 0, stream>>>(src, D, ptree, qtree);
-    else
-        lookup_leaf_kernel<3, UNIT><<<grid, THREADS, 0, stream>>>(src, D, ptree, qtree);
+    dispatch_layers<0>(s, [&](auto S) { lookup_leaf_kernel<S(), UNIT><<<grid, THREADS, 0, stream>>>(src, D, ptree, qtree); });
 }
 
 // every layer below layer D, which (p_in, q_in) hold; p_in NULL: unit numerators

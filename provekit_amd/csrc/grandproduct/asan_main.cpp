@@ -14,7 +14,6 @@
 namespace {
 
 using asan_case::take;
-using asan_case::take_block;
 
 int run(const char* path, bool multiset) {
     if (!asan_case::read_file(path)) return 2;
@@ -33,37 +32,18 @@ int run(const char* path, bool multiset) {
         st = pkg_statement{head[0], head[1]};
         rc = pkg_proof_bytes(&st, &proof_len);
     }
-    if (rc) {
-        printf("%d 0 REFUSED 0 0 0 %s\n", rc, pkg_create_error());
-        return 0;
-    }
-    const unsigned n = multiset ? ms.n : st.n, n_bind = multiset ? ms.n_bind : st.n_bind;
-    uint32_t pattern_len, count;
-    take(&pattern_len, 4);
-    uint8_t* pattern = (uint8_t*)take_block(pattern_len);
-    uint64_t* bind = n_bind ? (uint64_t*)take_block(32 * (size_t)n_bind) : nullptr;
-    take(&count, 4);
+    asan_case::Proofs d;
+    d.n_bind = multiset ? ms.n_bind : st.n_bind, d.create_error = pkg_create_error, d.check_name = pkg_check_name;
+    if (rc) return asan_case::refused(d, rc), 0;
     pkg_multiset_claims* claims = (pkg_multiset_claims*)malloc(sizeof(pkg_multiset_claims));
-    uint64_t* point = (uint64_t*)malloc(32 * (size_t)n);  // exactly n coordinates
+    uint64_t* point = (uint64_t*)malloc(32 * (size_t)(multiset ? ms.n : st.n));  // exactly n coordinates
     uint64_t* scalars = (uint64_t*)malloc(64);
-    for (uint32_t c = 0; c < count; c++) {
-        uint64_t len;
-        take(&len, 8);
-        uint8_t* proof = (uint8_t*)take_block(len);
-        pkv_result r;
-        int side = 0;
-        unsigned layer = 0;
-        if (multiset)
-            rc = pkg_multiset_verify(&ms, pattern_len ? pattern : nullptr, pattern_len, bind, proof, len, claims, &side, &layer, &r);
-        else
-            rc = pkg_verify(&st, pattern_len ? pattern : nullptr, pattern_len, bind, nullptr, proof, len, scalars, point, scalars + 4, &layer, &r);
-        if (rc)
-            printf("%d 0 REFUSED 0 0 0 %s\n", rc, pkg_create_error());
-        else
-            printf("0 %d %s %d %u %llu\n", r.accepted, pkg_check_name(r.check), side, layer, (unsigned long long)r.offset);
-        free(proof);
-    }
-    free(scalars), free(point), free(claims), free(bind), free(pattern);
+    asan_case::run_proofs<pkv_result>(d, [&](const uint8_t* pattern, size_t pattern_len, const uint64_t* bind, const uint64_t*, const uint8_t* proof, size_t len,
+                                             int* side, unsigned* layer, pkv_result* r) {
+        if (multiset) return pkg_multiset_verify(&ms, pattern, pattern_len, bind, proof, len, claims, side, layer, r);
+        return pkg_verify(&st, pattern, pattern_len, bind, nullptr, proof, len, scalars, point, scalars + 4, layer, r);
+    });
+    free(scalars), free(point), free(claims);
     return 0;
 }
 

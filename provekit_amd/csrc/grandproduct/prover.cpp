@@ -5,28 +5,15 @@
 
 using pk::fail;
 using pk::fe;
-using pk::host_ms_since;
 
 namespace {
 
 // a prover of `stmt` with its arena, events and pks provers; the reason of a failure goes to pkg::g_error
-int make_prover(pk_ctx* ctx, const pkg_statement& stmt, std::unique_ptr<pkg_prover>& out) {
-    auto stop = [](int rc, const std::string& reason) { return pkg::g_error = reason, rc; };
-    std::unique_ptr<pkg_prover> p(new pkg_prover());  // its destructor gives back what a return or a throw below leaves behind
-    p->ctx = ctx;
+int make_prover(pk_ctx* ctx, const pkg_statement& stmt, std::unique_ptr<pkg_prover>& p) {
+    p.reset(new pkg_prover());  // its destructor gives back what a failure or a throw below leaves behind
     p->st = stmt;
     p->pattern = pkg::io_pattern(stmt);
-    void* base = nullptr;
-    if (int rc = pk_malloc(ctx, pkg::tree_bytes(stmt.n), &base)) return stop(rc, "pk_malloc of the arena failed");
-    p->tree = (uint64_t*)base;
-    for (hipEvent_t& e : p->ev)
-        if (hipEventCreate(&e) != hipSuccess) return stop(PK_ERR_HIP, "hipEventCreate failed");
-    for (unsigned d = 1; d < stmt.n; d++) {
-        const pks_statement ps = pkg::layer_statement(d);
-        if (int rc = pks_prover_create(ctx, &ps, &p->layer[d])) return stop(rc, std::string("pks_prover_create failed: ") + pks_create_error());
-    }
-    out = std::move(p);
-    return PK_OK;
+    return pk::gkr::make_frame(*p, ctx, pkg::tree_bytes(stmt.n), p->tree, stmt.n, pkg::layer_statement, pkg::g_error);
 }
 
 // after the tree's launches: the phase's time, the top values and the product, on the host
@@ -56,41 +43,25 @@ int build_leaves(pkg_prover* p, const pkg::Leaves& lv, uint64_t* d_leaf) {
     return read_top(p, d_leaf);
 }
 
-// The protocol on the tree as it stands (build / build_leaves of d_v): the outer transcript and the n - 1 pks proofs, into proof_out
-// (pkg::proof_bytes(p->st) bytes).  point: n elements, value: one; either may be NULL.
+// What the prover adds to the chain's rule (pkg::Chain, statement.hpp): layer d's two tables
+struct Proving : pkg::Chain {
+    const pkg_prover* p;
+    const uint64_t* d_v;
+    Proving(const pkg_prover* prover, const uint64_t* bottom) : Chain(prover->st), p(prover), d_v(bottom) {}
+    // L_d and R_d are the two halves of layer d + 1: of the caller's table at the bottom, of the arena above it
+    int tables(unsigned d, const fe*, const uint64_t** out) const {
+        const uint64_t* const L = d + 1 == s.n ? d_v : p->tree + ((size_t)8 << d);
+        out[0] = L, out[1] = L + ((size_t)4 << d);
+        return PK_OK;
+    }
+};
+
+// The protocol on the tree as it stands (build / build_leaves of d_v): gkr/chain.hpp's outer transcript and n - 1 pks proofs, into
+// proof_out (pkg::proof_bytes(p->st) bytes).  point: n elements, value: one; either may be NULL.
 int chain(pkg_prover* p, const uint64_t* d_v, const uint64_t* bind, uint8_t* proof_out, uint64_t* point_out, uint64_t* value_out) {
-    const unsigned n = p->st.n;
-    pk::Transcript tr(p->pattern);
-    for (unsigned i = 0; i < p->st.n_bind; i++) tr.add_scalar(pk::h_load(bind + 4 * i));
-    tr.add_scalars(p->top, 2);
-    for (int i = 0; i < 2; i++) {
-        const fe canon = pk::h_to_canon(p->top[i]);
-        memcpy(proof_out + 32 * i, canon.v, 32);
-    }
-    fe rho = tr.challenge_scalar();
-    fe z[PKG_MAX_VARS], r[PKG_MAX_VARS], lr[2];
-    fe claim = pkg::next_claim(p->top[0], p->top[1], rho);
-    z[0] = rho;
-    for (unsigned d = 1; d < n; d++) {
-        const fe seed = tr.challenge_scalar();
-        // L_d and R_d are the two halves of layer d + 1: of the caller's table at the bottom, of the arena above it
-        const uint64_t* const L = d + 1 == n ? d_v : p->tree + ((size_t)8 << d);
-        const uint64_t* const tables[2] = {L, L + ((size_t)4 << d)};
-        size_t part = 0;
-        const auto t0 = std::chrono::steady_clock::now();
-        if (int rc = pks_prove(p->layer[d], tables, (const uint64_t*)z, (const uint64_t*)seed.v, proof_out + pkg::layer_at(d), pkg::layer_bytes(d), &part,
-                               (uint64_t*)r, (uint64_t*)lr))
-            return fail(p, rc, "layer " + std::to_string(d) + "'s sumcheck failed: " + pks_last_error(p->layer[d]));
-        p->prof.layer_ms[d] = host_ms_since(t0);
-        tr.add_scalars(lr, 2);
-        rho = tr.challenge_scalar();
-        claim = pkg::next_claim(lr[0], lr[1], rho);
-        for (unsigned i = 0; i < d; i++) z[i + 1] = r[i];
-        z[0] = rho;
-    }
-    if (!tr.finished()) return fail(p, PK_ERR_IO_PATTERN, "the transcript left its pattern: " + tr.violation());
-    if (point_out) memcpy(point_out, z, 32 * (size_t)n);
-    if (value_out) pkg::put_fe(value_out, claim);
+    Proving rule(p, d_v);
+    if (int rc = pk::gkr::prove_chain(p, rule, p->top, bind, proof_out, point_out)) return rc;
+    if (value_out) pkg::put_fe(value_out, rule.claim);
     return PK_OK;
 }
 
@@ -99,37 +70,16 @@ int chain(pkg_prover* p, const uint64_t* d_v, const uint64_t* bind, uint8_t* pro
 extern "C" {
 
 int pkg_prover_create(pk_ctx* ctx, const pkg_statement* stmt, pkg_prover** out) {
-    if (out) *out = nullptr;
-    std::string why;
-    if (!ctx || !out) return pkg::refuse("null pointer");
-    if (!pkg::statement_ok(stmt, why)) return pkg::refuse(why);
-    try {
-        std::unique_ptr<pkg_prover> p;
-        if (int rc = make_prover(ctx, *stmt, p)) return rc;
-        *out = p.release();
-        pkg::g_error.clear();
-        return PK_OK;
-    } catch (...) {
-        return pk::out_of_host_memory(pkg::g_error);
-    }
+    return pk::create<pkg::Lib>(ctx, stmt, out, [&](std::unique_ptr<pkg_prover>& p) { return make_prover(ctx, *stmt, p); });
 }
 
-int pkg_prover_destroy(pkg_prover* p) {
-    if (!p) return PK_OK;
-    const int rc = p->give_back();
-    delete p;
-    return rc;
-}
+int pkg_prover_destroy(pkg_prover* p) { return pk::destroy(p); }
 
 const char* pkg_last_error(const pkg_prover* p) { return p ? p->err.c_str() : "null prover"; }
 
 // Host only; here and not next to the verifier because the sumcheck provers' share comes from their launch header.
 int pkg_prover_arena_bytes(const pkg_statement* stmt, size_t* bytes) {
-    std::string why;
-    if (!bytes) return pkg::refuse("null pointer");
-    if (!pkg::statement_ok(stmt, why)) return pkg::refuse(why);
-    *bytes = pkg::tree_bytes(stmt->n) + pkg::layers_arena_bytes(stmt->n);
-    return PK_OK;
+    return pk::size_out<pkg::Lib>(stmt, bytes, [](const pkg_statement& s) { return pkg::tree_bytes(s.n) + pkg::layers_arena_bytes(s.n); });
 }
 
 int pkg_tree(pk_ctx* ctx, unsigned n, const uint64_t* d_v, uint64_t* d_tree_out, uint64_t* product_out) {
@@ -146,12 +96,7 @@ int pkg_prove(pkg_prover* p, const uint64_t* d_v, const uint64_t* bind, uint8_t*
     if (!p) return PK_ERR_BAD_ARG;
     const pkg_statement& st = p->st;
     if (!d_v || !len || (!proof_out && cap)) return fail(p, PK_ERR_BAD_ARG, "null pointer");
-    const size_t need = pkg::proof_bytes(st);
-    *len = need;
-    if (cap < need) return fail(p, PK_ERR_BAD_ARG, "the proof buffer holds " + std::to_string(cap) + " bytes, the proof has " + std::to_string(need));
-    if (st.n_bind && !bind) return fail(p, PK_ERR_BAD_ARG, "the statement binds elements: pass them");
-    std::string why;
-    if (!pkg::elements_below_p(bind, st.n_bind, "bind", why)) return fail(p, PK_ERR_BAD_ARG, why);
+    if (int rc = pk::proof_room_and_bind(p, pkg::proof_bytes(st), cap, len, bind, st.n_bind)) return rc;
     try {
         if (int rc = build(p, d_v)) return rc;
         if (int rc = chain(p, d_v, bind, proof_out, point_out, value_out)) return rc;
@@ -164,12 +109,8 @@ int pkg_prove(pkg_prover* p, const uint64_t* d_v, const uint64_t* bind, uint8_t*
 }
 
 int pkg_multiset_prover_create(pk_ctx* ctx, const pkg_multiset_statement* stmt, pkg_multiset_prover** out) {
-    if (out) *out = nullptr;
-    std::string why;
-    if (!ctx || !out) return pkg::refuse("null pointer");
-    if (!pkg::statement_ok(stmt, why)) return pkg::refuse(why);
-    try {
-        std::unique_ptr<pkg_multiset_prover> p(new pkg_multiset_prover());
+    return pk::create<pkg::Lib>(ctx, stmt, out, [&](std::unique_ptr<pkg_multiset_prover>& p) {
+        p.reset(new pkg_multiset_prover());
         p->ctx = ctx;
         p->st = *stmt;
         p->pattern = pkg::io_pattern(*stmt);
@@ -179,20 +120,11 @@ int pkg_multiset_prover_create(pk_ctx* ctx, const pkg_multiset_statement* stmt, 
         std::unique_ptr<pkg_prover> inner;
         if (int rc = make_prover(ctx, pkg::side_statement(*stmt), inner)) return rc;
         p->inner = inner.release();
-        *out = p.release();
-        pkg::g_error.clear();
         return PK_OK;
-    } catch (...) {
-        return pk::out_of_host_memory(pkg::g_error);
-    }
+    });
 }
 
-int pkg_multiset_prover_destroy(pkg_multiset_prover* p) {
-    if (!p) return PK_OK;
-    const int rc = p->give_back();
-    delete p;
-    return rc;
-}
+int pkg_multiset_prover_destroy(pkg_multiset_prover* p) { return pk::destroy(p); }
 
 const char* pkg_multiset_last_error(const pkg_multiset_prover* p) { return p ? p->err.c_str() : "null prover"; }
 
@@ -201,14 +133,11 @@ int pkg_multiset_prove(pkg_multiset_prover* p, const uint64_t* const* d_a, const
     if (!p) return PK_ERR_BAD_ARG;
     const pkg_multiset_statement& st = p->st;
     if (!d_a || !d_b || !len || (!proof_out && cap)) return fail(p, PK_ERR_BAD_ARG, "null pointer");
-    const size_t half = pkg::proof_bytes(pkg::side_statement(st)), need = 2 * half;
-    *len = need;
-    if (cap < need) return fail(p, PK_ERR_BAD_ARG, "the proof buffer holds " + std::to_string(cap) + " bytes, the proof has " + std::to_string(need));
+    const size_t half = pkg::proof_bytes(pkg::side_statement(st));
+    if (int rc = pk::proof_room(p, 2 * half, cap, len)) return rc;
     for (unsigned j = 0; j < st.w; j++)
         if (!d_a[j] || !d_b[j]) return fail(p, PK_ERR_BAD_ARG, "null column");
-    if (st.n_bind && !bind) return fail(p, PK_ERR_BAD_ARG, "the statement binds elements: pass them");
-    std::string why;
-    if (!pkg::elements_below_p(bind, st.n_bind, "bind", why)) return fail(p, PK_ERR_BAD_ARG, why);
+    if (int rc = pk::bind_ok(p, bind, st.n_bind)) return rc;
     try {
         pk::Transcript tr(p->pattern);
         for (unsigned i = 0; i < st.n_bind; i++) tr.add_scalar(pk::h_load(bind + 4 * i));

@@ -2,9 +2,6 @@
 // which sets the grid and the layers per launch of a prover's kernels and reads where its last proof's time went: test and benchmark
 // knobs that the C ABI does not carry.
 #pragma once
-#include <memory>
-
-#include "../prover_transcript.hpp"
 #include "../sumcheck/round.hpp"
 #include "kernels.hpp"
 
@@ -26,38 +23,15 @@ inline size_t layers_arena_bytes(unsigned n) {
 
 }  // namespace pkg
 
-struct pkg_prover {
-    pk_ctx* ctx = nullptr;
+// gkr/chain.hpp's frame (ctx, pattern, err, layer[], grid, layers; ev[2]: around the tree phase, on the null stream) and what is the
+// grand product's own
+struct pkg_prover : pk::gkr::ProverFrame<2> {
     pkg_statement st{};
-    std::string pattern, err;
-    uint64_t* tree = nullptr;                        // the arena: 2^n elements, heap layout
-    pks_prover* layer[PKG_MAX_VARS] = {};            // layer[d], 1 <= d < n
-    unsigned grid = 0;    // the workgroups of tree_kernel / leaf_kernel; 0: the rule.  No bit of a result depends on it
-    unsigned layers = 0;  // layers per launch, 1 .. 3; 0: the library's value.  No bit of a result depends on it
-    hipEvent_t ev[2] = {nullptr, nullptr};  // around the tree phase, on the null stream
-    pk::fe top[2], product;                 // of the tree as it stands (build / build_leaves)
+    uint64_t* tree = nullptr;  // the arena: 2^n elements, heap layout
+    pk::fe top[2], product;    // of the tree as it stands (build / build_leaves)
     pkg::Profile prof;
 
-    pkg_prover() = default;
-    pkg_prover(const pkg_prover&) = delete;
-    pkg_prover& operator=(const pkg_prover&) = delete;
-    // gives back whatever the prover holds, so a creation that stops half way leaks nothing; rc: the first failure's code
-    int give_back() {
-        int rc = PK_OK;
-        for (pks_prover*& s : layer) {
-            if (s)
-                if (int r = pks_prover_destroy(s)) rc = rc ? rc : r;
-            s = nullptr;
-        }
-        for (hipEvent_t& e : ev) {
-            if (e) (void)hipEventDestroy(e);
-            e = nullptr;
-        }
-        if (tree)
-            if (int r = pk_free(ctx, tree)) rc = rc ? rc : r;
-        tree = nullptr;
-        return rc;
-    }
+    int give_back() { return ProverFrame::give_back(tree); }
     ~pkg_prover() { (void)give_back(); }
 };
 

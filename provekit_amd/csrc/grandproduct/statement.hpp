@@ -1,15 +1,17 @@
 // statement.hpp -- what the sources of libprovekit_grandproduct.so share on the host: which statements the library takes, the two
-// outer IO patterns, the pks statement of a layer, the proof's framing and the step from one layer's claim to the next.  Host only; no
-// device, no product call.
+// outer IO patterns, the pks statement of a layer, the proof's framing, the step from one layer's claim to the next, and with them
+// the rule of this library's chain (gkr/chain.hpp) as far as prover and verifier share it.  Host only; no device, no product call.
 #pragma once
 #include <string>
 
 #include "../../../include/provekit_grandproduct.h"
-#include "../argument.hpp"
+#include "../gkr/chain.hpp"
 
 namespace pkg {
 
 using pk::fe;
+
+static_assert(PKG_MAX_VARS == pk::gkr::MAX_VARS && PKG_MAX_BIND == pk::gkr::MAX_BIND, "gkr/chain.hpp sizes its arrays by these");
 
 extern thread_local std::string g_error;  // pkg_create_error
 inline int refuse(const std::string& why) { return pk::refuse(g_error, why); }
@@ -71,5 +73,30 @@ inline size_t proof_bytes(const pkg_multiset_statement& s) { return 2 * layer_at
 
 // c' = (1 - rho) l + rho r
 inline fe next_claim(const fe& l, const fe& r, const fe& rho) { return pk::h_add(l, pk::h_mul(rho, pk::h_sub(r, l))); }
+
+// The rule of this library's chain, the part both sides of the transcript share: two top values, the seed alone in front of a layer's
+// sumcheck, two tables and so two finals (l, r) per layer, and one running claim: the value of V_d at z_d.
+struct Chain {
+    static constexpr unsigned TOP = 2, MAX_FINALS = 2, CHALLENGES = 1;
+    const pkg_statement& s;
+    fe claim;
+    explicit Chain(const pkg_statement& st) : s(st) {}
+    pks_statement layer_statement(unsigned d) const { return pkg::layer_statement(d); }
+    size_t layer_at(unsigned d) const { return pkg::layer_at(d); }
+    size_t layer_bytes(unsigned d) const { return pkg::layer_bytes(d); }
+    unsigned finals(unsigned) const { return 2; }
+    void start(const fe* top, const fe& rho) { claim = next_claim(top[0], top[1], rho); }
+    fe expected(const fe*) const { return claim; }
+    void step(unsigned, const fe* lr, const fe*, const fe& rho) { claim = next_claim(lr[0], lr[1], rho); }
+};
+
+// the library's overload sets, for argument.hpp's templates
+struct Lib {
+    static std::string& error() { return g_error; }
+    template <class S>
+    static bool ok(const S* s, std::string& why) { return statement_ok(s, why); }
+    template <class S>
+    static std::string pattern(const S& s) { return io_pattern(s); }
+};
 
 }  // namespace pkg

@@ -101,21 +101,16 @@ __global__ __launch_bounds__(THREADS) void tail_kernel(const fe* __restrict__ in
     }
 }
 
-int launched() { return hipGetLastError() == hipSuccess ? PK_OK : PK_ERR_HIP; }
-bool knobs_ok(unsigned layers, unsigned grid) { return layers <= TREE_MAX_LAYERS && grid <= PKG_MAX_GRID; }
-// how many layers the next launch takes when it reads layer D
-unsigned step(unsigned D, unsigned layers) { return D > TAIL_MAX_N ? (layers < D - TAIL_MAX_N ? layers : D - TAIL_MAX_N) : 0; }
+using pk::gkr::dispatch_layers;
+using pk::gkr::launched;
+bool knobs_ok(unsigned layers, unsigned grid) { return pk::gkr::knobs_ok(layers, grid, PKG_MAX_GRID); }
+unsigned step(unsigned D, unsigned layers) { return pk::gkr::step(D, layers, TAIL_MAX_N); }
 
 // every layer below layer D, which `in` holds
 int finish(hipStream_t stream, unsigned D, const fe* in, fe* tree, unsigned layers, unsigned grid_or_0) {
     while (unsigned s = step(D, layers)) {
         const unsigned grid = grid_or_0 ? grid_or_0 : lanes_grid((size_t)1 << (D - s));
-        if (s == 1)
-            tree_kernel<1><<<grid, THREADS, 0, stream>>>(in, D, tree);
-        else if (s == 2)
-            tree_kernel<2><<<grid, THREADS, 0, stream>>>(in, D, tree);
-        else
-            tree_kernel<3><<<grid, THREADS, 0, stream>>>(in, D, tree);
+        dispatch_layers<1>(s, [&](auto S) { tree_kernel<S()><<<grid, THREADS, 0, stream>>>(in, D, tree); });
         D -= s;
         in = tree + ((size_t)1 << D);
     }
@@ -143,14 +138,7 @@ int leaf_tree_launch(hipStream_t stream, unsigned n, const Leaves& lv, uint64_t*
     const unsigned layers = layers_or_0 ? layers_or_0 : TREE_LAYERS, s = step(n, layers);
     const unsigned grid = grid_or_0 ? grid_or_0 : lanes_grid((size_t)1 << (n - s));
     fe* const tree = (fe*)d_tree;
-    if (s == 0)
-        leaf_kernel<0><<<grid, THREADS, 0, stream>>>(src, n, tree);
-    else if (s == 1)
-        leaf_kernel<1><<<grid, THREADS, 0, stream>>>(src, n, tree);
-    else if (s == 2)
-        leaf_kernel<2><<<grid, THREADS, 0, stream>>>(src, n, tree);
-    else
-        leaf_kernel<3><<<grid, THREADS, 0, stream>>>(src, n, tree);
+    dispatch_layers<0>(s, [&](auto S) { leaf_kernel<S()><<<grid, THREADS, 0, stream>>>(src, n, tree); });
     const unsigned D = n - s;
     return finish(stream, D, s ? tree + ((size_t)1 << D) : (const fe*)d_leaf, tree, layers, grid_or_0);
 }

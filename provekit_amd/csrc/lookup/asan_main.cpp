@@ -11,40 +11,21 @@
 
 namespace {
 
-using asan_case::take;
-using asan_case::take_block;
-
 int run_verify(const char* path) {
     if (!asan_case::read_file(path)) return 2;
     uint32_t head[4];
-    take(head, sizeof head);
+    asan_case::take(head, sizeof head);
     pkl_statement st{head[0], head[1], head[2], head[3]};
     size_t proof_len = 0;
-    if (int rc = pkl_proof_bytes(&st, &proof_len)) {
-        printf("%d 0 REFUSED 0 0 %s\n", rc, pkl_create_error());
-        return 0;
-    }
-    uint32_t pattern_len, count;
-    take(&pattern_len, 4);
-    uint8_t* pattern = (uint8_t*)take_block(pattern_len);
-    uint64_t* bind = st.n_bind ? (uint64_t*)take_block(32 * (size_t)st.n_bind) : nullptr;
-    uint64_t* bind2 = st.n_bind2 ? (uint64_t*)take_block(32 * (size_t)st.n_bind2) : nullptr;
-    take(&count, 4);
+    asan_case::Proofs d;
+    d.n_bind = st.n_bind, d.n_bind2 = st.n_bind2, d.layer_column = false, d.side = -1, d.create_error = pkl_create_error, d.check_name = pks_check_name;
+    if (int rc = pkl_proof_bytes(&st, &proof_len)) return asan_case::refused(d, rc), 0;
     pkl_claims* claims = (pkl_claims*)malloc(sizeof(pkl_claims));
-    for (uint32_t c = 0; c < count; c++) {
-        uint64_t len;
-        take(&len, 8);
-        uint8_t* proof = (uint8_t*)take_block(len);
-        pkv_result r;
-        int side = -1;
-        const int rc = pkl_verify(&st, pattern_len ? pattern : nullptr, pattern_len, bind, bind2, proof, len, claims, &side, &r);
-        if (rc)
-            printf("%d 0 REFUSED 0 0 %s\n", rc, pkl_create_error());
-        else
-            printf("0 %d %s %d %llu\n", r.accepted, pks_check_name(r.check), side, (unsigned long long)r.offset);
-        free(proof);
-    }
-    free(claims), free(bind2), free(bind), free(pattern);
+    asan_case::run_proofs<pkv_result>(d, [&](const uint8_t* pattern, size_t pattern_len, const uint64_t* bind, const uint64_t* bind2, const uint8_t* proof,
+                                             size_t len, int* side, unsigned*, pkv_result* r) {
+        return pkl_verify(&st, pattern, pattern_len, bind, bind2, proof, len, claims, side, r);
+    });
+    free(claims);
     return 0;
 }
 

@@ -10,41 +10,21 @@
 
 namespace {
 
-using asan_case::take;
-using asan_case::take_block;
-
 int run(const char* path) {
     if (!asan_case::read_file(path)) return 2;
     uint32_t head[5];
-    take(head, sizeof head);
+    asan_case::take(head, sizeof head);
     const pkt_statement st{head[0], head[1], head[2], head[3], head[4]};
     size_t proof_len = 0;
-    int rc = pkt_proof_bytes(&st, &proof_len);
-    if (rc) {
-        printf("%d 0 REFUSED 0 0 0 %s\n", rc, pkt_create_error());
-        return 0;
-    }
-    uint32_t pattern_len, count;
-    take(&pattern_len, 4);
-    uint8_t* pattern = (uint8_t*)take_block(pattern_len);
-    uint64_t* bind = st.n_bind ? (uint64_t*)take_block(32 * (size_t)st.n_bind) : nullptr;
-    take(&count, 4);
+    asan_case::Proofs d;
+    d.n_bind = st.n_bind, d.create_error = pkt_create_error, d.check_name = pkt_check_name;
+    if (int rc = pkt_proof_bytes(&st, &proof_len)) return asan_case::refused(d, rc), 0;
     pkt_claims* claims = (pkt_claims*)malloc(sizeof(pkt_claims));
-    for (uint32_t c = 0; c < count; c++) {
-        uint64_t len;
-        take(&len, 8);
-        uint8_t* proof = (uint8_t*)take_block(len);
-        pkv_result r;
-        int side = 0;
-        unsigned layer = 0;
-        rc = pkt_verify(&st, pattern_len ? pattern : nullptr, pattern_len, bind, proof, len, claims, &side, &layer, &r);
-        if (rc)
-            printf("%d 0 REFUSED 0 0 0 %s\n", rc, pkt_create_error());
-        else
-            printf("0 %d %s %d %u %llu\n", r.accepted, pkt_check_name(r.check), side, layer, (unsigned long long)r.offset);
-        free(proof);
-    }
-    free(claims), free(bind), free(pattern);
+    asan_case::run_proofs<pkv_result>(d, [&](const uint8_t* pattern, size_t pattern_len, const uint64_t* bind, const uint64_t*, const uint8_t* proof, size_t len,
+                                             int* side, unsigned* layer, pkv_result* r) {
+        return pkt_verify(&st, pattern, pattern_len, bind, proof, len, claims, side, layer, r);
+    });
+    free(claims);
     return 0;
 }
 

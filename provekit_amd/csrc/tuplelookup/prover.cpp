@@ -12,7 +12,7 @@ using pk::host_ms_since;
 
 namespace {
 
-bool is_zero(const fe& x) { return pk::fe_eq(x, pk::fe_zero()); }
+using pk::is_zero;
 
 // the caller's c * w (or w) device pointers into the kernels' argument; false: one is NULL
 bool take_columns(const uint64_t* const* d_cols, unsigned w, unsigned c, pkt::Columns& out) {
@@ -65,13 +65,9 @@ int pkt_prover_arena_bytes(const pkt_statement* stmt, size_t* bytes) {
 }
 
 int pkt_prover_create(pk_ctx* ctx, const pkt_statement* stmt, pkt_prover** out) {
-    if (out) *out = nullptr;
-    std::string why;
-    if (!ctx || !out) return pkt::refuse("null pointer");
-    if (!pkt::statement_ok(stmt, why)) return pkt::refuse(why);
     auto stop = [](int rc, const std::string& reason) { return pkt::g_error = reason, rc; };
-    try {
-        std::unique_ptr<pkt_prover> p(new pkt_prover());  // its destructor gives back what a return or a throw below leaves behind
+    return pk::create<pkt::Lib>(ctx, stmt, out, [&](std::unique_ptr<pkt_prover>& p) {
+        p.reset(new pkt_prover());  // its destructor gives back what a return or a throw below leaves behind
         p->ctx = ctx;
         p->st = *stmt;
         p->pattern = pkt::io_pattern(*stmt);
@@ -87,20 +83,11 @@ int pkt_prover_create(pk_ctx* ctx, const pkt_statement* stmt, pkt_prover** out) 
             if (int rc = pkf_proof_bytes(&sides[which], &p->side_bytes[which])) return stop(rc, std::string("pkf_proof_bytes failed: ") + pkf_create_error());
         }
         p->staging.resize(p->side_bytes[0] + p->side_bytes[1]);
-        *out = p.release();
-        pkt::g_error.clear();
         return PK_OK;
-    } catch (...) {
-        return pk::out_of_host_memory(pkt::g_error);
-    }
+    });
 }
 
-int pkt_prover_destroy(pkt_prover* p) {
-    if (!p) return PK_OK;
-    const int rc = p->give_back();
-    delete p;
-    return rc;
-}
+int pkt_prover_destroy(pkt_prover* p) { return pk::destroy(p); }
 
 const char* pkt_last_error(const pkt_prover* p) { return p ? p->err.c_str() : "null prover"; }
 
@@ -158,11 +145,7 @@ int pkt_prove(pkt_prover* p, const uint64_t* const* d_f, const uint64_t* const* 
     const pkt_statement& st = p->st;
     if (!d_f || !d_t || !d_m || !len || (!proof_out && cap)) return fail(p, PK_ERR_BAD_ARG, "null pointer");
     const size_t len_f = p->side_bytes[PKT_SIDE_F], need = len_f + p->side_bytes[PKT_SIDE_T];
-    *len = need;
-    if (cap < need) return fail(p, PK_ERR_BAD_ARG, "the proof buffer holds " + std::to_string(cap) + " bytes, the proof has " + std::to_string(need));
-    if (st.n_bind && !bind) return fail(p, PK_ERR_BAD_ARG, "the statement binds elements: pass them");
-    std::string why;
-    if (!pkt::elements_below_p(bind, st.n_bind, "bind", why)) return fail(p, PK_ERR_BAD_ARG, why);
+    if (int rc = pk::proof_room_and_bind(p, need, cap, len, bind, st.n_bind)) return rc;
     try {
         pkt::Columns f{}, t{};
         if (!take_columns(d_f, st.w, st.c, f)) return fail(p, PK_ERR_BAD_ARG, "a column of f is NULL");

@@ -73,6 +73,13 @@ inline void fill_claims(const pkt_statement& s, const Challenges& ch, const fe* 
     put_fe(out->m_value, cp_t);
 }
 
+// the library's overload sets, for argument.hpp's templates (the proof's length comes from the fractional-sum library's C ABI)
+struct Lib {
+    static std::string& error() { return g_error; }
+    static bool ok(const pkt_statement* s, std::string& why) { return statement_ok(s, why); }
+    static std::string pattern(const pkt_statement& s) { return io_pattern(s); }
+};
+
 // P_a Q_b = P_b Q_a
 inline bool same_fraction(const fe& Pa, const fe& Qa, const fe& Pb, const fe& Qb) { return pk::fe_eq(pk::h_mul(Pa, Qb), pk::h_mul(Pb, Qa)); }
 

@@ -14,11 +14,7 @@ namespace {
 
 using pk::fe;
 
-void verdict(pkv_result* r, int check, uint64_t offset, const std::string& msg) {
-    pkv::Verdict v;
-    v.failed = check != PKV_CHECK_NONE, v.check = check, v.offset = offset, v.message = msg;
-    pkv::to_result(v, r);
-}
+using pk::verdict;
 
 // the two sides' lengths; a pkf refusal of a statement this library made is passed on with its reason
 int side_bytes(const pkt_statement& s, size_t out[2]) {
@@ -40,16 +36,7 @@ const char* pkt_create_error(void) { return pkt::g_error.c_str(); }
 
 unsigned pkt_count_lds_max_k(void) { return pkt::COUNT_LDS_MAX_K; }
 
-int pkt_io_pattern(const pkt_statement* stmt, uint8_t* buf, size_t cap, size_t* len) {
-    std::string why;
-    if (!len) return pkt::refuse("null pointer");
-    if (!pkt::statement_ok(stmt, why)) return pkt::refuse(why);
-    try {
-        return pk::pattern_out(pkt::io_pattern(*stmt), buf, cap, len);
-    } catch (...) {
-        return PK_ERR_OOM;
-    }
-}
+int pkt_io_pattern(const pkt_statement* stmt, uint8_t* buf, size_t cap, size_t* len) { return pk::pattern_out<pkt::Lib>(stmt, buf, cap, len); }
 
 int pkt_proof_bytes(const pkt_statement* stmt, size_t* len) {
     std::string why;
@@ -72,47 +59,27 @@ int pkt_verify(const pkt_statement* stmt, const uint8_t* io_pattern_or_null, siz
     try {
         pkv::Statement st;
         if (int rc = pk::parse_pattern(st, io_pattern_or_null, io_pattern_len, pkt::io_pattern(s), pkt::g_error)) return rc;
-        if (layer_out) *layer_out = 0;
-        if (side_out) *side_out = PKT_SIDE_F;
-        // framing first: both parts have a fixed length, so a proof of another length is judged before any part is read
         size_t part[2];
         if (int rc = side_bytes(s, part)) return rc;
-        const size_t at[2] = {0, part[0]}, total = part[0] + part[1];
-        if (len < total) return verdict(result, PKV_CHECK_TRANSCRIPT_SHORT, len, "the proof is shorter than its two parts"), PK_OK;
-        if (len > total) return verdict(result, PKV_CHECK_TRAILING_BYTES, total, "bytes left after the proof"), PK_OK;
-
-        // the outer transcript absorbs nothing of the proof
-        std::vector<uint8_t> bytes;
-        pk::put_canonical(bytes, bind, s.n_bind);
-        pkv::Verdict v;
-        pkv::Arthur A(st, bytes.data(), bytes.size(), v);
-        fe scratch[PKT_MAX_BIND];
+        const pk::TwoSides sides(part[0], part[1], side_out, layer_out, result);
+        if (!sides.framed(len)) return PK_OK;
         pkt::Challenges ch;
         ch.beta = pk::fe_one();
-        const bool walked = (!s.n_bind || A.next_scalars(s.n_bind, scratch)) && A.challenge_scalars(1, &ch.alpha) && (s.w == 1 || A.challenge_scalars(1, &ch.beta)) &&
-                            A.challenge_scalars(2, ch.seeds) && (A.done() || A.fail(PKV_CHECK_IO_PATTERN, "declared operations left after the outer transcript"));
-        if (!walked) {
-            v.offset = 0;
-            pkv::to_result(v, result);
-            return PK_OK;
-        }
-        const pkf_statement sides[2] = {pkt::side_f(s), pkt::side_t(s)};
+        if (!pk::squeeze_outer(st, bind, s.n_bind, {{1, &ch.alpha}, {s.w > 1, &ch.beta}, {2, ch.seeds}}, result)) return PK_OK;
+        const pkf_statement side[2] = {pkt::side_f(s), pkt::side_t(s)};
         fe frac[2][2], z[2][PKT_MAX_VARS], cq[2], cp;
-        for (int which = PKT_SIDE_F; which <= PKT_SIDE_T; which++) {
-            unsigned layer = 0;
-            const int rc = pkf_verify(&sides[which], nullptr, 0, (const uint64_t*)ch.seeds[which].v, nullptr, proof + at[which], part[which], (uint64_t*)frac[which],
-                                      (uint64_t*)z[which], which == PKT_SIDE_T ? (uint64_t*)cp.v : nullptr, (uint64_t*)cq[which].v, &layer, result);
-            if (rc) return pkt::g_error = pkf_create_error(), rc;
-            result->offset += at[which];
-            if (side_out) *side_out = which;
-            if (layer_out) *layer_out = layer;
-            if (!result->accepted) return PK_OK;
-        }
-        if (layer_out) *layer_out = 0;
+        if (int rc = sides.each([&](int which, unsigned& layer) {
+                const int r = pkf_verify(&side[which], nullptr, 0, (const uint64_t*)ch.seeds[which].v, nullptr, proof + sides.at[which], part[which],
+                                          (uint64_t*)frac[which], (uint64_t*)z[which], which == PKT_SIDE_T ? (uint64_t*)cp.v : nullptr, (uint64_t*)cq[which].v, &layer,
+                                          result);
+                if (r) pkt::g_error = pkf_create_error();
+                return r;
+            }))
+            return rc;
+        if (!result->accepted) return PK_OK;
         if (!pkt::same_fraction(frac[0][0], frac[0][1], frac[1][0], frac[1][1]))
-            return verdict(result, PKF_CHECK_FRACTION, at[1] + 128, "the two sides' fractions differ"), PK_OK;
-        verdict(result, PKV_CHECK_NONE, total, "");
-        if (side_out) *side_out = PKT_SIDE_F;  // accepted: no part to point at
+            return verdict(result, PKF_CHECK_FRACTION, sides.at[1] + 128, "the two sides' fractions differ"), PK_OK;
+        sides.accept();
         if (claims_out) pkt::fill_claims(s, ch, z[0], cq[0], z[1], cp, cq[1], claims_out);
         return PK_OK;
     } catch (...) {
