@@ -218,6 +218,24 @@ int pk_probe_tuple_set_grid(struct pkt_prover *p, unsigned grid);
 int pk_probe_tuple_profile(const struct pkt_prover *p, double *leaf_ms, double *count_ms, double *side_ms2);
 unsigned pk_probe_tuple_leaf_items(void);
 
+/* libprovekit_memcheck.so's two leaf kernels by themselves (csrc/memcheck/kernels.hpp) with the grid its C ABI does not carry (1 .. 1024
+ * workgroups; 0: the library's rule, pk_probe_mem_leaf_items rows per lane).  No bit of the tables depends on it
+ * (tests/test_gpu_memcheck.py).  Arguments as pkm_leaves; ms2: the device time of the pass over the operations, then the cells.  Blocking.
+ * A pkm_prover's test and benchmark knobs (csrc/memcheck/prover.hpp), host only: pk_probe_mem_set_grid sets the grid of every kernel of
+ * its traces and proofs from the next call on; pk_probe_mem_profile: in milliseconds, trace_ms4 the last pkm_trace's key, sort, resolve
+ * and count phases and *leaf_ms the last proof's two leaf launches in device time, and side_ms3[PKM_SIDE_*] the three inner proofs in
+ * host time.  pk_probe_mem_trace_items: the rows per lane the trace builder's grid rule aims at; pk_probe_mem_count_lds_max_n: up to
+ * 2^this bins the time side's histogram is counted in LDS. */
+struct pkm_prover;
+struct pkm_columns;
+int pk_probe_mem_leaves(pk_ctx *ctx, unsigned n, unsigned k, const struct pkm_columns *cols, const uint64_t *gamma, const uint64_t *beta, uint64_t *d_ops,
+                        uint64_t *d_mem, uint64_t *d_f_or_null, unsigned grid, float *ms2);
+int pk_probe_mem_set_grid(struct pkm_prover *p, unsigned grid);
+int pk_probe_mem_profile(const struct pkm_prover *p, double *trace_ms4, double *leaf_ms, double *side_ms3);
+unsigned pk_probe_mem_leaf_items(void);
+unsigned pk_probe_mem_trace_items(void);
+unsigned pk_probe_mem_count_lds_max_n(void);
+
 /* csrc/witness.hip's thresholds (csrc/witness_shape.hpp) and the shape of a levelled builder list (witness.hip here), for
  * tests/test_witness_edge_cases_host.py and tests/test_gpu_witness_edges.py.  Host only.  pk_probe_witness_phases: *n_phases = the
  * phases of postcard(Vec<WitnessBuilder>) after levelling (two per level); with cap >= *n_phases, widths[ph] = the items of phase
