@@ -72,12 +72,18 @@ int pk_selftest_permute(uint64_t l[4], uint64_t r[4]) {
 }
 
 // op: 0 fe_mul29(a,b)  1 compress v2  2 compress v1  3 from_mont  4 a*b*2^-256 via mont256_29  5 a^2*2^-256 via sqr256_29
-// a, b, out: n field elements (4 x u64 each).  Host only; no device needed.
+// 6..26: the rest of the table in selftest_ops.hpp (conversions, lazy reductions, wide_reduce, the scaled path, dot29, the inverse,
+// the Shoup product, the NTT's constants)
+// the carry chains of fe.hpp: 27 fe_add(a,b)  28 fe_sub(a,b)  29 fe_neg(a)  30 fe_dbl(a)  31 {a < b, a == b, b < a} in words 0..2
+// 32/33/34 cond_sub_kp<1/2/4>(a)  35 fe_reduce_any(a)  36 fe_fold(a, b, one) == b  37 fe_fold(a, b, a)  38 pack_canon29(unpack29(a))
+// a, b, out: n field elements (4 x u64 each); b may be NULL for the one-operand ops.  Host only; no device needed.
 int pk_selftest_arith(int op, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n) {
-    if (!a || !out || (!b && (op == 0 || op == 1 || op == 2 || op == 4 || op == 15 || op == 16 || op == 19 || op == 20 || op == 24 || op == 25))) return PK_ERR_BAD_ARG;
+    const bool two = op == 0 || op == 1 || op == 2 || op == 4 || op == 15 || op == 16 || op == 19 || op == 20 || op == 24 || op == 25 ||
+                     op == 27 || op == 28 || op == 31 || op == 36 || op == 37;
+    if (!a || !out || (!b && two)) return PK_ERR_BAD_ARG;
     for (size_t i = 0; i < n; i++) {
         fe x = load_host(a + 4 * i), y = b ? load_host(b + 4 * i) : x;
-        if (op < 0 || op > 26) return PK_ERR_BAD_ARG;
+        if (op < 0 || op > 38) return PK_ERR_BAD_ARG;
         fe r = selftest_op(op, x, y);
         store_host(out + 4 * i, r);
     }

@@ -1,5 +1,5 @@
 // selftest_ops.hpp -- the table of arithmetic self-test operations: each op runs one piece of the library's __host__ __device__
-// arithmetic (fe29.hpp, skyscraper29.hpp, skyscraper29s.hpp, feinv.hpp, reduce.hpp) exactly as the kernels compile it.  Two users:
+// arithmetic (fe.hpp, fe29.hpp, skyscraper29.hpp, skyscraper29s.hpp, feinv.hpp, reduce.hpp) exactly as the kernels compile it.  Two users:
 // pk_selftest_arith (selftest.hip, in the product: the CPU suite checks the host build against the oracle without a GPU) and
 // pk_probe_arith_device (tools/probes, not shipped: the same ops run by a kernel, for a device-vs-host codegen diff).
 #pragma once
@@ -102,6 +102,25 @@ PK_HD fe selftest_op(int op, const fe& x, const fe& y) {
         case 21: r = fe_inverse_mont(x); break;   // feinv.hpp: Montgomery in, Montgomery out (0 -> 0)
         case 22: r = fe_inverse_plain(x); break;  // plain integers mod p, constant sequence
         case 23: r = fe_inverse_plain_var(x); break;  // the same, variable-time steps
+        // fe.hpp: the add-/subtract-with-carry chains every kernel reduces through, one op per function so that a wrong carry-out or a
+        // select keyed on the wrong borrow shows in this op's bits (tests/fe_carry_cases.py builds the operands that ride the chains)
+        case 27: r = fe_add(x, y); break;  // 27..30: x, y < p
+        case 28: r = fe_sub(x, y); break;
+        case 29: r = fe_neg(x); break;
+        case 30: r = fe_dbl(x); break;
+        case 31:  // the comparisons, any 256-bit x, y: word 0 = x < y, word 1 = x == y, word 2 = y < x
+            r = fe_zero();
+            r.v[0] = fe_lt(x, y) ? 1u : 0u;
+            r.v[1] = fe_eq(x, y) ? 1u : 0u;
+            r.v[2] = fe_lt(y, x) ? 1u : 0u;
+            break;
+        case 32: r = cond_sub_kp<1>(x); break;  // 32..35: any 256-bit x
+        case 33: r = cond_sub_kp<2>(x); break;
+        case 34: r = cond_sub_kp<4>(x); break;
+        case 35: r = fe_reduce_any(x); break;
+        case 36: r = fe_fold(x, y, fe_one()); break;  // x, y < p: x + 1 (y - x) = y bit for bit (the add reduces exactly when y < x)
+        case 37: r = fe_fold(x, y, x); break;         // x, y < p: x + x (y - x) 2^-256
+        case 38: r = pack_canon29(unpack29<0>(x)); break;  // x < 2p: the borrow chain behind every product's last step
         default: break;
     }
     return r;

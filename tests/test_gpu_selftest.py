@@ -8,8 +8,9 @@ pytestmark = pytest.mark.gpu
 
 
 # 15-20: the scaled Skyscraper path and dot29; 21-23: the safegcd inverse (feinv.hpp), both step forms; 24-26: the Shoup product, its
-# lazy-limb form and the NTT's in-register constants
-@pytest.mark.parametrize("op", list(range(27)))
+# lazy-limb form and the NTT's in-register constants; 27-38: the carry chains of fe.hpp, fe_fold and pack_canon29 (every one accepts
+# operands below p; their edge operands are in tests/test_gpu_fe_carry.py)
+@pytest.mark.parametrize("op", list(range(39)))
 def test_device_equals_host(ctx, oracle, op):
     from provekit_amd._lib import lib
     from tools.pk_probes import lib as probes

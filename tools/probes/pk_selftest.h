@@ -12,7 +12,10 @@ extern "C" {
 /* self-test (host only, no device)
  * Runs the library's __host__ __device__ arithmetic (the same source the kernels compile) on the CPU:
  * op 0: a*b*2^-256 mod p (ark-ff mul)   1: Skyscraper v2 compress   2: v1 compress   3: from Montgomery
- * 4/5: the lazy 29-bit product / square followed by exact reduction.  n elements of 4 x u64 each. */
+ * 4/5: the lazy 29-bit product / square followed by exact reduction.  n elements of 4 x u64 each.
+ * 27..38: the carry chains of fe.hpp -- 27 fe_add  28 fe_sub  29 fe_neg  30 fe_dbl  31 {a < b, a == b, b < a} in words 0..2
+ * 32/33/34 cond_sub_kp<1/2/4>  35 fe_reduce_any  36 fe_fold(a, b, one)  37 fe_fold(a, b, a)  38 pack_canon29(unpack29(a))
+ * (the whole table: csrc/selftest_ops.hpp) */
 /* host-only pieces of the transcript: domain-separator tag, one sponge permutation on canonical (l, r) */
 int pk_selftest_keccak_tag(const uint8_t *data, size_t len, uint8_t tag[32]);
 int pk_selftest_permute(uint64_t l[4], uint64_t r[4]);
