@@ -289,6 +289,13 @@ int pk_ctx_set_latency_mode(pk_ctx* ctx, int on) {
     return PK_OK;
 }
 
+int pk_selftest_set_host_tail(pk_ctx* ctx, unsigned log2_len) {
+    if (!ctx) return PK_ERR_BAD_ARG;
+    if (log2_len > PK_HOST_TAIL_MAX_LOG2) return set_err(ctx, PK_ERR_BAD_ARG, "bad argument: host tail threshold is 0 (off) or 1 .. %d", PK_HOST_TAIL_MAX_LOG2);
+    ctx->host_tail_log2 = log2_len;
+    return PK_OK;
+}
+
 }  // extern "C"
 
 namespace pk {

@@ -19,6 +19,12 @@ struct pk_prof_rec {
 
 struct pk_comm;  // comm.hip
 
+// host tail: the default threshold (EXPERIMENTS.md, the round that measured it) and the longest table the setter accepts
+#ifndef PK_HOST_TAIL_DEFAULT_LOG2
+#define PK_HOST_TAIL_DEFAULT_LOG2 10
+#endif
+#define PK_HOST_TAIL_MAX_LOG2 11
+
 struct pk_ctx {
     int device = 0;
     pk_comm* comm = nullptr;  // optional: this context's rank in a sharded commit (comm.hip); null = single GPU
@@ -47,6 +53,10 @@ struct pk_ctx {
     // workgroup slots while it waits, which is wasted capacity when other provers share the chip.
     bool latency_mode = false;
     unsigned gate_seq = 0;  // sequence number of the last gate handed out (reduce.hpp)
+    // Host tail (pk_selftest_set_host_tail; host_tail.hpp): once the tables of a prover sumcheck are no longer than 2^host_tail_log2 entries
+    // they are brought to the host thread once and the remaining rounds, folds and weights run there -- a round over a few hundred
+    // entries is cheaper than its launch, synchronisation and polling wait.  0 = off; a context in a device set never takes it.
+    unsigned host_tail_log2 = PK_HOST_TAIL_DEFAULT_LOG2;
     void* d_ws = nullptr;  // large reusable workspace (NTT scratch); grows, never shrinks
     void* d_ztab = nullptr;  // 256 field elements: z^t for the point of the univariate evaluation in flight (mle.hip)
     size_t ws_bytes = 0;

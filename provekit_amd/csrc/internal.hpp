@@ -116,6 +116,9 @@ int to_coeffs_generated(pk_ctx* ctx, unsigned m, const uint64_t* d_wit, size_t n
 // r = NULL with gate_seq != 0: the challenge arrives through the gate (latency mode)
 int fold_pairs2(pk_ctx* ctx, const uint64_t* d_v0, uint64_t* d_out0, const uint64_t* d_v1, uint64_t* d_out1, size_t len, const uint64_t* r,
                 unsigned gate_seq = 0);
+// count (1 .. 4) runs of n[k] elements at d_src[k], back to back into host_out: one launch that writes the context's mailbox, one
+// synchronisation (the host tail's transfer of a sumcheck's short tables; at most 4 * 2^PK_HOST_TAIL_MAX_LOG2 elements in all)
+int tables_to_host(pk_ctx* ctx, const uint64_t* const* d_src, const size_t* n, unsigned count, uint64_t* host_out);
 // launch only: round results go to the pinned page under sequence number *red_seq_out.  gate_seq != 0 (latency mode, folding rounds
 // only): the folding challenge is not known yet -- the kernel waits for sumcheck_gate_publish(ctx, gate_seq, challenge).
 // The weight of the cubic round's pairs is d_weight, one of two kinds:

@@ -695,6 +695,23 @@ __global__ void fold_pairs_kernel(const fe* __restrict__ v0, fe* __restrict__ ou
     }
 }
 
+// up to four runs of elements, back to back into dst -- the context's mailbox, pinned host memory the device writes directly: the short
+// tables of a sumcheck reach the host thread in one launch and no copy operation (prover.hip, the host tail)
+struct table_runs {
+    const fe* src[4];
+    size_t n[4];
+};
+__global__ __launch_bounds__(256) void tables_to_host_kernel(table_runs R, fe* __restrict__ dst) {
+    PK_LATENCY_PRIO();
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    size_t base = 0;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < R.n[k]; i += stride) fe_store(dst + base + i, fe_load(R.src[k] + i));
+        base += R.n[k];
+    }
+}
+
 // ---------------------------------------------------------------- S5: dot product(s)
 // <w,f> and optionally <w,g> in one pass over w (the statement needs both sums, whir_r1cs.rs:401-405)
 template <int NV>
@@ -1134,6 +1151,31 @@ int fold_pairs2(pk_ctx* ctx, const uint64_t* d_v0, uint64_t* d_out0, const uint6
                                                                                      len / 2, r ? to_arg(r) : fe_arg{},
                                                                                      gate_seq ? gate_for(ctx, gate_seq) : gate_none());
     PK_LAUNCH_CHECK(ctx);
+    return PK_OK;
+}
+int tables_to_host(pk_ctx* ctx, const uint64_t* const* d_src, const size_t* n, unsigned count, uint64_t* host_out) {
+    PK_REQUIRE(ctx, d_src && n && host_out && count >= 1 && count <= 4, "one to four runs");
+    table_runs R{};
+    size_t total = 0;
+    for (unsigned k = 0; k < count; k++) {
+        PK_REQUIRE(ctx, d_src[k] || !n[k], "null pointer");
+        R.src[k] = (const fe*)d_src[k];
+        R.n[k] = n[k];
+        total += n[k];
+    }
+    if (!total) return PK_OK;
+    PK_REQUIRE(ctx, total <= ((size_t)4 << PK_HOST_TAIL_MAX_LOG2), "short tables only");
+    fe* m_dst = nullptr;
+    int rc = mail_alloc(ctx, 32 * total, (void**)&m_dst);
+    if (rc) return rc;
+    {
+        ProfScope prof(ctx, "tables_to_host");
+        tables_to_host_kernel<<<grid_for(ctx, total, 256), 256, 0, ctx->stream>>>(R, m_dst);
+    }
+    PK_LAUNCH_CHECK(ctx);
+    rc = sync_stream(ctx);  // the mailbox rewinds: what it holds is taken out before anything else is allocated there
+    if (rc) return rc;
+    memcpy(host_out, m_dst, 32 * total);
     return PK_OK;
 }
 

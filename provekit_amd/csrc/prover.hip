@@ -2,7 +2,8 @@
 //
 // This is the compiled host side of the drop-in (the reference's is Rust): transcript, challenge bookkeeping and the
 // O(m_0^2) blinding algebra run here on the CPU; every data-parallel step is a call into this library's kernels on
-// buffers that never leave HBM.  One proof allocates nothing: all device memory comes from a per-scheme arena.
+// buffers that never leave HBM -- but for the sumchecks' short tails: tables of at most 2^host_tail_log2 entries come to the host once and
+// finish there (host_tail.hpp; sumcheck_round_loop below).  One proof allocates no device memory: it all comes from a per-scheme arena.
 //
 //   pk_prove -> prove, one stage per step of the reference (struct Proof)
 //    +- commit_witness (whir_r1cs.rs:57-69, 182-209): mask / random polynomial on device, to_coeffs x2, commit_batch
@@ -23,6 +24,7 @@
 #include <string>
 #include <vector>
 
+#include "host_tail.hpp"
 #include "internal.hpp"
 #include "shard_map.hpp"
 #include "prover_transcript.hpp"
@@ -88,6 +90,9 @@ struct Arena {
 
 inline uint64_t* U(fe* p) { return (uint64_t*)p; }
 inline const uint64_t* U(const fe* p) { return (const uint64_t*)p; }
+
+// the context's host-tail threshold in entries (pk_selftest_set_host_tail); 0 = never: switched off, or the context is a rank of a device set
+inline size_t host_tail_len(const pk_ctx* ctx) { return !ctx->comm && ctx->host_tail_log2 ? (size_t)1 << ctx->host_tail_log2 : 0; }
 
 // ------------------------------------------------------------------ one proof over a device set
 // Besides the commits (tree.hip), the linear-size arrays of a sharded proof are split over the G ranks:
@@ -323,24 +328,43 @@ bool rows_at_equal_stride3(fe* const* d_weights, const size_t* weight_len, unsig
 // BEFORE round t's result is read, gated on the challenge the host publishes once it has squeezed it, and meanwhile() runs under that
 // kernel; the round trip then costs the link, not a launch + sync.  A gated kernel waits on the host: PendingGate releases it on
 // whatever path leaves the round.  Otherwise every round is a synchronous call that first folds by the previous challenge.
+// The host tail (pk_selftest_set_host_tail, host_tail.hpp): once what comes next -- a round, or the closing fold -- would read tables of s.len
+// entries or fewer than the context's threshold, s.to_host(t) brings them over as they stand (one launch, one synchronisation) and from
+// there on the loop is the host's: host_round(t, fold) applies the pending fold by the previous challenge ON THE HOST, after the copy,
+// then sums; host_fold closes.  In latency mode the round at the boundary is not enqueued behind a gate.  Only a sumcheck whose
+// host_capable() holds: not sharded.
 template <class S>
 int sumcheck_round_loop(pk_ctx* ctx, Transcript& T, unsigned rounds, bool pipelined, S& s) {
     unsigned red_cur = 0, red_next = 0;
     uint64_t f[4];  // the previous round's challenge
-    if (pipelined) CK(s.launch(0, nullptr, 0, &red_cur));
+    const size_t tail = host_tail_len(ctx);
+    auto host_next = [&] { return s.on_host() || (tail && s.host_capable() && s.len <= tail); };
+    bool queued = false;  // latency mode: this round's kernel is in the queue already ...
+    bool closed = false;  // ... and so is the closing fold
+    if (pipelined && !host_next()) {
+        CK(s.launch(0, nullptr, 0, &red_cur));
+        queued = true;
+    }
     for (unsigned t = 0; t < rounds; t++) {
         PendingGate gate(ctx);
         const bool more = t + 1 < rounds;
-        if (pipelined && (more || s.closing_fold())) {
-            gate.arm(sumcheck_gate_next(ctx));
-            CK(more ? s.launch(t + 1, nullptr, gate.seq, &red_next) : s.fold(nullptr, gate.seq));
-        }
-        s.meanwhile(t);
+        bool queued_next = false;
         uint64_t out[12];
-        if (pipelined) {
+        if (!queued && host_next()) {  // the tables only shrink: once true, true for the rest of the loop
+            CK(s.to_host(t));
+            s.meanwhile(t);
+            s.host_round(t, t ? f : nullptr, out);
+        } else if (pipelined) {
+            if ((more || s.closing_fold()) && !host_next()) {
+                gate.arm(sumcheck_gate_next(ctx));
+                CK(more ? s.launch(t + 1, nullptr, gate.seq, &red_next) : s.fold(nullptr, gate.seq));
+                (more ? queued_next : closed) = true;
+            }
+            s.meanwhile(t);
             CK(sumcheck_collect_spin(ctx, s.nsums(t), red_cur, out));
             red_cur = red_next;
         } else {
+            s.meanwhile(t);
             CK(s.before_sync_launch());
             Across ac(ctx, s.sharded);
             CK(ac.rc);
@@ -355,8 +379,16 @@ int sumcheck_round_loop(pk_ctx* ctx, Transcript& T, unsigned rounds, bool pipeli
         gate.publish(r);
         h_store(f, r);
         s.record(t, msg, r);
+        queued = queued_next;
     }
-    if (!pipelined && rounds && s.closing_fold()) CK(s.fold(f, 0));
+    if (rounds && !closed && s.closing_fold()) {
+        if (host_next()) {
+            CK(s.to_host(rounds));
+            s.host_fold(f);
+        } else {
+            CK(s.fold(f, 0));
+        }
+    }
     return PK_OK;
 }
 
@@ -373,6 +405,11 @@ struct WhirProver {
     fe* bp[2] = {};        // sumcheck operands: p = evaluations of c over the hypercube, w = combined weights; ping-pong halves
     fe* bw[2] = {};
     fe* gathered[4] = {};  // sharded: where p, w go once the blocks are short (p0, p1, w0, w1)
+    // the host tail: once p and w are short they live here, folded in place, for the rest of the opening -- the rounds, the closing folds
+    // and the equality weights of the later rounds.  d_c stays on the device: it is folded, re-committed and evaluated there.
+    bool host = false;
+    std::vector<fe> hp, hw;
+    const fe* h_weight = nullptr;  // an opening that starts on the host: the caller's host copy of its one statement weight
     int cur = 0;
     size_t len;             // local length of p and w
     std::vector<fe> rs;     // the challenges of the last sumcheck_rounds call
@@ -420,6 +457,10 @@ struct WhirProver {
             g = h_mul(g, gamma);
         }
         *next = g;
+        if (host) {  // never a rank's block: lg = 0
+            host_tail::eq_accumulate(hw.data(), nv, pts.data(), scales.data(), q, overwrite != 0);
+            return PK_OK;
+        }
         if (!defer) return pk_eq_accumulate(ctx, U(dst), nl, (const uint64_t*)pts.data(), (const uint64_t*)scales.data(), (unsigned)q, overwrite);
         first.a = opening_first{};
         first.a.d_w = U(dst);
@@ -476,6 +517,38 @@ struct WhirProver {
         flip();
         return PK_OK;
     }
+    // the host tail: p and w as they stand -- a pending fold is applied on the host, by host_round -- and from then on for good
+    bool on_host() const { return host; }
+    bool host_capable() const { return !sharded; }
+    int to_host(unsigned) {
+        if (host) return PK_OK;
+        if (first.pending) return set_err(ctx, PK_ERR_HIP, "host tail: a round's weights are still to be formed on the device");
+        hp.resize(len);
+        hw.resize(len);
+        const uint64_t* src[2] = {U(bp[cur]), U(bw[cur])};
+        const size_t cnt[2] = {len, len};
+        std::vector<fe> both(2 * len);
+        CK(tables_to_host(ctx, src, cnt, 2, U(both.data())));
+        std::copy(both.begin(), both.begin() + len, hp.begin());
+        std::copy(both.begin() + len, both.end(), hw.begin());
+        host = true;
+        return PK_OK;
+    }
+    // before new weights join w, or an opening's last stage: tables this short move now, so that the weights are formed on the host too
+    int maybe_to_host() {
+        const size_t tail = host_tail_len(ctx);
+        return !host && tail && !sharded && len <= tail ? to_host(0) : PK_OK;
+    }
+    void host_round(unsigned t, const uint64_t* fold, uint64_t out[12]) {
+        const fe r = fold ? h_load(fold) : fe_zero();
+        len = host_tail::quadratic_round(hp.data(), hw.data(), len, fold ? &r : nullptr, nsums(t), out);
+    }
+    void host_fold(const uint64_t* r) {
+        const fe rr = h_load(r);
+        host_tail::fold_pairs(hp.data(), len, rr);
+        host_tail::fold_pairs(hw.data(), len, rr);
+        len /= 2;
+    }
     int before_sync_launch() { return PK_OK; }
     void meanwhile(unsigned) {}
     unsigned message(unsigned t, uint64_t out[12], fe msg[4]) {
@@ -510,8 +583,20 @@ struct WhirProver {
 
     // the working polynomial, the sumcheck tables, the initial weights and the first k sumcheck rounds
     // weight_sums[i * batch + b] = <weight i, polynomial b>, as the transcript holds them (may be null: the first round then forms three sums)
-    int start(fe* const* d_weights, const size_t* weight_len, unsigned n_weights, const fe* weight_sums) {
+    // h_evals != null (an opening no longer than the host tail's threshold, a batch of two, at most one weight -- the blinding proof): the
+    // caller's host copy of the two evaluation tables, 2^n entries each, back to back, and h_w that of the weight.  p0 and w0 are then
+    // formed on the host and never exist on the device; only the working polynomial does.
+    int start(fe* const* d_weights, const size_t* weight_len, unsigned n_weights, const fe* weight_sums, const fe* h_evals, const fe* h_w) {
         const size_t N = (size_t)1 << n;
+        if (h_evals) {
+            PK_REQUIRE(ctx, !sharded && C.batch == 2 && n_weights <= 1 && (!n_weights || (h_w && weight_len[0] <= N)),
+                       "an opening that starts on the host: batch 2, one weight");
+            host = true;
+            h_weight = h_w;
+            hp.resize(N);
+            hw.resize(N);
+            host_tail::lincomb2(hp.data(), h_evals, C.beta, h_evals + N, N);
+        }
         ALLOC(dc, N);
         d_c = dc;
         ALLOC(p0, B0);
@@ -525,8 +610,10 @@ struct WhirProver {
         // The opening's first launch (mle.hip opening_first_launch): p0, w0 and round 0's sums from one pass over the two evaluation tables
         // and the statement rows.  Everything else -- a rank's block, another batch, no tables, rows it does not take -- keeps the sequence below.
         const bool rows3 = rows_at_equal_stride3(d_weights, weight_len, n_weights);
-        const bool fused = pair && !sharded && B0 >= 2 && k >= 1 && (rows3 || n_weights == 1) && weight_len[0] <= B0;
-        if (fused) {
+        // (tables that round 0 takes to the host at once are formed by the plain sequence: the first launch would leave them pending)
+        const size_t tail = host_tail_len(ctx);
+        const bool fused = !host && !(tail && !sharded && B0 <= tail) && pair && !sharded && B0 >= 2 && k >= 1 && (rows3 || n_weights == 1) && weight_len[0] <= B0;
+        if (fused || host) {  // the working polynomial alone: p0 comes from the first launch, or stands on the host already
             h_store(first.beta, C.beta);
             CK(lincomb2(ctx, U(d_c), U(C.polys[0]), first.beta, U(C.polys[1]), N));
         } else if (pair) {  // the coefficient and the evaluation combination of a batch of two in one launch
@@ -536,7 +623,8 @@ struct WhirProver {
         } else {
             CK(batch_combine(d_c, C.polys, 0, N));
         }
-        if (have_evals) {
+        if (host) {  // p0 stands, on the host
+        } else if (have_evals) {
             if (!pair) CK(batch_combine(p0, C.evals, off0, B0));  // to_evals is linear: combine the tables the committer kept instead of transforming d_c
         } else if (!sharded) {
             CK(pk_to_evals_into(ctx, U(d_c), U(p0), n));
@@ -581,7 +669,8 @@ struct WhirProver {
             uint64_t s[4];
             h_store(s, g);
             const size_t cnt = in_block(weight_len[i], off0, B0);
-            if (cnt && !rows3 && !fused) CK(pk_fe_axpy(ctx, U(w0), s, U(d_weights[i] + off0), cnt));
+            if (host) host_tail::axpy(hw.data(), g, h_weight, cnt);
+            else if (cnt && !rows3 && !fused) CK(pk_fe_axpy(ctx, U(w0), s, U(d_weights[i] + off0), cnt));
             if (weight_sums) claim = h_add(claim, h_mul(g, batched(weight_sums + (size_t)i * C.batch, 1)));
             g = h_mul(g, gamma);
         }
@@ -635,7 +724,9 @@ struct WhirProver {
             fe g;
             // not a rank's block: the round's first sumcheck launch adds them.  At every number of points: the fused kernel runs at three waves
             // per SIMD where eq_accumulate_kernel has four, and the round of 110 points still came out ahead (EXPERIMENTS.md round 29)
-            CK(eq_weights(bw[cur], nv, zs, gamma, 0, &g, /*defer=*/!sharded && len >= 2 && k >= 1));
+            // Tables short enough for the host tail go there first, and the weights join w on the host.
+            CK(maybe_to_host());
+            CK(eq_weights(bw[cur], nv, zs, gamma, 0, &g, /*defer=*/!host && !sharded && len >= 2 && k >= 1));
             have_claim = false;  // the new weights' sums include the folded polynomial at the STIR points, which the prover never evaluates
             // W3
             CK(sumcheck_rounds(k));
@@ -679,7 +770,11 @@ struct WhirProver {
         const bool sh = whir_sharded(ctx, n);  // the eq table and the dot products by blocks, like the weights themselves
         std::vector<fe> evals(n_weights);
         const bool rows3 = rows_at_equal_stride3(d_weights, weight_len, n_weights);
-        if (!sh && (rows3 || n_weights == 1)) {  // without the table: each lane forms its entries from the point's half tables
+        if (h_weight) {  // the opening started on the host: its one weight is there too
+            uint64_t o[4] = {};
+            host_tail::dot_rows_eq(h_weight, 0, 1, point.data(), n, weight_len[0], o);
+            evals[0] = h_load(o);
+        } else if (!sh && (rows3 || n_weights == 1)) {  // without the table: each lane forms its entries from the point's half tables
             uint64_t o[12] = {};
             CK(dot_rows_eq(ctx, U(d_weights[0]), rows3 ? (size_t)(d_weights[1] - d_weights[0]) : 0, n_weights, (const uint64_t*)point.data(), n,
                            weight_len[0], o));
@@ -713,9 +808,9 @@ struct WhirProver {
     }
 };
 int whir_prove(pk_ctx* ctx, Arena& A, const pk_whir_config& cfg, const Commitment& C, fe* const* d_weights, const size_t* weight_len,
-               unsigned n_weights, const fe* weight_sums, Transcript& T) {
+               unsigned n_weights, const fe* weight_sums, Transcript& T, const fe* h_evals = nullptr, const fe* h_weight = nullptr) {
     WhirProver P(ctx, A, cfg, C, T);
-    CK(P.start(d_weights, weight_len, n_weights, weight_sums));
+    CK(P.start(d_weights, weight_len, n_weights, weight_sums, h_evals, h_weight));
     CK(P.rounds());
     return P.deferred_hint(d_weights, weight_len, n_weights);
 }
@@ -990,6 +1085,32 @@ struct ZkRounds {
     fe* ztmp;
     fe gp[4];        // the blinding polynomial's coefficients of the round
     uint64_t P[4];   // P_t = prod_{k<t} eq(r_k, alpha_k)
+    // the host tail, from round t0 on: a, b, c as they stood before round t0's fold, and the levels E_t0 .. of z[3], back to back
+    bool host = false;
+    unsigned t0 = 0;
+    std::vector<fe> h;  // a | b | c (n0 entries each) | levels
+    size_t n0 = 0;
+
+    bool on_host() const { return host; }
+    bool host_capable() const { return !sharded && r; }  // the Level form only
+    int to_host(unsigned t) {
+        if (host) return PK_OK;
+        t0 = t;
+        n0 = len;
+        const size_t nlev = M >> t;  // levels t .. (M >> t) - 1 entries, and the buffer's last element
+        const uint64_t* src[4] = {U(z[0]), U(z[1]), U(z[2]), U(z[3] + (M - nlev))};
+        const size_t cnt[4] = {len, len, len, nlev};
+        h.resize(3 * len + nlev);
+        CK(tables_to_host(ctx, src, cnt, 4, U(h.data())));
+        host = true;
+        return PK_OK;
+    }
+    void host_round(unsigned t, const uint64_t* fold, uint64_t out[12]) {
+        const fe f = fold ? h_load(fold) : fe_zero();
+        const fe* E = h.data() + 3 * n0 + ((M >> t0) - (M >> t));  // level E_t
+        len = host_tail::cubic_round(h.data(), h.data() + n0, h.data() + 2 * n0, E, len, fold ? &f : nullptr, out);
+    }
+    void host_fold(const uint64_t*) {}  // no closing fold
 
     int nsums(unsigned) const { return 3; }
     int launch(unsigned t, const uint64_t* fold, unsigned gate_seq, unsigned* red_seq) {  // in place; the level E_t or the eq array
@@ -1063,13 +1184,25 @@ int Proof::prove_blinding() {
         wv[4 * i + 3] = h_mul(wv[4 * i + 2], alpha[i]);
     }
     ALLOC(d_bw, nbw);
-    CK(pk_memcpy_h2d(ctx, d_bw, wv.data(), 32 * nbw));
     uint64_t fg[8];
-    CK(pk_dot2(ctx, U(d_bw), U(B.f_evals), U(B.g_evals), nbw, fg));
+    // The host tail: a blinding opening no longer than the threshold never puts its sumcheck on the device.  The two evaluation tables
+    // come over once; the statement's two sums, the opening's tables and its deferred hint are formed from them and from wv on the host.
+    const size_t NB2 = (size_t)2 << s->nb, tail = host_tail_len(ctx);
+    std::vector<fe> h_evals;
+    if (tail && NB2 <= tail) {
+        h_evals.resize(2 * NB2);
+        const uint64_t* src[2] = {U(B.f_evals), U(B.g_evals)};
+        const size_t cnt[2] = {NB2, NB2};
+        CK(tables_to_host(ctx, src, cnt, 2, U(h_evals.data())));
+        host_tail::dot2(wv.data(), h_evals.data(), h_evals.data() + NB2, nbw, fg);
+    } else {
+        CK(pk_memcpy_h2d(ctx, d_bw, wv.data(), 32 * nbw));
+        CK(pk_dot2(ctx, U(d_bw), U(B.f_evals), U(B.g_evals), nbw, fg));
+    }
     const fe sums[2] = {h_load(fg), h_load(fg + 4)};
     T.add_scalars(sums, 2);
-    fe* wts[1] = {d_bw};
-    return whir_prove(ctx, A, s->whir_hiding, B.com, wts, &nbw, 1, sums, T);
+    fe* wts[1] = {d_bw};  // on the host path never read: the weight is wv
+    return whir_prove(ctx, A, s->whir_hiding, B.com, wts, &nbw, 1, sums, T, h_evals.empty() ? nullptr : h_evals.data(), h_evals.empty() ? nullptr : wv.data());
 }
 
 // --- the statement over the witness commitment (whir_r1cs.rs:81-91): external rows, their six sums, the claimed_evaluations hint

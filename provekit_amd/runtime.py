@@ -92,6 +92,10 @@ class Context:
         """pk_ctx_set_latency_mode: sumcheck rounds enqueued one ahead behind a host-published gate (one proof at a time only)"""
         self._check(lib.pk_ctx_set_latency_mode(self.handle, 1 if on else 0))
 
+    def set_host_tail(self, log2_len: int):
+        """pk_selftest_set_host_tail: sumcheck tables of at most 2^log2_len entries finish on the host thread (0 = never)"""
+        self._check(lib.pk_selftest_set_host_tail(self.handle, log2_len))
+
     def comm_info(self):
         r, w, k = C.c_int(), C.c_int(), C.c_int()
         self._check(lib.pk_comm_info(self.handle, C.byref(r), C.byref(w), C.byref(k)))

@@ -54,6 +54,14 @@ int pk_selftest_sumcheck_quadratic_claim(pk_ctx *ctx, const uint64_t *d_f, const
  * in-process stand-in tests/stub_rccl: real RCCL refuses two ranks on one GPU) */
 int pk_selftest_set_hook(int which, long value);
 
+/* The host tail's threshold of one context (csrc/host_tail.hpp), for the suite and for threshold sweeps; the build's default
+ * (PK_HOST_TAIL_DEFAULT_LOG2, csrc/ctx.hpp) applies where this is never called.  Once the tables of one of pk_prove's sumchecks are no longer
+ * than 2^log2_len entries they are brought to the calling thread once and the remaining rounds, the closing fold and the equality weights
+ * that join them run there; an opening whose polynomial is that short (the blinding proof) forms its tables there from the start.  The
+ * proof's bytes do not change.  log2_len = 0: off, exactly the device path; 1 .. 11 otherwise (anything else is refused).  A context that is
+ * a rank of a device set ignores the setting. */
+int pk_selftest_set_host_tail(pk_ctx *ctx, unsigned log2_len);
+
 #ifdef __cplusplus
 }
 #endif
