@@ -68,6 +68,14 @@ int proof_room_and_bind(Prover* p, size_t need, size_t cap, size_t* len, const u
 
 inline bool is_zero(const fe& x) { return fe_eq(x, fe_zero()); }
 
+// I(z) = sum_j z_j 2^(v-1-j): the multilinear extension of x -> x over v variables, variable 0 the most significant bit (the memory
+// check's cell and time columns, Spark's index column)
+inline fe index_at(const fe* z, unsigned v) {
+    fe acc = fe_zero();
+    for (unsigned j = 0; j < v; j++) acc = h_add(h_add(acc, acc), z[j]);  // Horner in 2
+    return acc;
+}
+
 // whir_config.hip's zero-count rule: an operation of no elements is no operation
 inline void pattern_op(std::string& d, char kind, size_t n, const char* label) {
     if (!n) return;

@@ -46,12 +46,8 @@ struct Challenges {
     fe gamma, beta, seeds[3];
 };
 
-// I(z) = sum_j z_j 2^(v-1-j): the multilinear extension of x -> x over v variables, variable 0 the most significant bit
-inline fe index_at(const fe* z, unsigned v) {
-    fe acc = pk::fe_zero();
-    for (unsigned j = 0; j < v; j++) acc = pk::h_add(pk::h_add(acc, acc), z[j]);  // Horner in 2
-    return acc;
-}
+// I(z) = sum_j z_j 2^(v-1-j): argument.hpp's, shared with the Spark library
+using pk::index_at;
 // the sign table's extension at a stacked point: +1 on the first half, -1 on the second
 inline fe sign_at(const fe& z0) { return pk::h_sub(pk::fe_one(), pk::h_add(z0, z0)); }
 // P_a / Q_a + P_b / Q_b = 0

@@ -101,6 +101,12 @@ SIGNATURES = {
     "pk_probe_mem_leaf_items": (C.c_uint, []),
     "pk_probe_mem_trace_items": (C.c_uint, []),
     "pk_probe_mem_count_lds_max_n": (C.c_uint, []),
+    # libprovekit_spark.so's gather kernel with its grid; a pkx_prover's grid knob and the phases of its last calls (tools/probes/spark.hip)
+    "pk_probe_spark_gather": (C.c_int, [vp, C.c_uint, C.c_uint, C.c_uint, vp, vp, vp, vp, vp, vp, vp, C.c_uint, C.POINTER(C.c_float)]),
+    "pk_probe_spark_set_grid": (C.c_int, [vp, C.c_uint]),
+    "pk_probe_spark_profile": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "pk_probe_spark_gather_items": (C.c_uint, []),
+    "pk_probe_spark_matrix_items": (C.c_uint, []),
     # csrc/witness.hip's thresholds and the shape of a levelled builder list (tools/probes/witness.hip): host only
     "pk_probe_witness_narrow": (C.c_uint, []),
     "pk_probe_witness_sum_heavy": (C.c_uint, []),

@@ -236,6 +236,22 @@ unsigned pk_probe_mem_leaf_items(void);
 unsigned pk_probe_mem_trace_items(void);
 unsigned pk_probe_mem_count_lds_max_n(void);
 
+/* libprovekit_spark.so's gather kernel by itself (csrc/spark/kernels.hpp) over tables the caller holds, with the grid its C ABI does not
+ * carry (1 .. 1024 workgroups; 0: the library's rule, pk_probe_spark_gather_items entries per lane): d_eq_row 2^s and d_eq_col 2^t
+ * elements, d_bad one u64 cell (all ones afterwards: every index was inside).  *ms: its device time.  Blocking.
+ * A pkx_prover's test and benchmark knobs (csrc/spark/prover.hpp), host only: pk_probe_spark_set_grid sets the grid of every kernel of
+ * its calls from the next call on -- no bit of a result depends on it (tests/test_gpu_spark.py); pk_probe_spark_profile: in
+ * milliseconds, matrix_ms2 the last pkx_matrix's count and column phases and *gather_ms the last pkx_begin's gather in device time,
+ * *eq_ms the last proof's two eq tables and side_ms3[PKX_SIDE_*] its three inner proofs in host time.  pk_probe_spark_matrix_items:
+ * the entries per lane the preprocessing kernels' grid rule aims at. */
+struct pkx_prover;
+int pk_probe_spark_gather(pk_ctx *ctx, unsigned n, unsigned s, unsigned t, const uint32_t *d_row_idx, const uint32_t *d_col_idx, const uint64_t *d_eq_row,
+                          const uint64_t *d_eq_col, uint64_t *d_e_row, uint64_t *d_e_col, unsigned long long *d_bad, unsigned grid, float *ms);
+int pk_probe_spark_set_grid(struct pkx_prover *p, unsigned grid);
+int pk_probe_spark_profile(const struct pkx_prover *p, double *matrix_ms2, double *gather_ms, double *eq_ms, double *side_ms3);
+unsigned pk_probe_spark_gather_items(void);
+unsigned pk_probe_spark_matrix_items(void);
+
 /* csrc/witness.hip's thresholds (csrc/witness_shape.hpp) and the shape of a levelled builder list (witness.hip here), for
  * tests/test_witness_edge_cases_host.py and tests/test_gpu_witness_edges.py.  Host only.  pk_probe_witness_phases: *n_phases = the
  * phases of postcard(Vec<WitnessBuilder>) after levelling (two per level); with cap >= *n_phases, widths[ph] = the items of phase
