@@ -172,6 +172,9 @@ class SparseMatrixStruct(C.Structure):
 # test entry points the library exports besides its API (tools/probes/pk_selftest.h)
 SELFTEST_SIGNATURES = {
     "pk_selftest_set_host_tail": (C.c_int, [vp, C.c_uint]),
+    "pk_selftest_set_host_pow": (C.c_int, [vp, C.c_uint]),
+    "pk_selftest_host_commit": (C.c_int, [C.c_int, vp, C.c_uint, C.c_uint, C.c_uint, C.c_uint, vp, vp]),
+    "pk_selftest_host_pow": (C.c_int, [vp, C.c_double, C.POINTER(C.c_uint64)]),
     "pk_selftest_eq_suffix_tables": (C.c_int, [vp, vp, C.c_uint, vp]),
     "pk_selftest_sumcheck_cubic_spliteq": (C.c_int, [vp, vp, vp, vp, vp, C.c_uint, C.c_uint, vp, vp, vp]),
     "pk_selftest_sumcheck_quadratic_claim": (C.c_int, [vp, vp, vp, sz, vp, vp, vp, vp, vp]),

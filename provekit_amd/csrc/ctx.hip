@@ -296,6 +296,13 @@ int pk_selftest_set_host_tail(pk_ctx* ctx, unsigned log2_len) {
     return PK_OK;
 }
 
+int pk_selftest_set_host_pow(pk_ctx* ctx, unsigned max_bits) {
+    if (!ctx) return PK_ERR_BAD_ARG;
+    if (max_bits > PK_HOST_POW_CEILING) return set_err(ctx, PK_ERR_BAD_ARG, "bad argument: host grinder bound is 0 (off) or 1 .. %d bits", PK_HOST_POW_CEILING);
+    ctx->host_pow_max_bits = max_bits;
+    return PK_OK;
+}
+
 }  // extern "C"
 
 namespace pk {

@@ -24,6 +24,12 @@ struct pk_comm;  // comm.hip
 #define PK_HOST_TAIL_DEFAULT_LOG2 10
 #endif
 #define PK_HOST_TAIL_MAX_LOG2 11
+// host grinder: proofs of work of at most this many bits are ground on the host thread (prover.hip pow_round; EXPERIMENTS.md round 34), and
+// the largest bound the setter accepts: a grind is ~2^bits host compressions, and the witness opening's 11 bits stay on the device
+#ifndef PK_HOST_POW_MAX_BITS
+#define PK_HOST_POW_MAX_BITS 4
+#endif
+#define PK_HOST_POW_CEILING 8
 
 struct pk_ctx {
     int device = 0;
@@ -57,6 +63,9 @@ struct pk_ctx {
     // they are brought to the host thread once and the remaining rounds, folds and weights run there -- a round over a few hundred
     // entries is cheaper than its launch, synchronisation and polling wait.  0 = off; a context in a device set never takes it.
     unsigned host_tail_log2 = PK_HOST_TAIL_DEFAULT_LOG2;
+    // Host grinder (pk_selftest_set_host_pow): where the host tail is on, a proof of work of at most this many bits is searched on the host
+    // thread (host_whir.hpp pow_grind) instead of by a launch and a synchronisation.  0 = every grind on the device.
+    unsigned host_pow_max_bits = PK_HOST_POW_MAX_BITS;
     void* d_ws = nullptr;  // large reusable workspace (NTT scratch); grows, never shrinks
     void* d_ztab = nullptr;  // 256 field elements: z^t for the point of the univariate evaluation in flight (mle.hip)
     size_t ws_bytes = 0;

@@ -3,12 +3,15 @@
 // This is the compiled host side of the drop-in (the reference's is Rust): transcript, challenge bookkeeping and the
 // O(m_0^2) blinding algebra run here on the CPU; every data-parallel step is a call into this library's kernels on
 // buffers that never leave HBM -- but for the sumchecks' short tails: tables of at most 2^host_tail_log2 entries come to the host once and
-// finish there (host_tail.hpp; sumcheck_round_loop below).  One proof allocates no device memory: it all comes from a per-scheme arena.
+// finish there (host_tail.hpp; sumcheck_round_loop below), and for the blinding polynomial, whose tables are that short and depend on the
+// proof's key alone: they are drawn on the device, come over once, and its commitment and its whole WHIR proof run on the host thread (host_whir.hpp; Proof::commit_witness below).  One
+// proof allocates no device memory: it all comes from a per-scheme arena.
 //
 //   pk_prove -> prove, one stage per step of the reference (struct Proof)
-//    +- commit_witness (whir_r1cs.rs:57-69, 182-209): mask / random polynomial on device, to_coeffs x2, commit_batch
-//    +- zk_sumcheck (whir_r1cs.rs:228-369): witness bounds, eq table, blinding commitment, m_0 cubic rounds
-//    +- prove_blinding: small WHIR proof of the blinding polynomial
+//    +- commit_witness (whir_r1cs.rs:57-69, 182-209): mask / random polynomial on device, to_coeffs x2, commit_batch; underneath it the
+//    |    blinding commitment on the host thread
+//    +- zk_sumcheck (whir_r1cs.rs:228-369): witness bounds, eq table, blinding commitment (its transcript half; on the device route all of it), m_0 cubic rounds
+//    +- prove_blinding: small WHIR proof of the blinding polynomial (host thread; device route beyond the host tail's threshold)
 //    +- witness_statement: external rows, weighted sums, claimed_evaluations hint (whir_r1cs.rs:81-91)
 //    +- prove_witness: whir_prove (whir::Prover::prove; structure pinned by recursive-verifier/app/circuit/whir.go:51-220)
 //
@@ -21,10 +24,12 @@
 #include <algorithm>
 #include <chrono>
 #include <cstdlib>
+#include <memory>
 #include <string>
 #include <vector>
 
 #include "host_tail.hpp"
+#include "host_whir.hpp"
 #include "internal.hpp"
 #include "shard_map.hpp"
 #include "prover_transcript.hpp"
@@ -213,7 +218,10 @@ int pow_round(pk_ctx* ctx, Transcript& T, double bits) {
     uint8_t challenge[POW_CHALLENGE_BYTES], be[POW_NONCE_BYTES];
     T.challenge_bytes(challenge, sizeof challenge);
     uint64_t nonce = 0;
-    const int rc = pow_solve_x(ctx, challenge, bits, &nonce, comm_world(ctx) > 1);  // nonce ranges striped over the ranks of a device set
+    int rc = PK_OK;
+    // a few bits: ~2^bits host compressions against a launch and a synchronisation (the same nonce: the smallest valid one)
+    if (host_tail_len(ctx) && bits <= (double)ctx->host_pow_max_bits) nonce = host_whir::pow_grind(challenge, bits);
+    else rc = pow_solve_x(ctx, challenge, bits, &nonce, comm_world(ctx) > 1);  // nonce ranges striped over the ranks of a device set
     nonce_to_bytes(nonce, be);
     T.add_bytes(be, sizeof be);
     return rc;
@@ -227,6 +235,10 @@ struct Commitment {  // whir::committer::Witness
     fe* leaves = nullptr;
     fe* nodes = nullptr;
     size_t rows = 0, width = 0;
+    // Where polys, evals, leaves and nodes live: in the arena, or -- a commitment made by whir_commit_host (host_whir.hpp) -- in host memory:
+    // leaves and nodes in `mem` (shared by the copies of this struct), polys and evals with the caller.  Whoever reads them asks here.
+    bool host = false;
+    std::shared_ptr<std::vector<fe>> mem;
     pk_commit_layout layout{};    // how commit_into laid the codeword out (shards, leaf encoding): recorded, not recomputed
     std::vector<fe> ood_points;   // Montgomery
     std::vector<fe> ood_answers;  // [poly][point], Montgomery
@@ -239,7 +251,8 @@ int emit_opening_hints(pk_ctx* ctx, Transcript& T, const Commitment& C, const st
     const unsigned logn = ilog2(C.rows);
     const size_t plen = logn ? logn - 1 : 0;
     std::vector<uint64_t> leaves(4 * k * width), sib(4 * (k ? k : 1)), paths(4 * (k * plen ? k * plen : 1));
-    CK(open_raw(ctx, U(C.leaves), U(C.nodes), C.rows, width, C.layout, idx.data(), k, /*canonical=*/1, leaves.data(), sib.data(), paths.data()));
+    if (C.host) host_whir::open(C.leaves, C.nodes, C.rows, width, idx.data(), k, (fe*)leaves.data(), (fe*)sib.data(), (fe*)paths.data());
+    else CK(open_raw(ctx, U(C.leaves), U(C.nodes), C.rows, width, C.layout, idx.data(), k, /*canonical=*/1, leaves.data(), sib.data(), paths.data()));
     const auto ser0 = std::chrono::steady_clock::now();
     std::vector<uint8_t> buf;
     put_u64(buf, k);
@@ -274,6 +287,20 @@ int whir_commit_compute(pk_ctx* ctx, Arena& A, unsigned n_vars, unsigned log_inv
     for (unsigned b = 0; b < batch; b++) ptrs[b] = U(polys[b]);
     return commit_into(ctx, ptrs, batch, n_vars, log_inv_rate, fold, U(leaves), U(nodes), (uint64_t*)ctx->d_ws, &C.layout);
 }
+// the same commitment of polynomials that stand in host memory, on the host thread (host_whir.hpp): nothing of the arena, no launch
+void whir_commit_host(const pk_ctx* ctx, unsigned n_vars, unsigned log_inv_rate, unsigned fold, fe* const* polys, unsigned batch, Commitment& C) {
+    C.n_vars = n_vars;
+    C.batch = batch;
+    C.rows = (size_t)1 << (n_vars + log_inv_rate - fold);
+    C.width = (size_t)batch << fold;
+    for (unsigned b = 0; b < batch; b++) C.polys[b] = polys[b];
+    C.host = true;
+    C.mem = std::make_shared<std::vector<fe>>(C.rows * C.width + 2 * C.rows);
+    C.leaves = C.mem->data();
+    C.nodes = C.leaves + C.rows * C.width;
+    C.layout = pk_commit_layout{1, 0, PK_LEAVES_MONTGOMERY};
+    host_whir::commit(ctx->hash_version, polys, batch, n_vars, log_inv_rate, fold, C.leaves, C.nodes);
+}
 // ... and the half that talks: root, OOD points and answers, batching randomness (mtUtilities.go:51-76)
 int whir_commit_transcript(pk_ctx* ctx, const pk_whir_config& cfg, const fe& root, Transcript& T, Commitment& C) {
     const unsigned batch = C.batch;
@@ -287,7 +314,8 @@ int whir_commit_transcript(pk_ctx* ctx, const pk_whir_config& cfg, const fe& roo
         for (unsigned b = 0; b < batch; b += 2) {
             const unsigned np = batch - b >= 2 ? 2 : 1;
             fe ans[2];
-            CK(eval_univariate_multi_x(ctx, polys + b, np, (size_t)1 << cfg.n_vars, C.ood_points[j], ans));
+            if (C.host) for (unsigned q = 0; q < np; q++) ans[q] = host_whir::horner(polys[b + q], (size_t)1 << cfg.n_vars, C.ood_points[j]);
+            else CK(eval_univariate_multi_x(ctx, polys + b, np, (size_t)1 << cfg.n_vars, C.ood_points[j], ans));
             for (unsigned q = 0; q < np; q++) C.ood_answers[(b + q) * C.ood_points.size() + j] = ans[q];
         }
     }
@@ -406,9 +434,11 @@ struct WhirProver {
     fe* bw[2] = {};
     fe* gathered[4] = {};  // sharded: where p, w go once the blocks are short (p0, p1, w0, w1)
     // the host tail: once p and w are short they live here, folded in place, for the rest of the opening -- the rounds, the closing folds
-    // and the equality weights of the later rounds.  d_c stays on the device: it is folded, re-committed and evaluated there.
+    // and the equality weights of the later rounds.  d_c stays on the device: it is folded, re-committed and evaluated there -- unless
+    // the commitment opened is the host's (C.host): then the working polynomial is hc, and its folds, re-commitments, OOD evaluations and
+    // openings run on the host too (host_whir.hpp); nothing of the opening touches the device or the arena.
     bool host = false;
-    std::vector<fe> hp, hw;
+    std::vector<fe> hp, hw, hc;
     const fe* h_weight = nullptr;  // an opening that starts on the host: the caller's host copy of its one statement weight
     int cur = 0;
     size_t len;             // local length of p and w
@@ -597,13 +627,21 @@ struct WhirProver {
             hw.resize(N);
             host_tail::lincomb2(hp.data(), h_evals, C.beta, h_evals + N, N);
         }
-        ALLOC(dc, N);
-        d_c = dc;
-        ALLOC(p0, B0);
-        ALLOC(p1, B0 / 2 ? B0 / 2 : 1);
-        ALLOC(w0, B0);
-        ALLOC(w1, B0 / 2 ? B0 / 2 : 1);
-        bp[0] = p0; bp[1] = p1; bw[0] = w0; bw[1] = w1;
+        fe *p0 = nullptr, *w0 = nullptr;
+        if (C.host) {  // the commitment's polynomials are the host's: so is the working polynomial, and no buffer of the arena is taken
+            PK_REQUIRE(ctx, host, "a host commitment is opened from the host's tables");
+            hc.resize(N);
+            host_tail::lincomb2(hc.data(), C.polys[0], C.beta, C.polys[1], N);
+        } else {
+            ALLOC(dc, N);
+            d_c = dc;
+            ALLOC(p0_, B0);
+            ALLOC(p1, B0 / 2 ? B0 / 2 : 1);
+            ALLOC(w0_, B0);
+            ALLOC(w1, B0 / 2 ? B0 / 2 : 1);
+            p0 = p0_, w0 = w0_;
+            bp[0] = p0; bp[1] = p1; bw[0] = w0; bw[1] = w1;
+        }
         bool have_evals = true;
         for (unsigned b = 0; b < C.batch; b++) have_evals = have_evals && C.evals[b] != nullptr;
         const bool pair = have_evals && C.batch == 2;
@@ -613,7 +651,8 @@ struct WhirProver {
         // (tables that round 0 takes to the host at once are formed by the plain sequence: the first launch would leave them pending)
         const size_t tail = host_tail_len(ctx);
         const bool fused = !host && !(tail && !sharded && B0 <= tail) && pair && !sharded && B0 >= 2 && k >= 1 && (rows3 || n_weights == 1) && weight_len[0] <= B0;
-        if (fused || host) {  // the working polynomial alone: p0 comes from the first launch, or stands on the host already
+        if (C.host) {  // the working polynomial stands, on the host
+        } else if (fused || host) {  // the working polynomial alone: p0 comes from the first launch, or stands on the host already
             h_store(first.beta, C.beta);
             CK(lincomb2(ctx, U(d_c), U(C.polys[0]), first.beta, U(C.polys[1]), N));
         } else if (pair) {  // the coefficient and the evaluation combination of a batch of two in one launch
@@ -696,22 +735,37 @@ struct WhirProver {
         for (unsigned r = 0; r < cfg.n_rounds; r++) {
             // W1: fold the coefficient form by this round's randomness
             const unsigned nv2 = nv - k;
-            ALLOC(d_c2, (size_t)1 << nv2);
-            CK(pk_fold_coeffs(ctx, U(d_c), nv, (const uint64_t*)rs.data(), k, U(d_c2)));
-            d_c = d_c2;
+            if (C.host) {
+                std::vector<fe> hc2((size_t)1 << nv2);
+                host_whir::fold_coeffs(hc.data(), nv, rs.data(), k, hc2.data());
+                hc.swap(hc2);
+                d_c = hc.data();  // read through next.host below, never handed to a launch
+            } else {
+                ALLOC(d_c2, (size_t)1 << nv2);
+                CK(pk_fold_coeffs(ctx, U(d_c), nv, (const uint64_t*)rs.data(), k, U(d_c2)));
+                d_c = d_c2;
+            }
             nv = nv2;
             log_inv_rate += k - 1;  // the domain halves while the polynomial shrinks 2^k-fold
             // N1+N2+M1+M2: re-commit
             Commitment next;
-            CK(whir_commit_compute(ctx, A, nv, log_inv_rate, k, &d_c, 1, next));
             fe root;
-            CK(read_root(ctx, U(next.nodes), next.rows, (uint64_t*)root.v));
+            if (C.host) {
+                whir_commit_host(ctx, nv, log_inv_rate, k, &d_c, 1, next);
+                root = next.nodes[1];
+            } else {
+                CK(whir_commit_compute(ctx, A, nv, log_inv_rate, k, &d_c, 1, next));
+                CK(read_root(ctx, U(next.nodes), next.rows, (uint64_t*)root.v));
+            }
             T.add_canon(root);
             // E1: OOD
             std::vector<fe> zs(cfg.ood_samples[r]);
             T.challenge_scalars(zs.data(), zs.size());
             std::vector<fe> ood_ans(zs.size());
-            for (size_t j = 0; j < zs.size(); j++) CK(eval_univariate_x(ctx, d_c, (size_t)1 << nv, zs[j], ood_ans[j]));
+            for (size_t j = 0; j < zs.size(); j++) {
+                if (next.host) ood_ans[j] = host_whir::horner(d_c, (size_t)1 << nv, zs[j]);
+                else CK(eval_univariate_x(ctx, d_c, (size_t)1 << nv, zs[j], ood_ans[j]));
+            }
             T.add_scalars(ood_ans.data(), ood_ans.size());
             // P1
             CK(pow_round(ctx, T, cfg.pow_bits[r]));
@@ -750,10 +804,14 @@ struct WhirProver {
             CK(gather(fp0, fp1, fw0, fw1));
         }
         const unsigned nv2 = nv - k;
-        ALLOC(d_final, (size_t)1 << nv2);
-        CK(pk_fold_coeffs(ctx, U(d_c), nv, (const uint64_t*)rs.data(), k, U(d_final)));
         std::vector<fe> fin((size_t)1 << nv2);
-        CK(pk_memcpy_d2h(ctx, fin.data(), d_final, 32 * fin.size()));
+        if (C.host) {
+            host_whir::fold_coeffs(hc.data(), nv, rs.data(), k, fin.data());
+        } else {
+            ALLOC(d_final, (size_t)1 << nv2);
+            CK(pk_fold_coeffs(ctx, U(d_c), nv, (const uint64_t*)rs.data(), k, U(d_final)));
+            CK(pk_memcpy_d2h(ctx, fin.data(), d_final, 32 * fin.size()));
+        }
         T.add_scalars(fin.data(), fin.size());
         CK(pow_round(ctx, T, cfg.final_pow_bits));
         const std::vector<uint64_t> idx = stir_queries(T, domain_size, k, cfg.final_queries);
@@ -820,6 +878,7 @@ struct BatchCommit {
     Commitment com;
     fe* f_evals = nullptr;  // masked polynomial, evaluation form (2^m)
     fe* g_evals = nullptr;  // random polynomial, evaluation form (2^m)
+    std::vector<fe> h_tables;  // a host commitment (com.host): f, g, then their coefficient forms, 2^m entries each, as they came over; f_evals .. point here
 };
 // masks, coefficient forms and the commitment's device work on `ctx`'s stream; nothing is read back and the transcript is not touched
 int batch_commit_compute(pk_ctx* ctx, Arena& A, unsigned m, const pk_whir_config& cfg, const fe* d_evals, size_t n_evals, const RngKey& key,
@@ -946,6 +1005,9 @@ struct Proof {
         aux = side.c;
         return PK_OK;
     }
+    // The blinding WHIR on the host thread (host_whir.hpp): its tables are within the host tail's threshold and the context is not a rank
+    // of a device set -- the condition under which prove_blinding's tables stand on the host.  Else every line of the device route.
+    bool blinding_on_host() const { return host_tail_len(ctx) && ((size_t)2 << s->nb) <= host_tail_len(ctx); }
     // the external rows go to the side context too, unless there are none
     pk_ctx* rows_ctx() const { return n_witness ? aux : ctx; }
     // a failure on the side context is reported where the caller looks
@@ -988,6 +1050,43 @@ int blinding_compute(pk_ctx* ctx, Proof& P) {
     return batch_commit_compute(ctx, A, P.s->nb + 1, P.s->whir_hiding, d_blind, NB, P.key, RNG_MASK_B, RNG_G_B, P.B);
 }
 
+// The host route (Proof::blinding_on_host), first half: the blinding coefficients, the two tables and their coefficient forms are drawn
+// and formed on the device as blinding_compute does -- three small launches -- and come over in ONE transfer, f | g | their coefficient
+// forms, 2^(nb+1) entries each (tables_to_host: one launch, one synchronisation).  Nothing of the blinding polynomial is on the device
+// afterwards.  Called before the witness commitment is enqueued, so that its wait is for these launches alone.
+int blinding_tables_to_host(pk_ctx* ctx, Proof& P) {
+    Arena& A = P.A;
+    const unsigned mb = P.s->nb + 1;
+    const size_t NB = (size_t)1 << P.s->nb, N = 2 * NB, n = P.g_univ.size();
+    ALLOC(d_blind, NB);
+    ALLOC(f, N);
+    ALLOC(g, N);
+    ALLOC(fc, N);
+    ALLOC(gc, N);
+    CK(pk_memset_zero(ctx, d_blind, 32 * NB));
+    CK(random_fe(ctx, U(d_blind), n, P.key, RNG_BLIND));
+    CK(to_coeffs_generated(ctx, mb, U(d_blind), NB, P.key, RNG_MASK_B, RNG_G_B, U(f), U(g), U(fc), U(gc)));
+    P.B.h_tables.resize(4 * N);
+    const uint64_t* src[4] = {U(f), U(g), U(fc), U(gc)};
+    const size_t cnt[4] = {N, N, N, N};
+    CK(tables_to_host(ctx, src, cnt, 4, U(P.B.h_tables.data())));
+    std::copy(P.B.h_tables.begin(), P.B.h_tables.begin() + n, P.g_univ.begin());  // f's head is the blinding polynomial
+    return PK_OK;
+}
+// ... second half: the commitment of the tables that came over, on the host thread (host_whir.hpp)
+void blinding_commit_host(const pk_ctx* ctx, Proof& P) {
+    BatchCommit& out = P.B;
+    const pk_whir_config& cfg = P.s->whir_hiding;
+    const size_t N = (size_t)2 << P.s->nb;
+    fe *f = out.h_tables.data(), *g = f + N;
+    out.f_evals = f;
+    out.g_evals = g;
+    fe* polys[2] = {g + N, g + 2 * N};
+    whir_commit_host(ctx, cfg.n_vars, cfg.starting_log_inv_rate, cfg.folding_factor, polys, 2, out.com);
+    out.com.evals[0] = f;
+    out.com.evals[1] = g;
+}
+
 // external rows (whir_r1cs.rs:81-91, 382-412): eq(alpha) and the three rows [S4] on `ctx`'s stream.  On the side context the six
 // weighted sums follow at once, deferred: their results are read after its next synchronisation.
 int external_rows(pk_ctx* ctx, Proof& P) {
@@ -1003,13 +1102,26 @@ int external_rows(pk_ctx* ctx, Proof& P) {
     return dot_rows(ctx, U(rows), nw, 3, U(P.W.f_evals), U(P.W.g_evals), nw, nullptr, /*defer=*/true);
 }
 
-// --- commit to the masked witness polynomial (whir_r1cs.rs:57-69).  Latency mode: the blinding commitment depends on nothing but the
-// proof's key -- 0.6 ms of launches that keep 32 lanes busy (its two leaf hashes are chains of 31 compressions).  Its device work goes
-// to the side stream right after the witness commitment's launches and runs underneath them, which fill the chip for 2.6 ms; only its
-// transcript half (root, OOD, batching) waits for its turn.
+// --- commit to the masked witness polynomial (whir_r1cs.rs:57-69), and -- underneath it -- to the blinding polynomial, which depends on
+// nothing but the proof's key.  The witness commitment's launches fill the chip for 2.6 ms (several times that under load), and this
+// thread would only wait for its root.  What runs where:
+//   blinding tables within the host tail's threshold (blinding_on_host: every size pk_prove is used at): the tables are drawn on the
+//     device FIRST and come over in one transfer (blinding_tables_to_host); then, between the witness commitment's launches and read_root,
+//     the 32-leaf codeword, its leaf hashes (chains of 31 compressions, ~0.7 ms of host time) and the tree are computed HERE, on this
+//     thread, in either mode;
+//   otherwise (threshold 0, a device set, a larger blinding polynomial) it is device work, 0.6 ms of launches that keep 32 lanes busy:
+//     in latency mode on the side stream right after the witness commitment's launches, underneath them; in plain mode inline on the
+//     prover's own stream, from zk_sumcheck.
+// Only the blinding commitment's transcript half (root, OOD, batching) waits for its turn (blinding_transcript).
 int Proof::commit_witness() {
+    const bool hostb = blinding_on_host();
+    if (hostb) CK(blinding_tables_to_host(ctx, *this));
     CK(batch_commit_compute(ctx, A, s->m, s->whir_witness, d_witness, n_witness, key, RNG_MASK, RNG_G, W));
-    if (aux != ctx) CK(relay(aux, blinding_compute(aux, *this), "blinding commitment"));
+    if (hostb) {
+        blinding_commit_host(ctx, *this);
+    } else if (aux != ctx) {
+        CK(relay(aux, blinding_compute(aux, *this), "blinding commitment"));
+    }
     fe root;
     CK(read_root(ctx, U(W.com.nodes), W.com.rows, (uint64_t*)root.v));
     return whir_commit_transcript(ctx, s->whir_witness, root, T, W.com);
@@ -1019,7 +1131,8 @@ int Proof::commit_witness() {
 // for its stream and rewinds its mailbox), then the coefficients are taken out of the mailbox before anything is allocated there.
 int Proof::blinding_transcript() {
     fe root;
-    CK(relay(aux, read_root(aux, U(B.com.nodes), B.com.rows, (uint64_t*)root.v), "blinding commitment"));
+    if (B.com.host) root = B.com.nodes[1];  // everything stands in host memory since commit_witness
+    else CK(relay(aux, read_root(aux, U(B.com.nodes), B.com.rows, (uint64_t*)root.v), "blinding commitment"));
     if (h_univ) memcpy(g_univ.data(), h_univ, 32 * g_univ.size());
     return whir_commit_transcript(ctx, s->whir_hiding, root, T, B.com);
 }
@@ -1059,7 +1172,7 @@ int Proof::zk_sumcheck() {
         CK(pk_r1cs_witness_bounds(ctx, s->r1cs, U(d_witness), m_0, U(d_a), U(d_b), U(d_cc)));  // S1
         CK(eq_suffix_tables(ctx, (const uint64_t*)r.data(), m_0, U(d_eq)));                  // S2: the levels E_i instead of the table (mle.hip)
     }
-    if (aux == ctx) CK(blinding_compute(ctx, *this));  // else the side stream finished it long ago
+    if (aux == ctx && !B.com.host) CK(blinding_compute(ctx, *this));  // else the side stream, or the host, finished it long ago
     CK(blinding_transcript());
     lap("bounds+eq+blinding commit");
     fe* z[4] = {d_a, d_b, d_cc, d_eq};
@@ -1183,26 +1296,31 @@ int Proof::prove_blinding() {
         wv[4 * i + 2] = h_mul(alpha[i], alpha[i]);
         wv[4 * i + 3] = h_mul(wv[4 * i + 2], alpha[i]);
     }
-    ALLOC(d_bw, nbw);
     uint64_t fg[8];
     // The host tail: a blinding opening no longer than the threshold never puts its sumcheck on the device.  The two evaluation tables
     // come over once; the statement's two sums, the opening's tables and its deferred hint are formed from them and from wv on the host.
     const size_t NB2 = (size_t)2 << s->nb, tail = host_tail_len(ctx);
     std::vector<fe> h_evals;
-    if (tail && NB2 <= tail) {
+    fe* d_bw = nullptr;
+    if (B.com.host) {  // the tables never left the host: f and g stand back to back in the commitment's own memory
+        host_tail::dot2(wv.data(), B.f_evals, B.g_evals, nbw, fg);
+    } else if (tail && NB2 <= tail) {
         h_evals.resize(2 * NB2);
         const uint64_t* src[2] = {U(B.f_evals), U(B.g_evals)};
         const size_t cnt[2] = {NB2, NB2};
         CK(tables_to_host(ctx, src, cnt, 2, U(h_evals.data())));
         host_tail::dot2(wv.data(), h_evals.data(), h_evals.data() + NB2, nbw, fg);
     } else {
+        ALLOC(bw_, nbw);
+        d_bw = bw_;
         CK(pk_memcpy_h2d(ctx, d_bw, wv.data(), 32 * nbw));
         CK(pk_dot2(ctx, U(d_bw), U(B.f_evals), U(B.g_evals), nbw, fg));
     }
     const fe sums[2] = {h_load(fg), h_load(fg + 4)};
     T.add_scalars(sums, 2);
     fe* wts[1] = {d_bw};  // on the host path never read: the weight is wv
-    return whir_prove(ctx, A, s->whir_hiding, B.com, wts, &nbw, 1, sums, T, h_evals.empty() ? nullptr : h_evals.data(), h_evals.empty() ? nullptr : wv.data());
+    const fe* h_ev = B.com.host ? B.f_evals : h_evals.empty() ? nullptr : h_evals.data();
+    return whir_prove(ctx, A, s->whir_hiding, B.com, wts, &nbw, 1, sums, T, h_ev, h_ev ? wv.data() : nullptr);
 }
 
 // --- the statement over the witness commitment (whir_r1cs.rs:81-91): external rows, their six sums, the claimed_evaluations hint
@@ -1414,6 +1532,27 @@ int pk_scheme_set_io_pattern(pk_ctx* ctx, pk_scheme* s, const uint8_t* pattern, 
     const std::string bad = io_pattern_mismatch(theirs, s->m_0, s->whir_witness, s->whir_hiding);
     if (!bad.empty()) return set_err(ctx, PK_ERR_IO_PATTERN, "%s", bad.c_str());
     s->domain_separator = theirs;
+    return PK_OK;
+}
+
+/* ---- the host restatement of a commitment and of the grinder (host_whir.hpp), for the suite: host memory in, host memory out ---- */
+
+// commit_into on the host thread: `batch` coefficient vectors of 2^n_vars Montgomery elements each, back to back -> the column-major leaf
+// matrix (rows * width elements, Montgomery) and the heap of 2 * rows canonical digests, as pk_commit_into leaves them on the device
+int pk_selftest_host_commit(int hash_version, const uint64_t* coeffs, unsigned batch, unsigned n_vars, unsigned log_inv_rate, unsigned fold,
+                            uint64_t* leaves_out, uint64_t* nodes_out) {
+    if (!coeffs || !leaves_out || !nodes_out || (hash_version != 1 && hash_version != 2) || batch < 1 || batch > 4 || fold > n_vars ||
+        n_vars + log_inv_rate - fold > PK_HOST_TAIL_MAX_LOG2)
+        return PK_ERR_BAD_ARG;
+    const fe* polys[4];
+    for (unsigned b = 0; b < batch; b++) polys[b] = (const fe*)coeffs + ((size_t)b << n_vars);
+    host_whir::commit(hash_version, polys, batch, n_vars, log_inv_rate, fold, (fe*)leaves_out, (fe*)nodes_out);
+    return PK_OK;
+}
+// pk_pow_solve on the host thread: the smallest valid nonce, by a search in ascending order
+int pk_selftest_host_pow(const uint8_t challenge[32], double bits, uint64_t* nonce) {
+    if (!challenge || !nonce || !(bits >= 0.0 && bits <= (double)PK_HOST_POW_CEILING)) return PK_ERR_BAD_ARG;
+    *nonce = host_whir::pow_grind(challenge, bits);
     return PK_OK;
 }
 

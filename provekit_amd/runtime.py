@@ -96,6 +96,10 @@ class Context:
         """pk_selftest_set_host_tail: sumcheck tables of at most 2^log2_len entries finish on the host thread (0 = never)"""
         self._check(lib.pk_selftest_set_host_tail(self.handle, log2_len))
 
+    def set_host_pow(self, max_bits: int):
+        """pk_selftest_set_host_pow: proofs of work of at most max_bits bits are ground on the host thread (0 = never; at most 8)"""
+        self._check(lib.pk_selftest_set_host_pow(self.handle, max_bits))
+
     def comm_info(self):
         r, w, k = C.c_int(), C.c_int(), C.c_int()
         self._check(lib.pk_comm_info(self.handle, C.byref(r), C.byref(w), C.byref(k)))

@@ -61,6 +61,18 @@ int pk_selftest_set_hook(int which, long value);
  * proof's bytes do not change.  log2_len = 0: off, exactly the device path; 1 .. 11 otherwise (anything else is refused).  A context that is
  * a rank of a device set ignores the setting. */
 int pk_selftest_set_host_tail(pk_ctx *ctx, unsigned log2_len);
+/* The host grinder's bound of one context (csrc/host_whir.hpp pow_grind, csrc/prover.hip pow_round): where the host tail is on, a proof of
+ * work of at most max_bits bits is searched on the calling thread instead of by a launch and a synchronisation; the nonce is the same, the
+ * smallest valid one.  0: every grind on the device; 1 .. 8 otherwise (anything else is refused: the witness opening's 11 bits are 2^11
+ * host compressions).  The build's default is PK_HOST_POW_MAX_BITS (csrc/ctx.hpp). */
+int pk_selftest_set_host_pow(pk_ctx *ctx, unsigned max_bits);
+/* The host restatement of a commitment and of the grinder (csrc/host_whir.hpp; host memory in and out, no device): what pk_prove runs for a
+ * blinding polynomial within the host tail's threshold.  host_commit: `batch` (1 .. 4) coefficient vectors of 2^n_vars Montgomery elements,
+ * back to back -> the column-major leaf matrix (rows x width, Montgomery) and the heap of 2 * rows canonical digests that pk_commit_into
+ * leaves on the device, rows = 2^(n_vars + log_inv_rate - fold) <= 2^11.  host_pow: the nonce pk_pow_solve returns, bits <= 8. */
+int pk_selftest_host_commit(int hash_version, const uint64_t *coeffs, unsigned batch, unsigned n_vars, unsigned log_inv_rate, unsigned fold,
+                            uint64_t *leaves_out, uint64_t *nodes_out);
+int pk_selftest_host_pow(const uint8_t challenge[32], double bits, uint64_t *nonce);
 
 #ifdef __cplusplus
 }
