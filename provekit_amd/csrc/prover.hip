@@ -98,6 +98,11 @@ inline const uint64_t* U(const fe* p) { return (const uint64_t*)p; }
 
 // the context's host-tail threshold in entries (pk_selftest_set_host_tail); 0 = never: switched off, or the context is a rank of a device set
 inline size_t host_tail_len(const pk_ctx* ctx) { return !ctx->comm && ctx->host_tail_log2 ? (size_t)1 << ctx->host_tail_log2 : 0; }
+// "these tables go to the host tail": `len` entries, whole (not a rank's block), within the threshold.  Every place that asks, asks here.
+inline bool host_tail_takes(const pk_ctx* ctx, bool sharded, size_t len) {
+    const size_t tail = host_tail_len(ctx);
+    return tail && !sharded && len <= tail;
+}
 
 // ------------------------------------------------------------------ one proof over a device set
 // Besides the commits (tree.hip), the linear-size arrays of a sharded proof are split over the G ranks:
@@ -174,7 +179,6 @@ int eval_univariate_multi_x(pk_ctx* ctx, const fe* const* d_polys, unsigned np, 
     for (unsigned q = 0; q < np; q++) out[q] = h_load(o + 4 * q);
     return PK_OK;
 }
-int eval_univariate_x(pk_ctx* ctx, const fe* d_poly, size_t n, const fe& z, fe& out) { return eval_univariate_multi_x(ctx, &d_poly, 1, n, z, &out); }
 
 // ------------------------------------------------------------------ S6: blinding algebra (host, O(m_0^2))
 // compute_blinding_coefficients_for_round (provekit/prover/src/whir_r1cs.rs:103-170)
@@ -235,7 +239,7 @@ struct Commitment {  // whir::committer::Witness
     fe* leaves = nullptr;
     fe* nodes = nullptr;
     size_t rows = 0, width = 0;
-    // Where polys, evals, leaves and nodes live: in the arena, or -- a commitment made by whir_commit_host (host_whir.hpp) -- in host memory:
+    // Where polys, evals, leaves and nodes live: in the arena, or -- a commitment of polynomials in host memory (whir_commit_compute, host_whir.hpp) -- in host memory:
     // leaves and nodes in `mem` (shared by the copies of this struct), polys and evals with the caller.  Whoever reads them asks here.
     bool host = false;
     std::shared_ptr<std::vector<fe>> mem;
@@ -244,6 +248,26 @@ struct Commitment {  // whir::committer::Witness
     std::vector<fe> ood_answers;  // [poly][point], Montgomery
     fe beta;                      // batching randomness
 };
+// What the prover asks of a commitment -- its root, its polynomials at a point, its rows opened: the bodies below hold the only tests of
+// where it lives.  A device root is read on the context that built the tree.
+int commitment_root(pk_ctx* ctx, const Commitment& C, fe& root) {
+    if (!C.host) return read_root(ctx, U(C.nodes), C.rows, (uint64_t*)root.v);
+    root = C.nodes[1];
+    return PK_OK;
+}
+// polynomials b .. b + np - 1 (np <= 2) at one point: one launch (and one host round trip) on the device, Horner on the host
+int commitment_evaluate(pk_ctx* ctx, const Commitment& C, unsigned b, unsigned np, const fe& z, fe* out) {
+    const size_t n = (size_t)1 << C.n_vars;
+    if (!C.host) return eval_univariate_multi_x(ctx, C.polys + b, np, n, z, out);
+    for (unsigned q = 0; q < np; q++) out[q] = host_whir::horner(C.polys[b + q], n, z);
+    return PK_OK;
+}
+// the k rows idx[] (canonical), each row's sibling digest and authentication path
+int commitment_open(pk_ctx* ctx, const Commitment& C, const uint64_t* idx, size_t k, uint64_t* leaves, uint64_t* sib, uint64_t* paths) {
+    if (!C.host) return open_raw(ctx, U(C.leaves), U(C.nodes), C.rows, C.width, C.layout, idx, k, /*canonical=*/1, leaves, sib, paths);
+    host_whir::open(C.leaves, C.nodes, C.rows, C.width, idx, k, (fe*)leaves, (fe*)sib, (fe*)paths);
+    return PK_OK;
+}
 
 // hints: stir_answers = Vec<Vec<F>> and merkle_proof = ark MultiPath of the commitment's tree at the queried rows (common.go:36-61)
 int emit_opening_hints(pk_ctx* ctx, Transcript& T, const Commitment& C, const std::vector<uint64_t>& idx) {
@@ -251,8 +275,7 @@ int emit_opening_hints(pk_ctx* ctx, Transcript& T, const Commitment& C, const st
     const unsigned logn = ilog2(C.rows);
     const size_t plen = logn ? logn - 1 : 0;
     std::vector<uint64_t> leaves(4 * k * width), sib(4 * (k ? k : 1)), paths(4 * (k * plen ? k * plen : 1));
-    if (C.host) host_whir::open(C.leaves, C.nodes, C.rows, width, idx.data(), k, (fe*)leaves.data(), (fe*)sib.data(), (fe*)paths.data());
-    else CK(open_raw(ctx, U(C.leaves), U(C.nodes), C.rows, width, C.layout, idx.data(), k, /*canonical=*/1, leaves.data(), sib.data(), paths.data()));
+    CK(commitment_open(ctx, C, idx.data(), k, leaves.data(), sib.data(), paths.data()));
     const auto ser0 = std::chrono::steady_clock::now();
     std::vector<uint8_t> buf;
     put_u64(buf, k);
@@ -270,14 +293,24 @@ int emit_opening_hints(pk_ctx* ctx, Transcript& T, const Commitment& C, const st
 // CommitmentWriter::commit_batch (call site provekit/prover/src/whir_r1cs.rs:200-206; transcript order mtUtilities.go:51-76)
 // the commitment's device work (RS-encode, leaf hashes, tree) on `ctx`'s stream, nothing read back: the half that needs no transcript
 // -- in latency mode the blinding commitment's runs on a second stream while the witness commitment fills the chip.  Also the
-// re-commit of every WHIR round (batch 1).
-int whir_commit_compute(pk_ctx* ctx, Arena& A, unsigned n_vars, unsigned log_inv_rate, unsigned fold, fe* const* polys, unsigned batch,
+// re-commit of every WHIR round (batch 1).  host: the polynomials stand in host memory and so will the commitment, computed on the host
+// thread (host_whir.hpp): nothing of the arena, no launch.
+int whir_commit_compute(pk_ctx* ctx, Arena& A, bool host, unsigned n_vars, unsigned log_inv_rate, unsigned fold, fe* const* polys, unsigned batch,
                         Commitment& C) {
     C.n_vars = n_vars;
     C.batch = batch;
     C.rows = (size_t)1 << (n_vars + log_inv_rate - fold);
     C.width = (size_t)batch << fold;
     for (unsigned b = 0; b < batch; b++) C.polys[b] = polys[b];
+    if (host) {
+        C.host = true;
+        C.mem = std::make_shared<std::vector<fe>>(C.rows * C.width + 2 * C.rows);
+        C.leaves = C.mem->data();
+        C.nodes = C.leaves + C.rows * C.width;
+        C.layout = pk_commit_layout{1, 0, PK_LEAVES_MONTGOMERY};
+        host_whir::commit(ctx->hash_version, polys, batch, n_vars, log_inv_rate, fold, C.leaves, C.nodes);
+        return PK_OK;
+    }
     ALLOC(leaves, C.rows * C.width / shard_factor(ctx, C.rows));  // a rank of a device set keeps only its rows (tree.hip)
     ALLOC(nodes, 2 * C.rows);
     C.leaves = leaves;
@@ -287,24 +320,9 @@ int whir_commit_compute(pk_ctx* ctx, Arena& A, unsigned n_vars, unsigned log_inv
     for (unsigned b = 0; b < batch; b++) ptrs[b] = U(polys[b]);
     return commit_into(ctx, ptrs, batch, n_vars, log_inv_rate, fold, U(leaves), U(nodes), (uint64_t*)ctx->d_ws, &C.layout);
 }
-// the same commitment of polynomials that stand in host memory, on the host thread (host_whir.hpp): nothing of the arena, no launch
-void whir_commit_host(const pk_ctx* ctx, unsigned n_vars, unsigned log_inv_rate, unsigned fold, fe* const* polys, unsigned batch, Commitment& C) {
-    C.n_vars = n_vars;
-    C.batch = batch;
-    C.rows = (size_t)1 << (n_vars + log_inv_rate - fold);
-    C.width = (size_t)batch << fold;
-    for (unsigned b = 0; b < batch; b++) C.polys[b] = polys[b];
-    C.host = true;
-    C.mem = std::make_shared<std::vector<fe>>(C.rows * C.width + 2 * C.rows);
-    C.leaves = C.mem->data();
-    C.nodes = C.leaves + C.rows * C.width;
-    C.layout = pk_commit_layout{1, 0, PK_LEAVES_MONTGOMERY};
-    host_whir::commit(ctx->hash_version, polys, batch, n_vars, log_inv_rate, fold, C.leaves, C.nodes);
-}
 // ... and the half that talks: root, OOD points and answers, batching randomness (mtUtilities.go:51-76)
 int whir_commit_transcript(pk_ctx* ctx, const pk_whir_config& cfg, const fe& root, Transcript& T, Commitment& C) {
     const unsigned batch = C.batch;
-    fe* const* polys = C.polys;
     T.add_canon(root);
     C.ood_points.resize(cfg.commitment_ood_samples);
     T.challenge_scalars(C.ood_points.data(), C.ood_points.size());
@@ -314,8 +332,7 @@ int whir_commit_transcript(pk_ctx* ctx, const pk_whir_config& cfg, const fe& roo
         for (unsigned b = 0; b < batch; b += 2) {
             const unsigned np = batch - b >= 2 ? 2 : 1;
             fe ans[2];
-            if (C.host) for (unsigned q = 0; q < np; q++) ans[q] = host_whir::horner(polys[b + q], (size_t)1 << cfg.n_vars, C.ood_points[j]);
-            else CK(eval_univariate_multi_x(ctx, polys + b, np, (size_t)1 << cfg.n_vars, C.ood_points[j], ans));
+            CK(commitment_evaluate(ctx, C, b, np, C.ood_points[j], ans));
             for (unsigned q = 0; q < np; q++) C.ood_answers[(b + q) * C.ood_points.size() + j] = ans[q];
         }
     }
@@ -324,11 +341,9 @@ int whir_commit_transcript(pk_ctx* ctx, const pk_whir_config& cfg, const fe& roo
     return PK_OK;
 }
 
-// whir::Prover::prove with `n_weights` linear statement weights: evaluation tables over the 2^n hypercube of which only the
-// first weight_len[i] entries are stored -- the rest is zero by construction (create_combined_statement_over_two_polynomials
-// zero-extends each row, whir_r1cs.rs:382-412), so nothing is spent on the zero half.
+// whir::Prover::prove opens a batch of two at the linear weights of a statement (struct Weights).
 // On a device set (and a polynomial long enough) the sumcheck tables, the weights and the OOD evaluations are split into the
-// ranks' blocks; of a sharded weight only the entries inside this rank's block need to be present in d_weights[i].
+// ranks' blocks.
 bool whir_sharded(const pk_ctx* ctx, unsigned n_vars) {
     const size_t G = (size_t)comm_world(ctx);
     return G > 1 && (((size_t)1 << n_vars) / G) >= 2 * SHARD_MIN_LOCAL;
@@ -338,11 +353,20 @@ size_t in_block(size_t stored, size_t off, size_t len) {
     const size_t hi = stored < off + len ? stored : off + len;
     return hi > off ? hi - off : 0;
 }
-// the three external rows at equal stride and of one length: one pass serves all three (the statement weights into w0, the deferred hint)
-bool rows_at_equal_stride3(fe* const* d_weights, const size_t* weight_len, unsigned n_weights) {
-    return n_weights == 3 && weight_len[0] == weight_len[1] && weight_len[1] == weight_len[2] && d_weights[1] > d_weights[0] &&
-           d_weights[1] - d_weights[0] == d_weights[2] - d_weights[1];
-}
+// The linear weights of a statement, stated once: `n` evaluation tables over the hypercube of which only the first len[i] entries are
+// stored -- the rest is zero by construction (create_combined_statement_over_two_polynomials zero-extends each row,
+// whir_r1cs.rs:382-412), so nothing is spent on the zero half.  The rows stand on the device -- of a sharded opening only the entries
+// inside this rank's block need to be present -- or, the one row of a statement over a host commitment, in host memory.
+struct Weights {
+    bool host;
+    unsigned n;
+    const fe* row[3];
+    size_t len[3];
+    const fe* sums;  // sums[i * 2 + b] = <weight i, polynomial b>, as the transcript holds them (may be null: the first round then forms three sums)
+    // three device rows at equal stride and of one length: one pass serves all three (the statement weights into w0, the deferred hint)
+    const bool equal_stride3 = n == 3 && len[0] == len[1] && len[1] == len[2] && row[1] > row[0] && row[1] - row[0] == row[2] - row[1];
+    size_t stride() const { return equal_stride3 ? (size_t)(row[1] - row[0]) : 0; }
+};
 
 // ------------------------------------------------------------------ the round loop of the prover's sumchecks
 // `rounds` rounds, each: the round's sums, the message, absorb, squeeze the folding challenge, record it.  The Spartan cubic rounds
@@ -365,8 +389,7 @@ template <class S>
 int sumcheck_round_loop(pk_ctx* ctx, Transcript& T, unsigned rounds, bool pipelined, S& s) {
     unsigned red_cur = 0, red_next = 0;
     uint64_t f[4];  // the previous round's challenge
-    const size_t tail = host_tail_len(ctx);
-    auto host_next = [&] { return s.on_host() || (tail && s.host_capable() && s.len <= tail); };
+    auto host_next = [&] { return s.on_host() || (s.host_capable() && host_tail_takes(ctx, s.sharded, s.len)); };
     bool queued = false;  // latency mode: this round's kernel is in the queue already ...
     bool closed = false;  // ... and so is the closing fold
     if (pipelined && !host_next()) {
@@ -420,6 +443,54 @@ int sumcheck_round_loop(pk_ctx* ctx, Transcript& T, unsigned rounds, bool pipeli
     return PK_OK;
 }
 
+// The working polynomial of an opening, c = sum_b beta^b poly_b (mtUtilities.go:98-114), in coefficient form and whole on every rank: what
+// each round folds, re-commits and evaluates.  It lives where the commitment opened lives: in the arena, or -- a host commitment -- in host
+// memory, where its folds, re-commitments and evaluations are host_whir.hpp's and nothing of the arena is taken.  The bodies below hold
+// the only tests of which.
+struct WorkingPoly {
+    pk_ctx* ctx;
+    Arena& A;
+    const bool host;
+    unsigned nv;
+    fe* d = nullptr;     // device
+    std::vector<fe> h;   // host
+
+    // fold the coefficient form by the k challenges rs
+    int fold(const std::vector<fe>& rs, unsigned k) {
+        const unsigned nv2 = nv - k;
+        if (host) {
+            std::vector<fe> h2((size_t)1 << nv2);
+            host_whir::fold_coeffs(h.data(), nv, rs.data(), k, h2.data());
+            h.swap(h2);
+        } else {
+            ALLOC(d2, (size_t)1 << nv2);
+            CK(pk_fold_coeffs(ctx, U(d), nv, (const uint64_t*)rs.data(), k, U(d2)));
+            d = d2;
+        }
+        nv = nv2;
+        return PK_OK;
+    }
+    // commit to it alone (N1+N2+M1+M2): the tree of the next round
+    int commit(unsigned log_inv_rate, unsigned fold, Commitment& next) {
+        fe* poly = host ? h.data() : d;
+        return whir_commit_compute(ctx, A, host, nv, log_inv_rate, fold, &poly, 1, next);
+    }
+    int evaluate(const fe& z, fe& out) {
+        if (!host) return eval_univariate_multi_x(ctx, &d, 1, (size_t)1 << nv, z, &out);
+        out = host_whir::horner(h.data(), (size_t)1 << nv, z);
+        return PK_OK;
+    }
+    // the coefficients in the clear, for the transcript: the last use of the polynomial
+    int to_host(std::vector<fe>& out) {
+        if (host) {
+            out = std::move(h);
+            return PK_OK;
+        }
+        out.resize((size_t)1 << nv);
+        return pk_memcpy_d2h(ctx, out.data(), d, 32 * out.size());
+    }
+};
+
 struct WhirProver {
     pk_ctx* ctx;
     Arena& A;
@@ -429,17 +500,15 @@ struct WhirProver {
     const unsigned n, k, G, lgG, rank;
     bool sharded;          // the sumcheck tables are this rank's block [off0, off0 + B0) of the hypercube
     const size_t B0, off0;
-    fe* d_c = nullptr;     // working polynomial c = sum_b beta^b poly_b (mtUtilities.go:98-114), whole on every rank: folded, re-committed
+    WorkingPoly c;
     fe* bp[2] = {};        // sumcheck operands: p = evaluations of c over the hypercube, w = combined weights; ping-pong halves
     fe* bw[2] = {};
     fe* gathered[4] = {};  // sharded: where p, w go once the blocks are short (p0, p1, w0, w1)
-    // the host tail: once p and w are short they live here, folded in place, for the rest of the opening -- the rounds, the closing folds
-    // and the equality weights of the later rounds.  d_c stays on the device: it is folded, re-committed and evaluated there -- unless
-    // the commitment opened is the host's (C.host): then the working polynomial is hc, and its folds, re-commitments, OOD evaluations and
-    // openings run on the host too (host_whir.hpp); nothing of the opening touches the device or the arena.
+    // the host tail: once p and w are short they live here (p, then w, in one buffer), folded in place, for the rest of the opening -- the
+    // rounds, the closing folds and the equality weights of the later rounds.  The opening of a host commitment starts here.
     bool host = false;
-    std::vector<fe> hp, hw, hc;
-    const fe* h_weight = nullptr;  // an opening that starts on the host: the caller's host copy of its one statement weight
+    std::vector<fe> htab;
+    fe *hp = nullptr, *hw = nullptr;
     int cur = 0;
     size_t len;             // local length of p and w
     std::vector<fe> rs;     // the challenges of the last sumcheck_rounds call
@@ -450,28 +519,13 @@ struct WhirProver {
     WhirProver(pk_ctx* c, Arena& a, const pk_whir_config& cf, const Commitment& com, Transcript& t)
         : ctx(c), A(a), cfg(cf), C(com), T(t), n(cf.n_vars), k(cf.folding_factor), G((unsigned)comm_world(c)), lgG(ilog2(G)),
           rank((unsigned)comm_rank(c)), sharded(whir_sharded(c, n)), B0(sharded ? ((size_t)1 << n) / G : (size_t)1 << n),
-          off0(sharded ? (size_t)rank * B0 : 0), len(B0) {}
-
-    // sum_b beta^b x_b over `cnt` entries from `from` of coefficient tables or evaluation tables: the first two in one pass
-    int batch_combine(fe* dst, fe* const* x, size_t from, size_t cnt) {
-        if (C.batch == 1) return pk_memcpy_d2d(ctx, dst, x[0] + from, 32 * cnt);
-        uint64_t s[4];
-        h_store(s, C.beta);
-        int rc = lincomb2(ctx, U(dst), U(x[0] + from), s, U(x[1] + from), cnt);
-        fe bp_ = h_mul(C.beta, C.beta);
-        for (unsigned b = 2; b < C.batch && !rc; b++) {
-            h_store(s, bp_);
-            rc = pk_fe_axpy(ctx, U(dst), s, U(x[b] + from), cnt);
-            bp_ = h_mul(bp_, C.beta);
-        }
-        return rc;
-    }
+          off0(sharded ? (size_t)rank * B0 : 0), c{ctx, A, com.host, cf.n_vars}, len(B0) {}
 
     // equality weights of the univariate points zs (expand_from_univariate; variable 0 <-> the top index bit), scaled by 1, gamma,
-    // gamma^2, ... and accumulated into a weight table; *next = the following power of gamma.  The whole table, or -- sharded -- this
-    // rank's block, whose top lgG index bits are the rank: that factor of eq goes into the scale and the table is built over the rest.
-    // defer: the accumulation is left to round 0's own launch (launch(0), mle.hip opening_first_launch), which needs w's pairs anyway
-    int eq_weights(fe* dst, unsigned nv, const std::vector<fe>& zs, const fe& gamma, int overwrite, fe* next, bool defer = false) {
+    // gamma^2, ... and accumulated into the weight table w.  The whole table, or -- sharded -- this rank's block, whose top lgG index bits
+    // are the rank: that factor of eq goes into the scale and the table is built over the rest.  defer: the accumulation is left to
+    // round 0's own launch (launch(0), mle.hip opening_first_launch), which needs w's pairs anyway
+    int eq_weights(unsigned nv, const std::vector<fe>& zs, const fe& gamma, int overwrite, bool defer) {
         const size_t q = zs.size();
         const unsigned lg = sharded ? lgG : 0, nl = nv - lg;
         std::vector<fe> x(nv ? nv : 1);
@@ -486,14 +540,13 @@ struct WhirProver {
             std::copy(x.begin() + lg, x.begin() + nv, pts.begin() + j * nl);
             g = h_mul(g, gamma);
         }
-        *next = g;
         if (host) {  // never a rank's block: lg = 0
-            host_tail::eq_accumulate(hw.data(), nv, pts.data(), scales.data(), q, overwrite != 0);
+            host_tail::eq_accumulate(hw, nv, pts.data(), scales.data(), q, overwrite != 0);
             return PK_OK;
         }
-        if (!defer) return pk_eq_accumulate(ctx, U(dst), nl, (const uint64_t*)pts.data(), (const uint64_t*)scales.data(), (unsigned)q, overwrite);
+        if (!defer) return pk_eq_accumulate(ctx, U(bw[cur]), nl, (const uint64_t*)pts.data(), (const uint64_t*)scales.data(), (unsigned)q, overwrite);
         first.a = opening_first{};
-        first.a.d_w = U(dst);
+        first.a.d_w = U(bw[cur]);
         first.a.n = (size_t)1 << nl;
         first.a.points = (const uint64_t*)pts.data();
         first.a.scales = (const uint64_t*)scales.data();
@@ -553,30 +606,25 @@ struct WhirProver {
     int to_host(unsigned) {
         if (host) return PK_OK;
         if (first.pending) return set_err(ctx, PK_ERR_HIP, "host tail: a round's weights are still to be formed on the device");
-        hp.resize(len);
-        hw.resize(len);
+        host_tables(len);
         const uint64_t* src[2] = {U(bp[cur]), U(bw[cur])};
         const size_t cnt[2] = {len, len};
-        std::vector<fe> both(2 * len);
-        CK(tables_to_host(ctx, src, cnt, 2, U(both.data())));
-        std::copy(both.begin(), both.begin() + len, hp.begin());
-        std::copy(both.begin() + len, both.end(), hw.begin());
-        host = true;
-        return PK_OK;
+        return tables_to_host(ctx, src, cnt, 2, U(htab.data()));  // the two runs back to back: p, then w
     }
-    // before new weights join w, or an opening's last stage: tables this short move now, so that the weights are formed on the host too
-    int maybe_to_host() {
-        const size_t tail = host_tail_len(ctx);
-        return !host && tail && !sharded && len <= tail ? to_host(0) : PK_OK;
+    void host_tables(size_t entries) {
+        htab.resize(2 * entries);
+        hp = htab.data();
+        hw = hp + entries;
+        host = true;
     }
     void host_round(unsigned t, const uint64_t* fold, uint64_t out[12]) {
         const fe r = fold ? h_load(fold) : fe_zero();
-        len = host_tail::quadratic_round(hp.data(), hw.data(), len, fold ? &r : nullptr, nsums(t), out);
+        len = host_tail::quadratic_round(hp, hw, len, fold ? &r : nullptr, nsums(t), out);
     }
     void host_fold(const uint64_t* r) {
         const fe rr = h_load(r);
-        host_tail::fold_pairs(hp.data(), len, rr);
-        host_tail::fold_pairs(hw.data(), len, rr);
+        host_tail::fold_pairs(hp, len, rr);
+        host_tail::fold_pairs(hw, len, rr);
         len /= 2;
     }
     int before_sync_launch() { return PK_OK; }
@@ -611,107 +659,39 @@ struct WhirProver {
     // once a rank's block is short; a sumcheck_rounds call shrinks the block 2^k-fold, so blocks never run out inside one
     int maybe_gather() { return sharded && len <= SHARD_MIN_LOCAL ? gather(gathered[0], gathered[1], gathered[2], gathered[3]) : PK_OK; }
 
+    // How the opening starts: where c, p0 and w0 are formed.  Chosen once, by start().
+    enum class Route {
+        Host,         // a host commitment: c, p0, w0 on the host; nothing of the arena
+        FirstLaunch,  // mle.hip opening_first_launch: p0, w0 and round 0's sums from one pass over the two evaluation tables and the statement rows
+        Plain         // everything else on the device: a rank's block, tables the host tail takes at once, rows the first launch does not take
+    };
+
     // the working polynomial, the sumcheck tables, the initial weights and the first k sumcheck rounds
-    // weight_sums[i * batch + b] = <weight i, polynomial b>, as the transcript holds them (may be null: the first round then forms three sums)
-    // h_evals != null (an opening no longer than the host tail's threshold, a batch of two, at most one weight -- the blinding proof): the
-    // caller's host copy of the two evaluation tables, 2^n entries each, back to back, and h_w that of the weight.  p0 and w0 are then
-    // formed on the host and never exist on the device; only the working polynomial does.
-    int start(fe* const* d_weights, const size_t* weight_len, unsigned n_weights, const fe* weight_sums, const fe* h_evals, const fe* h_w) {
-        const size_t N = (size_t)1 << n;
-        if (h_evals) {
-            PK_REQUIRE(ctx, !sharded && C.batch == 2 && n_weights <= 1 && (!n_weights || (h_w && weight_len[0] <= N)),
-                       "an opening that starts on the host: batch 2, one weight");
-            host = true;
-            h_weight = h_w;
-            hp.resize(N);
-            hw.resize(N);
-            host_tail::lincomb2(hp.data(), h_evals, C.beta, h_evals + N, N);
-        }
-        fe *p0 = nullptr, *w0 = nullptr;
-        if (C.host) {  // the commitment's polynomials are the host's: so is the working polynomial, and no buffer of the arena is taken
-            PK_REQUIRE(ctx, host, "a host commitment is opened from the host's tables");
-            hc.resize(N);
-            host_tail::lincomb2(hc.data(), C.polys[0], C.beta, C.polys[1], N);
-        } else {
-            ALLOC(dc, N);
-            d_c = dc;
-            ALLOC(p0_, B0);
-            ALLOC(p1, B0 / 2 ? B0 / 2 : 1);
-            ALLOC(w0_, B0);
-            ALLOC(w1, B0 / 2 ? B0 / 2 : 1);
-            p0 = p0_, w0 = w0_;
-            bp[0] = p0; bp[1] = p1; bw[0] = w0; bw[1] = w1;
-        }
-        bool have_evals = true;
-        for (unsigned b = 0; b < C.batch; b++) have_evals = have_evals && C.evals[b] != nullptr;
-        const bool pair = have_evals && C.batch == 2;
-        // The opening's first launch (mle.hip opening_first_launch): p0, w0 and round 0's sums from one pass over the two evaluation tables
-        // and the statement rows.  Everything else -- a rank's block, another batch, no tables, rows it does not take -- keeps the sequence below.
-        const bool rows3 = rows_at_equal_stride3(d_weights, weight_len, n_weights);
+    int start(const Weights& W) {
+        // pk_prove opens what commit_batch made, and a host commitment at a host weight: general batches are libprovekit_whir's (whir_pcs/pcs.cpp)
+        PK_REQUIRE(ctx, C.batch == 2 && C.evals[0] && C.evals[1] && W.host == C.host && !(C.host && (sharded || W.n != 1 || W.len[0] > ((size_t)1 << n))),
+                   "an opening of pk_prove: a batch of two with both evaluation tables, its weights where the commitment is");
         // (tables that round 0 takes to the host at once are formed by the plain sequence: the first launch would leave them pending)
-        const size_t tail = host_tail_len(ctx);
-        const bool fused = !host && !(tail && !sharded && B0 <= tail) && pair && !sharded && B0 >= 2 && k >= 1 && (rows3 || n_weights == 1) && weight_len[0] <= B0;
-        if (C.host) {  // the working polynomial stands, on the host
-        } else if (fused || host) {  // the working polynomial alone: p0 comes from the first launch, or stands on the host already
-            h_store(first.beta, C.beta);
-            CK(lincomb2(ctx, U(d_c), U(C.polys[0]), first.beta, U(C.polys[1]), N));
-        } else if (pair) {  // the coefficient and the evaluation combination of a batch of two in one launch
-            uint64_t s[4];
-            h_store(s, C.beta);
-            CK(lincomb2_pair(ctx, U(d_c), U(C.polys[0]), U(C.polys[1]), N, U(p0), U(C.evals[0] + off0), U(C.evals[1] + off0), B0, s));
-        } else {
-            CK(batch_combine(d_c, C.polys, 0, N));
-        }
-        if (host) {  // p0 stands, on the host
-        } else if (have_evals) {
-            if (!pair) CK(batch_combine(p0, C.evals, off0, B0));  // to_evals is linear: combine the tables the committer kept instead of transforming d_c
-        } else if (!sharded) {
-            CK(pk_to_evals_into(ctx, U(d_c), U(p0), n));
-        } else {
-            ALLOC(d_ev, N);
-            CK(pk_to_evals_into(ctx, U(d_c), U(d_ev), n));
-            CK(pk_memcpy_d2d(ctx, p0, d_ev + off0, 32 * B0));
-        }
+        const bool first_launch = !host_tail_takes(ctx, sharded, B0) && !sharded && B0 >= 2 && k >= 1 && (W.equal_stride3 || W.n == 1) && W.len[0] <= B0;
+        const Route route = C.host ? Route::Host : first_launch ? Route::FirstLaunch : Route::Plain;
         // initial combination randomness; weights = sum gamma^i w_i over [OOD constraints..., statement weights...]
         const fe gamma = T.challenge_scalar();
-        fe g;
-        CK(eq_weights(w0, n, C.ood_points, gamma, /*overwrite=*/1, &g, /*defer=*/fused));
-        // <p, w> of the tables just built, from values the transcript holds: an OOD constraint's sum is its answer, a statement weight's its claimed sum
-        auto batched = [&](const fe* v, size_t step) {  // sum_b beta^b v[b * step]
-            fe acc = v[0], bb = C.beta;
-            for (unsigned b = 1; b < C.batch; b++, bb = h_mul(bb, C.beta)) acc = h_add(acc, h_mul(bb, v[b * step]));
-            return acc;
-        };
+        // <p, w> of the tables about to be built, from values the transcript holds: an OOD constraint's sum is its answer, a statement weight's its claimed sum
+        auto batched = [&](const fe* v, size_t step) { return h_add(v[0], h_mul(C.beta, v[step])); };  // sum_b beta^b v[b * step]
         const size_t q = C.ood_points.size();
         claim = fe_zero();
-        fe gq = fe_one();
-        for (size_t j = 0; j < q; j++, gq = h_mul(gq, gamma)) claim = h_add(claim, h_mul(gq, batched(&C.ood_answers[j], q)));
-        have_claim = weight_sums || !n_weights;
-        if (fused) {  // the rows join w0 where round 0 first reads it
-            fe g3 = g;
-            for (unsigned i = 0; i < n_weights; i++, g3 = h_mul(g3, gamma)) h_store(first.row_scales + 4 * i, g3);
-            first.a.d_e0 = U(C.evals[0]);
-            first.a.d_e1 = U(C.evals[1]);
-            first.a.beta = first.beta;
-            first.a.d_rows = U(d_weights[0]);
-            first.a.row_stride = rows3 ? (size_t)(d_weights[1] - d_weights[0]) : 0;
-            first.a.nrows = n_weights;
-            first.a.row_len = weight_len[0];
-            first.a.row_scales = first.row_scales;
-        } else if (rows3) {  // one read and one write of w0 instead of three
-            uint64_t s3[12];
-            fe g3 = g;
-            for (int i = 0; i < 3; i++, g3 = h_mul(g3, gamma)) h_store(s3 + 4 * i, g3);
-            CK(axpy3(ctx, U(w0), s3, U(d_weights[0] + off0), (size_t)(d_weights[1] - d_weights[0]), in_block(weight_len[0], off0, B0)));
+        fe g = fe_one();
+        for (size_t j = 0; j < q; j++, g = h_mul(g, gamma)) claim = h_add(claim, h_mul(g, batched(&C.ood_answers[j], q)));
+        fe scale[3];  // of the statement rows: the powers of gamma that follow the OOD constraints'
+        for (unsigned i = 0; i < W.n; i++, g = h_mul(g, gamma)) {
+            scale[i] = g;
+            if (W.sums) claim = h_add(claim, h_mul(g, batched(W.sums + 2 * (size_t)i, 1)));
         }
-        for (unsigned i = 0; i < n_weights; i++) {
-            uint64_t s[4];
-            h_store(s, g);
-            const size_t cnt = in_block(weight_len[i], off0, B0);
-            if (host) host_tail::axpy(hw.data(), g, h_weight, cnt);
-            else if (cnt && !rows3 && !fused) CK(pk_fe_axpy(ctx, U(w0), s, U(d_weights[i] + off0), cnt));
-            if (weight_sums) claim = h_add(claim, h_mul(g, batched(weight_sums + (size_t)i * C.batch, 1)));
-            g = h_mul(g, gamma);
+        have_claim = W.sums || !W.n;
+        switch (route) {
+            case Route::Host: CK(start_host(W, gamma, scale)); break;
+            case Route::FirstLaunch: CK(start_first_launch(W, gamma, scale)); break;
+            case Route::Plain: CK(start_plain(W, gamma, scale)); break;
         }
         if (sharded) {
             const size_t cap = G * SHARD_MIN_LOCAL;
@@ -724,77 +704,113 @@ struct WhirProver {
         CK(sumcheck_rounds(k));
         return maybe_gather();
     }
+    int start_host(const Weights& W, const fe& gamma, const fe* scale) {
+        const size_t N = (size_t)1 << n;
+        host_tables(N);
+        host_tail::lincomb2(hp, C.evals[0], C.beta, C.evals[1], N);
+        c.h.resize(N);
+        host_tail::lincomb2(c.h.data(), C.polys[0], C.beta, C.polys[1], N);
+        CK(eq_weights(n, C.ood_points, gamma, /*overwrite=*/1, /*defer=*/false));
+        host_tail::axpy(hw, scale[0], W.row[0], W.len[0]);
+        return PK_OK;
+    }
+    int device_tables() {  // of both device routes: c, and the ping-pong halves of p and w
+        ALLOC(dc, (size_t)1 << n);
+        ALLOC(p0, B0);
+        ALLOC(p1, B0 / 2 ? B0 / 2 : 1);
+        ALLOC(w0, B0);
+        ALLOC(w1, B0 / 2 ? B0 / 2 : 1);
+        c.d = dc;
+        bp[0] = p0; bp[1] = p1; bw[0] = w0; bw[1] = w1;
+        return PK_OK;
+    }
+    int start_first_launch(const Weights& W, const fe& gamma, const fe* scale) {
+        CK(device_tables());
+        h_store(first.beta, C.beta);
+        CK(lincomb2(ctx, U(c.d), U(C.polys[0]), first.beta, U(C.polys[1]), (size_t)1 << n));  // the working polynomial alone: p0 comes from the first launch
+        CK(eq_weights(n, C.ood_points, gamma, /*overwrite=*/1, /*defer=*/true));
+        for (unsigned i = 0; i < W.n; i++) h_store(first.row_scales + 4 * i, scale[i]);  // the rows join w0 where round 0 first reads it
+        first.a.d_e0 = U(C.evals[0]);
+        first.a.d_e1 = U(C.evals[1]);
+        first.a.beta = first.beta;
+        first.a.d_rows = U(W.row[0]);
+        first.a.row_stride = W.stride();
+        first.a.nrows = W.n;
+        first.a.row_len = W.len[0];
+        first.a.row_scales = first.row_scales;
+        return PK_OK;
+    }
+    int start_plain(const Weights& W, const fe& gamma, const fe* scale) {
+        CK(device_tables());
+        uint64_t beta[4], s[12];
+        h_store(beta, C.beta);  // the coefficient and the evaluation combination of a batch of two in one launch
+        CK(lincomb2_pair(ctx, U(c.d), U(C.polys[0]), U(C.polys[1]), (size_t)1 << n, U(bp[0]), U(C.evals[0] + off0), U(C.evals[1] + off0), B0, beta));
+        CK(eq_weights(n, C.ood_points, gamma, /*overwrite=*/1, /*defer=*/false));
+        for (unsigned i = 0; i < W.n; i++) h_store(s + 4 * i, scale[i]);
+        if (W.equal_stride3) return axpy3(ctx, U(bw[0]), s, U(W.row[0] + off0), W.stride(), in_block(W.len[0], off0, B0));  // one read and one write of w0 instead of three
+        for (unsigned i = 0; i < W.n; i++) {
+            const size_t cnt = in_block(W.len[i], off0, B0);
+            if (cnt) CK(pk_fe_axpy(ctx, U(bw[0]), s + 4 * i, U(W.row[i] + off0), cnt));
+        }
+        return PK_OK;
+    }
+
+    // W2: a round's new weights -- the equality weights of its OOD and STIR points, scaled by powers of the combination randomness -- join w.
+    // Tables short enough for the host tail go there first, and the weights join w on the host.  Else, unless this is a rank's block, the
+    // round's first sumcheck launch adds them.  At every number of points: the fused kernel runs at three waves per SIMD where
+    // eq_accumulate_kernel has four, and the round of 110 points still came out ahead (EXPERIMENTS.md round 29)
+    int round_weights(const std::vector<fe>& zs, const fe& gamma) {
+        if (host_tail_takes(ctx, sharded, len)) CK(to_host(0));
+        CK(eq_weights(c.nv, zs, gamma, /*overwrite=*/0, /*defer=*/!host && !sharded && len >= 2 && k >= 1));
+        have_claim = false;  // the new weights' sums include the folded polynomial at the STIR points, which the prover never evaluates
+        return PK_OK;
+    }
 
     // the folding rounds: fold, re-commit, OOD, PoW, STIR openings of the previous tree, new weights, k sumcheck rounds (whir.go:51-220)
     int rounds() {
         const Commitment* prev = &C;  // the tree this round's STIR queries open
         Commitment com;
-        unsigned nv = n, log_inv_rate = cfg.starting_log_inv_rate;
+        unsigned log_inv_rate = cfg.starting_log_inv_rate;
         size_t domain_size = (size_t)1 << (n + log_inv_rate);
         fe exp_gen = folded_domain_generator(n + log_inv_rate, k);
         for (unsigned r = 0; r < cfg.n_rounds; r++) {
             // W1: fold the coefficient form by this round's randomness
-            const unsigned nv2 = nv - k;
-            if (C.host) {
-                std::vector<fe> hc2((size_t)1 << nv2);
-                host_whir::fold_coeffs(hc.data(), nv, rs.data(), k, hc2.data());
-                hc.swap(hc2);
-                d_c = hc.data();  // read through next.host below, never handed to a launch
-            } else {
-                ALLOC(d_c2, (size_t)1 << nv2);
-                CK(pk_fold_coeffs(ctx, U(d_c), nv, (const uint64_t*)rs.data(), k, U(d_c2)));
-                d_c = d_c2;
-            }
-            nv = nv2;
+            CK(c.fold(rs, k));
             log_inv_rate += k - 1;  // the domain halves while the polynomial shrinks 2^k-fold
             // N1+N2+M1+M2: re-commit
             Commitment next;
             fe root;
-            if (C.host) {
-                whir_commit_host(ctx, nv, log_inv_rate, k, &d_c, 1, next);
-                root = next.nodes[1];
-            } else {
-                CK(whir_commit_compute(ctx, A, nv, log_inv_rate, k, &d_c, 1, next));
-                CK(read_root(ctx, U(next.nodes), next.rows, (uint64_t*)root.v));
-            }
+            CK(c.commit(log_inv_rate, k, next));
+            CK(commitment_root(ctx, next, root));
             T.add_canon(root);
             // E1: OOD
             std::vector<fe> zs(cfg.ood_samples[r]);
             T.challenge_scalars(zs.data(), zs.size());
             std::vector<fe> ood_ans(zs.size());
-            for (size_t j = 0; j < zs.size(); j++) {
-                if (next.host) ood_ans[j] = host_whir::horner(d_c, (size_t)1 << nv, zs[j]);
-                else CK(eval_univariate_x(ctx, d_c, (size_t)1 << nv, zs[j], ood_ans[j]));
-            }
+            for (size_t j = 0; j < zs.size(); j++) CK(c.evaluate(zs[j], ood_ans[j]));
             T.add_scalars(ood_ans.data(), ood_ans.size());
             // P1
             CK(pow_round(ctx, T, cfg.pow_bits[r]));
             // Q1: STIR queries into the previous tree
             const std::vector<uint64_t> idx = stir_queries(T, domain_size, k, cfg.num_queries[r]);
             CK(emit_opening_hints(ctx, T, *prev, idx));
-            // W2: equality weights of the OOD and STIR points, scaled by powers of the combination randomness
+            // W2: equality weights of the OOD and STIR points
             const fe gamma = T.challenge_scalar();
             for (uint64_t i : idx) zs.push_back(h_pow(exp_gen, i));
-            fe g;
-            // not a rank's block: the round's first sumcheck launch adds them.  At every number of points: the fused kernel runs at three waves
-            // per SIMD where eq_accumulate_kernel has four, and the round of 110 points still came out ahead (EXPERIMENTS.md round 29)
-            // Tables short enough for the host tail go there first, and the weights join w on the host.
-            CK(maybe_to_host());
-            CK(eq_weights(bw[cur], nv, zs, gamma, 0, &g, /*defer=*/!host && !sharded && len >= 2 && k >= 1));
-            have_claim = false;  // the new weights' sums include the folded polynomial at the STIR points, which the prover never evaluates
+            CK(round_weights(zs, gamma));
             // W3
             CK(sumcheck_rounds(k));
             CK(maybe_gather());
-            com = next;
+            com = std::move(next);
             prev = &com;
             domain_size /= 2;
             exp_gen = h_mul(exp_gen, exp_gen);
         }
-        return final_round(*prev, nv, domain_size);
+        return final_round(*prev, domain_size);
     }
 
     // final round: the folded polynomial in the clear, PoW, final STIR openings, final sumcheck
-    int final_round(const Commitment& prev, unsigned nv, size_t domain_size) {
+    int final_round(const Commitment& prev, size_t domain_size) {
         if (sharded) {  // a schedule that ends before the blocks got short: finish replicated
             const size_t cap = len * G;
             ALLOC(fp0, cap);
@@ -803,40 +819,32 @@ struct WhirProver {
             ALLOC(fw1, cap / 2 ? cap / 2 : 1);
             CK(gather(fp0, fp1, fw0, fw1));
         }
-        const unsigned nv2 = nv - k;
-        std::vector<fe> fin((size_t)1 << nv2);
-        if (C.host) {
-            host_whir::fold_coeffs(hc.data(), nv, rs.data(), k, fin.data());
-        } else {
-            ALLOC(d_final, (size_t)1 << nv2);
-            CK(pk_fold_coeffs(ctx, U(d_c), nv, (const uint64_t*)rs.data(), k, U(d_final)));
-            CK(pk_memcpy_d2h(ctx, fin.data(), d_final, 32 * fin.size()));
-        }
+        CK(c.fold(rs, k));
+        std::vector<fe> fin;
+        CK(c.to_host(fin));
         T.add_scalars(fin.data(), fin.size());
         CK(pow_round(ctx, T, cfg.final_pow_bits));
         const std::vector<uint64_t> idx = stir_queries(T, domain_size, k, cfg.final_queries);
         CK(emit_opening_hints(ctx, T, prev, idx));
-        CK(sumcheck_rounds(nv2));
+        CK(sumcheck_rounds(c.nv));
         return pow_round(ctx, T, cfg.final_folding_pow_bits);  // whir.go:196-201
     }
 
     // deferred_weight_evaluations hint (common.go:63-73): each linear weight's MLE at the full folding point.
     // Round t folds index bit t (LSB first), so the point in eval_eq's MSB-first order is reverse(all_r).
-    int deferred_hint(fe* const* d_weights, const size_t* weight_len, unsigned n_weights) {
-        if (!n_weights) return PK_OK;
+    int deferred_hint(const Weights& W) {
+        if (!W.n) return PK_OK;
         std::vector<fe> point(all_r.rbegin(), all_r.rend());
         const bool sh = whir_sharded(ctx, n);  // the eq table and the dot products by blocks, like the weights themselves
-        std::vector<fe> evals(n_weights);
-        const bool rows3 = rows_at_equal_stride3(d_weights, weight_len, n_weights);
-        if (h_weight) {  // the opening started on the host: its one weight is there too
+        std::vector<fe> evals(W.n);
+        if (W.host) {
             uint64_t o[4] = {};
-            host_tail::dot_rows_eq(h_weight, 0, 1, point.data(), n, weight_len[0], o);
+            host_tail::dot_rows_eq(W.row[0], 0, 1, point.data(), n, W.len[0], o);
             evals[0] = h_load(o);
-        } else if (!sh && (rows3 || n_weights == 1)) {  // without the table: each lane forms its entries from the point's half tables
+        } else if (!sh && (W.equal_stride3 || W.n == 1)) {  // without the table: each lane forms its entries from the point's half tables
             uint64_t o[12] = {};
-            CK(dot_rows_eq(ctx, U(d_weights[0]), rows3 ? (size_t)(d_weights[1] - d_weights[0]) : 0, n_weights, (const uint64_t*)point.data(), n,
-                           weight_len[0], o));
-            for (unsigned i = 0; i < n_weights; i++) evals[i] = h_load(o + 4 * i);
+            CK(dot_rows_eq(ctx, U(W.row[0]), W.stride(), W.n, (const uint64_t*)point.data(), n, W.len[0], o));
+            for (unsigned i = 0; i < W.n; i++) evals[i] = h_load(o + 4 * i);
         } else {
             ALLOC(d_eq, B0);
             if (sh) {
@@ -847,30 +855,29 @@ struct WhirProver {
             }
             Across ac(ctx, sh);
             CK(ac.rc);
-            if (rows3) {  // the three external rows against the eq table in one pass
+            if (W.equal_stride3) {  // the three external rows against the eq table in one pass
                 uint64_t o[12] = {};
-                CK(dot_rows(ctx, U(d_weights[0] + off0), (size_t)(d_weights[1] - d_weights[0]), 3, U(d_eq), nullptr, in_block(weight_len[0], off0, B0), o));
+                CK(dot_rows(ctx, U(W.row[0] + off0), W.stride(), 3, U(d_eq), nullptr, in_block(W.len[0], off0, B0), o));
                 for (int i = 0; i < 3; i++) evals[i] = h_load(o + 4 * i);
             } else {
-                for (unsigned i = 0; i < n_weights; i++) {
+                for (unsigned i = 0; i < W.n; i++) {
                     uint64_t o[4] = {};
-                    if (sh || weight_len[i]) CK(pk_dot(ctx, U(d_weights[i] + off0), U(d_eq), in_block(weight_len[i], off0, B0), o));
+                    if (sh || W.len[i]) CK(pk_dot(ctx, U(W.row[i] + off0), U(d_eq), in_block(W.len[i], off0, B0), o));
                     evals[i] = h_load(o);
                 }
             }
         }
         std::vector<uint8_t> buf;
-        put_vec(buf, evals.data(), n_weights);
+        put_vec(buf, evals.data(), W.n);
         T.hint(buf.data(), buf.size());
         return PK_OK;
     }
 };
-int whir_prove(pk_ctx* ctx, Arena& A, const pk_whir_config& cfg, const Commitment& C, fe* const* d_weights, const size_t* weight_len,
-               unsigned n_weights, const fe* weight_sums, Transcript& T, const fe* h_evals = nullptr, const fe* h_weight = nullptr) {
+int whir_prove(pk_ctx* ctx, Arena& A, const pk_whir_config& cfg, const Commitment& C, const Weights& W, Transcript& T) {
     WhirProver P(ctx, A, cfg, C, T);
-    CK(P.start(d_weights, weight_len, n_weights, weight_sums, h_evals, h_weight));
+    CK(P.start(W));
     CK(P.rounds());
-    return P.deferred_hint(d_weights, weight_len, n_weights);
+    return P.deferred_hint(W);
 }
 
 // batch_commit_to_polynomial (provekit/prover/src/whir_r1cs.rs:182-209)
@@ -906,7 +913,7 @@ int batch_commit_compute(pk_ctx* ctx, Arena& A, unsigned m, const pk_whir_config
     out.f_evals = f;
     out.g_evals = g;
     fe* polys[2] = {fe_, ge_};
-    int rc = whir_commit_compute(ctx, A, cfg.n_vars, cfg.starting_log_inv_rate, cfg.folding_factor, polys, 2, out.com);
+    int rc = whir_commit_compute(ctx, A, /*host=*/false, cfg.n_vars, cfg.starting_log_inv_rate, cfg.folding_factor, polys, 2, out.com);
     out.com.evals[0] = f;
     out.com.evals[1] = g;
     return rc;
@@ -999,15 +1006,17 @@ struct Proof {
           lgG(ilog2(G)), rank((unsigned)comm_rank(c)), st_sharded(whir_sharded(c, sc->m)), blk(((size_t)1 << sc->m) / (st_sharded ? G : 1)),
           blk_lo(st_sharded ? (size_t)rank * blk : 0), aux(c), g_univ(4 * (size_t)sc->m_0) {}
 
+    // where the blinding commitment runs, decided once by init(): what each means is told above commit_witness
+    enum class BlindingAt { HostThread, SideStream, Inline } blinding_at = BlindingAt::Inline;
+
     int init() {
-        if (!ctx->latency_mode || G != 1) return PK_OK;
-        CK(side.open(ctx, s));
-        aux = side.c;
+        if (ctx->latency_mode && G == 1) {
+            CK(side.open(ctx, s));
+            aux = side.c;
+        }
+        blinding_at = host_tail_takes(ctx, false, (size_t)2 << s->nb) ? BlindingAt::HostThread : aux != ctx ? BlindingAt::SideStream : BlindingAt::Inline;
         return PK_OK;
     }
-    // The blinding WHIR on the host thread (host_whir.hpp): its tables are within the host tail's threshold and the context is not a rank
-    // of a device set -- the condition under which prove_blinding's tables stand on the host.  Else every line of the device route.
-    bool blinding_on_host() const { return host_tail_len(ctx) && ((size_t)2 << s->nb) <= host_tail_len(ctx); }
     // the external rows go to the side context too, unless there are none
     pk_ctx* rows_ctx() const { return n_witness ? aux : ctx; }
     // a failure on the side context is reported where the caller looks
@@ -1035,13 +1044,21 @@ struct Proof {
 
 // blinding univariates: 4 random coefficients per variable [RNG], committed with the small WHIR (whir_r1cs.rs:212-226): the device
 // work, on `ctx`'s stream.  On the side context the coefficients come back through its mailbox, else at once.
+// First the draw, shared with the host route: 4 m_0 coefficients at the head of a zeroed table of 2^nb
+int blinding_draw(pk_ctx* ctx, Proof& P, fe*& d_blind) {
+    Arena& A = P.A;
+    const size_t NB = (size_t)1 << P.s->nb;
+    ALLOC(tab, NB);
+    d_blind = tab;
+    CK(pk_memset_zero(ctx, d_blind, 32 * NB));
+    return random_fe(ctx, U(d_blind), P.g_univ.size(), P.key, RNG_BLIND);  // 4 m_0 <= 108: one workgroup
+}
 int blinding_compute(pk_ctx* ctx, Proof& P) {
     Arena& A = P.A;
     const size_t NB = (size_t)1 << P.s->nb, n = P.g_univ.size();
-    ALLOC(d_blind, NB);
-    CK(pk_memset_zero(ctx, d_blind, 32 * NB));
-    CK(random_fe(ctx, U(d_blind), n, P.key, RNG_BLIND));  // n = 4 m_0 <= 108: one workgroup
-    if (ctx == P.ctx) {
+    fe* d_blind = nullptr;
+    CK(blinding_draw(ctx, P, d_blind));
+    if (P.blinding_at == Proof::BlindingAt::Inline) {
         CK(pk_memcpy_d2h(ctx, P.g_univ.data(), d_blind, 32 * n));
     } else {
         CK(mail_alloc(ctx, 32 * n, (void**)&P.h_univ));
@@ -1050,7 +1067,7 @@ int blinding_compute(pk_ctx* ctx, Proof& P) {
     return batch_commit_compute(ctx, A, P.s->nb + 1, P.s->whir_hiding, d_blind, NB, P.key, RNG_MASK_B, RNG_G_B, P.B);
 }
 
-// The host route (Proof::blinding_on_host), first half: the blinding coefficients, the two tables and their coefficient forms are drawn
+// The host route (BlindingAt::HostThread), first half: the blinding coefficients, the two tables and their coefficient forms are drawn
 // and formed on the device as blinding_compute does -- three small launches -- and come over in ONE transfer, f | g | their coefficient
 // forms, 2^(nb+1) entries each (tables_to_host: one launch, one synchronisation).  Nothing of the blinding polynomial is on the device
 // afterwards.  Called before the witness commitment is enqueued, so that its wait is for these launches alone.
@@ -1058,13 +1075,12 @@ int blinding_tables_to_host(pk_ctx* ctx, Proof& P) {
     Arena& A = P.A;
     const unsigned mb = P.s->nb + 1;
     const size_t NB = (size_t)1 << P.s->nb, N = 2 * NB, n = P.g_univ.size();
-    ALLOC(d_blind, NB);
+    fe* d_blind = nullptr;
+    CK(blinding_draw(ctx, P, d_blind));
     ALLOC(f, N);
     ALLOC(g, N);
     ALLOC(fc, N);
     ALLOC(gc, N);
-    CK(pk_memset_zero(ctx, d_blind, 32 * NB));
-    CK(random_fe(ctx, U(d_blind), n, P.key, RNG_BLIND));
     CK(to_coeffs_generated(ctx, mb, U(d_blind), NB, P.key, RNG_MASK_B, RNG_G_B, U(f), U(g), U(fc), U(gc)));
     P.B.h_tables.resize(4 * N);
     const uint64_t* src[4] = {U(f), U(g), U(fc), U(gc)};
@@ -1074,7 +1090,7 @@ int blinding_tables_to_host(pk_ctx* ctx, Proof& P) {
     return PK_OK;
 }
 // ... second half: the commitment of the tables that came over, on the host thread (host_whir.hpp)
-void blinding_commit_host(const pk_ctx* ctx, Proof& P) {
+int blinding_commit_host(pk_ctx* ctx, Proof& P) {
     BatchCommit& out = P.B;
     const pk_whir_config& cfg = P.s->whir_hiding;
     const size_t N = (size_t)2 << P.s->nb;
@@ -1082,9 +1098,9 @@ void blinding_commit_host(const pk_ctx* ctx, Proof& P) {
     out.f_evals = f;
     out.g_evals = g;
     fe* polys[2] = {g + N, g + 2 * N};
-    whir_commit_host(ctx, cfg.n_vars, cfg.starting_log_inv_rate, cfg.folding_factor, polys, 2, out.com);
     out.com.evals[0] = f;
     out.com.evals[1] = g;
+    return whir_commit_compute(ctx, P.A, /*host=*/true, cfg.n_vars, cfg.starting_log_inv_rate, cfg.folding_factor, polys, 2, out.com);
 }
 
 // external rows (whir_r1cs.rs:81-91, 382-412): eq(alpha) and the three rows [S4] on `ctx`'s stream.  On the side context the six
@@ -1104,26 +1120,22 @@ int external_rows(pk_ctx* ctx, Proof& P) {
 
 // --- commit to the masked witness polynomial (whir_r1cs.rs:57-69), and -- underneath it -- to the blinding polynomial, which depends on
 // nothing but the proof's key.  The witness commitment's launches fill the chip for 2.6 ms (several times that under load), and this
-// thread would only wait for its root.  What runs where:
-//   blinding tables within the host tail's threshold (blinding_on_host: every size pk_prove is used at): the tables are drawn on the
+// thread would only wait for its root.  What runs where (Proof::blinding_at):
+//   HostThread: the blinding tables (2^(nb+1) entries) go to the host tail -- every size pk_prove is used at.  They are drawn on the
 //     device FIRST and come over in one transfer (blinding_tables_to_host); then, between the witness commitment's launches and read_root,
 //     the 32-leaf codeword, its leaf hashes (chains of 31 compressions, ~0.7 ms of host time) and the tree are computed HERE, on this
-//     thread, in either mode;
+//     thread, in either mode, and so is the whole blinding WHIR later (host_whir.hpp);
 //   otherwise (threshold 0, a device set, a larger blinding polynomial) it is device work, 0.6 ms of launches that keep 32 lanes busy:
-//     in latency mode on the side stream right after the witness commitment's launches, underneath them; in plain mode inline on the
+//     SideStream, in latency mode, right after the witness commitment's launches, underneath them; Inline, in plain mode, on the
 //     prover's own stream, from zk_sumcheck.
 // Only the blinding commitment's transcript half (root, OOD, batching) waits for its turn (blinding_transcript).
 int Proof::commit_witness() {
-    const bool hostb = blinding_on_host();
-    if (hostb) CK(blinding_tables_to_host(ctx, *this));
+    if (blinding_at == BlindingAt::HostThread) CK(blinding_tables_to_host(ctx, *this));
     CK(batch_commit_compute(ctx, A, s->m, s->whir_witness, d_witness, n_witness, key, RNG_MASK, RNG_G, W));
-    if (hostb) {
-        blinding_commit_host(ctx, *this);
-    } else if (aux != ctx) {
-        CK(relay(aux, blinding_compute(aux, *this), "blinding commitment"));
-    }
+    if (blinding_at == BlindingAt::HostThread) CK(blinding_commit_host(ctx, *this));
+    if (blinding_at == BlindingAt::SideStream) CK(relay(aux, blinding_compute(aux, *this), "blinding commitment"));  // Inline: zk_sumcheck enqueues it
     fe root;
-    CK(read_root(ctx, U(W.com.nodes), W.com.rows, (uint64_t*)root.v));
+    CK(commitment_root(ctx, W.com, root));
     return whir_commit_transcript(ctx, s->whir_witness, root, T, W.com);
 }
 
@@ -1131,9 +1143,8 @@ int Proof::commit_witness() {
 // for its stream and rewinds its mailbox), then the coefficients are taken out of the mailbox before anything is allocated there.
 int Proof::blinding_transcript() {
     fe root;
-    if (B.com.host) root = B.com.nodes[1];  // everything stands in host memory since commit_witness
-    else CK(relay(aux, read_root(aux, U(B.com.nodes), B.com.rows, (uint64_t*)root.v), "blinding commitment"));
-    if (h_univ) memcpy(g_univ.data(), h_univ, 32 * g_univ.size());
+    CK(relay(aux, commitment_root(aux, B.com, root), "blinding commitment"));
+    if (blinding_at == BlindingAt::SideStream) memcpy(g_univ.data(), h_univ, 32 * g_univ.size());
     return whir_commit_transcript(ctx, s->whir_hiding, root, T, B.com);
 }
 
@@ -1172,7 +1183,7 @@ int Proof::zk_sumcheck() {
         CK(pk_r1cs_witness_bounds(ctx, s->r1cs, U(d_witness), m_0, U(d_a), U(d_b), U(d_cc)));  // S1
         CK(eq_suffix_tables(ctx, (const uint64_t*)r.data(), m_0, U(d_eq)));                  // S2: the levels E_i instead of the table (mle.hip)
     }
-    if (aux == ctx && !B.com.host) CK(blinding_compute(ctx, *this));  // else the side stream, or the host, finished it long ago
+    if (blinding_at == BlindingAt::Inline) CK(blinding_compute(ctx, *this));  // else the side stream, or the host, finished it long ago
     CK(blinding_transcript());
     lap("bounds+eq+blinding commit");
     fe* z[4] = {d_a, d_b, d_cc, d_eq};
@@ -1297,30 +1308,19 @@ int Proof::prove_blinding() {
         wv[4 * i + 3] = h_mul(wv[4 * i + 2], alpha[i]);
     }
     uint64_t fg[8];
-    // The host tail: a blinding opening no longer than the threshold never puts its sumcheck on the device.  The two evaluation tables
-    // come over once; the statement's two sums, the opening's tables and its deferred hint are formed from them and from wv on the host.
-    const size_t NB2 = (size_t)2 << s->nb, tail = host_tail_len(ctx);
-    std::vector<fe> h_evals;
-    fe* d_bw = nullptr;
-    if (B.com.host) {  // the tables never left the host: f and g stand back to back in the commitment's own memory
+    const fe* weight = wv.data();
+    if (B.com.host) {  // the tables never left the host: the statement's two sums, the opening's tables and its deferred hint are formed from them and from wv there
         host_tail::dot2(wv.data(), B.f_evals, B.g_evals, nbw, fg);
-    } else if (tail && NB2 <= tail) {
-        h_evals.resize(2 * NB2);
-        const uint64_t* src[2] = {U(B.f_evals), U(B.g_evals)};
-        const size_t cnt[2] = {NB2, NB2};
-        CK(tables_to_host(ctx, src, cnt, 2, U(h_evals.data())));
-        host_tail::dot2(wv.data(), h_evals.data(), h_evals.data() + NB2, nbw, fg);
     } else {
-        ALLOC(bw_, nbw);
-        d_bw = bw_;
+        ALLOC(d_bw, nbw);
         CK(pk_memcpy_h2d(ctx, d_bw, wv.data(), 32 * nbw));
         CK(pk_dot2(ctx, U(d_bw), U(B.f_evals), U(B.g_evals), nbw, fg));
+        weight = d_bw;
     }
     const fe sums[2] = {h_load(fg), h_load(fg + 4)};
     T.add_scalars(sums, 2);
-    fe* wts[1] = {d_bw};  // on the host path never read: the weight is wv
-    const fe* h_ev = B.com.host ? B.f_evals : h_evals.empty() ? nullptr : h_evals.data();
-    return whir_prove(ctx, A, s->whir_hiding, B.com, wts, &nbw, 1, sums, T, h_ev, h_ev ? wv.data() : nullptr);
+    const Weights wts{B.com.host, 1, {weight}, {nbw}, sums};
+    return whir_prove(ctx, A, s->whir_hiding, B.com, wts, T);
 }
 
 // --- the statement over the witness commitment (whir_r1cs.rs:81-91): external rows, their six sums, the claimed_evaluations hint
@@ -1353,9 +1353,8 @@ int Proof::witness_statement() {
 
 // --- WHIR weighted batch opening (whir_r1cs.rs:94-95)
 int Proof::prove_witness() {
-    fe* wts[3] = {rows, rows + n_witness, rows + 2 * n_witness};
-    const size_t wlen[3] = {n_witness, n_witness, n_witness};
-    CK(whir_prove(ctx, A, s->whir_witness, W.com, wts, wlen, 3, row_sums, T));
+    const Weights wts{false, 3, {rows, rows + n_witness, rows + 2 * n_witness}, {n_witness, n_witness, n_witness}, row_sums};
+    CK(whir_prove(ctx, A, s->whir_witness, W.com, wts, T));
     return pk_ctx_sync(ctx);
 }
 

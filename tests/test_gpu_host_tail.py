@@ -107,8 +107,8 @@ def launches(c, scheme, d_z):
 @pytest.mark.parametrize("latency", [False, True], ids=["plain", "latency"])
 def test_the_rounds_move_to_the_host_and_zero_brings_them_back(own_ctx, oracle, latency):
     """m = 12, m_0 = 9: at 0 the zk sumcheck is 9 cubic launches and nothing goes through the tables' transfer; at 2^11 no cubic launch is
-    left, the only quadratic launch is the witness opening's round 1, and the transfers are three: the zk tables, the blinding
-    opening's evaluation tables, the witness opening's p and w; at 2^4 the first 6 cubic rounds stay; back at 0, the first counts"""
+    left, the only quadratic launch is the witness opening's round 1, and the transfers are three: the four blinding tables (f, g and
+    their coefficient forms), the zk tables, the witness opening's p and w; at 2^4 the first 6 cubic rounds stay; back at 0, the first counts"""
     c = own_ctx
     m, m_0 = 12, 9
     scheme, r1cs, zm, _ = make_scheme(c, oracle, m, m_0, False)
