@@ -419,6 +419,12 @@ int pk_multipath_serialize(const uint64_t *indices, size_t k, size_t path_len, c
  * pk_prove = WhirR1CSProver::prove(&self, &R1CS, Vec<FieldElement>) -> WhirR1CSProof{transcript}
  * (provekit/prover/src/whir_r1cs.rs:36-100): d_witness = n_witness Montgomery FEs on the device; the proof string is
  * written to transcript_out (capacity cap; *len receives its length).
+ * n_witness must equal the scheme's num_witnesses.  n_witness = 0 (an R1CS without columns) is a statement like any other: d_witness
+ * must still be non-NULL and nothing is read through it; the committed polynomial is the mask alone, the three external rows are
+ * empty, so the six claimed evaluations and the three deferred weight evaluations are zero, and the witness opening starts by the
+ * plain sequence (the rows do not join its first launch).  Shapes: every config whir_config_error passes -- folding factors 1 .. 8,
+ * rates from 1/2 down, 0 .. 16 folding rounds with folding_factor * (rounds + 1) <= n_vars, 0 .. 4 OOD samples, any grinding
+ * difficulty -- at 1 <= m, m_0 <= 27 (tests/test_gpu_prove_shapes.py proves at every one of them against the oracle prover).
  * Randomness: the reference takes the ZK mask, the random polynomial and the blinding univariates from thread_rng
  * (provekit/common/src/utils/zk_utils.rs:13-22, provekit/prover/src/whir_r1cs.rs:197,212-221).  With
  * rng_seed32 == NULL (production) pk_prove draws a fresh 256-bit key from the OS CSPRNG (getrandom) for every proof

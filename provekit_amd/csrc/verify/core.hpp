@@ -270,12 +270,14 @@ inline fe mle_eval_table(std::vector<fe> v, const std::vector<fe>& point) {  // 
 }
 
 // ---- the statement's shape: what a prover of this library accepts --------------------------------------------------------------
-inline bool config_ok(const pk_whir_config& c, std::string& why) {
+// max_fold: pk_scheme_create takes folding factors up to 8 (whir_config.hip whir_config_error) and so does the walk of its proofs
+// (statement_ok); libprovekit_whir's prover stops at 4 (whir_pcs/pcs.hpp config_ok)
+inline bool config_ok(const pk_whir_config& c, std::string& why, unsigned max_fold = 4) {
     auto bad = [&](const char* s) {
         why = s;
         return false;
     };
-    if (c.folding_factor < 1 || c.folding_factor > 4) return bad("folding_factor must be 1..4");
+    if (c.folding_factor < 1 || c.folding_factor > max_fold) return bad(max_fold == 4 ? "folding_factor must be 1..4" : "folding_factor must be 1..8");
     if (c.batch_size < 1 || c.batch_size > 4) return bad("batch_size must be 1..4");
     if (c.n_rounds > PK_MAX_WHIR_ROUNDS) return bad("too many WHIR rounds");
     if (c.n_vars > 28 || c.starting_log_inv_rate < 1 || c.n_vars + c.starting_log_inv_rate > 28) return bad("n_vars + log_inv_rate must be <= 28");
@@ -294,7 +296,7 @@ inline bool config_ok(const pk_whir_config& c, std::string& why) {
     return true;
 }
 inline bool statement_ok(const Statement& st, std::string& why) {
-    if (st.m < 2 || st.m_0 < 1 || st.m_0 > 28) {
+    if (st.m < 1 || st.m_0 < 1 || st.m_0 > 28) {
         why = "m / m_0 out of range";
         return false;
     }
@@ -302,7 +304,7 @@ inline bool statement_ok(const Statement& st, std::string& why) {
         why = "hash version must be 1 or 2";
         return false;
     }
-    if (!config_ok(st.w, why) || !config_ok(st.b, why)) return false;
+    if (!config_ok(st.w, why, 8) || !config_ok(st.b, why, 8)) return false;
     if (st.w.n_vars != st.m) {
         why = "whir_witness.n_vars must equal m";
         return false;

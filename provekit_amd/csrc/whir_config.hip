@@ -13,7 +13,8 @@ namespace pk {
 // host-only entry point that takes a config.
 const char* whir_config_error(const pk_whir_config* c) {
     if (!c) return "null pointer";
-    if (c->folding_factor < 1 || c->folding_factor > 8 || c->n_rounds > PK_MAX_WHIR_ROUNDS) return "bad WHIR config";
+    if (c->folding_factor < 1 || c->folding_factor > 8) return "folding factor out of range (1 .. 8)";
+    if (c->n_rounds > PK_MAX_WHIR_ROUNDS) return "too many WHIR rounds";
     if (c->n_vars < c->folding_factor * (c->n_rounds + 1)) return "WHIR rounds exceed the number of variables";
     if (c->commitment_ood_samples > 4) return "too many OOD samples";
     if (c->batch_size < 1 || c->batch_size > 4) return "batch size out of range";

@@ -1,6 +1,7 @@
 """GPU: the prover's host tail (pk_selftest_set_host_tail; csrc/host_tail.hpp, csrc/prover.hip sumcheck_round_loop).  Whole proofs with the
 switch at 0 -- every sumcheck round on the device -- against every threshold 2^1 .. 2^11, byte for byte, plain and in latency mode, and at
-m <= 10 against the oracle's prover (oracle/prover_ref.py).  With folding factor 4 the thresholds meet every position of the boundary:
+m <= 10 against the oracle's prover (oracle/prover_ref.py).  With folding factor 4 (the other folds, 1 .. 8, with the boundary inside each
+opening: tests/test_gpu_prove_shapes.py) the thresholds meet every position of the boundary:
 
   zk sumcheck (tables of 2^m_0):  2^11 >= 2^m_0: before the first round, all rounds on the host;  in between: in the middle;
                                   2^2: the last round alone (its tables have 4 entries before its fold);  2^1: never reached
