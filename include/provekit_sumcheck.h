@@ -33,9 +33,10 @@
  * those m evaluation claims and proves nothing about them.  pkw_open / pkw_verify (provekit_whir.h) at point_out is the way to
  * establish them for committed tables: point_out's coordinate order is already pkw_open's.
  *
- * Out of scope: hiding / zero knowledge of the round polynomials; more than 4 tables, or powers of one table in a term; a batched
- * device verifier.  Device sets: a prover of pks_prover_create on a context of a set runs whole on its rank;
- * provekit_sumcheck_sharded.h shards the same proof over the set's ranks (pkss_prover_create, pkss_prove).
+ * Out of scope: hiding / zero knowledge of the round polynomials; a batched device verifier.  More than 4 tables or terms, and powers
+ * of one table in a term, are provekit_sumcheck_wide.h's (pksw_*: 16 tables, 16 terms, degree 5; another label).  Device sets: a
+ * prover of pks_prover_create on a context of a set runs whole on its rank; provekit_sumcheck_sharded.h shards the same proof over
+ * the set's ranks (pkss_prover_create, pkss_prove).
  *
  * Conventions: provekit_hip.h's.  Every call returns PK_OK or a negative PK_ERR_*; "rejected" is a verdict in the pkv_result, not an
  * error.  Field elements are Montgomery 4 x u64 unless a parameter says canonical.  A pks_prover is single-caller.

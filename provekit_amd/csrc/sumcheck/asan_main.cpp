@@ -18,12 +18,19 @@
 //     length.  Then pkss_plan for m = 1 .. 4 at this (n, world): prints "n m g c S local_len handover_len arena_bytes" per line, or the
 //     refusal.  With `lone`, one more column: the bytes of the lone prover's arena at this (n, m), the layout of a device set of one.
 //     exit 1: the rule is not a bijection.
+//   pks_verify_asan wide verify <case file>
+//       u32 n, m, T, has_tau, n_bind, lens[16], factors[16][5] | u64 coeffs[16][4] | then as `verify`
+//     the same for a wide statement (provekit_sumcheck_wide.h) and pksw_verify.
+//   pks_verify_asan wide lane <D> <m> <T> <weighted 0|1> <weight> <repeats> T x (<indices joined by '.'> <coeff>) m x (<lo> <hi>)
+//     runs wide_lane.hpp's wide_lane_accumulate<D> -- the wide kernel's arithmetic, compiled for the host -- on the caller's terms (the
+//     kinds and the packed lists taken by wide_terms, as wide.hip's launch takes them) and per-table (lo, hi), and prints the D + 1 sums.
 #include <string>
 
 #include "../../../include/provekit_sumcheck.h"
 #include "../asan_case.hpp"
 #include "lane.hpp"
 #include "layout.hpp"
+#include "wide_lane.hpp"
 
 namespace {
 
@@ -195,15 +202,103 @@ int run_shard(unsigned n, unsigned world, bool lone) {
     return 0;
 }
 
+int run_wide_verify(const char* path) {
+    if (!asan_case::read_file(path)) return 2;
+    pksw_statement st;
+    memset(&st, 0, sizeof st);
+    uint32_t head[5];
+    take(head, sizeof head);
+    st.n = head[0], st.m = head[1], st.T = head[2], st.has_tau = head[3], st.n_bind = head[4];
+    take(st.lens, sizeof st.lens);
+    take(st.factors, sizeof st.factors);
+    take(st.coeffs, sizeof st.coeffs);
+    size_t proof_len = 0;
+    if (int rc = pksw_proof_bytes(&st, &proof_len)) {
+        printf("%d 0 REFUSED 0 %s\n", rc, pksw_create_error());
+        return 0;
+    }
+    uint32_t with_expected, pattern_len;
+    take(&with_expected, 4);
+    take(&pattern_len, 4);
+    uint8_t* pattern = (uint8_t*)take_block(pattern_len);
+    uint64_t* tau = st.has_tau ? (uint64_t*)take_block(32 * (size_t)st.n) : nullptr;
+    uint64_t* bind = st.n_bind ? (uint64_t*)take_block(32 * (size_t)st.n_bind) : nullptr;
+    uint64_t* expected = with_expected ? (uint64_t*)take_block(32) : nullptr;
+    uint32_t count;
+    take(&count, 4);
+    uint64_t* point = (uint64_t*)malloc(32 * (size_t)st.n);
+    uint64_t* finals = (uint64_t*)malloc(32 * (size_t)st.m);
+    for (uint32_t c = 0; c < count; c++) {
+        uint64_t len;
+        take(&len, 8);
+        uint8_t* proof = (uint8_t*)take_block(len);
+        pkv_result r;
+        const int rc = pksw_verify(&st, pattern_len ? pattern : nullptr, pattern_len, tau, bind, expected, proof, len, point, finals, &r);
+        if (rc)
+            printf("%d 0 REFUSED 0 %s\n", rc, pksw_create_error());
+        else
+            printf("0 %d %s %llu\n", r.accepted, pks_check_name(r.check), (unsigned long long)r.offset);
+        free(proof);
+    }
+    free(point), free(finals), free(expected), free(bind), free(tau), free(pattern);
+    return 0;
+}
+
+template <int D>
+void wide_lane(const pk::fe* lo, const pk::fe* hi, const pks::WideTerms& tm, bool weighted, const pk::fe& w, unsigned repeats) {
+    pk::fe acc[D + 1];
+    for (int k = 0; k <= D; k++) acc[k] = pk::fe_zero();
+    auto load = [&](unsigned j, pk::fe& l, pk::fe& h) { l = lo[j], h = hi[j]; };
+    for (unsigned r = 0; r < repeats; r++) pks::wide_lane_accumulate<D>(tm, load, weighted, w, acc);
+    for (int k = 0; k <= D; k++) print_hex(acc[k]);
+}
+
+int run_wide_lane(int argc, char** argv) {  // argv[3 ..]: D m T weighted weight repeats, the terms, the pairs
+    if (argc < 9) return 2;
+    pksw_statement st;
+    memset(&st, 0, sizeof st);
+    const unsigned D = (unsigned)atoi(argv[3]);
+    st.n = 1, st.m = (unsigned)atoi(argv[4]), st.T = (unsigned)atoi(argv[5]);
+    const bool weighted = atoi(argv[6]) != 0;
+    const unsigned repeats = (unsigned)atoi(argv[8]);
+    pk::fe w, lo[PKSW_MAX_TABLES], hi[PKSW_MAX_TABLES];
+    if (st.m < 1 || st.m > PKSW_MAX_TABLES || st.T < 1 || st.T > PKSW_MAX_TERMS || (unsigned)argc != 9 + 2 * st.T + 2 * st.m || !parse_hex(argv[7], w)) return 2;
+    for (unsigned t = 0; t < st.T; t++) {
+        for (const char* c = argv[9 + 2 * t]; *c; c++) {
+            if (st.lens[t] >= PKSW_MAX_DEGREE) return 2;
+            char* end;
+            st.factors[t][st.lens[t]++] = (unsigned)strtoul(c, &end, 10);
+            if (end == c || (*end && *end != '.')) return 2;
+            c = *end ? end : end - 1;
+        }
+        pk::fe coeff;
+        if (!parse_hex(argv[10 + 2 * t], coeff)) return 2;
+        memcpy(st.coeffs[t], coeff.v, 32);
+    }
+    std::string why;
+    if (!pks::statement_ok(&st, why) || pks::degree(st) != D) return fprintf(stderr, "%s\n", why.c_str()), 2;  // the kernel's caller takes D from the lists
+    for (unsigned j = 0; j < st.m; j++)
+        if (!parse_hex(argv[9 + 2 * st.T + 2 * j], lo[j]) || !parse_hex(argv[10 + 2 * st.T + 2 * j], hi[j])) return 2;
+    const pks::WideTerms tm = pks::wide_terms(st);
+#define PKSW_DEGREE(DEG) \
+    if (D == DEG) return wide_lane<DEG>(lo, hi, tm, weighted, w, repeats), 0;
+    PKSW_DEGREE(1) PKSW_DEGREE(2) PKSW_DEGREE(3) PKSW_DEGREE(4) PKSW_DEGREE(5)
+#undef PKSW_DEGREE
+    return 2;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
+    if (argc == 4 && !strcmp(argv[1], "wide") && !strcmp(argv[2], "verify")) return run_wide_verify(argv[3]);
+    if (argc >= 3 && !strcmp(argv[1], "wide") && !strcmp(argv[2], "lane")) return run_wide_lane(argc, argv);
     if (argc == 3 && !strcmp(argv[1], "verify")) return run_verify(argv[2]);
     if (argc >= 2 && !strcmp(argv[1], "lane")) return run_lane(argc, argv);
     if (argc >= 2 && !strcmp(argv[1], "lanes")) return run_lanes(argc, argv);
     const bool lone = argc == 5 && !strcmp(argv[4], "lone");
     if ((argc == 4 || lone) && !strcmp(argv[1], "shard")) return run_shard((unsigned)atoi(argv[2]), (unsigned)atoi(argv[3]), lone);
     fprintf(stderr, "usage: pks_verify_asan verify <case file> | lane <D> <lo> <hi> <coeff> <weight> <repeats> | "
-                    "lanes <D> <m> <T> <weighted> <weight> <repeats> T x (<mask> <coeff>) m x (<lo> <hi>) | shard <n> <world> [lone]\n");
+                    "lanes <D> <m> <T> <weighted> <weight> <repeats> T x (<mask> <coeff>) m x (<lo> <hi>) | shard <n> <world> [lone] | "
+                    "wide verify <case file> | wide lane <D> <m> <T> <weighted> <weight> <repeats> T x (<i.j.k> <coeff>) m x (<lo> <hi>)\n");
     return 2;
 }

@@ -21,7 +21,8 @@ struct Layout {
     size_t local_half = 0, handover = 0;  // the strides of the compact and the replicated tables
     size_t compact = 0, replicated = 0, gather_send = 0, gather_recv = 0, xchg_send = 0, xchg_recv = 0, scratch = 0, eq = 0, total = 0;
 };
-inline Layout layout(unsigned n, unsigned m, unsigned g) {
+// scratch_fes: one round's scratch, ROUND_SCRATCH_FES or the wide statements' WIDE_SCRATCH_FES
+inline Layout layout(unsigned n, unsigned m, unsigned g, size_t scratch_fes = pks::ROUND_SCRATCH_FES) {
     Layout L;
     L.g = g, L.S = g ? sharded_rounds(n, g) : 0;
     L.local_half = L.S >= 2 ? ((size_t)1 << (n - 1)) >> g : 0;
@@ -33,7 +34,7 @@ inline Layout layout(unsigned n, unsigned m, unsigned g) {
     L.xchg_send = L.gather_recv + G * block;
     L.xchg_recv = L.xchg_send + xchg;
     L.scratch = L.xchg_recv + G * xchg;
-    L.eq = L.scratch + pks::ROUND_SCRATCH_FES;
+    L.eq = L.scratch + scratch_fes;
     L.total = L.eq + pks::eq_split(n - 1).fes();
     return L;
 }

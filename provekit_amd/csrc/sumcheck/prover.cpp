@@ -1,7 +1,8 @@
 // prover.cpp -- the device half of libprovekit_sumcheck.so's C ABI: the prover (one arena, the round loop over round.hip, the
 // prover side of the transcript) and the round by itself, each written once for a lone context and for a rank of a device set; and
-// the lone entry points (prover_sharded.cpp has the device set's).  Host code; of the product library it calls what provekit_hip.h
-// declares.
+// the lone entry points (prover_sharded.cpp has the device set's), pks_* and the wide statements' pksw_*: the round loop and the round by
+// itself are templates over the statement, and only the launch differs (round.hip, wide.hip).  Host code; of the product library it
+// calls what provekit_hip.h declares.
 //
 // A lone prover is a device set of one: no round is sharded, and its exchange is the rank's own status and values.
 //
@@ -29,22 +30,33 @@ int hip_rc(hipError_t e) { return e == hipSuccess ? PK_OK : PK_ERR_HIP; }
 
 namespace pks {
 
-int make_prover(pk_ctx* ctx, const pks_statement* stmt, unsigned rank, unsigned world, std::unique_ptr<pks_prover>& out) {
-    std::unique_ptr<pks_prover> p(new pks_prover());  // its destructor gives back what a return or a throw below leaves behind
+namespace {
+
+// what a prover holds of its statement, either kind (stmt null: of the smallest one), and its arena.  The reason of a failure goes to `slot`
+template <class S>
+int equip(pks_prover* p, pk_ctx* ctx, const S* stmt, unsigned rank, unsigned world, std::string& slot) {
     p->ctx = ctx;
     p->rank = rank, p->world = world;
     unsigned g = 0;
     while ((1u << g) < world) g++;
-    p->lay = pkss::layout(stmt ? stmt->n : 1, stmt ? stmt->m : 1, g);
+    p->lay = pkss::layout(stmt ? stmt->n : 1, stmt ? stmt->m : 1, g, scratch_fes(S{}));
     if (stmt) {
-        p->st = *stmt;
         p->D = degree(*stmt);
         p->pattern = io_pattern(*stmt);
         p->split = eq_split(stmt->n - 1);
     }
     void* base = nullptr;
-    if (int rc = pk_malloc(ctx, 32 * p->lay.total, &base)) return g_error = "pk_malloc of the arena failed", rc;
+    if (int rc = pk_malloc(ctx, 32 * p->lay.total, &base)) return slot = "pk_malloc of the arena failed", rc;
     p->arena = (uint64_t*)base;
+    return PK_OK;
+}
+
+}  // namespace
+
+int make_prover(pk_ctx* ctx, const pks_statement* stmt, unsigned rank, unsigned world, std::unique_ptr<pks_prover>& out) {
+    std::unique_ptr<pks_prover> p(new pks_prover());  // its destructor gives back what a return or a throw below leaves behind
+    if (stmt) p->st = *stmt;
+    if (int rc = equip(p.get(), ctx, stmt, rank, world, g_error)) return rc;
     out = std::move(p);
     return PK_OK;
 }
@@ -78,9 +90,13 @@ unsigned first_differing(const std::vector<fe>& all) {
     return 0;
 }
 
-int prove(pks_prover* p, const uint64_t* const* d_tables, const uint64_t* tau_or_null, const uint64_t* bind, uint8_t* proof_out, size_t cap, size_t* len,
-          uint64_t* point_out, uint64_t* finals_out) {
-    const pks_statement& st = p->st;
+namespace {
+
+// the one round loop, of either statement: only the launch differs (round.hip's for a pks_statement, wide.hip's for a pksw_statement,
+// which is never sharded)
+template <class Stmt>
+int prove_any(pks_prover* p, const Stmt& st, const uint64_t* const* d_tables, const uint64_t* tau_or_null, const uint64_t* bind, uint8_t* proof_out, size_t cap,
+              size_t* len, uint64_t* point_out, uint64_t* finals_out) {
     const pkss::Layout& L = p->lay;
     const unsigned n = st.n, m = st.m, D = p->D, S = L.S, g = L.g;
     if (!d_tables || !len || (!proof_out && cap)) return fail(p, PK_ERR_BAD_ARG, "null pointer");
@@ -96,7 +112,7 @@ int prove(pks_prover* p, const uint64_t* const* d_tables, const uint64_t* tau_or
         p->handover_seconds = p->total_seconds = 0;
         uint64_t* const d_scratch = p->arena + 4 * L.scratch;
         uint64_t* const d_eq = p->arena + 4 * L.eq;
-        const uint64_t* const d_results = d_scratch + 4 * (size_t)4 * PKS_MAX_GRID;
+        const uint64_t* const d_results = d_scratch + 4 * results_at(st);
         auto compact = [&](unsigned j) { return p->arena + 4 * (L.compact + (size_t)j * L.local_half); };
         auto replicated = [&](unsigned j) { return p->arena + 4 * (L.replicated + (size_t)j * L.handover); };
 
@@ -130,7 +146,7 @@ int prove(pks_prover* p, const uint64_t* const* d_tables, const uint64_t* tau_or
 
         RoundTables rt{};
         std::vector<fe> point(n);
-        fe h[PKS_MAX_TERM_TABLES + 1];
+        fe h[MAX_ROUND_VALUES];
         for (unsigned i = 0; i < n; i++) {
             // round i: pairs of the tables at length 2^(n-i); from round 1 on they are folded by r_{i-1} on the way, into the arena
             const size_t pairs = (size_t)1 << (n - 1 - i);
@@ -219,8 +235,11 @@ int prove(pks_prover* p, const uint64_t* const* d_tables, const uint64_t* tau_or
     }
 }
 
-int round_alone(pk_ctx* ctx, const pks_statement& st, const uint64_t* const* d_tables, uint64_t* const* d_out_tables, size_t pairs, size_t mine,
-                const uint64_t* tau_rest_or_null, const uint64_t* fold_or_null, unsigned grid, const ShardSlice* shard, uint64_t* out) {
+// a round by itself, of either statement; a refusal's reason goes to `slot`
+template <class S>
+int round_any(pk_ctx* ctx, const S& st, std::string& slot, const uint64_t* const* d_tables, uint64_t* const* d_out_tables, size_t pairs, size_t mine,
+              const uint64_t* tau_rest_or_null, const uint64_t* fold_or_null, unsigned grid, const ShardSlice* shard, uint64_t* out) {
+    auto refuse = [&](const char* why) { return pk::refuse(slot, why); };
     if (grid > PKS_MAX_GRID) return refuse("grid must be 0..1024");
     if (fold_or_null && !d_out_tables) return refuse("a fold needs output tables");
     unsigned R = 0;  // the round's length is 2 * pairs = 2^(R + 1)
@@ -242,9 +261,9 @@ int round_alone(pk_ctx* ctx, const pks_statement& st, const uint64_t* const* d_t
             eq_split_build(split, t.data(), eq);
         }
         void* base = nullptr;
-        if (int rc = pk_malloc(ctx, 32 * (ROUND_SCRATCH_FES + split.fes()), &base)) return rc;
+        if (int rc = pk_malloc(ctx, 32 * (scratch_fes(st) + split.fes()), &base)) return rc;
         uint64_t* const d_scratch = (uint64_t*)base;
-        uint64_t* const d_eq = d_scratch + 4 * ROUND_SCRATCH_FES;
+        uint64_t* const d_eq = d_scratch + 4 * scratch_fes(st);
         size_t hi = 0, lo = 0;
         unsigned lo_bits = 0;
         split.round(0, hi, lo, lo_bits);
@@ -255,12 +274,24 @@ int round_alone(pk_ctx* ctx, const pks_statement& st, const uint64_t* const* d_t
         if (!rc)
             rc = shard ? round_shard_launch(nullptr, st, rt, mine, fold_or_null, d_hi, d_lo, lo_bits, grid, d_scratch, *shard)
                        : round_launch(nullptr, st, rt, mine, fold_or_null, d_hi, d_lo, lo_bits, grid, d_scratch);
-        if (!rc) rc = hip_rc(hipMemcpy(out, d_scratch + 4 * (size_t)4 * PKS_MAX_GRID, 32 * (size_t)(degree(st) + 1), hipMemcpyDeviceToHost));
+        if (!rc) rc = hip_rc(hipMemcpy(out, d_scratch + 4 * results_at(st), 32 * (size_t)(degree(st) + 1), hipMemcpyDeviceToHost));
         pk_free(ctx, base);
         return rc;
     } catch (...) {
         return PK_ERR_OOM;
     }
+}
+
+}  // namespace
+
+int prove(pks_prover* p, const uint64_t* const* d_tables, const uint64_t* tau_or_null, const uint64_t* bind, uint8_t* proof_out, size_t cap, size_t* len,
+          uint64_t* point_out, uint64_t* finals_out) {
+    return prove_any(p, p->st, d_tables, tau_or_null, bind, proof_out, cap, len, point_out, finals_out);
+}
+
+int round_alone(pk_ctx* ctx, const pks_statement& st, const uint64_t* const* d_tables, uint64_t* const* d_out_tables, size_t pairs, size_t mine,
+                const uint64_t* tau_rest_or_null, const uint64_t* fold_or_null, unsigned grid, const ShardSlice* shard, uint64_t* out) {
+    return round_any(ctx, st, g_error, d_tables, d_out_tables, pairs, mine, tau_rest_or_null, fold_or_null, grid, shard, out);
 }
 
 }  // namespace pks
@@ -308,6 +339,62 @@ int pks_round(pk_ctx* ctx, const pks_statement* stmt, const uint64_t* const* d_t
     if (len < min_len || (len & (len - 1)) || len > ((size_t)1 << stmt->n)) return pks::refuse("len must be a power of two, at least 2 (4 with a fold) and at most 2^n");
     const size_t pairs = fold_or_null ? len / 4 : len / 2;
     return pks::round_alone(ctx, *stmt, d_tables, d_out_tables, pairs, pairs, tau_rest_or_null, fold_or_null, grid, nullptr, out);
+}
+
+}  // extern "C"
+
+// ---- the wide statements (include/provekit_sumcheck_wide.h): the same prover object, round loop and round by itself ------------------
+
+struct pksw_prover : pks_prover {
+    pksw_statement wide{};
+};
+
+extern "C" {
+
+int pksw_prover_create(pk_ctx* ctx, const pksw_statement* stmt, pksw_prover** out) {
+    if (out) *out = nullptr;
+    std::string why;
+    if (!ctx || !out) return pks::refuse_wide("null pointer");
+    if (!pks::statement_ok(stmt, why)) return pks::refuse_wide(why);
+    try {
+        std::unique_ptr<pksw_prover> p(new pksw_prover());
+        p->wide = *stmt;
+        if (int rc = pks::equip(p.get(), ctx, stmt, 0, 1, pks::g_wide_error)) return rc;
+        *out = p.release();
+        pks::g_wide_error.clear();
+        return PK_OK;
+    } catch (...) {
+        return pk::out_of_host_memory(pks::g_wide_error);
+    }
+}
+
+int pksw_prover_destroy(pksw_prover* p) {
+    if (!p) return PK_OK;
+    const int rc = p->give_back();
+    delete p;
+    return rc;
+}
+
+const char* pksw_last_error(const pksw_prover* p) { return p ? p->err.c_str() : "null prover"; }
+
+int pksw_prove(pksw_prover* p, const uint64_t* const* d_tables, const uint64_t* tau_or_null, const uint64_t* bind, uint8_t* proof_out, size_t cap,
+               size_t* len, uint64_t* point_out, uint64_t* finals_out) {
+    if (!p) return PK_ERR_BAD_ARG;
+    return pks::prove_any(static_cast<pks_prover*>(p), p->wide, d_tables, tau_or_null, bind, proof_out, cap, len, point_out, finals_out);
+}
+
+int pksw_round(pk_ctx* ctx, const pksw_statement* stmt, const uint64_t* const* d_tables, size_t len, const uint64_t* tau_rest_or_null,
+               const uint64_t* fold_or_null, uint64_t* const* d_out_tables, unsigned grid, uint64_t* out) {
+    std::string why;
+    if (!ctx || !d_tables || !out) return pks::refuse_wide("null pointer");
+    if (!pks::statement_ok(stmt, why)) return pks::refuse_wide(why);
+    // the split eq weights are tables over the bits of the pair index: a weighted round needs a power of two.  Nothing else does
+    const size_t unit = fold_or_null ? 4 : 2;
+    if (len < unit || len % unit || len > ((size_t)1 << stmt->n))
+        return pks::refuse_wide("len must be a multiple of 2 (of 4 with a fold), at least that and at most 2^n");
+    if (tau_rest_or_null && (len & (len - 1))) return pks::refuse_wide("with tau_rest, len must be a power of two");
+    const size_t pairs = len / unit;
+    return pks::round_any(ctx, *stmt, pks::g_wide_error, d_tables, d_out_tables, pairs, pairs, tau_rest_or_null, fold_or_null, grid, nullptr, out);
 }
 
 }  // extern "C"

@@ -11,8 +11,9 @@ namespace pks {
 
 using pk::elements_below_p;
 
-// what pks_prove and pkss_prove refuse of their arguments, with the reason
-inline int check_prove_arguments(const pks_statement& st, const uint64_t* const* d_tables, const uint64_t* tau, const uint64_t* bind, size_t cap, size_t need,
+// what pks_prove, pkss_prove and pksw_prove refuse of their arguments, with the reason
+template <class S>
+int check_prove_arguments(const S& st, const uint64_t* const* d_tables, const uint64_t* tau, const uint64_t* bind, size_t cap, size_t need,
                                  std::string& why) {
     auto no = [&](const std::string& reason) { return why = reason, PK_ERR_BAD_ARG; };
     if (cap < need) return no("the proof buffer holds " + std::to_string(cap) + " bytes, the proof has " + std::to_string(need));

@@ -184,11 +184,15 @@ int launch(hipStream_t stream, const pks_statement& st, const RoundTables& rt, s
     PKS_CASE(1, 1) PKS_CASE(1, 2) PKS_CASE(1, 3) PKS_CASE(1, 4) PKS_CASE(2, 2) PKS_CASE(2, 3) PKS_CASE(2, 4) PKS_CASE(3, 3) PKS_CASE(3, 4)
     return PK_ERR_BAD_ARG;  // D <= m: a term's tables are distinct
 #undef PKS_CASE
-    finish_kernel<<<D + 1, THREADS, 0, stream>>>(partial, grid, partial + (size_t)4 * PKS_MAX_GRID);
-    return hipGetLastError() == hipSuccess ? PK_OK : PK_ERR_HIP;
+    return finish_launch(stream, d_scratch, grid, D + 1, d_scratch + 4 * results_at(st));
 }
 
 }  // namespace
+
+int finish_launch(hipStream_t stream, const uint64_t* d_partial, unsigned n_wg, unsigned sums, uint64_t* d_out) {
+    finish_kernel<<<sums, THREADS, 0, stream>>>((const fe*)d_partial, n_wg, (fe*)d_out);
+    return hipGetLastError() == hipSuccess ? PK_OK : PK_ERR_HIP;
+}
 
 int round_launch(hipStream_t stream, const pks_statement& st, const RoundTables& rt, size_t pairs, const uint64_t* fold_or_null, const uint64_t* d_eq_hi,
                  const uint64_t* d_eq_lo, unsigned lo_bits, unsigned grid, uint64_t* d_scratch) {

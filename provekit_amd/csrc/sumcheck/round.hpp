@@ -4,7 +4,7 @@
 
 #include <vector>
 
-#include "statement.hpp"
+#include "wide_statement.hpp"
 
 namespace pks {
 
@@ -56,9 +56,9 @@ inline void eq_split_build(const EqSplit& s, const fe* t, std::vector<fe>& buf) 
 }
 
 // ---- the kernel ----------------------------------------------------------------------------------------------------------------
-struct RoundTables {
-    const uint64_t* in[PKS_MAX_TABLES];
-    uint64_t* out[PKS_MAX_TABLES];  // fold only
+struct RoundTables {  // of either statement: the first m
+    const uint64_t* in[PKSW_MAX_TABLES];
+    uint64_t* out[PKSW_MAX_TABLES];  // fold only
 };
 // the library's grid for a round of `pairs` pairs: two pairs per lane, at most PKS_MAX_GRID workgroups of 256
 unsigned round_grid(size_t pairs);
@@ -73,6 +73,21 @@ inline size_t lone_arena_fes(unsigned n, unsigned m) { return (size_t)m * ((size
 int round_launch(hipStream_t stream, const pks_statement& st, const RoundTables& tb, size_t pairs, const uint64_t* fold_or_null, const uint64_t* d_eq_hi,
                  const uint64_t* d_eq_lo, unsigned lo_bits, unsigned grid, uint64_t* d_scratch);
 
+// out[k] = the sum of d_partial[k * n_wg ..+ n_wg) for k < sums: the finish of every round launch, round.hip's and wide.hip's
+int finish_launch(hipStream_t stream, const uint64_t* d_partial, unsigned n_wg, unsigned sums, uint64_t* d_out);
+
+// ---- the wide statements (wide.hip) ----------------------------------------------------------------------------------------------
+// a wide round's scratch: up to MAX_ROUND_VALUES partial sums per workgroup, then the results
+constexpr size_t WIDE_SCRATCH_FES = (size_t)MAX_ROUND_VALUES * PKS_MAX_GRID + 8;
+// Where a round's D + 1 sums arrive inside its scratch, in field elements; the scratch's size
+inline size_t results_at(const pks_statement&) { return (size_t)4 * PKS_MAX_GRID; }
+inline size_t results_at(const pksw_statement&) { return (size_t)MAX_ROUND_VALUES * PKS_MAX_GRID; }
+inline size_t scratch_fes(const pks_statement&) { return ROUND_SCRATCH_FES; }
+inline size_t scratch_fes(const pksw_statement&) { return WIDE_SCRATCH_FES; }
+// round_launch for a wide statement: the same arguments, the sums to d_scratch[results_at ..)
+int round_launch(hipStream_t stream, const pksw_statement& st, const RoundTables& tb, size_t pairs, const uint64_t* fold_or_null, const uint64_t* d_eq_hi,
+                 const uint64_t* d_eq_lo, unsigned lo_bits, unsigned grid, uint64_t* d_scratch);
+
 // ---- device sets (shard.hpp) -----------------------------------------------------------------------------------------------------
 // one rank's slice of a round: G = 2^g ranks, this is `rank`; in_global: the input tables are full tables at the round's global
 // length (the caller's, rounds 0 and 1), read at the rank's own indices; otherwise the rank's compacted ones.  Output tables are compacted
@@ -84,6 +99,11 @@ struct ShardSlice {
 // pair index; the rank's D + 1 partial sums to d_scratch[4 * PKS_MAX_GRID ..)
 int round_shard_launch(hipStream_t stream, const pks_statement& st, const RoundTables& tb, size_t pairs, const uint64_t* fold_or_null, const uint64_t* d_eq_hi,
                        const uint64_t* d_eq_lo, unsigned lo_bits, unsigned grid, uint64_t* d_scratch, const ShardSlice& shard);
+// a wide statement has no slices (provekit_sumcheck_wide.h: device sets are out of scope); the round loop never asks for one
+inline int round_shard_launch(hipStream_t, const pksw_statement&, const RoundTables&, size_t, const uint64_t*, const uint64_t*, const uint64_t*, unsigned, unsigned,
+                              uint64_t*, const ShardSlice&) {
+    return PK_ERR_BAD_ARG;
+}
 // the hand-over: d_gathered = G blocks (rank order) of m tables of 2^(c+1) elements -> d_out[j * out_stride + x], the m tables of
 // 2^(c+g+1) in global order
 int handover_launch(hipStream_t stream, const uint64_t* d_gathered, unsigned m, unsigned g, uint64_t* d_out, size_t out_stride);

@@ -47,21 +47,27 @@ inline size_t proof_elems(const pks_statement& s) { return 1 + (size_t)s.n * (de
 // what both sides absorb before it: bind, tau, the coefficients
 inline size_t public_elems(const pks_statement& s) { return (size_t)s.n_bind + (s.has_tau ? s.n : 0) + s.T; }
 
+// the operations behind a label, for every statement of this library (pks and the wide pksw): absorb n_bind caller elements, tau if
+// given, the T coefficients and s; per round absorb D + 1 values and squeeze one challenge; absorb the m final values
+inline void pattern_ops(std::string& d, unsigned n, unsigned m, unsigned T, unsigned has_tau, unsigned n_bind, unsigned D) {
+    auto A = [&](size_t k, const char* label) { pk::pattern_op(d, 'A', k, label); };
+    A(n_bind, "bind");
+    if (has_tau) A(n, "tau");
+    A(T, "coefficients");
+    A(1, "sum");
+    for (unsigned i = 0; i < n; i++) {
+        A(D + 1, "round_values");
+        d.push_back('\0');
+        d += "S1challenge";
+    }
+    A(m, "final_values");
+}
+
 inline std::string io_pattern(const pks_statement& s) {
     std::string d = "provekit-hip/sumcheck/v1/n" + std::to_string(s.n) + "/m" + std::to_string(s.m) + "/T" + std::to_string(s.T) + "/tau" +
                     std::to_string(s.has_tau) + "/masks";
     for (unsigned t = 0; t < s.T; t++) d += (t ? "." : "") + std::to_string(s.masks[t]);
-    auto A = [&](size_t n, const char* label) { pk::pattern_op(d, 'A', n, label); };
-    A(s.n_bind, "bind");
-    if (s.has_tau) A(s.n, "tau");
-    A(s.T, "coefficients");
-    A(1, "sum");
-    for (unsigned i = 0; i < s.n; i++) {
-        A(degree(s) + 1, "round_values");
-        d.push_back('\0');
-        d += "S1challenge";
-    }
-    A(s.m, "final_values");
+    pattern_ops(d, s.n, s.m, s.T, s.has_tau, s.n_bind, degree(s));
     return d;
 }
 
@@ -77,7 +83,10 @@ inline fe terms_at(const pks_statement& s, const fe* v) {
     return g;
 }
 
-// the polynomial of degree <= D through h(0) .. h(D) at x, D = 1 .. 3 (Lagrange over the nodes 0 .. D)
+// the most values a round sends: D + 1 at the wide statements' D = 5 (provekit_sumcheck_wide.h)
+constexpr unsigned MAX_ROUND_VALUES = 6;
+
+// the polynomial of degree <= D through h(0) .. h(D) at x, D = 1 .. 5 (Lagrange over the nodes 0 .. D)
 inline fe round_poly_at(const fe* h, unsigned D, const fe& x) {
     // 1/6 canonical: (5 p + 1) / 6
     static const uint64_t INV6[4] = {0xb891a1fb48000001ULL, 0x4c2b4191bac53323ULL, 0xc442e4c2c1411ef8ULL, 0x285396b510feb022ULL};
@@ -90,10 +99,26 @@ inline fe round_poly_at(const fe* h, unsigned D, const fe& x) {
                  c = pk::h_mul(pk::h_mul(h[2], half), pk::h_mul(x, x1));
         return pk::h_add(pk::h_sub(a, b), c);
     }
-    // -h0 (x-1)(x-2)(x-3)/6 + h1 x (x-2)(x-3)/2 - h2 x (x-1)(x-3)/2 + h3 x (x-1)(x-2)/6
-    const fe a = pk::h_mul(pk::h_mul(h[0], sixth), pk::h_mul(pk::h_mul(x1, x2), x3)), b = pk::h_mul(pk::h_mul(h[1], half), pk::h_mul(pk::h_mul(x, x2), x3)),
-             c = pk::h_mul(pk::h_mul(h[2], half), pk::h_mul(pk::h_mul(x, x1), x3)), e = pk::h_mul(pk::h_mul(h[3], sixth), pk::h_mul(pk::h_mul(x, x1), x2));
-    return pk::h_add(pk::h_sub(b, a), pk::h_sub(e, c));
+    if (D == 3) {
+        // -h0 (x-1)(x-2)(x-3)/6 + h1 x (x-2)(x-3)/2 - h2 x (x-1)(x-3)/2 + h3 x (x-1)(x-2)/6
+        const fe a = pk::h_mul(pk::h_mul(h[0], sixth), pk::h_mul(pk::h_mul(x1, x2), x3)), b = pk::h_mul(pk::h_mul(h[1], half), pk::h_mul(pk::h_mul(x, x2), x3)),
+                 c = pk::h_mul(pk::h_mul(h[2], half), pk::h_mul(pk::h_mul(x, x1), x3)), e = pk::h_mul(pk::h_mul(h[3], sixth), pk::h_mul(pk::h_mul(x, x1), x2));
+        return pk::h_add(pk::h_sub(b, a), pk::h_sub(e, c));
+    }
+    // D = 4, 5: sum_k h_k (-1)^(D-k) / (k! (D-k)!) prod_{j != k} (x - j).  1/5 canonical: (2 p + 1) / 5
+    static const uint64_t INV5[4] = {0xe7f3fbd4c6666667ULL, 0xa9ae5ce9ca4a2d06ULL, 0x49b9b57c33cd568bULL, 0x135b52945a13d9aaULL};
+    fe inv_fact[MAX_ROUND_VALUES] = {one, one, half, sixth, pk::h_mul(sixth, pk::h_mul(half, half)), one};
+    inv_fact[5] = pk::h_mul(inv_fact[4], pk::h_from_canon(pk::h_load(INV5)));
+    fe xs[MAX_ROUND_VALUES] = {x, x1, x2, x3, pk::h_sub(x3, one), one};
+    xs[5] = pk::h_sub(xs[4], one);
+    fe total = pk::fe_zero();
+    for (unsigned k = 0; k <= D; k++) {
+        fe term = pk::h_mul(h[k], pk::h_mul(inv_fact[k], inv_fact[D - k]));
+        for (unsigned j = 0; j <= D; j++)
+            if (j != k) term = pk::h_mul(term, xs[j]);
+        total = (D - k) & 1 ? pk::h_sub(total, term) : pk::h_add(total, term);
+    }
+    return total;
 }
 
 // eq(t, r) = t r + (1 - t)(1 - r)
