@@ -252,6 +252,22 @@ int pk_probe_spark_profile(const struct pkx_prover *p, double *matrix_ms2, doubl
 unsigned pk_probe_spark_gather_items(void);
 unsigned pk_probe_spark_matrix_items(void);
 
+/* libprovekit_rangecheck.so's decomposition pass by itself (csrc/rangecheck/kernels.hpp) over tables the caller holds, with the grid its
+ * C ABI does not carry (1 .. 1024 workgroups; 0: the library's rule, pk_probe_range_decompose_items entries per lane): d_limbs L device
+ * pointers on the host, d_counts 2^k u32, d_bad one u64 cell (all ones afterwards: every entry was below 2^bits), d_m 2^k elements.
+ * *ms: its device time, the counts' Montgomery pass included.  Blocking.
+ * A pkr_prover's test and benchmark knobs (csrc/rangecheck/prover.hpp), host only: pk_probe_range_set_grid sets the grid of every
+ * kernel of its calls from the next call on -- no bit of a result depends on it (tests/test_gpu_rangecheck.py); pk_probe_range_profile:
+ * in milliseconds, the last pkr_decompose's launches and the last proof's scale pass in device time, its pkt_prove in host time.
+ * pk_probe_range_grids: the workgroups the library's rule gives the decompose, scale (0: none), index and m kernels of a statement. */
+struct pkr_prover;
+int pk_probe_range_decompose(pk_ctx *ctx, unsigned n, unsigned bits, unsigned k, const uint64_t *d_f, uint64_t *const *d_limbs, uint32_t *d_counts,
+                             unsigned long long *d_bad, uint64_t *d_m, unsigned grid, float *ms);
+int pk_probe_range_set_grid(struct pkr_prover *p, unsigned grid);
+int pk_probe_range_profile(const struct pkr_prover *p, double *decompose_ms, double *scale_ms, double *lookup_ms);
+int pk_probe_range_grids(unsigned n, unsigned bits, unsigned k, unsigned *grids4);
+unsigned pk_probe_range_decompose_items(void);
+
 /* csrc/witness.hip's thresholds (csrc/witness_shape.hpp) and the shape of a levelled builder list (witness.hip here), for
  * tests/test_witness_edge_cases_host.py and tests/test_gpu_witness_edges.py.  Host only.  pk_probe_witness_phases: *n_phases = the
  * phases of postcard(Vec<WitnessBuilder>) after levelling (two per level); with cap >= *n_phases, widths[ph] = the items of phase
