@@ -377,9 +377,10 @@ int pk_commit(pk_ctx *ctx, const uint64_t *const *d_coeffs, unsigned batch, unsi
  * pk_commit_layout it reports (layout_out, or pk_tree_layout for a pk_tree):
  *   n_shards / shard   rows i = shard (mod n_shards) are present, local row t = i / n_shards (1 / 0 outside a device set)
  *   encoding           PK_LEAVES_MONTGOMERY: elements are Montgomery images (what pk_rs_encode / pk_leaf_hash take and give);
- *                      PK_LEAVES_SCALED32: elements are the plain integers 32*v mod p, lazily reduced (< 1.6 p) -- the form the
- *                      Skyscraper kernels compute in (csrc/skyscraper29s.hpp), emitted by the commit's NTT from 2^11 local rows
- *                      up, so the leaf hash converts nothing.
+ *                      PK_LEAVES_SCALED32: elements are the plain integers 32*v mod p, lazily reduced (< 1.6 p: SCALED32_BOUND of
+ *                      csrc/skyscraper29s.hpp, where the range is stated; pk_commit_open and pk_gather_leaves_enc take any such
+ *                      buffer, a commit itself stays below p (1 + 2^-10)) -- the form the Skyscraper kernels compute in, emitted
+ *                      by the commit's NTT from 2^11 local rows up, so the leaf hash converts nothing.
  * Which encoding a commit uses is a function of (device set, rows) only.  Raw buffers in PK_LEAVES_SCALED32 must NOT be handed
  * to pk_tree_from_leaves / pk_leaf_hash / pk_gather_leaves (they assume Montgomery): open them with pk_commit_open, or gather
  * rows with pk_gather_leaves_enc; both convert the opened rows back to canonical / Montgomery. */

@@ -28,8 +28,9 @@ __global__ __launch_bounds__(256) void compress_many_kernel(const fe* __restrict
 }
 
 // SkyscraperCRH::evaluate (provekit/common/src/skyscraper/whir.rs:30-48): h = x0; h = C(h, x_j)
-// SCALED_IN: the leaves are in the hash-ready encoding the commit's own NTT emits (32 * value as a plain integer < p,
-// ntt.hip ntt_scaled_available): they enter the fold as they are.  Otherwise they are Montgomery images (the C ABI form).
+// SCALED_IN: the leaves are in the hash-ready encoding the commit's own NTT emits (32 * value as a plain integer, lazily reduced:
+// any element below skyscraper29s.hpp SCALED32_BOUND; ntt.hip ntt_scaled_available): they enter the fold as they are.  Otherwise
+// they are Montgomery images (the C ABI form).
 template <int VERSION, int LAYOUT, bool SCALED_IN>
 __global__ __launch_bounds__(256) void leaf_hash_kernel(const fe* __restrict__ leaves, size_t n_leaves, unsigned width,
                                                         fe* __restrict__ digests) {

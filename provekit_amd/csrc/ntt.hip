@@ -127,8 +127,10 @@ struct PassParams {
     unsigned ncols;
     int xcd_tiles;
     int lazy_store;     // outputs may be stored almost reduced instead of canonical: intermediate passes, and the hash-ready final
-                        // pass (its consumers reduce anyway).  pack29 of a value the pass leaves normalised and < 1.2p (ntt_regs.hpp):
-                        // the next pass loads it as it is, below the 1.2p its butterfly network takes.
+                        // pass (its consumers reduce anyway).  An intermediate pass stores pack29 of a value it leaves normalised and
+                        // < 1.2p (ntt_regs.hpp): the next pass loads it as it is, below the 1.2p its butterfly network takes.  The
+                        // hash-ready final pass has no twiddle: it stores pack29 of red29 / red29w's result, the producer bound of
+                        // skyscraper29s.hpp ("the hash-ready codeword"), far below the SCALED32_BOUND its consumers take.
     size_t n_mask;      // N - 1
     size_t tw_mul;      // twiddle exponent = tw_mul * k * v  (0 = no twiddle)
     size_t wr_step;     // w_R^j = W[j * wr_step]
@@ -681,8 +683,8 @@ NttPlan ntt_plan(unsigned log_n, size_t nonzero) {
     return q;
 }
 
-// Can a transform of this size deliver the hash-ready output (every output = 32 * value as a plain integer < p instead of
-// the Montgomery image)?  It rides on the LAST inter-pass twiddle multiplication (pass P-1's), so the size needs two or more passes
+// Can a transform of this size deliver the hash-ready output (every output = 32 * value as a plain integer, lazily reduced within
+// the producer bound of skyscraper29s.hpp, instead of the Montgomery image)?  It rides on the LAST inter-pass twiddle multiplication (pass P-1's), so the size needs two or more passes
 // and that pass must be the register-radix kernel.  A pure function of the size: commit and openings agree on the encoding.
 bool ntt_scaled_available(unsigned log_n) {
     if (log_n <= 9 || log_n > 27) return false;

@@ -76,14 +76,16 @@ int pk_selftest_permute(uint64_t l[4], uint64_t r[4]) {
 // the Shoup product, the NTT's constants)
 // the carry chains of fe.hpp: 27 fe_add(a,b)  28 fe_sub(a,b)  29 fe_neg(a)  30 fe_dbl(a)  31 {a < b, a == b, b < a} in words 0..2
 // 32/33/34 cond_sub_kp<1/2/4>(a)  35 fe_reduce_any(a)  36 fe_fold(a, b, one) == b  37 fe_fold(a, b, a)  38 pack_canon29(unpack29(a))
+// the consumers of a stored hash-ready codeword element (a, b < SCALED32_BOUND, skyscraper29s.hpp): 39 / 40 compress v2 / v1 as the leaf
+// fold enters it  41 a fold of three  42 / 43 the canonical / Montgomery opening (opened_element)
 // a, b, out: n field elements (4 x u64 each); b may be NULL for the one-operand ops.  Host only; no device needed.
 int pk_selftest_arith(int op, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n) {
     const bool two = op == 0 || op == 1 || op == 2 || op == 4 || op == 15 || op == 16 || op == 19 || op == 20 || op == 24 || op == 25 ||
-                     op == 27 || op == 28 || op == 31 || op == 36 || op == 37;
+                     op == 27 || op == 28 || op == 31 || op == 36 || op == 37 || op == 39 || op == 40 || op == 41;
     if (!a || !out || (!b && two)) return PK_ERR_BAD_ARG;
     for (size_t i = 0; i < n; i++) {
         fe x = load_host(a + 4 * i), y = b ? load_host(b + 4 * i) : x;
-        if (op < 0 || op > 38) return PK_ERR_BAD_ARG;
+        if (op < 0 || op > 43) return PK_ERR_BAD_ARG;
         fe r = selftest_op(op, x, y);
         store_host(out + 4 * i, r);
     }

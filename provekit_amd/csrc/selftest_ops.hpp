@@ -121,6 +121,21 @@ PK_HD fe selftest_op(int op, const fe& x, const fe& y) {
         case 36: r = fe_fold(x, y, fe_one()); break;  // x, y < p: x + 1 (y - x) = y bit for bit (the add reduces exactly when y < x)
         case 37: r = fe_fold(x, y, x); break;         // x, y < p: x + x (y - x) 2^-256
         case 38: r = pack_canon29(unpack29<0>(x)); break;  // x < 2p: the borrow chain behind every product's last step
+        // the consumers of a STORED hash-ready codeword element (skyscraper29s.hpp "the hash-ready codeword": x, y = 32 * value as plain
+        // integers, any x, y < SCALED32_BOUND), written as the leaf kernel and the openings write them -- unpack29<0> of the stored
+        // words, no to_scaled29 in front (tests/scaled_codeword_cases.py holds the operands)
+        case 39: r = from_scaled_canon(compress29s<2>(unpack29<0>(x), unpack29<0>(y))); break;  // C(x / 32, y / 32), canonical
+        case 40: r = from_scaled_canon(compress29s<1>(unpack29<0>(x), unpack29<0>(y))); break;
+        case 41: {  // the leaf fold of a width-4 leaf (x, y, x, y), as op 19 without the conversion
+            fe29 a = unpack29<0>(x), b = unpack29<0>(y);
+            fe29 h = compress29s<2>(a, b);
+            h = compress29s<2>(h, a);
+            h = compress29s<2>(h, b);
+            r = from_scaled_canon(h);
+            break;
+        }
+        case 42: r = opened_element(x, true, 1); break;  // the canonical opening x / 32 mod p (also the digest of a width-1 leaf)
+        case 43: r = opened_element(x, true, 0); break;  // the Montgomery opening x / 32 * 2^256 mod p
         default: break;
     }
     return r;

@@ -13,7 +13,9 @@
 // The bar rounds need the true value's bytes: bar_s divides by 32 exactly (one 5-bit Montgomery step: add m*p with
 // m = -L/p mod 32, shift), applies the byte S-box, and multiplies by 32 again while reducing (subtracting q*p as adding
 // q*(2^261 - p) in unsigned 64-bit columns, the 2^261 multiple falling off the top limb).
-// Values: "scaled" = 32*x mod p, limbs 0..7 < 2^29, limb 8 holds the rest; between compressions < 1.05p, inside < 31p.
+// Values: "scaled" = 32*x mod p, limbs 0..7 < 2^29, limb 8 holds the rest; into a compression < SCALED32_BOUND (below), out of
+// it < 1.04p, inside < 31p (with both inputs at 1.6p the rounds' own bounds, l' < r + l^2 / 169p + 2p for a square round and
+// l' < r + 2.1p for a bar round, end at 30.9p after v2's 18 rounds and stay below 16p at every bar).
 #pragma once
 #include "skyscraper29.hpp"
 
@@ -143,6 +145,30 @@ PK_HD fe from_scaled_canon(const fe29& L) {
     return r;
 }
 
+// ---- the hash-ready codeword (PK_LEAVES_SCALED32) ------------------------------------------------------------------------
+// A commitment of 2^11 or more local rows keeps its codeword in HBM in this domain's form: an element of value v is stored as the
+// plain integer x = 32*v mod p in 8 x u32, LAZILY reduced -- x may be p or more.  How much more is stated here and nowhere else:
+//   consumers  take every x < SCALED32_BOUND = 8p/5 (1.6p): the leaf fold (hash.hip leaf_hash_kernel<*, *, SCALED_IN>: unpack29<0>(x)
+//              is the fold's seed and every later right input of compress29s; the digest of a width-1 leaf is from_scaled_canon of it)
+//              and the openings (opened_element below).  This is the public promise (include/provekit_hip.h, pk_commit_layout):
+//              pk_commit_open and pk_gather_leaves_enc accept caller buffers up to it.
+//   producer   the commit's NTT (ntt.hip, the hash-ready last pass) stores pack29 of a value that left reduce_almost29 (red29 /
+//              red29w, ntt_regs.hpp), or a canonical value: x <= p + (p >> SCALED32_PRODUCER_SHIFT), i.e. below p (1 + 2^-10).
+// tests/scaled_codeword_cases.py holds the values, tests/test_scaled_codeword_host.py and tests/test_gpu_scaled_codeword.py drive
+// every consumer over [0, SCALED32_BOUND) on the host and the device builds and hold the producer to its bound.
+constexpr unsigned SCALED32_BOUND_NUM = 8, SCALED32_BOUND_DEN = 5;  // SCALED32_BOUND = floor(8p / 5)
+constexpr unsigned SCALED32_PRODUCER_SHIFT = 10;
+
+// an element of the stored codeword -> what an opening returns: canonical (the ark-serialize form) or Montgomery
+PK_HD fe opened_element(const fe& x, bool scaled, int canonical) {
+    if (!scaled) return canonical ? fe_from_montx(x) : x;
+    if (canonical) return from_scaled_canon(unpack29<0>(x));  // 32v -> v
+    fe k;  // 2^507 mod p: mont(32v, 2^507) = 32v * 2^507 * 2^-256 = v * 2^256
+    k.v[0] = 0xc0f10b6eu; k.v[1] = 0x95e64f0du; k.v[2] = 0x2e33c2c0u; k.v[3] = 0xf2087f4eu;
+    k.v[4] = 0x7fcae90cu; k.v[5] = 0xc4610290u; k.v[6] = 0x4be93745u; k.v[7] = 0x25df13cfu;
+    return fe_mulx(x, k);
+}
+
 // ---- rounds ------------------------------------------------------------------------------------------------------------
 // (l, r) <- (r + l^2 * 2^-261 + 32 rc, l)
 template <int RCI>
@@ -201,7 +227,8 @@ PK_HD void sky_bar_round_s(fe29& l, fe29& r) {
     l = s;
 }
 
-// l, r: scaled, normalised, < 1.05p.  Returns the scaled digest, normalised, < 1.04p.
+// l, r: scaled, normalised, < SCALED32_BOUND (the leaf fold hands it unpack29<0> of stored codeword elements unchanged).  Returns
+// the scaled digest, normalised, < 1.04p.
 template <int VERSION>
 PK_HD fe29 compress29s(const fe29& l_in, const fe29& r_in) {
     fe29 l = l_in, r = r_in;
@@ -236,7 +263,7 @@ PK_HD fe29 compress29s(const fe29& l_in, const fe29& r_in) {
         sky_sq_round_s<8>(l, r);
         sky_sq_round_s<0>(l, r);
     }
-    fe29 s = add29(l, l_in);  // < 32p, limbs < 2^30
+    fe29 s = add29(l, l_in);  // < 31p + SCALED32_BOUND, limbs < 2^30
     return sub_qp_wide29(s, quot_estimate29(s.v[8]));
 }
 

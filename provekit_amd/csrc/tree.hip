@@ -28,25 +28,16 @@ struct pk_tree {
     int layout = PK_COL_MAJOR;
     // sharded commit: this rank holds the codeword rows i = shard (mod n_shards), local row t = i / n_shards
     unsigned shard = 0, n_shards = 1;
-    // the codeword is held in the hash-ready encoding the commit's NTT emits (32 * value, plain integer < p) instead of
-    // Montgomery images: the leaf hash consumes it without conversion, openings convert the ~100 opened rows
+    // the codeword is held in the hash-ready encoding the commit's NTT emits (32 * value as a plain integer, lazily reduced:
+    // below skyscraper29s.hpp SCALED32_BOUND) instead of Montgomery images: the leaf hash consumes it without conversion,
+    // openings convert the ~100 opened rows
     bool scaled = false;
 };
 
 namespace {
 
-// an element of the stored codeword -> what an opening returns: canonical (the ark-serialize form) or Montgomery
-__device__ __forceinline__ fe opened_element(const fe& x, bool scaled, int canonical) {
-    if (!scaled) return canonical ? fe_from_montx(x) : x;
-    if (canonical) return from_scaled_canon(unpack29<0>(x));  // 32v -> v
-    fe k;  // 2^507 mod p: mont(32v, 2^507) = 32v * 2^507 * 2^-256 = v * 2^256
-    k.v[0] = 0xc0f10b6eu; k.v[1] = 0x95e64f0du; k.v[2] = 0x2e33c2c0u; k.v[3] = 0xf2087f4eu;
-    k.v[4] = 0x7fcae90cu; k.v[5] = 0xc4610290u; k.v[6] = 0x4be93745u; k.v[7] = 0x25df13cfu;
-    return fe_mulx(x, k);
-}
-
-// One launch serves an opening: the first k*width lanes gather the opened leaves to leaf-major order (optionally
-// converted to canonical, the ark-serialize form), the next k*(plen+1) lanes the sibling digests -- out_sib[q] =
+// One launch serves an opening: the first k*width lanes gather the opened leaves to leaf-major order (each through
+// skyscraper29s.hpp opened_element: Montgomery, or canonical, the ark-serialize form), the next k*(plen+1) lanes the sibling digests -- out_sib[q] =
 // nodes[(n+i)^1]; out_path[q][d-1] = sibling of the depth-d ancestor, d = 1..logn-1 (root -> leaf).  idx and the three
 // outputs live in the context's pinned mailbox: the kernel reads the indices from and writes the openings to host memory
 // directly, so an opening costs no copy operations.

@@ -9,8 +9,9 @@ pytestmark = pytest.mark.gpu
 
 # 15-20: the scaled Skyscraper path and dot29; 21-23: the safegcd inverse (feinv.hpp), both step forms; 24-26: the Shoup product, its
 # lazy-limb form and the NTT's in-register constants; 27-38: the carry chains of fe.hpp, fe_fold and pack_canon29 (every one accepts
-# operands below p; their edge operands are in tests/test_gpu_fe_carry.py)
-@pytest.mark.parametrize("op", list(range(39)))
+# operands below p; their edge operands are in tests/test_gpu_fe_carry.py); 39-43: the consumers of a stored hash-ready codeword element
+# (operands below 1.6p: values below p here, the whole range and its edges in tests/test_gpu_scaled_codeword.py)
+@pytest.mark.parametrize("op", list(range(44)))
 def test_device_equals_host(ctx, oracle, op):
     from provekit_amd._lib import lib
     from tools.pk_probes import lib as probes

@@ -28,6 +28,9 @@ SIGNATURES = {
     "pk_probe_mfma_reduce": (C.c_int, [vp, vp, vp, sz]),
     "pk_probe_mfma_reduce_rate": (C.c_int, [vp, C.c_uint, C.c_uint, C.POINTER(C.c_double)]),
     "pk_probe_mfma_valu_rate": (C.c_int, [vp, C.c_uint, C.c_uint, C.c_uint, C.POINTER(C.c_double)]),
+    # the leaf hash of a caller-built hash-ready codeword and the encoding's stated range, for tests/test_gpu_scaled_codeword.py
+    "pk_probe_leaf_hash_scaled": (C.c_int, [vp, vp, sz, sz, vp]),
+    "pk_probe_scaled32_bounds": (C.c_int, [vp, vp]),
     # csrc/mle.hip's entry points without a C ABI (csrc/internal.hpp), for tests/test_gpu_mle_edges.py
     "pk_probe_num_cus": (C.c_int, [vp, C.POINTER(C.c_int)]),
     "pk_probe_reduction_blocks": (C.c_int, [vp, sz, C.POINTER(C.c_uint)]),

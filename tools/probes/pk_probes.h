@@ -53,6 +53,14 @@ int pk_probe_mfma_reduce(pk_ctx *ctx, const uint32_t *d_t_limbs, int32_t *d_out,
 int pk_probe_mfma_reduce_rate(pk_ctx *ctx, unsigned waves_per_simd, unsigned iters, double *squarings_per_s);
 int pk_probe_mfma_valu_rate(pk_ctx *ctx, unsigned waves_per_simd, unsigned ilp, unsigned iters, double *squarings_per_s);
 
+/* The leaf hash of a column-major codeword the CALLER built in the hash-ready encoding PK_LEAVES_SCALED32 (csrc/internal.hpp
+ * leaf_hash_x with scaled_in: the kernel the product reaches only behind its own NTT), for tests/test_gpu_scaled_codeword.py:
+ * d_leaves = width x n_leaves elements, each below the encoding's consumer bound; d_digests = n_leaves canonical digests.
+ * pk_probe_scaled32_bounds (host only): that bound and the largest element a commit stores, as csrc/skyscraper29s.hpp states
+ * them (SCALED32_BOUND_NUM / _DEN, SCALED32_PRODUCER_SHIFT), 4 x u64 each. */
+int pk_probe_leaf_hash_scaled(pk_ctx *ctx, const uint64_t *d_leaves, size_t n_leaves, size_t width, uint64_t *d_digests);
+int pk_probe_scaled32_bounds(uint64_t consumer_bound[4], uint64_t producer_max[4]);
+
 /* The entry points of csrc/mle.hip that have no C ABI of their own (csrc/internal.hpp: dot_rows, eval_univariate_multi, lincomb2,
  * fold_pairs2 and the launch-only sumcheck rounds), for tests/test_gpu_mle_edges.py: the functions' own argument order, device
  * pointers the caller owns.  dot_rows in its non-deferred form, fold_pairs2 and the sumcheck launches without a gate (gate_seq = 0)

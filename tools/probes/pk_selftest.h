@@ -15,6 +15,8 @@ extern "C" {
  * 4/5: the lazy 29-bit product / square followed by exact reduction.  n elements of 4 x u64 each.
  * 27..38: the carry chains of fe.hpp -- 27 fe_add  28 fe_sub  29 fe_neg  30 fe_dbl  31 {a < b, a == b, b < a} in words 0..2
  * 32/33/34 cond_sub_kp<1/2/4>  35 fe_reduce_any  36 fe_fold(a, b, one)  37 fe_fold(a, b, a)  38 pack_canon29(unpack29(a))
+ * 39..43: the consumers of a stored hash-ready codeword element (a, b = 32 * value as plain integers below 8p/5) -- 39/40 Skyscraper
+ * v2/v1 compress as the leaf fold enters it  41 a fold of three  42/43 the canonical / Montgomery opening
  * (the whole table: csrc/selftest_ops.hpp) */
 /* host-only pieces of the transcript: domain-separator tag, one sponge permutation on canonical (l, r) */
 int pk_selftest_keccak_tag(const uint8_t *data, size_t len, uint8_t tag[32]);

@@ -892,6 +892,47 @@ extern "C" int pk_probe_launch_chain(pk_ctx* ctx, unsigned launches, unsigned th
 // own argument order, device pointers the caller owns.  Launches that could wait on a gate are wrapped with gate_seq = 0 only: a gated
 // kernel whose challenge nobody publishes spins to its give-up bound, and that belongs to the whole-proof latency tests.
 extern "C" {
+// the leaf hash of a column-major codeword the caller built in the hash-ready encoding (hash.hip leaf_hash_kernel<*, PK_COL_MAJOR, true>,
+// which the product reaches only behind its own NTT), for tests/test_gpu_scaled_codeword.py
+int pk_probe_leaf_hash_scaled(pk_ctx* ctx, const uint64_t* d_leaves, size_t n_leaves, size_t width, uint64_t* d_digests) {
+    PK_ENTER(ctx);
+    PK_REQUIRE(ctx, width >= 1 && width < (1u << 20), "leaf width out of range");
+    PK_REQUIRE(ctx, n_leaves == 0 || (d_leaves && d_digests), "null pointer");
+    return leaf_hash_x(ctx, d_leaves, n_leaves, width, d_digests, true);
+}
+// skyscraper29s.hpp's one statement of the encoding's range as integers (8 x u32 little-endian each, host only): every consumer takes
+// x < consumer_bound = floor(SCALED32_BOUND_NUM p / SCALED32_BOUND_DEN); the commit stores x <= producer_max = p + (p >> SCALED32_PRODUCER_SHIFT)
+int pk_probe_scaled32_bounds(uint64_t consumer_bound[4], uint64_t producer_max[4]) {
+    if (!consumer_bound || !producer_max) return PK_ERR_BAD_ARG;
+    u32 c[8], m[8];
+    u64 carry = 0;
+    u32 wide[9];
+    for (int i = 0; i < 8; i++) {  // p * NUM
+        carry += (u64)kPlimb(i) * SCALED32_BOUND_NUM;
+        wide[i] = (u32)carry;
+        carry >>= 32;
+    }
+    wide[8] = (u32)carry;
+    u64 rem = 0;
+    for (int i = 8; i >= 0; i--) {  // / DEN
+        const u64 cur = (rem << 32) | wide[i];
+        const u64 q = cur / SCALED32_BOUND_DEN;
+        rem = cur % SCALED32_BOUND_DEN;
+        if (i == 8 && q) return PK_ERR_BAD_ARG;  // the bound must fit 256 bits
+        if (i < 8) c[i] = (u32)q;
+    }
+    carry = 0;
+    for (int i = 0; i < 8; i++) {  // p + (p >> SHIFT), SHIFT < 32
+        const u64 hi = i + 1 < 8 ? kPlimb(i + 1) : 0;
+        const u32 sh = (u32)((((u64)hi << 32) | kPlimb(i)) >> SCALED32_PRODUCER_SHIFT);
+        carry += (u64)kPlimb(i) + sh;
+        m[i] = (u32)carry;
+        carry >>= 32;
+    }
+    memcpy(consumer_bound, c, 32);
+    memcpy(producer_max, m, 32);
+    return PK_OK;
+}
 int pk_probe_num_cus(pk_ctx* ctx, int* num_cus) {
     if (!ctx || !num_cus) return PK_ERR_BAD_ARG;
     *num_cus = ctx->num_cus;
