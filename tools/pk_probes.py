@@ -117,6 +117,13 @@ SIGNATURES = {
     "pk_probe_range_profile": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "pk_probe_range_grids": (C.c_int, [C.c_uint, C.c_uint, C.c_uint, C.POINTER(C.c_uint)]),
     "pk_probe_range_decompose_items": (C.c_uint, []),
+    # libprovekit_bitwise.so's decomposition pass with its grid; a pkb_prover's grid knob, the phases of its last calls and the grid
+    # of each kernel (tools/probes/bitwise.hip)
+    "pk_probe_bitwise_decompose": (C.c_int, [vp, C.c_uint, C.c_uint, C.c_uint, C.c_uint, vp, vp, vp, C.c_int, vp, vp, vp, vp, C.c_uint, C.POINTER(C.c_float)]),
+    "pk_probe_bitwise_set_grid": (C.c_int, [vp, C.c_uint]),
+    "pk_probe_bitwise_profile": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "pk_probe_bitwise_grids": (C.c_int, [C.c_uint, C.c_uint, C.c_uint, C.c_uint, C.POINTER(C.c_uint)]),
+    "pk_probe_bitwise_decompose_items": (C.c_uint, []),
     # csrc/witness.hip's thresholds and the shape of a levelled builder list (tools/probes/witness.hip): host only
     "pk_probe_witness_narrow": (C.c_uint, []),
     "pk_probe_witness_sum_heavy": (C.c_uint, []),

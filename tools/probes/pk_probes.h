@@ -276,6 +276,23 @@ int pk_probe_range_profile(const struct pkr_prover *p, double *decompose_ms, dou
 int pk_probe_range_grids(unsigned n, unsigned bits, unsigned k, unsigned *grids4);
 unsigned pk_probe_range_decompose_items(void);
 
+/* libprovekit_bitwise.so's decomposition pass by itself (csrc/bitwise/kernels.hpp) over tables the caller holds, with the grid its C
+ * ABI does not carry (1 .. 1024 workgroups; 0: the library's rule, pk_probe_bitwise_decompose_items entries per lane): d_c written
+ * (c_given = 0) or read and compared, d_digits 3 L device pointers on the host ([j L + i]), d_counts 2^(2d) u32, d_bad one u64 cell
+ * (all ones afterwards: no entry failed; else (x << 2) | case of the smallest failing x), d_m 2^(2d) elements.  *ms: its device time,
+ * the counts' Montgomery pass included.  Blocking.
+ * A pkb_prover's test and benchmark knobs (csrc/bitwise/prover.hpp), host only: pk_probe_bitwise_set_grid sets the grid of every
+ * kernel of its calls from the next call on -- no bit of a result depends on it (tests/test_gpu_bitwise.py); pk_probe_bitwise_profile:
+ * in milliseconds, the last pkb_decompose's launches in device time, the last proof's pkt_prove in host time.
+ * pk_probe_bitwise_grids: the workgroups the library's rule gives the decompose, table and m kernels of a statement. */
+struct pkb_prover;
+int pk_probe_bitwise_decompose(pk_ctx *ctx, unsigned n, unsigned op, unsigned d, unsigned L, const uint64_t *d_a, const uint64_t *d_b, uint64_t *d_c, int c_given,
+                               uint64_t *const *d_digits, uint32_t *d_counts, unsigned long long *d_bad, uint64_t *d_m, unsigned grid, float *ms);
+int pk_probe_bitwise_set_grid(struct pkb_prover *p, unsigned grid);
+int pk_probe_bitwise_profile(const struct pkb_prover *p, double *decompose_ms, double *lookup_ms);
+int pk_probe_bitwise_grids(unsigned n, unsigned op, unsigned d, unsigned L, unsigned *grids3);
+unsigned pk_probe_bitwise_decompose_items(void);
+
 /* csrc/witness.hip's thresholds (csrc/witness_shape.hpp) and the shape of a levelled builder list (witness.hip here), for
  * tests/test_witness_edge_cases_host.py and tests/test_gpu_witness_edges.py.  Host only.  pk_probe_witness_phases: *n_phases = the
  * phases of postcard(Vec<WitnessBuilder>) after levelling (two per level); with cap >= *n_phases, widths[ph] = the items of phase
