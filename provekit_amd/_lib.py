@@ -181,6 +181,7 @@ SELFTEST_SIGNATURES = {
     "pk_selftest_keccak_tag": (C.c_int, [vp, sz, vp]),
     "pk_selftest_permute": (C.c_int, [vp, vp]),
     "pk_selftest_arith": (C.c_int, [C.c_int, vp, vp, vp, sz]),
+    "pk_selftest_inv30": (C.c_int, [C.c_int, vp, vp, sz]),
     "pk_selftest_chacha": (C.c_int, [vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, vp]),
     "pk_selftest_random_fe": (C.c_int, [vp, vp, C.c_uint32, vp, sz]),
     "pk_selftest_dft": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, sz]),

@@ -92,6 +92,15 @@ int pk_selftest_arith(int op, const uint64_t* a, const uint64_t* b, uint64_t* ou
     return PK_OK;
 }
 
+// the parts of the safegcd inverse (feinv.hpp: divsteps30, divsteps30_var, update_de, update_fg, normalize, to_s30, from_s30 = part 0..6) on
+// n records of 32 words in, 32 words out; the packing of a record is stated at selftest_inv30 (selftest_inv30.hpp).  Host only.
+int pk_selftest_inv30(int part, const int32_t* in, int32_t* out, size_t n) {
+    if (!in || !out || part < 0 || part > 6) return PK_ERR_BAD_ARG;
+    for (size_t i = 0; i < n; i++)
+        if (!selftest_inv30(part, in + 32 * i, out + 32 * i)) return PK_ERR_BAD_ARG;
+    return PK_OK;
+}
+
 int pk_selftest_pre_load(const uint64_t* x, const uint64_t* tw, uint64_t* out, int terms, int live, size_t n) {
     if (!x || !tw || !out || terms < 1 || terms > 4 || live < 0 || live > terms) return PK_ERR_BAD_ARG;
     return selftest_pre_load(x, tw, out, terms, live, n);

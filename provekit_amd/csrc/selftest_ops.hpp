@@ -8,6 +8,7 @@
 #include "feinv.hpp"
 #include "skyscraper29s.hpp"
 #include "ntt_regs.hpp"
+#include "selftest_inv30.hpp"  // the parts of feinv.hpp one at a time: a table of its own, a record of 32 words per call
 
 namespace pk {
 

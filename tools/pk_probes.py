@@ -16,6 +16,7 @@ lib = C.CDLL(LIB_PATH)
 
 SIGNATURES = {
     "pk_probe_arith_device": (C.c_int, [vp, C.c_int, vp, vp, vp, sz]),
+    "pk_probe_inv30_device": (C.c_int, [vp, C.c_int, vp, vp, sz]),
     "pk_probe_modmul_rate": (C.c_int, [vp, C.c_uint, C.c_uint, C.c_uint, C.POINTER(C.c_double)]),
     "pk_probe_sq_round_rate": (C.c_int, [vp, C.c_int, C.c_uint, C.c_uint, C.c_uint, C.POINTER(C.c_double)]),
     "pk_probe_fp52_sqr": (C.c_int, [vp, vp, sz]),

@@ -10,6 +10,9 @@ extern "C" {
 
 /* the same ops run by a kernel on device buffers (device-vs-host codegen diff in the GPU suite) */
 int pk_probe_arith_device(pk_ctx *ctx, int op, const uint64_t *d_a, const uint64_t *d_b, uint64_t *d_out, size_t n);
+/* the parts of the safegcd inverse (pk_selftest_inv30, pk_selftest.h: parts 0..6) run by a kernel, one lane per record: d_in and d_out
+ * hold n records of 32 words each */
+int pk_probe_inv30_device(pk_ctx *ctx, int part, const int32_t *d_in, int32_t *d_out, size_t n);
 /* measurement aid (SURVEY 8d "measured_peak_modmul_per_s"): rate of register-resident 9x29-bit Montgomery squarings,
  * ilp (1|2|4) independent chains per lane, waves_per_simd (1..8) resident waves, iters squarings per chain */
 int pk_probe_modmul_rate(pk_ctx *ctx, unsigned waves_per_simd, unsigned ilp, unsigned iters, double *modmul_per_s);

@@ -22,6 +22,11 @@ extern "C" {
 int pk_selftest_keccak_tag(const uint8_t *data, size_t len, uint8_t tag[32]);
 int pk_selftest_permute(uint64_t l[4], uint64_t r[4]);
 int pk_selftest_arith(int op, const uint64_t *a, const uint64_t *b, uint64_t *out, size_t n);
+/* the parts of the safegcd inverse (csrc/feinv.hpp) one at a time, where whole inversions of chosen operands cannot steer the state:
+ * part 0 divsteps30  1 divsteps30_var  2 update_de  3 update_fg  4 normalize  5 to_s30  6 from_s30, on n records of 32 words in and
+ * 32 words out (the packing: csrc/selftest_inv30.hpp; operands and expected values: tests/feinv_refs.py).  Any other part
+ * is refused. */
+int pk_selftest_inv30(int part, const int32_t *in, int32_t *out, size_t n);
 /* the proof RNG: one ChaCha block (host; RFC 8439 state layout, words 12-13 = counter, 14-15 = nonce; `rounds` = 20 for the
  * RFC's vectors, 12 is what the library runs -- rand's ThreadRng cipher) and the device draw of n uniform field elements
  * for (seed32, stream): elements 2j, 2j+1 take the first / second 254-bit candidate of blocks (counter j, nonce {stream,

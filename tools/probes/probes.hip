@@ -17,6 +17,16 @@ __global__ void selftest_kernel(int op, const fe* a, const fe* b, fe* out, size_
     fe_store(out + i, selftest_op(op, x, y));
 }
 
+// the parts of feinv.hpp, one lane per record of 32 words (selftest_inv30.hpp)
+__global__ void selftest_inv30_kernel(int part, const int32_t* in, int32_t* out, size_t n) {
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    int32_t x[32], y[32];
+    for (int k = 0; k < 32; k++) x[k] = in[32 * i + k];
+    selftest_inv30(part, x, y);
+    for (int k = 0; k < 32; k++) out[32 * i + k] = y[k];
+}
+
 // peak-rate probe for SURVEY 8d's second roofline ("achieved modmul/s over measured peak modmul/s"): ILP independent
 // register-resident chains of the 9x29-bit Montgomery squaring the hash and NTT kernels use, nothing else.
 template <int ILP>
@@ -434,6 +444,15 @@ int pk_probe_arith_device(pk_ctx* ctx, int op, const uint64_t* d_a, const uint64
     PK_ENTER(ctx);
     if (!n) return PK_OK;
     selftest_kernel<<<(unsigned)((n + 63) / 64), 64, 0, ctx->stream>>>(op, (const fe*)d_a, (const fe*)d_b, (fe*)d_out, n);
+    PK_LAUNCH_CHECK(ctx);
+    return PK_OK;
+}
+// the parts of the safegcd inverse (pk_selftest_inv30's parts 0..6) by a kernel: d_in, d_out hold n records of 32 words each
+int pk_probe_inv30_device(pk_ctx* ctx, int part, const int32_t* d_in, int32_t* d_out, size_t n) {
+    if (!ctx || !d_in || !d_out || part < 0 || part > 6) return PK_ERR_BAD_ARG;
+    PK_ENTER(ctx);
+    if (!n) return PK_OK;
+    selftest_inv30_kernel<<<(unsigned)((n + 63) / 64), 64, 0, ctx->stream>>>(part, d_in, d_out, n);
     PK_LAUNCH_CHECK(ctx);
     return PK_OK;
 }
